@@ -19,11 +19,17 @@ results cannot reach the logits/gradients in MFB-baseline because mfb.py:84,118
 take their softmax over a singleton axis.  roofline.achieved
 counts only FLOPs actually executed by the measured kernel.
 
-After the headline (BASELINE config 2) a default 1-GPU run frees the model and
-times, in the same process, BASELINE config 3 (MHBCoAtt, bf16 operands, B=512)
-and config 4 (HieCoAtten, fp32, B=256): `secondary.config3 / .config4`, each
-with its own ms_per_step, value, dtype and roofline object.  The headline keys
-are unaffected (`--no-secondary` skips them).
+A plain run sets up, warms up, times the --steps steps (the dominant GEMM
+launches carry hipEvent brackets: the `roofline` object), writes the last timed
+step's outputs if --dump-outputs DIR is given and prints the line.  Everything
+that takes runs of its own is behind --full: the per-kernel census, the exposed
+all-reduce times, the live weight-gradient probe, the HBM yardsticks, the
+one-rank data-parallel rehearsal, the CPU baseline and, after the headline
+(BASELINE config 2) of a 1-GPU run, BASELINE config 3 (MHBCoAtt, bf16
+operands, B=512) and config 4 (HieCoAtten, fp32, B=256):
+`secondary.config3 / .config4`, each with its own ms_per_step, value, dtype and
+roofline object.  The headline keys are unaffected (`--no-secondary` skips
+the secondary configs of a --full run).
 """
 import argparse
 import glob
@@ -322,6 +328,7 @@ class Workload:
     def __init__(self, vqa_amd, model_name, dtype, B, rank, dev, args=None):
         ops = vqa_amd.ops
         self.name, self.dtype, self.B = model_name, dtype, B
+        torch.manual_seed(0)           # module default init (the biases) from a fixed seed: the same weights in every run
         if model_name == "hieCoAtten":
             model = vqa_amd.HieCoAtten(block_num=196, word_num=14, img_size=2048, vocab_size=1000,
                                        embed_size=512, output_size=1000)
@@ -362,15 +369,21 @@ class Workload:
             self.img = ops.cast_bf16(self.img.view(-1, self.img.shape[-1])).view(self.img.shape)
         self.soft = torch.softmax(torch.randn((B, 1000), generator=torch.Generator().manual_seed(1236 + rank)), 1).to(dev)
         self.reducer = None
+        self.keep_out = False          # --dump-outputs: keep the forward output of the last step
+        self.last_out = None
 
     def step(self):
         m = self.model
         if self.forward_only:
             with torch.no_grad():
                 out = m.forward(self.img, self.q)
+                if self.keep_out:
+                    self.last_out = out
                 return (out[0] if self.name == "hieCoAtten" else out).sum()
         self.opt.zero_grad(set_to_none=True)
         out = m.forward(self.img, self.q)
+        if self.keep_out:
+            self.last_out = out
         if self.name == "hieCoAtten":
             out = out[0]
         loss = self.criterion(out, self.soft if self.name == "mhb_coAtt" else self.a)
@@ -387,6 +400,44 @@ class Workload:
         import gc
         gc.collect()
         torch.cuda.empty_cache()
+
+
+DUMP_SAMPLE = 1 << 17      # entries kept of a larger parameter or gradient by --dump-outputs (a fixed, seeded sample)
+DUMP_SAMPLE_OUT = 1 << 20  # the same for the loss and the forward output
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(wl, loss, out_dir):
+    """--dump-outputs DIR: what the timed path computed in its last step, as float32 .npy files: `loss`, the forward output
+    (`output`, or `output.<i>` for a tuple), and after the Adam step every parameter (`param.<name>`) and its gradient
+    (`grad.<name>`; none for a parameter left without one).  A parameter or gradient of more than DUMP_SAMPLE entries (an
+    output of more than DUMP_SAMPLE_OUT) is written as that many entries at sorted indices drawn by numpy's default_rng
+    seeded with the crc32 of the file name, so that two builds give the same sample."""
+    import zlib
+    import numpy as np
+    arrays = {"loss": loss}
+    outs = wl.last_out if isinstance(wl.last_out, (tuple, list)) else (wl.last_out,)
+    for i, o in enumerate(outs):
+        if o is not None:
+            arrays["output" if len(outs) == 1 else "output.%d" % i] = o
+    for name, p in wl.model.named_parameters():
+        arrays["param." + name] = p
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        keep = DUMP_SAMPLE if name.startswith(("param.", "grad.")) else DUMP_SAMPLE_OUT
+        if flat.numel() > keep:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.sort(rng.choice(flat.numel(), keep, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.float().cpu().numpy().reshape(t.shape if flat.numel() == t.numel() else (-1,))
+        total += a.nbytes
+        assert total <= DUMP_LIMIT_BYTES, "--dump-outputs: more than %d bytes" % DUMP_LIMIT_BYTES
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def dominant_mnk(model_name, B):
@@ -537,7 +588,7 @@ def dp_one_rank_child(steps, warmup, pg_timeout=None, timeout_s=600.0):
     process: round 5 first timed it in-process behind the three secondary configurations and read 46.5 ms where the stand-alone
     run of the same build gives 40.8 -- gpurun_out/r05/b_one_rank.json; the child's number is the stand-alone one)."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--one-rank-group", "--no-cpu-baseline", "--no-secondary", "--steps", str(steps),
+    cmd = [sys.executable, os.path.abspath(__file__), "--one-rank-group", "--full", "--no-cpu-baseline", "--no-secondary", "--steps", str(steps),
            "--warmup", str(warmup)]
     if pg_timeout:
         cmd += ["--pg-timeout", str(pg_timeout)]
@@ -865,6 +916,13 @@ def main():
                     help="A/B: the two products of a final MFB block (and their gradients) on two streams (functions.FinalMfbFn.TWO_STREAMS)")
     ap.add_argument("--no-dp-one-rank", action="store_true",
                     help="skip the one-rank data-parallel rehearsal (`secondary_summary.dp_one_rank`) of a default 1-GPU run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: per-kernel census, exposed all-reduce "
+                         "times, live weight-gradient probe, HBM yardsticks, the secondary configs, the one-rank data-parallel "
+                         "rehearsal and the CPU baseline (default: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, forward output, parameters after the optimizer step, "
+                         "gradients) as DIR/<name>.npy, float32; tensors above %d entries as a fixed, seeded sample" % DUMP_SAMPLE)
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -872,7 +930,7 @@ def main():
 
     multi = int(os.environ.get("WORLD_SIZE", "1")) > 1
     dp_one = None
-    if (not multi and args.gpus == 1 and args.model == "mfb" and args.dtype == "f32" and args.batch == 512 and not args.pruned
+    if (args.full and not multi and args.gpus == 1 and args.model == "mfb" and args.dtype == "f32" and args.batch == 512 and not args.pruned
             and not args.forward_only and not args.miopen_lstm and not args.no_secondary and not args.one_rank_group
             and not args.no_dp_one_rank):
         # the one-rank data-parallel rehearsal of a default run: a fresh child, finished before this process touches the GPU
@@ -933,6 +991,7 @@ def main():
     reducer = parallel.GradientAllReducer(wl.model, gemm_workgroups=args.gemm_workgroups,   # broadcasts rank 0's weights; no-op at world 1
                                           single_rank=args.one_rank_group)
     wl.reducer = reducer
+    wl.keep_out = bool(args.dump_outputs) and rank == 0
     if multi:
         faulthandler.cancel_dump_traceback_later()
         loop_bound = args.launch_timeout + 2.0 * (args.warmup + args.steps + 2 * CENSUS_STEPS)
@@ -945,6 +1004,8 @@ def main():
         torch.cuda.synchronize()
 
     elapsed, loss = timed_steps(wl, ops, args.warmup, args.steps, fence)
+    if wl.keep_out:
+        dump_outputs(wl, loss, args.dump_outputs)
     if multi:
         stage("%d warm-up + %d timed steps done (%.1f ms per step on this rank)" % (args.warmup, args.steps, 1e3 * elapsed / args.steps))
     if world > 1:
@@ -979,10 +1040,10 @@ def main():
                                  "operands": ("in-step launch; in faithful MFB dP is EXACTLY ZERO (singleton-axis "
                                               "softmax): see wgrad_live for random operands")
                                  if (args.model == "mfb" and not args.pruned) else "in-step launch, live operands"}
-    exposed = exposed_allreduce_steps(wl, CENSUS_STEPS, fence)
-    rep = census_steps(wl, ops, CENSUS_STEPS, fence)
+    exposed = exposed_allreduce_steps(wl, CENSUS_STEPS, fence) if args.full else None
+    rep = census_steps(wl, ops, CENSUS_STEPS, fence) if args.full else {}
     gemm_wg = reducer.gemm_workgroups()
-    if roofline is not None and world == 1 and args.dtype == "f32" and args.model == "mfb" and not args.forward_only:
+    if args.full and roofline is not None and world == 1 and args.dtype == "f32" and args.model == "mfb" and not args.forward_only:
         n_l, ms_l, red_l = live_wgrad_probe(ops, B, dev)
         if n_l:
             achl = flops / (ms_l / n_l * 1e-3) / 1e12
@@ -996,7 +1057,7 @@ def main():
                 roofline["wgrad_live"].update(traffic=tr, traffic_source=src)
     kernels = kernel_table(rep, CENSUS_STEPS)
     yardstick = None
-    if world == 1 and args.dtype == "f32" and args.model == "mfb" and not args.forward_only and B == 512:
+    if args.full and world == 1 and args.dtype == "f32" and args.model == "mfb" and not args.forward_only and B == 512:
         yardstick = hbm_yardsticks(ops, B, dev)
     # secondary roofline: the HBM-bound kernels of the step.  algorithmic bytes per step: fusion fwd reads P (+q) and
     # writes R for the L=196 stage and the final block; bwd reads P, dY, Y and writes dP; the glimpse passes
@@ -1062,7 +1123,7 @@ def main():
         }
     headline_default = (args.model == "mfb" and args.dtype == "f32" and B == 512 and not args.pruned
                         and not args.forward_only and not args.miopen_lstm)
-    if world == 1 and headline_default and not args.no_secondary and not args.one_rank_group:
+    if args.full and world == 1 and headline_default and not args.no_secondary and not args.one_rank_group:
         wl.free()
         del reducer
         out["secondary"] = {}
@@ -1077,10 +1138,15 @@ def main():
                 dp_one["overhead_frac"] = round(dp_one["ms_per_step"] / ms_per_step - 1.0, 4)
             out["secondary"]["dp_one_rank"] = dp_one
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and not args.one_rank_group:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.one_rank_group:
             out["cpu_baseline"] = cpu_baseline(batch=args.cpu_batch)
             out["speedup_vs_cpu"] = round(value / out["cpu_baseline"]["value"], 1)
-        print(json.dumps(compact_line(out, args)), flush=True)
+        if args.full:
+            print(json.dumps(compact_line(out, args)), flush=True)
+        else:
+            for k in ("roofline_hbm_kernels", "hbm_yardsticks", "kernels_ms_per_step", "kernels_note"):
+                out.pop(k)          # measured by --full only
+            print(json.dumps(out), flush=True)
     if multi:
         faulthandler.cancel_dump_traceback_later()
         stage("line printed" if rank == 0 else "done")

@@ -348,7 +348,59 @@ def run_att_module(case):
     return out
 
 
+def state_dict_layouts():
+    """{model: [[key, shape], ...]} of the reference classes' state_dicts, in their order (the checkpoint-interchange test
+    of tests/test_abi_cpu.py loads these layouts strictly into the HIP classes)."""
+    def layout(m):
+        return [[k, list(v.shape)] for k, v in m.state_dict().items()]
+    cfgb = types.SimpleNamespace(q_vocab_size=50, a_vocab_size=30, emb_dim=24, hidden_dim=64,
+                                 img_feature_channel=96, img_feature_dim=196, model_name="mhb")
+    kw = dict(block_num=20, word_num=7, img_size=96, vocab_size=50, embed_size=64, output_size=30)
+    return {
+        "MFB": layout(ref_mfb.MFB(make_cfg(MFB_CASES[0]))),
+        "MHBCoAtt": layout(ref_mhb.MHBCoAtt(make_cfg(MHBCOATT_CASES[3]))),
+        "MHB": layout(ref_mhb.MHB(cfgb)),
+        "HieCoAtten": layout(ref_hie.HieCoAtten(**kw)),
+        "AttentionNet": layout(ref_net.AttentionNet(att_num=6, **kw)),
+        "iBOWIMG": layout(ref_net.iBOWIMG(96, 50, 64, 30)),
+    }
+
+
+def oracle_noise32():
+    """{case: {name: |g32 - g64|}}: the fp32 noise of the ORACLE's MHBCoAtt gradients against its fp64 run on the golden cases'
+    inputs (the yardstick tests/test_gpu_models.py::test_mhbcoatt_matches_reference_golden passes to grad_parity)."""
+    sys.path[:0] = [os.path.dirname(HERE), os.path.dirname(os.path.dirname(HERE))]
+    from golden_util import mfb_inputs, recipe_sd
+    from oracle import ref_torch as O
+    res = {}
+    for case in MHBCOATT_CASES:
+        cfg, img, q, glove, _, soft = mfb_inputs(case)
+        grads = []
+        for dt in (torch.float32, torch.float64):
+            sd = {k: v.to(dt).requires_grad_(True) for k, v in recipe_sd(O.mfb_shapes(cfg, mhb=True), case["salt"]).items()}
+            out = O.mhbcoatt_forward(sd, cfg, img.to(dt), q, glove=None if glove is None else glove.to(dt))
+            O.kldiv_loss(out, soft.to(dt)).backward()
+            grads.append({k: v.grad for k, v in sd.items()})
+        res[case["name"]] = {k: float((g.double() - grads[1][k]).norm()) for k, g in grads[0].items() if g is not None}
+    return res
+
+
 def main():
+    only = sys.argv[1:]
+    if not only or "noise32" in only:
+        import json
+        path = os.path.join(HERE, "mhbcoatt_noise32.json")
+        with open(path, "w") as f:
+            json.dump(oracle_noise32(), f, indent=1)
+            f.write("\n")
+        print("%-40s %8.1f KB" % ("mhbcoatt_noise32", os.path.getsize(path) / 1024))
+    if not only or "layouts" in only:
+        import json
+        path = os.path.join(HERE, "ref_state_dict_layouts.json")
+        with open(path, "w") as f:
+            json.dump(state_dict_layouts(), f, indent=1)
+            f.write("\n")
+        print("%-40s %8.1f KB" % ("ref_state_dict_layouts", os.path.getsize(path) / 1024))
     jobs = []
     for c in MFB_CASES:
         jobs.append(("mfb_" + c["name"], lambda c=c: run_mfb_like(c, False)))
@@ -364,7 +416,6 @@ def main():
         jobs.append(("ibow_" + c["name"], lambda c=c: run_ibow(c)))
     for c in ATT_MODULE_CASES:
         jobs.append(("mod_" + c["name"], lambda c=c: run_att_module(c)))
-    only = sys.argv[1:]
     for name, fn in jobs:
         if only and not any(o in name for o in only):
             continue

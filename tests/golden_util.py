@@ -54,11 +54,19 @@ def check_tensor_digest(prefix, t, gold, tol):
         assert rel_err(a[idx], gold[prefix + "/samp"]) <= tol, prefix
 
 
+FP32_SPREAD = 2.0    # check_grads: two fp32 runs differ by up to ~2x what one of them is from the fp64 value
+
+
 def check_grads(named_grads, gold, tol, zero_ok_abs=1e-9):
     """named_grads: {name: tensor or None}.  Compares norms + sampled entries.
 
     Sampled entries are compared relative to the gradient's RMS magnitude
     (norm / sqrt(numel)) so that near-zero samples do not dominate.
+
+    Where the golden also holds the reference's fp64 norm (g64norm/), a tensor whose recorded fp32 norm is itself
+    further than tol / FP32_SPREAD from it is compared at FP32_SPREAD x that recorded distance instead of tol: the fp32
+    rounding behind the signed square root depends on the host's BLAS code path (AVX-512, AVX2, SSE), and two fp32 runs
+    can differ by the sum of their distances to the fp64 value.  The fp64 digests pin such tensors exactly (check_grads64).
     """
     gmax = max([float(v) for kk, v in gold.items() if kk.startswith("gnorm/")] + [0.0])
     zero_ok_abs = max(zero_ok_abs, 1e-6 * gmax)
@@ -75,12 +83,16 @@ def check_grads(named_grads, gold, tol, zero_ok_abs=1e-9):
             # front of a shift-invariant softmax): only require "still negligible"
             assert n <= 10 * zero_ok_abs, (k, "reference gradient is (numerically) zero", n)
             continue
-        assert abs(n - gn) <= tol * gn, (k, "norm", n, gn)
+        tol_k = tol
+        g64n = float(gold.get("g64norm/" + k, 0.0))
+        if g64n > zero_ok_abs:
+            tol_k = max(tol, FP32_SPREAD * abs(gn - g64n) / g64n)
+        assert abs(n - gn) <= tol_k * gn, (k, "norm", n, gn, tol_k)
         idx = sample_indices(k, a.size, 16)
         rms = gn / np.sqrt(a.size)
         d = np.abs(a[idx] - gold["gsamp/" + k].astype(np.float64)).max()
         scale = max(np.abs(gold["gsamp/" + k]).max(), rms)
-        assert d <= tol * scale * 4, (k, "samples", d, scale)
+        assert d <= tol_k * scale * 4, (k, "samples", d, scale)
 
 
 def check_grads64(named_grads, gold, tol=1e-8):
@@ -122,7 +134,7 @@ def _report_parity(label, worst, worst_name, detail=""):
 ILL_CONDITIONED = 0.05      # noise/|g64| above which grad_parity's bound (8x the noise) is too loose to pin a tensor on its own
 
 
-def grad_parity(gpu_grads, g32, g64, k=8.0, floor=5e-4, label="", node_checked=None):
+def grad_parity(gpu_grads, g32, g64, k=8.0, floor=5e-4, label="", node_checked=None, noise32=None):
     """Conditioning-aware gradient criterion.
 
     g64 = oracle gradients in float64 (pinned to the reference's fp64 run at 1e-8),
@@ -139,6 +151,10 @@ def grad_parity(gpu_grads, g32, g64, k=8.0, floor=5e-4, label="", node_checked=N
     5-300 % from the fp64 gradient for the tensors behind the signed square root, so this criterion alone would accept an
     all-zero gradient there.  Every tensor with noise/|g64| > ILL_CONDITIONED must be in node_checked (asserted, and listed
     in the report line); callers at the full batch sizes pass it.
+
+    noise32 ({name: |g32 - g64|}, recorded under tests/golden/ by make_golden.py): the fp32 noise term of a recorded oracle run
+    in place of the one computed on this host.  The CPU fp32 path's summation order depends on the host's BLAS code path (the noise of
+    one tensor differs by up to ~5x between hosts), so a recorded yardstick keeps the bound the same on every machine.
     """
     gmax = max(float(g.norm()) for g in g64.values() if g is not None)
     worst, worst_name, worst_rel = 0.0, "-", (0.0, 0.0)
@@ -151,7 +167,7 @@ def grad_parity(gpu_grads, g32, g64, k=8.0, floor=5e-4, label="", node_checked=N
             continue
         assert gg is not None, (name, "missing gradient")
         r64 = r64.double()
-        noise = float((g32[name].double() - r64).norm())
+        noise = float(noise32[name]) if noise32 is not None else float((g32[name].double() - r64).norm())
         err = float((gg.detach().cpu().double() - r64).norm())
         bound = max(k * noise, floor * float(r64.norm()), 1e-6 * gmax)
         assert err <= bound, (name, "err %.3e bound %.3e noise32 %.3e norm %.3e" % (err, bound, noise, float(r64.norm())))

@@ -1,5 +1,6 @@
-"""bench.py keeps its output contract: ONE JSON line with the driver's keys, the roofline object of the dominant
-kernel and the cpu_baseline object (a short run: 2 timed steps; the CPU leg is the bounded sample itself)."""
+"""bench.py keeps its output contract: ONE JSON line with the driver's keys and the roofline object of the dominant kernel;
+with --full also the cpu_baseline object, the census and the secondary configs (a short run: 2 timed steps; the CPU leg is
+the bounded sample itself)."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_contract_line():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
                         "--cpu-batch", "64",           # the default (the metric's B=512) takes ~75 s of CPU time
                         "--secondary-steps", "2", "--secondary-warmup", "1"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
@@ -87,6 +88,39 @@ def test_bench_prints_one_contract_line():
     assert len(dps["allreduce_exposed_ms"]) == len(dp["allreduce_bucket_bytes"]) >= 4 and sum(dp["allreduce_bucket_bytes"]) == 240124080
 
 
+def test_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """A plain run (no --full) times the headline only: the headline keys and the in-step roofline, nothing that takes runs of
+    its own.  --dump-outputs writes the last timed step's loss, forward output, parameters and gradients as float32 .npy
+    files (at most 64 MB), the same ones for the same arguments."""
+    import numpy as np
+    outs = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["metric"] == "QA-pairs/sec fwd+bwd, MFB-baseline batch 512" and d["unit"] == "QA-pairs/s" and d["dtype"] == "f32"
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True
+        assert abs(d["value"] - 512 * 1000.0 / d["ms_per_step"]) / d["value"] < 1e-3
+        assert 0.3 < d["roofline"]["frac"] < 1.0
+        for k in ("cpu_baseline", "secondary_summary", "census_file", "kernels_ms_per_step", "hbm_yardsticks", "roofline_hbm_kernels"):
+            assert k not in d, k
+        assert "wgrad_live" not in d["roofline"]
+        files = sorted(os.listdir(tmp_path / run))
+        assert {"loss.npy", "output.npy", "param.img_conv1d.weight.npy", "grad.linear_pred.weight.npy"} <= set(files), files
+        arrs = {f: np.load(tmp_path / run / f) for f in files}
+        assert all(a.dtype == np.float32 for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs["output.npy"].shape == (512, 1000) and abs(float(arrs["loss.npy"]) - d["loss"]) < 1e-4
+        outs.append(arrs)
+    assert sorted(outs[0]) == sorted(outs[1]) and all(a.shape == outs[1][f].shape for f, a in outs[0].items())
+    for f in ("loss.npy", "output.npy"):          # same inputs, weights and dropout seeds in both runs
+        a, b = outs[0][f], outs[1][f]
+        assert np.abs(a - b).max() <= 1e-4 * np.abs(b).max(), f
+
+
 def test_stalled_rank_trips_the_launch_deadline_on_the_gpu_box():
     """tests/test_launch_deadline.py's first case again where the driver's GPU suite runs (the stall precedes any GPU call)."""
     import test_launch_deadline as t
@@ -124,7 +158,7 @@ def test_bench_bare_gpus_2_starts_its_own_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
                                                             "VQF_DIST_INIT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--backend", "gloo", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--backend", "gloo", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -140,7 +174,7 @@ def test_bench_two_ranks_on_one_gpu_gloo_rehearsal(tmp_path):
     240 124 080 bytes), ranks seen by torch.distributed, the per-bucket exposed all-reduce times."""
     env = dict(os.environ, WORLD_SIZE="2", LOCAL_RANK="0", VQF_DIST_INIT="file://" + str(tmp_path / "store"))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--backend", "gloo", "--no-cpu-baseline"]
+           "--backend", "gloo", "--no-cpu-baseline", "--full"]
     procs = [subprocess.Popen(cmd, cwd=ROOT, env=dict(env, RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                               text=True) for r in range(2)]
     outs = [p.communicate(timeout=900) for p in procs]

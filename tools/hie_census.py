@@ -2,7 +2,7 @@
     VQF_LIB=variants/libvqf_X.so python tools/hie_census.py"""
 import json, os, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model", "hieCoAtten", "--no-cpu-baseline", "--no-secondary",
+subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model", "hieCoAtten", "--full", "--no-cpu-baseline", "--no-secondary",
                 "--steps", "8", "--warmup", "3"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
 d = json.load(open(os.path.join(root, "gpurun_out", "bench_census.json")))
 ks = d["kernels_ms_per_step"]

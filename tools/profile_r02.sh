@@ -22,5 +22,5 @@ run f32_fwd --dtype f32 --shape fwd
 run f32_wgrad --dtype f32 --shape wgrad
 run bf16_fwd --dtype bf16 --shape fwd --out-bf16
 run bf16_wgrad --dtype bf16 --shape wgrad
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o r02 -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/trace.log 2>&1 || echo "trace failed"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o r02 -- python3 $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline > $O/trace.log 2>&1 || echo "trace failed"
 ls -R $O | head -60

@@ -34,7 +34,7 @@ for part in "$@"; do
     mid)   pmc hie_fwd $R/tools/gemm_one.py --dtype f32 --shape hie_fwd
            pmc hie_wgrad $R/tools/gemm_one.py --dtype f32 --shape hie_wgrad
            pmc coatt_fwd $R/tools/gemm_one.py --dtype f32 --shape coatt_fwd ;;
-    trace) timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o r04 -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --secondary-steps 5 --secondary-warmup 2 > $O/trace.log 2>&1 || echo "trace failed" ;;
+    trace) timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o r04 -- python3 $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --secondary-steps 5 --secondary-warmup 2 > $O/trace.log 2>&1 || echo "trace failed" ;;
   esac
 done
 ls -R $O | head -80

@@ -43,7 +43,7 @@ for part in "$@"; do
     n80)   pmc m512 $R/tools/gemm_one.py --dtype f32 --shape m512 --reps 10 ;;
     c4)    pmc hie_fwd $R/tools/gemm_one.py --dtype f32 --shape hie_fwd
            pmc hie_dgrad $R/tools/gemm_one.py --dtype f32 --shape hie_dgrad ;;
-    trace) timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o r05 -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --secondary-steps 5 --secondary-warmup 2 > $O/trace.log 2>&1 || echo "trace failed" ;;
+    trace) timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o r05 -- python3 $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --secondary-steps 5 --secondary-warmup 2 > $O/trace.log 2>&1 || echo "trace failed" ;;
   esac
 done
 ls $O | head -60

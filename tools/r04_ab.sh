@@ -4,11 +4,11 @@
 # "-DVQF_STREAM_NT=0" fusion.hip,attention.hip).
 mkdir -p gpurun_out/r04
 {
-  echo "# headline step (python bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-secondary), same box, alternating:"
+  echo "# headline step (python bench.py --steps 12 --warmup 4 --full --no-cpu-baseline --no-secondary), same box, alternating:"
   echo "# default = VQF_STREAM_NT=1 (non-temporal loads / stores on once-touched streams), nt0 = the same build with VQF_STREAM_NT=0"
   for v in default nt0 default nt0; do
     if [ $v = default ]; then unset VQF_LIB; else export VQF_LIB=variants/libvqf_$v.so; fi
-    python bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-secondary > /dev/null 2>&1
+    python bench.py --steps 12 --warmup 4 --full --no-cpu-baseline --no-secondary > /dev/null 2>&1
     echo "== $v"
     python tools/census_print.py | grep -E "ms_per_step|mfb_fuse|glimpse|att_logits|wgrad|fwd\)"
   done
