@@ -242,7 +242,7 @@ int vqf_multi_copy_f32(const float* const* src, float* const* dst, const long lo
 
 /* logits[m,g] = hid[m,:] . w2[g,:] + b2[g],  g < G (G = 2 glimpses: mfb.py / mhb_coAtt.py;
  * G = 1: hieCoAtten.py:40,47 fc_Whv/fc_Whq, modules.py:60 Attention_1.fc); hid is (M,Hh),
- * w2 (G,Hh), logits (M,G). */
+ * w2 (G,Hh), logits (M,G); G = 3: the ladder's three levels (HieCoAttenLadder, a block-diagonal w2). */
 int vqf_att_logits_fwd(const float* hid, const float* w2, const float* b2,
                        int M, int Hh, int G, float* logits, void* stream);
 
@@ -256,7 +256,7 @@ int vqf_att_logits_fwd_lin(const float* hid, const float* w2, const float* b2, c
  *   dhid_pre[m,j] = (sum_g dl[m,g] w2[g,j]) * (hid[m,j] > 0  or 1)
  *   dw2[g,j] = sum_m dl[m,g] hid[m,j];  db2[g] = sum_m dl[m,g]
  *   dbias1[j] = sum_m dhid_pre[m,j]          (bias grad of the layer before)
- * ws: at least vqf_att_logits_bwd_ws_bytes(M,Hh). */
+ * G in {1,2}; G = 3 (the ladder's levels) without the ReLU and the row scale.  ws: at least vqf_att_logits_bwd_ws_bytes(M,Hh). */
 size_t vqf_att_logits_bwd_ws_bytes(int M, int Hh);
 int vqf_att_logits_bwd(const float* dlogits, const float* hid, const float* w2,
                        int M, int Hh, int G, int relu_mask, float* dhid_pre, float* dw2,
@@ -275,7 +275,7 @@ int vqf_att_logits_bwd_rowscale_obf16(const float* dlogits, const float* hid, co
 
 /* wts[n,g,:] = softmax_s(logits[n,:,g])   (unit_softmax != 0: wts == 1, the
  * mfb.py:84,118 singleton-axis softmax);  pooled[n, g*C + c] = sum_s wts[n,g,s] feat[n,s,c].
- * feat (N,S,C), logits (N*S,G), wts (N,G,S), pooled (N,G*C).  S <= 1024, G in {1,2}. */
+ * feat (N,S,C), logits (N*S,G), wts (N,G,S), pooled (N,G*C).  S <= 1024, G in {1,2,3} (3: the ladder's three levels). */
 int vqf_glimpse_pool_fwd(const float* feat, const float* logits, int N, int S, int C, int G,
                          int unit_softmax, float* wts, float* pooled, void* stream);
 
@@ -466,6 +466,26 @@ int vqf_hie_affinity_supported(int N, int L, int E, int T, int pairs);
 int vqf_hie_affinity(const float* x1, int ldx1, const float* y1, int ldy1, const float* x2, int ldx2, const float* y2, int ldy2,
                      int epi, const float* yprev, const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int E, int T,
                      float* out, void* stream);
+
+/* The word / phrase / sentence ladder (HieCoAttenLadder; csrc/hie_ladder.hip; additions within ABI 7).
+ * Phrase level: Z (N*T, 6E) = Qw Wcat^T, the six conv taps [uni0 | bi0 bi1 | tri0 tri1 tri2] (row pitch ldz), bias (3E) =
+ * [b1 | b2 | b3].  u_k[t] = b_k + sum_{j<k, t+j<T} Z[n*T+t+j, tap(k,j)];  Qp = tanh(max_k u_k) (row pitch ldq), idx (N*T, E)
+ * uint8 = the winning k - 1 (first maximum on a tie).  Backward: dZ (N*T, 6E, pitch ldz) with row r of tap (k, j) = du[r - j]
+ * where idx[r - j] == k - 1 and t - j >= 0, else 0; du = dQp (1 - Qp^2).  No atomics.  The column sums of dZ's taps
+ * (1,0), (2,0), (3,0) are the bias gradients.  Supported: 1 <= T <= 32, E % 4 == 0. */
+int vqf_phrase_ngram_supported(int T, int E);
+int vqf_phrase_ngram_fwd(const float* Z, int ldz, const float* bias, int N, int T, int E, float* Qp, int ldq, uint8_t* idx,
+                         void* stream);
+int vqf_phrase_ngram_bwd(const float* dQp, int ldd, const float* Qp, int ldq, const uint8_t* idx, int N, int T, int E, float* dZ,
+                         int ldz, void* stream);
+/* vqf_hie_affinity for G <= 3 levels in one pass over the y rows: level g reads x rows at column offset g * ldx_level and y
+ * rows at g * ldy_level (0: all levels share one y, read once).  out[g] (G, N, T, L) contiguous = epi(sums of level g); epi 0:
+ * the sums, 1: tanh, 2: sums * (1 - yprev^2) with yprev (G, N, T, L).  No dropout.  Same k order as vqf_hie_affinity (G = 1:
+ * the same bits).  Supported: T <= 16, E % 32 == 0, G * pairs * 16 * (E + 4) floats of LDS <= 160 KB. */
+int vqf_hie_affinity_levels_supported(int N, int L, int E, int T, int G, int pairs);
+int vqf_hie_affinity_levels(const float* x1, int ldx1, int ldx_level1, const float* y1, int ldy1, int ldy_level1,
+                            const float* x2, int ldx2, int ldx_level2, const float* y2, int ldy2, int ldy_level2,
+                            int G, int epi, const float* yprev, int N, int L, int E, int T, float* out, void* stream);
 
 /* softmax over the last axis of (R,W) and its backward   modules.py:91-92 */
 int vqf_softmax_rows_fwd(const float* x, int R, int W, float* y, void* stream);

@@ -1,0 +1,108 @@
+"""Train step of HieCoAttenLadder (host/hie_ladder.py) at config 4's shapes: forward, CE loss, backward, the project's Adam.
+
+    python tools/hie_ladder_bench.py [--batch 256] [--steps 20] [--warmup 5] [--json OUT]
+
+Prints ms / step and QA pairs / s (device events around the timed steps), the step's FLOP count from the shapes with its
+MFMA floor at 157.3 TF/s (fp32 MFMA peak of the MI355X) and the fraction reached, the library profiler's per-kernel table
+of one extra step, and config 4's single-level HieCoAtten at the same shapes in the same process for context."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+import vqa_amd  # noqa: E402
+
+PEAK_TFS = 157.3
+
+
+def ladder_flops(N, L, D, E, T, H, O):
+    """multiply-add pairs x 2 of the step's products (forward + input gradients + weight gradients); the image features are
+    data (no input gradient for img_emb)"""
+    M, MT = N * L, N * T
+    f = {
+        "img_emb (fwd + wgrad)": 2 * 2 * M * D * E,
+        "Vh = V [Wv0;Wv1;Wv2]^T (fwd + dgrad + wgrad)": 3 * 2 * M * E * 3 * E,
+        "[Cq|Qh] per level (x3)": 3 * 3 * 2 * MT * E * 2 * E,
+        "phrase taps Z (x3)": 3 * 2 * MT * E * 6 * E,
+        "sentence LSTM (x3)": 3 * 2 * 2 * MT * E * 4 * E,
+        "affinity + rank-T passes": 3 * (2 + 2 * 2 + 2 + 2 + 2 + 2 + 2) * MT * L * E,
+        "answer MLP (x3)": 3 * 2 * N * (E * E + 2 * E * E + 2 * E * H + H * O),
+    }
+    return f, sum(f.values())
+
+
+def timed(model, img, ids, target, steps, warmup):
+    crit = vqa_amd.CrossEntropyLoss()
+    opt = vqa_amd.Adam(model.parameters(), lr=1e-4)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        out = model(img, ids)
+        loss = crit(out[0], target)
+        loss.backward()
+        opt.step()
+
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        step()
+    b.record()
+    torch.cuda.synchronize()
+    ms = a.elapsed_time(b) / steps
+    ops = vqa_amd.ops
+    ops.prof_reset()
+    ops.prof_enable(True)
+    step()
+    torch.cuda.synchronize()
+    ops.prof_enable(False)
+    return ms, ops.prof_report()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    N, L, D, E, T, H, O, V = a.batch, 196, 2048, 512, 14, 1024, 1000, 15881
+    dev = "cuda:0"
+    torch.manual_seed(0)
+    img = torch.rand(N, L, D, device=dev)
+    ids = torch.randint(0, V, (N, T), device=dev)
+    target = torch.randint(0, O, (N,), device=dev)
+    ladder = vqa_amd.HieCoAttenLadder(block_num=L, word_num=T, img_size=D, vocab_size=V, embed_size=E, hidden_size=H,
+                                      output_size=O).to(dev).train()
+    ms, kern = timed(ladder, img, ids, target, a.steps, a.warmup)
+    parts, flops = ladder_flops(N, L, D, E, T, H, O)
+    floor_ms = flops / (PEAK_TFS * 1e12) * 1e3
+    print("HieCoAttenLadder train step  B=%d L=%d img=%d E=%d T=%d hidden=%d out=%d" % (N, L, D, E, T, H, O))
+    print("  %.3f ms/step   %.0f QA pairs/s" % (ms, N / ms * 1e3))
+    print("  %.3f TFLOP/step:" % (flops / 1e12))
+    for k, v in parts.items():
+        print("    %-48s %7.1f GFLOP" % (k, v / 1e9))
+    print("  MFMA floor at %.1f TF/s: %.3f ms   fraction reached %.3f" % (PEAK_TFS, floor_ms, floor_ms / ms))
+    print("  per kernel (one profiled step; event brackets add a few us per launch):")
+    for k, (n, t) in sorted(kern.items(), key=lambda kv: -kv[1][1]):
+        print("    %-28s %4d launches  %8.3f ms" % (k, n, t))
+    del ladder
+    torch.cuda.empty_cache()
+    hie = vqa_amd.HieCoAtten(block_num=L, word_num=T, img_size=D, vocab_size=V, embed_size=E, output_size=O).to(dev).train()
+    ms4, _ = timed(hie, img, ids, target, a.steps, a.warmup)
+    print("config 4 HieCoAtten (word level only) at the same shapes: %.3f ms/step   %.0f QA pairs/s" % (ms4, N / ms4 * 1e3))
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        json.dump({"ms_per_step": ms, "qa_per_s": N / ms * 1e3, "tflop_per_step": flops / 1e12, "floor_ms": floor_ms,
+                   "fraction_of_floor": floor_ms / ms, "kernels": kern, "hiecoatten_ms_per_step": ms4}, open(a.json, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()

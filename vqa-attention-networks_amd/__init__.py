@@ -19,7 +19,7 @@ def __getattr__(name):
     import importlib
     table = {
         "MFB": ".host.mfb", "MHBCoAtt": ".host.mhb_coAtt", "MHB": ".host.mhb_coAtt",
-        "HieCoAtten": ".host.hieCoAtten",
+        "HieCoAtten": ".host.hieCoAtten", "HieCoAttenLadder": ".host.hie_ladder",
         "Attention_layer": ".host.modules", "Attention_1": ".host.modules",
         "Attention_2": ".host.modules", "Nonlinear_layer": ".host.modules",
         "AttentionNet": ".host.networks", "iBOWIMG": ".host.networks",

@@ -381,11 +381,14 @@ extern "C" {
 int vqf_att_logits_fwd(const float* hid, const float* w2, const float* b2, int M, int Hh, int G,
                        float* logits, void* stream) {
   if (!hid || !w2 || !b2 || !logits || M <= 0 || Hh <= 0) return VQF_E_BADARG;
-  if (G != 1 && G != 2) return VQF_E_UNSUPPORTED;
+  if (G < 1 || G > 3) return VQF_E_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const float* nob1 = nullptr;
   float* nolin = nullptr;
-  if (G == 2)
+  if (G == 3)          // the ladder's three levels (HieCoAttenLadder): a block-diagonal (3, 3E) weight over [Hv_0 | Hv_1 | Hv_2]
+    VQF_LAUNCH(KID_ATT_LOGITS_FWD, (att_logits_fwd_kernel<3, false>), dim3((M + 3) / 4), dim3(256), 0, s, hid,
+               w2, b2, nob1, M, Hh, logits, nolin);
+  else if (G == 2)
     VQF_LAUNCH(KID_ATT_LOGITS_FWD, (att_logits_fwd_kernel<2, false>), dim3((M + 3) / 4), dim3(256), 0, s, hid,
                w2, b2, nob1, M, Hh, logits, nolin);
   else
@@ -411,7 +414,7 @@ int vqf_att_logits_fwd_lin(const float* hid, const float* w2, const float* b2, c
 size_t vqf_att_logits_bwd_ws_bytes(int M, int Hh) {
   if (M <= 0 || Hh <= 0) return 0;
   const int lb = att_bwd_rows_per_block(M);
-  return (size_t)((M + lb - 1) / lb + 1 + VQF_REDUCE_SPLITS) * (size_t)(3 * Hh + 4) * sizeof(float);
+  return (size_t)((M + lb - 1) / lb + 1 + VQF_REDUCE_SPLITS) * (size_t)(4 * Hh + 4) * sizeof(float);     // (G + 1) Hh + 4, G <= 3
 }
 
 int vqf_att_logits_bwd(const float* dlogits, const float* hid, const float* w2, int M, int Hh, int G,
@@ -446,7 +449,7 @@ static int att_logits_bwd_impl(const float* dlogits, const float* hid, const flo
                                float* db2, float* dbias1, void* ws, size_t ws_bytes, void* stream) {
   if (!dlogits || !hid || !w2 || !dhid_pre || !dw2 || !db2 || M <= 0 || Hh <= 0 || rows_per_scale <= 0)
     return VQF_E_BADARG;
-  if (G != 1 && G != 2) return VQF_E_UNSUPPORTED;
+  if (G < 1 || G > 3 || (G == 3 && (relu_mask || rowscale))) return VQF_E_UNSUPPORTED;
   if (!ws || ws_bytes < vqf_att_logits_bwd_ws_bytes(M, Hh)) return VQF_E_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   const int lb = att_bwd_rows_per_block(M);
@@ -459,6 +462,7 @@ static int att_logits_bwd_impl(const float* dlogits, const float* hid, const flo
              dlogits, hid, w2, M, Hh, dhid_pre, part, rowscale, rows_per_scale, lb)
   if (out_bf16)    VQF_LAUNCH(KID_ATT_LOGITS_BWD, (att_logits_bwd_kernel<2, true, true>), dim3(nb), dim3(256), 0, s, dlogits, hid, w2, M,
                               Hh, dhid_pre, part, rowscale, rows_per_scale, lb);
+  else if (G == 3) VQF_LB(3, false);
   else if (G == 2) { if (relu_mask) VQF_LB(2, true); else VQF_LB(2, false); }
   else             { if (relu_mask) VQF_LB(1, true); else VQF_LB(1, false); }
 #undef VQF_LB
@@ -539,7 +543,7 @@ template <typename FT>
 int glimpse_fwd_launch(const FT* feat, const float* logits, int N, int S, int C, int G, int unit_softmax,
                        float* wts, float* pooled, void* stream) {
   if (!feat || !logits || !pooled || N <= 0 || S <= 0 || C <= 0) return VQF_E_BADARG;
-  if (S > MAXS || (G != 1 && G != 2) || N > 65535) return VQF_E_UNSUPPORTED;
+  if (S > MAXS || G < 1 || G > 3 || N > 65535) return VQF_E_UNSUPPORTED;
   dim3 grid((C + 1023) / 1024, N);
   hipStream_t s = (hipStream_t)stream;
   {
@@ -550,7 +554,10 @@ int glimpse_fwd_launch(const FT* feat, const float* logits, int N, int S, int C,
       const int RS = 1024 / CT;
       const size_t lds = sizeof(float) * ((size_t)G * S + (size_t)RS * G * C);
       if (RS >= G && lds <= 64 * 1024) {
-        if (G == 2)
+        if (G == 3)
+          VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<3, FT>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
+                     unit_softmax, wts, pooled);
+        else if (G == 2)
           VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<2, FT>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
                      unit_softmax, wts, pooled);
         else
@@ -560,7 +567,10 @@ int glimpse_fwd_launch(const FT* feat, const float* logits, int N, int S, int C,
       }
     }
   }
-  if (G == 2)
+  if (G == 3)
+    VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<3, FT>), grid, dim3(256), 0, s, feat, logits, N, S,
+               C, unit_softmax, wts, pooled);
+  else if (G == 2)
     VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<2, FT>), grid, dim3(256), 0, s, feat, logits, N, S,
                C, unit_softmax, wts, pooled);
   else
@@ -573,7 +583,7 @@ template <typename FT>
 int glimpse_bwd_launch(const float* dpooled, const float* dwts_extra, const FT* feat, const float* wts, int N,
                        int S, int C, int G, int unit_softmax, float* dlogits, float* dfeat, void* stream) {
   if (!dpooled || !feat || !wts || !dlogits || N <= 0 || S <= 0 || C <= 0) return VQF_E_BADARG;
-  if (S > MAXS || (G != 1 && G != 2)) return VQF_E_UNSUPPORTED;
+  if (S > MAXS || G < 1 || G > 3) return VQF_E_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   // one workgroup per sample.  A wave keeps ceil(C / 256) 16-byte loads per lane in flight (a row of the grid); about 64 such
   // loads per lane and CU stream best: 8 waves per CU at C = 2048 (the headline: 256 threads per sample, two samples per CU; few
@@ -589,7 +599,10 @@ int glimpse_bwd_launch(const float* dpooled, const float* dwts_extra, const FT* 
     if (want > waves) waves = want > 16 ? 16 : want;
   }
   const dim3 block(64 * waves);
-  if (G == 2)
+  if (G == 3)
+    VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<3, FT>), dim3(N), block, 0, s, dpooled,
+               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat);
+  else if (G == 2)
     VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<2, FT>), dim3(N), block, 0, s, dpooled,
                dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat);
   else

@@ -55,6 +55,9 @@ enum VqfKernelId {
   KID_HIE_LEFT,
   KID_HIE_SLABSUM,
   KID_HIE_AFF,
+  KID_PHRASE_FWD,
+  KID_PHRASE_BWD,
+  KID_HIE_AFF_LEVELS,
   KID_COUNT
 };
 
@@ -118,16 +121,19 @@ static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0;
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is per device: a single process may drive several GPUs (the
 // reference wraps the model in nn.DataParallel, solver.py:34-36), so every kernel instantiation that asks for
-// more dynamic LDS than the default keeps one flag PER DEVICE.  Idempotent; a race only repeats the same call.
-struct VqfDynLdsFlags { bool done[64]; };
+// more dynamic LDS than the default keeps the largest size set so far PER DEVICE.  A launch that needs more than
+// that sets the attribute again (one instantiation may be launched at several LDS sizes in one process: the
+// affinity pass with one and with two operand pairs); one that needs no more makes no call.  A race only repeats
+// a call with a size that is at least as large as needed.
+struct VqfDynLdsFlags { int bytes[64]; };
 static inline int vqf_set_dyn_lds(const void* fn, int bytes, VqfDynLdsFlags& f) {
   int dev = 0;
   (void)hipGetDevice(&dev);
   const bool tracked = dev >= 0 && dev < 64;
-  if (tracked && f.done[dev]) return VQF_OK;
+  if (tracked && f.bytes[dev] >= bytes) return VQF_OK;
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (e != hipSuccess) return (int)e;
-  if (tracked) f.done[dev] = true;
+  if (tracked && f.bytes[dev] < bytes) f.bytes[dev] = bytes;
   return VQF_OK;
 }
 

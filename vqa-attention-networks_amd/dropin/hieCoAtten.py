@@ -2,3 +2,4 @@
 from _pkg import pkg as _p
 
 HieCoAtten = _p.HieCoAtten
+HieCoAttenLadder = _p.HieCoAttenLadder

@@ -1,0 +1,313 @@
+"""HieCoAttenLadder: the word / phrase / sentence hierarchical co-attention model (Lu et al. 2016, "Hierarchical
+Question-Image Co-Attention for Visual Question Answering") on the HIP path.
+
+The reference has no code for it (its HieCoAtten, host/hieCoAtten.py, is the word level alone); the
+equations below are the specification, restated line by line in tests/hie_ladder_ref.py:
+
+    V   = drop(tanh(img_emb(img)))                       (N, L, E)
+    Qw  = drop(tanh(word_emb(ids)))                      (N, T, E)
+    u_k[t] = b_k + sum_{j<k, t+j<T} W_k[:, :, j] Qw[t+j]  k = 1, 2, 3   (right zero padding)
+    Qp  = max_k tanh(u_k)
+    Qs  = sent_lstm(Qp)                                  zero initial state, all T outputs
+    per level i, Q in (Qw, Qp, Qs):
+        C = tanh((Q Wb^T) V^T);  Vh = V Wv^T;  Qh = Q Wq^T
+        Hv = tanh(Vh + C^T Qh);  Hq = tanh(Qh + C Vh)
+        av_i = softmax_L(Hv whv^T);  aq_i = softmax_T(Hq whq^T)
+        v_i = sum_l av_i[l] V[l];  q_i = sum_t aq_i[t] Q[t]
+    h_w = tanh(ans_w(drop(q_0 + v_0)));  h_p = tanh(ans_p(drop([q_1 + v_1, h_w])))
+    h_s = tanh(ans_s(drop([q_2 + v_2, h_p])));  logits = ans_h(drop(h_s))
+
+`drop` is dropout with rate drop_p in train mode only.  Padded words are NOT masked (as in HieCoAtten): a padding id is an
+ordinary word of the vocabulary at every level.
+
+Stages (every product and every pass over an (N*L, .) or (N*T, .) tensor runs in libvqa_fusion.so):
+  * img_emb / word embedding: LinearFn + TanhDropFn, EmbedTanhFn + DropoutFn;
+  * phrase level (PhraseFn): the six conv taps as one GEMM, then vqf_phrase_ngram_fwd / _bwd (csrc/hie_ladder.hip);
+  * sentence level: LstmBatchFn, its (N, T) <-> (T, N) re-layouts in DropoutBTFn passes at rate 0;
+  * the three co-attention levels (LadderCoattFn): one Vh product for all levels, one multi-level affinity pass over V
+    (vqf_hie_affinity_levels), the streaming Hv / Hq passes of csrc/hie.hip per level on column blocks, one G = 3 image-side
+    pooling over V;
+  * the answer MLP: LinearFn, TanhDropFn, DropoutFn; torch does its O(N E) adds and concatenations.
+"""
+import torch
+import torch.nn as nn
+
+from . import ops
+from .functions import _c, EmbedTanhFn, LinearFn, DropoutFn, TanhDropFn, DropoutBTFn, LstmBatchFn
+from .lib import VqfError
+from .mfb import _DropSeeds
+
+_NODROP = (None, 0, 0.0)
+
+
+class PhraseFn(torch.autograd.Function):
+    """Qp = max_k tanh(conv_k(Qw) + b_k) over the n-gram sizes k = 1, 2, 3 (right zero padding).  qw (N*T, E) contiguous;
+    w_k (E, E, k), b_k (E) the nn.Conv1d parameters.  Forward: Z = qw Wcat^T with the six taps stacked (one GEMM), then one
+    streaming pass (vqf_phrase_ngram_fwd) that also records the winning k.  Backward: dZ gathered from the winners
+    (vqf_phrase_ngram_bwd), dqw and dWcat as GEMMs, the bias gradients as column sums of dZ."""
+
+    @staticmethod
+    def forward(ctx, qw, w1, b1, w2, b2, w3, b3, N, T):
+        E = qw.shape[1]
+        wcat = torch.cat([w1[:, :, 0], w2[:, :, 0], w2[:, :, 1], w3[:, :, 0], w3[:, :, 1], w3[:, :, 2]], 0).contiguous()
+        bcat = torch.cat([b1, b2, b3], 0).contiguous()
+        Z = ops.gemm(qw, wcat)                                     # (N*T, 6E)
+        qp, idx = ops.phrase_ngram_fwd(Z, bcat, N, T)
+        ctx.save_for_backward(qw, wcat, qp, idx)
+        ctx.dims = (N, T, E)
+        return qp
+
+    @staticmethod
+    def backward(ctx, dqp):
+        qw, wcat, qp, idx = ctx.saved_tensors
+        N, T, E = ctx.dims
+        dZ = ops.phrase_ngram_bwd(_c(dqp), qp, idx, N, T)
+        dqw = ops.gemm(dZ, wcat, tb=True)                         # (N*T, E)
+        dW = ops.gemm(dZ, qw, ta=True, tb=True)                   # (6E, E)
+        db = ops.colsum(dZ)
+        dw1 = dW[:E].unsqueeze(2).contiguous()
+        dw2 = torch.stack([dW[E:2 * E], dW[2 * E:3 * E]], 2)
+        dw3 = torch.stack([dW[3 * E:4 * E], dW[4 * E:5 * E], dW[5 * E:6 * E]], 2)
+        return dqw, dw1, db[:E], dw2, db[E:2 * E], dw3, db[3 * E:4 * E], None, None
+
+
+class LadderCoattFn(torch.autograd.Function):
+    """The three parallel co-attention levels over ONE image tensor.  V (N*L, E), q0 / q1 / q2 (N*T, E) contiguous;
+    weights: for each level (Wb, Wv, Wq (E, E), whv, whq (1, E)).  Returns (vcat (N, 3E) = [v_0 | v_1 | v_2], q_0, q_1, q_2
+    (N, E), av (N, 3, L), aq_0, aq_1, aq_2 (N, 1, T)).
+
+    Forward: Vh = V [Wv_0; Wv_1; Wv_2]^T (one product, (N*L, 3E)); [Cq_i | Qh_i] = Q_i [Wb_i; Wq_i]^T into one (N*T, 6E)
+    buffer; C_i = tanh(Cq_i V^T) for the three levels in one pass over V (vqf_hie_affinity_levels); per level Hv_i and the
+    T-row sums ti_i = C_i Vh_i in one streaming pass over Vh_i (vqf_hie_hv_fwd), Hq_i = tanh(Qh_i + ti_i); the image-side
+    logits of all levels with a block-diagonal (3, 3E) weight and ONE G = 3 pooling pass over V.  Where the streaming
+    passes do not take the shape (T > 16) the T-row products run on the batched GEMM and the element-wise kernels.
+    Backward: the same stages in reverse; dC_i = (dti_i Vh_i^T + Qh_i dtq_i^T)(1 - C_i^2) in one affinity pass (all levels
+    in one launch where the LDS holds them, one launch per level otherwise)."""
+
+    STREAM = True      # the T-row stages as streaming passes where supported; False: batched GEMMs + element-wise (A/B)
+
+    @staticmethod
+    def forward(ctx, V, q0, q1, q2, N, L, T, *w):
+        E = V.shape[1]
+        M, MT = N * L, N * T
+        dev = V.device
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        Q = (q0, q1, q2)
+        Wb, Wv, Wq, whv, whq = ([_c(w[5 * g + i]) for g in range(3)] for i in range(5))
+        wv_cat = torch.cat(Wv, 0).contiguous()                                      # (3E, E)
+        wq2 = [torch.cat([Wb[g], Wq[g]], 0).contiguous() for g in range(3)]         # (2E, E) each
+        wblk = torch.zeros((3, 3 * E), dtype=torch.float32, device=dev)             # block-diagonal head weight
+        for g in range(3):
+            wblk[g, g * E:(g + 1) * E] = whv[g].view(E)
+        zb3, zb1 = torch.zeros(3, dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev)
+        Vh = ops.gemm_rows(V, wv_cat, L)                                            # (M, 3E) = [Vh_0 | Vh_1 | Vh_2]
+        CQ = new(MT, 6 * E)                                                         # [Cq_0 | Qh_0 | Cq_1 | Qh_1 | Cq_2 | Qh_2]
+        for g in range(3):
+            ops.gemm(Q[g], wq2[g], out=CQ[:, 2 * g * E:(2 * g + 2) * E])
+        stream = LadderCoattFn.STREAM and ops.hie_stream_supported(N, L, E, T)
+        if stream and ops.hie_affinity_levels_supported(N, L, E, T, 3, 1):
+            C = ops.hie_affinity_levels(CQ, 2 * E, V, 0, 3, N, L, T, E, epi=1)      # (3, N, T, L), V read once
+        else:
+            C = new(3, N, T, L)
+            for g in range(3):
+                ops.bgemm(CQ[:, 2 * g * E:(2 * g + 1) * E].view(N, T, E), V.view(N, L, E), out=C[g])
+            ops.tanh_dropout_fwd(C.view(3 * MT, L), None, *_NODROP, out=C.view(3 * MT, L))
+        Hv = new(M, 3 * E)
+        Hq = new(3, MT, E)                                                          # ti_i first, then Hq_i in place
+        S = ops.hie_chunks(N, L) if stream else 1
+        part = new(S, MT, E) if stream and S > 1 else None
+        for g in range(3):
+            Vh_g, Qh_g, Hv_g, ti_g = (Vh[:, g * E:(g + 1) * E], CQ[:, (2 * g + 1) * E:(2 * g + 2) * E], Hv[:, g * E:(g + 1) * E],
+                                      Hq[g])
+            if stream:
+                if part is None:
+                    ops.hie_hv_fwd(Vh_g, C[g], Qh_g, _NODROP, N, L, T, Hv_g, ti_g)
+                else:
+                    ops.hie_hv_fwd(Vh_g, C[g], Qh_g, _NODROP, N, L, T, Hv_g, part)
+                    ops.hie_slab_sum(part, ti_g)
+            else:
+                tq = ops.bgemm(C[g], Qh_g.view(N, T, E), ta=True, tb=True).view(M, E)      # C^T Qh
+                ops.tanh_dropout_fwd2d(Vh_g, tq, *_NODROP, out=Hv_g)
+                ops.bgemm(C[g], Vh_g.view(N, L, E), ta=False, tb=True, out=ti_g.view(N, T, E))   # C Vh
+            ops.tanh_dropout_fwd2d(Qh_g, ti_g, *_NODROP, out=ti_g)
+        av, vcat = ops.glimpse_pool_fwd(V.view(N, L, E), ops.att_logits_fwd(Hv, wblk, zb3), False)   # (N, 3, L), (N, 3E)
+        aq, qo = [], []
+        for g in range(3):
+            a_g, q_g = ops.glimpse_pool_fwd(Q[g].view(N, T, E), ops.att_logits_fwd(Hq[g], whq[g], zb1), False)
+            aq.append(a_g)
+            qo.append(q_g)
+        ctx.save_for_backward(V, q0, q1, q2, wv_cat, wq2[0], wq2[1], wq2[2], wblk, whq[0], whq[1], whq[2], Vh, CQ, C, Hv, Hq, av,
+                              aq[0], aq[1], aq[2])
+        ctx.dims, ctx.stream = (N, L, T, E), stream
+        ctx.set_materialize_grads(False)
+        return (vcat, qo[0], qo[1], qo[2], av, aq[0], aq[1], aq[2])
+
+    @staticmethod
+    def backward(ctx, dvcat, dq0, dq1, dq2, dav, daq0, daq1, daq2):
+        (V, q0, q1, q2, wv_cat, wq0, wq1, wq2_, wblk, whq0, whq1, whq2, Vh, CQ, C, Hv, Hq, av, aq0, aq1, aq2) = ctx.saved_tensors
+        N, L, T, E = ctx.dims
+        M, MT = N * L, N * T
+        dev = V.device
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        Q, wq2, whq, aq = (q0, q1, q2), (wq0, wq1, wq2_), (whq0, whq1, whq2), (aq0, aq1, aq2)
+        dq, daq = (dq0, dq1, dq2), (daq0, daq1, daq2)
+        stream = ctx.stream
+        dCQ = new(MT, 6 * E)                                                        # [dCq_0 | dQh_0 | ...]
+        dti = new(MT, 3 * E)
+        dQ, dwhq = [], []
+        # question side: q_i = aq_i^T Q_i, aq_i = softmax(whq_i Hq_i), Hq_i = tanh(Qh_i + ti_i)
+        for g in range(3):
+            dqg = _c(dq[g]) if dq[g] is not None else zeros(N, E)
+            dl, dQg = ops.glimpse_pool_bwd(dqg, Q[g].view(N, T, E), aq[g], False, True,
+                                           dwts=None if daq[g] is None else _c(daq[g]))
+            dHq, dw, _, _ = ops.att_logits_bwd(dl, Hq[g], whq[g], relu_mask=False)
+            ops.tanh_dropout_bwd2d(dHq, Hq[g], *_NODROP, out=dti[:, g * E:(g + 1) * E])   # d(Qh_i + ti_i)
+            if not stream:
+                ops.tanh_dropout_bwd2d(dHq, Hq[g], *_NODROP, out=dCQ[:, (2 * g + 1) * E:(2 * g + 2) * E])
+            dQ.append(dQg.view(MT, E))
+            dwhq.append(dw)
+        # image side: one G = 3 pooling backward over V, the block-diagonal head, Hv_i = tanh(Vh_i + tq_i)
+        dvc = _c(dvcat) if dvcat is not None else zeros(N, 3 * E)
+        dlv, dV = ops.glimpse_pool_bwd(dvc, V.view(N, L, E), av, False, True, dwts=None if dav is None else _c(dav))
+        dV = dV.view(M, E)
+        dHv, dwblk, _, _ = ops.att_logits_bwd(dlv, Hv, wblk, relu_mask=False)
+        dVh = ops.tanh_dropout_bwd2d(dHv, Hv, *_NODROP, out=dHv)                   # dtq_i = d(Vh_i + tq_i); dVh_i below
+        dC = new(3, N, T, L)
+        if stream and ops.hie_affinity_levels_supported(N, L, E, T, 3, 2):
+            ops.hie_affinity_levels(dti, E, Vh, E, 3, N, L, T, E, x2=CQ[:, E:], lvx2=2 * E, y2=dVh, lvy2=E, epi=2, yprev=C, out=dC)
+        elif stream and ops.hie_affinity_supported(N, L, E, T, 2):                  # (E = 512: three levels x two pairs exceed the LDS)
+            for g in range(3):
+                ops.hie_affinity(dti[:, g * E:(g + 1) * E], Vh[:, g * E:(g + 1) * E], N, L, T, x2=CQ[:, (2 * g + 1) * E:(2 * g + 2) * E],
+                                 y2=dVh[:, g * E:(g + 1) * E], epi=2, yprev=C[g], out=dC[g])
+        else:
+            for g in range(3):
+                ops.bgemm(dti[:, g * E:(g + 1) * E].view(N, T, E), Vh[:, g * E:(g + 1) * E].view(N, L, E), out=dC[g])
+                ops.bgemm(CQ[:, (2 * g + 1) * E:(2 * g + 2) * E].view(N, T, E), dVh[:, g * E:(g + 1) * E].view(N, L, E),
+                          out=dC[g], accumulate=True)
+            ops.tanh_dropout_bwd(dC.view(3 * MT, L), C.view(3 * MT, L), *_NODROP, out=dC.view(3 * MT, L))
+        if stream:
+            S = ops.hie_chunks(N, L)
+            part, scratch = new(S, MT, E), new(M, E)
+        for g in range(3):
+            cq_g, qh_g = CQ[:, 2 * g * E:(2 * g + 1) * E], CQ[:, (2 * g + 1) * E:(2 * g + 2) * E]
+            dcq_g, dqh_g = dCQ[:, 2 * g * E:(2 * g + 1) * E], dCQ[:, (2 * g + 1) * E:(2 * g + 2) * E]
+            dti_g, dtq_g = dti[:, g * E:(g + 1) * E], dVh[:, g * E:(g + 1) * E]
+            if stream:
+                ops.hie_rank_left(C[g], dti_g, dtq_g, N, L, T, scratch, part)        # C dtq (the T-row sums)
+                ops.hie_slab_sum(part, dqh_g, add=dti_g)                            # dQh = dti + C dtq
+                ops.hie_rank_add(dtq_g, C[g], dti_g, N, L, T, dtq_g)                # dVh = dtq + C^T dti   (in place)
+                ops.hie_rank_left(dC[g], cq_g, V, N, L, T, scratch, part)           # dCq = dC V  (T-row sums over V)
+                ops.hie_slab_sum(part, dcq_g)
+                ops.hie_rank_add(dV, dC[g], cq_g, N, L, T, dV)                      # dV += dC^T Cq   (in place)
+            else:
+                ops.bgemm(C[g], dtq_g.view(N, L, E), ta=False, tb=True, out=dqh_g.view(N, T, E), accumulate=True)
+                ops.bgemm(C[g], dti_g.view(N, T, E), ta=True, tb=True, out=dtq_g.view(N, L, E), accumulate=True)
+                ops.bgemm(dC[g], V.view(N, L, E), ta=False, tb=True, out=dcq_g.view(N, T, E))
+                ops.bgemm(dC[g], cq_g.view(N, T, E), ta=True, tb=True, out=dV.view(N, L, E), accumulate=True)
+        # the concatenated layers: dV += dVh [Wv_0; Wv_1; Wv_2], one weight-gradient product; per level the [Wb; Wq] pair
+        ops.gemm(dVh, wv_cat, tb=True, out=dV, accumulate=True)
+        dwv = ops.gemm(dVh, V, ta=True, tb=True)                                   # (3E, E)
+        grads = []
+        for g in range(3):
+            blk = dCQ[:, 2 * g * E:(2 * g + 2) * E]
+            ops.gemm(blk, wq2[g], tb=True, out=dQ[g], accumulate=True)
+            dwq2 = ops.gemm(blk, Q[g], ta=True, tb=True)                           # (2E, E) = [dWb; dWq]
+            grads += [dwq2[:E], dwv[g * E:(g + 1) * E], dwq2[E:], dwblk[g:g + 1, g * E:(g + 1) * E].contiguous(), dwhq[g]]
+        return (dV, dQ[0], dQ[1], dQ[2], None, None, None, *grads)
+
+
+class _Coatt(nn.Module):
+    """One level's co-attention weights (no biases: a bias inside the softmax cancels, and Wb / Wv / Wq are bias-free)."""
+
+    def __init__(self, E):
+        super(_Coatt, self).__init__()
+        self.Wb = nn.Linear(E, E, bias=False)
+        self.Wv = nn.Linear(E, E, bias=False)
+        self.Wq = nn.Linear(E, E, bias=False)
+        self.whv = nn.Linear(E, 1, bias=False)
+        self.whq = nn.Linear(E, 1, bias=False)
+
+
+class HieCoAttenLadder(nn.Module):
+    """forward(img_features (N, L, img_size) fp32 GPU, que_features (N, T) int64 GPU)
+    -> (logits (N, output_size), av (N, 3, L), aq (N, 3, T)); levels ordered word, phrase, sentence.
+
+    The image features are data (img_features.requires_grad raises), fp32 on the GPU: CPU tensors and bf16 features raise
+    VqfError -- there is no CPU fallback.  Padded words are not masked.  Dropout (rate drop_p) is active in train mode only;
+    set_keep_masks() supplies explicit uint8 keep-masks for the tests, otherwise the kernels draw Philox masks."""
+
+    def __init__(self, block_num=196, word_num=22, img_size=2048, vocab_size=15881, embed_size=512, hidden_size=1024,
+                 output_size=3000, drop_p=0.5):
+        super(HieCoAttenLadder, self).__init__()
+        E = embed_size
+        self.img_emb = nn.Linear(img_size, E)
+        self.word_emb = nn.Embedding(vocab_size, E)
+        self.phrase_uni = nn.Conv1d(E, E, 1)
+        self.phrase_bi = nn.Conv1d(E, E, 2)
+        self.phrase_tri = nn.Conv1d(E, E, 3)
+        self.sent_lstm = nn.LSTM(E, E, batch_first=True)
+        self.coatt = nn.ModuleList([_Coatt(E) for _ in range(3)])
+        self.ans_w = nn.Linear(E, E)
+        self.ans_p = nn.Linear(2 * E, E)
+        self.ans_s = nn.Linear(2 * E, hidden_size)
+        self.ans_h = nn.Linear(hidden_size, output_size)
+        self.drop_p = drop_p
+        self._seeds = _DropSeeds()
+
+    def set_keep_masks(self, **masks):
+        """Test hook: uint8 keep-masks 'img' (N*L, E), 'word' (N*T, E), 'ans_w' (N, E), 'ans_p' (N, 2E), 'ans_s' (N, 2E),
+        'ans_h' (N, hidden_size); used in train mode in place of the in-kernel draws."""
+        self._seeds.keep = masks
+
+    def _drop(self, x, tag):
+        seed, p = self._seeds.next(self.training, self.drop_p)                  # one draw per tag and call: the same order always
+        keep = self._seeds.keep.get(tag) if self.training else None
+        if keep is None and p <= 0.0:
+            return x
+        return DropoutFn.apply(_c(x), keep, seed, self.drop_p if keep is not None else p)
+
+    def forward(self, img_features, que_features):
+        if not img_features.is_cuda or not que_features.is_cuda:
+            raise VqfError("HieCoAttenLadder needs GPU tensors (the HIP extension is the only path; no CPU fallback)")
+        if img_features.dtype != torch.float32:
+            raise VqfError("HieCoAttenLadder takes fp32 img_features (got %s)" % img_features.dtype)
+        if img_features.requires_grad:
+            raise VqfError("HieCoAttenLadder: img_features are data (no gradient into the image features)")
+        if que_features.dtype != torch.int64:
+            raise VqfError("HieCoAttenLadder takes int64 word ids")
+        N, L, D = img_features.shape
+        T = que_features.shape[1]
+        E = self.img_emb.out_features
+        if E % 32 or not ops.phrase_ngram_supported(T, E) or L > 1024 or T > 1024:
+            raise VqfError("HieCoAttenLadder: embed_size %% 32 == 0, T <= 32 and L <= 1024 are supported (got E=%d, T=%d, L=%d)"
+                           % (E, T, L))
+        M, MT = N * L, N * T
+        # V = drop(tanh(img_emb(img)))
+        seed, p = self._seeds.next(self.training, self.drop_p)
+        keep = self._seeds.keep.get("img") if self.training else None
+        V = LinearFn.apply(_c(img_features).view(M, D), self.img_emb.weight, self.img_emb.bias, False)
+        V = TanhDropFn.apply(V, None, keep, seed, self.drop_p if keep is not None else p)
+        # Qw = drop(tanh(word_emb(ids)))
+        qw = EmbedTanhFn.apply(que_features, self.word_emb.weight, True, False).view(MT, E)
+        qw = self._drop(qw, "word")
+        # phrase level
+        qp = PhraseFn.apply(qw, self.phrase_uni.weight, self.phrase_uni.bias, self.phrase_bi.weight, self.phrase_bi.bias,
+                            self.phrase_tri.weight, self.phrase_tri.bias, N, T)
+        # sentence level: the HIP LSTM over time-major rows (the re-layouts are dropout passes at rate 0)
+        lstm = self.sent_lstm
+        xt = DropoutBTFn.apply(qp.view(N, T, E).transpose(0, 1), None, 0, 0.0)            # (T, N, E) contiguous
+        hs = LstmBatchFn.apply(xt, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, False)
+        qs = DropoutBTFn.apply(hs.transpose(0, 1), None, 0, 0.0).view(MT, E)            # (N*T, E)
+        # the three co-attention levels
+        w = [p_ for c in self.coatt for p_ in (c.Wb.weight, c.Wv.weight, c.Wq.weight, c.whv.weight, c.whq.weight)]
+        vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, *w)
+        v0, v1, v2 = vcat[:, :E], vcat[:, E:2 * E], vcat[:, 2 * E:]
+        th = lambda x: TanhDropFn.apply(x, None, None, 0, 0.0)
+        lin = lambda x, m: LinearFn.apply(_c(x), m.weight, m.bias, False)
+        h_w = th(lin(self._drop(q0 + v0, "ans_w"), self.ans_w))
+        h_p = th(lin(self._drop(torch.cat([q1 + v1, h_w], 1), "ans_p"), self.ans_p))
+        h_s = th(lin(self._drop(torch.cat([q2 + v2, h_p], 1), "ans_s"), self.ans_s))
+        logits = lin(self._drop(h_s, "ans_h"), self.ans_h)
+        aq = torch.cat([aq0, aq1, aq2], 1)                                              # (N, 3, T): 3 N T floats
+        return logits, av, aq

@@ -85,6 +85,12 @@ SIGNATURES = {
     "vqf_hie_slab_sum": (c_i, [c_f, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_p]),
     "vqf_hie_affinity_supported": (c_i, [c_i, c_i, c_i, c_i, c_i]),
     "vqf_hie_affinity": (c_i, [c_f, c_i, c_f, c_i, c_f, c_i, c_f, c_i, c_i, c_f, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_p]),
+    "vqf_phrase_ngram_supported": (c_i, [c_i, c_i]),
+    "vqf_phrase_ngram_fwd": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_f, c_i, c_p, c_p]),
+    "vqf_phrase_ngram_bwd": (c_i, [c_f, c_i, c_f, c_i, c_p, c_i, c_i, c_i, c_f, c_i, c_p]),
+    "vqf_hie_affinity_levels_supported": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    "vqf_hie_affinity_levels": (c_i, [c_f, c_i, c_i, c_f, c_i, c_i, c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i,
+                                      c_f, c_p]),
     "vqf_softmax_rows_fwd": (c_i, [c_f, c_i, c_i, c_f, c_p]),
     "vqf_softmax_rows_bwd": (c_i, [c_f, c_f, c_i, c_i, c_f, c_p]),
     "vqf_log_softmax_rows_fwd": (c_i, [c_f, c_i, c_i, c_f, c_p]),

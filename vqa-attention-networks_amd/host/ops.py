@@ -313,7 +313,7 @@ def relu_bwd(dx, y, want_bias=True):
 
 
 def att_logits_fwd(hid, w2, b2):
-    """logits (M,G) = hid (M,Hh) @ w2 (G,Hh)^T + b2; G in {1,2}."""
+    """logits (M,G) = hid (M,Hh) @ w2 (G,Hh)^T + b2; G in {1,2,3}."""
     _chk(hid, w2, b2)
     M, Hh = hid.shape
     G = w2.shape[0]
@@ -658,6 +658,67 @@ def hie_slab_sum(part, out, add=None):
     S, R, W = part.shape
     _l.check(_lib().vqf_hie_slab_sum(_ptr(part), S, R, W, _ptr(add), add.stride(0) if add is not None else 0, _ptr(out),
                                      out.stride(0), _stream()), "vqf_hie_slab_sum")
+    return out
+
+
+# ---------------------------------------------------------------------------
+# the word / phrase / sentence ladder (csrc/hie_ladder.hip; include/vqa_fusion.h vqf_phrase_ngram_*, vqf_hie_affinity_levels)
+def phrase_ngram_supported(T, E):
+    return bool(_lib().vqf_phrase_ngram_supported(int(T), int(E)))
+
+
+def phrase_ngram_fwd(Z, bias, N, T, out=None, idx=None):
+    """Z (N*T, 6E) = Qw Wcat^T (rows may be strided), bias (3E) = [b1 | b2 | b3] -> (Qp (N*T, E), idx (N*T, E) uint8):
+    Qp = tanh(max_k u_k), idx = the winning k - 1"""
+    _chk2s(Z, out)
+    _chk(bias)
+    E = Z.shape[1] // 6
+    if Z.shape != (N * T, 6 * E) or bias.numel() != 3 * E:
+        raise _l.VqfError("phrase_ngram_fwd: Z must be (N*T, 6E) and bias (3E)")
+    if out is None:
+        out = torch.empty((N * T, E), dtype=torch.float32, device=Z.device)
+    if idx is None:
+        idx = torch.empty((N * T, E), dtype=torch.uint8, device=Z.device)
+    _l.check(_lib().vqf_phrase_ngram_fwd(_ptr(Z), Z.stride(0), _ptr(bias), int(N), int(T), int(E), _ptr(out), out.stride(0),
+                                         _ptr(idx), _stream()), "vqf_phrase_ngram_fwd")
+    return out, idx
+
+
+def phrase_ngram_bwd(dQp, Qp, idx, N, T, out=None):
+    """-> dZ (N*T, 6E): the gradient of Z gathered from du = dQp (1 - Qp^2) at the winning taps"""
+    _chk2s(dQp, Qp, out)
+    E = Qp.shape[1]
+    if not idx.is_cuda or idx.dtype != torch.uint8 or not idx.is_contiguous() or idx.shape != (N * T, E):
+        raise _l.VqfError("phrase_ngram_bwd: idx must be a contiguous (N*T, E) uint8 GPU tensor")
+    if out is None:
+        out = torch.empty((N * T, 6 * E), dtype=torch.float32, device=Qp.device)
+    _l.check(_lib().vqf_phrase_ngram_bwd(_ptr(dQp), dQp.stride(0), _ptr(Qp), Qp.stride(0), _ptr(idx), int(N), int(T), int(E),
+                                         _ptr(out), out.stride(0), _stream()), "vqf_phrase_ngram_bwd")
+    return out
+
+
+def hie_affinity_levels_supported(N, L, E, T, G, pairs=1):
+    return bool(_lib().vqf_hie_affinity_levels_supported(int(N), int(L), int(E), int(T), int(G), int(pairs)))
+
+
+def hie_affinity_levels(x1, lvx1, y1, lvy1, G, N, L, T, E, x2=None, lvx2=0, y2=None, lvy2=0, epi=0, yprev=None, out=None):
+    """out (G, N, T, L): level g = epi(X1_g Y1_g^T [+ X2_g Y2_g^T]) per sample, X_g = the E columns of x at offset g * lvx (rows
+    n*T + t), Y_g those of y at g * lvy (rows n*L + l; lvy = 0: one y shared by the levels).  2-D operands, rows may be strided.
+    epi 0: the sums; 1: tanh; 2: sums * (1 - yprev^2)."""
+    _chk2s(x1, y1, x2, y2)
+    if x1.shape[0] != N * T or y1.shape[0] != N * L or (x2 is not None and (x2.shape[0] != N * T or y2.shape[0] != N * L)):
+        raise _l.VqfError("hie_affinity_levels: operand shapes")
+    if out is None:
+        out = torch.empty((G, N, T, L), dtype=torch.float32, device=x1.device)
+    _chk(out)
+    if out.numel() != G * N * T * L or (yprev is not None and yprev.numel() != G * N * T * L):
+        raise _l.VqfError("hie_affinity_levels: out / yprev must hold (G, N, T, L)")
+    _chk(yprev)
+    sx2 = x2.stride(0) if x2 is not None else 0
+    sy2 = y2.stride(0) if y2 is not None else 0
+    _l.check(_lib().vqf_hie_affinity_levels(_ptr(x1), x1.stride(0), int(lvx1), _ptr(y1), y1.stride(0), int(lvy1),
+                                            _ptr(x2), sx2, int(lvx2), _ptr(y2), sy2, int(lvy2), int(G), int(epi), _ptr(yprev),
+                                            int(N), int(L), int(E), int(T), _ptr(out), _stream()), "vqf_hie_affinity_levels")
     return out
 
 
