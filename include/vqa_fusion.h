@@ -467,7 +467,7 @@ int vqf_hie_affinity(const float* x1, int ldx1, const float* y1, int ldy1, const
                      int epi, const float* yprev, const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int E, int T,
                      float* out, void* stream);
 
-/* The word / phrase / sentence ladder (HieCoAttenLadder; csrc/hie_ladder.hip; additions within ABI 7).
+/* The word / phrase / sentence ladder (HieCoAttenLadder; csrc/hie_ladder.hip, the affinity in csrc/hie.hip; additions within ABI 7).
  * Phrase level: Z (N*T, 6E) = Qw Wcat^T, the six conv taps [uni0 | bi0 bi1 | tri0 tri1 tri2] (row pitch ldz), bias (3E) =
  * [b1 | b2 | b3].  u_k[t] = b_k + sum_{j<k, t+j<T} Z[n*T+t+j, tap(k,j)];  Qp = tanh(max_k u_k) (row pitch ldq), idx (N*T, E)
  * uint8 = the winning k - 1 (first maximum on a tie).  Backward: dZ (N*T, 6E, pitch ldz) with row r of tap (k, j) = du[r - j]
@@ -478,7 +478,7 @@ int vqf_phrase_ngram_fwd(const float* Z, int ldz, const float* bias, int N, int 
                          void* stream);
 int vqf_phrase_ngram_bwd(const float* dQp, int ldd, const float* Qp, int ldq, const uint8_t* idx, int N, int T, int E, float* dZ,
                          int ldz, void* stream);
-/* vqf_hie_affinity for G <= 3 levels in one pass over the y rows: level g reads x rows at column offset g * ldx_level and y
+/* vqf_hie_affinity (the same kernel template) for G <= 3 levels in one pass over the y rows: level g reads x rows at column offset g * ldx_level and y
  * rows at g * ldy_level (0: all levels share one y, read once).  out[g] (G, N, T, L) contiguous = epi(sums of level g); epi 0:
  * the sums, 1: tanh, 2: sums * (1 - yprev^2) with yprev (G, N, T, L).  No dropout.  Same k order as vqf_hie_affinity (G = 1:
  * the same bits).  Supported: T <= 16, E % 32 == 0, G * pairs * 16 * (E + 4) floats of LDS <= 160 KB. */

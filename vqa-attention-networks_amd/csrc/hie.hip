@@ -285,11 +285,18 @@ __global__ void slab_sum_kernel(const float* __restrict__ part, int S, int R, in
 // pair (X2, Y2) accumulated behind the first (dC = dti img_^T + que_ dtq^T in one launch) and the element-wise neighbour in the
 // epilogue: EPI 1 = dropout(tanh(.)) (:32-33), EPI 2 = its backward given the forward's output.  The dropout index of (n,t,l)
 // is that of the contiguous (N*T, L) tensor: same masks as vqf_tanh_dropout_fwd / _bwd.
+//
+// G <= 3 levels in ONE pass over the y rows (vqf_hie_affinity_levels; HieCoAttenLadder, host/hie_ladder.py: its three levels
+// attend over the same image tensor V, so C_g = tanh(Cq_g V^T) reads V once instead of three times).  X_g are the rows of x at
+// column offset g * lvx, Y_g those of y at g * lvy (0: one shared y, loaded once per k slab and fed to all G accumulators);
+// out and yprev (G, N, T, L), contiguous per level.  The k order of a level does not depend on G.  The two entry points are two
+// sets of instantiations of the one template: vqf_hie_affinity <EPI, 1, DROP = true>, vqf_hie_affinity_levels <EPI, G, false>
+// (the ladder has no dropout on C; with the dropout epilogue compiled in, <2, 3> needs 128 registers and spills).
 struct AffArgs {
-  const float* x1; int ldx1; const float* y1; int ldy1;
-  const float* x2; int ldx2; const float* y2; int ldy2;
+  const float* x1; int ldx1, lvx1; const float* y1; int ldy1, lvy1;     // lv*: column offset of level g is g * lv* (unused for G = 1)
+  const float* x2; int ldx2, lvx2; const float* y2; int ldy2, lvy2;
   const float* yprev; float* out;
-  const uint8_t* keep; uint64_t seed; uint32_t thr; float inv_keep;
+  const uint8_t* keep; uint64_t seed; uint32_t thr; float inv_keep;     // DROP only
   int N, L, E, T;
 };
 
@@ -302,75 +309,86 @@ __device__ __forceinline__ float keep1(const uint8_t* __restrict__ keep, uint64_
   return v >= thr ? inv_keep : 0.f;
 }
 
-template <int EPI>
+// LDS holds the G x npair (16, E) X images; a wave owns 16 y rows and G accumulators
+template <int EPI, int G, bool DROP>
 __global__ void __launch_bounds__(1024) hie_affinity_kernel(const AffArgs g) {
   extern __shared__ float smem[];
   const int E = g.E, T = g.T, L = g.L, ES = E + 4;           // + 4: the 16 rows of a b128 fragment read fall on distinct banks
   const int n = blockIdx.y, tid = threadIdx.x, W = blockDim.x >> 6, wave = tid >> 6, lane = tid & 63;
   const int npair = g.x2 ? 2 : 1, CT = E >> 2;
-  for (int p = 0; p < npair; ++p) {
-    const float* x = p ? g.x2 : g.x1;
-    const int ldx = p ? g.ldx2 : g.ldx1;
-    float* Xs = smem + p * 16 * ES;
-    for (int i = tid; i < 16 * CT; i += blockDim.x) {
-      const int t = i / CT, c = i - t * CT;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (t < T) v = *reinterpret_cast<const f32x4*>(x + (long long)(n * T + t) * ldx + 4 * c);
-      *reinterpret_cast<f32x4*>(Xs + t * ES + 4 * c) = v;
+  for (int p = 0; p < npair; ++p)
+    for (int lv = 0; lv < G; ++lv) {
+      const float* x = p ? g.x2 + lv * g.lvx2 : g.x1 + lv * g.lvx1;
+      const int ldx = p ? g.ldx2 : g.ldx1;
+      float* Xs = smem + (p * G + lv) * 16 * ES;
+      for (int i = tid; i < 16 * CT; i += blockDim.x) {
+        const int t = i / CT, c = i - t * CT;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (t < T) v = *reinterpret_cast<const f32x4*>(x + (long long)(n * T + t) * ldx + 4 * c);
+        *reinterpret_cast<f32x4*>(Xs + t * ES + 4 * c) = v;
+      }
     }
-  }
   __syncthreads();
-  const int G = (L + 15) >> 4;
+  const int NG = (L + 15) >> 4;
   const int r = lane & 15, kq = lane >> 4;
-  for (int grp = blockIdx.x * W + wave; grp < G; grp += gridDim.x * W) {
+  for (int grp = blockIdx.x * W + wave; grp < NG; grp += gridDim.x * W) {
     const int l = grp * 16 + r;
     const long long row = (long long)n * L + (l < L ? l : L - 1);      // rows past L: a valid row, result not stored
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[G];
+#pragma unroll
+    for (int lv = 0; lv < G; ++lv) acc[lv] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int p = 0; p < npair; ++p) {
-      const float* y = (p ? g.y2 : g.y1) + row * (p ? g.ldy2 : g.ldy1) + 8 * kq;
-      const float* xs = smem + p * 16 * ES + r * ES + 8 * kq;
+      const int lvy = p ? g.lvy2 : g.lvy1;
+      const float* y0 = (p ? g.y2 : g.y1) + row * (p ? g.ldy2 : g.ldy1) + 8 * kq;
       for (int k0 = 0; k0 < E; k0 += 256) {
         f32x4 b[16];
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (k0 + 32 * u < E) {                                       // (uniform)
-            b[2 * u] = vqf_ld_stream(reinterpret_cast<const f32x4*>(y + k0 + 32 * u));
-            b[2 * u + 1] = vqf_ld_stream(reinterpret_cast<const f32x4*>(y + k0 + 32 * u + 4));
+        for (int lv = 0; lv < G; ++lv) {
+          if (lv == 0 || lvy != 0) {                                    // (uniform) a shared y is loaded once per k slab
+            const float* y = y0 + lv * lvy;
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+              if (k0 + 32 * u < E) {                                    // (uniform)
+                b[2 * u] = vqf_ld_stream(reinterpret_cast<const f32x4*>(y + k0 + 32 * u));
+                b[2 * u + 1] = vqf_ld_stream(reinterpret_cast<const f32x4*>(y + k0 + 32 * u + 4));
+              }
           }
+          const float* xs = smem + (p * G + lv) * 16 * ES + r * ES + 8 * kq;
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (k0 + 32 * u < E) {
-            const f32x4 a0 = *reinterpret_cast<const f32x4*>(xs + k0 + 32 * u);
-            const f32x4 a1 = *reinterpret_cast<const f32x4*>(xs + k0 + 32 * u + 4);
+          for (int u = 0; u < 8; ++u)
+            if (k0 + 32 * u < E) {
+              const f32x4 a0 = *reinterpret_cast<const f32x4*>(xs + k0 + 32 * u);
+              const f32x4 a1 = *reinterpret_cast<const f32x4*>(xs + k0 + 32 * u + 4);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j], b[2 * u][j], acc, 0, 0, 0);
+              for (int j = 0; j < 4; ++j) acc[lv] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j], b[2 * u][j], acc[lv], 0, 0, 0);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j], b[2 * u + 1][j], acc, 0, 0, 0);
-          }
+              for (int j = 0; j < 4; ++j) acc[lv] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j], b[2 * u + 1][j], acc[lv], 0, 0, 0);
+            }
+        }
       }
     }
     if (l < L) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int t = 4 * kq + j;                                      // D: rows 4 (lane / 16) + j, column lane % 16
-        if (t < T) {
-          const long long idx = ((long long)n * T + t) * L + l;
-          float v = acc[j];
-          if (EPI == 1) {
-            v = vqf_tanh_fast(v) * keep1(g.keep, g.seed, g.thr, g.inv_keep, idx);
-          } else if (EPI == 2) {
-            const float sc = keep1(g.keep, g.seed, g.thr, g.inv_keep, idx);
-            const float th = sc > 0.f ? g.yprev[idx] * (1.0f / g.inv_keep) : 0.f;
-            v = v * sc * (1.0f - th * th);
+      for (int lv = 0; lv < G; ++lv)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int t = 4 * kq + j;                                    // D: rows 4 (lane / 16) + j, column lane % 16
+          if (t < T) {
+            const long long idx = (((long long)lv * g.N + n) * T + t) * L + l;
+            const float sc = DROP && EPI ? keep1(g.keep, g.seed, g.thr, g.inv_keep, idx) : 1.0f;
+            float v = acc[lv][j];
+            if (EPI == 1) {
+              v = vqf_tanh_fast(v) * sc;
+            } else if (EPI == 2) {                                     // (DROP: the tanh value back from the stored tanh * keep / (1 - p))
+              const float th = !DROP ? g.yprev[idx] : sc > 0.f ? g.yprev[idx] * (1.0f / g.inv_keep) : 0.f;
+              v = v * sc * (1.0f - th * th);
+            }
+            g.out[idx] = v;
           }
-          g.out[idx] = v;
         }
-      }
     }
   }
 }
-
-VqfDynLdsFlags g_aff_lds[3];
 
 bool shape_ok(int N, int L, int E, int T) {
   if (N <= 0 || L <= 0 || E <= 0 || T <= 0 || N > 65535 || T > TMAX_ALL || (E % 4)) return false;
@@ -426,6 +444,60 @@ int launch(int mode, HieArgs& g, const uint8_t* keep, uint64_t seed, float p, hi
 }
 
 bool rows_ok(const float* p, int ld, int E) { return p && aligned16(p) && ld >= E && (ld % 4) == 0; }
+
+bool affinity_shape_ok(int N, int L, int E, int T, int G, int pairs) {
+  if (N <= 0 || N > 65535 || L <= 0 || T <= 0 || T > 16 || E <= 0 || (E % 32) || G < 1 || G > 3 || pairs < 1 || pairs > 2)
+    return false;
+  return (size_t)G * pairs * 16 * (E + 4) * sizeof(float) <= 160 * 1024;
+}
+
+template <int EPI, int G, bool DROP>
+int affinity_go(int kid, dim3 grid, dim3 block, int lds, hipStream_t s, const AffArgs& g) {
+  static VqfDynLdsFlags lds_set;                   // (one per instantiation: the attribute belongs to the kernel function)
+  if (lds > 64 * 1024) {
+    const int rc = vqf_set_dyn_lds((const void*)hie_affinity_kernel<EPI, G, DROP>, lds, lds_set);
+    if (rc != VQF_OK) return rc;
+  }
+  VQF_LAUNCH(kid, (hie_affinity_kernel<EPI, G, DROP>), grid, block, lds, s, g);
+  return vqf_last_error();
+}
+
+template <int G, bool DROP>
+int affinity_epi(int epi, int kid, dim3 grid, dim3 block, int lds, hipStream_t s, const AffArgs& g) {
+  switch (epi) {
+    case 0:  return affinity_go<0, G, DROP>(kid, grid, block, lds, s, g);
+    case 1:  return affinity_go<1, G, DROP>(kid, grid, block, lds, s, g);
+    default: return affinity_go<2, G, DROP>(kid, grid, block, lds, s, g);
+  }
+}
+
+// both entry points: the operands are in g (dropout fields filled by the caller when `drop`), everything else is decided here
+int affinity_launch(int kid, const AffArgs& g, int G, int epi, bool drop, hipStream_t s) {
+  const int E = g.E, pairs = g.x2 ? 2 : 1;
+  if (!g.out || !rows_ok(g.x1, g.ldx1, E) || !rows_ok(g.y1, g.ldy1, E) || (!g.x2) != (!g.y2) ||
+      (g.x2 && (!rows_ok(g.x2, g.ldx2, E) || !rows_ok(g.y2, g.ldy2, E))) || epi < 0 || epi > 2 || (epi == 2 && !g.yprev) ||
+      g.lvx1 < 0 || g.lvy1 < 0 || (g.lvx1 % 4) || (g.lvy1 % 4) || (g.x2 && (g.lvx2 < 0 || g.lvy2 < 0 || (g.lvx2 % 4) || (g.lvy2 % 4))))
+    return VQF_E_BADARG;
+  if (!affinity_shape_ok(g.N, g.L, E, g.T, G, pairs)) return VQF_E_UNSUPPORTED;
+  // every level's columns stay inside the row (a level offset plus E within the row pitch)
+  if ((G - 1) * g.lvx1 + E > g.ldx1 || (G - 1) * g.lvy1 + E > g.ldy1 ||
+      (g.x2 && ((G - 1) * g.lvx2 + E > g.ldx2 || (G - 1) * g.lvy2 + E > g.ldy2)))
+    return VQF_E_BADARG;
+  const int cus = vqf_cu_count() > 0 ? vqf_cu_count() : 256;
+  const int NG = (g.L + 15) / 16;
+  int S = (cus + g.N - 1) / g.N;                   // whole samples per workgroup once N >= the CU count
+  if (S > NG) S = NG;
+  int W = (NG + S - 1) / S;
+  if (W > 16) W = 16;
+  const int lds = G * pairs * 16 * (E + 4) * (int)sizeof(float);
+  const dim3 grid(S, g.N), block(64 * W);
+  if (drop) return affinity_epi<1, true>(epi, kid, grid, block, lds, s, g);
+  switch (G) {
+    case 1:  return affinity_epi<1, false>(epi, kid, grid, block, lds, s, g);
+    case 2:  return affinity_epi<2, false>(epi, kid, grid, block, lds, s, g);
+    default: return affinity_epi<3, false>(epi, kid, grid, block, lds, s, g);
+  }
+}
 
 }  // namespace
 
@@ -499,45 +571,31 @@ int vqf_hie_rank_left(const float* U, const float* V, int ldv, const float* z, i
   return launch(MODE_LEFT, g, nullptr, 0, 0.f, (hipStream_t)stream);
 }
 
-int vqf_hie_affinity_supported(int N, int L, int E, int T, int pairs) {
-  if (N <= 0 || N > 65535 || L <= 0 || T <= 0 || T > 16 || E <= 0 || (E % 32) || pairs < 1 || pairs > 2) return 0;
-  return (size_t)pairs * 16 * (E + 4) * sizeof(float) <= 160 * 1024;
-}
+int vqf_hie_affinity_supported(int N, int L, int E, int T, int pairs) { return affinity_shape_ok(N, L, E, T, 1, pairs); }
 
 int vqf_hie_affinity(const float* x1, int ldx1, const float* y1, int ldy1, const float* x2, int ldx2, const float* y2, int ldy2,
                      int epi, const float* yprev, const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int E, int T,
                      float* out, void* stream) {
-  const int pairs = x2 ? 2 : 1;
-  if (!out || !rows_ok(x1, ldx1, E) || !rows_ok(y1, ldy1, E) || (!x2) != (!y2) || (x2 && (!rows_ok(x2, ldx2, E) || !rows_ok(y2, ldy2, E))) ||
-      epi < 0 || epi > 2 || (epi == 2 && !yprev) || p_drop < 0.f || p_drop >= 1.f)
-    return VQF_E_BADARG;
-  if (!vqf_hie_affinity_supported(N, L, E, T, pairs)) return VQF_E_UNSUPPORTED;
+  if (p_drop < 0.f || p_drop >= 1.f) return VQF_E_BADARG;
   AffArgs g = {};
   g.x1 = x1; g.ldx1 = ldx1; g.y1 = y1; g.ldy1 = ldy1; g.x2 = x2; g.ldx2 = ldx2; g.y2 = y2; g.ldy2 = ldy2;
   g.yprev = yprev; g.out = out; g.N = N; g.L = L; g.E = E; g.T = T;
   g.keep = epi ? keep : nullptr; g.seed = seed;
   g.thr = (!epi || keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
   g.inv_keep = (epi && (keep || p_drop > 0.f)) ? 1.0f / (1.0f - p_drop) : 1.0f;
-  const int cus = vqf_cu_count() > 0 ? vqf_cu_count() : 256;
-  const int G = (L + 15) / 16;
-  int S = (cus + N - 1) / N;                       // whole samples per workgroup once N >= the CU count
-  if (S > G) S = G;
-  int W = (G + S - 1) / S;
-  if (W > 16) W = 16;
-  const int lds = pairs * 16 * (E + 4) * (int)sizeof(float);
-  const void* fn = epi == 0 ? (const void*)hie_affinity_kernel<0> : epi == 1 ? (const void*)hie_affinity_kernel<1> : (const void*)hie_affinity_kernel<2>;
-  if (lds > 64 * 1024) {
-    const int rc = vqf_set_dyn_lds(fn, lds, g_aff_lds[epi]);
-    if (rc != VQF_OK) return rc;
-  }
-  const dim3 grid(S, N), block(64 * W);
-  hipStream_t s = (hipStream_t)stream;
-  switch (epi) {
-    case 0:  VQF_LAUNCH(KID_HIE_AFF, hie_affinity_kernel<0>, grid, block, lds, s, g); break;
-    case 1:  VQF_LAUNCH(KID_HIE_AFF, hie_affinity_kernel<1>, grid, block, lds, s, g); break;
-    default: VQF_LAUNCH(KID_HIE_AFF, hie_affinity_kernel<2>, grid, block, lds, s, g); break;
-  }
-  return vqf_last_error();
+  return affinity_launch(KID_HIE_AFF, g, 1, epi, true, (hipStream_t)stream);
+}
+
+int vqf_hie_affinity_levels_supported(int N, int L, int E, int T, int G, int pairs) { return affinity_shape_ok(N, L, E, T, G, pairs); }
+
+int vqf_hie_affinity_levels(const float* x1, int ldx1, int ldx_level1, const float* y1, int ldy1, int ldy_level1,
+                            const float* x2, int ldx2, int ldx_level2, const float* y2, int ldy2, int ldy_level2,
+                            int G, int epi, const float* yprev, int N, int L, int E, int T, float* out, void* stream) {
+  AffArgs g = {};
+  g.x1 = x1; g.ldx1 = ldx1; g.lvx1 = ldx_level1; g.y1 = y1; g.ldy1 = ldy1; g.lvy1 = ldy_level1;
+  g.x2 = x2; g.ldx2 = ldx2; g.lvx2 = ldx_level2; g.y2 = y2; g.ldy2 = ldy2; g.lvy2 = ldy_level2;
+  g.yprev = yprev; g.out = out; g.N = N; g.L = L; g.E = E; g.T = T;
+  return affinity_launch(KID_HIE_AFF_LEVELS, g, G, epi, false, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -745,6 +745,49 @@ class AttPoolFn(torch.autograd.Function):
         return (dx if ctx.needs_input_grad[0] else None), dfeat, dw.view_as(w), db, None
 
 
+def _hie_hv_ti(Vh, C, Qh, drop, N, L, T, Hv, ti, stream):
+    """One co-attention level's image side: Hv = dropout(tanh(Vh + C^T Qh)) and the T-row sums ti = C Vh, written into Hv
+    (N*L, E) and ti (N*T, E).  Vh, Hv, Qh may be column blocks of wider buffers; C (N, T, L).  stream: ONE pass over Vh
+    (csrc/hie.hip) -- one workgroup per sample writes the final sums; small batches cut a sample into S chunks whose
+    partial slabs a second launch sums.  Otherwise the batched-GEMM form."""
+    E = Vh.shape[1]
+    if stream:
+        S = ops.hie_chunks(N, L)
+        if S == 1:
+            ops.hie_hv_fwd(Vh, C, Qh, drop, N, L, T, Hv, ti)
+        else:
+            part = torch.empty((S, N * T, E), dtype=torch.float32, device=Vh.device)
+            ops.hie_hv_fwd(Vh, C, Qh, drop, N, L, T, Hv, part)
+            ops.hie_slab_sum(part, ti)
+    else:
+        tq = ops.bgemm(C, Qh.view(N, T, E), ta=True, tb=True).view(N * L, E)                # C^T Qh
+        ops.tanh_dropout_fwd2d(Vh, tq, *drop, out=Hv)
+        ops.bgemm(C, Vh.view(N, L, E), ta=False, tb=True, out=ti.view(N, T, E))             # C Vh
+
+
+def _hie_dc(dti, Vh, Qh, dtq, C, drop, N, L, T, aff, out=None):
+    """One level's gradient of the affinity's pre-activation: (dti Vh^T + Qh dtq^T) through the backward of
+    C = dropout(tanh(.)), (N, T, L).  aff: ONE pass over Vh and dtq (vqf_hie_affinity, two pairs); otherwise two batched
+    products and the element-wise backward.  Reads dtq: call it before dtq is updated in place."""
+    if aff:
+        return ops.hie_affinity(dti, Vh, N, L, T, x2=Qh, y2=dtq, epi=2, yprev=C, drop=drop, out=out)
+    E = Vh.shape[1]
+    dC = ops.bgemm(dti.view(N, T, E), Vh.view(N, L, E), out=out)
+    ops.bgemm(Qh.view(N, T, E), dtq.view(N, L, E), out=dC, accumulate=True)
+    ops.tanh_dropout_bwd(dC.view(N * T, L), C.view(N * T, L), *drop, out=dC.view(N * T, L))
+    return dC
+
+
+def _hie_bwd_bgemm(C, dC, dti, dtq, V, Cq, dQh, dCq, dV, N, L, T, dv_accumulate):
+    """The batched-GEMM form of one level's remaining backward products (the streaming passes' A/B partner):
+    dQh += C dtq;  dtq += C^T dti (in place: dtq becomes dVh);  dCq = dC V;  dV = (dV +) dC^T Cq."""
+    E = V.shape[1]
+    ops.bgemm(C, dtq.view(N, L, E), ta=False, tb=True, out=dQh.view(N, T, E), accumulate=True)
+    ops.bgemm(C, dti.view(N, T, E), ta=True, tb=True, out=dtq.view(N, L, E), accumulate=True)
+    ops.bgemm(dC, V.view(N, L, E), ta=False, tb=True, out=dCq.view(N, T, E))
+    ops.bgemm(dC, Cq.view(N, T, E), ta=True, tb=True, out=dV.view(N, L, E), accumulate=dv_accumulate)
+
+
 class HieCoreFn(torch.autograd.Function):
     """HieCoAtten's ladder from the raw inputs to cat((v, q), 0).view(N, -1) (hieCoAtten.py:25-53) as ONE autograd node with a
     hand-ordered backward, so that
@@ -788,31 +831,17 @@ class HieCoreFn(torch.autograd.Function):
                         (_c(wbv), Wq2[:E]), (_c(wq), Wq2[E:]), (bbv, bq2[:E]), (bq, bq2[E:])])
         CI = ops.gemm_rows(img, Wi, L, bias=bi)               # (M, 2E)  = [Cv | img_]
         CQ = ops.gemm(que, Wq2, bias=bq2)                     # (MT, 2E) = [Cq | que_]
-        Cv3, img_3 = CI[:, :E].view(N, L, E), CI[:, E:].view(N, L, E)
-        Cq3, que_3 = CQ[:, :E].view(N, T, E), CQ[:, E:].view(N, T, E)
         # :32-33  C = dropout(tanh(Cq Cv^T))   (N,T,L)
         stream = HieCoreFn.STREAM and ops.hie_stream_supported(N, L, E, T)
         aff = stream and HieCoreFn.AFFINITY and ops.hie_affinity_supported(N, L, E, T, 2)
         if aff:                  # one pass over Cv on 16x16x4 MFMAs, tanh + dropout in its epilogue (csrc/hie.hip)
             C3 = ops.hie_affinity(CQ[:, :E], CI[:, :E], N, L, T, epi=1, drop=drops["C"])
         else:
-            C3 = ops.bgemm(Cq3, Cv3)
+            C3 = ops.bgemm(CQ[:, :E].view(N, T, E), CI[:, :E].view(N, L, E))
             ops.tanh_dropout_fwd(C3.view(MT, L), None, *drops["C"], out=C3.view(MT, L))
         # :38-42  Hv = dropout(tanh(img_ + C^T que_)), av = softmax_L(Whv Hv), v = av^T img;  :45  ti = C img_
-        if stream:
-            # ONE pass over img_: the rank-T update, tanh, dropout, and the T-row sums of ti in registers (csrc/hie.hip)
-            S = ops.hie_chunks(N, L)
-            if S == 1:           # one workgroup per sample: the T-row sums are final, no partial slabs, no slab-sum launch
-                ti = new(MT, E)
-                Hv = ops.hie_hv_fwd(CI[:, E:], C3, CQ[:, E:], drops["Hv"], N, L, T, new(M, E), ti)
-            else:
-                part = new(S, MT, E)
-                Hv = ops.hie_hv_fwd(CI[:, E:], C3, CQ[:, E:], drops["Hv"], N, L, T, new(M, E), part)
-                ti = ops.hie_slab_sum(part, new(MT, E))
-        else:
-            tq = ops.bgemm(C3, que_3, ta=True, tb=True).view(M, E)
-            Hv = ops.tanh_dropout_fwd2d(CI[:, E:], tq, *drops["Hv"], out=tq)
-            ti = ops.bgemm(C3, img_3, ta=False, tb=True).view(MT, E)
+        Hv, ti = new(M, E), new(MT, E)
+        _hie_hv_ti(CI[:, E:], C3, CQ[:, E:], drops["Hv"], N, L, T, Hv, ti, stream)
         xcat = new(2 * N, E)
         av, _ = ops.glimpse_pool_fwd(img.view(N, L, E), ops.att_logits_fwd(Hv, _w2d(whv), bhv), False, pooled_out=xcat[:N])
         # :45-49  Hq = dropout(tanh(que_ + C img_)), aq = softmax_T(Whq Hq), q = aq^T que
@@ -837,8 +866,6 @@ class HieCoreFn(torch.autograd.Function):
             dx = torch.zeros((N, 2 * E), dtype=torch.float32, device=dev)
         dxcat = _c(dx).view(2 * N, E)
         dv, dq = dxcat[:N], dxcat[N:]
-        Cv3, img_3 = CI[:, :E].view(N, L, E), CI[:, E:].view(N, L, E)
-        Cq3, que_3 = CQ[:, :E].view(N, T, E), CQ[:, E:].view(N, T, E)
         dCI, dCQ = new(M, 2 * E), new(MT, 2 * E)              # [dCv | dimg_], [dCq | dque_]
         # question-side head: q = aq^T que, aq = softmax(Whq Hq), Hq = dropout(tanh(que_ + ti))
         dlq, dque = ops.glimpse_pool_bwd(dq, que.view(N, T, E), aq, False, True, dwts=None if daq is None else _c(daq))
@@ -848,7 +875,6 @@ class HieCoreFn(torch.autograd.Function):
         dti = ops.tanh_dropout_bwd2d(dHq, Hq, *drops["Hq"], out=dHq)           # ... and, untouched by the sums below, dti (7 MB)
         # image-side head
         dlv, _ = ops.glimpse_pool_bwd(dv, img.view(N, L, E), av, False, False, dwts=None if dav is None else _c(dav))
-        dti3, dtq3 = dti.view(N, T, E), dCI[:, E:].view(N, L, E)
         if ctx.stream:
             # dtq = d(img_ + tq) straight from the logit gradient (dHv = dlv (x) whv is never written), C dtq and dlv^T Hv on the way
             S = ops.hie_chunks(N, L)
@@ -860,17 +886,12 @@ class HieCoreFn(torch.autograd.Function):
                 ops.hie_head_bwd(Hv, dlv.view(M), whv.view(E), C3, drops["Hv"], N, L, T, dCI[:, E:], dCQ[:, E:], wpart, part_add=dti)
             else:
                 ops.hie_head_bwd(Hv, dlv.view(M), whv.view(E), C3, drops["Hv"], N, L, T, dCI[:, E:], part, wpart)
-            if ctx.aff:          # dC = dti img_^T + que_ dtq^T and the backward of C = dropout(tanh(.)) in ONE pass over img_ and dtq
-                dC3 = ops.hie_affinity(dti, CI[:, E:], N, L, T, x2=CQ[:, E:], y2=dCI[:, E:], epi=2, yprev=C3, drop=drops["C"])
-            else:
-                dC3 = ops.bgemm(dti3, img_3)                                       # dC = dti img_^T + que_ dtq^T
-                ops.bgemm(que_3, dtq3, out=dC3, accumulate=True)
+            # dC = dti img_^T + que_ dtq^T and the backward of C = dropout(tanh(Cq Cv^T))
+            dC3 = _hie_dc(dti, CI[:, E:], CQ[:, E:], dCI[:, E:], C3, drops["C"], N, L, T, ctx.aff)
             if S > 1:
                 ops.hie_slab_sum(part, dCQ[:, E:], add=dti)                        # dque_ = dti + C dtq
             ops.hie_rank_add(dCI[:, E:], C3, dti, N, L, T, dCI[:, E:], colpart=cpart[:, E:2 * E])      # dimg_ = dtq + C^T dti (dtq's own uses are above)
-            # C = dropout(tanh(Cq Cv^T)):  dCv = daff^T Cq,  dCq = daff Cv   (one pass over Cv)
-            if not ctx.aff:
-                ops.tanh_dropout_bwd(dC3.view(MT, L), C3.view(MT, L), *drops["C"], out=dC3.view(MT, L))
+            # dCv = dC^T Cq,  dCq = dC Cv   (one pass over Cv)
             if S == 1:
                 ops.hie_rank_left(dC3, CQ[:, :E], CI[:, :E], N, L, T, dCI[:, :E], dCQ[:, :E], colpart=cpart[:, :E])      # dCq straight into its column block
             else:
@@ -880,15 +901,10 @@ class HieCoreFn(torch.autograd.Function):
             dHv, dwhv, dbhv, _ = ops.att_logits_bwd(dlv, Hv, _w2d(whv), relu_mask=False)
             ops.tanh_dropout_bwd2d(dHv, Hv, *drops["Hv"], out=dCI[:, E:])          # d(img_ + tq), first term of dimg_
             del dHv
-            # tq = C^T que_, ti = C img_:  dC = dti img_^T + que_ dtq^T;  dque_ += C dtq;  dimg_ += C^T dti
-            dC3 = ops.bgemm(dti3, img_3)
-            ops.bgemm(que_3, dtq3, out=dC3, accumulate=True)
-            ops.bgemm(C3, dtq3, ta=False, tb=True, out=dCQ[:, E:].view(N, T, E), accumulate=True)
-            ops.bgemm(C3, dti3, ta=True, tb=True, out=dtq3, accumulate=True)       # (dtq's own uses are above this line)
-            # C = dropout(tanh(Cq Cv^T)):  dCq = daff Cv,  dCv = daff^T Cq
-            ops.tanh_dropout_bwd(dC3.view(MT, L), C3.view(MT, L), *drops["C"], out=dC3.view(MT, L))
-            ops.bgemm(dC3, Cv3, ta=False, tb=True, out=dCQ[:, :E].view(N, T, E))
-            ops.bgemm(dC3, Cq3, ta=True, tb=True, out=dCI[:, :E].view(N, L, E))
+            # tq = C^T que_, ti = C img_, C = dropout(tanh(Cq Cv^T)):  dC, then dque_ += C dtq;  dimg_ += C^T dti;  dCq = dC Cv;
+            # dCv = dC^T Cq
+            dC3 = _hie_dc(dti, CI[:, E:], CQ[:, E:], dCI[:, E:], C3, drops["C"], N, L, T, False)
+            _hie_bwd_bgemm(C3, dC3, dti, dCI[:, E:], CI[:, :E], CQ[:, :E], dCQ[:, E:], dCQ[:, :E], dCI[:, :E], N, L, T, False)
         # the concatenated layers: one input-gradient product (K = 2E), one weight-gradient product and one column sum per side
         dimg = ops.gemm_rows(dCI, Wi, L, tb=True)                              # (M, E); the pool's rank-1 term is added below
         ops.gemm(dCQ, Wq2, tb=True, out=dque.view(MT, E), accumulate=True)     # on top of the pool's gradient into que

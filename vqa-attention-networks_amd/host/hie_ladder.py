@@ -33,7 +33,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .functions import _c, EmbedTanhFn, LinearFn, DropoutFn, TanhDropFn, DropoutBTFn, LstmBatchFn
+from .functions import _c, _hie_hv_ti, _hie_dc, _hie_bwd_bgemm, EmbedTanhFn, LinearFn, DropoutFn, TanhDropFn, DropoutBTFn, LstmBatchFn
 from .lib import VqfError
 from .mfb import _DropSeeds
 
@@ -114,21 +114,9 @@ class LadderCoattFn(torch.autograd.Function):
             ops.tanh_dropout_fwd(C.view(3 * MT, L), None, *_NODROP, out=C.view(3 * MT, L))
         Hv = new(M, 3 * E)
         Hq = new(3, MT, E)                                                          # ti_i first, then Hq_i in place
-        S = ops.hie_chunks(N, L) if stream else 1
-        part = new(S, MT, E) if stream and S > 1 else None
         for g in range(3):
-            Vh_g, Qh_g, Hv_g, ti_g = (Vh[:, g * E:(g + 1) * E], CQ[:, (2 * g + 1) * E:(2 * g + 2) * E], Hv[:, g * E:(g + 1) * E],
-                                      Hq[g])
-            if stream:
-                if part is None:
-                    ops.hie_hv_fwd(Vh_g, C[g], Qh_g, _NODROP, N, L, T, Hv_g, ti_g)
-                else:
-                    ops.hie_hv_fwd(Vh_g, C[g], Qh_g, _NODROP, N, L, T, Hv_g, part)
-                    ops.hie_slab_sum(part, ti_g)
-            else:
-                tq = ops.bgemm(C[g], Qh_g.view(N, T, E), ta=True, tb=True).view(M, E)      # C^T Qh
-                ops.tanh_dropout_fwd2d(Vh_g, tq, *_NODROP, out=Hv_g)
-                ops.bgemm(C[g], Vh_g.view(N, L, E), ta=False, tb=True, out=ti_g.view(N, T, E))   # C Vh
+            Qh_g, ti_g = CQ[:, (2 * g + 1) * E:(2 * g + 2) * E], Hq[g]
+            _hie_hv_ti(Vh[:, g * E:(g + 1) * E], C[g], Qh_g, _NODROP, N, L, T, Hv[:, g * E:(g + 1) * E], ti_g, stream)
             ops.tanh_dropout_fwd2d(Qh_g, ti_g, *_NODROP, out=ti_g)
         av, vcat = ops.glimpse_pool_fwd(V.view(N, L, E), ops.att_logits_fwd(Hv, wblk, zb3), False)   # (N, 3, L), (N, 3E)
         aq, qo = [], []
@@ -176,16 +164,11 @@ class LadderCoattFn(torch.autograd.Function):
         dC = new(3, N, T, L)
         if stream and ops.hie_affinity_levels_supported(N, L, E, T, 3, 2):
             ops.hie_affinity_levels(dti, E, Vh, E, 3, N, L, T, E, x2=CQ[:, E:], lvx2=2 * E, y2=dVh, lvy2=E, epi=2, yprev=C, out=dC)
-        elif stream and ops.hie_affinity_supported(N, L, E, T, 2):                  # (E = 512: three levels x two pairs exceed the LDS)
+        else:                      # per level (E = 512: three levels x two pairs exceed the LDS: one two-pair launch each)
+            aff = stream and ops.hie_affinity_supported(N, L, E, T, 2)
             for g in range(3):
-                ops.hie_affinity(dti[:, g * E:(g + 1) * E], Vh[:, g * E:(g + 1) * E], N, L, T, x2=CQ[:, (2 * g + 1) * E:(2 * g + 2) * E],
-                                 y2=dVh[:, g * E:(g + 1) * E], epi=2, yprev=C[g], out=dC[g])
-        else:
-            for g in range(3):
-                ops.bgemm(dti[:, g * E:(g + 1) * E].view(N, T, E), Vh[:, g * E:(g + 1) * E].view(N, L, E), out=dC[g])
-                ops.bgemm(CQ[:, (2 * g + 1) * E:(2 * g + 2) * E].view(N, T, E), dVh[:, g * E:(g + 1) * E].view(N, L, E),
-                          out=dC[g], accumulate=True)
-            ops.tanh_dropout_bwd(dC.view(3 * MT, L), C.view(3 * MT, L), *_NODROP, out=dC.view(3 * MT, L))
+                _hie_dc(dti[:, g * E:(g + 1) * E], Vh[:, g * E:(g + 1) * E], CQ[:, (2 * g + 1) * E:(2 * g + 2) * E],
+                        dVh[:, g * E:(g + 1) * E], C[g], _NODROP, N, L, T, aff, out=dC[g])
         if stream:
             S = ops.hie_chunks(N, L)
             part, scratch = new(S, MT, E), new(M, E)
@@ -201,10 +184,7 @@ class LadderCoattFn(torch.autograd.Function):
                 ops.hie_slab_sum(part, dcq_g)
                 ops.hie_rank_add(dV, dC[g], cq_g, N, L, T, dV)                      # dV += dC^T Cq   (in place)
             else:
-                ops.bgemm(C[g], dtq_g.view(N, L, E), ta=False, tb=True, out=dqh_g.view(N, T, E), accumulate=True)
-                ops.bgemm(C[g], dti_g.view(N, T, E), ta=True, tb=True, out=dtq_g.view(N, L, E), accumulate=True)
-                ops.bgemm(dC[g], V.view(N, L, E), ta=False, tb=True, out=dcq_g.view(N, T, E))
-                ops.bgemm(dC[g], cq_g.view(N, T, E), ta=True, tb=True, out=dV.view(N, L, E), accumulate=True)
+                _hie_bwd_bgemm(C[g], dC[g], dti_g, dtq_g, V, cq_g, dqh_g, dcq_g, dV, N, L, T, True)
         # the concatenated layers: dV += dVh [Wv_0; Wv_1; Wv_2], one weight-gradient product; per level the [Wb; Wq] pair
         ops.gemm(dVh, wv_cat, tb=True, out=dV, accumulate=True)
         dwv = ops.gemm(dVh, V, ta=True, tb=True)                                   # (3E, E)

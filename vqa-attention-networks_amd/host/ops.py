@@ -5,6 +5,7 @@ HIP stream; all arithmetic happens in libvqa_fusion.so.  There is no CPU
 fallback -- a CPU tensor raises.
 """
 import ctypes
+import math
 import torch
 
 from . import lib as _l
@@ -632,22 +633,34 @@ def hie_affinity_supported(N, L, E, T, pairs=1):
     return bool(_lib().vqf_hie_affinity_supported(int(N), int(L), int(E), int(T), int(pairs)))
 
 
+def _aff_operands(name, x1, y1, x2, y2, yprev, out, dims):
+    """The operand checks of hie_affinity / hie_affinity_levels: x* 2-D with N*T rows, y* with N*L rows (rows may be strided);
+    out (allocated here when None) and yprev contiguous with the elements of dims = (..., N, T, L).
+    -> (out, row pitch of x2, row pitch of y2)"""
+    _chk2s(x1, y1, x2, y2)
+    N, T, L = dims[-3:]
+    if x1.shape[0] != N * T or y1.shape[0] != N * L or (x2 is not None and (x2.shape[0] != N * T or y2.shape[0] != N * L)):
+        raise _l.VqfError(name + ": operand shapes")
+    if out is None:
+        out = torch.empty(dims, dtype=torch.float32, device=x1.device)
+    _chk(out, yprev)
+    numel = math.prod(dims)
+    if out.numel() != numel or (yprev is not None and yprev.numel() != numel):
+        raise _l.VqfError(name + ": out / yprev must hold %s" % (dims,))
+    return out, (x2.stride(0) if x2 is not None else 0), (y2.stride(0) if y2 is not None else 0)
+
+
 def hie_affinity(x1, y1, N, L, T, x2=None, y2=None, epi=0, yprev=None, drop=(None, 0, 0.0), out=None):
     """out (N, T, L) = epi(x1 y1^T [+ x2 y2^T]) per sample: x* rows n*T + t, y* rows n*L + l (2-D, rows may be strided).
     epi 0: the sums; 1: dropout(tanh(.)) with `drop` = (keep | None, seed, p); 2: the backward of epi 1 given its output yprev."""
-    _chk2s(x1, y1, x2, y2)
+    out, sx2, sy2 = _aff_operands("hie_affinity", x1, y1, x2, y2, yprev, out, (N, T, L))
     E = x1.shape[1]
-    if x1.shape[0] != N * T or y1.shape != (N * L, E) or (x2 is not None and (x2.shape != x1.shape or y2.shape != y1.shape)):
+    if y1.shape[1] != E or (x2 is not None and (x2.shape[1] != E or y2.shape[1] != E)):
         raise _l.VqfError("hie_affinity: operand shapes")
-    if out is None:
-        out = torch.empty((N, T, L), dtype=torch.float32, device=x1.device)
-    _chk(out)
-    if yprev is not None:
-        _chk_ntl(yprev, N, T, L)
     keep, seed, p = drop
-    _l.check(_lib().vqf_hie_affinity(_ptr(x1), x1.stride(0), _ptr(y1), y1.stride(0), _ptr(x2), x2.stride(0) if x2 is not None else 0,
-                                     _ptr(y2), y2.stride(0) if y2 is not None else 0, int(epi), _ptr(yprev), _keep_ptr(keep),
-                                     int(seed), float(p), N, L, E, T, _ptr(out), _stream()), "vqf_hie_affinity")
+    _l.check(_lib().vqf_hie_affinity(_ptr(x1), x1.stride(0), _ptr(y1), y1.stride(0), _ptr(x2), sx2, _ptr(y2), sy2, int(epi),
+                                     _ptr(yprev), _keep_ptr(keep), int(seed), float(p), N, L, E, T, _ptr(out), _stream()),
+             "vqf_hie_affinity")
     return out
 
 
@@ -662,7 +675,8 @@ def hie_slab_sum(part, out, add=None):
 
 
 # ---------------------------------------------------------------------------
-# the word / phrase / sentence ladder (csrc/hie_ladder.hip; include/vqa_fusion.h vqf_phrase_ngram_*, vqf_hie_affinity_levels)
+# the word / phrase / sentence ladder (csrc/hie_ladder.hip, the affinity in csrc/hie.hip; include/vqa_fusion.h vqf_phrase_ngram_*,
+# vqf_hie_affinity_levels)
 def phrase_ngram_supported(T, E):
     return bool(_lib().vqf_phrase_ngram_supported(int(T), int(E)))
 
@@ -705,17 +719,7 @@ def hie_affinity_levels(x1, lvx1, y1, lvy1, G, N, L, T, E, x2=None, lvx2=0, y2=N
     """out (G, N, T, L): level g = epi(X1_g Y1_g^T [+ X2_g Y2_g^T]) per sample, X_g = the E columns of x at offset g * lvx (rows
     n*T + t), Y_g those of y at g * lvy (rows n*L + l; lvy = 0: one y shared by the levels).  2-D operands, rows may be strided.
     epi 0: the sums; 1: tanh; 2: sums * (1 - yprev^2)."""
-    _chk2s(x1, y1, x2, y2)
-    if x1.shape[0] != N * T or y1.shape[0] != N * L or (x2 is not None and (x2.shape[0] != N * T or y2.shape[0] != N * L)):
-        raise _l.VqfError("hie_affinity_levels: operand shapes")
-    if out is None:
-        out = torch.empty((G, N, T, L), dtype=torch.float32, device=x1.device)
-    _chk(out)
-    if out.numel() != G * N * T * L or (yprev is not None and yprev.numel() != G * N * T * L):
-        raise _l.VqfError("hie_affinity_levels: out / yprev must hold (G, N, T, L)")
-    _chk(yprev)
-    sx2 = x2.stride(0) if x2 is not None else 0
-    sy2 = y2.stride(0) if y2 is not None else 0
+    out, sx2, sy2 = _aff_operands("hie_affinity_levels", x1, y1, x2, y2, yprev, out, (G, N, T, L))
     _l.check(_lib().vqf_hie_affinity_levels(_ptr(x1), x1.stride(0), int(lvx1), _ptr(y1), y1.stride(0), int(lvy1),
                                             _ptr(x2), sx2, int(lvx2), _ptr(y2), sy2, int(lvy2), int(G), int(epi), _ptr(yprev),
                                             int(N), int(L), int(E), int(T), _ptr(out), _stream()), "vqf_hie_affinity_levels")
