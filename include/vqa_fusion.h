@@ -487,6 +487,45 @@ int vqf_hie_affinity_levels(const float* x1, int ldx1, int ldx_level1, const flo
                             const float* x2, int ldx2, int ldx_level2, const float* y2, int ldy2, int ldy_level2,
                             int G, int epi, const float* yprev, int N, int L, int E, int T, float* out, void* stream);
 
+/* Question lengths for HieCoAttenLadder (host/hie_ladder.py): the *_len forms of the passes that stream the ladder's (N*T, .)
+ * and (N, T, L) tensors.  lens (N) int32 on the device, 4-byte aligned: lens[n] = the real words of sample n, positions
+ * t >= lens[n] of its T are padding (values outside [1, T] act as 1 and T where a kernel clamps; the host clamps them before).
+ * Each runs the kernel of its unmasked form with the row test added (same launch shape, same profiler slot) and gives that
+ * form's bits when every length is T.  lens = NULL: VQF_E_BADARG (call the unmasked form).
+ *   embed_tanh_fwd_len  ids (N, Tq): out rows of padded tokens are zero whatever the id;
+ *   embed_tanh_bwd_len  padded tokens add to no row of dW (a padding id that occurs nowhere else gets an exact zero row);
+ *   phrase_ngram_fwd_len  the window of t stops at lens[n] (u_k[t] sums j < k, t + j < lens[n]); padded rows: Qp = 0, idx = 3;
+ *   phrase_ngram_bwd_len  padded rows of dZ are zero, nothing read from padded rows of dQp;
+ *   dropout_bt_len      rows (b, t >= lens[b]) of y are zero, x unread there (the re-layout after the sentence LSTM, and its
+ *                       backward with the strides swapped);
+ *   glimpse_pool_fwd_len  softmax over s < lens[n] only, wts exactly 0 beyond, pooled sums the real rows;
+ *   glimpse_pool_bwd_len  dlogits and dfeat rows of padded positions are zero, dwts_extra unread there;
+ *   hie_affinity_len / hie_affinity_levels_len  out rows t >= lens[n] are zero after the epilogue (dC of padded question rows);
+ *   tanh_bwd_rows_len   dx = dy (1 - y^2) on the real rows of a contiguous (N, T, L) tensor, 0 on the padded ones
+ *                       (N * T * L % 4 == 0; in place allowed): the ladder's dC on the batched-GEMM route (T > 16). */
+int vqf_embed_tanh_fwd_len(const float* W, const long long* ids, const int* lens, int N, int Tq, int V, int E, float* out,
+                           void* stream);
+int vqf_embed_tanh_bwd_len(const float* dout, const float* out, const long long* ids, const int* lens, int N, int Tq, int V, int E,
+                           float* dW, void* stream);
+int vqf_phrase_ngram_fwd_len(const float* Z, int ldz, const float* bias, const int* lens, int N, int T, int E, float* Qp, int ldq,
+                             uint8_t* idx, void* stream);
+int vqf_phrase_ngram_bwd_len(const float* dQp, int ldd, const float* Qp, int ldq, const uint8_t* idx, const int* lens, int N, int T,
+                             int E, float* dZ, int ldz, void* stream);
+int vqf_dropout_bt_len(const float* x, long long sb_in, long long st_in, const uint8_t* keep, uint64_t seed, float p_drop,
+                       const int* lens, int B, int T, int H, float* y, long long sb_out, long long st_out, void* stream);
+int vqf_glimpse_pool_fwd_len(const float* feat, const float* logits, const int* lens, int N, int S, int C, int G,
+                             int unit_softmax, float* wts, float* pooled, void* stream);
+int vqf_glimpse_pool_bwd_len(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* lens,
+                             int N, int S, int C, int G, int unit_softmax, float* dlogits, float* dfeat, void* stream);
+int vqf_hie_affinity_len(const float* x1, int ldx1, const float* y1, int ldy1, const float* x2, int ldx2, const float* y2, int ldy2,
+                         int epi, const float* yprev, const uint8_t* keep, uint64_t seed, float p_drop, const int* lens, int N, int L,
+                         int E, int T, float* out, void* stream);
+int vqf_hie_affinity_levels_len(const float* x1, int ldx1, int ldx_level1, const float* y1, int ldy1, int ldy_level1,
+                                const float* x2, int ldx2, int ldx_level2, const float* y2, int ldy2, int ldy_level2,
+                                int G, int epi, const float* yprev, const int* lens, int N, int L, int E, int T, float* out,
+                                void* stream);
+int vqf_tanh_bwd_rows_len(const float* dy, const float* y, const int* lens, int N, int T, int L, float* dx, void* stream);
+
 /* softmax over the last axis of (R,W) and its backward   modules.py:91-92 */
 int vqf_softmax_rows_fwd(const float* x, int R, int W, float* y, void* stream);
 int vqf_softmax_rows_bwd(const float* dy, const float* y, int R, int W, float* dx, void* stream);

@@ -1,10 +1,12 @@
 """Train step of HieCoAttenLadder (host/hie_ladder.py) at config 4's shapes: forward, CE loss, backward, the project's Adam.
 
-    python tools/hie_ladder_bench.py [--batch 256] [--steps 20] [--warmup 5] [--json OUT]
+    python tools/hie_ladder_bench.py [--batch 256] [--steps 20] [--warmup 5] [--lengths] [--json OUT]
 
 Prints ms / step and QA pairs / s (device events around the timed steps), the step's FLOP count from the shapes with its
 MFMA floor at 157.3 TF/s (fp32 MFMA peak of the MI355X) and the fraction reached, the library profiler's per-kernel table
-of one extra step, and config 4's single-level HieCoAtten at the same shapes in the same process for context."""
+of one extra step, and config 4's single-level HieCoAtten at the same shapes in the same process for context.
+--lengths: the masked step, forward(img, ids, q_length) with seeded question lengths in [3, T] (the products stay dense N*T
+rows: the FLOP count is the unmasked step's)."""
 import argparse
 import json
 import os
@@ -36,13 +38,13 @@ def ladder_flops(N, L, D, E, T, H, O):
     return f, sum(f.values())
 
 
-def timed(model, img, ids, target, steps, warmup):
+def timed(model, img, ids, target, steps, warmup, q_len=None):
     crit = vqa_amd.CrossEntropyLoss()
     opt = vqa_amd.Adam(model.parameters(), lr=1e-4)
 
     def step():
         opt.zero_grad(set_to_none=True)
-        out = model(img, ids)
+        out = model(img, ids) if q_len is None else model(img, ids, q_len)
         loss = crit(out[0], target)
         loss.backward()
         opt.step()
@@ -71,6 +73,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--lengths", action="store_true", help="time the masked step: seeded question lengths in [3, T]")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     N, L, D, E, T, H, O, V = a.batch, 196, 2048, 512, 14, 1024, 1000, 15881
@@ -81,10 +84,14 @@ def main():
     target = torch.randint(0, O, (N,), device=dev)
     ladder = vqa_amd.HieCoAttenLadder(block_num=L, word_num=T, img_size=D, vocab_size=V, embed_size=E, hidden_size=H,
                                       output_size=O).to(dev).train()
-    ms, kern = timed(ladder, img, ids, target, a.steps, a.warmup)
+    q_len = None
+    if a.lengths:
+        q_len = torch.randint(3, T + 1, (N,), generator=torch.Generator().manual_seed(1)).to(dev)
+    ms, kern = timed(ladder, img, ids, target, a.steps, a.warmup, q_len)
     parts, flops = ladder_flops(N, L, D, E, T, H, O)
     floor_ms = flops / (PEAK_TFS * 1e12) * 1e3
-    print("HieCoAttenLadder train step  B=%d L=%d img=%d E=%d T=%d hidden=%d out=%d" % (N, L, D, E, T, H, O))
+    print("HieCoAttenLadder train step  B=%d L=%d img=%d E=%d T=%d hidden=%d out=%d%s"
+          % (N, L, D, E, T, H, O, "  question lengths in [3, %d], mean %.1f" % (T, float(q_len.float().mean())) if a.lengths else ""))
     print("  %.3f ms/step   %.0f QA pairs/s" % (ms, N / ms * 1e3))
     print("  %.3f TFLOP/step:" % (flops / 1e12))
     for k, v in parts.items():
@@ -100,7 +107,7 @@ def main():
     print("config 4 HieCoAtten (word level only) at the same shapes: %.3f ms/step   %.0f QA pairs/s" % (ms4, N / ms4 * 1e3))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        json.dump({"ms_per_step": ms, "qa_per_s": N / ms * 1e3, "tflop_per_step": flops / 1e12, "floor_ms": floor_ms,
+        json.dump({"lengths": bool(a.lengths), "ms_per_step": ms, "qa_per_s": N / ms * 1e3, "tflop_per_step": flops / 1e12, "floor_ms": floor_ms,
                    "fraction_of_floor": floor_ms / ms, "kernels": kern, "hiecoatten_ms_per_step": ms4}, open(a.json, "w"), indent=1)
 
 

@@ -206,29 +206,40 @@ template <> __device__ __forceinline__ f32x4 load4<__bf16>(const __bf16* p) {
 }
 
 // ---- softmax over S + G glimpse sums ---------------------------------------------------------
+// lens (vqf_glimpse_pool_fwd_len / _bwd_len; N int32, null: all S): the softmax of sample n runs over its first lens[n]
+// positions only (maximum, sum and weighted rows: a padded position enters none of them, so there is no inf - inf); the
+// weights beyond are exact zeros, and so are their dlogits and dfeat rows in the backward.
+__device__ __forceinline__ int pool_len(const int* __restrict__ lens, int n, int S) {
+  if (!lens) return S;
+  const int len = lens[n];
+  return len < 1 ? 1 : (len > S ? S : len);
+}
+
 // grid (ceil(C/1024), N); thread = 4 consecutive channels
 template <int G, typename FT>
 __global__ void glimpse_pool_fwd_kernel(const FT* __restrict__ feat,
                                         const float* __restrict__ logits, int N, int S, int C,
                                         int unit, float* __restrict__ wts,
-                                        float* __restrict__ pooled) {
+                                        float* __restrict__ pooled, const int* __restrict__ lens) {
   __shared__ float w[G][MAXS];
   const int n = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int Sv = pool_len(lens, n, S);                // (uniform) the sample's real positions
   if (wave < G) {
     const int g = wave;
     const float* lg = logits + (long long)n * S * G + g;
     if (unit) {
-      for (int s = lane; s < S; s += 64) w[g][s] = 1.0f;
+      for (int s = lane; s < S; s += 64) w[g][s] = s < Sv ? 1.0f : 0.f;
     } else {
       float mx = -INFINITY;
-      for (int s = lane; s < S; s += 64) mx = fmaxf(mx, lg[G * s]);
+      for (int s = lane; s < Sv; s += 64) mx = fmaxf(mx, lg[G * s]);
       mx = wave_max(mx);
       float sum = 0.f;
-      for (int s = lane; s < S; s += 64) { const float e = expf(lg[G * s] - mx); w[g][s] = e; sum += e; }
+      for (int s = lane; s < Sv; s += 64) { const float e = expf(lg[G * s] - mx); w[g][s] = e; sum += e; }
       sum = wave_sum(sum);
       const float rs = 1.0f / sum;
-      for (int s = lane; s < S; s += 64) w[g][s] *= rs;
+      for (int s = lane; s < Sv; s += 64) w[g][s] *= rs;
+      for (int s = Sv + lane; s < S; s += 64) w[g][s] = 0.f;
     }
   }
   __syncthreads();
@@ -246,7 +257,7 @@ __global__ void glimpse_pool_fwd_kernel(const FT* __restrict__ feat,
   if (vec) {
     int s = 0;
     // VQF_GLIMPSE_FWD_ROWS rows per trip, every load issued before the first is consumed (the sums keep the row order: same bits)
-    for (; s + VQF_GLIMPSE_FWD_ROWS - 1 < S; s += VQF_GLIMPSE_FWD_ROWS) {
+    for (; s + VQF_GLIMPSE_FWD_ROWS - 1 < Sv; s += VQF_GLIMPSE_FWD_ROWS) {
       f32x4 x[VQF_GLIMPSE_FWD_ROWS];
 #pragma unroll
       for (int u = 0; u < VQF_GLIMPSE_FWD_ROWS; ++u) x[u] = load4<FT>(f + (long long)(s + u) * C);
@@ -256,7 +267,7 @@ __global__ void glimpse_pool_fwd_kernel(const FT* __restrict__ feat,
         for (int u = 0; u < VQF_GLIMPSE_FWD_ROWS; ++u) a[g] += x[u] * w[g][s + u];
       }
     }
-    for (; s < S; ++s) {
+    for (; s < Sv; ++s) {
       const f32x4 x = load4<FT>(f + (long long)s * C);
 #pragma unroll
       for (int g = 0; g < G; ++g) a[g] += x * w[g][s];
@@ -266,7 +277,7 @@ __global__ void glimpse_pool_fwd_kernel(const FT* __restrict__ feat,
       *reinterpret_cast<f32x4*>(pooled + (long long)n * G * C + g * C + c) = a[g];
   } else {
     const int nc = min(4, C - c);
-    for (int s = 0; s < S; ++s)
+    for (int s = 0; s < Sv; ++s)
       for (int j = 0; j < nc; ++j) {
         const float x = (float)f[(long long)s * C + j];
 #pragma unroll
@@ -285,11 +296,12 @@ __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
                                         const float* __restrict__ dwts_extra,
                                         const FT* __restrict__ feat,
                                         const float* __restrict__ wts, int N, int S, int C, int unit,
-                                        float* __restrict__ dlogits, float* __restrict__ dfeat) {
+                                        float* __restrict__ dlogits, float* __restrict__ dfeat, const int* __restrict__ lens) {
   __shared__ float dw[G][MAXS];
   __shared__ float ws[G][MAXS];
   const int n = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwave = blockDim.x >> 6;
+  const int Sv = pool_len(lens, n, S);                // (uniform) positions Sv .. S - 1 are padding: weight 0, gradient 0
   for (int i = tid; i < G * S; i += blockDim.x) ws[i / S][i % S] = wts[(long long)n * G * S + i];
   __syncthreads();
   const float* dp = dpooled + (long long)n * G * C;
@@ -306,7 +318,7 @@ __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
 #pragma unroll
       for (int g = 0; g < G; ++g) pr[g][k] = c < C ? *reinterpret_cast<const f32x4*>(dp + g * C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    for (int s = wave; s < S; s += nwave) {
+    for (int s = wave; s < Sv; s += nwave) {
       const FT* f = feat + ((long long)n * S + s) * C;
       f32x4 x[KC];
 #pragma unroll
@@ -328,6 +340,13 @@ __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
   for (int s = wave; s < S; s += nwave) {
     const FT* f = feat + ((long long)n * S + s) * C;
     float* df = dfeat ? dfeat + ((long long)n * S + s) * C : nullptr;
+    if (s >= Sv) {                                     // (wave-uniform) a padded row: zero gradient, feat unread
+      if (df) {
+        if (vec) for (int c = lane * 4; c < C; c += 256) *reinterpret_cast<f32x4*>(df + c) = f32x4{0.f, 0.f, 0.f, 0.f};
+        else for (int c = lane; c < C; c += 64) df[c] = 0.f;
+      }
+      continue;
+    }
     float a[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) a[g] = 0.f;
@@ -363,12 +382,12 @@ __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
     const int g = wave;
     float dot = 0.f;
     if (!unit) {
-      for (int s = lane; s < S; s += 64) dot += ws[g][s] * dw[g][s];
+      for (int s = lane; s < Sv; s += 64) dot += ws[g][s] * dw[g][s];
       dot = wave_sum(dot);
     }
     for (int s = lane; s < S; s += 64) {
       // softmax over a singleton axis: y == 1 and dy - sum(dy*y) == 0 exactly
-      const float d = unit ? 0.f : ws[g][s] * (dw[g][s] - dot);
+      const float d = (unit || s >= Sv) ? 0.f : ws[g][s] * (dw[g][s] - dot);
       dlogits[((long long)n * S + s) * G + g] = d;
     }
   }
@@ -487,26 +506,28 @@ namespace {
 template <int G, typename FT>
 __global__ void __launch_bounds__(1024) glimpse_pool_fwd_rows_kernel(const FT* __restrict__ feat, const float* __restrict__ logits,
                                                                      int N, int S, int C, int unit, float* __restrict__ wts,
-                                                                     float* __restrict__ pooled) {
+                                                                     float* __restrict__ pooled, const int* __restrict__ lens) {
   extern __shared__ float smem_g[];
   float* w = smem_g;                                   // [G][S]
   float* red = smem_g + G * S;                         // [RS][G][C]
   const int n = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int Sv = pool_len(lens, n, S);
   if (wave < G) {
     const int g = wave;
     const float* lg = logits + (long long)n * S * G + g;
     if (unit) {
-      for (int s = lane; s < S; s += 64) w[g * S + s] = 1.0f;
+      for (int s = lane; s < S; s += 64) w[g * S + s] = s < Sv ? 1.0f : 0.f;
     } else {
       float mx = -INFINITY;
-      for (int s = lane; s < S; s += 64) mx = fmaxf(mx, lg[G * s]);
+      for (int s = lane; s < Sv; s += 64) mx = fmaxf(mx, lg[G * s]);
       mx = wave_max(mx);
       float sum = 0.f;
-      for (int s = lane; s < S; s += 64) { const float e = expf(lg[G * s] - mx); w[g * S + s] = e; sum += e; }
+      for (int s = lane; s < Sv; s += 64) { const float e = expf(lg[G * s] - mx); w[g * S + s] = e; sum += e; }
       sum = wave_sum(sum);
       const float rs = 1.0f / sum;
-      for (int s = lane; s < S; s += 64) w[g * S + s] *= rs;
+      for (int s = lane; s < Sv; s += 64) w[g * S + s] *= rs;
+      for (int s = Sv + lane; s < S; s += 64) w[g * S + s] = 0.f;
     }
   }
   __syncthreads();
@@ -519,12 +540,12 @@ __global__ void __launch_bounds__(1024) glimpse_pool_fwd_rows_kernel(const FT* _
 #pragma unroll
   for (int g = 0; g < G; ++g) a[g] = f32x4{0, 0, 0, 0};
   int s = rs;
-  for (; s + RS < S; s += 2 * RS) {
+  for (; s + RS < Sv; s += 2 * RS) {
     const f32x4 x0 = load4<FT>(f + (long long)s * C), x1 = load4<FT>(f + (long long)(s + RS) * C);
 #pragma unroll
     for (int g = 0; g < G; ++g) { a[g] += x0 * w[g * S + s]; a[g] += x1 * w[g * S + s + RS]; }
   }
-  if (s < S) {
+  if (s < Sv) {
     const f32x4 x0 = load4<FT>(f + (long long)s * C);
 #pragma unroll
     for (int g = 0; g < G; ++g) a[g] += x0 * w[g * S + s];
@@ -541,8 +562,8 @@ __global__ void __launch_bounds__(1024) glimpse_pool_fwd_rows_kernel(const FT* _
 
 template <typename FT>
 int glimpse_fwd_launch(const FT* feat, const float* logits, int N, int S, int C, int G, int unit_softmax,
-                       float* wts, float* pooled, void* stream) {
-  if (!feat || !logits || !pooled || N <= 0 || S <= 0 || C <= 0) return VQF_E_BADARG;
+                       float* wts, float* pooled, void* stream, const int* lens = nullptr) {
+  if (!feat || !logits || !pooled || N <= 0 || S <= 0 || C <= 0 || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
   if (S > MAXS || G < 1 || G > 3 || N > 65535) return VQF_E_UNSUPPORTED;
   dim3 grid((C + 1023) / 1024, N);
   hipStream_t s = (hipStream_t)stream;
@@ -556,33 +577,34 @@ int glimpse_fwd_launch(const FT* feat, const float* logits, int N, int S, int C,
       if (RS >= G && lds <= 64 * 1024) {
         if (G == 3)
           VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<3, FT>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
-                     unit_softmax, wts, pooled);
+                     unit_softmax, wts, pooled, lens);
         else if (G == 2)
           VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<2, FT>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
-                     unit_softmax, wts, pooled);
+                     unit_softmax, wts, pooled, lens);
         else
           VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<1, FT>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
-                     unit_softmax, wts, pooled);
+                     unit_softmax, wts, pooled, lens);
         return vqf_last_error();
       }
     }
   }
   if (G == 3)
     VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<3, FT>), grid, dim3(256), 0, s, feat, logits, N, S,
-               C, unit_softmax, wts, pooled);
+               C, unit_softmax, wts, pooled, lens);
   else if (G == 2)
     VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<2, FT>), grid, dim3(256), 0, s, feat, logits, N, S,
-               C, unit_softmax, wts, pooled);
+               C, unit_softmax, wts, pooled, lens);
   else
     VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<1, FT>), grid, dim3(256), 0, s, feat, logits, N, S,
-               C, unit_softmax, wts, pooled);
+               C, unit_softmax, wts, pooled, lens);
   return vqf_last_error();
 }
 
 template <typename FT>
 int glimpse_bwd_launch(const float* dpooled, const float* dwts_extra, const FT* feat, const float* wts, int N,
-                       int S, int C, int G, int unit_softmax, float* dlogits, float* dfeat, void* stream) {
-  if (!dpooled || !feat || !wts || !dlogits || N <= 0 || S <= 0 || C <= 0) return VQF_E_BADARG;
+                       int S, int C, int G, int unit_softmax, float* dlogits, float* dfeat, void* stream,
+                       const int* lens = nullptr) {
+  if (!dpooled || !feat || !wts || !dlogits || N <= 0 || S <= 0 || C <= 0 || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
   if (S > MAXS || G < 1 || G > 3) return VQF_E_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   // one workgroup per sample.  A wave keeps ceil(C / 256) 16-byte loads per lane in flight (a row of the grid); about 64 such
@@ -601,13 +623,13 @@ int glimpse_bwd_launch(const float* dpooled, const float* dwts_extra, const FT* 
   const dim3 block(64 * waves);
   if (G == 3)
     VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<3, FT>), dim3(N), block, 0, s, dpooled,
-               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat);
+               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens);
   else if (G == 2)
     VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<2, FT>), dim3(N), block, 0, s, dpooled,
-               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat);
+               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens);
   else
     VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<1, FT>), dim3(N), block, 0, s, dpooled,
-               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat);
+               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens);
   return vqf_last_error();
 }
 }  // namespace
@@ -629,6 +651,18 @@ int vqf_glimpse_pool_bwd(const float* dpooled, const float* dwts_extra, const fl
                          float* dlogits, float* dfeat, void* stream) {
   return glimpse_bwd_launch<float>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, dfeat,
                                    stream);
+}
+
+int vqf_glimpse_pool_fwd_len(const float* feat, const float* logits, const int* lens, int N, int S, int C, int G,
+                             int unit_softmax, float* wts, float* pooled, void* stream) {
+  if (!lens) return VQF_E_BADARG;
+  return glimpse_fwd_launch<float>(feat, logits, N, S, C, G, unit_softmax, wts, pooled, stream, lens);
+}
+
+int vqf_glimpse_pool_bwd_len(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* lens,
+                             int N, int S, int C, int G, int unit_softmax, float* dlogits, float* dfeat, void* stream) {
+  if (!lens) return VQF_E_BADARG;
+  return glimpse_bwd_launch<float>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, dfeat, stream, lens);
 }
 
 int vqf_glimpse_pool_bwd_bf16(const float* dpooled, const float* dwts_extra, const void* feat,

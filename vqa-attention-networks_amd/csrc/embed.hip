@@ -12,6 +12,9 @@
 //   ~0.1 ms of the MFB train step; this is one launch of ~10 us).
 // Ids outside [0, V) select no row: the forward writes zeros for them, the backward ignores them (the reference's ids come
 // from its own vocabulary, utils.py:185,303-304; torch would raise).
+//
+// Question lengths (vqf_embed_tanh_fwd_len / _bwd_len; ids (N, Tq), lens (N) int32): a token at position >= lens[n] is padding,
+// whatever its id: the forward writes a zero row for it and the backward skips it, so the padding id's row gets no gradient.
 #include "common.h"
 
 namespace {
@@ -20,6 +23,13 @@ namespace {
 // (Tq, N) -- what the batch-major LSTM consumes (mfb.py:68-69), so no transposing copy sits between the lookup and the recursion.
 __device__ __forceinline__ int tok_of_row(int t, int T, int swapN) {
   return swapN > 0 ? (t % swapN) * (T / swapN) + t / swapN : t;
+}
+
+// token tok of ids (N, Tq) is a real word (lens null: every token is)
+__device__ __forceinline__ bool tok_real(const int* __restrict__ lens, int tok, int Tq) {
+  if (!lens) return true;
+  const int n = tok / Tq;
+  return tok - n * Tq < lens[n];
 }
 
 // keep scale of element e of the flat (T, E) tensor: the draw of the element-wise dropout kernels (elementwise.hip keep4: one Philox
@@ -36,12 +46,13 @@ __device__ __forceinline__ float keep_scale(const uint8_t* __restrict__ keep, ui
 template <bool TANH, bool DROP = false>
 __global__ void embed_fwd_kernel(const float* __restrict__ W, const long long* __restrict__ ids, int T, int V, int E,
                                       float* __restrict__ out, int swapN, const uint8_t* __restrict__ keep = nullptr, uint64_t seed = 0,
-                                      uint32_t thr = 0u, float inv_keep = 1.0f) {
+                                      uint32_t thr = 0u, float inv_keep = 1.0f, const int* __restrict__ lens = nullptr, int Tq = 1) {
   const int t = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (t >= T) return;
   const int lane = threadIdx.x & 63;
-  const long long id = ids[tok_of_row(t, T, swapN)];
-  const bool ok = id >= 0 && id < V;
+  const int tok = tok_of_row(t, T, swapN);
+  const long long id = ids[tok];
+  const bool ok = id >= 0 && id < V && tok_real(lens, tok, Tq);     // (wave-uniform: a wave owns the row)
   const float* w = W + (ok ? id : 0) * (long long)E;
   float* o = out + (long long)t * E;
   if ((E & 3) == 0 && aligned16_dev(W) && aligned16_dev(out)) {
@@ -75,7 +86,8 @@ template <bool TANH, bool DROP = false>
 __global__ void __launch_bounds__(256) embed_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ out,
                                                             const long long* __restrict__ ids, int T, int V, int E, int RV,
                                                             float* __restrict__ dW, int swapN, const uint8_t* __restrict__ keep = nullptr,
-                                                            uint64_t seed = 0, uint32_t thr = 0u, float inv_keep = 1.0f) {
+                                                            uint64_t seed = 0, uint32_t thr = 0u, float inv_keep = 1.0f,
+                                                            const int* __restrict__ lens = nullptr, int Tq = 1) {
   __shared__ int list[4][EB_CHUNK / 4];
   __shared__ int count[4];
   const int v0 = blockIdx.x * RV, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -91,7 +103,8 @@ __global__ void __launch_bounds__(256) embed_bwd_kernel(const float* __restrict_
 #pragma unroll
     for (int q = 0; q < EB_CHUNK / 4 / 64; ++q) {        // the 8 id loads of a wave are issued together, once per round
       const int t = b0 + 64 * q + lane;
-      idv[q] = t < T ? ids[tok_of_row(t, T, swapN)] : -1;
+      const int tok = t < T ? tok_of_row(t, T, swapN) : 0;
+      idv[q] = t < T && tok_real(lens, tok, Tq) ? ids[tok] : -1;     // a padded token matches no row
     }
 #pragma unroll
     for (int r = 0; r < EB_ROWS; ++r) {
@@ -185,6 +198,32 @@ int vqf_embed_bwd(const float* dout, const long long* ids, int T, int V, int E, 
   const int rv = embed_rows_per_wg(V);
   VQF_LAUNCH(KID_EMBED_BWD, embed_bwd_kernel<false>, dim3((V + rv - 1) / rv), dim3(256), 0, (hipStream_t)stream, dout, none, ids, T, V,
              E, rv, dW, 0);
+  return vqf_last_error();
+}
+
+// ids (N, Tq), lens (N) int32: tokens at positions >= lens[n] are padding (zero rows forward, no gradient backward)
+int vqf_embed_tanh_fwd_len(const float* W, const long long* ids, const int* lens, int N, int Tq, int V, int E, float* out,
+                           void* stream) {
+  if (!W || !ids || !lens || !out || N <= 0 || Tq <= 0 || V <= 0 || E <= 0 || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
+  if ((long long)N * Tq >= (1LL << 31)) return VQF_E_UNSUPPORTED;
+  const int T = N * Tq;
+  const uint8_t* none = nullptr;
+  vqf_prof_dims(T, V, E);
+  VQF_LAUNCH(KID_EMBED_FWD, embed_fwd_kernel<true>, dim3((T + 3) / 4), dim3(256), 0, (hipStream_t)stream, W, ids, T, V, E, out, 0,
+             none, (uint64_t)0, 0u, 1.0f, lens, Tq);
+  return vqf_last_error();
+}
+
+int vqf_embed_tanh_bwd_len(const float* dout, const float* out, const long long* ids, const int* lens, int N, int Tq, int V, int E,
+                           float* dW, void* stream) {
+  if (!dout || !out || !ids || !lens || !dW || N <= 0 || Tq <= 0 || V <= 0 || E <= 0 || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
+  if (E > 1024 || (long long)N * Tq >= (1LL << 31)) return VQF_E_UNSUPPORTED;
+  const int T = N * Tq;
+  const uint8_t* none = nullptr;
+  vqf_prof_dims(T, V, E);
+  const int rv = embed_rows_per_wg(V);
+  VQF_LAUNCH(KID_EMBED_BWD, embed_bwd_kernel<true>, dim3((V + rv - 1) / rv), dim3(256), 0, (hipStream_t)stream, dout, out, ids, T, V, E,
+             rv, dW, 0, none, (uint64_t)0, 0u, 1.0f, lens, Tq);
   return vqf_last_error();
 }
 

@@ -292,12 +292,17 @@ __global__ void slab_sum_kernel(const float* __restrict__ part, int S, int R, in
 // out and yprev (G, N, T, L), contiguous per level.  The k order of a level does not depend on G.  The two entry points are two
 // sets of instantiations of the one template: vqf_hie_affinity <EPI, 1, DROP = true>, vqf_hie_affinity_levels <EPI, G, false>
 // (the ladder has no dropout on C; with the dropout epilogue compiled in, <2, 3> needs 128 registers and spills).
+//
+// lens (vqf_hie_affinity_len / vqf_hie_affinity_levels_len; N int32 row counts, null: all T): output rows t >= len[n] are written as zero whatever the
+// operands hold.  The ladder's dC needs it: (dti Vh^T + Qh dtq^T)(1 - C^2) of a padded question row is only zero while both
+// x operands are, and dC feeds dCq, dQ and dV.  One uniform load per workgroup (n = blockIdx.y), a compare per output row.
 struct AffArgs {
   const float* x1; int ldx1, lvx1; const float* y1; int ldy1, lvy1;     // lv*: column offset of level g is g * lv* (unused for G = 1)
   const float* x2; int ldx2, lvx2; const float* y2; int ldy2, lvy2;
   const float* yprev; float* out;
   const uint8_t* keep; uint64_t seed; uint32_t thr; float inv_keep;     // DROP only
   int N, L, E, T;
+  const int* lens;                                                      // null: every one of the T rows is real
 };
 
 __device__ __forceinline__ float keep1(const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep, long long idx) {
@@ -331,6 +336,7 @@ __global__ void __launch_bounds__(1024) hie_affinity_kernel(const AffArgs g) {
   __syncthreads();
   const int NG = (L + 15) >> 4;
   const int r = lane & 15, kq = lane >> 4;
+  const int len = g.lens ? g.lens[n] : T;                               // (uniform) rows len .. T - 1 are padding: stored as zero
   for (int grp = blockIdx.x * W + wave; grp < NG; grp += gridDim.x * W) {
     const int l = grp * 16 + r;
     const long long row = (long long)n * L + (l < L ? l : L - 1);      // rows past L: a valid row, result not stored
@@ -383,7 +389,7 @@ __global__ void __launch_bounds__(1024) hie_affinity_kernel(const AffArgs g) {
               const float th = !DROP ? g.yprev[idx] : sc > 0.f ? g.yprev[idx] * (1.0f / g.inv_keep) : 0.f;
               v = v * sc * (1.0f - th * th);
             }
-            g.out[idx] = v;
+            g.out[idx] = t < len ? v : 0.f;
           }
         }
     }
@@ -586,6 +592,19 @@ int vqf_hie_affinity(const float* x1, int ldx1, const float* y1, int ldy1, const
   return affinity_launch(KID_HIE_AFF, g, 1, epi, true, (hipStream_t)stream);
 }
 
+int vqf_hie_affinity_len(const float* x1, int ldx1, const float* y1, int ldy1, const float* x2, int ldx2, const float* y2, int ldy2,
+                         int epi, const float* yprev, const uint8_t* keep, uint64_t seed, float p_drop, const int* lens, int N, int L,
+                         int E, int T, float* out, void* stream) {
+  if (p_drop < 0.f || p_drop >= 1.f || !lens || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
+  AffArgs g = {};
+  g.x1 = x1; g.ldx1 = ldx1; g.y1 = y1; g.ldy1 = ldy1; g.x2 = x2; g.ldx2 = ldx2; g.y2 = y2; g.ldy2 = ldy2;
+  g.yprev = yprev; g.out = out; g.N = N; g.L = L; g.E = E; g.T = T; g.lens = lens;
+  g.keep = epi ? keep : nullptr; g.seed = seed;
+  g.thr = (!epi || keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
+  g.inv_keep = (epi && (keep || p_drop > 0.f)) ? 1.0f / (1.0f - p_drop) : 1.0f;
+  return affinity_launch(KID_HIE_AFF, g, 1, epi, true, (hipStream_t)stream);
+}
+
 int vqf_hie_affinity_levels_supported(int N, int L, int E, int T, int G, int pairs) { return affinity_shape_ok(N, L, E, T, G, pairs); }
 
 int vqf_hie_affinity_levels(const float* x1, int ldx1, int ldx_level1, const float* y1, int ldy1, int ldy_level1,
@@ -595,6 +614,18 @@ int vqf_hie_affinity_levels(const float* x1, int ldx1, int ldx_level1, const flo
   g.x1 = x1; g.ldx1 = ldx1; g.lvx1 = ldx_level1; g.y1 = y1; g.ldy1 = ldy1; g.lvy1 = ldy_level1;
   g.x2 = x2; g.ldx2 = ldx2; g.lvx2 = ldx_level2; g.y2 = y2; g.ldy2 = ldy2; g.lvy2 = ldy_level2;
   g.yprev = yprev; g.out = out; g.N = N; g.L = L; g.E = E; g.T = T;
+  return affinity_launch(KID_HIE_AFF_LEVELS, g, G, epi, false, (hipStream_t)stream);
+}
+
+int vqf_hie_affinity_levels_len(const float* x1, int ldx1, int ldx_level1, const float* y1, int ldy1, int ldy_level1,
+                                const float* x2, int ldx2, int ldx_level2, const float* y2, int ldy2, int ldy_level2,
+                                int G, int epi, const float* yprev, const int* lens, int N, int L, int E, int T, float* out,
+                                void* stream) {
+  if (!lens || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
+  AffArgs g = {};
+  g.x1 = x1; g.ldx1 = ldx1; g.lvx1 = ldx_level1; g.y1 = y1; g.ldy1 = ldy1; g.lvy1 = ldy_level1;
+  g.x2 = x2; g.ldx2 = ldx2; g.lvx2 = ldx_level2; g.y2 = y2; g.ldy2 = ldy2; g.lvy2 = ldy_level2;
+  g.yprev = yprev; g.out = out; g.N = N; g.L = L; g.E = E; g.T = T; g.lens = lens;
   return affinity_launch(KID_HIE_AFF_LEVELS, g, G, epi, false, (hipStream_t)stream);
 }
 

@@ -12,6 +12,13 @@
 // output r - j of the same sample (no atomics, every element written once).  The column sums of dZ's j = 0 taps are the three
 // bias gradients; dQw and dWcat are GEMMs on the existing kernels.  T <= 32 (the windows of a sample stay in one workgroup's
 // reach), E % 4 == 0.
+//
+// Question lengths (the *_len entry points; lens (N) int32, len[n] real words, the rest of the T positions padding): the window
+// of position t stops at len[n] instead of T, a padded output row is zero with idx = 3 (no winner), and the backward writes
+// zeros to the padded rows of dZ -- nothing is scattered to or from padding.  lens = null is the unmasked form, same bits.
+//
+// vqf_tanh_bwd_rows_len: dx = dy (1 - y^2) on the real rows of a contiguous (N, T, L) tensor, zero on the padded ones (the
+// ladder's dC on the batched-GEMM route, T > 16; the streaming route masks in the affinity epilogue of hie.hip).
 #include "common.h"
 
 namespace {
@@ -19,16 +26,28 @@ namespace {
 constexpr int PH_TMAX = 32;
 
 // one thread per (row, 4 columns); rows r = n * T + t
+__device__ __forceinline__ int row_len(const int* __restrict__ lens, int n, int T) {
+  if (!lens) return T;
+  const int len = lens[n];
+  return len < 1 ? 1 : (len > T ? T : len);
+}
+
 __global__ void phrase_ngram_fwd_kernel(const float* __restrict__ Z, int ldz, const float* __restrict__ bias, int NT, int T,
-                                        int E, float* __restrict__ Qp, int ldq, uint8_t* __restrict__ idx) {
+                                        int E, float* __restrict__ Qp, int ldq, uint8_t* __restrict__ idx,
+                                        const int* __restrict__ lens) {
   const int CT = E >> 2;
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)NT * CT) return;
   const int r = (int)(i / CT), c = 4 * (int)(i - (long long)r * CT);
-  const int t = r % T;
-  const float* z0 = Z + (long long)r * ldz + c;
-  const bool h1 = t + 1 < T, h2 = t + 2 < T;
+  const int t = r % T, len = row_len(lens, r / T, T);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  if (t >= len) {                                   // a padded row: zero, no winner
+    *reinterpret_cast<f32x4*>(Qp + (long long)r * ldq + c) = zero;
+    *reinterpret_cast<uint32_t*>(idx + (long long)r * E + c) = 0x03030303u;
+    return;
+  }
+  const float* z0 = Z + (long long)r * ldz + c;
+  const bool h1 = t + 1 < len, h2 = t + 2 < len;
   const f32x4 u1t0 = *reinterpret_cast<const f32x4*>(z0);
   const f32x4 u2t0 = *reinterpret_cast<const f32x4*>(z0 + E);
   const f32x4 u2t1 = h1 ? *reinterpret_cast<const f32x4*>(z0 + ldz + 2 * E) : zero;
@@ -58,19 +77,21 @@ __global__ void phrase_ngram_fwd_kernel(const float* __restrict__ Z, int ldz, co
 
 // dZ[r, tap(k, j)] = (t - j >= 0 && idx[r - j] == k - 1) ? du[r - j] : 0,  du = dQp (1 - Qp^2)
 __global__ void phrase_ngram_bwd_kernel(const float* __restrict__ dQp, int ldd, const float* __restrict__ Qp, int ldq,
-                                        const uint8_t* __restrict__ idx, int NT, int T, int E, float* __restrict__ dZ, int ldz) {
+                                        const uint8_t* __restrict__ idx, int NT, int T, int E, float* __restrict__ dZ, int ldz,
+                                        const int* __restrict__ lens) {
   const int CT = E >> 2;
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)NT * CT) return;
   const int r = (int)(i / CT), c = 4 * (int)(i - (long long)r * CT);
   const int t = r % T;
+  const bool real = t < row_len(lens, r / T, T);  // a padded row of Z entered no window: its dZ is zero
   f32x4 du[3];
   uint32_t win[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {                   // the outputs r, r - 1, r - 2 of the same sample
     du[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     win[j] = 0xFFFFFFFFu;
-    if (t - j >= 0) {
+    if (real && t - j >= 0) {
       const long long rr = r - j;
       const f32x4 d = *reinterpret_cast<const f32x4*>(dQp + rr * ldd + c);
       const f32x4 q = *reinterpret_cast<const f32x4*>(Qp + rr * ldq + c);
@@ -91,6 +112,48 @@ __global__ void phrase_ngram_bwd_kernel(const float* __restrict__ dQp, int ldd, 
     }
 }
 
+// dx[n, t, l] = t < len[n] ? dy (1 - y^2) : 0 over a contiguous (N, T, L) tensor, four elements per thread (a group of four may
+// straddle two rows when L % 4 != 0: the row is found per element)
+__global__ void tanh_bwd_rows_len_kernel(const float* __restrict__ dy, const float* __restrict__ y, const int* __restrict__ lens,
+                                         long long n4, int T, int L, float* __restrict__ dx) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const f32x4 d = *reinterpret_cast<const f32x4*>(dy + 4 * i);
+    const f32x4 v = *reinterpret_cast<const f32x4*>(y + 4 * i);
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long long row = (4 * i + j) / L;
+      const int n = (int)(row / T), t = (int)(row - (long long)n * T);
+      o[j] = t < row_len(lens, n, T) ? d[j] * (1.0f - v[j] * v[j]) : 0.f;
+    }
+    *reinterpret_cast<f32x4*>(dx + 4 * i) = o;
+  }
+}
+
+int phrase_fwd_launch(const float* Z, int ldz, const float* bias, const int* lens, int N, int T, int E, float* Qp, int ldq,
+                      uint8_t* idx, void* stream) {
+  if (!Z || !bias || !Qp || !idx || N <= 0 || ldz < 6 * E || ldq < E || (ldz % 4) || (ldq % 4)) return VQF_E_BADARG;
+  if (!vqf_phrase_ngram_supported(T, E) || (long long)N * T * (E / 4) >= (1LL << 31)) return VQF_E_UNSUPPORTED;
+  if (!aligned16(Z) || !aligned16(bias) || !aligned16(Qp) || (((uintptr_t)idx) & 3) || (((uintptr_t)lens) & 3)) return VQF_E_ALIGN;
+  const long long n4 = (long long)N * T * (E / 4);
+  VQF_LAUNCH(KID_PHRASE_FWD, phrase_ngram_fwd_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Z, ldz,
+             bias, N * T, T, E, Qp, ldq, idx, lens);
+  return vqf_last_error();
+}
+
+int phrase_bwd_launch(const float* dQp, int ldd, const float* Qp, int ldq, const uint8_t* idx, const int* lens, int N, int T, int E,
+                      float* dZ, int ldz, void* stream) {
+  if (!dQp || !Qp || !idx || !dZ || N <= 0 || ldz < 6 * E || ldq < E || ldd < E || (ldz % 4) || (ldq % 4) || (ldd % 4))
+    return VQF_E_BADARG;
+  if (!vqf_phrase_ngram_supported(T, E) || (long long)N * T * (E / 4) >= (1LL << 31)) return VQF_E_UNSUPPORTED;
+  if (!aligned16(dQp) || !aligned16(Qp) || !aligned16(dZ) || (((uintptr_t)idx) & 3) || (((uintptr_t)lens) & 3)) return VQF_E_ALIGN;
+  const long long n4 = (long long)N * T * (E / 4);
+  VQF_LAUNCH(KID_PHRASE_BWD, phrase_ngram_bwd_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dQp,
+             ldd, Qp, ldq, idx, N * T, T, E, dZ, ldz, lens);
+  return vqf_last_error();
+}
+
 }  // namespace
 
 extern "C" {
@@ -101,24 +164,35 @@ int vqf_phrase_ngram_supported(int T, int E) {
 
 int vqf_phrase_ngram_fwd(const float* Z, int ldz, const float* bias, int N, int T, int E, float* Qp, int ldq, uint8_t* idx,
                          void* stream) {
-  if (!Z || !bias || !Qp || !idx || N <= 0 || ldz < 6 * E || ldq < E || (ldz % 4) || (ldq % 4)) return VQF_E_BADARG;
-  if (!vqf_phrase_ngram_supported(T, E) || (long long)N * T * (E / 4) >= (1LL << 31)) return VQF_E_UNSUPPORTED;
-  if (!aligned16(Z) || !aligned16(bias) || !aligned16(Qp) || (((uintptr_t)idx) & 3)) return VQF_E_ALIGN;
-  const long long n4 = (long long)N * T * (E / 4);
-  VQF_LAUNCH(KID_PHRASE_FWD, phrase_ngram_fwd_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Z, ldz,
-             bias, N * T, T, E, Qp, ldq, idx);
-  return vqf_last_error();
+  return phrase_fwd_launch(Z, ldz, bias, nullptr, N, T, E, Qp, ldq, idx, stream);
 }
 
 int vqf_phrase_ngram_bwd(const float* dQp, int ldd, const float* Qp, int ldq, const uint8_t* idx, int N, int T, int E, float* dZ,
                          int ldz, void* stream) {
-  if (!dQp || !Qp || !idx || !dZ || N <= 0 || ldz < 6 * E || ldq < E || ldd < E || (ldz % 4) || (ldq % 4) || (ldd % 4))
-    return VQF_E_BADARG;
-  if (!vqf_phrase_ngram_supported(T, E) || (long long)N * T * (E / 4) >= (1LL << 31)) return VQF_E_UNSUPPORTED;
-  if (!aligned16(dQp) || !aligned16(Qp) || !aligned16(dZ) || (((uintptr_t)idx) & 3)) return VQF_E_ALIGN;
-  const long long n4 = (long long)N * T * (E / 4);
-  VQF_LAUNCH(KID_PHRASE_BWD, phrase_ngram_bwd_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dQp,
-             ldd, Qp, ldq, idx, N * T, T, E, dZ, ldz);
+  return phrase_bwd_launch(dQp, ldd, Qp, ldq, idx, nullptr, N, T, E, dZ, ldz, stream);
+}
+
+int vqf_phrase_ngram_fwd_len(const float* Z, int ldz, const float* bias, const int* lens, int N, int T, int E, float* Qp, int ldq,
+                             uint8_t* idx, void* stream) {
+  if (!lens) return VQF_E_BADARG;
+  return phrase_fwd_launch(Z, ldz, bias, lens, N, T, E, Qp, ldq, idx, stream);
+}
+
+int vqf_phrase_ngram_bwd_len(const float* dQp, int ldd, const float* Qp, int ldq, const uint8_t* idx, const int* lens, int N, int T,
+                             int E, float* dZ, int ldz, void* stream) {
+  if (!lens) return VQF_E_BADARG;
+  return phrase_bwd_launch(dQp, ldd, Qp, ldq, idx, lens, N, T, E, dZ, ldz, stream);
+}
+
+int vqf_tanh_bwd_rows_len(const float* dy, const float* y, const int* lens, int N, int T, int L, float* dx, void* stream) {
+  if (!dy || !y || !lens || !dx || N <= 0 || T <= 0 || L <= 0) return VQF_E_BADARG;
+  const long long n = (long long)N * T * L;
+  if (n % 4) return VQF_E_UNSUPPORTED;
+  if (!aligned16(dy) || !aligned16(y) || !aligned16(dx) || (((uintptr_t)lens) & 3)) return VQF_E_ALIGN;
+  long long blocks = (n / 4 + 255) / 256;
+  if (blocks > 16384) blocks = 16384;
+  VQF_LAUNCH(KID_TANH_DROP_BWD, tanh_bwd_rows_len_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, dy, y, lens,
+             n / 4, T, L, dx);
   return vqf_last_error();
 }
 

@@ -29,20 +29,21 @@ def _bf16_ok(*dims):
 
 class EmbedTanhFn(torch.autograd.Function):
     """que_embedded = tanh(word_embedding(questions))   (mfb.py:68, mhb_coAtt.py:69): gather + tanh in one launch, and a
-    deterministic one-launch weight gradient (csrc/embed.hip) instead of torch's sort-based embedding backward."""
+    deterministic one-launch weight gradient (csrc/embed.hip) instead of torch's sort-based embedding backward.
+    lens ((N,) int32, ids (N, Tq); HieCoAttenLadder): the tokens at positions >= lens[n] are padding -- zero rows, no gradient."""
 
     @staticmethod
-    def forward(ctx, ids, weight, tanh=True, time_major=False):
+    def forward(ctx, ids, weight, tanh=True, time_major=False, lens=None):
         ids = ids.contiguous()
-        out = ops.embed_tanh_fwd(_c(weight), ids, tanh, time_major)
+        out = ops.embed_tanh_fwd(_c(weight), ids, tanh, time_major, lens=lens)
         ctx.save_for_backward(ids, out if tanh else None)
-        ctx.V, ctx.tm = weight.shape[0], bool(time_major)
+        ctx.V, ctx.tm, ctx.lens = weight.shape[0], bool(time_major), lens
         return out
 
     @staticmethod
     def backward(ctx, dout):
         ids, out = ctx.saved_tensors
-        return None, ops.embed_tanh_bwd(_c(dout), out, ids, ctx.V, ctx.tm), None, None
+        return None, ops.embed_tanh_bwd(_c(dout), out, ids, ctx.V, ctx.tm, lens=ctx.lens), None, None, None
 
 
 def _plain_embedding(embedding, ids):
@@ -616,13 +617,14 @@ class DropoutFn(torch.autograd.Function):
 class DropoutBTFn(torch.autograd.Function):
     """The LSTM-output dropout (mfb.py:70, mhb_coAtt.py:75): x (B, T, H), any strides on the first two axes (MFB hands in the
     transposed view of its time-major LSTM states) -> CONTIGUOUS dropout(x); the gradient goes back in x's own layout, so the
-    (T, B, H) <-> (B, T, H) re-layouts of both directions ride in the two dropout passes instead of torch copy kernels."""
+    (T, B, H) <-> (B, T, H) re-layouts of both directions ride in the two dropout passes instead of torch copy kernels.
+    lens ((B,) int32; HieCoAttenLadder's sentence level): rows t >= lens[b] are zero in the output, and so is their gradient."""
 
     @staticmethod
-    def forward(ctx, x, keep, seed, p_drop):
-        ctx.keep, ctx.seed, ctx.p = keep, seed, p_drop
+    def forward(ctx, x, keep, seed, p_drop, lens=None):
+        ctx.keep, ctx.seed, ctx.p, ctx.lens = keep, seed, p_drop, lens
         ctx.in_strides = (x.stride(0), x.stride(1))
-        return ops.dropout_bt(x, torch.empty(x.shape, dtype=torch.float32, device=x.device), keep, seed, p_drop)
+        return ops.dropout_bt(x, torch.empty(x.shape, dtype=torch.float32, device=x.device), keep, seed, p_drop, lens=lens)
 
     @staticmethod
     def backward(ctx, dy):
@@ -634,8 +636,8 @@ class DropoutBTFn(torch.autograd.Function):
             dx = torch.empty((T, B, H), dtype=torch.float32, device=dy.device).transpose(0, 1)
         else:
             dx = torch.empty((B, T, H), dtype=torch.float32, device=dy.device)
-        ops.dropout_bt(dy, dx, ctx.keep, ctx.seed, ctx.p)
-        return dx, None, None, None
+        ops.dropout_bt(dy, dx, ctx.keep, ctx.seed, ctx.p, lens=ctx.lens)
+        return dx, None, None, None, None
 
 
 def lstm_out_dropout(module, x, seeds, tag="l"):
@@ -765,16 +767,23 @@ def _hie_hv_ti(Vh, C, Qh, drop, N, L, T, Hv, ti, stream):
         ops.bgemm(C, Vh.view(N, L, E), ta=False, tb=True, out=ti.view(N, T, E))             # C Vh
 
 
-def _hie_dc(dti, Vh, Qh, dtq, C, drop, N, L, T, aff, out=None):
+def _hie_dc(dti, Vh, Qh, dtq, C, drop, N, L, T, aff, out=None, lens=None):
     """One level's gradient of the affinity's pre-activation: (dti Vh^T + Qh dtq^T) through the backward of
     C = dropout(tanh(.)), (N, T, L).  aff: ONE pass over Vh and dtq (vqf_hie_affinity, two pairs); otherwise two batched
-    products and the element-wise backward.  Reads dtq: call it before dtq is updated in place."""
+    products and the element-wise backward.  Reads dtq: call it before dtq is updated in place.
+    lens ((N,) int32, no dropout; HieCoAttenLadder): the rows t >= lens[n] of the result are zero (the affinity's epilogue, or
+    the element-wise backward's row test: no extra pass)."""
     if aff:
-        return ops.hie_affinity(dti, Vh, N, L, T, x2=Qh, y2=dtq, epi=2, yprev=C, drop=drop, out=out)
+        return ops.hie_affinity(dti, Vh, N, L, T, x2=Qh, y2=dtq, epi=2, yprev=C, drop=drop, out=out, lens=lens)
     E = Vh.shape[1]
     dC = ops.bgemm(dti.view(N, T, E), Vh.view(N, L, E), out=out)
     ops.bgemm(Qh.view(N, T, E), dtq.view(N, L, E), out=dC, accumulate=True)
-    ops.tanh_dropout_bwd(dC.view(N * T, L), C.view(N * T, L), *drop, out=dC.view(N * T, L))
+    if lens is not None:
+        if drop[0] is not None or drop[2] != 0.0:
+            raise ops._l.VqfError("_hie_dc: lens without dropout on C only")
+        ops.tanh_bwd_rows_len(dC, C, lens, N, T, out=dC)
+    else:
+        ops.tanh_dropout_bwd(dC.view(N * T, L), C.view(N * T, L), *drop, out=dC.view(N * T, L))
     return dC
 
 

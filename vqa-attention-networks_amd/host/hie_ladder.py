@@ -17,8 +17,24 @@ equations below are the specification, restated line by line in tests/hie_ladder
     h_w = tanh(ans_w(drop(q_0 + v_0)));  h_p = tanh(ans_p(drop([q_1 + v_1, h_w])))
     h_s = tanh(ans_s(drop([q_2 + v_2, h_p])));  logits = ans_h(drop(h_s))
 
-`drop` is dropout with rate drop_p in train mode only.  Padded words are NOT masked (as in HieCoAtten): a padding id is an
-ordinary word of the vocabulary at every level.
+`drop` is dropout with rate drop_p in train mode only.
+
+Question lengths.  forward(img, ids, q_length) -- the call form of the reference's training loop (solver.py:84-89,
+model.forward(i, q, q_l)) -- takes the loader's (N,) lengths (data_loader.py:34,45; questions are padded on the right up to
+T words, utils.py:185-196).  With valid[n, t] = t < len[n] (len clamped to [1, T] on the device, never read on the host):
+
+    Qw  = valid * drop(tanh(word_emb(ids)))
+    u_k[t] = b_k + sum_{j<k, t+j<len[n]} W_k[:, :, j] Qw[t+j]           (the window stops at the real end)
+    Qp  = valid * max_k tanh(u_k)
+    Qs  = valid * sent_lstm(Qp)                                         (causal: real steps never see padding)
+    per level: C[t, :] = 0 for padded t (Cq and Qh have no bias, so zero Q rows give it); aq = softmax over t < len[n] only,
+               exactly 0 elsewhere; q_i = sum_{t<len} aq[t] Q[t]; the image side unchanged in form
+
+so a padded batch gives, sample by sample, what the unmasked model gives on that sample alone cut to its own length: the
+padding ids do not matter, the padding id's embedding row gets no gradient, and every gradient of a padded row (dQw, dQp,
+dQs, dC, dHq, the phrase taps' dZ) is an exact zero.  The lengths ride in the passes that stream these tensors anyway (the
+*_len entry points of include/vqa_fusion.h): no extra launch, no torch op on an (N*T, E) or (N, T, L) tensor.  q_length=None
+is the unmasked model: a padding id is then an ordinary word of the vocabulary at every level (as in HieCoAtten).
 
 Stages (every product and every pass over an (N*L, .) or (N*T, .) tensor runs in libvqa_fusion.so):
   * img_emb / word embedding: LinearFn + TanhDropFn, EmbedTanhFn + DropoutFn;
@@ -44,31 +60,32 @@ class PhraseFn(torch.autograd.Function):
     """Qp = max_k tanh(conv_k(Qw) + b_k) over the n-gram sizes k = 1, 2, 3 (right zero padding).  qw (N*T, E) contiguous;
     w_k (E, E, k), b_k (E) the nn.Conv1d parameters.  Forward: Z = qw Wcat^T with the six taps stacked (one GEMM), then one
     streaming pass (vqf_phrase_ngram_fwd) that also records the winning k.  Backward: dZ gathered from the winners
-    (vqf_phrase_ngram_bwd), dqw and dWcat as GEMMs, the bias gradients as column sums of dZ."""
+    (vqf_phrase_ngram_bwd), dqw and dWcat as GEMMs, the bias gradients as column sums of dZ.
+    lens ((N,) int32 or None): the windows stop at lens[n], padded rows of Qp and of dZ are zero (the *_len kernels)."""
 
     @staticmethod
-    def forward(ctx, qw, w1, b1, w2, b2, w3, b3, N, T):
+    def forward(ctx, qw, w1, b1, w2, b2, w3, b3, N, T, lens=None):
         E = qw.shape[1]
         wcat = torch.cat([w1[:, :, 0], w2[:, :, 0], w2[:, :, 1], w3[:, :, 0], w3[:, :, 1], w3[:, :, 2]], 0).contiguous()
         bcat = torch.cat([b1, b2, b3], 0).contiguous()
         Z = ops.gemm(qw, wcat)                                     # (N*T, 6E)
-        qp, idx = ops.phrase_ngram_fwd(Z, bcat, N, T)
+        qp, idx = ops.phrase_ngram_fwd(Z, bcat, N, T, lens=lens)
         ctx.save_for_backward(qw, wcat, qp, idx)
-        ctx.dims = (N, T, E)
+        ctx.dims, ctx.lens = (N, T, E), lens
         return qp
 
     @staticmethod
     def backward(ctx, dqp):
         qw, wcat, qp, idx = ctx.saved_tensors
         N, T, E = ctx.dims
-        dZ = ops.phrase_ngram_bwd(_c(dqp), qp, idx, N, T)
+        dZ = ops.phrase_ngram_bwd(_c(dqp), qp, idx, N, T, lens=ctx.lens)
         dqw = ops.gemm(dZ, wcat, tb=True)                         # (N*T, E)
         dW = ops.gemm(dZ, qw, ta=True, tb=True)                   # (6E, E)
         db = ops.colsum(dZ)
         dw1 = dW[:E].unsqueeze(2).contiguous()
         dw2 = torch.stack([dW[E:2 * E], dW[2 * E:3 * E]], 2)
         dw3 = torch.stack([dW[3 * E:4 * E], dW[4 * E:5 * E], dW[5 * E:6 * E]], 2)
-        return dqw, dw1, db[:E], dw2, db[E:2 * E], dw3, db[3 * E:4 * E], None, None
+        return dqw, dw1, db[:E], dw2, db[E:2 * E], dw3, db[3 * E:4 * E], None, None, None
 
 
 class LadderCoattFn(torch.autograd.Function):
@@ -82,13 +99,17 @@ class LadderCoattFn(torch.autograd.Function):
     logits of all levels with a block-diagonal (3, 3E) weight and ONE G = 3 pooling pass over V.  Where the streaming
     passes do not take the shape (T > 16) the T-row products run on the batched GEMM and the element-wise kernels.
     Backward: the same stages in reverse; dC_i = (dti_i Vh_i^T + Qh_i dtq_i^T)(1 - C_i^2) in one affinity pass (all levels
-    in one launch where the LDS holds them, one launch per level otherwise)."""
+    in one launch where the LDS holds them, one launch per level otherwise).
+    lens ((N,) int32 or None; q0 / q1 / q2 come with zero rows at t >= lens[n]): the question-side poolings take the softmax
+    over the real words, and the dC stage writes zero rows for the padded ones on every route -- with those, every other
+    stage's padded rows are zero by its own arithmetic (bias-free products of zero rows, tanh(0) = 0)."""
 
     STREAM = True      # the T-row stages as streaming passes where supported; False: batched GEMMs + element-wise (A/B)
 
     @staticmethod
-    def forward(ctx, V, q0, q1, q2, N, L, T, *w):
+    def forward(ctx, V, q0, q1, q2, N, L, T, lens, *w):
         E = V.shape[1]
+        lk = {} if lens is None else {"lens": lens}
         M, MT = N * L, N * T
         dev = V.device
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
@@ -121,12 +142,12 @@ class LadderCoattFn(torch.autograd.Function):
         av, vcat = ops.glimpse_pool_fwd(V.view(N, L, E), ops.att_logits_fwd(Hv, wblk, zb3), False)   # (N, 3, L), (N, 3E)
         aq, qo = [], []
         for g in range(3):
-            a_g, q_g = ops.glimpse_pool_fwd(Q[g].view(N, T, E), ops.att_logits_fwd(Hq[g], whq[g], zb1), False)
+            a_g, q_g = ops.glimpse_pool_fwd(Q[g].view(N, T, E), ops.att_logits_fwd(Hq[g], whq[g], zb1), False, **lk)
             aq.append(a_g)
             qo.append(q_g)
         ctx.save_for_backward(V, q0, q1, q2, wv_cat, wq2[0], wq2[1], wq2[2], wblk, whq[0], whq[1], whq[2], Vh, CQ, C, Hv, Hq, av,
                               aq[0], aq[1], aq[2])
-        ctx.dims, ctx.stream = (N, L, T, E), stream
+        ctx.dims, ctx.stream, ctx.lens = (N, L, T, E), stream, lens
         ctx.set_materialize_grads(False)
         return (vcat, qo[0], qo[1], qo[2], av, aq[0], aq[1], aq[2])
 
@@ -140,7 +161,8 @@ class LadderCoattFn(torch.autograd.Function):
         zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
         Q, wq2, whq, aq = (q0, q1, q2), (wq0, wq1, wq2_), (whq0, whq1, whq2), (aq0, aq1, aq2)
         dq, daq = (dq0, dq1, dq2), (daq0, daq1, daq2)
-        stream = ctx.stream
+        stream, lens = ctx.stream, ctx.lens
+        lk = {} if lens is None else {"lens": lens}
         dCQ = new(MT, 6 * E)                                                        # [dCq_0 | dQh_0 | ...]
         dti = new(MT, 3 * E)
         dQ, dwhq = [], []
@@ -148,7 +170,7 @@ class LadderCoattFn(torch.autograd.Function):
         for g in range(3):
             dqg = _c(dq[g]) if dq[g] is not None else zeros(N, E)
             dl, dQg = ops.glimpse_pool_bwd(dqg, Q[g].view(N, T, E), aq[g], False, True,
-                                           dwts=None if daq[g] is None else _c(daq[g]))
+                                           dwts=None if daq[g] is None else _c(daq[g]), **lk)
             dHq, dw, _, _ = ops.att_logits_bwd(dl, Hq[g], whq[g], relu_mask=False)
             ops.tanh_dropout_bwd2d(dHq, Hq[g], *_NODROP, out=dti[:, g * E:(g + 1) * E])   # d(Qh_i + ti_i)
             if not stream:
@@ -163,12 +185,13 @@ class LadderCoattFn(torch.autograd.Function):
         dVh = ops.tanh_dropout_bwd2d(dHv, Hv, *_NODROP, out=dHv)                   # dtq_i = d(Vh_i + tq_i); dVh_i below
         dC = new(3, N, T, L)
         if stream and ops.hie_affinity_levels_supported(N, L, E, T, 3, 2):
-            ops.hie_affinity_levels(dti, E, Vh, E, 3, N, L, T, E, x2=CQ[:, E:], lvx2=2 * E, y2=dVh, lvy2=E, epi=2, yprev=C, out=dC)
+            ops.hie_affinity_levels(dti, E, Vh, E, 3, N, L, T, E, x2=CQ[:, E:], lvx2=2 * E, y2=dVh, lvy2=E, epi=2, yprev=C, out=dC,
+                                    **lk)
         else:                      # per level (E = 512: three levels x two pairs exceed the LDS: one two-pair launch each)
             aff = stream and ops.hie_affinity_supported(N, L, E, T, 2)
             for g in range(3):
                 _hie_dc(dti[:, g * E:(g + 1) * E], Vh[:, g * E:(g + 1) * E], CQ[:, (2 * g + 1) * E:(2 * g + 2) * E],
-                        dVh[:, g * E:(g + 1) * E], C[g], _NODROP, N, L, T, aff, out=dC[g])
+                        dVh[:, g * E:(g + 1) * E], C[g], _NODROP, N, L, T, aff, out=dC[g], **lk)
         if stream:
             S = ops.hie_chunks(N, L)
             part, scratch = new(S, MT, E), new(M, E)
@@ -194,7 +217,7 @@ class LadderCoattFn(torch.autograd.Function):
             ops.gemm(blk, wq2[g], tb=True, out=dQ[g], accumulate=True)
             dwq2 = ops.gemm(blk, Q[g], ta=True, tb=True)                           # (2E, E) = [dWb; dWq]
             grads += [dwq2[:E], dwv[g * E:(g + 1) * E], dwq2[E:], dwblk[g:g + 1, g * E:(g + 1) * E].contiguous(), dwhq[g]]
-        return (dV, dQ[0], dQ[1], dQ[2], None, None, None, *grads)
+        return (dV, dQ[0], dQ[1], dQ[2], None, None, None, None, *grads)
 
 
 class _Coatt(nn.Module):
@@ -210,11 +233,17 @@ class _Coatt(nn.Module):
 
 
 class HieCoAttenLadder(nn.Module):
-    """forward(img_features (N, L, img_size) fp32 GPU, que_features (N, T) int64 GPU)
+    """forward(img_features (N, L, img_size) fp32 GPU, que_features (N, T) int64 GPU, q_length=None)
     -> (logits (N, output_size), av (N, 3, L), aq (N, 3, T)); levels ordered word, phrase, sentence.
 
+    q_length: (N,) int64 or int32 on the same GPU, the real words of each right-padded question (the loader's q_l; the
+    reference's training loop calls model.forward(i, q, q_l)).  Padding is then masked at every level: the result of a sample
+    does not depend on the pad width or the padding ids, aq has exact zeros at the padded positions, the padding id's embedding
+    row gets no gradient.  Values are clamped to [1, T] on the device; the lengths are never read on the host.  None: no masking
+    (every id is a word), bit for bit the two-argument model.
+
     The image features are data (img_features.requires_grad raises), fp32 on the GPU: CPU tensors and bf16 features raise
-    VqfError -- there is no CPU fallback.  Padded words are not masked.  Dropout (rate drop_p) is active in train mode only;
+    VqfError -- there is no CPU fallback.  Dropout (rate drop_p) is active in train mode only;
     set_keep_masks() supplies explicit uint8 keep-masks for the tests, otherwise the kernels draw Philox masks."""
 
     def __init__(self, block_num=196, word_num=22, img_size=2048, vocab_size=15881, embed_size=512, hidden_size=1024,
@@ -247,7 +276,7 @@ class HieCoAttenLadder(nn.Module):
             return x
         return DropoutFn.apply(_c(x), keep, seed, self.drop_p if keep is not None else p)
 
-    def forward(self, img_features, que_features):
+    def forward(self, img_features, que_features, q_length=None):
         if not img_features.is_cuda or not que_features.is_cuda:
             raise VqfError("HieCoAttenLadder needs GPU tensors (the HIP extension is the only path; no CPU fallback)")
         if img_features.dtype != torch.float32:
@@ -263,25 +292,35 @@ class HieCoAttenLadder(nn.Module):
             raise VqfError("HieCoAttenLadder: embed_size %% 32 == 0, T <= 32 and L <= 1024 are supported (got E=%d, T=%d, L=%d)"
                            % (E, T, L))
         M, MT = N * L, N * T
+        lens = None
+        if q_length is not None:
+            if not torch.is_tensor(q_length) or q_length.dtype not in (torch.int64, torch.int32):
+                raise VqfError("HieCoAttenLadder: q_length must be an int64 or int32 tensor")
+            if tuple(q_length.shape) != (N,):
+                raise VqfError("HieCoAttenLadder: q_length must have shape (N,) = (%d,), got %s" % (N, tuple(q_length.shape)))
+            if q_length.device != que_features.device:
+                raise VqfError("HieCoAttenLadder: q_length must be on the questions' device (%s), got %s"
+                               % (que_features.device, q_length.device))
+            lens = q_length.clamp(1, T).to(torch.int32).contiguous()            # O(N), on the device: nothing is read back
         # V = drop(tanh(img_emb(img)))
         seed, p = self._seeds.next(self.training, self.drop_p)
         keep = self._seeds.keep.get("img") if self.training else None
         V = LinearFn.apply(_c(img_features).view(M, D), self.img_emb.weight, self.img_emb.bias, False)
         V = TanhDropFn.apply(V, None, keep, seed, self.drop_p if keep is not None else p)
         # Qw = drop(tanh(word_emb(ids)))
-        qw = EmbedTanhFn.apply(que_features, self.word_emb.weight, True, False).view(MT, E)
+        qw = EmbedTanhFn.apply(que_features, self.word_emb.weight, True, False, lens).view(MT, E)
         qw = self._drop(qw, "word")
         # phrase level
         qp = PhraseFn.apply(qw, self.phrase_uni.weight, self.phrase_uni.bias, self.phrase_bi.weight, self.phrase_bi.bias,
-                            self.phrase_tri.weight, self.phrase_tri.bias, N, T)
+                            self.phrase_tri.weight, self.phrase_tri.bias, N, T, lens)
         # sentence level: the HIP LSTM over time-major rows (the re-layouts are dropout passes at rate 0)
         lstm = self.sent_lstm
         xt = DropoutBTFn.apply(qp.view(N, T, E).transpose(0, 1), None, 0, 0.0)            # (T, N, E) contiguous
         hs = LstmBatchFn.apply(xt, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, False)
-        qs = DropoutBTFn.apply(hs.transpose(0, 1), None, 0, 0.0).view(MT, E)            # (N*T, E)
+        qs = DropoutBTFn.apply(hs.transpose(0, 1), None, 0, 0.0, lens).view(MT, E)      # (N*T, E), zero rows past the last word
         # the three co-attention levels
         w = [p_ for c in self.coatt for p_ in (c.Wb.weight, c.Wv.weight, c.Wq.weight, c.whv.weight, c.whq.weight)]
-        vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, *w)
+        vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, *w)
         v0, v1, v2 = vcat[:, :E], vcat[:, E:2 * E], vcat[:, 2 * E:]
         th = lambda x: TanhDropFn.apply(x, None, None, 0, 0.0)
         lin = lambda x, m: LinearFn.apply(_c(x), m.weight, m.bias, False)

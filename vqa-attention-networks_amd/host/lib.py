@@ -91,6 +91,20 @@ SIGNATURES = {
     "vqf_hie_affinity_levels_supported": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i]),
     "vqf_hie_affinity_levels": (c_i, [c_f, c_i, c_i, c_f, c_i, c_i, c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i,
                                       c_f, c_p]),
+    # the question-length forms of HieCoAttenLadder (lens: device int32 pointer, c_p)
+    "vqf_embed_tanh_fwd_len": (c_i, [c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p]),
+    "vqf_embed_tanh_bwd_len": (c_i, [c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p]),
+    "vqf_phrase_ngram_fwd_len": (c_i, [c_f, c_i, c_f, c_p, c_i, c_i, c_i, c_f, c_i, c_p, c_p]),
+    "vqf_phrase_ngram_bwd_len": (c_i, [c_f, c_i, c_f, c_i, c_p, c_p, c_i, c_i, c_i, c_f, c_i, c_p]),
+    "vqf_dropout_bt_len": (c_i, [c_f, ctypes.c_longlong, ctypes.c_longlong, c_p, c_u64, ctypes.c_float, c_p, c_i, c_i, c_i, c_f,
+                                 ctypes.c_longlong, ctypes.c_longlong, c_p]),
+    "vqf_glimpse_pool_fwd_len": (c_i, [c_f, c_f, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
+    "vqf_glimpse_pool_bwd_len": (c_i, [c_f, c_f, c_f, c_f, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
+    "vqf_hie_affinity_len": (c_i, [c_f, c_i, c_f, c_i, c_f, c_i, c_f, c_i, c_i, c_f, c_p, c_u64, ctypes.c_float, c_p, c_i, c_i, c_i,
+                                   c_i, c_f, c_p]),
+    "vqf_hie_affinity_levels_len": (c_i, [c_f, c_i, c_i, c_f, c_i, c_i, c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_p, c_i, c_i,
+                                          c_i, c_i, c_f, c_p]),
+    "vqf_tanh_bwd_rows_len": (c_i, [c_f, c_f, c_p, c_i, c_i, c_i, c_f, c_p]),
     "vqf_softmax_rows_fwd": (c_i, [c_f, c_i, c_i, c_f, c_p]),
     "vqf_softmax_rows_bwd": (c_i, [c_f, c_f, c_i, c_i, c_f, c_p]),
     "vqf_log_softmax_rows_fwd": (c_i, [c_f, c_i, c_i, c_f, c_p]),

@@ -362,8 +362,17 @@ def att_logits_bwd(dlogits, hid, w2, relu_mask=True, rowscale=None, rows_per_sca
     return dpre, dw2, db2, db1
 
 
-def glimpse_pool_fwd(feat, logits, unit_softmax, pooled_out=None):
-    """feat (N,S,C) fp32 | bf16, logits (N*S,G) -> wts (N,G,S), pooled (N,G*C) (fp32; pooled_out: written there)."""
+def _chk_lens(lens, N, what):
+    """lens of the question-length forms (include/vqa_fusion.h *_len): None, or a contiguous (N,) int32 GPU tensor"""
+    if lens is None:
+        return
+    if not lens.is_cuda or lens.dtype != torch.int32 or not lens.is_contiguous() or tuple(lens.shape) != (N,):
+        raise _l.VqfError(what + ": lens must be a contiguous (N,) int32 GPU tensor")
+
+
+def glimpse_pool_fwd(feat, logits, unit_softmax, pooled_out=None, lens=None):
+    """feat (N,S,C) fp32 | bf16, logits (N*S,G) -> wts (N,G,S), pooled (N,G*C) (fp32; pooled_out: written there).
+    lens (N) int32 (fp32 feat): the softmax runs over the first lens[n] positions, the weights beyond are exact zeros."""
     bf = feat.dtype == torch.bfloat16
     (_chk_bf16 if bf else _chk)(feat)
     if not feat.is_contiguous():
@@ -379,27 +388,40 @@ def glimpse_pool_fwd(feat, logits, unit_softmax, pooled_out=None):
         pooled = pooled_out
     else:
         pooled = torch.empty((N, G * C), dtype=torch.float32, device=feat.device)
+    if lens is not None:
+        if bf:
+            raise _l.VqfError("glimpse_pool_fwd: lens with a bf16 feature tensor")
+        _chk_lens(lens, N, "glimpse_pool_fwd")
+        _l.check(_lib().vqf_glimpse_pool_fwd_len(_ptr(feat), _ptr(logits), _ptr(lens), N, S, C, G, int(bool(unit_softmax)),
+                                                 _ptr(wts), _ptr(pooled), _stream()), "vqf_glimpse_pool_fwd_len")
+        return wts, pooled
     fn = _lib().vqf_glimpse_pool_fwd_bf16 if bf else _lib().vqf_glimpse_pool_fwd
     _l.check(fn(_ptr(feat), _ptr(logits), N, S, C, G, int(bool(unit_softmax)), _ptr(wts), _ptr(pooled), _stream()),
              "vqf_glimpse_pool_fwd")
     return wts, pooled
 
 
-def glimpse_pool_bwd(dpooled, feat, wts, unit_softmax, want_dfeat, dwts=None):
+def glimpse_pool_bwd(dpooled, feat, wts, unit_softmax, want_dfeat, dwts=None, lens=None):
     _chk(dpooled, wts, dwts)
     N, S, C = feat.shape
     G = wts.shape[1]
     dlogits = torch.empty((N * S, G), dtype=torch.float32, device=feat.device)
     if feat.dtype == torch.bfloat16:             # bf16 feature storage: the tensor is data
         _chk_bf16(feat)
-        if want_dfeat:
-            raise _l.VqfError("glimpse_pool_bwd: a bf16 feature tensor cannot receive a gradient")
+        if want_dfeat or lens is not None:
+            raise _l.VqfError("glimpse_pool_bwd: a bf16 feature tensor cannot receive a gradient or take lens")
         _l.check(_lib().vqf_glimpse_pool_bwd_bf16(_ptr(dpooled), _ptr(dwts), _ptr(feat), _ptr(wts), N, S, C, G,
                                                   int(bool(unit_softmax)), _ptr(dlogits), _stream()),
                  "vqf_glimpse_pool_bwd_bf16")
         return dlogits, None
     _chk(feat)
     dfeat = torch.empty_like(feat) if want_dfeat else None
+    if lens is not None:                         # dlogits and dfeat of the positions >= lens[n] are exact zeros
+        _chk_lens(lens, N, "glimpse_pool_bwd")
+        _l.check(_lib().vqf_glimpse_pool_bwd_len(_ptr(dpooled), _ptr(dwts), _ptr(feat), _ptr(wts), _ptr(lens), N, S, C, G,
+                                                 int(bool(unit_softmax)), _ptr(dlogits), _ptr(dfeat), _stream()),
+                 "vqf_glimpse_pool_bwd_len")
+        return dlogits, dfeat
     _l.check(_lib().vqf_glimpse_pool_bwd(_ptr(dpooled), _ptr(dwts), _ptr(feat), _ptr(wts), N, S, C, G,
                                          int(bool(unit_softmax)), _ptr(dlogits), _ptr(dfeat), _stream()),
              "vqf_glimpse_pool_bwd")
@@ -414,15 +436,21 @@ def dropout(x, keep=None, seed=0, p_drop=0.5, out=None):
     return y
 
 
-def dropout_bt(x, out, keep=None, seed=0, p_drop=0.0):
+def dropout_bt(x, out, keep=None, seed=0, p_drop=0.0, lens=None):
     """out[b,t,:] = x[b,t,:] * keep / (1 - p) for 3-D fp32 tensors of the same (B, T, H) shape with ANY strides on the first two
-    axes (a transposed view in, a contiguous tensor out, or the other way round); the mask is indexed by (b, t, h)."""
+    axes (a transposed view in, a contiguous tensor out, or the other way round); the mask is indexed by (b, t, h).
+    lens (B) int32: rows t >= lens[b] of out are zero."""
     for t_ in (x, out):
         if not t_.is_cuda or t_.dtype != torch.float32 or t_.dim() != 3 or t_.stride(2) != 1:
             raise _l.VqfError("dropout_bt: 3-D fp32 GPU tensors with a contiguous last axis expected")
     if x.shape != out.shape:
         raise _l.VqfError("dropout_bt: shapes differ")
     B, T, H = x.shape
+    if lens is not None:
+        _chk_lens(lens, B, "dropout_bt")
+        _l.check(_lib().vqf_dropout_bt_len(_ptr(x), x.stride(0), x.stride(1), _keep_ptr(keep), int(seed), float(p_drop), _ptr(lens),
+                                           B, T, H, _ptr(out), out.stride(0), out.stride(1), _stream()), "vqf_dropout_bt_len")
+        return out
     _l.check(_lib().vqf_dropout_bt(_ptr(x), x.stride(0), x.stride(1), _keep_ptr(keep), int(seed), float(p_drop), B, T, H,
                                    _ptr(out), out.stride(0), out.stride(1), _stream()), "vqf_dropout_bt")
     return out
@@ -441,6 +469,18 @@ def tanh_dropout_bwd(dy, y, keep=None, seed=0, p_drop=0.5, out=None):
     dx = torch.empty_like(y) if out is None else out          # in place (out is dy) allowed
     _l.check(_lib().vqf_tanh_dropout_bwd(_ptr(dy), _ptr(y), _keep_ptr(keep), int(seed), float(p_drop),
                                          y.numel(), _ptr(dx), _stream()), "vqf_tanh_dropout_bwd")
+    return dx
+
+
+def tanh_bwd_rows_len(dy, y, lens, N, T, out=None):
+    """dx = dy (1 - y^2) on the rows t < lens[n] of contiguous (N, T, L) tensors, zero on the others (in place allowed)"""
+    _chk(dy, y, out)
+    _chk_lens(lens, N, "tanh_bwd_rows_len")
+    if y.numel() % (N * T) or dy.numel() != y.numel():
+        raise _l.VqfError("tanh_bwd_rows_len: (N, T, L) tensors expected")
+    dx = torch.empty_like(y) if out is None else out
+    _l.check(_lib().vqf_tanh_bwd_rows_len(_ptr(dy), _ptr(y), _ptr(lens), int(N), int(T), y.numel() // (N * T), _ptr(dx), _stream()),
+             "vqf_tanh_bwd_rows_len")
     return dx
 
 
@@ -650,14 +690,21 @@ def _aff_operands(name, x1, y1, x2, y2, yprev, out, dims):
     return out, (x2.stride(0) if x2 is not None else 0), (y2.stride(0) if y2 is not None else 0)
 
 
-def hie_affinity(x1, y1, N, L, T, x2=None, y2=None, epi=0, yprev=None, drop=(None, 0, 0.0), out=None):
+def hie_affinity(x1, y1, N, L, T, x2=None, y2=None, epi=0, yprev=None, drop=(None, 0, 0.0), out=None, lens=None):
     """out (N, T, L) = epi(x1 y1^T [+ x2 y2^T]) per sample: x* rows n*T + t, y* rows n*L + l (2-D, rows may be strided).
-    epi 0: the sums; 1: dropout(tanh(.)) with `drop` = (keep | None, seed, p); 2: the backward of epi 1 given its output yprev."""
+    epi 0: the sums; 1: dropout(tanh(.)) with `drop` = (keep | None, seed, p); 2: the backward of epi 1 given its output yprev.
+    lens (N) int32: rows t >= lens[n] of out are zero."""
     out, sx2, sy2 = _aff_operands("hie_affinity", x1, y1, x2, y2, yprev, out, (N, T, L))
     E = x1.shape[1]
     if y1.shape[1] != E or (x2 is not None and (x2.shape[1] != E or y2.shape[1] != E)):
         raise _l.VqfError("hie_affinity: operand shapes")
     keep, seed, p = drop
+    if lens is not None:
+        _chk_lens(lens, N, "hie_affinity")
+        _l.check(_lib().vqf_hie_affinity_len(_ptr(x1), x1.stride(0), _ptr(y1), y1.stride(0), _ptr(x2), sx2, _ptr(y2), sy2, int(epi),
+                                             _ptr(yprev), _keep_ptr(keep), int(seed), float(p), _ptr(lens), N, L, E, T, _ptr(out),
+                                             _stream()), "vqf_hie_affinity_len")
+        return out
     _l.check(_lib().vqf_hie_affinity(_ptr(x1), x1.stride(0), _ptr(y1), y1.stride(0), _ptr(x2), sx2, _ptr(y2), sy2, int(epi),
                                      _ptr(yprev), _keep_ptr(keep), int(seed), float(p), N, L, E, T, _ptr(out), _stream()),
              "vqf_hie_affinity")
@@ -681,9 +728,9 @@ def phrase_ngram_supported(T, E):
     return bool(_lib().vqf_phrase_ngram_supported(int(T), int(E)))
 
 
-def phrase_ngram_fwd(Z, bias, N, T, out=None, idx=None):
+def phrase_ngram_fwd(Z, bias, N, T, out=None, idx=None, lens=None):
     """Z (N*T, 6E) = Qw Wcat^T (rows may be strided), bias (3E) = [b1 | b2 | b3] -> (Qp (N*T, E), idx (N*T, E) uint8):
-    Qp = tanh(max_k u_k), idx = the winning k - 1"""
+    Qp = tanh(max_k u_k), idx = the winning k - 1.  lens (N) int32: the windows stop at lens[n]; rows t >= lens[n]: Qp = 0, idx = 3"""
     _chk2s(Z, out)
     _chk(bias)
     E = Z.shape[1] // 6
@@ -693,19 +740,29 @@ def phrase_ngram_fwd(Z, bias, N, T, out=None, idx=None):
         out = torch.empty((N * T, E), dtype=torch.float32, device=Z.device)
     if idx is None:
         idx = torch.empty((N * T, E), dtype=torch.uint8, device=Z.device)
+    if lens is not None:
+        _chk_lens(lens, N, "phrase_ngram_fwd")
+        _l.check(_lib().vqf_phrase_ngram_fwd_len(_ptr(Z), Z.stride(0), _ptr(bias), _ptr(lens), int(N), int(T), int(E), _ptr(out),
+                                                 out.stride(0), _ptr(idx), _stream()), "vqf_phrase_ngram_fwd_len")
+        return out, idx
     _l.check(_lib().vqf_phrase_ngram_fwd(_ptr(Z), Z.stride(0), _ptr(bias), int(N), int(T), int(E), _ptr(out), out.stride(0),
                                          _ptr(idx), _stream()), "vqf_phrase_ngram_fwd")
     return out, idx
 
 
-def phrase_ngram_bwd(dQp, Qp, idx, N, T, out=None):
-    """-> dZ (N*T, 6E): the gradient of Z gathered from du = dQp (1 - Qp^2) at the winning taps"""
+def phrase_ngram_bwd(dQp, Qp, idx, N, T, out=None, lens=None):
+    """-> dZ (N*T, 6E): the gradient of Z gathered from du = dQp (1 - Qp^2) at the winning taps (lens: zero rows for t >= lens[n])"""
     _chk2s(dQp, Qp, out)
     E = Qp.shape[1]
     if not idx.is_cuda or idx.dtype != torch.uint8 or not idx.is_contiguous() or idx.shape != (N * T, E):
         raise _l.VqfError("phrase_ngram_bwd: idx must be a contiguous (N*T, E) uint8 GPU tensor")
     if out is None:
         out = torch.empty((N * T, 6 * E), dtype=torch.float32, device=Qp.device)
+    if lens is not None:
+        _chk_lens(lens, N, "phrase_ngram_bwd")
+        _l.check(_lib().vqf_phrase_ngram_bwd_len(_ptr(dQp), dQp.stride(0), _ptr(Qp), Qp.stride(0), _ptr(idx), _ptr(lens), int(N), int(T),
+                                                 int(E), _ptr(out), out.stride(0), _stream()), "vqf_phrase_ngram_bwd_len")
+        return out
     _l.check(_lib().vqf_phrase_ngram_bwd(_ptr(dQp), dQp.stride(0), _ptr(Qp), Qp.stride(0), _ptr(idx), int(N), int(T), int(E),
                                          _ptr(out), out.stride(0), _stream()), "vqf_phrase_ngram_bwd")
     return out
@@ -715,11 +772,19 @@ def hie_affinity_levels_supported(N, L, E, T, G, pairs=1):
     return bool(_lib().vqf_hie_affinity_levels_supported(int(N), int(L), int(E), int(T), int(G), int(pairs)))
 
 
-def hie_affinity_levels(x1, lvx1, y1, lvy1, G, N, L, T, E, x2=None, lvx2=0, y2=None, lvy2=0, epi=0, yprev=None, out=None):
+def hie_affinity_levels(x1, lvx1, y1, lvy1, G, N, L, T, E, x2=None, lvx2=0, y2=None, lvy2=0, epi=0, yprev=None, out=None,
+                        lens=None):
     """out (G, N, T, L): level g = epi(X1_g Y1_g^T [+ X2_g Y2_g^T]) per sample, X_g = the E columns of x at offset g * lvx (rows
     n*T + t), Y_g those of y at g * lvy (rows n*L + l; lvy = 0: one y shared by the levels).  2-D operands, rows may be strided.
-    epi 0: the sums; 1: tanh; 2: sums * (1 - yprev^2)."""
+    epi 0: the sums; 1: tanh; 2: sums * (1 - yprev^2).  lens (N) int32: rows t >= lens[n] of every level are zero."""
     out, sx2, sy2 = _aff_operands("hie_affinity_levels", x1, y1, x2, y2, yprev, out, (G, N, T, L))
+    if lens is not None:
+        _chk_lens(lens, N, "hie_affinity_levels")
+        _l.check(_lib().vqf_hie_affinity_levels_len(_ptr(x1), x1.stride(0), int(lvx1), _ptr(y1), y1.stride(0), int(lvy1),
+                                                    _ptr(x2), sx2, int(lvx2), _ptr(y2), sy2, int(lvy2), int(G), int(epi), _ptr(yprev),
+                                                    _ptr(lens), int(N), int(L), int(E), int(T), _ptr(out), _stream()),
+                 "vqf_hie_affinity_levels_len")
+        return out
     _l.check(_lib().vqf_hie_affinity_levels(_ptr(x1), x1.stride(0), int(lvx1), _ptr(y1), y1.stride(0), int(lvy1),
                                             _ptr(x2), sx2, int(lvx2), _ptr(y2), sy2, int(lvy2), int(G), int(epi), _ptr(yprev),
                                             int(N), int(L), int(E), int(T), _ptr(out), _stream()), "vqf_hie_affinity_levels")
@@ -926,13 +991,23 @@ def _chk_ids(ids):
         raise _l.VqfError("contiguous int64 GPU token ids expected")
 
 
-def embed_tanh_fwd(weight, ids, tanh=True, time_major=False):
+def embed_tanh_fwd(weight, ids, tanh=True, time_major=False, lens=None):
     """tanh(weight[ids]) (tanh=False: weight[ids]): weight (V,E) fp32, ids any shape int64 -> ids.shape + (E,);
-    time_major (ids (N,Tq), tanh only): -> (Tq, N, E), the rows in the order the batch-major LSTM walks them"""
+    time_major (ids (N,Tq), tanh only): -> (Tq, N, E), the rows in the order the batch-major LSTM walks them;
+    lens (N) int32 (ids (N,Tq), tanh, sample-major): the rows of the tokens at positions >= lens[n] are zero"""
     _chk(weight)
     _chk_ids(ids)
     V, E = weight.shape
     T = ids.numel()
+    if lens is not None:
+        if not tanh or time_major or ids.dim() != 2:
+            raise _l.VqfError("embed_tanh_fwd: lens goes with (N, Tq) ids, tanh and sample-major rows")
+        N, Tq = ids.shape
+        _chk_lens(lens, N, "embed_tanh_fwd")
+        out = torch.empty((N, Tq, E), dtype=torch.float32, device=weight.device)
+        _l.check(_lib().vqf_embed_tanh_fwd_len(_ptr(weight), ctypes.c_void_p(ids.data_ptr()), _ptr(lens), N, Tq, V, E, _ptr(out),
+                                               _stream()), "vqf_embed_tanh_fwd_len")
+        return out
     if time_major:
         if not tanh or ids.dim() != 2:
             raise _l.VqfError("embed_tanh_fwd: the time-major form takes (N, Tq) ids and applies tanh")
@@ -969,13 +1044,21 @@ def embed_dropout_bwd(dout, ids, V, keep=None, seed=0, p_drop=0.5):
     return dW
 
 
-def embed_tanh_bwd(dout, out, ids, V, time_major=False):
+def embed_tanh_bwd(dout, out, ids, V, time_major=False, lens=None):
     """-> dW (V,E): deterministic segment sum of dout * (1 - out^2) over the tokens of each id (out=None: of dout, the plain lookup);
-    time_major: dout / out are (Tq, N, E) for ids (N, Tq)"""
+    time_major: dout / out are (Tq, N, E) for ids (N, Tq); lens (N) int32: the tokens at positions >= lens[n] add to no row"""
     _chk(dout, out)
     _chk_ids(ids)
     E = dout.shape[-1]
     dW = torch.empty((V, E), dtype=torch.float32, device=dout.device)
+    if lens is not None:
+        if out is None or time_major or ids.dim() != 2:
+            raise _l.VqfError("embed_tanh_bwd: lens goes with (N, Tq) ids, tanh and sample-major rows")
+        N, Tq = ids.shape
+        _chk_lens(lens, N, "embed_tanh_bwd")
+        _l.check(_lib().vqf_embed_tanh_bwd_len(_ptr(dout), _ptr(out), ctypes.c_void_p(ids.data_ptr()), _ptr(lens), N, Tq, V, E,
+                                               _ptr(dW), _stream()), "vqf_embed_tanh_bwd_len")
+        return dW
     if time_major:
         N, Tq = ids.shape
         _l.check(_lib().vqf_embed_tanh_bwd_tm(_ptr(dout), _ptr(out), ctypes.c_void_p(ids.data_ptr()), N, Tq, V, E, _ptr(dW),
