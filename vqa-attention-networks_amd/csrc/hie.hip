@@ -430,7 +430,9 @@ int launch(int mode, HieArgs& g, const uint8_t* keep, uint64_t seed, float p, hi
   g.Lc = (g.L + g.S - 1) / g.S;
   g.S = (g.L + g.Lc - 1) / g.Lc;
   const size_t lds = lds_bytes(mode, g.E, g.T, g.Lc);
-  if (lds > 64 * 1024) return VQF_E_UNSUPPORTED;
+  // one predicate for all four passes, the one vqf_hie_stream_supported answers with (the forward's image is the largest): the
+  // head pass alone would fit E = 1024 at L = 196, and a caller asking `supported` first would never have sent it there
+  if (lds_bytes(MODE_FWD, g.E, g.T, g.Lc) > 64 * 1024) return VQF_E_UNSUPPORTED;
   if (g.S > 1 && (g.padd || (g.part && g.ldp != g.E))) return VQF_E_BADARG;     // several chunks: contiguous slabs, summed by vqf_hie_slab_sum
   const int nt = threads_for(g.E, g.Lc);
   g.keep = keep; g.seed = seed;
