@@ -526,6 +526,24 @@ int vqf_hie_affinity_levels_len(const float* x1, int ldx1, int ldx_level1, const
                                 void* stream);
 int vqf_tanh_bwd_rows_len(const float* dy, const float* y, const int* lens, int N, int T, int L, float* dx, void* stream);
 
+/* Guided attention logits (HieCoAttenLadder's alternating co-attention, coatt="alternating"; csrc/hie_ladder_alt.hip; additions
+ * within ABI 7).  Xh (N*S, row pitch ldx) holds G <= 3 attention steps over the same rows, step g at columns [g E, (g + 1) E);
+ * gp (N, G E) the per-sample guidance rows (NULL: none, H = tanh(Xh)); w (G, E).  The hidden activation
+ * H[r, g, :] = tanh(Xh[r, g E:(g + 1) E] + gp[r / S, g E:(g + 1) E]) is never stored:
+ *   fwd  logits (N*S, G) (the layout vqf_glimpse_pool_fwd takes) = sum_e w[g, e] H[r, g, e];
+ *   bwd  recomputes H; dXh (N*S, G E; row pitch lddx) = dlogits[r, g] w[g, e] (1 - H^2), dgp (N, G E) = sum_s dXh[n, s, :],
+ *        dw (G, E) = sum_r dlogits[r, g] H[r, g, :].  The sums run in a fixed order through ws (at least
+ *        vqf_guided_logits_bwd_ws_bytes), no atomics: two runs give the same bits.  A row whose dlogits are zero (a padded
+ *        question position out of vqf_glimpse_pool_bwd_len) gets a zero dXh row and adds nothing to dgp and dw.
+ * tanh is the fast form of the streaming kernels (absolute error ~1e-7).  Supported (vqf_guided_logits_supported):
+ * E % 32 == 0, E <= 1024, 1 <= S <= 1024 (any S), G in {1, 2, 3}, N <= 65535; 16-byte aligned operands, ldx % 4 == lddx % 4 == 0. */
+int vqf_guided_logits_supported(int N, int S, int E, int G);
+int vqf_guided_logits_fwd(const float* Xh, int ldx, const float* gp, const float* w, int N, int S, int E, int G, float* logits,
+                          void* stream);
+size_t vqf_guided_logits_bwd_ws_bytes(int N, int S, int E, int G);
+int vqf_guided_logits_bwd(const float* dlogits, const float* Xh, int ldx, const float* gp, const float* w, int N, int S, int E,
+                          int G, float* dXh, int lddx, float* dgp, float* dw, void* ws, size_t ws_bytes, void* stream);
+
 /* softmax over the last axis of (R,W) and its backward   modules.py:91-92 */
 int vqf_softmax_rows_fwd(const float* x, int R, int W, float* y, void* stream);
 int vqf_softmax_rows_bwd(const float* dy, const float* y, int R, int W, float* dx, void* stream);

@@ -1,12 +1,15 @@
 """Train step of HieCoAttenLadder (host/hie_ladder.py) at config 4's shapes: forward, CE loss, backward, the project's Adam.
 
-    python tools/hie_ladder_bench.py [--batch 256] [--steps 20] [--warmup 5] [--lengths] [--json OUT]
+    python tools/hie_ladder_bench.py [--batch 256] [--steps 20] [--warmup 5] [--lengths] [--coatt parallel|alternating] [--json OUT]
 
 Prints ms / step and QA pairs / s (device events around the timed steps), the step's FLOP count from the shapes with its
 MFMA floor at 157.3 TF/s (fp32 MFMA peak of the MI355X) and the fraction reached, the library profiler's per-kernel table
 of one extra step, and config 4's single-level HieCoAtten at the same shapes in the same process for context.
 --lengths: the masked step, forward(img, ids, q_length) with seeded question lengths in [3, T] (the products stay dense N*T
-rows: the FLOP count is the unmasked step's)."""
+rows: the FLOP count is the unmasked step's).
+--coatt alternating: the alternating co-attention model (its own FLOP table), and after it the streaming yardsticks of its
+image side in the same process: vqf_guided_logits_fwd / _bwd over the (N*L, 3E) projection beside vqf_att_logits_fwd over a
+tensor of the same size (the parallel mode's Hv pass: the same bytes read) and a device copy of that many bytes."""
 import argparse
 import json
 import os
@@ -36,6 +39,66 @@ def ladder_flops(N, L, D, E, T, H, O):
         "answer MLP (x3)": 3 * 2 * N * (E * E + 2 * E * E + 2 * E * H + H * O),
     }
     return f, sum(f.values())
+
+
+def ladder_alt_flops(N, L, D, E, T, H, O):
+    """the alternating step: the products as above, the (N, E) guidance-row products, and the streaming passes' VALU work
+    (guided logits: a dot product forward, the gradient row and two sums backward; the poolings likewise)"""
+    M, MT = N * L, N * T
+    rows = M * 3 * E + 2 * 3 * MT * E                                  # elements the attention steps stream: image + 2 x 3 question
+    f = {
+        "img_emb (fwd + wgrad)": 2 * 2 * M * D * E,
+        "VX = V [img_x0;img_x1;img_x2]^T (fwd + dgrad + wgrad)": 3 * 2 * M * E * 3 * E,
+        "[sum|que] per level (x3)": 3 * 3 * 2 * MT * E * 2 * E,
+        "phrase taps Z (x3)": 3 * 2 * MT * E * 6 * E,
+        "sentence LSTM (x3)": 3 * 2 * 2 * MT * E * 4 * E,
+        "guidance rows s img_g^T, v que_g^T (x3)": 3 * 6 * 2 * N * E * E,
+        "guided-logits passes (VALU, fwd 2 + bwd 6 / element)": 8 * rows,
+        "pooling passes (VALU, fwd 2 + bwd 4 / element)": 6 * (M * 3 * E + 2 * 3 * MT * E),
+        "answer MLP (x3)": 3 * 2 * N * (E * E + 2 * E * E + 2 * E * H + H * O),
+    }
+    return f, sum(f.values())
+
+
+def stream_yardsticks(N, L, E, reps=20):
+    """image-side guided logits beside att_logits_fwd on a tensor of the same size and a copy of the same bytes, device events
+    around `reps` back-to-back launches after a warm-up; bytes from the shapes: fwd reads (M, 3E); bwd reads it and writes it"""
+    ops = vqa_amd.ops
+    dev = "cuda:0"
+    M = N * L
+    g = torch.Generator().manual_seed(3)
+    x = ((torch.rand(M, 3 * E, generator=g) * 2 - 1) * 1.5).to(dev)
+    gp = (torch.rand(N, 3 * E, generator=g) * 2 - 1).to(dev)
+    w = ((torch.rand(3, E, generator=g) * 2 - 1) * 0.1).to(dev)
+    wblk = torch.zeros(3, 3 * E, device=dev)
+    for i in range(3):
+        wblk[i, i * E:(i + 1) * E] = w[i]
+    zb = torch.zeros(3, device=dev)
+    dl = (torch.rand(M, 3, generator=g) * 2 - 1).to(dev)
+    dst = torch.empty_like(x)
+    nbytes = x.numel() * 4
+
+    def run(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / reps
+
+    rows = [("att_logits_fwd (M, 3E) block-diagonal head", run(lambda: ops.att_logits_fwd(x, wblk, zb)), nbytes),
+            ("guided_logits_fwd (M, 3E), G = 3", run(lambda: ops.guided_logits_fwd(x, gp, w, N, L)), nbytes),
+            ("guided_logits_bwd (M, 3E), G = 3 (+ its reductions)", run(lambda: ops.guided_logits_bwd(dl, x, gp, w, N, L, out=dst)), 2 * nbytes),
+            ("hbm_copy of (M, 3E)", run(lambda: ops.hbm_copy(x, dst)), 2 * nbytes)]
+    print("  streaming yardsticks, M = %d, 3E = %d (%.0f MB per pass over the tensor; each includes its launch, %d back to back):"
+          % (M, 3 * E, nbytes / 1e6, reps))
+    for name, ms, b in rows:
+        print("    %-52s %7.3f ms  %6.2f TB/s  %.3f of 8 TB/s" % (name, ms, b / ms / 1e9, b / ms / 1e9 / 8.0))
+    return {name: {"ms": ms, "bytes": b} for name, ms, b in rows}
 
 
 def timed(model, img, ids, target, steps, warmup, q_len=None):
@@ -74,6 +137,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--lengths", action="store_true", help="time the masked step: seeded question lengths in [3, T]")
+    ap.add_argument("--coatt", choices=("parallel", "alternating"), default="parallel", help="the co-attention mechanism of the levels")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     N, L, D, E, T, H, O, V = a.batch, 196, 2048, 512, 14, 1024, 1000, 15881
@@ -83,31 +147,32 @@ def main():
     ids = torch.randint(0, V, (N, T), device=dev)
     target = torch.randint(0, O, (N,), device=dev)
     ladder = vqa_amd.HieCoAttenLadder(block_num=L, word_num=T, img_size=D, vocab_size=V, embed_size=E, hidden_size=H,
-                                      output_size=O).to(dev).train()
+                                      output_size=O, **({} if a.coatt == "parallel" else {"coatt": a.coatt})).to(dev).train()
     q_len = None
     if a.lengths:
         q_len = torch.randint(3, T + 1, (N,), generator=torch.Generator().manual_seed(1)).to(dev)
     ms, kern = timed(ladder, img, ids, target, a.steps, a.warmup, q_len)
-    parts, flops = ladder_flops(N, L, D, E, T, H, O)
+    parts, flops = (ladder_flops if a.coatt == "parallel" else ladder_alt_flops)(N, L, D, E, T, H, O)
     floor_ms = flops / (PEAK_TFS * 1e12) * 1e3
-    print("HieCoAttenLadder train step  B=%d L=%d img=%d E=%d T=%d hidden=%d out=%d%s"
-          % (N, L, D, E, T, H, O, "  question lengths in [3, %d], mean %.1f" % (T, float(q_len.float().mean())) if a.lengths else ""))
+    print("HieCoAttenLadder (coatt=%s) train step  B=%d L=%d img=%d E=%d T=%d hidden=%d out=%d%s"
+          % (a.coatt, N, L, D, E, T, H, O, "  question lengths in [3, %d], mean %.1f" % (T, float(q_len.float().mean())) if a.lengths else ""))
     print("  %.3f ms/step   %.0f QA pairs/s" % (ms, N / ms * 1e3))
     print("  %.3f TFLOP/step:" % (flops / 1e12))
     for k, v in parts.items():
-        print("    %-48s %7.1f GFLOP" % (k, v / 1e9))
+        print("    %-56s %7.1f GFLOP" % (k, v / 1e9))
     print("  MFMA floor at %.1f TF/s: %.3f ms   fraction reached %.3f" % (PEAK_TFS, floor_ms, floor_ms / ms))
     print("  per kernel (one profiled step; event brackets add a few us per launch):")
     for k, (n, t) in sorted(kern.items(), key=lambda kv: -kv[1][1]):
         print("    %-28s %4d launches  %8.3f ms" % (k, n, t))
     del ladder
     torch.cuda.empty_cache()
+    yard = stream_yardsticks(N, L, E) if a.coatt == "alternating" else None
     hie = vqa_amd.HieCoAtten(block_num=L, word_num=T, img_size=D, vocab_size=V, embed_size=E, output_size=O).to(dev).train()
     ms4, _ = timed(hie, img, ids, target, a.steps, a.warmup)
     print("config 4 HieCoAtten (word level only) at the same shapes: %.3f ms/step   %.0f QA pairs/s" % (ms4, N / ms4 * 1e3))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        json.dump({"lengths": bool(a.lengths), "ms_per_step": ms, "qa_per_s": N / ms * 1e3, "tflop_per_step": flops / 1e12, "floor_ms": floor_ms,
+        json.dump({"coatt": a.coatt, "yardsticks": yard, "lengths": bool(a.lengths), "ms_per_step": ms, "qa_per_s": N / ms * 1e3, "tflop_per_step": flops / 1e12, "floor_ms": floor_ms,
                    "fraction_of_floor": floor_ms / ms, "kernels": kern, "hiecoatten_ms_per_step": ms4}, open(a.json, "w"), indent=1)
 
 

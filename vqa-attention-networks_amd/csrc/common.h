@@ -58,6 +58,8 @@ enum VqfKernelId {
   KID_PHRASE_FWD,
   KID_PHRASE_BWD,
   KID_HIE_AFF_LEVELS,
+  KID_GUIDED_FWD,
+  KID_GUIDED_BWD,
   KID_COUNT
 };
 

@@ -1,0 +1,194 @@
+// Guided attention logits: the streaming passes of HieCoAttenLadder's ALTERNATING co-attention (host/hie_ladder.py,
+// coatt="alternating"; Lu et al. 2016, section 3.3).  One attention step is
+//   Xh = X Wx^T + bx   (a GEMM, (N*S, E))          H = tanh(Xh + gp[n])   with the per-sample guidance row gp[n] = g[n] Wg^T
+//   logit[n, s] = H[n, s, :] . w                    a = softmax_S(logit), x^ = sum_s a[s] X[s]   (vqf_glimpse_pool_*)
+// and the two kernels here are the H line and its backward for G <= 3 steps that share the rows (the three levels' image
+// attention: Xh (N*S, ldx) with step g's block at columns [g E, (g + 1) E), gp (N, G E), w (G, E)).  H is never stored:
+//   fwd   logits[r, g] = sum_e w[g, e] tanh(Xh[r, g E + e] + gp[n, g E + e])                 one read of Xh, (N*S, G) out
+//   bwd   recomputes H;  dXh[r, g, e] = dlogits[r, g] w[g, e] (1 - H^2)                      one read of Xh, one write of dXh
+//         dgp[n, :] = sum_s dXh[n, s, :]     dw[g, e] = sum_{n, s} dlogits[n, s, g] H[n, s, g, e]
+// gp = null is the unguided step (H = tanh(Xh)): the guidance row is taken as zeros, x + 0 == x, the same kernel.
+// Both are HBM streams.  A workgroup's rows belong to ONE sample, so its guidance row and the weights are read once per
+// workgroup (LDS in the forward, registers in the backward).  The sums run in a fixed order -- per workgroup over its rows, then
+// over the workgroups' partial rows in the workspace (reduce.hip) -- no atomics: two runs give the same bits.
+// tanh is vqf_tanh_fast (common.h): the value feeds a softmax logit, not a recursion.
+#include "common.h"
+
+namespace {
+
+constexpr int GL_EMAX = 1024, GL_SMAX = 1024;
+constexpr int GL_FWD_ROWS = 32;       // rows of a sample per forward workgroup (four waves, one row per wave and trip)
+constexpr int GL_BWD_ROWS = 64;       // rows of a sample per backward workgroup (one partial row of dgp and of dw each)
+
+// a sample's S rows in equal chunks of at most `cap` rows
+inline int gl_chunks(int S, int cap) { return (S + cap - 1) / cap; }
+inline int gl_rows(int S, int cap) { const int nc = gl_chunks(S, cap); return (S + nc - 1) / nc; }
+
+// grid (chunks, N), 256 threads.  LDS: [gp[n] (G E) | w (G E)].  A wave takes a row: lane q reads the 16-byte groups
+// q, q + 64, ... of the row's G E contiguous floats (four loads in flight), the group's step is found by comparison.
+template <int G>
+__global__ void __launch_bounds__(256) guided_logits_fwd_kernel(const float* __restrict__ Xh, int ldx, const float* __restrict__ gp,
+                                                                const float* __restrict__ w, int S, int E, int rows,
+                                                                float* __restrict__ logits) {
+  extern __shared__ __attribute__((aligned(16))) float gl_lds[];
+  const int GE = G * E, n = blockIdx.y;
+  float* gs = gl_lds;
+  float* ws = gl_lds + GE;
+  for (int c = threadIdx.x * 4; c < GE; c += 1024) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    *reinterpret_cast<f32x4*>(gs + c) = gp ? *reinterpret_cast<const f32x4*>(gp + (long long)n * GE + c) : zero;
+    *reinterpret_cast<f32x4*>(ws + c) = *reinterpret_cast<const f32x4*>(w + c);
+  }
+  __syncthreads();
+  const int s0 = blockIdx.x * rows, s1 = min(S, s0 + rows);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int nq = GE >> 2;
+  constexpr int UNR = 4;
+  for (int s = s0 + wave; s < s1; s += 4) {
+    const long long r = (long long)n * S + s;
+    const float* x = Xh + r * ldx;
+    float a[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) a[g] = 0.f;
+    for (int q0 = lane; q0 < nq; q0 += 64 * UNR) {
+      f32x4 xv[UNR];
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        const int q = min(q0 + 64 * u, nq - 1);                    // past the end: re-read the last group (not used)
+        xv[u] = vqf_ld_stream(reinterpret_cast<const f32x4*>(x + 4 * q));
+      }
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        const int c = 4 * (q0 + 64 * u);
+        if (c >= GE) break;
+        const f32x4 gv = *reinterpret_cast<const f32x4*>(gs + c);
+        const f32x4 wv = *reinterpret_cast<const f32x4*>(ws + c);
+        float p = vqf_tanh_fast(xv[u][0] + gv[0]) * wv[0];
+#pragma unroll
+        for (int j = 1; j < 4; ++j) p += vqf_tanh_fast(xv[u][j] + gv[j]) * wv[j];
+        const int lv = (G > 1 && c >= E) + (G > 2 && c >= 2 * E);
+#pragma unroll
+        for (int g = 0; g < G; ++g) a[g] += lv == g ? p : 0.f;
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const float t = wave_sum(a[g]);
+      if (lane == 0) logits[(long long)G * r + g] = t;
+    }
+  }
+}
+
+// grid (chunks, N), G E / 4 threads rounded up to whole waves: a thread owns four columns and walks the chunk's rows (four
+// rows in flight), so gp[n], w and the two running sums stay in registers.  part_g / part_w: one row of G E floats per
+// workgroup (row n * chunks + chunk); with one chunk per sample part_g is dgp itself.
+template <int G>
+__global__ void __launch_bounds__(768) guided_logits_bwd_kernel(const float* __restrict__ dl, const float* __restrict__ Xh, int ldx,
+                                                                const float* __restrict__ gp, const float* __restrict__ w, int S,
+                                                                int E, int rows, float* __restrict__ dXh, int ldd,
+                                                                float* __restrict__ part_g, float* __restrict__ part_w) {
+  const int GE = G * E, n = blockIdx.y;
+  const int c = threadIdx.x * 4;
+  if (c >= GE) return;
+  const int s0 = blockIdx.x * rows, s1 = min(S, s0 + rows);
+  const int lv = (G > 1 && c >= E) + (G > 2 && c >= 2 * E);
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 gv = gp ? *reinterpret_cast<const f32x4*>(gp + (long long)n * GE + c) : zero;
+  const f32x4 wv = *reinterpret_cast<const f32x4*>(w + c);
+  f32x4 sg = zero, sw = zero;
+  const long long r0 = (long long)n * S;
+  constexpr int RB = 4;
+  for (int sb = s0; sb < s1; sb += RB) {
+    f32x4 x[RB];
+    float d[RB];
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+      const long long r = r0 + min(sb + q, s1 - 1);                // the tail trip re-reads the last row (not used)
+      x[q] = vqf_ld_stream(reinterpret_cast<const f32x4*>(Xh + r * ldx + c));
+      d[q] = dl[(long long)G * r + lv];
+    }
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+      if (sb + q >= s1) break;
+      f32x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float h = vqf_tanh_fast(x[q][j] + gv[j]);
+        o[j] = (d[q] * wv[j]) * (1.0f - h * h);
+        sg[j] += o[j];
+        sw[j] += d[q] * h;
+      }
+      *reinterpret_cast<f32x4*>(dXh + (r0 + sb + q) * ldd + c) = o;
+    }
+  }
+  const long long prow = ((long long)n * gridDim.x + blockIdx.x) * GE + c;
+  *reinterpret_cast<f32x4*>(part_g + prow) = sg;
+  *reinterpret_cast<f32x4*>(part_w + prow) = sw;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vqf_guided_logits_supported(int N, int S, int E, int G) {
+  return N >= 1 && N <= 65535 && S >= 1 && S <= GL_SMAX && E >= 32 && E <= GL_EMAX && (E % 32) == 0 && G >= 1 && G <= 3 &&
+         (long long)N * S < (1LL << 31) / 4;
+}
+
+int vqf_guided_logits_fwd(const float* Xh, int ldx, const float* gp, const float* w, int N, int S, int E, int G, float* logits,
+                          void* stream) {
+  if (!Xh || !w || !logits || N <= 0 || S <= 0 || E <= 0 || G <= 0 || ldx < G * E || (ldx % 4)) return VQF_E_BADARG;
+  if (!vqf_guided_logits_supported(N, S, E, G)) return VQF_E_UNSUPPORTED;
+  if (!aligned16(Xh) || !aligned16(gp) || !aligned16(w)) return VQF_E_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  const int rows = gl_rows(S, GL_FWD_ROWS);
+  const dim3 grid(gl_chunks(S, rows), N);
+  const size_t lds = (size_t)2 * G * E * sizeof(float);
+#define VQF_GL(G_) \
+  VQF_LAUNCH(KID_GUIDED_FWD, (guided_logits_fwd_kernel<G_>), grid, dim3(256), lds, s, Xh, ldx, gp, w, S, E, rows, logits)
+  if (G == 3) VQF_GL(3);
+  else if (G == 2) VQF_GL(2);
+  else VQF_GL(1);
+#undef VQF_GL
+  return vqf_last_error();
+}
+
+size_t vqf_guided_logits_bwd_ws_bytes(int N, int S, int E, int G) {
+  if (N <= 0 || S <= 0 || E <= 0 || G <= 0) return 0;
+  const size_t nb = (size_t)N * gl_chunks(S, gl_rows(S, GL_BWD_ROWS));
+  return (2 * nb + VQF_REDUCE_SPLITS) * (size_t)G * E * sizeof(float);       // dgp partial rows, dw partial rows, reduction scratch
+}
+
+int vqf_guided_logits_bwd(const float* dlogits, const float* Xh, int ldx, const float* gp, const float* w, int N, int S, int E,
+                          int G, float* dXh, int lddx, float* dgp, float* dw, void* ws, size_t ws_bytes, void* stream) {
+  if (!dlogits || !Xh || !w || !dXh || !dgp || !dw || N <= 0 || S <= 0 || E <= 0 || G <= 0 || ldx < G * E || lddx < G * E ||
+      (ldx % 4) || (lddx % 4))
+    return VQF_E_BADARG;
+  if (!vqf_guided_logits_supported(N, S, E, G)) return VQF_E_UNSUPPORTED;
+  if (!aligned16(Xh) || !aligned16(gp) || !aligned16(w) || !aligned16(dXh) || !aligned16(dgp) || !aligned16(ws)) return VQF_E_ALIGN;
+  if (!ws || ws_bytes < vqf_guided_logits_bwd_ws_bytes(N, S, E, G)) return VQF_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const int GE = G * E;
+  const int rows = gl_rows(S, GL_BWD_ROWS), chunks = gl_chunks(S, rows);
+  const int nb = N * chunks;
+  float* part_w = (float*)ws;
+  float* part_g = chunks == 1 ? dgp : part_w + (size_t)nb * GE;
+  float* scratch = part_w + (size_t)2 * nb * GE;
+  const dim3 grid(chunks, N), block(((GE / 4 + 63) / 64) * 64);
+#define VQF_GL(G_)                                                                                                              \
+  VQF_LAUNCH(KID_GUIDED_BWD, (guided_logits_bwd_kernel<G_>), grid, block, 0, s, dlogits, Xh, ldx, gp, w, S, E, rows, dXh, lddx, \
+             part_g, part_w)
+  if (G == 3) VQF_GL(3);
+  else if (G == 2) VQF_GL(2);
+  else VQF_GL(1);
+#undef VQF_GL
+  int rc = vqf_last_error();
+  if (rc) return rc;
+  if (chunks > 1) {
+    rc = vqf_group_reduce_f32(part_g, N, chunks, GE, dgp, stream);           // dgp[n] = its chunks' rows, in chunk order
+    if (rc) return rc;
+  }
+  return vqf_colreduce_2stage(part_w, nb, GE, dw, scratch, s);
+}
+
+}  // extern "C"

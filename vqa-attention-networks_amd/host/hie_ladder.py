@@ -19,6 +19,20 @@ equations below are the specification, restated line by line in tests/hie_ladder
 
 `drop` is dropout with rate drop_p in train mode only.
 
+Alternating co-attention (coatt="alternating"; the paper's second mechanism, section 3.3).  The per-level block above becomes
+three attention steps, each with its own weights; with A(X, g; Wx, bx, Wg, wh) for X (N, S, E) and g (N, E) or absent:
+
+    Xh = X Wx^T + bx;  H = tanh(Xh + (g Wg^T)[:, None, :])  (absent g: H = tanh(Xh));  a = softmax_S(H wh^T);  x^ = sum_s a[s] X[s]
+    per level i, Q in (Qw, Qp, Qs):
+        s_i = A(Q, none)          (sum_x, sum_h)                 the question summary
+        v_i, av_i = A(V, s_i)     (img_x, img_g, img_h)          the image attended under the summary
+        q_i, aq_i = A(Q, v_i)     (que_x, que_g, que_h)          the question attended under the attended image
+
+v_i, q_i, av_i, aq_i feed the same answer MLP; everything before the levels is unchanged.  With q_length the softmax of steps 1
+and 3 runs over t < len[n] (exact zeros beyond); Xh of a padded row is bx, not zero, but the row enters nothing: its weight
+is an exact zero, and in the backward its dlogit is an exact zero out of vqf_glimpse_pool_bwd_len, so its dXh row, and its part
+of dgp and dwh, are zero by arithmetic.  H is never stored (vqf_guided_logits_fwd / _bwd, csrc/hie_ladder_alt.hip).
+
 Question lengths.  forward(img, ids, q_length) -- the call form of the reference's training loop (solver.py:84-89,
 model.forward(i, q, q_l)) -- takes the loader's (N,) lengths (data_loader.py:34,45; questions are padded on the right up to
 T words, utils.py:185-196).  With valid[n, t] = t < len[n] (len clamped to [1, T] on the device, never read on the host):
@@ -43,6 +57,9 @@ Stages (every product and every pass over an (N*L, .) or (N*T, .) tensor runs in
   * the three co-attention levels (LadderCoattFn): one Vh product for all levels, one multi-level affinity pass over V
     (vqf_hie_affinity_levels), the streaming Hv / Hq passes of csrc/hie.hip per level on column blocks, one G = 3 image-side
     pooling over V;
+  * alternating mode (LadderAltCoattFn) instead: one product V [img_x_0; img_x_1; img_x_2]^T, one product per level
+    Q_i [sum_x_i; que_x_i]^T, the guided-logits passes (one G = 3 launch over the image rows, one launch per level and step
+    over the question rows), the same pooling kernels, (N, E) products for the guidance rows;
   * the answer MLP: LinearFn, TanhDropFn, DropoutFn; torch does its O(N E) adds and concatenations.
 """
 import torch
@@ -220,6 +237,122 @@ class LadderCoattFn(torch.autograd.Function):
         return (dV, dQ[0], dQ[1], dQ[2], None, None, None, None, *grads)
 
 
+class LadderAltCoattFn(torch.autograd.Function):
+    """The three alternating co-attention levels over ONE image tensor (the module docstring's A steps).  V (N*L, E),
+    q0 / q1 / q2 (N*T, E) contiguous; weights: for each level (sum_x.weight (E, E), sum_x.bias (E), sum_h.weight (1, E),
+    img_x.weight, img_x.bias, img_g.weight (E, E), img_h.weight, que_x.weight, que_x.bias, que_g.weight, que_h.weight).
+    Returns what LadderCoattFn returns: (vcat (N, 3E), q_0, q_1, q_2 (N, E), av (N, 3, L), aq_0, aq_1, aq_2 (N, 1, T)).
+
+    Forward: VX = V [img_x_0; img_x_1; img_x_2]^T + b (one product, (N*L, 3E)); [sum_i | que_i] = Q_i [sum_x_i; que_x_i]^T + b
+    into one (N*T, 6E) buffer; step 1 per level: guided logits without guidance over the sum_i block, pooling over Q_i -> s_i;
+    step 2: the guidance rows s_i img_g_i^T (N, 3E), ONE G = 3 guided-logits pass over VX and ONE G = 3 pooling pass over V;
+    step 3 per level: v_i que_g_i^T, guided logits over the que_i block, pooling over Q_i.
+    Backward: step 3 -> step 2 -> step 1 through the guidance-row gradients dgp; the guided-logits backward writes dXh straight
+    into the (N*T, 6E) / (N*L, 3E) operands of the weight- and input-gradient products; the bias gradients are column sums of
+    the (N, .) dgp.  lens ((N,) int32 or None; q0 / q1 / q2 come with zero rows at t >= lens[n]): the question-side poolings
+    take the softmax over the real words and give zero dlogits for the padded ones."""
+
+    PER_LEVEL = 11
+
+    @staticmethod
+    def forward(ctx, V, q0, q1, q2, N, L, T, lens, *w):
+        E = V.shape[1]
+        lk = {} if lens is None else {"lens": lens}
+        M, MT = N * L, N * T
+        dev = V.device
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        Q = (q0, q1, q2)
+        (sum_x, sum_b, sum_h, img_x, img_b, img_g, img_h, que_x, que_b, que_g, que_h) = \
+            ([_c(w[LadderAltCoattFn.PER_LEVEL * g + i]) for g in range(3)] for i in range(LadderAltCoattFn.PER_LEVEL))
+        wimg = torch.cat(img_x, 0).contiguous()                                     # (3E, E)
+        bimg = torch.cat(img_b, 0).contiguous()
+        whimg = torch.cat(img_h, 0).contiguous()                                    # (3, E)
+        wq2 = [torch.cat([sum_x[g], que_x[g]], 0).contiguous() for g in range(3)]   # (2E, E) each
+        bq2 = [torch.cat([sum_b[g], que_b[g]], 0).contiguous() for g in range(3)]
+        VX = ops.gemm_rows(V, wimg, L, bias=bimg)                                   # (M, 3E) = [img_0 | img_1 | img_2]
+        QX = new(MT, 6 * E)                                                         # [sum_0 | que_0 | sum_1 | que_1 | sum_2 | que_2]
+        for g in range(3):
+            ops.gemm(Q[g], wq2[g], bias=bq2[g], out=QX[:, 2 * g * E:(2 * g + 2) * E])
+        # step 1: the question summaries
+        asum, s = [], []
+        for g in range(3):
+            lg = ops.guided_logits_fwd(QX[:, 2 * g * E:(2 * g + 1) * E], None, sum_h[g], N, T)
+            a_g, s_g = ops.glimpse_pool_fwd(Q[g].view(N, T, E), lg, False, **lk)
+            asum.append(a_g)
+            s.append(s_g)
+        # step 2: the image under the summaries, all levels in one pass over VX and one over V
+        gpv = new(N, 3 * E)
+        for g in range(3):
+            ops.gemm(s[g], img_g[g], out=gpv[:, g * E:(g + 1) * E])
+        av, vcat = ops.glimpse_pool_fwd(V.view(N, L, E), ops.guided_logits_fwd(VX, gpv, whimg, N, L), False)   # (N, 3, L), (N, 3E)
+        # step 3: the question under the attended image
+        gpq = new(3, N, E)
+        aq, qo = [], []
+        for g in range(3):
+            ops.gemm(vcat[:, g * E:(g + 1) * E], que_g[g], out=gpq[g])
+            lg = ops.guided_logits_fwd(QX[:, (2 * g + 1) * E:(2 * g + 2) * E], gpq[g], que_h[g], N, T)
+            a_g, q_g = ops.glimpse_pool_fwd(Q[g].view(N, T, E), lg, False, **lk)
+            aq.append(a_g)
+            qo.append(q_g)
+        ctx.save_for_backward(V, q0, q1, q2, wimg, whimg, VX, QX, gpv, gpq, vcat, av, *wq2, *sum_h, *img_g, *que_g, *que_h, *s, *asum,
+                              *aq)
+        ctx.dims, ctx.lens = (N, L, T, E), lens
+        ctx.set_materialize_grads(False)
+        return (vcat, qo[0], qo[1], qo[2], av, aq[0], aq[1], aq[2])
+
+    @staticmethod
+    def backward(ctx, dvcat, dq0, dq1, dq2, dav, daq0, daq1, daq2):
+        t = ctx.saved_tensors
+        V, q0, q1, q2, wimg, whimg, VX, QX, gpv, gpq, vcat, av = t[:12]
+        wq2, sum_h, img_g, que_g, que_h, s, asum, aq = (t[12 + 3 * i:15 + 3 * i] for i in range(8))
+        N, L, T, E = ctx.dims
+        M, MT = N * L, N * T
+        dev = V.device
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        Q, dq, daq = (q0, q1, q2), (dq0, dq1, dq2), (daq0, daq1, daq2)
+        lens = ctx.lens
+        lk = {} if lens is None else {"lens": lens}
+        dQX = new(MT, 6 * E)                                                        # [dsum_0 | dque_0 | ...]
+        dvc = dvcat.clone(memory_format=torch.contiguous_format) if dvcat is not None else zeros(N, 3 * E)               # dv_i: the answer MLP's plus step 3's
+        dQ, g3 = [], []
+        # step 3: q_i = aq_i^T Q_i, aq_i = softmax(que_h_i tanh(que_i + v_i que_g_i^T))
+        for g in range(3):
+            blk = slice(g * E, (g + 1) * E)
+            dqg = _c(dq[g]) if dq[g] is not None else zeros(N, E)
+            dl, dQg = ops.glimpse_pool_bwd(dqg, Q[g].view(N, T, E), aq[g], False, True,
+                                           dwts=None if daq[g] is None else _c(daq[g]), **lk)
+            _, dgp, dwh = ops.guided_logits_bwd(dl, QX[:, (2 * g + 1) * E:(2 * g + 2) * E], gpq[g], que_h[g], N, T,
+                                                out=dQX[:, (2 * g + 1) * E:(2 * g + 2) * E])
+            ops.gemm(dgp, que_g[g], tb=True, out=dvc[:, blk], accumulate=True)      # dv_i += dgp que_g_i
+            g3.append((ops.colsum(dgp), ops.gemm(dgp, vcat[:, blk], ta=True, tb=True), dwh))   # que_x.bias, que_g, que_h
+            dQ.append(dQg.view(MT, E))
+        # step 2: one G = 3 pooling backward over V, one G = 3 guided-logits backward over VX
+        dlv, dV = ops.glimpse_pool_bwd(dvc, V.view(N, L, E), av, False, True, dwts=None if dav is None else _c(dav))
+        dV = dV.view(M, E)
+        dVX, dgpv, dwhimg = ops.guided_logits_bwd(dlv, VX, gpv, whimg, N, L)
+        dbimg = ops.colsum(dgpv)
+        ops.gemm(dVX, wimg, tb=True, out=dV, accumulate=True)                      # dV += dVX [img_x_0; img_x_1; img_x_2]
+        dwimg = ops.gemm(dVX, V, ta=True, tb=True)                                 # (3E, E)
+        # step 1: s_i = asum_i^T Q_i; then the [sum_x_i; que_x_i] pair's products
+        grads, dQ1 = [], []
+        for g in range(3):
+            blk = slice(g * E, (g + 1) * E)
+            ds = ops.gemm(dgpv[:, blk], img_g[g], tb=True)                          # (N, E)
+            dimg_g = ops.gemm(dgpv[:, blk], s[g], ta=True, tb=True)
+            dl, dQ1g = ops.glimpse_pool_bwd(ds, Q[g].view(N, T, E), asum[g], False, True, **lk)
+            _, dgp, dwsum_h = ops.guided_logits_bwd(dl, QX[:, 2 * g * E:(2 * g + 1) * E], None, sum_h[g], N, T,
+                                                    out=dQX[:, 2 * g * E:(2 * g + 1) * E])
+            pair = dQX[:, 2 * g * E:(2 * g + 2) * E]
+            ops.gemm(pair, wq2[g], tb=True, out=dQ[g], accumulate=True)
+            dwq2 = ops.gemm(pair, Q[g], ta=True, tb=True)                           # (2E, E) = [dsum_x; dque_x]
+            dQ1.append(dQ1g.view(MT, E))
+            grads += [dwq2[:E], ops.colsum(dgp), dwsum_h, dwimg[blk], dbimg[blk], dimg_g, dwhimg[g:g + 1], dwq2[E:], g3[g][0],
+                      g3[g][1], g3[g][2]]
+        ops.multi_add([(dQ[g], dQ1[g], dQ[g]) for g in range(3)])                   # dQ_i: step 3's + the pair's + step 1's
+        return (dV, dQ[0], dQ[1], dQ[2], None, None, None, None, *grads)
+
+
 class _Coatt(nn.Module):
     """One level's co-attention weights (no biases: a bias inside the softmax cancels, and Wb / Wv / Wq are bias-free)."""
 
@@ -232,6 +365,26 @@ class _Coatt(nn.Module):
         self.whq = nn.Linear(E, 1, bias=False)
 
 
+class _CoattAlt(nn.Module):
+    """One level's alternating co-attention weights: the three attention steps (question summary, image, question), each a
+    projection with a bias (*_x), a bias-free guidance projection (*_g; the summary step has no guidance) and a head (*_h; a
+    bias inside the softmax cancels)."""
+
+    def __init__(self, E):
+        super(_CoattAlt, self).__init__()
+        self.sum_x = nn.Linear(E, E)
+        self.sum_h = nn.Linear(E, 1, bias=False)
+        self.img_x = nn.Linear(E, E)
+        self.img_g = nn.Linear(E, E, bias=False)
+        self.img_h = nn.Linear(E, 1, bias=False)
+        self.que_x = nn.Linear(E, E)
+        self.que_g = nn.Linear(E, E, bias=False)
+        self.que_h = nn.Linear(E, 1, bias=False)
+
+
+COATT_MODES = ("parallel", "alternating")
+
+
 class HieCoAttenLadder(nn.Module):
     """forward(img_features (N, L, img_size) fp32 GPU, que_features (N, T) int64 GPU, q_length=None)
     -> (logits (N, output_size), av (N, 3, L), aq (N, 3, T)); levels ordered word, phrase, sentence.
@@ -242,13 +395,21 @@ class HieCoAttenLadder(nn.Module):
     row gets no gradient.  Values are clamped to [1, T] on the device; the lengths are never read on the host.  None: no masking
     (every id is a word), bit for bit the two-argument model.
 
+    coatt: "parallel" (the default: the affinity form of the module docstring) or "alternating" (the paper's alternating
+    co-attention: question summary -> image attention -> question attention per level; self.coatt then holds three modules
+    with sum_x, sum_h, img_x, img_g, img_h, que_x, que_g, que_h).  Anything else raises ValueError; coatt_mode holds the string.
+    Inputs, outputs, masking and the dropout sites are the same in both modes.
+
     The image features are data (img_features.requires_grad raises), fp32 on the GPU: CPU tensors and bf16 features raise
     VqfError -- there is no CPU fallback.  Dropout (rate drop_p) is active in train mode only;
     set_keep_masks() supplies explicit uint8 keep-masks for the tests, otherwise the kernels draw Philox masks."""
 
     def __init__(self, block_num=196, word_num=22, img_size=2048, vocab_size=15881, embed_size=512, hidden_size=1024,
-                 output_size=3000, drop_p=0.5):
+                 output_size=3000, drop_p=0.5, coatt="parallel"):
         super(HieCoAttenLadder, self).__init__()
+        if coatt not in COATT_MODES:
+            raise ValueError("HieCoAttenLadder: coatt must be one of %s, got %r" % (", ".join(COATT_MODES), coatt))
+        self.coatt_mode = coatt
         E = embed_size
         self.img_emb = nn.Linear(img_size, E)
         self.word_emb = nn.Embedding(vocab_size, E)
@@ -256,7 +417,7 @@ class HieCoAttenLadder(nn.Module):
         self.phrase_bi = nn.Conv1d(E, E, 2)
         self.phrase_tri = nn.Conv1d(E, E, 3)
         self.sent_lstm = nn.LSTM(E, E, batch_first=True)
-        self.coatt = nn.ModuleList([_Coatt(E) for _ in range(3)])
+        self.coatt = nn.ModuleList([(_Coatt if coatt == "parallel" else _CoattAlt)(E) for _ in range(3)])
         self.ans_w = nn.Linear(E, E)
         self.ans_p = nn.Linear(2 * E, E)
         self.ans_s = nn.Linear(2 * E, hidden_size)
@@ -291,6 +452,10 @@ class HieCoAttenLadder(nn.Module):
         if E % 32 or not ops.phrase_ngram_supported(T, E) or L > 1024 or T > 1024:
             raise VqfError("HieCoAttenLadder: embed_size %% 32 == 0, T <= 32 and L <= 1024 are supported (got E=%d, T=%d, L=%d)"
                            % (E, T, L))
+        alt = self.coatt_mode == "alternating"
+        if alt and not (ops.guided_logits_supported(N, L, E, 3) and ops.guided_logits_supported(N, T, E, 1)):
+            raise VqfError("HieCoAttenLadder(coatt='alternating'): embed_size %% 32 == 0, embed_size <= 1024, L <= 1024 and "
+                           "N <= 65535 are supported (got E=%d, L=%d, T=%d, N=%d)" % (E, L, T, N))
         M, MT = N * L, N * T
         lens = None
         if q_length is not None:
@@ -319,8 +484,14 @@ class HieCoAttenLadder(nn.Module):
         hs = LstmBatchFn.apply(xt, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, False)
         qs = DropoutBTFn.apply(hs.transpose(0, 1), None, 0, 0.0, lens).view(MT, E)      # (N*T, E), zero rows past the last word
         # the three co-attention levels
-        w = [p_ for c in self.coatt for p_ in (c.Wb.weight, c.Wv.weight, c.Wq.weight, c.whv.weight, c.whq.weight)]
-        vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, *w)
+        if alt:
+            w = [p_ for c in self.coatt for p_ in (c.sum_x.weight, c.sum_x.bias, c.sum_h.weight, c.img_x.weight, c.img_x.bias,
+                                                   c.img_g.weight, c.img_h.weight, c.que_x.weight, c.que_x.bias, c.que_g.weight,
+                                                   c.que_h.weight)]
+            vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderAltCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, *w)
+        else:
+            w = [p_ for c in self.coatt for p_ in (c.Wb.weight, c.Wv.weight, c.Wq.weight, c.whv.weight, c.whq.weight)]
+            vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, *w)
         v0, v1, v2 = vcat[:, :E], vcat[:, E:2 * E], vcat[:, 2 * E:]
         th = lambda x: TanhDropFn.apply(x, None, None, 0, 0.0)
         lin = lambda x, m: LinearFn.apply(_c(x), m.weight, m.bias, False)

@@ -105,6 +105,11 @@ SIGNATURES = {
     "vqf_hie_affinity_levels_len": (c_i, [c_f, c_i, c_i, c_f, c_i, c_i, c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_p, c_i, c_i,
                                           c_i, c_i, c_f, c_p]),
     "vqf_tanh_bwd_rows_len": (c_i, [c_f, c_f, c_p, c_i, c_i, c_i, c_f, c_p]),
+    # the guided attention logits of HieCoAttenLadder's alternating co-attention (csrc/hie_ladder_alt.hip)
+    "vqf_guided_logits_supported": (c_i, [c_i, c_i, c_i, c_i]),
+    "vqf_guided_logits_fwd": (c_i, [c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_p]),
+    "vqf_guided_logits_bwd_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "vqf_guided_logits_bwd": (c_i, [c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_f, c_p, c_sz, c_p]),
     "vqf_softmax_rows_fwd": (c_i, [c_f, c_i, c_i, c_f, c_p]),
     "vqf_softmax_rows_bwd": (c_i, [c_f, c_f, c_i, c_i, c_f, c_p]),
     "vqf_log_softmax_rows_fwd": (c_i, [c_f, c_i, c_i, c_f, c_p]),

@@ -791,6 +791,53 @@ def hie_affinity_levels(x1, lvx1, y1, lvy1, G, N, L, T, E, x2=None, lvx2=0, y2=N
     return out
 
 
+# the guided attention logits of the ladder's alternating co-attention (csrc/hie_ladder_alt.hip; include/vqa_fusion.h
+# vqf_guided_logits_*)
+def guided_logits_supported(N, S, E, G):
+    return bool(_lib().vqf_guided_logits_supported(int(N), int(S), int(E), int(G)))
+
+
+def _guided_operands(name, xh, gp, w, N, S):
+    _chk2s(xh)
+    _chk(gp, w)
+    G, E = w.shape
+    if xh.shape[0] != N * S or xh.shape[1] != G * E or (gp is not None and tuple(gp.shape) != (N, G * E)):
+        raise _l.VqfError(name + ": xh must be (N*S, G*E), gp (N, G*E) or None, w (G, E)")
+    if not guided_logits_supported(N, S, E, G):
+        raise _l.VqfError(name + ": E %% 32 == 0, E <= 1024, 1 <= S <= 1024, G in {1, 2, 3} and N <= 65535 are supported "
+                          "(got N=%d, S=%d, E=%d, G=%d)" % (N, S, E, G))
+    return G, E
+
+
+def guided_logits_fwd(xh, gp, w, N, S):
+    """xh (N*S, G*E) (rows may be strided: a column block of a wider buffer), gp (N, G*E) or None, w (G, E) ->
+    logits (N*S, G) = sum_e w[g, e] tanh(xh[r, g*E + e] + gp[r // S, g*E + e]); the hidden activation is not stored."""
+    G, E = _guided_operands("guided_logits_fwd", xh, gp, w, N, S)
+    out = torch.empty((N * S, G), dtype=torch.float32, device=xh.device)
+    _l.check(_lib().vqf_guided_logits_fwd(_ptr(xh), xh.stride(0), _ptr(gp), _ptr(w), int(N), int(S), E, G, _ptr(out), _stream()),
+             "vqf_guided_logits_fwd")
+    return out
+
+
+def guided_logits_bwd(dlogits, xh, gp, w, N, S, out=None):
+    """-> (dxh (N*S, G*E) (out: written there, rows may be strided), dgp (N, G*E) = the per-sample row sums of dxh (also when
+    gp is None: its column sum is the bias gradient of the layer that made xh), dw (G, E)); fixed summation order."""
+    G, E = _guided_operands("guided_logits_bwd", xh, gp, w, N, S)
+    _chk(dlogits)
+    _chk2s(out)
+    if tuple(dlogits.shape) != (N * S, G) or (out is not None and tuple(out.shape) != (N * S, G * E)):
+        raise _l.VqfError("guided_logits_bwd: dlogits must be (N*S, G) and out (N*S, G*E)")
+    if out is None:
+        out = torch.empty((N * S, G * E), dtype=torch.float32, device=xh.device)
+    dgp = torch.empty((N, G * E), dtype=torch.float32, device=xh.device)
+    dw = torch.empty((G, E), dtype=torch.float32, device=xh.device)
+    ws = workspace(xh.device, _lib().vqf_guided_logits_bwd_ws_bytes(int(N), int(S), E, G))
+    _l.check(_lib().vqf_guided_logits_bwd(_ptr(dlogits), _ptr(xh), xh.stride(0), _ptr(gp), _ptr(w), int(N), int(S), E, G, _ptr(out),
+                                          out.stride(0), _ptr(dgp), _ptr(dw), _ptr(ws), ws.numel(), _stream()),
+             "vqf_guided_logits_bwd")
+    return out, dgp, dw
+
+
 def softmax_rows_fwd(x):
     _chk(x)
     R, W = x.shape
