@@ -646,6 +646,52 @@ int vqf_ce_loss(const float* logits, const long long* target, int N, int A, floa
 int vqf_kldiv_loss(const float* logp, const float* target, int N, int A, float* loss, float* dlogp,
                    void* ws, size_t ws_bytes, void* stream);
 
+/* --------------------------------------------------------------------------
+ * Evaluation tail: what the solver does with the logits after the criterion (solver.py:96-101 in the training loop,
+ * :148-153 in val()) -- softmax, max, compare, mean -- without the softmax (its arg-max is the logits' arg-max) and without
+ * a pass of its own, and the k most likely answers of every row.
+ *
+ * Order of values, common to the three entry points:
+ *   - ties go to the LOWEST index, in the arg-max and at every rank of the top-k;
+ *   - a row that contains NaN predicts the lowest index holding a NaN, and NaN ranks above +inf in the top-k (torch.max);
+ *   - -inf entries are ordinary values; -0 equals +0.
+ * Totals.  counts (2 x long long) and the double sums live on the device, so that a validation epoch is read back once:
+ * accumulate == 0 overwrites them with this call's totals, accumulate != 0 adds this call's totals to what they hold (calls
+ * on one stream are ordered; the sums are formed in a fixed order, no atomics).  acc[0] is always THIS call's
+ * hits / rows as fp32 (NaN when no row counts, the mean of an empty tensor).  Every output named "may be NULL" is optional.
+ * Stores are ordinary vector stores.  Bad arguments (N <= 0, A <= 0, a NULL mandatory pointer, k < 1, k > W, ldx < W, a mode
+ * other than 0 / 1) return VQF_E_BADARG before any GPU call.
+ *
+ * vqf_ce_loss_pred  vqf_ce_loss (same two launches; loss and dlogits bit-identical to it) plus, from the same row pass:
+ *                   pred[n] (int64, may be NULL) = arg-max of logits[n, :];
+ *                   counts[0] = rows with target != -100 and pred == target, counts[1] = rows with target != -100;
+ *                   loss_sum[0] = sum of the counted rows' losses (double, in the finish kernel's fixed order).
+ *                   A row whose target is outside [0, A) (and not -100) has a NaN loss, as in vqf_ce_loss, counts as a row
+ *                   and is never a hit.  counts, loss_sum, acc may be NULL.  ws: at least 8 * N bytes.
+ * vqf_answer_match_rows  the soft-target models (mhb, mhb_coAtt; KL criterion), after vqf_kldiv_loss: one row launch and the
+ *                   totals.  pred[n] = arg-max of logp[n, :]; tpred[n] = arg-max of target[n, :] (solver.py:100);
+ *                   score[n] = target[n, pred[n]], the soft VQA score of the predicted answer (a copy);
+ *                   counts[0] = rows with pred == tpred, counts[1] = N; score_sum[0] = sum of score (double);
+ *                   loss (a DEVICE scalar, e.g. what vqf_kldiv_loss just wrote) with loss_sum: loss_sum[0] gets N * loss[0],
+ *                   the batch's mean weighted by its rows, so that loss_sum / counts[1] is the mean over all rows seen.
+ *                   pred, tpred, score, counts, score_sum, loss, loss_sum, acc may be NULL.  ws: at least 8 * N bytes.
+ * vqf_topk_rows     x (R, W) with leading dimension ldx >= W -> idx (R, k) int64, val (R, k) fp32: each row's k largest entries
+ *                   in descending order.  mode 0: val = the entries; mode 1: val = softmax probabilities exp(x - lse), lse the
+ *                   log-sum-exp of the WHOLE row.  One workgroup per row, the row held in LDS.
+ *                   Supported (vqf_topk_rows_supported): 1 <= k <= VQF_TOPK_MAX_K, k <= W <= VQF_TOPK_MAX_W; else
+ *                   VQF_E_UNSUPPORTED, nothing launched, outputs untouched.
+ */
+#define VQF_TOPK_MAX_K 16
+#define VQF_TOPK_MAX_W 16384
+int vqf_ce_loss_pred(const float* logits, const long long* target, int N, int A, float* loss, float* dlogits,
+                     long long* pred, long long* counts, double* loss_sum, float* acc, int accumulate, void* ws,
+                     size_t ws_bytes, void* stream);
+int vqf_answer_match_rows(const float* logp, const float* target, int N, int A, long long* pred, long long* tpred,
+                          float* score, long long* counts, double* score_sum, const float* loss, double* loss_sum,
+                          float* acc, int accumulate, void* ws, size_t ws_bytes, void* stream);
+int vqf_topk_rows_supported(int W, int k);
+int vqf_topk_rows(const float* x, int R, int W, int ldx, int k, int mode, long long* idx, float* val, void* stream);
+
 /* torch.optim.Adam(model.parameters(), lr) of solver.py:29,93 (amsgrad off, maximize off), all
  * tensors of a step in as few launches as possible (VQF_ADAM_MAX_TENSORS per launch):
  *   g += wd*p;  m += (g-m)(1-b1);  v = v*b2 + (1-b2) g g;

@@ -27,8 +27,10 @@ def __getattr__(name):
         "train_step": ".host.train_step", "CrossEntropyLoss": ".host.train_step",
         "KLDivLoss": ".host.train_step", "Adam": ".host.train_step",
         "data_loader": ".host.data_loader", "FeatureStager": ".host.data_loader",
+        "evaluate": ".host.evaluate", "loss_and_accuracy": ".host.evaluate", "Evaluator": ".host.evaluate",
+        "predict": ".host.evaluate", "topk_answers": ".host.evaluate",
     }
     if name in table:
         mod = importlib.import_module(table[name], __name__)
-        return mod if name in ("ops", "functions", "parallel", "train_step", "data_loader") else getattr(mod, name)
+        return mod if name in ("ops", "functions", "parallel", "train_step", "data_loader", "evaluate") else getattr(mod, name)
     raise AttributeError(name)

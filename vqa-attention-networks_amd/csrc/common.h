@@ -60,6 +60,9 @@ enum VqfKernelId {
   KID_HIE_AFF_LEVELS,
   KID_GUIDED_FWD,
   KID_GUIDED_BWD,
+  KID_CE_LOSS_PRED,
+  KID_ANSWER_MATCH,
+  KID_TOPK_ROWS,
   KID_COUNT
 };
 
@@ -186,6 +189,34 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+
+// Arg-max as ONE unsigned maximum (the evaluation tail: train.hip's predicting row pass, eval.hip): a (value, index) pair packed
+// so that the unsigned order of the word is the order of include/vqa_fusion.h's rules -- the larger value first; NaN above +inf;
+// -0 == +0; -inf an ordinary value; among equals (and among NaNs) the LOWER index first.  No index makes the word 0 (a lane
+// without an element holds 0 and loses to every element) and none makes it ~0 (eval.hip's "everything so far" bound).
+__device__ __forceinline__ unsigned long long vqf_argmax_key(float v, int idx) {
+  const unsigned int b = __float_as_uint(v);
+  const unsigned int k = (v != v) ? 0xFFFFFFFEu : (v == 0.f ? 0x80000000u : ((b & 0x80000000u) ? ~b : (b | 0x80000000u)));
+  return ((unsigned long long)k << 32) | (unsigned int)~(unsigned int)idx;
+}
+__device__ __forceinline__ int vqf_argmax_index(unsigned long long key) { return (int)~(unsigned int)key; }
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long t = __shfl_xor(v, o, 64);
+    v = t > v ? t : v;
+  }
+  return v;
+}
+// 256-thread workgroups; sh: 4 words; result on all threads
+__device__ __forceinline__ unsigned long long vqf_block256_max_u64(unsigned long long v, unsigned long long* sh) {
+  v = wave_max_u64(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const unsigned long long a = sh[0] > sh[1] ? sh[0] : sh[1], b = sh[2] > sh[3] ? sh[2] : sh[3];
+  return a > b ? a : b;
 }
 
 // Split-K combined inside the GEMM launch (cdna_hip_programming.md, "In-launch split-K reduction"): every K-slice workgroup

@@ -3,7 +3,8 @@
 //
 //  * cross entropy (nn.CrossEntropyLoss(), mean over the non-ignored rows, ignore_index = -100):
 //    one block per row computes lse, the row loss and dlogits = (softmax - onehot) / count in the
-//    same pass; a single-block kernel adds the row losses in a fixed order.
+//    same pass; a single-block kernel adds the row losses in a fixed order.  vqf_ce_loss_pred is the same two launches
+//    with the solver's next lines (solver.py:96-101) riding in them: the row's arg-max, the hit count, the loss total.
 //  * KL divergence (nn.KLDivLoss(), default reduction: mean over all N*A elements):
 //    loss = mean(t * (log t - logp)) with 0 where t == 0; dlogp = -t / (N*A).
 //  * Adam: m, v, p updated in place in the order of torch's single-tensor path; HBM-bound
@@ -32,12 +33,37 @@ __device__ __forceinline__ float block_max(float v, float* sh) {
   return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
 }
 
-// one block per row n
+// 4-wave block reductions of the totals below (sh: >= 4 elements; result on all threads)
+__device__ __forceinline__ double block_sum(double v, double* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int w = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[w] = v;
+  __syncthreads();
+  return sh[0] + sh[1] + sh[2] + sh[3];
+}
+__device__ __forceinline__ long long block_sum(long long v, long long* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int w = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[w] = v;
+  __syncthreads();
+  return sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+// one block per row n.  PRED: the row's argmax rides in the pass that finds the maximum for the log-sum-exp, as one
+// (value, index) key per lane (vqf_argmax_key: ties to the lowest index, NaN above everything); loss and dlogits keep the
+// arithmetic and the reduction order of the plain form, so both instantiations give the same bits.
+template <bool PRED>
 __global__ __launch_bounds__(TR_THREADS) void ce_rows_kernel(const float* __restrict__ logits,
                                                              const long long* __restrict__ target, int N, int A,
                                                              float* __restrict__ rowloss,
-                                                             float* __restrict__ dlogits) {
+                                                             float* __restrict__ dlogits,
+                                                             long long* __restrict__ pred, int* __restrict__ hit) {
   __shared__ float sh[4];
+  __shared__ unsigned long long shk[4];
   const int n = blockIdx.x;
   // rows that count (every block recomputes it: N int64 loads out of L2)
   float cnt = 0.f;
@@ -47,7 +73,15 @@ __global__ __launch_bounds__(TR_THREADS) void ce_rows_kernel(const float* __rest
 
   const float* x = logits + (size_t)n * A;
   float mx = -INFINITY;
-  for (int a = threadIdx.x; a < A; a += TR_THREADS) mx = fmaxf(mx, x[a]);
+  unsigned long long best = 0ull;
+  for (int a = threadIdx.x; a < A; a += TR_THREADS) {
+    const float v = x[a];
+    mx = fmaxf(mx, v);
+    if (PRED) {
+      const unsigned long long key = vqf_argmax_key(v, a);
+      best = key > best ? key : best;
+    }
+  }
   mx = block_max(mx, sh);
   float se = 0.f;
   for (int a = threadIdx.x; a < A; a += TR_THREADS) se += expf(x[a] - mx);
@@ -56,6 +90,13 @@ __global__ __launch_bounds__(TR_THREADS) void ce_rows_kernel(const float* __rest
   const long long t = target[n];
   const bool live = (t != -100);
   if (threadIdx.x == 0) rowloss[n] = (live && t >= 0 && t < A) ? (lse - x[t]) : (live ? NAN : 0.f);
+  if (PRED) {
+    const int p = vqf_argmax_index(vqf_block256_max_u64(best, shk));
+    if (threadIdx.x == 0) {
+      if (pred) pred[n] = p;
+      hit[n] = (live && (long long)p == t) ? 1 : 0;      // an out-of-range target is never a hit
+    }
+  }
   if (dlogits) {
     float* d = dlogits + (size_t)n * A;
     const float inv_se = 1.f / se;
@@ -66,10 +107,20 @@ __global__ __launch_bounds__(TR_THREADS) void ce_rows_kernel(const float* __rest
   }
 }
 
+// what the evaluation tail adds to the finish (vqf_ce_loss_pred): hit[N] per-row flags of the row kernel; every output may be NULL
+struct LossTotals {
+  const int* hit;
+  long long* counts;     // [0] hits, [1] rows whose target != -100
+  double* loss_sum;      // sum of the row losses (ignored rows hold 0)
+  float* acc;            // hits / counted rows of THIS call
+  int accumulate;        // != 0: counts and loss_sum are added to
+};
+
 // loss = sum(part[0..P)) * scale  (scale < 0: divide by the number of targets != -100 instead)
+template <bool TOTALS>
 __global__ __launch_bounds__(TR_THREADS) void loss_finish_kernel(const float* __restrict__ part, int P, float scale,
                                                                  const long long* __restrict__ target, int N,
-                                                                 float* __restrict__ loss) {
+                                                                 float* __restrict__ loss, const LossTotals tt) {
   __shared__ float sh[4];
   float s = 0.f;
   for (int i = threadIdx.x; i < P; i += TR_THREADS) s += part[i];
@@ -81,6 +132,28 @@ __global__ __launch_bounds__(TR_THREADS) void loss_finish_kernel(const float* __
     scale = 1.f / cnt;       // 0/0 -> NaN like torch when every row is ignored
   }
   if (threadIdx.x == 0) loss[0] = s * scale;
+  if (TOTALS) {              // P == N row losses, target != NULL; the same fixed order as above, in double / integers
+    __shared__ double shd[4];
+    __shared__ long long shl[4];
+    double ds = 0.0;
+    long long hits = 0, rows = 0;
+    for (int i = threadIdx.x; i < N; i += TR_THREADS) {
+      ds += (double)part[i];
+      hits += tt.hit[i];
+      rows += (target[i] != -100) ? 1 : 0;
+    }
+    ds = block_sum(ds, shd);
+    hits = block_sum(hits, shl);
+    rows = block_sum(rows, shl);
+    if (threadIdx.x == 0) {
+      if (tt.counts) {
+        tt.counts[0] = (tt.accumulate ? tt.counts[0] : 0) + hits;
+        tt.counts[1] = (tt.accumulate ? tt.counts[1] : 0) + rows;
+      }
+      if (tt.loss_sum) tt.loss_sum[0] = (tt.accumulate ? tt.loss_sum[0] : 0.0) + ds;
+      if (tt.acc) tt.acc[0] = (float)hits / (float)rows;      // 0 / 0 = NaN: the mean of no rows
+    }
+  }
 }
 
 // element-wise part of KLDivLoss; each block reduces a contiguous chunk into part[blockIdx.x]
@@ -183,9 +256,27 @@ int vqf_ce_loss(const float* logits, const long long* target, int N, int A, floa
   hipStream_t s = (hipStream_t)stream;
   float* rowloss = (float*)ws;
   vqf_prof_dims(N, A, 0);
-  VQF_LAUNCH(KID_CE_LOSS, ce_rows_kernel, dim3(N), dim3(TR_THREADS), 0, s, logits, target, N, A, rowloss, dlogits);
-  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(TR_THREADS), 0, s, (const float*)rowloss, N, -1.f, target, N,
-                     loss);
+  VQF_LAUNCH(KID_CE_LOSS, ce_rows_kernel<false>, dim3(N), dim3(TR_THREADS), 0, s, logits, target, N, A, rowloss, dlogits,
+             (long long*)nullptr, (int*)nullptr);
+  hipLaunchKernelGGL(loss_finish_kernel<false>, dim3(1), dim3(TR_THREADS), 0, s, (const float*)rowloss, N, -1.f, target, N,
+                     loss, LossTotals{});
+  return vqf_last_error();
+}
+
+int vqf_ce_loss_pred(const float* logits, const long long* target, int N, int A, float* loss, float* dlogits,
+                     long long* pred, long long* counts, double* loss_sum, float* acc, int accumulate, void* ws,
+                     size_t ws_bytes, void* stream) {
+  if (N <= 0 || A <= 0) return VQF_E_BADARG;
+  if (!logits || !target || !loss || !ws) return VQF_E_BADARG;
+  if (ws_bytes < (size_t)N * (sizeof(float) + sizeof(int))) return VQF_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  float* rowloss = (float*)ws;
+  int* hit = (int*)(rowloss + N);
+  vqf_prof_dims(N, A, 0);
+  VQF_LAUNCH(KID_CE_LOSS_PRED, ce_rows_kernel<true>, dim3(N), dim3(TR_THREADS), 0, s, logits, target, N, A, rowloss,
+             dlogits, pred, hit);
+  hipLaunchKernelGGL(loss_finish_kernel<true>, dim3(1), dim3(TR_THREADS), 0, s, (const float*)rowloss, N, -1.f, target, N,
+                     loss, LossTotals{hit, counts, loss_sum, acc, accumulate});
   return vqf_last_error();
 }
 
@@ -203,8 +294,8 @@ int vqf_kldiv_loss(const float* logp, const float* target, int N, int A, float* 
   vqf_prof_dims(N, A, 0);
   VQF_LAUNCH(KID_KLDIV_LOSS, kldiv_kernel, dim3((unsigned)parts), dim3(TR_THREADS), 0, s, logp, target, n, inv_n, part,
              dlogp);
-  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(TR_THREADS), 0, s, (const float*)part, (int)parts, inv_n,
-                     (const long long*)nullptr, 0, loss);
+  hipLaunchKernelGGL(loss_finish_kernel<false>, dim3(1), dim3(TR_THREADS), 0, s, (const float*)part, (int)parts, inv_n,
+                     (const long long*)nullptr, 0, loss, LossTotals{});
   return vqf_last_error();
 }
 

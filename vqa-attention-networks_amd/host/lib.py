@@ -149,6 +149,11 @@ SIGNATURES = {
     "vqf_loss_ws_bytes": (c_sz, [c_i, c_i]),
     "vqf_ce_loss": (c_i, [c_f, c_p, c_i, c_i, c_f, c_f, c_p, c_sz, c_p]),
     "vqf_kldiv_loss": (c_i, [c_f, c_f, c_i, c_i, c_f, c_f, c_p, c_sz, c_p]),
+    # the evaluation tail (csrc/train.hip, csrc/eval.hip): counts int64 x 2, sums double, all device pointers
+    "vqf_ce_loss_pred": (c_i, [c_f, c_p, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_f, c_i, c_p, c_sz, c_p]),
+    "vqf_answer_match_rows": (c_i, [c_f, c_f, c_i, c_i, c_p, c_p, c_f, c_p, c_p, c_f, c_p, c_f, c_i, c_p, c_sz, c_p]),
+    "vqf_topk_rows_supported": (c_i, [c_i, c_i]),
+    "vqf_topk_rows": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_p, c_f, c_p]),
     "vqf_adam_step": (c_i, [c_p, c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                             ctypes.c_double, ctypes.c_longlong, c_p]),
     "vqf_hbm_copy": (c_i, [c_p, c_p, ctypes.c_longlong, c_i, c_p]),

@@ -1161,13 +1161,98 @@ def ce_loss(logits, target, want_grad=True):
     return loss, d
 
 
-def kldiv_loss(logp, target, want_grad=True):
-    """-> (loss (1,), dlogp | None): nn.KLDivLoss() (element-wise mean) forward and gradient."""
+def _chk_totals(name, dev, accumulate, **bufs):
+    """the device totals of the evaluation tail: counts (2,) int64, sums (1,) float64, acc / loss (1,) float32"""
+    want = {"counts": (torch.int64, 2), "loss_sum": (torch.float64, 1), "score_sum": (torch.float64, 1),
+            "acc": (torch.float32, 1), "loss": (torch.float32, 1), "loss_out": (torch.float32, 1)}
+    for k, t in bufs.items():
+        if t is None:
+            continue
+        dt, n = want[k]
+        if not t.is_cuda or t.device != dev or t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise _l.VqfError("%s: %s must be a contiguous %s GPU tensor of %d element(s) on the inputs' device"
+                              % (name, k, dt, n))
+    return 1 if accumulate else 0
+
+
+def ce_loss_pred(logits, target, want_grad=True, want_pred=True, counts=None, loss_sum=None, acc=None, accumulate=False,
+                 loss_out=None):
+    """-> (loss (1,), dlogits | None, pred (N,) int64 | None): ce_loss (the same bits) with the row arg-max riding in its
+    row pass.  counts (2,) int64 = [rows with pred == target, rows with target != -100], loss_sum (1,) float64 = the sum of
+    the row losses: written, or added to when `accumulate`; acc (1,) fp32 = this call's hits / counted rows."""
+    _chk(logits)
+    if logits.dim() != 2 or target.shape != (logits.shape[0],):
+        raise _l.VqfError("ce_loss_pred: logits (N,A) and targets (N,) expected")
+    if not target.is_cuda or target.dtype != torch.int64 or not target.is_contiguous():
+        raise _l.VqfError("ce_loss_pred: contiguous int64 GPU targets expected")
+    acc_flag = _chk_totals("ce_loss_pred", logits.device, accumulate, counts=counts, loss_sum=loss_sum, acc=acc,
+                           loss_out=loss_out)
+    N, A = logits.shape
+    loss = loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=logits.device)
+    d = torch.empty_like(logits) if want_grad else None
+    pred = torch.empty(N, dtype=torch.int64, device=logits.device) if want_pred else None
+    nb = 8 * N
+    ws = workspace(logits.device, nb)
+    _l.check(_lib().vqf_ce_loss_pred(_ptr(logits), _ptr(target), N, A, _ptr(loss), _ptr(d), _ptr(pred), _ptr(counts),
+                                     _ptr(loss_sum), _ptr(acc), acc_flag, _ptr(ws), nb, _stream()), "vqf_ce_loss_pred")
+    return loss, d, pred
+
+
+def answer_match_rows(logp, target, want_score=True, counts=None, score_sum=None, loss=None, loss_sum=None, acc=None,
+                      accumulate=False):
+    """-> (pred (N,), tpred (N,) int64, score (N,) fp32 | None) for the soft-target models: the arg-max of the log-probs, the
+    arg-max of the soft target (solver.py:100) and score = target[n, pred[n]].  counts = [rows with pred == tpred, N],
+    score_sum = the sum of score, loss_sum = N * loss[0] (`loss`: the device scalar kldiv_loss returned): written, or
+    added to when `accumulate`; acc (1,) fp32 = this call's hits / N."""
+    _chk(logp, target)
+    if logp.dim() != 2 or target.shape != logp.shape:
+        raise _l.VqfError("answer_match_rows: log-probs and targets of the same (N,A) shape expected")
+    acc_flag = _chk_totals("answer_match_rows", logp.device, accumulate, counts=counts, score_sum=score_sum, loss=loss,
+                           loss_sum=loss_sum, acc=acc)
+    N, A = logp.shape
+    pred = torch.empty(N, dtype=torch.int64, device=logp.device)
+    tpred = torch.empty(N, dtype=torch.int64, device=logp.device)
+    score = torch.empty(N, dtype=torch.float32, device=logp.device) if want_score else None
+    nb = 8 * N
+    ws = workspace(logp.device, nb)
+    _l.check(_lib().vqf_answer_match_rows(_ptr(logp), _ptr(target), N, A, _ptr(pred), _ptr(tpred), _ptr(score),
+                                          _ptr(counts), _ptr(score_sum), _ptr(loss), _ptr(loss_sum), _ptr(acc), acc_flag,
+                                          _ptr(ws), nb, _stream()), "vqf_answer_match_rows")
+    return pred, tpred, score
+
+
+def topk_rows_supported(W, k):
+    return bool(_lib().vqf_topk_rows_supported(int(W), int(k)))
+
+
+def topk_rows(x, k, mode=0):
+    """x (R, W) fp32, unit stride along W (rows may be strided: a column slice of a wider matrix) -> (idx (R, k) int64,
+    val (R, k) fp32), every row's k largest entries in descending order, ties to the lowest index, NaN first.
+    mode 0: the entries; mode 1: their softmax probabilities over the whole row."""
+    if not x.is_cuda:
+        raise _l.VqfError("vqa fusion ops need GPU tensors (HIP extension is the only path; no CPU fallback)")
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise _l.VqfError("topk_rows: a non-empty fp32 (R, W) tensor expected")
+    R, W = x.shape
+    ldx = x.stride(0) if R > 1 else W
+    if x.stride(1) != 1 or ldx < W:
+        raise _l.VqfError("topk_rows: unit stride along the row and a row pitch >= W expected")
+    k = int(k)
+    idx = torch.empty(R, max(k, 0), dtype=torch.int64, device=x.device)
+    val = torch.empty(R, max(k, 0), dtype=torch.float32, device=x.device)
+    _l.check(_lib().vqf_topk_rows(_ptr(x), R, W, ldx, k, int(mode), _ptr(idx), _ptr(val), _stream()), "vqf_topk_rows")
+    return idx, val
+
+
+def kldiv_loss(logp, target, want_grad=True, loss_out=None):
+    """-> (loss (1,), dlogp | None): nn.KLDivLoss() (element-wise mean) forward and gradient.
+    loss_out: a (1,) fp32 GPU tensor to write the loss into (the evaluator's device record) instead of a new one."""
     _chk(logp, target)
     if logp.dim() != 2 or target.shape != logp.shape:
         raise _l.VqfError("kldiv_loss: log-probs and targets of the same (N,A) shape expected")
+    _chk_totals("kldiv_loss", logp.device, False, loss_out=loss_out)
     N, A = logp.shape
-    loss = torch.empty(1, dtype=torch.float32, device=logp.device)
+    loss = loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=logp.device)
     d = torch.empty_like(logp) if want_grad else None
     ws, nb = _loss_ws(N, A, logp.device)
     _l.check(_lib().vqf_kldiv_loss(_ptr(logp), _ptr(target), N, A, _ptr(loss), _ptr(d), _ptr(ws), nb, _stream()),
