@@ -544,6 +544,47 @@ size_t vqf_guided_logits_bwd_ws_bytes(int N, int S, int E, int G);
 int vqf_guided_logits_bwd(const float* dlogits, const float* Xh, int ldx, const float* gp, const float* w, int N, int S, int E,
                           int G, float* dXh, int lddx, float* dgp, float* dw, void* ws, size_t ws_bytes, void* stream);
 
+/* The grouped forms: N questions over U shared images (HieCoAttenLadder.forward(..., img_index); additions within ABI 7).
+ * idx (N) int32: question n looks at image idx[n]; order (N) int32: the questions sorted by image (a stable sort of idx);
+ * grp_off (U + 1) int32: image u's questions are order[grp_off[u]] .. order[grp_off[u + 1] - 1] (host/hie_ladder.py::_group_index
+ * derives all three on the device).  The kernels clamp idx to [0, U - 1], order to [0, N - 1] and grp_off to [0, N] (kept
+ * monotone) where they read them: nothing these arrays hold makes a kernel read or write out of range.  Every sum over a group
+ * runs in `order`, inside one thread, no atomics: two runs give the same bits; an empty group gives exact zeros.
+ *   guided_logits_fwd_grouped   Xh (U*S, ldx), gp (N, G E) (not NULL), logits (N*S, G): row block n reads the Xh rows of image
+ *                               idx[n] and the guidance row gp[n] -- the kernel of vqf_guided_logits_fwd;
+ *   guided_logits_bwd_grouped   dlogits (N*S, G); H_n = tanh(Xh[u] + gp[n]) recomputed per question, never stored;
+ *                               dXh (U*S, G E; pitch lddx)[u, s, g E + e] = sum_{n in group u} dlogits[n, s, g] w[g, e] (1 - H_n^2);
+ *                               dgp (N, G E)[n] = sum_s dlogits[n, s, g] w[g, e] (1 - H_n^2); dw (G, E) = sum_{n, s} dlogits H_n.
+ *                               A workgroup owns a tile of one image's rows and walks its questions four at a time: the first
+ *                               pass writes dXh, later passes add to what the same thread wrote.  ws: at least
+ *                               vqf_guided_logits_bwd_grouped_ws_bytes;
+ *   glimpse_pool_fwd_grouped    feat (U, S, C), logits (N*S, G) -> wts (N, G, S), pooled (N, G C): the kernels of vqf_glimpse_pool_fwd
+ *                               reading image idx[n]'s rows;
+ *   glimpse_pool_bwd_grouped    dlogits (N*S, G) per question (the kernel of vqf_glimpse_pool_bwd), then, dfeat != NULL, one pass
+ *                               dfeat (U, S, C)[u, s, :] = sum_{n in group u} sum_g wts[n, g, s] dpooled[n, g C:(g + 1) C];
+ *   row_block_gather            dst (N, blk) = src (U, blk)[idx[n]] (the parallel mode's V (U, L E) -> (N, L E));
+ *   row_block_group_sum         out (U, blk)[u] = sum_{n in group u} src (N, blk)[n], the gather's backward.
+ * Supported: vqf_guided_logits_grouped_supported = vqf_guided_logits_supported(N, S, E, G) and 1 <= U <= 65535;
+ * vqf_glimpse_pool_grouped_supported: N, U <= 65535, S <= 1024, C % 4 == 0, G in {1, 2, 3}; vqf_row_block_supported: N, U <= 65535,
+ * blk % 4 == 0, blk <= 2^31; 16-byte aligned float operands, 4-byte aligned index arrays. */
+int vqf_guided_logits_grouped_supported(int N, int U, int S, int E, int G);
+int vqf_guided_logits_fwd_grouped(const float* Xh, int ldx, const float* gp, const float* w, const int* idx, int N, int U, int S,
+                                  int E, int G, float* logits, void* stream);
+size_t vqf_guided_logits_bwd_grouped_ws_bytes(int N, int U, int S, int E, int G);
+int vqf_guided_logits_bwd_grouped(const float* dlogits, const float* Xh, int ldx, const float* gp, const float* w, const int* order,
+                                  const int* grp_off, int N, int U, int S, int E, int G, float* dXh, int lddx, float* dgp, float* dw,
+                                  void* ws, size_t ws_bytes, void* stream);
+int vqf_glimpse_pool_grouped_supported(int N, int U, int S, int C, int G);
+int vqf_glimpse_pool_fwd_grouped(const float* feat, const float* logits, const int* idx, int N, int U, int S, int C, int G,
+                                 float* wts, float* pooled, void* stream);
+int vqf_glimpse_pool_bwd_grouped(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
+                                 const int* order, const int* grp_off, int N, int U, int S, int C, int G, float* dlogits,
+                                 float* dfeat, void* stream);
+int vqf_row_block_supported(int N, int U, long long blk);
+int vqf_row_block_gather(const float* src, const int* idx, int N, int U, long long blk, float* dst, void* stream);
+int vqf_row_block_group_sum(const float* src, const int* order, const int* grp_off, int N, int U, long long blk, float* out,
+                            void* stream);
+
 /* softmax over the last axis of (R,W) and its backward   modules.py:91-92 */
 int vqf_softmax_rows_fwd(const float* x, int R, int W, float* y, void* stream);
 int vqf_softmax_rows_bwd(const float* dy, const float* y, int R, int W, float* dx, void* stream);

@@ -1,6 +1,7 @@
 """Train step of HieCoAttenLadder (host/hie_ladder.py) at config 4's shapes: forward, CE loss, backward, the project's Adam.
 
     python tools/hie_ladder_bench.py [--batch 256] [--steps 20] [--warmup 5] [--lengths] [--coatt parallel|alternating] [--json OUT]
+                                     [--questions-per-image Q] [--repeats R] [--no-context]
 
 Prints ms / step and QA pairs / s (device events around the timed steps), the step's FLOP count from the shapes with its
 MFMA floor at 157.3 TF/s (fp32 MFMA peak of the MI355X) and the fraction reached, the library profiler's per-kernel table
@@ -9,7 +10,12 @@ of one extra step, and config 4's single-level HieCoAtten at the same shapes in 
 rows: the FLOP count is the unmasked step's).
 --coatt alternating: the alternating co-attention model (its own FLOP table), and after it the streaming yardsticks of its
 image side in the same process: vqf_guided_logits_fwd / _bwd over the (N*L, 3E) projection beside vqf_att_logits_fwd over a
-tensor of the same size (the parallel mode's Hv pass: the same bytes read) and a device copy of that many bytes."""
+tensor of the same size (the parallel mode's Hv pass: the same bytes read) and a device copy of that many bytes.
+--questions-per-image Q: the shared-image call, forward(img (U, L, D), ids, q_length, img_index): N stays --batch, U = N / Q,
+img_index = arange(N) // Q shuffled with a fixed seed (Q = 1: every question its own image, through the index).  The FLOP table
+stays the per-question model's (what the step would cost without sharing).  --repeats R: R timed windows of --steps steps; the
+line reports their median and the spread (max - min), the run-to-run figure to hold differences against.  --no-context: skip
+the streaming yardsticks and the HieCoAtten step."""
 import argparse
 import json
 import os
@@ -101,13 +107,16 @@ def stream_yardsticks(N, L, E, reps=20):
     return {name: {"ms": ms, "bytes": b} for name, ms, b in rows}
 
 
-def timed(model, img, ids, target, steps, warmup, q_len=None):
+def timed(model, img, ids, target, steps, warmup, q_len=None, img_index=None, repeats=1):
     crit = vqa_amd.CrossEntropyLoss()
     opt = vqa_amd.Adam(model.parameters(), lr=1e-4)
 
     def step():
         opt.zero_grad(set_to_none=True)
-        out = model(img, ids) if q_len is None else model(img, ids, q_len)
+        if img_index is not None:
+            out = model(img, ids, q_len, img_index=img_index)
+        else:
+            out = model(img, ids) if q_len is None else model(img, ids, q_len)
         loss = crit(out[0], target)
         loss.backward()
         opt.step()
@@ -115,19 +124,23 @@ def timed(model, img, ids, target, steps, warmup, q_len=None):
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(steps):
-        step()
-    b.record()
-    torch.cuda.synchronize()
-    ms = a.elapsed_time(b) / steps
+    windows = []
+    for _ in range(max(1, repeats)):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(steps):
+            step()
+        b.record()
+        torch.cuda.synchronize()
+        windows.append(a.elapsed_time(b) / steps)
+    ms = sorted(windows)[len(windows) // 2]
     ops = vqa_amd.ops
     ops.prof_reset()
     ops.prof_enable(True)
     step()
     torch.cuda.synchronize()
     ops.prof_enable(False)
+    timed.windows = windows
     return ms, ops.prof_report()
 
 
@@ -139,11 +152,22 @@ def main():
     ap.add_argument("--lengths", action="store_true", help="time the masked step: seeded question lengths in [3, T]")
     ap.add_argument("--coatt", choices=("parallel", "alternating"), default="parallel", help="the co-attention mechanism of the levels")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--questions-per-image", type=int, default=0, metavar="Q",
+                    help="shared images: U = batch / Q images, img_index = arange(N) // Q shuffled (seed 2); 0: no index")
+    ap.add_argument("--repeats", type=int, default=1, help="timed windows; the median and the spread (max - min) are reported")
+    ap.add_argument("--no-context", action="store_true", help="skip the streaming yardsticks and the HieCoAtten step")
     a = ap.parse_args()
     N, L, D, E, T, H, O, V = a.batch, 196, 2048, 512, 14, 1024, 1000, 15881
     dev = "cuda:0"
     torch.manual_seed(0)
-    img = torch.rand(N, L, D, device=dev)
+    Q = a.questions_per_image
+    if Q < 0 or (Q and N % Q):
+        ap.error("--questions-per-image must divide --batch")
+    U = N // Q if Q else N
+    img_index = None
+    if Q:
+        img_index = (torch.arange(N) // Q)[torch.randperm(N, generator=torch.Generator().manual_seed(2))].to(dev)
+    img = torch.rand(U, L, D, device=dev)
     ids = torch.randint(0, V, (N, T), device=dev)
     target = torch.randint(0, O, (N,), device=dev)
     ladder = vqa_amd.HieCoAttenLadder(block_num=L, word_num=T, img_size=D, vocab_size=V, embed_size=E, hidden_size=H,
@@ -151,12 +175,17 @@ def main():
     q_len = None
     if a.lengths:
         q_len = torch.randint(3, T + 1, (N,), generator=torch.Generator().manual_seed(1)).to(dev)
-    ms, kern = timed(ladder, img, ids, target, a.steps, a.warmup, q_len)
+    ms, kern = timed(ladder, img, ids, target, a.steps, a.warmup, q_len, img_index, a.repeats)
+    windows = list(timed.windows)
+    launches = sum(n for n, _ in kern.values())
     parts, flops = (ladder_flops if a.coatt == "parallel" else ladder_alt_flops)(N, L, D, E, T, H, O)
     floor_ms = flops / (PEAK_TFS * 1e12) * 1e3
     print("HieCoAttenLadder (coatt=%s) train step  B=%d L=%d img=%d E=%d T=%d hidden=%d out=%d%s"
           % (a.coatt, N, L, D, E, T, H, O, "  question lengths in [3, %d], mean %.1f" % (T, float(q_len.float().mean())) if a.lengths else ""))
-    print("  %.3f ms/step   %.0f QA pairs/s" % (ms, N / ms * 1e3))
+    if Q:
+        print("  shared images: %d questions per image, U = %d images, img_index shuffled" % (Q, U))
+    print("  %.3f ms/step   %.0f QA pairs/s   (median of %d windows of %d steps, spread %.3f ms; %d library launches per step)"
+          % (ms, N / ms * 1e3, len(windows), a.steps, max(windows) - min(windows), launches))
     print("  %.3f TFLOP/step:" % (flops / 1e12))
     for k, v in parts.items():
         print("    %-56s %7.1f GFLOP" % (k, v / 1e9))
@@ -166,13 +195,16 @@ def main():
         print("    %-28s %4d launches  %8.3f ms" % (k, n, t))
     del ladder
     torch.cuda.empty_cache()
-    yard = stream_yardsticks(N, L, E) if a.coatt == "alternating" else None
-    hie = vqa_amd.HieCoAtten(block_num=L, word_num=T, img_size=D, vocab_size=V, embed_size=E, output_size=O).to(dev).train()
-    ms4, _ = timed(hie, img, ids, target, a.steps, a.warmup)
-    print("config 4 HieCoAtten (word level only) at the same shapes: %.3f ms/step   %.0f QA pairs/s" % (ms4, N / ms4 * 1e3))
+    yard, ms4 = None, None
+    if not a.no_context:
+        yard = stream_yardsticks(N, L, E) if a.coatt == "alternating" else None
+        hie = vqa_amd.HieCoAtten(block_num=L, word_num=T, img_size=D, vocab_size=V, embed_size=E, output_size=O).to(dev).train()
+        ms4, _ = timed(hie, torch.rand(N, L, D, device=dev) if Q else img, ids, target, a.steps, a.warmup)
+        print("config 4 HieCoAtten (word level only) at the same shapes: %.3f ms/step   %.0f QA pairs/s" % (ms4, N / ms4 * 1e3))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        json.dump({"coatt": a.coatt, "yardsticks": yard, "lengths": bool(a.lengths), "ms_per_step": ms, "qa_per_s": N / ms * 1e3, "tflop_per_step": flops / 1e12, "floor_ms": floor_ms,
+        json.dump({"coatt": a.coatt, "questions_per_image": Q, "images": U, "windows_ms": windows, "spread_ms": max(windows) - min(windows),
+                   "launches_per_step": launches, "yardsticks": yard, "lengths": bool(a.lengths), "ms_per_step": ms, "qa_per_s": N / ms * 1e3, "tflop_per_step": flops / 1e12, "floor_ms": floor_ms,
                    "fraction_of_floor": floor_ms / ms, "kernels": kern, "hiecoatten_ms_per_step": ms4}, open(a.json, "w"), indent=1)
 
 

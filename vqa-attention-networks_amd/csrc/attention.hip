@@ -215,12 +215,21 @@ __device__ __forceinline__ int pool_len(const int* __restrict__ lens, int n, int
   return len < 1 ? 1 : (len > S ? S : len);
 }
 
+// idx (the grouped forms, vqf_glimpse_pool_*_grouped; N int32, null: u = n): sample n pools the feature rows of image
+// u = idx[n], clamped to [0, U - 1] here (feat is (U, S, C)); logits, wts, pooled and dlogits stay per sample.
+__device__ __forceinline__ int pool_src(const int* __restrict__ idx, int n, int U) {
+  if (!idx) return n;
+  const int u = idx[n];
+  return u < 0 ? 0 : (u >= U ? U - 1 : u);
+}
+
 // grid (ceil(C/1024), N); thread = 4 consecutive channels
 template <int G, typename FT>
 __global__ void glimpse_pool_fwd_kernel(const FT* __restrict__ feat,
                                         const float* __restrict__ logits, int N, int S, int C,
                                         int unit, float* __restrict__ wts,
-                                        float* __restrict__ pooled, const int* __restrict__ lens) {
+                                        float* __restrict__ pooled, const int* __restrict__ lens,
+                                        const int* __restrict__ idx, int U) {
   __shared__ float w[G][MAXS];
   const int n = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -249,7 +258,7 @@ __global__ void glimpse_pool_fwd_kernel(const FT* __restrict__ feat,
 
   const int c = (blockIdx.x * blockDim.x + tid) * 4;
   if (c >= C) return;
-  const FT* f = feat + (long long)n * S * C + c;
+  const FT* f = feat + (long long)pool_src(idx, n, U) * S * C + c;
   const bool vec = ((C & 3) == 0) && aligned16_dev(feat) && aligned16_dev(pooled);
   f32x4 a[G];
 #pragma unroll
@@ -296,7 +305,8 @@ __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
                                         const float* __restrict__ dwts_extra,
                                         const FT* __restrict__ feat,
                                         const float* __restrict__ wts, int N, int S, int C, int unit,
-                                        float* __restrict__ dlogits, float* __restrict__ dfeat, const int* __restrict__ lens) {
+                                        float* __restrict__ dlogits, float* __restrict__ dfeat, const int* __restrict__ lens,
+                                        const int* __restrict__ idx, int U) {
   __shared__ float dw[G][MAXS];
   __shared__ float ws[G][MAXS];
   const int n = blockIdx.x;
@@ -319,7 +329,7 @@ __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
       for (int g = 0; g < G; ++g) pr[g][k] = c < C ? *reinterpret_cast<const f32x4*>(dp + g * C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
     for (int s = wave; s < Sv; s += nwave) {
-      const FT* f = feat + ((long long)n * S + s) * C;
+      const FT* f = feat + ((long long)pool_src(idx, n, U) * S + s) * C;
       f32x4 x[KC];
 #pragma unroll
       for (int k = 0; k < KC; ++k) {
@@ -338,7 +348,7 @@ __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
     }
   } else
   for (int s = wave; s < S; s += nwave) {
-    const FT* f = feat + ((long long)n * S + s) * C;
+    const FT* f = feat + ((long long)pool_src(idx, n, U) * S + s) * C;
     float* df = dfeat ? dfeat + ((long long)n * S + s) * C : nullptr;
     if (s >= Sv) {                                     // (wave-uniform) a padded row: zero gradient, feat unread
       if (df) {
@@ -506,7 +516,8 @@ namespace {
 template <int G, typename FT>
 __global__ void __launch_bounds__(1024) glimpse_pool_fwd_rows_kernel(const FT* __restrict__ feat, const float* __restrict__ logits,
                                                                      int N, int S, int C, int unit, float* __restrict__ wts,
-                                                                     float* __restrict__ pooled, const int* __restrict__ lens) {
+                                                                     float* __restrict__ pooled, const int* __restrict__ lens,
+                                                                     const int* __restrict__ idx, int U) {
   extern __shared__ float smem_g[];
   float* w = smem_g;                                   // [G][S]
   float* red = smem_g + G * S;                         // [RS][G][C]
@@ -535,7 +546,7 @@ __global__ void __launch_bounds__(1024) glimpse_pool_fwd_rows_kernel(const FT* _
     for (int i = tid; i < G * S; i += blockDim.x) wts[(long long)n * G * S + i] = w[i];
   const int CT = C >> 2, RS = blockDim.x / CT;
   const int c4 = tid % CT, rs = tid / CT;
-  const FT* f = feat + (long long)n * S * C + 4 * c4;
+  const FT* f = feat + (long long)pool_src(idx, n, U) * S * C + 4 * c4;
   f32x4 a[G];
 #pragma unroll
   for (int g = 0; g < G; ++g) a[g] = f32x4{0, 0, 0, 0};
@@ -562,7 +573,7 @@ __global__ void __launch_bounds__(1024) glimpse_pool_fwd_rows_kernel(const FT* _
 
 template <typename FT>
 int glimpse_fwd_launch(const FT* feat, const float* logits, int N, int S, int C, int G, int unit_softmax,
-                       float* wts, float* pooled, void* stream, const int* lens = nullptr) {
+                       float* wts, float* pooled, void* stream, const int* lens = nullptr, const int* idx = nullptr, int U = 0) {
   if (!feat || !logits || !pooled || N <= 0 || S <= 0 || C <= 0 || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
   if (S > MAXS || G < 1 || G > 3 || N > 65535) return VQF_E_UNSUPPORTED;
   dim3 grid((C + 1023) / 1024, N);
@@ -577,33 +588,33 @@ int glimpse_fwd_launch(const FT* feat, const float* logits, int N, int S, int C,
       if (RS >= G && lds <= 64 * 1024) {
         if (G == 3)
           VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<3, FT>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
-                     unit_softmax, wts, pooled, lens);
+                     unit_softmax, wts, pooled, lens, idx, U);
         else if (G == 2)
           VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<2, FT>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
-                     unit_softmax, wts, pooled, lens);
+                     unit_softmax, wts, pooled, lens, idx, U);
         else
           VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<1, FT>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
-                     unit_softmax, wts, pooled, lens);
+                     unit_softmax, wts, pooled, lens, idx, U);
         return vqf_last_error();
       }
     }
   }
   if (G == 3)
     VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<3, FT>), grid, dim3(256), 0, s, feat, logits, N, S,
-               C, unit_softmax, wts, pooled, lens);
+               C, unit_softmax, wts, pooled, lens, idx, U);
   else if (G == 2)
     VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<2, FT>), grid, dim3(256), 0, s, feat, logits, N, S,
-               C, unit_softmax, wts, pooled, lens);
+               C, unit_softmax, wts, pooled, lens, idx, U);
   else
     VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<1, FT>), grid, dim3(256), 0, s, feat, logits, N, S,
-               C, unit_softmax, wts, pooled, lens);
+               C, unit_softmax, wts, pooled, lens, idx, U);
   return vqf_last_error();
 }
 
 template <typename FT>
 int glimpse_bwd_launch(const float* dpooled, const float* dwts_extra, const FT* feat, const float* wts, int N,
                        int S, int C, int G, int unit_softmax, float* dlogits, float* dfeat, void* stream,
-                       const int* lens = nullptr) {
+                       const int* lens = nullptr, const int* idx = nullptr, int U = 0) {
   if (!dpooled || !feat || !wts || !dlogits || N <= 0 || S <= 0 || C <= 0 || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
   if (S > MAXS || G < 1 || G > 3) return VQF_E_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
@@ -623,14 +634,96 @@ int glimpse_bwd_launch(const float* dpooled, const float* dwts_extra, const FT* 
   const dim3 block(64 * waves);
   if (G == 3)
     VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<3, FT>), dim3(N), block, 0, s, dpooled,
-               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens);
+               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U);
   else if (G == 2)
     VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<2, FT>), dim3(N), block, 0, s, dpooled,
-               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens);
+               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U);
   else
     VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<1, FT>), dim3(N), block, 0, s, dpooled,
-               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens);
+               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U);
   return vqf_last_error();
+}
+
+// ---- the grouped forms: U images shared by N questions (HieCoAttenLadder's img_index) ------------------------------------------
+// order (N): the questions sorted by image (stable); grp_off (U + 1): image u's questions are order[grp_off[u]] ..
+// order[grp_off[u + 1] - 1].  Every sum over a group runs in that order in one thread: no atomics, the same bits on every run;
+// an empty group gives exact zeros.  grp_off is clamped to [0, N] (and kept monotone) and order to [0, N - 1] where they are
+// read, idx to [0, U - 1]: nothing these arrays hold makes a kernel read or write out of range.
+constexpr int GP_ROWS = 16;      // feature rows of an image per workgroup of the dfeat sum (their sums stay in registers)
+constexpr int GP_Q = 4;          // questions of a group per trip (their dpooled loads are issued together)
+
+// dfeat[u, s, c] = sum_{n in group u} sum_g wts[n, g, s] dpooled[n, g C + c].  grid (ceil(S / GP_ROWS), U); a thread owns four
+// channels (and c + 4 blockDim, ...), the weights are workgroup-uniform loads.
+template <int G>
+__global__ void __launch_bounds__(256) glimpse_dfeat_grouped_kernel(const float* __restrict__ dpooled, const float* __restrict__ wts,
+                                                                    const int* __restrict__ order, const int* __restrict__ grp_off,
+                                                                    int N, int S, int C, float* __restrict__ dfeat) {
+  const int u = blockIdx.y;
+  const int s0 = blockIdx.x * GP_ROWS, nr = min(GP_ROWS, S - s0);
+  const int jb = min(max(grp_off[u], 0), N), je = min(max(grp_off[u + 1], jb), N);
+  for (int c = threadIdx.x * 4; c < C; c += blockDim.x * 4) {
+    f32x4 acc[GP_ROWS];
+#pragma unroll
+    for (int r = 0; r < GP_ROWS; ++r) acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j0 = jb; j0 < je; j0 += GP_Q) {
+      int nn[GP_Q];
+      f32x4 p[GP_Q][G];
+#pragma unroll
+      for (int q = 0; q < GP_Q; ++q) {                              // past the group's end: the last question again (not used)
+        nn[q] = min(max(order[min(j0 + q, je - 1)], 0), N - 1);
+#pragma unroll
+        for (int g = 0; g < G; ++g) p[q][g] = *reinterpret_cast<const f32x4*>(dpooled + ((long long)nn[q] * G + g) * C + c);
+      }
+#pragma unroll
+      for (int q = 0; q < GP_Q; ++q) {
+        if (j0 + q < je) {
+          const float* wq = wts + (long long)nn[q] * G * S + s0;
+#pragma unroll
+          for (int r = 0; r < GP_ROWS; ++r) {
+            if (r < nr) {
+#pragma unroll
+              for (int g = 0; g < G; ++g) acc[r] += p[q][g] * wq[g * S + r];
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < GP_ROWS; ++r)
+      if (r < nr) *reinterpret_cast<f32x4*>(dfeat + ((long long)u * S + s0 + r) * C + c) = acc[r];
+  }
+}
+
+// dst[n] = src[idx[n]] for row blocks of blk4 16-byte groups (V (U, L E) -> (N, L E)).  grid (x, N)
+__global__ void __launch_bounds__(256) row_block_gather_kernel(const f32x4* __restrict__ src, const int* __restrict__ idx, int U,
+                                                               long long blk4, f32x4* __restrict__ dst) {
+  const int n = blockIdx.y;
+  const f32x4* s = src + (long long)pool_src(idx, n, U) * blk4;
+  f32x4* d = dst + (long long)n * blk4;
+  const long long step = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < blk4; i += step) d[i] = s[i];
+}
+
+// out[u] = sum_{n in group u} src[n], the gather's backward.  grid (x, U); GP_Q loads in flight, added in `order`
+__global__ void __launch_bounds__(256) row_block_group_sum_kernel(const f32x4* __restrict__ src, const int* __restrict__ order,
+                                                                  const int* __restrict__ grp_off, int N, long long blk4,
+                                                                  f32x4* __restrict__ out) {
+  const int u = blockIdx.y;
+  const int jb = min(max(grp_off[u], 0), N), je = min(max(grp_off[u + 1], jb), N);
+  const long long step = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < blk4; i += step) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int j0 = jb; j0 < je; j0 += GP_Q) {
+      f32x4 x[GP_Q];
+#pragma unroll
+      for (int q = 0; q < GP_Q; ++q)
+        x[q] = src[(long long)min(max(order[min(j0 + q, je - 1)], 0), N - 1) * blk4 + i];
+#pragma unroll
+      for (int q = 0; q < GP_Q; ++q)
+        if (j0 + q < je) acc += x[q];
+    }
+    out[(long long)u * blk4 + i] = acc;
+  }
 }
 }  // namespace
 
@@ -670,6 +763,69 @@ int vqf_glimpse_pool_bwd_bf16(const float* dpooled, const float* dwts_extra, con
                               float* dlogits, void* stream) {
   return glimpse_bwd_launch<__bf16>(dpooled, dwts_extra, (const __bf16*)feat, wts, N, S, C, G, unit_softmax,
                                     dlogits, nullptr, stream);
+}
+
+int vqf_glimpse_pool_grouped_supported(int N, int U, int S, int C, int G) {
+  return N >= 1 && N <= 65535 && U >= 1 && U <= 65535 && S >= 1 && S <= MAXS && C >= 4 && (C % 4) == 0 && G >= 1 && G <= 3;
+}
+
+int vqf_glimpse_pool_fwd_grouped(const float* feat, const float* logits, const int* idx, int N, int U, int S, int C, int G,
+                                 float* wts, float* pooled, void* stream) {
+  if (!idx || (((uintptr_t)idx) & 3) || N <= 0 || U <= 0 || S <= 0 || C <= 0) return VQF_E_BADARG;
+  if (!vqf_glimpse_pool_grouped_supported(N, U, S, C, G)) return VQF_E_UNSUPPORTED;
+  return glimpse_fwd_launch<float>(feat, logits, N, S, C, G, 0, wts, pooled, stream, nullptr, idx, U);
+}
+
+int vqf_glimpse_pool_bwd_grouped(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
+                                 const int* order, const int* grp_off, int N, int U, int S, int C, int G, float* dlogits,
+                                 float* dfeat, void* stream) {
+  if (!idx || !order || !grp_off || ((((uintptr_t)idx) | ((uintptr_t)order) | ((uintptr_t)grp_off)) & 3) || N <= 0 || U <= 0 ||
+      S <= 0 || C <= 0)
+    return VQF_E_BADARG;
+  if (!vqf_glimpse_pool_grouped_supported(N, U, S, C, G)) return VQF_E_UNSUPPORTED;
+  if (!aligned16(dpooled) || !aligned16(dfeat)) return VQF_E_ALIGN;
+  // the per-question half (dlogits: feat[idx[n]] . dpooled[n], then the softmax backward) on the kernel of the plain form ...
+  int rc = glimpse_bwd_launch<float>(dpooled, dwts_extra, feat, wts, N, S, C, G, 0, dlogits, nullptr, stream, nullptr, idx, U);
+  if (rc || !dfeat) return rc;
+  // ... and the per-image half: dfeat[u] = the sum over the image's questions, in `order`
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((S + GP_ROWS - 1) / GP_ROWS, U), block(C / 4 >= 256 ? 256 : ((C / 4 + 63) / 64) * 64);
+#define VQF_GD(G_)                                                                                                      \
+  VQF_LAUNCH(KID_GLIMPSE_DFEAT_GROUPED, (glimpse_dfeat_grouped_kernel<G_>), grid, block, 0, s, dpooled, wts, order, grp_off, N, S, C, \
+             dfeat)
+  if (G == 3) VQF_GD(3);
+  else if (G == 2) VQF_GD(2);
+  else VQF_GD(1);
+#undef VQF_GD
+  return vqf_last_error();
+}
+
+int vqf_row_block_supported(int N, int U, long long blk) {
+  return N >= 1 && N <= 65535 && U >= 1 && U <= 65535 && blk >= 4 && (blk % 4) == 0 && blk <= (1LL << 31);
+}
+
+int vqf_row_block_gather(const float* src, const int* idx, int N, int U, long long blk, float* dst, void* stream) {
+  if (!src || !idx || !dst || (((uintptr_t)idx) & 3) || N <= 0 || U <= 0 || blk <= 0) return VQF_E_BADARG;
+  if (!vqf_row_block_supported(N, U, blk)) return VQF_E_UNSUPPORTED;
+  if (!aligned16(src) || !aligned16(dst)) return VQF_E_ALIGN;
+  const long long blk4 = blk / 4;
+  const long long gx = (blk4 + 1023) / 1024;                                   // four 16-byte groups per thread
+  VQF_LAUNCH(KID_ROW_BLOCK_GATHER, row_block_gather_kernel, dim3((unsigned)(gx > 1024 ? 1024 : gx), N), dim3(256), 0,
+             (hipStream_t)stream, reinterpret_cast<const f32x4*>(src), idx, U, blk4, reinterpret_cast<f32x4*>(dst));
+  return vqf_last_error();
+}
+
+int vqf_row_block_group_sum(const float* src, const int* order, const int* grp_off, int N, int U, long long blk, float* out,
+                            void* stream) {
+  if (!src || !order || !grp_off || !out || ((((uintptr_t)order) | ((uintptr_t)grp_off)) & 3) || N <= 0 || U <= 0 || blk <= 0)
+    return VQF_E_BADARG;
+  if (!vqf_row_block_supported(N, U, blk)) return VQF_E_UNSUPPORTED;
+  if (!aligned16(src) || !aligned16(out)) return VQF_E_ALIGN;
+  const long long blk4 = blk / 4;
+  const long long gx = (blk4 + 255) / 256;
+  VQF_LAUNCH(KID_ROW_BLOCK_GROUP_SUM, row_block_group_sum_kernel, dim3((unsigned)(gx > 1024 ? 1024 : gx), U), dim3(256), 0,
+             (hipStream_t)stream, reinterpret_cast<const f32x4*>(src), order, grp_off, N, blk4, reinterpret_cast<f32x4*>(out));
+  return vqf_last_error();
 }
 
 }  // extern "C"

@@ -63,6 +63,9 @@ enum VqfKernelId {
   KID_CE_LOSS_PRED,
   KID_ANSWER_MATCH,
   KID_TOPK_ROWS,
+  KID_GLIMPSE_DFEAT_GROUPED,
+  KID_ROW_BLOCK_GATHER,
+  KID_ROW_BLOCK_GROUP_SUM,
   KID_COUNT
 };
 

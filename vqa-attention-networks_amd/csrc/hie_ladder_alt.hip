@@ -24,14 +24,16 @@ constexpr int GL_BWD_ROWS = 64;       // rows of a sample per backward workgroup
 inline int gl_chunks(int S, int cap) { return (S + cap - 1) / cap; }
 inline int gl_rows(int S, int cap) { const int nc = gl_chunks(S, cap); return (S + nc - 1) / nc; }
 
-// grid (chunks, N), 256 threads.  LDS: [gp[n] (G E) | w (G E)].  A wave takes a row: lane q reads the 16-byte groups
+// grid (chunks, N), 256 threads.  LDS: [gp[n] (G E) | w (G E)].  idx (N, or null: u = n; the grouped form): question n reads the
+// Xh rows of sample u = idx[n], clamped to [0, U - 1] here, and writes its own logits rows.  A wave takes a row: lane q reads the 16-byte groups
 // q, q + 64, ... of the row's G E contiguous floats (four loads in flight), the group's step is found by comparison.
 template <int G>
 __global__ void __launch_bounds__(256) guided_logits_fwd_kernel(const float* __restrict__ Xh, int ldx, const float* __restrict__ gp,
                                                                 const float* __restrict__ w, int S, int E, int rows,
-                                                                float* __restrict__ logits) {
+                                                                float* __restrict__ logits, const int* __restrict__ idx, int U) {
   extern __shared__ __attribute__((aligned(16))) float gl_lds[];
   const int GE = G * E, n = blockIdx.y;
+  const int u = idx ? min(max(idx[n], 0), U - 1) : n;               // (uniform) the sample whose Xh rows this question reads
   float* gs = gl_lds;
   float* ws = gl_lds + GE;
   for (int c = threadIdx.x * 4; c < GE; c += 1024) {
@@ -46,7 +48,7 @@ __global__ void __launch_bounds__(256) guided_logits_fwd_kernel(const float* __r
   constexpr int UNR = 4;
   for (int s = s0 + wave; s < s1; s += 4) {
     const long long r = (long long)n * S + s;
-    const float* x = Xh + r * ldx;
+    const float* x = Xh + ((long long)u * S + s) * ldx;
     float a[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) a[g] = 0.f;
@@ -126,6 +128,70 @@ __global__ void __launch_bounds__(768) guided_logits_bwd_kernel(const float* __r
   *reinterpret_cast<f32x4*>(part_w + prow) = sw;
 }
 
+// The grouped backward: Xh (U*S, .) is shared by the questions of an image.  grid (chunks, U), the thread layout of the kernel
+// above.  A workgroup owns `rows` rows of image u and walks that image's questions order[grp_off[u]] .. order[grp_off[u + 1] - 1]
+// in that order, GL_GRP_Q at a time (their guidance rows and dgp sums in registers): the first pass over the rows writes
+// dXh[u] = the pass's sum, each later pass adds to what the same thread wrote -- a fixed order, no atomics.  part_g: row
+// n * chunks + chunk (each question is in one group: written once); part_w: row u * chunks + chunk.  An empty group writes zero
+// dXh rows and a zero part_w row.  grp_off and order are clamped to [0, N] / [0, N - 1] here: nothing they hold reads out of range.
+constexpr int GL_GRP_Q = 4;
+
+template <int G>
+__global__ void __launch_bounds__(768) guided_logits_bwd_grouped_kernel(const float* __restrict__ dl, const float* __restrict__ Xh,
+                                                                        int ldx, const float* __restrict__ gp,
+                                                                        const float* __restrict__ w, const int* __restrict__ order,
+                                                                        const int* __restrict__ grp_off, int N, int S, int E, int rows,
+                                                                        float* __restrict__ dXh, int ldd, float* __restrict__ part_g,
+                                                                        float* __restrict__ part_w) {
+  const int GE = G * E, u = blockIdx.y;
+  const int c = threadIdx.x * 4;
+  if (c >= GE) return;
+  const int s0 = blockIdx.x * rows, s1 = min(S, s0 + rows);
+  const int lv = (G > 1 && c >= E) + (G > 2 && c >= 2 * E);
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 wv = *reinterpret_cast<const f32x4*>(w + c);
+  const int jb = min(max(grp_off[u], 0), N), je = min(max(grp_off[u + 1], jb), N);
+  const long long r0 = (long long)u * S;
+  f32x4 sw = zero;
+  if (jb == je)
+    for (int s = s0; s < s1; ++s) *reinterpret_cast<f32x4*>(dXh + (r0 + s) * ldd + c) = zero;
+  for (int j0 = jb; j0 < je; j0 += GL_GRP_Q) {
+    const int nq = min(GL_GRP_Q, je - j0);
+    int nn[GL_GRP_Q];
+    f32x4 gv[GL_GRP_Q], sg[GL_GRP_Q];
+#pragma unroll
+    for (int q = 0; q < GL_GRP_Q; ++q) {                            // past the group's end: the last question again (not used)
+      nn[q] = min(max(order[min(j0 + q, je - 1)], 0), N - 1);
+      gv[q] = *reinterpret_cast<const f32x4*>(gp + (long long)nn[q] * GE + c);
+      sg[q] = zero;
+    }
+    for (int s = s0; s < s1; ++s) {
+      const f32x4 x = *reinterpret_cast<const f32x4*>(Xh + (r0 + s) * ldx + c);
+      f32x4 o = j0 == jb ? zero : *reinterpret_cast<const f32x4*>(dXh + (r0 + s) * ldd + c);
+      float d[GL_GRP_Q];
+#pragma unroll
+      for (int q = 0; q < GL_GRP_Q; ++q) d[q] = dl[(long long)G * ((long long)nn[q] * S + s) + lv];
+#pragma unroll
+      for (int q = 0; q < GL_GRP_Q; ++q) {
+        if (q >= nq) break;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float h = vqf_tanh_fast(x[j] + gv[q][j]);
+          const float t = (d[q] * wv[j]) * (1.0f - h * h);
+          o[j] += t;
+          sg[q][j] += t;
+          sw[j] += d[q] * h;
+        }
+      }
+      *reinterpret_cast<f32x4*>(dXh + (r0 + s) * ldd + c) = o;
+    }
+#pragma unroll
+    for (int q = 0; q < GL_GRP_Q; ++q)
+      if (q < nq) *reinterpret_cast<f32x4*>(part_g + ((long long)nn[q] * gridDim.x + blockIdx.x) * GE + c) = sg[q];
+  }
+  *reinterpret_cast<f32x4*>(part_w + ((long long)u * gridDim.x + blockIdx.x) * GE + c) = sw;
+}
+
 }  // namespace
 
 extern "C" {
@@ -145,7 +211,32 @@ int vqf_guided_logits_fwd(const float* Xh, int ldx, const float* gp, const float
   const dim3 grid(gl_chunks(S, rows), N);
   const size_t lds = (size_t)2 * G * E * sizeof(float);
 #define VQF_GL(G_) \
-  VQF_LAUNCH(KID_GUIDED_FWD, (guided_logits_fwd_kernel<G_>), grid, dim3(256), lds, s, Xh, ldx, gp, w, S, E, rows, logits)
+  VQF_LAUNCH(KID_GUIDED_FWD, (guided_logits_fwd_kernel<G_>), grid, dim3(256), lds, s, Xh, ldx, gp, w, S, E, rows, logits, \
+             (const int*)nullptr, N)
+  if (G == 3) VQF_GL(3);
+  else if (G == 2) VQF_GL(2);
+  else VQF_GL(1);
+#undef VQF_GL
+  return vqf_last_error();
+}
+
+int vqf_guided_logits_grouped_supported(int N, int U, int S, int E, int G) {
+  return vqf_guided_logits_supported(N, S, E, G) && U >= 1 && U <= 65535 && (long long)U * S < (1LL << 31) / 4;
+}
+
+int vqf_guided_logits_fwd_grouped(const float* Xh, int ldx, const float* gp, const float* w, const int* idx, int N, int U, int S,
+                                  int E, int G, float* logits, void* stream) {
+  if (!Xh || !gp || !w || !idx || !logits || N <= 0 || U <= 0 || S <= 0 || E <= 0 || G <= 0 || ldx < G * E || (ldx % 4) ||
+      (((uintptr_t)idx) & 3))
+    return VQF_E_BADARG;
+  if (!vqf_guided_logits_grouped_supported(N, U, S, E, G)) return VQF_E_UNSUPPORTED;
+  if (!aligned16(Xh) || !aligned16(gp) || !aligned16(w)) return VQF_E_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  const int rows = gl_rows(S, GL_FWD_ROWS);
+  const dim3 grid(gl_chunks(S, rows), N);
+  const size_t lds = (size_t)2 * G * E * sizeof(float);
+#define VQF_GL(G_) \
+  VQF_LAUNCH(KID_GUIDED_FWD, (guided_logits_fwd_kernel<G_>), grid, dim3(256), lds, s, Xh, ldx, gp, w, S, E, rows, logits, idx, U)
   if (G == 3) VQF_GL(3);
   else if (G == 2) VQF_GL(2);
   else VQF_GL(1);
@@ -189,6 +280,44 @@ int vqf_guided_logits_bwd(const float* dlogits, const float* Xh, int ldx, const 
     if (rc) return rc;
   }
   return vqf_colreduce_2stage(part_w, nb, GE, dw, scratch, s);
+}
+
+size_t vqf_guided_logits_bwd_grouped_ws_bytes(int N, int U, int S, int E, int G) {
+  if (N <= 0 || U <= 0 || S <= 0 || E <= 0 || G <= 0) return 0;
+  const size_t chunks = gl_chunks(S, gl_rows(S, GL_BWD_ROWS));
+  return (((size_t)N + U) * chunks + VQF_REDUCE_SPLITS) * (size_t)G * E * sizeof(float);   // dgp rows, dw rows, reduction scratch
+}
+
+int vqf_guided_logits_bwd_grouped(const float* dlogits, const float* Xh, int ldx, const float* gp, const float* w, const int* order,
+                                  const int* grp_off, int N, int U, int S, int E, int G, float* dXh, int lddx, float* dgp, float* dw,
+                                  void* ws, size_t ws_bytes, void* stream) {
+  if (!dlogits || !Xh || !gp || !w || !order || !grp_off || !dXh || !dgp || !dw || N <= 0 || U <= 0 || S <= 0 || E <= 0 || G <= 0 ||
+      ldx < G * E || lddx < G * E || (ldx % 4) || (lddx % 4) || (((uintptr_t)order) & 3) || (((uintptr_t)grp_off) & 3))
+    return VQF_E_BADARG;
+  if (!vqf_guided_logits_grouped_supported(N, U, S, E, G)) return VQF_E_UNSUPPORTED;
+  if (!aligned16(Xh) || !aligned16(gp) || !aligned16(w) || !aligned16(dXh) || !aligned16(dgp) || !aligned16(ws)) return VQF_E_ALIGN;
+  if (!ws || ws_bytes < vqf_guided_logits_bwd_grouped_ws_bytes(N, U, S, E, G)) return VQF_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const int GE = G * E;
+  const int rows = gl_rows(S, GL_BWD_ROWS), chunks = gl_chunks(S, rows);
+  float* part_w = (float*)ws;                                                 // (U * chunks, GE)
+  float* part_g = chunks == 1 ? dgp : part_w + (size_t)U * chunks * GE;       // (N * chunks, GE)
+  float* scratch = part_w + ((size_t)U + N) * chunks * GE;
+  const dim3 grid(chunks, U), block(((GE / 4 + 63) / 64) * 64);
+#define VQF_GL(G_)                                                                                                               \
+  VQF_LAUNCH(KID_GUIDED_BWD, (guided_logits_bwd_grouped_kernel<G_>), grid, block, 0, s, dlogits, Xh, ldx, gp, w, order, grp_off, \
+             N, S, E, rows, dXh, lddx, part_g, part_w)
+  if (G == 3) VQF_GL(3);
+  else if (G == 2) VQF_GL(2);
+  else VQF_GL(1);
+#undef VQF_GL
+  int rc = vqf_last_error();
+  if (rc) return rc;
+  if (chunks > 1) {
+    rc = vqf_group_reduce_f32(part_g, N, chunks, GE, dgp, stream);           // dgp[n] = its chunks' rows, in chunk order
+    if (rc) return rc;
+  }
+  return vqf_colreduce_2stage(part_w, U * chunks, GE, dw, scratch, s);
 }
 
 }  // extern "C"

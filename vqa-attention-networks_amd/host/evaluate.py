@@ -125,7 +125,9 @@ def topk_answers(logits, k=5):
 def predict(model, img, q, q_length=None, k=5, **fwd_kwargs):
     """'What are the k most likely answers, and how sure is the model?' -> (ids (N, k) int64, probs (N, k) fp32).
     Runs `model` in eval() mode (dropout off) under torch.no_grad() and puts its `training` flag back; q_length is passed
-    only when given; HieCoAtten / HieCoAttenLadder return (logits, attention maps...): the first element is used."""
+    only when given; HieCoAtten / HieCoAttenLadder return (logits, attention maps...): the first element is used.
+    Further keyword arguments go to the model's forward: predict(model, img (U, L, D), q (N, T), q_length, img_index=idx) asks
+    HieCoAttenLadder N questions about U shared images (idx (N,): the image of each question)."""
     was_training = model.training
     model.eval()
     try:

@@ -50,6 +50,21 @@ dQs, dC, dHq, the phrase taps' dZ) is an exact zero.  The lengths ride in the pa
 *_len entry points of include/vqa_fusion.h): no extra launch, no torch op on an (N*T, E) or (N, T, L) tensor.  q_length=None
 is the unmasked model: a padding id is then an ordinary word of the vocabulary at every level (as in HieCoAtten).
 
+Shared images.  forward(img (U, L, D), ids (N, T), q_length, img_index (N,)) -- VQA asks several questions about each image --
+is the model above on img[img_index] with everything question-independent computed once per IMAGE: V = drop(tanh(img_emb(img)))
+is (U*L, E) (one dropout mask per image: the questions of an image see the same dropped V), and its gradient is the sum over
+the image's questions.  The index is never read on the host: _group_index clamps it to [0, U - 1] and derives, on the device,
+order (the questions sorted by image, a stable sort) and grp_off (U + 1 group bounds); the kernels clamp again what they read.
+  * alternating mode: the image side STAYS at U -- VX = V [img_x]^T + b is (U*L, 3E), the step-2 passes are the grouped entry
+    points (vqf_guided_logits_fwd_grouped / _bwd_grouped, vqf_glimpse_pool_fwd_grouped / _bwd_grouped): a question reads its
+    image's rows in the forward, and in the backward a workgroup owns a tile of one image's rows and walks that image's questions
+    in `order` (fixed summation order, no atomics, the same bits on every run; an image without a question gets exact zeros).
+    No (N*L, .) tensor exists on the image side; the products run on U*L rows.
+  * parallel mode: V is computed at U and expanded to (N*L, E) by one row-block gather (vqf_row_block_gather; backward
+    vqf_row_block_group_sum, the same fixed-order sum); LadderCoattFn is unchanged.  Sharing Vh and teaching the affinity /
+    rank-T streaming kernels the index is out of scope: only img_emb and the tanh / dropout pass are saved there.
+img_index=None is the (N, L, D) model, bit for bit: the same code path, no extra launch.
+
 Stages (every product and every pass over an (N*L, .) or (N*T, .) tensor runs in libvqa_fusion.so):
   * img_emb / word embedding: LinearFn + TanhDropFn, EmbedTanhFn + DropoutFn;
   * phrase level (PhraseFn): the six conv taps as one GEMM, then vqf_phrase_ngram_fwd / _bwd (csrc/hie_ladder.hip);
@@ -103,6 +118,37 @@ class PhraseFn(torch.autograd.Function):
         dw2 = torch.stack([dW[E:2 * E], dW[2 * E:3 * E]], 2)
         dw3 = torch.stack([dW[3 * E:4 * E], dW[4 * E:5 * E], dW[5 * E:6 * E]], 2)
         return dqw, dw1, db[:E], dw2, db[E:2 * E], dw3, db[3 * E:4 * E], None, None, None
+
+
+def _group_index(img_index, U):
+    """img_index (N,) int64 / int32 on any device, U images -> (idx32 (N,), order (N,), grp_off (U + 1,)), int32 on that device:
+    idx32 = the index clamped to [0, U - 1]; order = the questions sorted by image (stable: ascending n inside an image);
+    image u's questions are order[grp_off[u]:grp_off[u + 1]].  O(N) torch ops, nothing read back to the host (the counts are
+    a scatter_add_: torch.bincount would read the maximum back)."""
+    idx = img_index.to(torch.int64).clamp(0, U - 1)
+    order = torch.sort(idx, stable=True).indices
+    counts = torch.zeros(U, dtype=torch.int64, device=idx.device).scatter_add_(0, idx, torch.ones_like(idx))
+    grp_off = torch.zeros(U + 1, dtype=torch.int64, device=idx.device)
+    grp_off[1:] = torch.cumsum(counts, 0)
+    return idx.to(torch.int32).contiguous(), order.to(torch.int32).contiguous(), grp_off.to(torch.int32).contiguous()
+
+
+class RowBlockGatherFn(torch.autograd.Function):
+    """(U*L, E) -> (N*L, E): question n's rows are image idx[n]'s (vqf_row_block_gather); backward: the sum over each image's
+    questions in `order` (vqf_row_block_group_sum; zeros for an image without a question)."""
+
+    @staticmethod
+    def forward(ctx, V, idx, order, grp_off, L):
+        U, E = V.shape[0] // L, V.shape[1]
+        ctx.save_for_backward(order, grp_off)
+        ctx.dims = (U, L, E)
+        return ops.row_block_gather(V.view(U, L * E), idx).view(idx.shape[0] * L, E)
+
+    @staticmethod
+    def backward(ctx, dV):
+        order, grp_off = ctx.saved_tensors
+        U, L, E = ctx.dims
+        return ops.row_block_group_sum(_c(dV).view(order.shape[0], L * E), order, grp_off).view(U * L, E), None, None, None, None
 
 
 class LadderCoattFn(torch.autograd.Function):
@@ -250,15 +296,18 @@ class LadderAltCoattFn(torch.autograd.Function):
     Backward: step 3 -> step 2 -> step 1 through the guidance-row gradients dgp; the guided-logits backward writes dXh straight
     into the (N*T, 6E) / (N*L, 3E) operands of the weight- and input-gradient products; the bias gradients are column sums of
     the (N, .) dgp.  lens ((N,) int32 or None; q0 / q1 / q2 come with zero rows at t >= lens[n]): the question-side poolings
-    take the softmax over the real words and give zero dlogits for the padded ones."""
+    take the softmax over the real words and give zero dlogits for the padded ones.
+    grp (None, or (idx, order, grp_off) of _group_index): V is (U*L, E), shared -- VX stays (U*L, 3E), step 2 runs on the grouped
+    entry points (question n reads image idx[n]'s rows; dV and dVX sum each image's questions in `order`)."""
 
     PER_LEVEL = 11
 
     @staticmethod
-    def forward(ctx, V, q0, q1, q2, N, L, T, lens, *w):
+    def forward(ctx, V, q0, q1, q2, N, L, T, lens, grp, *w):
         E = V.shape[1]
         lk = {} if lens is None else {"lens": lens}
-        M, MT = N * L, N * T
+        U = V.shape[0] // L
+        MT = N * T
         dev = V.device
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         Q = (q0, q1, q2)
@@ -269,7 +318,7 @@ class LadderAltCoattFn(torch.autograd.Function):
         whimg = torch.cat(img_h, 0).contiguous()                                    # (3, E)
         wq2 = [torch.cat([sum_x[g], que_x[g]], 0).contiguous() for g in range(3)]   # (2E, E) each
         bq2 = [torch.cat([sum_b[g], que_b[g]], 0).contiguous() for g in range(3)]
-        VX = ops.gemm_rows(V, wimg, L, bias=bimg)                                   # (M, 3E) = [img_0 | img_1 | img_2]
+        VX = ops.gemm_rows(V, wimg, L, bias=bimg)                                   # (U*L, 3E) = [img_0 | img_1 | img_2]
         QX = new(MT, 6 * E)                                                         # [sum_0 | que_0 | sum_1 | que_1 | sum_2 | que_2]
         for g in range(3):
             ops.gemm(Q[g], wq2[g], bias=bq2[g], out=QX[:, 2 * g * E:(2 * g + 2) * E])
@@ -284,7 +333,11 @@ class LadderAltCoattFn(torch.autograd.Function):
         gpv = new(N, 3 * E)
         for g in range(3):
             ops.gemm(s[g], img_g[g], out=gpv[:, g * E:(g + 1) * E])
-        av, vcat = ops.glimpse_pool_fwd(V.view(N, L, E), ops.guided_logits_fwd(VX, gpv, whimg, N, L), False)   # (N, 3, L), (N, 3E)
+        if grp is None:
+            av, vcat = ops.glimpse_pool_fwd(V.view(N, L, E), ops.guided_logits_fwd(VX, gpv, whimg, N, L), False)   # (N, 3, L), (N, 3E)
+        else:
+            av, vcat = ops.glimpse_pool_fwd_grouped(V.view(U, L, E), ops.guided_logits_fwd_grouped(VX, gpv, whimg, grp[0], N, U, L),
+                                                    grp[0])
         # step 3: the question under the attended image
         gpq = new(3, N, E)
         aq, qo = [], []
@@ -295,7 +348,7 @@ class LadderAltCoattFn(torch.autograd.Function):
             aq.append(a_g)
             qo.append(q_g)
         ctx.save_for_backward(V, q0, q1, q2, wimg, whimg, VX, QX, gpv, gpq, vcat, av, *wq2, *sum_h, *img_g, *que_g, *que_h, *s, *asum,
-                              *aq)
+                              *aq, *(grp or ()))
         ctx.dims, ctx.lens = (N, L, T, E), lens
         ctx.set_materialize_grads(False)
         return (vcat, qo[0], qo[1], qo[2], av, aq[0], aq[1], aq[2])
@@ -305,8 +358,10 @@ class LadderAltCoattFn(torch.autograd.Function):
         t = ctx.saved_tensors
         V, q0, q1, q2, wimg, whimg, VX, QX, gpv, gpq, vcat, av = t[:12]
         wq2, sum_h, img_g, que_g, que_h, s, asum, aq = (t[12 + 3 * i:15 + 3 * i] for i in range(8))
+        grp = t[36:39]                                                              # (idx, order, grp_off), or empty
         N, L, T, E = ctx.dims
-        M, MT = N * L, N * T
+        U = V.shape[0] // L
+        MT = N * T
         dev = V.device
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
@@ -328,9 +383,14 @@ class LadderAltCoattFn(torch.autograd.Function):
             g3.append((ops.colsum(dgp), ops.gemm(dgp, vcat[:, blk], ta=True, tb=True), dwh))   # que_x.bias, que_g, que_h
             dQ.append(dQg.view(MT, E))
         # step 2: one G = 3 pooling backward over V, one G = 3 guided-logits backward over VX
-        dlv, dV = ops.glimpse_pool_bwd(dvc, V.view(N, L, E), av, False, True, dwts=None if dav is None else _c(dav))
-        dV = dV.view(M, E)
-        dVX, dgpv, dwhimg = ops.guided_logits_bwd(dlv, VX, gpv, whimg, N, L)
+        dwts = None if dav is None else _c(dav)
+        if not grp:
+            dlv, dV = ops.glimpse_pool_bwd(dvc, V.view(N, L, E), av, False, True, dwts=dwts)
+            dVX, dgpv, dwhimg = ops.guided_logits_bwd(dlv, VX, gpv, whimg, N, L)
+        else:                       # dV (U, L, E) and dVX (U*L, 3E): each image's questions summed in `order`
+            dlv, dV = ops.glimpse_pool_bwd_grouped(dvc, V.view(U, L, E), av, grp[0], grp[1], grp[2], True, dwts=dwts)
+            dVX, dgpv, dwhimg = ops.guided_logits_bwd_grouped(dlv, VX, gpv, whimg, grp[1], grp[2], N, U, L)
+        dV = dV.view(U * L, E)
         dbimg = ops.colsum(dgpv)
         ops.gemm(dVX, wimg, tb=True, out=dV, accumulate=True)                      # dV += dVX [img_x_0; img_x_1; img_x_2]
         dwimg = ops.gemm(dVX, V, ta=True, tb=True)                                 # (3E, E)
@@ -350,7 +410,7 @@ class LadderAltCoattFn(torch.autograd.Function):
             grads += [dwq2[:E], ops.colsum(dgp), dwsum_h, dwimg[blk], dbimg[blk], dimg_g, dwhimg[g:g + 1], dwq2[E:], g3[g][0],
                       g3[g][1], g3[g][2]]
         ops.multi_add([(dQ[g], dQ1[g], dQ[g]) for g in range(3)])                   # dQ_i: step 3's + the pair's + step 1's
-        return (dV, dQ[0], dQ[1], dQ[2], None, None, None, None, *grads)
+        return (dV, dQ[0], dQ[1], dQ[2], None, None, None, None, None, *grads)
 
 
 class _Coatt(nn.Module):
@@ -386,8 +446,15 @@ COATT_MODES = ("parallel", "alternating")
 
 
 class HieCoAttenLadder(nn.Module):
-    """forward(img_features (N, L, img_size) fp32 GPU, que_features (N, T) int64 GPU, q_length=None)
+    """forward(img_features (N, L, img_size) fp32 GPU, que_features (N, T) int64 GPU, q_length=None, img_index=None)
     -> (logits (N, output_size), av (N, 3, L), aq (N, 3, T)); levels ordered word, phrase, sentence.
+
+    img_index: (N,) int64 or int32 on the questions' device; img_features is then (U, L, img_size) for any U >= 1 and question n
+    looks at image img_index[n] (any order, repeated indices, images without a question, N < U and N > U).  Values are clamped
+    to [0, U - 1] on the device; the index is never read on the host.  The question-independent image work runs once per image
+    (module docstring, "Shared images"); in train mode the 'img' dropout mask is drawn once per image, over (U*L, E): the
+    questions of one image see the same dropped V.  In parallel mode only img_emb and its tanh / dropout pass are shared
+    (sharing Vh and the affinity / rank-T passes is out of scope).  None: today's (N, L, img_size) model, bit for bit.
 
     q_length: (N,) int64 or int32 on the same GPU, the real words of each right-padded question (the loader's q_l; the
     reference's training loop calls model.forward(i, q, q_l)).  Padding is then masked at every level: the result of a sample
@@ -426,7 +493,7 @@ class HieCoAttenLadder(nn.Module):
         self._seeds = _DropSeeds()
 
     def set_keep_masks(self, **masks):
-        """Test hook: uint8 keep-masks 'img' (N*L, E), 'word' (N*T, E), 'ans_w' (N, E), 'ans_p' (N, 2E), 'ans_s' (N, 2E),
+        """Test hook: uint8 keep-masks 'img' (N*L, E) ((U*L, E) with img_index: one mask per image), 'word' (N*T, E), 'ans_w' (N, E), 'ans_p' (N, 2E), 'ans_s' (N, 2E),
         'ans_h' (N, hidden_size); used in train mode in place of the in-kernel draws."""
         self._seeds.keep = masks
 
@@ -437,7 +504,7 @@ class HieCoAttenLadder(nn.Module):
             return x
         return DropoutFn.apply(_c(x), keep, seed, self.drop_p if keep is not None else p)
 
-    def forward(self, img_features, que_features, q_length=None):
+    def forward(self, img_features, que_features, q_length=None, img_index=None):
         if not img_features.is_cuda or not que_features.is_cuda:
             raise VqfError("HieCoAttenLadder needs GPU tensors (the HIP extension is the only path; no CPU fallback)")
         if img_features.dtype != torch.float32:
@@ -446,7 +513,8 @@ class HieCoAttenLadder(nn.Module):
             raise VqfError("HieCoAttenLadder: img_features are data (no gradient into the image features)")
         if que_features.dtype != torch.int64:
             raise VqfError("HieCoAttenLadder takes int64 word ids")
-        N, L, D = img_features.shape
+        U, L, D = img_features.shape
+        N = U if img_index is None else que_features.shape[0]
         T = que_features.shape[1]
         E = self.img_emb.out_features
         if E % 32 or not ops.phrase_ngram_supported(T, E) or L > 1024 or T > 1024:
@@ -456,7 +524,22 @@ class HieCoAttenLadder(nn.Module):
         if alt and not (ops.guided_logits_supported(N, L, E, 3) and ops.guided_logits_supported(N, T, E, 1)):
             raise VqfError("HieCoAttenLadder(coatt='alternating'): embed_size %% 32 == 0, embed_size <= 1024, L <= 1024 and "
                            "N <= 65535 are supported (got E=%d, L=%d, T=%d, N=%d)" % (E, L, T, N))
-        M, MT = N * L, N * T
+        grp = None
+        if img_index is not None:
+            if not torch.is_tensor(img_index) or img_index.dtype not in (torch.int64, torch.int32):
+                raise VqfError("HieCoAttenLadder: img_index must be an int64 or int32 tensor")
+            if tuple(img_index.shape) != (N,):
+                raise VqfError("HieCoAttenLadder: img_index must have shape (N,) = (%d,), got %s" % (N, tuple(img_index.shape)))
+            if img_index.device != que_features.device:
+                raise VqfError("HieCoAttenLadder: img_index must be on the questions' device (%s), got %s"
+                               % (que_features.device, img_index.device))
+            ok = (ops.guided_logits_grouped_supported(N, U, L, E, 3) and ops.glimpse_pool_grouped_supported(N, U, L, E, 3)) if alt \
+                else ops.row_block_supported(N, U, L * E)
+            if not ok:
+                raise VqfError("HieCoAttenLadder(img_index): 1 <= U <= 65535 images and N <= 65535 questions are supported "
+                               "(got U=%d, N=%d, L=%d, E=%d)" % (U, N, L, E))
+            grp = _group_index(img_index, U)                                    # O(N), on the device: nothing is read back
+        M, MT = U * L, N * T
         lens = None
         if q_length is not None:
             if not torch.is_tensor(q_length) or q_length.dtype not in (torch.int64, torch.int32):
@@ -471,7 +554,9 @@ class HieCoAttenLadder(nn.Module):
         seed, p = self._seeds.next(self.training, self.drop_p)
         keep = self._seeds.keep.get("img") if self.training else None
         V = LinearFn.apply(_c(img_features).view(M, D), self.img_emb.weight, self.img_emb.bias, False)
-        V = TanhDropFn.apply(V, None, keep, seed, self.drop_p if keep is not None else p)
+        V = TanhDropFn.apply(V, None, keep, seed, self.drop_p if keep is not None else p)           # (U*L, E): once per image
+        if grp is not None and not alt:
+            V = RowBlockGatherFn.apply(V, grp[0], grp[1], grp[2], L)                                  # (N*L, E)
         # Qw = drop(tanh(word_emb(ids)))
         qw = EmbedTanhFn.apply(que_features, self.word_emb.weight, True, False, lens).view(MT, E)
         qw = self._drop(qw, "word")
@@ -488,7 +573,7 @@ class HieCoAttenLadder(nn.Module):
             w = [p_ for c in self.coatt for p_ in (c.sum_x.weight, c.sum_x.bias, c.sum_h.weight, c.img_x.weight, c.img_x.bias,
                                                    c.img_g.weight, c.img_h.weight, c.que_x.weight, c.que_x.bias, c.que_g.weight,
                                                    c.que_h.weight)]
-            vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderAltCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, *w)
+            vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderAltCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, grp, *w)
         else:
             w = [p_ for c in self.coatt for p_ in (c.Wb.weight, c.Wv.weight, c.Wq.weight, c.whv.weight, c.whq.weight)]
             vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, *w)

@@ -110,6 +110,18 @@ SIGNATURES = {
     "vqf_guided_logits_fwd": (c_i, [c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_p]),
     "vqf_guided_logits_bwd_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "vqf_guided_logits_bwd": (c_i, [c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_f, c_p, c_sz, c_p]),
+    # the grouped forms: N questions over U shared images (idx / order / grp_off: device int32 pointers, c_p)
+    "vqf_guided_logits_grouped_supported": (c_i, [c_i, c_i, c_i, c_i, c_i]),
+    "vqf_guided_logits_fwd_grouped": (c_i, [c_f, c_i, c_f, c_f, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
+    "vqf_guided_logits_bwd_grouped_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+    "vqf_guided_logits_bwd_grouped": (c_i, [c_f, c_f, c_i, c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_f, c_p, c_sz,
+                                            c_p]),
+    "vqf_glimpse_pool_grouped_supported": (c_i, [c_i, c_i, c_i, c_i, c_i]),
+    "vqf_glimpse_pool_fwd_grouped": (c_i, [c_f, c_f, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
+    "vqf_glimpse_pool_bwd_grouped": (c_i, [c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
+    "vqf_row_block_supported": (c_i, [c_i, c_i, ctypes.c_longlong]),
+    "vqf_row_block_gather": (c_i, [c_f, c_p, c_i, c_i, ctypes.c_longlong, c_f, c_p]),
+    "vqf_row_block_group_sum": (c_i, [c_f, c_p, c_p, c_i, c_i, ctypes.c_longlong, c_f, c_p]),
     "vqf_softmax_rows_fwd": (c_i, [c_f, c_i, c_i, c_f, c_p]),
     "vqf_softmax_rows_bwd": (c_i, [c_f, c_f, c_i, c_i, c_f, c_p]),
     "vqf_log_softmax_rows_fwd": (c_i, [c_f, c_i, c_i, c_f, c_p]),

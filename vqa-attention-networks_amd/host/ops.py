@@ -838,6 +838,144 @@ def guided_logits_bwd(dlogits, xh, gp, w, N, S, out=None):
     return out, dgp, dw
 
 
+# the grouped forms: N questions over U shared images (include/vqa_fusion.h "The grouped forms"; host/hie_ladder.py::_group_index
+# makes idx / order / grp_off).  The kernels clamp what the index arrays hold; only their type, shape and device are checked here.
+def _chk_group(name, N, U, idx=None, order=None, grp_off=None):
+    for t, shape, what in ((idx, (N,), "idx"), (order, (N,), "order"), (grp_off, (U + 1,), "grp_off")):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise _l.VqfError("%s: %s must be a contiguous %s int32 GPU tensor" % (name, what, shape))
+
+
+def guided_logits_grouped_supported(N, U, S, E, G):
+    return bool(_lib().vqf_guided_logits_grouped_supported(int(N), int(U), int(S), int(E), int(G)))
+
+
+def _guided_grouped_operands(name, xh, gp, w, N, U, S):
+    _chk2s(xh)
+    _chk(gp, w)
+    G, E = w.shape
+    if gp is None or xh.shape[0] != U * S or xh.shape[1] != G * E or tuple(gp.shape) != (N, G * E):
+        raise _l.VqfError(name + ": xh must be (U*S, G*E), gp (N, G*E), w (G, E)")
+    if not guided_logits_grouped_supported(N, U, S, E, G):
+        raise _l.VqfError(name + ": E %% 32 == 0, E <= 1024, 1 <= S <= 1024, G in {1, 2, 3}, N <= 65535 and U <= 65535 are "
+                          "supported (got N=%d, U=%d, S=%d, E=%d, G=%d)" % (N, U, S, E, G))
+    return G, E
+
+
+def guided_logits_fwd_grouped(xh, gp, w, idx, N, U, S):
+    """xh (U*S, G*E) (rows may be strided), gp (N, G*E), w (G, E), idx (N) int32 -> logits (N*S, G): question n reads the xh
+    rows of image idx[n] (clamped to [0, U - 1] in the kernel) and its own guidance row."""
+    G, E = _guided_grouped_operands("guided_logits_fwd_grouped", xh, gp, w, N, U, S)
+    _chk_group("guided_logits_fwd_grouped", N, U, idx=idx)
+    out = torch.empty((N * S, G), dtype=torch.float32, device=xh.device)
+    _l.check(_lib().vqf_guided_logits_fwd_grouped(_ptr(xh), xh.stride(0), _ptr(gp), _ptr(w), _ptr(idx), int(N), int(U), int(S), E, G,
+                                                  _ptr(out), _stream()), "vqf_guided_logits_fwd_grouped")
+    return out
+
+
+def guided_logits_bwd_grouped(dlogits, xh, gp, w, order, grp_off, N, U, S, out=None):
+    """-> (dxh (U*S, G*E) = the sum over each image's questions (out: written there, rows may be strided; an image without a
+    question gets zero rows), dgp (N, G*E), dw (G, E)); the questions of a group are added in `order`: fixed summation order."""
+    G, E = _guided_grouped_operands("guided_logits_bwd_grouped", xh, gp, w, N, U, S)
+    _chk_group("guided_logits_bwd_grouped", N, U, order=order, grp_off=grp_off)
+    _chk(dlogits)
+    _chk2s(out)
+    if tuple(dlogits.shape) != (N * S, G) or (out is not None and tuple(out.shape) != (U * S, G * E)):
+        raise _l.VqfError("guided_logits_bwd_grouped: dlogits must be (N*S, G) and out (U*S, G*E)")
+    if out is None:
+        out = torch.empty((U * S, G * E), dtype=torch.float32, device=xh.device)
+    dgp = torch.empty((N, G * E), dtype=torch.float32, device=xh.device)
+    dw = torch.empty((G, E), dtype=torch.float32, device=xh.device)
+    ws = workspace(xh.device, _lib().vqf_guided_logits_bwd_grouped_ws_bytes(int(N), int(U), int(S), E, G))
+    _l.check(_lib().vqf_guided_logits_bwd_grouped(_ptr(dlogits), _ptr(xh), xh.stride(0), _ptr(gp), _ptr(w), _ptr(order), _ptr(grp_off),
+                                                  int(N), int(U), int(S), E, G, _ptr(out), out.stride(0), _ptr(dgp), _ptr(dw),
+                                                  _ptr(ws), ws.numel(), _stream()), "vqf_guided_logits_bwd_grouped")
+    return out, dgp, dw
+
+
+def glimpse_pool_grouped_supported(N, U, S, C, G):
+    return bool(_lib().vqf_glimpse_pool_grouped_supported(int(N), int(U), int(S), int(C), int(G)))
+
+
+def _pool_grouped_dims(name, feat, G, N):
+    _chk(feat)
+    U, S, C = feat.shape
+    if not glimpse_pool_grouped_supported(N, U, S, C, G):
+        raise _l.VqfError(name + ": N <= 65535, U <= 65535, S <= 1024, C %% 4 == 0 and G in {1, 2, 3} are supported "
+                          "(got N=%d, U=%d, S=%d, C=%d, G=%d)" % (N, U, S, C, G))
+    return U, S, C
+
+
+def glimpse_pool_fwd_grouped(feat, logits, idx):
+    """feat (U, S, C), logits (N*S, G), idx (N) int32 -> wts (N, G, S), pooled (N, G*C): question n pools the rows of image idx[n]."""
+    _chk(logits)
+    N, G = idx.shape[0], logits.shape[1]
+    U, S, C = _pool_grouped_dims("glimpse_pool_fwd_grouped", feat, G, N)
+    _chk_group("glimpse_pool_fwd_grouped", N, U, idx=idx)
+    if logits.shape[0] != N * S:
+        raise _l.VqfError("glimpse_pool_fwd_grouped: logits must be (N*S, G)")
+    wts = torch.empty((N, G, S), dtype=torch.float32, device=feat.device)
+    pooled = torch.empty((N, G * C), dtype=torch.float32, device=feat.device)
+    _l.check(_lib().vqf_glimpse_pool_fwd_grouped(_ptr(feat), _ptr(logits), _ptr(idx), N, U, S, C, G, _ptr(wts), _ptr(pooled),
+                                                 _stream()), "vqf_glimpse_pool_fwd_grouped")
+    return wts, pooled
+
+
+def glimpse_pool_bwd_grouped(dpooled, feat, wts, idx, order, grp_off, want_dfeat, dwts=None):
+    """dpooled (N, G*C), feat (U, S, C), wts (N, G, S) -> (dlogits (N*S, G), dfeat (U, S, C) or None): dfeat[u] sums the questions
+    of image u in `order` (fixed summation order; zero rows for an image without a question)."""
+    _chk(dpooled, wts, dwts)
+    N, G, S_ = wts.shape
+    U, S, C = _pool_grouped_dims("glimpse_pool_bwd_grouped", feat, G, N)
+    _chk_group("glimpse_pool_bwd_grouped", N, U, idx=idx, order=order, grp_off=grp_off)
+    if S_ != S or tuple(dpooled.shape) != (N, G * C) or (dwts is not None and tuple(dwts.shape) != (N, G, S)):
+        raise _l.VqfError("glimpse_pool_bwd_grouped: dpooled must be (N, G*C), wts and dwts (N, G, S)")
+    dlogits = torch.empty((N * S, G), dtype=torch.float32, device=feat.device)
+    dfeat = torch.empty_like(feat) if want_dfeat else None
+    _l.check(_lib().vqf_glimpse_pool_bwd_grouped(_ptr(dpooled), _ptr(dwts), _ptr(feat), _ptr(wts), _ptr(idx), _ptr(order),
+                                                 _ptr(grp_off), N, U, S, C, G, _ptr(dlogits), _ptr(dfeat), _stream()),
+             "vqf_glimpse_pool_bwd_grouped")
+    return dlogits, dfeat
+
+
+def row_block_supported(N, U, blk):
+    return bool(_lib().vqf_row_block_supported(int(N), int(U), int(blk)))
+
+
+def row_block_gather(src, idx):
+    """src (U, ...) contiguous, idx (N) int32 -> (N, ...) = src[idx] (idx clamped to [0, U - 1] in the kernel)."""
+    _chk(src)
+    if not torch.is_tensor(idx) or idx.dim() != 1:
+        raise _l.VqfError("row_block_gather: idx must be a contiguous (N,) int32 GPU tensor")
+    U, N = src.shape[0], idx.shape[0]
+    blk = src[0].numel()
+    _chk_group("row_block_gather", N, U, idx=idx)
+    if not row_block_supported(N, U, blk):
+        raise _l.VqfError("row_block_gather: N <= 65535, U <= 65535 and a block of a multiple of 4 floats are supported "
+                          "(got N=%d, U=%d, block=%d)" % (N, U, blk))
+    out = torch.empty((N,) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
+    _l.check(_lib().vqf_row_block_gather(_ptr(src), _ptr(idx), N, U, blk, _ptr(out), _stream()), "vqf_row_block_gather")
+    return out
+
+
+def row_block_group_sum(src, order, grp_off):
+    """src (N, ...) contiguous -> (U, ...): out[u] = the sum of the blocks order[grp_off[u]] .. order[grp_off[u + 1] - 1], added in
+    that order (the backward of row_block_gather; an empty group gives zeros)."""
+    _chk(src)
+    N, U = src.shape[0], grp_off.shape[0] - 1
+    blk = src[0].numel()
+    _chk_group("row_block_group_sum", N, U, order=order, grp_off=grp_off)
+    if not row_block_supported(N, U, blk):
+        raise _l.VqfError("row_block_group_sum: N <= 65535, U <= 65535 and a block of a multiple of 4 floats are supported "
+                          "(got N=%d, U=%d, block=%d)" % (N, U, blk))
+    out = torch.empty((U,) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
+    _l.check(_lib().vqf_row_block_group_sum(_ptr(src), _ptr(order), _ptr(grp_off), N, U, blk, _ptr(out), _stream()),
+             "vqf_row_block_group_sum")
+    return out
+
+
 def softmax_rows_fwd(x):
     _chk(x)
     R, W = x.shape
