@@ -380,6 +380,29 @@ int vqf_mfb_fuse_bwd_pbf16(const float* dY, const float* Y, const float* inv, co
                            const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O, void* dP_bf16,
                            float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream);
 
+/* The grouped forms of the image fusion: N questions over U shared images (MFB / MHBCoAtt.forward(..., img_index); additions
+ * within ABI 7; fp32 only, no cascade / zdrop).  P (U*L, 5*O) is the projection of the U images, computed once per image;
+ * idx / order / grp_off as in "The grouped forms" below (host/grouping.py::_group_index), clamped where the kernels read them.
+ * q, keep (N*L, 5*O), the Philox element index (n*L + l)*5*O + c, R, rowssq, dY, Y, inv, coefA, coefB and dq stay per QUESTION:
+ * the result is vqf_mfb_fuse_fwd / _bwd on the gathered tensor P[idx], which is never made.
+ *   fwd_grouped   the kernel of vqf_mfb_fuse_fwd; the block of question n reads the rows of image idx[n].  With idx[n] = n and
+ *                 U = N it gives that kernel's bits.
+ *   bwd_grouped   two passes, neither of which allocates or writes a (N*L, 5*O) tensor:
+ *                 question-owned -- the kernel of vqf_mfb_fuse_bwd reading P through idx, without its dP store: dq (N, 5*O);
+ *                 image-owned    -- a workgroup owns rows of one image and walks the image's questions in `order`, one thread
+ *                                   per 20 columns, no atomics (two runs give the same bits); it regenerates each question's
+ *                                   mask and stores  dP (U*L, 5*O)[u,l,c] = sum_{n in group u} dz[n,l,c] q[n,c]  once (exact zero
+ *                                   rows for an image without a question);  dbiasP (5*O) = the column sums of dP (or NULL).
+ *                 ws: at least vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O), always.
+ * Supported (vqf_mfb_fuse_grouped_supported): 1 <= N, U <= 65535, O % 4 == 0, O <= 1024, N*L and U*L below 2^29. */
+int vqf_mfb_fuse_grouped_supported(int N, int U, int L, int O);
+int vqf_mfb_fuse_fwd_grouped(const float* P, const float* pbias, const float* q, const int* idx, const uint8_t* keep, uint64_t seed,
+                             float p_drop, int N, int U, int L, int O, float* R, float* rowssq, void* stream);
+size_t vqf_mfb_fuse_bwd_grouped_ws_bytes(int N, int U, int L, int O);
+int vqf_mfb_fuse_bwd_grouped(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
+                             const float* P, const float* pbias, const float* q, const int* idx, const int* order,
+                             const int* grp_off, const uint8_t* keep, uint64_t seed, float p_drop, int N, int U, int L, int O,
+                             float* dP, float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream);
 
 
 /* --------------------------------------------------------------------------
@@ -546,7 +569,7 @@ int vqf_guided_logits_bwd(const float* dlogits, const float* Xh, int ldx, const 
 
 /* The grouped forms: N questions over U shared images (HieCoAttenLadder.forward(..., img_index); additions within ABI 7).
  * idx (N) int32: question n looks at image idx[n]; order (N) int32: the questions sorted by image (a stable sort of idx);
- * grp_off (U + 1) int32: image u's questions are order[grp_off[u]] .. order[grp_off[u + 1] - 1] (host/hie_ladder.py::_group_index
+ * grp_off (U + 1) int32: image u's questions are order[grp_off[u]] .. order[grp_off[u + 1] - 1] (host/grouping.py::_group_index
  * derives all three on the device).  The kernels clamp idx to [0, U - 1], order to [0, N - 1] and grp_off to [0, N] (kept
  * monotone) where they read them: nothing these arrays hold makes a kernel read or write out of range.  Every sum over a group
  * runs in `order`, inside one thread, no atomics: two runs give the same bits; an empty group gives exact zeros.

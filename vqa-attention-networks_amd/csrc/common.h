@@ -66,6 +66,7 @@ enum VqfKernelId {
   KID_GLIMPSE_DFEAT_GROUPED,
   KID_ROW_BLOCK_GATHER,
   KID_ROW_BLOCK_GROUP_SUM,
+  KID_MFB_FUSE_BWD_IMAGE,
   KID_COUNT
 };
 

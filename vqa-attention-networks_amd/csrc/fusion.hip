@@ -199,14 +199,17 @@ __device__ __forceinline__ void keep_scale20(const uint8_t* __restrict__ keep, u
 // row is reduced.  Dropout keys on the flat element index, so the masks do not depend on this mapping.
 // COAL: 0 = direct (strided) P loads, 1 = LDS-transposed loads with the next row's pieces prefetched into registers,
 // 2 = LDS-transposed loads issued at the top of the row (20 registers fewer: one more block per CU; A/B, option fuse_coal = 2)
-template <typename PT, int COAL>
+// GRP (vqf_mfb_fuse_fwd_grouped: N questions over U shared images): P is (U*L, 5O) and the block of question n reads the rows of
+// image idx[n], clamped to [0, U - 1] here; q, keep / the Philox element index, R and rowssq stay per question.  Nothing else
+// differs: with idx[n] = n the values, the operations and their order are those of the plain kernel.
+template <typename PT, int COAL, bool GRP = false>
 __global__ void __launch_bounds__(256)
 mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
                     const float* __restrict__ q,
                     const float* __restrict__ cascade, const uint8_t* __restrict__ keep,
                     uint64_t seed, uint32_t thr, float inv_keep, int L, int O, int LS,
                     float* __restrict__ R, float* __restrict__ rowssq, float* __restrict__ zdrop,
-                    unsigned short* __restrict__ Rb, int ldrb) {
+                    unsigned short* __restrict__ Rb, int ldrb, const int* __restrict__ idx, int U) {
   // Rb != nullptr: a bf16 copy of R (round-to-nearest-even) with row pitch ldrb >= O, columns O .. ldrb-1 zero: the K-padded A
   // operand of the co-attention conv's bf16 GEMM (BASELINE config 3) straight from the registers that hold R -- no
   // vqf_cast_f32_bf16 pass over the 401 MB tensor.  ldrb / 4 <= 256.
@@ -219,6 +222,7 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int nt = O / TPT;                       // active threads (250 at O = 1000); O / TPT <= 256
   const bool act = tid < nt;
+  const long long prow0 = (long long)(GRP ? min(max(idx[n], 0), U - 1) : n) * L;     // first projection row of the sample
   float qq[CPT], pb[CPT], p[CPT], pn[CPT];
   Raw<PT> rn;                                   // COAL: the next row's span of this wave, lane-linear pieces
 #pragma unroll
@@ -226,26 +230,26 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
   if (act) {
     load20(q + (long long)n * W5 + CPT * tid, qq);
     if (pbias) load20(pbias + CPT * tid, pb);
-    if (!COAL && ls < L) load20(P + ((long long)n * L + ls) * W5 + CPT * tid, pn);
+    if (!COAL && ls < L) load20(P + (prow0 + ls) * W5 + CPT * tid, pn);
   }
-  if (COAL == 1 && ls < L) raw_load(P + ((long long)n * L + ls) * W5, W5, wave, lane, rn);     // every lane of the wave
+  if (COAL == 1 && ls < L) raw_load(P + (prow0 + ls) * W5, W5, wave, lane, rn);     // every lane of the wave
   int it = 0;
   for (int l = ls; l < L; l += LS, ++it) {
-    const long long row = (long long)n * L + l;
+    const long long row = (long long)n * L + l, prow = prow0 + l;
     const long long e0 = row * W5 + (long long)CPT * tid;
     float ssq = 0.f;
     if (COAL == 1) {
       raw_to_own(rn, tl + wave * WLDS, lane, p);
-      if (l + LS < L) raw_load(P + (row + LS) * W5, W5, wave, lane, rn);   // prefetch the next row of this block
+      if (l + LS < L) raw_load(P + (prow + LS) * W5, W5, wave, lane, rn);   // prefetch the next row of this block
     } else if (COAL == 2) {
-      raw_load(P + row * W5, W5, wave, lane, rn);
+      raw_load(P + prow * W5, W5, wave, lane, rn);
       raw_to_own(rn, tl + wave * WLDS, lane, p);
     }
     if (act) {
       if (!COAL) {
 #pragma unroll
         for (int i = 0; i < CPT; ++i) p[i] = pn[i];
-        if (l + LS < L) load20(P + (row + LS) * W5 + CPT * tid, pn);      // prefetch the next row of this block
+        if (l + LS < L) load20(P + (prow + LS) * W5 + CPT * tid, pn);      // prefetch the next row of this block
       }
       float sc[CPT], cc[CPT];
       keep_scale20(keep, seed, thr, inv_keep, e0, sc);
@@ -295,7 +299,9 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
 }
 
 // grid (N, LS); block 256.  Each block walks rows l = ls, ls+LS, ... of sample n.
-template <bool CASC, bool DBIAS, typename DPT, typename PT, bool COAL>
+// GRP (the question-owned pass of vqf_mfb_fuse_bwd_grouped): P is (U*L, 5O), read at the rows of image idx[n] (clamped here), and
+// dP is NOT written -- this pass leaves the dq partials only; mfb_fuse_bwd_image_kernel sums dP over each image's questions.
+template <bool CASC, bool DBIAS, typename DPT, typename PT, bool COAL, bool GRP = false>
 __global__ void __launch_bounds__(256)
 mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdrop,
                     const float* __restrict__ Y,
@@ -305,12 +311,13 @@ mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdr
                     const float* __restrict__ q, const float* __restrict__ cascade,
                     const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep,
                     int L, int O, int LS, DPT* __restrict__ dP, float* __restrict__ dq_part,
-                    float* __restrict__ dcascade, float* __restrict__ db_part) {
+                    float* __restrict__ dcascade, float* __restrict__ db_part, const int* __restrict__ idx, int U) {
   __shared__ __attribute__((aligned(16))) char tl[COAL ? 4 * WLDS : 16];
   const int n = blockIdx.x, ls = blockIdx.y;
   const int W5 = KP * O;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const float ca = coefA[n], cb = coefB[n], hi = 0.5f * inv[n];
+  const long long prow0 = (long long)(GRP ? min(max(idx[n], 0), U - 1) : n) * L;     // first projection row of the sample
   // COAL (O / 4 <= 256: one pass): every lane of a wave takes part in the coalesced P loads / dP stores, threads past
   // O / 4 only skip the arithmetic
   for (int t = threadIdx.x; COAL ? t < 256 : t < O / TPT; t += 256) {
@@ -323,20 +330,20 @@ mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdr
       if (pbias) load20(pbias + CPT * t, pb);
     }
     for (int l = ls; l < L; l += LS) {
-      const long long row = (long long)n * L + l;
+      const long long row = (long long)n * L + l, prow = prow0 + l;
       const long long e0 = row * W5 + (long long)CPT * t;
       float p[CPT], sc[CPT], cc[CPT], dp[CPT], dc[CPT], dzx[CPT];
 #pragma unroll
       for (int i = 0; i < CPT; ++i) { p[i] = 0.f; dp[i] = 0.f; }
       if (COAL) {
         Raw<PT> rw;
-        raw_load(P + row * W5, W5, wave, lane, rw);
+        raw_load(P + prow * W5, W5, wave, lane, rw);
         raw_to_own(rw, tl + wave * WLDS, lane, p);
       }
       if (act) {
         const f32x4 dy = *reinterpret_cast<const f32x4*>(dY + row * O + TPT * t);
         const f32x4 y = *reinterpret_cast<const f32x4*>(Y + row * O + TPT * t);
-        if (!COAL) load20(P + e0, p);
+        if (!COAL) load20(P + prow * W5 + CPT * t, p);
         if (pbias) {
 #pragma unroll
           for (int i = 0; i < CPT; ++i) p[i] += pb[i];
@@ -364,10 +371,10 @@ mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdr
           }
           if (DBIAS) db[i] += dp[i];
         }
-        if (!COAL) store20(dP + e0, dp);
+        if (!COAL && !GRP) store20(dP + e0, dp);
         if (CASC) store20(dcascade + e0, dc);
       }
-      if (COAL) own_store(dP + row * W5, W5, wave, lane, tl + wave * WLDS, dp);
+      if (COAL && !GRP) own_store(dP + row * W5, W5, wave, lane, tl + wave * WLDS, dp);
     }
     if (act) {
       const long long po = ((long long)n * LS + ls) * W5 + CPT * t;
@@ -375,6 +382,79 @@ mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdr
       if (DBIAS) store20(db_part + po, db);
     }
   }
+}
+
+// The image-owned pass of vqf_mfb_fuse_bwd_grouped: dP (U*L, 5O)[u, l, c] = sum over the questions n of image u of dz[n, l, c] q[n, c].
+// grid (U, LS); block 256, thread t owns the 20 columns 20 t .. 20 t + 19 (as everywhere in this file).  A block walks the row
+// pairs l0 = 2 ls, 2 (ls + LS), ... of image u; for each pair it walks the image's questions order[grp_off[u]] .. in that order
+// and, per question, reads its three scalars, its 20 q values (Q x 20 KB per image: they stay in L2; the pair halves that
+// traffic), the dY / Y pieces of the two rows, regenerates the two masks and adds into dp[2][20] -- registers, one thread, a
+// fixed order: no atomics, the same bits on every run, and an image without a question stores exact zeros.  Each row is stored
+// once through own_store (every lane of a wave takes part); the column sums of the rows a block wrote are its db partial.
+// P is not read.  order is clamped to [0, N - 1] and grp_off to [0, N] (kept monotone) where they are read.
+constexpr int IRB = 2;              // rows per walk of an image's questions
+template <bool DBIAS>
+__global__ void __launch_bounds__(256)
+mfb_fuse_bwd_image_kernel(const float* __restrict__ dY, const float* __restrict__ Y, const float* __restrict__ inv,
+                          const float* __restrict__ coefA, const float* __restrict__ coefB, const float* __restrict__ q,
+                          const int* __restrict__ order, const int* __restrict__ grp_off,
+                          const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep,
+                          int N, int L, int O, int LS, float* __restrict__ dP, float* __restrict__ db_part) {
+  __shared__ __attribute__((aligned(16))) char tl[4 * WLDS];
+  const int u = blockIdx.x, ls = blockIdx.y;
+  const int W5 = KP * O;
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  const bool act = t < O / TPT;
+  const int jb = min(max(grp_off[u], 0), N), je = min(max(grp_off[u + 1], jb), N);
+  float db[CPT];
+#pragma unroll
+  for (int i = 0; i < CPT; ++i) db[i] = 0.f;
+  for (int l0 = IRB * ls; l0 < L; l0 += IRB * LS) {
+    float dp[IRB][CPT];
+#pragma unroll
+    for (int r = 0; r < IRB; ++r)
+#pragma unroll
+      for (int i = 0; i < CPT; ++i) dp[r][i] = 0.f;
+    if (act) {
+      for (int j = jb; j < je; ++j) {
+        const int n = min(max(order[j], 0), N - 1);
+        const float ca = coefA[n], cb = coefB[n], hi = 0.5f * inv[n];
+        float qq[CPT];
+        load20(q + (long long)n * W5 + CPT * t, qq);
+#pragma unroll
+        for (int r = 0; r < IRB; ++r) {
+          if (l0 + r < L) {
+            const long long row = (long long)n * L + l0 + r;
+            const f32x4 dy = *reinterpret_cast<const f32x4*>(dY + row * O + TPT * t);
+            const f32x4 y = *reinterpret_cast<const f32x4*>(Y + row * O + TPT * t);
+            float sc[CPT], ds[TPT];
+            keep_scale20(keep, seed, thr, inv_keep, row * W5 + (long long)CPT * t, sc);
+#pragma unroll
+            for (int k = 0; k < TPT; ++k) {
+              const float ay = fabsf(y[k]);
+              ds[k] = ay > 0.f ? (ca * dy[k] - cb * y[k]) * (hi / ay) : 0.f;      // as mfb_fuse_bwd_kernel
+            }
+#pragma unroll
+            for (int i = 0; i < CPT; ++i) {
+              const float dz = ds[i / KP] * sc[i];
+              dp[r][i] += dz * qq[i];
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < IRB; ++r) {
+      if (l0 + r < L) {                                  // (uniform over the block)
+        own_store(dP + ((long long)u * L + l0 + r) * W5, W5, wave, lane, tl + wave * WLDS, dp[r]);
+        if (DBIAS) {
+#pragma unroll
+          for (int i = 0; i < CPT; ++i) db[i] += dp[r][i];
+        }
+      }
+    }
+  }
+  if (DBIAS && act) store20(db_part + ((long long)u * LS + ls) * W5 + CPT * t, db);
 }
 
 // Coalesced (LDS-transposed) P / dP access.  Measured at the headline shape (tools/fuse_bench.py, profiles/r03_fuse_ab.log,
@@ -405,6 +485,13 @@ int pick_ls(int N, int L) {
   return ls;
 }
 
+int pick_ls_image(int U, int L) {
+  // the image-owned pass: blocks for 256 CUs x 8, a block keeps at least one row pair; at most 32 db partial rows per image
+  int ls = 1;
+  while ((long long)U * ls < 2048 && ls * 2 * IRB <= L && ls < 32) ls *= 2;
+  return ls;
+}
+
 }  // namespace
 
 static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, const float* inv,
@@ -413,7 +500,9 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
                      const float* cascade,
                      const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O,
                      void* dP, int dp_bf16, float* dq, float* dcascade, float* dbiasP, void* ws,
-                     size_t ws_bytes, void* stream) {
+                     size_t ws_bytes, void* stream, const int* idx = nullptr, const int* order = nullptr,
+                     const int* grp_off = nullptr, int U = 0) {
+  // idx != nullptr: the grouped form (vqf_mfb_fuse_bwd_grouped, which has checked its own operands): P and dP are (U*L, 5O)
   if (!dY || !Y || !inv || !coefA || !coefB || !P || !q || !dP || !dq || N <= 0 || L <= 0 || O <= 0)
     return VQF_E_BADARG;
   if (O % TPT) return VQF_E_UNSUPPORTED;
@@ -429,7 +518,8 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
   const int W5 = KP * O;
   const bool direct = (LS == 1);      // dq partial == dq
   if (!direct || dbiasP) {
-    if (!ws || ws_bytes < vqf_mfb_fuse_bwd_ws_bytes(N, L, O) || !aligned16(ws)) return VQF_E_WORKSPACE;
+    const size_t need = idx ? vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O) : vqf_mfb_fuse_bwd_ws_bytes(N, L, O);
+    if (!ws || ws_bytes < need || !aligned16(ws)) return VQF_E_WORKSPACE;
   }
   float* dq_part = direct ? dq : (float*)ws;
   float* db_part = (float*)ws + (size_t)N * LS * W5;
@@ -442,8 +532,38 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
 #define VQF_BWD1(C_, D_, T_, PT_, CO_)                                                           \
   VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<C_, D_, T_, PT_, CO_>), grid, dim3(256), 0, s, dY, dzdrop, Y, inv, \
              coefA, coefB, (const PT_*)P, pbias, q, cascade, keep, seed, thr, inv_keep, L, O, LS, (T_*)dP, dq_part, \
-             dcascade, db_part)
+             dcascade, db_part, nullptr, 0)
 #define VQF_BWD(C_, D_, T_, PT_) do { if (coal) VQF_BWD1(C_, D_, T_, PT_, true); else VQF_BWD1(C_, D_, T_, PT_, false); } while (0)
+  if (idx) {
+    // question-owned pass: the plain kernel reading P through idx, no dP store, no bias partials (the dq partials only) ...
+    if (coal)
+      VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<false, false, float, float, true, true>), grid, dim3(256), 0, s, dY, nullptr,
+                 Y, inv, coefA, coefB, (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, (float*)nullptr,
+                 dq_part, nullptr, nullptr, idx, U);
+    else
+      VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<false, false, float, float, false, true>), grid, dim3(256), 0, s, dY, nullptr,
+                 Y, inv, coefA, coefB, (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, (float*)nullptr,
+                 dq_part, nullptr, nullptr, idx, U);
+    int rcg = vqf_last_error();
+    if (rcg) return rcg;
+    // ... image-owned pass: dP rows and the bias partials of the U*L rows it wrote
+    const int LSI = pick_ls_image(U, L);
+    db_part = (float*)ws + (size_t)N * LS * W5;                   // [U * LSI][5O], then the reducer's VQF_REDUCE_SPLITS rows
+    if (dbiasP)
+      VQF_LAUNCH(KID_MFB_FUSE_BWD_IMAGE, (mfb_fuse_bwd_image_kernel<true>), dim3(U, LSI), dim3(256), 0, s, dY, Y, inv, coefA, coefB, q,
+                 order, grp_off, keep, seed, thr, inv_keep, N, L, O, LSI, (float*)dP, db_part);
+    else
+      VQF_LAUNCH(KID_MFB_FUSE_BWD_IMAGE, (mfb_fuse_bwd_image_kernel<false>), dim3(U, LSI), dim3(256), 0, s, dY, Y, inv, coefA, coefB, q,
+                 order, grp_off, keep, seed, thr, inv_keep, N, L, O, LSI, (float*)dP, nullptr);
+    rcg = vqf_last_error();
+    if (rcg) return rcg;
+    if (!direct) {
+      rcg = vqf_group_reduce_f32(dq_part, N, LS, W5, dq, stream);
+      if (rcg) return rcg;
+    }
+    if (dbiasP) rcg = vqf_colreduce_2stage(db_part, U * LSI, W5, dbiasP, db_part + (size_t)U * LSI * W5, s);
+    return rcg;
+  }
   if (p_bf16)       { if (dbiasP) VQF_BWD(false, true, __bf16, __bf16); else VQF_BWD(false, false, __bf16, __bf16); }
   else if (dp_bf16) { if (dbiasP) VQF_BWD(false, true, __bf16, float); else VQF_BWD(false, false, __bf16, float); }
   else if (cascade) { if (dbiasP) VQF_BWD(true, true, float, float); else VQF_BWD(true, false, float, float); }
@@ -465,7 +585,8 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
 
 static int fuse_fwd_impl(const void* P, int p_bf16, const float* pbias, const float* q, const float* cascade,
                          const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O, float* R,
-                         float* rowssq, float* zdrop, void* stream, void* R_bf16 = nullptr, int ldrb = 0) {
+                         float* rowssq, float* zdrop, void* stream, void* R_bf16 = nullptr, int ldrb = 0,
+                         const int* idx = nullptr, int U = 0) {
   if (!P || !q || !R || !rowssq || N <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
   if (R_bf16 && (ldrb < O || (ldrb % 4) || ldrb / 4 > 256 || (((uintptr_t)R_bf16) & 7))) return VQF_E_BADARG;
   if ((O % TPT) || O / TPT > 256) return VQF_E_UNSUPPORTED;     // one thread per 4 pooled outputs: O <= 1024 (the reference's 1000)
@@ -481,9 +602,15 @@ static int fuse_fwd_impl(const void* P, int p_bf16, const float* pbias, const fl
   const bool nopf = coal && g_vqf_opt[VQF_OPT_FUSE_COAL] != 1;   // default: no register prefetch (126 VGPRs, 4 blocks per CU)
 #define VQF_FWD(PT_, CO_)                                                                                             \
   VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<PT_, CO_>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream,         \
-             (const PT_*)P, pbias, q, cascade, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, zdrop, (unsigned short*)R_bf16, ldrb)
-  if (p_bf16) { if (nopf) VQF_FWD(__bf16, 2); else if (coal) VQF_FWD(__bf16, 1); else VQF_FWD(__bf16, 0); }
+             (const PT_*)P, pbias, q, cascade, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, zdrop, (unsigned short*)R_bf16, ldrb, \
+             nullptr, 0)
+#define VQF_FWDG(CO_)                                                                                                 \
+  VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<float, CO_, true>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream, \
+             (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, nullptr, nullptr, 0, idx, U)
+  if (idx)    { if (nopf) VQF_FWDG(2); else if (coal) VQF_FWDG(1); else VQF_FWDG(0); }       // the grouped form (fp32 only)
+  else if (p_bf16) { if (nopf) VQF_FWD(__bf16, 2); else if (coal) VQF_FWD(__bf16, 1); else VQF_FWD(__bf16, 0); }
   else        { if (nopf) VQF_FWD(float, 2); else if (coal) VQF_FWD(float, 1); else VQF_FWD(float, 0); }
+#undef VQF_FWDG
 #undef VQF_FWD
   return vqf_last_error();
 }
@@ -519,6 +646,38 @@ int vqf_mfb_fuse_bwd(const float* dY, const float* dzdrop, const float* Y, const
                      float* dP, float* dq, float* dcascade, float* dbiasP, void* ws, size_t ws_bytes, void* stream) {
   return fuse_bwd_impl(dY, dzdrop, Y, inv, coefA, coefB, P, 0, pbias, q, cascade, keep, seed, p_drop, N, L, O, dP, 0, dq,
                        dcascade, dbiasP, ws, ws_bytes, stream);
+}
+
+int vqf_mfb_fuse_grouped_supported(int N, int U, int L, int O) {
+  return N >= 1 && N <= 65535 && U >= 1 && U <= 65535 && L >= 1 && O >= TPT && O % TPT == 0 && O / TPT <= 256 &&
+         (long long)N * L < (1LL << 29) && (long long)U * L < (1LL << 29);
+}
+
+static bool grouped_index_ok(const int* a) { return a && (((uintptr_t)a) & 3) == 0; }
+
+int vqf_mfb_fuse_fwd_grouped(const float* P, const float* pbias, const float* q, const int* idx, const uint8_t* keep, uint64_t seed,
+                             float p_drop, int N, int U, int L, int O, float* R, float* rowssq, void* stream) {
+  if (!grouped_index_ok(idx) || N <= 0 || U <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
+  if (!vqf_mfb_fuse_grouped_supported(N, U, L, O)) return VQF_E_UNSUPPORTED;
+  return fuse_fwd_impl(P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, R, rowssq, nullptr, stream, nullptr, 0, idx, U);
+}
+
+size_t vqf_mfb_fuse_bwd_grouped_ws_bytes(int N, int U, int L, int O) {
+  if (N <= 0 || U <= 0 || L <= 0 || O <= 0) return 0;
+  return ((size_t)N * pick_ls(N, L) + (size_t)U * pick_ls_image(U, L) + VQF_REDUCE_SPLITS) * KP * O * sizeof(float);
+}
+
+int vqf_mfb_fuse_bwd_grouped(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
+                             const float* P, const float* pbias, const float* q, const int* idx, const int* order,
+                             const int* grp_off, const uint8_t* keep, uint64_t seed, float p_drop, int N, int U, int L, int O,
+                             float* dP, float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream) {
+  if (!grouped_index_ok(idx) || !grouped_index_ok(order) || !grouped_index_ok(grp_off) || N <= 0 || U <= 0 || L <= 0 || O <= 0)
+    return VQF_E_BADARG;
+  if (!vqf_mfb_fuse_grouped_supported(N, U, L, O)) return VQF_E_UNSUPPORTED;
+  // the image-owned pass carves its bias partials from the workspace whether or not dq needs partials
+  if (!ws || ws_bytes < vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O) || !aligned16(ws)) return VQF_E_WORKSPACE;
+  return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
+                       dbiasP, ws, ws_bytes, stream, idx, order, grp_off, U);
 }
 
 int vqf_mfb_fuse_bwd_pbf16(const float* dY, const float* Y, const float* inv, const float* coefA,

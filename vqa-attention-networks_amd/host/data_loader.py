@@ -111,3 +111,21 @@ def stage_features(batch, bf16=False, device=None):
     st = FeatureStager(n, channels=D, regions=int(np.prod(b.shape[2:])), device=device, bf16=bf16, depth=1)
     st.submit(b)
     return st.next()
+
+
+def group_batch(image_ids):
+    """The host half of a shared-image batch (forward(..., img_index)): image_ids = the batch's image ids as the loader has
+    them, one per question (any hashable) -> (rows (U,), img_index (N,)), both int64 CPU tensors.  rows[u] is the position in
+    the batch of the FIRST question about the u-th distinct image, in order of appearance; question n looks at image
+    img_index[n] of [features[r] for r in rows] -- the only features the loader then has to stage (FeatureStager.submit)."""
+    ids = list(image_ids)
+    if not ids:
+        raise ValueError("group_batch: an empty batch")
+    seen, rows, index = {}, [], []
+    for n, key in enumerate(ids):
+        u = seen.get(key)
+        if u is None:
+            u = seen[key] = len(rows)
+            rows.append(n)
+        index.append(u)
+    return torch.tensor(rows, dtype=torch.int64), torch.tensor(index, dtype=torch.int64)

@@ -82,6 +82,7 @@ import torch.nn as nn
 
 from . import ops
 from .functions import _c, _hie_hv_ti, _hie_dc, _hie_bwd_bgemm, EmbedTanhFn, LinearFn, DropoutFn, TanhDropFn, DropoutBTFn, LstmBatchFn
+from .grouping import _group_index    # noqa: F401  (its home is host/grouping.py; importable from here as before)
 from .lib import VqfError
 from .mfb import _DropSeeds
 
@@ -118,19 +119,6 @@ class PhraseFn(torch.autograd.Function):
         dw2 = torch.stack([dW[E:2 * E], dW[2 * E:3 * E]], 2)
         dw3 = torch.stack([dW[3 * E:4 * E], dW[4 * E:5 * E], dW[5 * E:6 * E]], 2)
         return dqw, dw1, db[:E], dw2, db[E:2 * E], dw3, db[3 * E:4 * E], None, None, None
-
-
-def _group_index(img_index, U):
-    """img_index (N,) int64 / int32 on any device, U images -> (idx32 (N,), order (N,), grp_off (U + 1,)), int32 on that device:
-    idx32 = the index clamped to [0, U - 1]; order = the questions sorted by image (stable: ascending n inside an image);
-    image u's questions are order[grp_off[u]:grp_off[u + 1]].  O(N) torch ops, nothing read back to the host (the counts are
-    a scatter_add_: torch.bincount would read the maximum back)."""
-    idx = img_index.to(torch.int64).clamp(0, U - 1)
-    order = torch.sort(idx, stable=True).indices
-    counts = torch.zeros(U, dtype=torch.int64, device=idx.device).scatter_add_(0, idx, torch.ones_like(idx))
-    grp_off = torch.zeros(U + 1, dtype=torch.int64, device=idx.device)
-    grp_off[1:] = torch.cumsum(counts, 0)
-    return idx.to(torch.int32).contiguous(), order.to(torch.int32).contiguous(), grp_off.to(torch.int32).contiguous()
 
 
 class RowBlockGatherFn(torch.autograd.Function):

@@ -141,6 +141,12 @@ SIGNATURES = {
                                      c_i, c_i, c_i, c_p, c_f, c_f, c_p, c_sz, c_p]),
     "vqf_mfb_fuse_bwd_bf16dp": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_u64, ctypes.c_float,
                                       c_i, c_i, c_i, c_p, c_f, c_f, c_p, c_sz, c_p]),
+    # the grouped image fusion: N questions over U shared images (MFB / MHBCoAtt forward(..., img_index))
+    "vqf_mfb_fuse_grouped_supported": (c_i, [c_i, c_i, c_i, c_i]),
+    "vqf_mfb_fuse_fwd_grouped": (c_i, [c_f, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
+    "vqf_mfb_fuse_bwd_grouped_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "vqf_mfb_fuse_bwd_grouped": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_u64, ctypes.c_float,
+                                       c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_p, c_sz, c_p]),
     "vqf_lstm_seq_supported": (c_i, [c_i, c_i]),
     "vqf_lstm_seq_ws_bytes": (c_sz, [c_i, c_i]),
     "vqf_lstm_seq_fwd": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_p, c_sz, c_p]),

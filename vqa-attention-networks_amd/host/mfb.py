@@ -11,6 +11,8 @@ libvqa_fusion.so (`use_hip_lstm = False` puts the LSTM back on nn.LSTM / MIOpen)
 import torch
 import torch.nn as nn
 
+from . import ops
+from .grouping import _group_index, check_img_index
 from .functions import (LinearFn, AttHeadFn, ImgFuseFn, ImgProjFn, ImgProjLateFn, ImgProjDeferFn, MfbFuseFn, FinalMfbFn,
                         LstmBatchFn, UnitPoolFn, DeadParamsFn, NormLink, img_project, embed_tanh, lstm_out_dropout)
 
@@ -33,6 +35,24 @@ def _image_is_data(img, gemm_dtype="fp32"):
     if img.requires_grad:
         raise VqfError("img_features.requires_grad=True: the HIP fusion path treats the image tensor as "
                        "data and does not produce its gradient")
+
+
+def shared_image_groups(who, img_features, questions, img_index, gemm_dtype):
+    """forward(..., img_index): the refusals of the shared-image call and the device-side grouping.  img_features (U, L, D),
+    questions (N, ...), img_index (N,) int64 / int32 on the questions' device -> (idx, order, grp_off) (grouping._group_index:
+    the index is clamped to [0, U - 1] on the device and never read on the host)."""
+    from .lib import VqfError
+    if gemm_dtype != "fp32" or img_features.dtype != torch.float32:
+        raise VqfError("%s: img_index is fp32 only (the grouped fusion kernels have no bf16 form); got gemm_dtype=%r and %s "
+                       "img_features" % (who, gemm_dtype, img_features.dtype))
+    U, L, D = img_features.shape
+    N = questions.shape[0]
+    check_img_index(who, img_index, N, U, questions.device)
+    if not (ops.mfb_fuse_grouped_supported(N, U, L, 1000) and ops.glimpse_pool_grouped_supported(N, U, L, D, 2)
+            and ops.row_block_supported(N, U, 2 * D)):
+        raise VqfError("%s: img_index needs L <= 1024 regions and a channel count that is a multiple of 4 (got U=%d, N=%d, L=%d, "
+                       "D=%d)" % (who, U, N, L, D))
+    return _group_index(img_index, U)
 
 
 _warned = set()
@@ -217,12 +237,14 @@ class MFB(nn.Module):
         """Test hook: explicit uint8 keep-masks 'm1' (N*L,5000), 'm2' (N,5000) instead of Philox."""
         self._seeds.keep = masks
 
-    def _forward_pruned(self, img_features, ques_feature, keep):
+    def _forward_pruned(self, img_features, ques_feature, keep, grp=None):
         """The live part of the reference graph when both softmaxes are over a singleton axis."""
         pm = self.dropout_m.p
         qa = UnitPoolFn.apply(ques_feature, 2)                             # (N, 2H)   mfb.py:85-89 with weights 1
         self._seeds.next(self.training, pm)                                # the regions' dropout draw (unused, keeps the stream)
         va = UnitPoolFn.apply(img_features, 2)                             # (N, 2D)   mfb.py:119-123 with weights 1
+        if grp is not None:                                                # per image (U, 2D), one row block per question
+            va = ops.row_block_gather(va, grp[0])
         seed, p = self._seeds.next(self.training, pm)
         k2 = keep.get('m2')
         y = FinalMfbFn.apply(qa, va, self.ques_proj2.weight, self.ques_proj2.bias,
@@ -235,8 +257,12 @@ class MFB(nn.Module):
         params = [t for m in dead for t in (m.weight, m.bias) if t.requires_grad]
         return DeadParamsFn.apply(out, *params) if params and torch.is_grad_enabled() else out
 
-    def forward(self, img_features, questions, is_training=True):
+    def forward(self, img_features, questions, is_training=True, img_index=None):
+        """img_index (None, or (N,) int64 / int32 on the questions' device): img_features holds the U images the batch's N
+        questions share, and question n looks at image img_index[n] (any order, repeats, images without a question).  The
+        result is this model on img_features[img_index]; img_conv1d and its weight gradient run once per image."""
         _image_is_data(img_features, self.gemm_dtype)
+        grp = None if img_index is None else shared_image_groups("MFB", img_features, questions, img_index, self.gemm_dtype)
         bf16_img = self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
         bf16_all = self.gemm_dtype == "bf16-all"          # also ques_proj*, img_proj*, the question-attention conv
         # a5 starts first, on the side stream: it only needs the image and its weights
@@ -258,7 +284,7 @@ class MFB(nn.Module):
         L = img_features.shape[1]
         keep = self._seeds.keep
         if self.pruned and self.unit_softmax:
-            return self._forward_pruned(img_features, ques_feature, keep)
+            return self._forward_pruned(img_features, ques_feature, keep, grp)
 
         # a3: question attention                                             mfb.py:73-89
         wm, bm = self._mc('ques_att_multiconv')
@@ -275,15 +301,15 @@ class MFB(nn.Module):
         link = NormLink() if (self.fold_norm and not self.multilayer) else None
         if proj is not None:
             P0 = self._side.join(*proj)
-            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link)
+            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, grp)
         else:
             Y = ImgFuseFn.apply(img_features, self.img_conv1d.weight, self.img_conv1d.bias, qp,
-                                k1, seed, pm if k1 is not None else p, bf16_img, link)
+                                k1, seed, pm if k1 is not None else p, bf16_img, link, grp)
         # a7+a8: co-attention over the regions                               mfb.py:109-123
         # (with a link Y is the un-normalised R and 1/norm rides in co_att_conv1's GEMM epilogue)
         wm, bm = self._mc('co_att_multiconv')
         va = AttHeadFn.apply(Y, img_features, self.co_att_conv1.weight, self.co_att_conv1.bias, wm, bm,
-                             self.co_att_conv2.weight, self.co_att_conv2.bias, self.unit_softmax, coatt_bf16, link)
+                             self.co_att_conv2.weight, self.co_att_conv2.bias, self.unit_softmax, coatt_bf16, link, False, grp)
         # a9: final MFB block                                                mfb.py:126-135
         seed, p = self._seeds.next(self.training, pm)
         k2 = keep.get('m2')

@@ -10,7 +10,7 @@ import torch.nn as nn
 from . import ops
 from .functions import (LinearFn, Linear2Fn, AttHeadFn, ImgFuseFn, MfbFuseFn, FinalMfbFn, LstmSeqFn, LstmBatchFn, LogSoftmaxRowsFn,
                         NormLink, embed_tanh, embed, lstm_out_dropout)
-from .mfb import _DropSeeds, _image_is_data, _SideStream, _lstm_bf16, batch_first_lstm, warn_once
+from .mfb import _DropSeeds, _image_is_data, _SideStream, _lstm_bf16, batch_first_lstm, warn_once, shared_image_groups
 
 
 class MHBCoAtt(nn.Module):
@@ -50,9 +50,14 @@ class MHBCoAtt(nn.Module):
     def set_keep_masks(self, **masks):
         self._seeds.keep = masks
 
-    def forward(self, img_features, questions, glove_matrix=None, is_training=True):
+    def forward(self, img_features, questions, glove_matrix=None, is_training=True, img_index=None):
+        """img_index: see MFB.forward -- img_features (U, L, D) are the images the N questions share; the batch-axis LSTM
+        recursion runs over the questions in the caller's order, untouched."""
         _image_is_data(img_features, self.gemm_dtype)
+        grp = None if img_index is None else shared_image_groups("MHBCoAtt", img_features, questions, img_index, self.gemm_dtype)
         N, L, D = img_features.shape
+        if grp is not None:
+            N = questions.shape[0]
         keep = self._seeds.keep
         bf16_img = self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
         bf16_all = self.gemm_dtype == "bf16-all"          # also ques_proj*, img_proj*, the question-attention conv
@@ -99,12 +104,12 @@ class MHBCoAtt(nn.Module):
         link = NormLink() if self.fold_norm else None
         if proj is not None:
             P0 = self._side.join(*proj)
-            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link)
+            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, grp)
         else:
             Y = ImgFuseFn.apply(img_features, self.img_conv1d.weight, self.img_conv1d.bias, qp,
-                                k1, seed, pm if k1 is not None else p, bf16_img, link)
+                                k1, seed, pm if k1 is not None else p, bf16_img, link, grp)
         va = AttHeadFn.apply(Y, img_features, self.co_att_conv1.weight, self.co_att_conv1.bias, None, None,
-                             self.co_att_conv2.weight, self.co_att_conv2.bias, False, coatt_bf16, link)
+                             self.co_att_conv2.weight, self.co_att_conv2.bias, False, coatt_bf16, link, False, grp)
         ys = []
         for tag, qpj, ipj in (('m2', self.ques_proj2, self.img_proj2), ('m3', self.ques_proj3, self.img_proj3)):
             seed, p = self._seeds.next(self.training, pm)

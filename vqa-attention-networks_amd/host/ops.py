@@ -838,7 +838,7 @@ def guided_logits_bwd(dlogits, xh, gp, w, N, S, out=None):
     return out, dgp, dw
 
 
-# the grouped forms: N questions over U shared images (include/vqa_fusion.h "The grouped forms"; host/hie_ladder.py::_group_index
+# the grouped forms: N questions over U shared images (include/vqa_fusion.h "The grouped forms"; host/grouping.py::_group_index
 # makes idx / order / grp_off).  The kernels clamp what the index arrays hold; only their type, shape and device are checked here.
 def _chk_group(name, N, U, idx=None, order=None, grp_off=None):
     for t, shape, what in ((idx, (N,), "idx"), (order, (N,), "order"), (grp_off, (U + 1,), "grp_off")):
@@ -1104,6 +1104,75 @@ def mfb_fuse_bwd(dY, Y, norm, inv, P, q, N, L, O, keep=None, seed=0, p_drop=0.0,
                                      _ptr(dP), _ptr(dq), _ptr(dc), _ptr(db), _ptr(ws), ws.numel(), _stream()),
              "vqf_mfb_fuse_bwd")
     return dP, dq, dc, db
+
+
+def mfb_fuse_grouped_supported(N, U, L, O):
+    return bool(_lib().vqf_mfb_fuse_grouped_supported(int(N), int(U), int(L), int(O)))
+
+
+def _fuse_grouped_operands(name, P, q, N, U, L, O, pbias):
+    _chk(P, q, pbias)
+    if P.dim() != 2 or tuple(P.shape) != (U * L, POOL_K * O) or tuple(q.shape) != (N, POOL_K * O) or \
+            (pbias is not None and tuple(pbias.shape) != (POOL_K * O,)):
+        raise _l.VqfError("%s: P must be a contiguous (U*L, 5*O) = (%d, %d) tensor, q (N, 5*O) and pbias (5*O,); got P %s, q %s"
+                          % (name, U * L, POOL_K * O, tuple(P.shape), tuple(q.shape)))
+    if not mfb_fuse_grouped_supported(N, U, L, O):
+        raise _l.VqfError("%s: N <= 65535, U <= 65535, O %% 4 == 0 and O <= 1024 are supported (got N=%d, U=%d, L=%d, O=%d)"
+                          % (name, N, U, L, O))
+
+
+def mfb_fuse_fwd_grouped(P, q, idx, N, U, L, O, keep=None, seed=0, p_drop=0.0, pbias=None, normalise=True):
+    """The image fusion of N questions over U shared images: P (U*L, 5*O) fp32, q (N, 5*O), idx (N) int32 (question n reads the
+    rows of image idx[n], clamped in the kernel); keep (N*L, 5*O) / the Philox draw stay per question
+    -> (Y (N*L, O), norm (N), inv (N)) as mfb_fuse_fwd on P[idx] would give them, without that tensor."""
+    _fuse_grouped_operands("mfb_fuse_fwd_grouped", P, q, N, U, L, O, pbias)
+    _chk_group("mfb_fuse_fwd_grouped", N, U, idx=idx)
+    dev = P.device
+    R = torch.empty((N * L, O), dtype=torch.float32, device=dev)
+    rowssq = torch.empty(N * L * 4, dtype=torch.float32, device=dev)
+    _l.check(_lib().vqf_mfb_fuse_fwd_grouped(_ptr(P), _ptr(pbias), _ptr(q), _ptr(idx), _keep_ptr(keep), int(seed), float(p_drop),
+                                             N, U, L, O, _ptr(R), _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_grouped")
+    norm = torch.empty(N, dtype=torch.float32, device=dev)
+    inv = torch.empty(N, dtype=torch.float32, device=dev)
+    _l.check(_lib().vqf_l2_group_norm(_ptr(rowssq), N, 4 * L, _ptr(norm), _ptr(inv), _stream()), "vqf_l2_group_norm")
+    if normalise:
+        _l.check(_lib().vqf_scale_rows(_ptr(R), _ptr(inv), N * L, L, O, _ptr(R), _stream()), "vqf_scale_rows")
+    return R, norm, inv
+
+
+def mfb_fuse_bwd_grouped(dY, Y, norm, inv, P, q, idx, order, grp_off, N, U, L, O, keep=None, seed=0, p_drop=0.0,
+                         want_dbias=False, pbias=None, lin=None):
+    """-> (dP (U*L, 5*O): the sum over each image's questions, added in `order` (zero rows for an image without a question),
+    dq (N, 5*O), dbiasP or None).  lin as in mfb_fuse_bwd.  No (N*L, 5*O) tensor is allocated."""
+    _fuse_grouped_operands("mfb_fuse_bwd_grouped", P, q, N, U, L, O, pbias)
+    _chk_group("mfb_fuse_bwd_grouped", N, U, idx=idx, order=order, grp_off=grp_off)
+    _chk(dY, Y, norm, inv)
+    if tuple(dY.shape) != (N * L, O) or tuple(Y.shape) != (N * L, O):
+        raise _l.VqfError("mfb_fuse_bwd_grouped: dY and Y must be (N*L, O)")
+    dev = P.device
+    cA = torch.empty(N, dtype=torch.float32, device=dev)
+    cB = torch.empty(N, dtype=torch.float32, device=dev)
+    if lin is not None:
+        dl, ln = lin
+        _chk(dl, ln)
+        unit = torch.empty(N, dtype=torch.float32, device=dev)
+        _l.check(_lib().vqf_l2_norm_bwd_coef_lin(_ptr(dl), _ptr(ln), dl.shape[1], _ptr(norm), _ptr(inv), N, L, _ptr(cA),
+                                                 _ptr(cB), _ptr(unit), _stream()), "vqf_l2_norm_bwd_coef_lin")
+        inv = unit
+    else:
+        rowdot = torch.empty(N * L, dtype=torch.float32, device=dev)
+        _l.check(_lib().vqf_rowdot(_ptr(Y), _ptr(dY), N * L, O, _ptr(rowdot), _stream()), "vqf_rowdot")
+        _l.check(_lib().vqf_l2_norm_bwd_coef(_ptr(rowdot), _ptr(norm), _ptr(inv), N, L, _ptr(cA), _ptr(cB),
+                                             _stream()), "vqf_l2_norm_bwd_coef")
+    dP = torch.empty_like(P)
+    dq = torch.empty((N, POOL_K * O), dtype=torch.float32, device=dev)
+    db = torch.empty(POOL_K * O, dtype=torch.float32, device=dev) if want_dbias else None
+    ws = workspace(dev, _lib().vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O))
+    _l.check(_lib().vqf_mfb_fuse_bwd_grouped(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
+                                             _ptr(idx), _ptr(order), _ptr(grp_off), _keep_ptr(keep), int(seed), float(p_drop),
+                                             N, U, L, O, _ptr(dP), _ptr(dq), _ptr(db), _ptr(ws), ws.numel(), _stream()),
+             "vqf_mfb_fuse_bwd_grouped")
+    return dP, dq, db
 
 
 def lstm_seq_supported(B, H):
