@@ -404,6 +404,40 @@ int vqf_mfb_fuse_bwd_grouped(const float* dY, const float* Y, const float* inv, 
                              const int* grp_off, const uint8_t* keep, uint64_t seed, float p_drop, int N, int U, int L, int O,
                              float* dP, float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream);
 
+/* Region counts for the image fusion (MFB / MHBCoAtt.forward((img, img_length), ...); additions within ABI 7; fp32 only, no cascade /
+ * zdrop): img_features is (N, L, D) right-padded to L regions and sample n has lens[n] real ones.  lens is device int32, 4-byte
+ * aligned (null or misaligned: VQF_E_BADARG), clamped to [1, L] where the kernels read it.  With valid[n, l] = l < lens[n]:
+ *   fwd_len   a workgroup walks the real rows of its sample as vqf_mfb_fuse_fwd does and reads NOTHING of the padded ones: their
+ *             R rows and rowssq partials are exact zeros, so vqf_l2_group_norm gives the norm over the real rows;
+ *   bwd_len   dY, Y and P are not read on padded rows, whose dP rows are exact zeros; dq and dbiasP sum the real rows.
+ *             ws: vqf_mfb_fuse_bwd_ws_bytes(N, L, O).
+ *   fwd_grouped_len / bwd_grouped_len   the same over U shared images: lens_u (U) is the count of each image and lens_q (N) that of
+ *             each question's image (lens_q[n] = lens_u[idx[n]]; the caller's gather).  The question-owned kernels read lens_q, the
+ *             image-owned pass reads lens_u: a row pair beyond the count skips the walk over the image's questions and stores zeros.
+ *             ws: vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O), always.
+ * The Philox element index stays (n*L + l)*5*O + c: the masks of the real elements do not depend on the counts.  With lens = L
+ * everywhere each form gives the bits of the form without lens; what the padded rows of P, dY and Y hold changes no output bit.
+ *   glimpse_pool_fwd_grouped_len / _bwd_grouped_len   vqf_glimpse_pool_fwd_grouped / _bwd_grouped with the softmax of question n over
+ *             its first lens[n] regions (lens (N): per QUESTION), as vqf_glimpse_pool_fwd_len / _bwd_len have it. */
+int vqf_mfb_fuse_fwd_len(const float* P, const float* pbias, const float* q, const int* lens, const uint8_t* keep, uint64_t seed,
+                         float p_drop, int N, int L, int O, float* R, float* rowssq, void* stream);
+int vqf_mfb_fuse_bwd_len(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB, const float* P,
+                         const float* pbias, const float* q, const int* lens, const uint8_t* keep, uint64_t seed, float p_drop,
+                         int N, int L, int O, float* dP, float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream);
+int vqf_mfb_fuse_fwd_grouped_len(const float* P, const float* pbias, const float* q, const int* idx, const int* lens_q,
+                                 const int* lens_u, const uint8_t* keep, uint64_t seed, float p_drop, int N, int U, int L, int O,
+                                 float* R, float* rowssq, void* stream);
+int vqf_mfb_fuse_bwd_grouped_len(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
+                                 const float* P, const float* pbias, const float* q, const int* idx, const int* order,
+                                 const int* grp_off, const int* lens_q, const int* lens_u, const uint8_t* keep, uint64_t seed,
+                                 float p_drop, int N, int U, int L, int O, float* dP, float* dq, float* dbiasP, void* ws,
+                                 size_t ws_bytes, void* stream);
+int vqf_glimpse_pool_fwd_grouped_len(const float* feat, const float* logits, const int* idx, const int* lens, int N, int U, int S, int C,
+                                     int G, float* wts, float* pooled, void* stream);
+int vqf_glimpse_pool_bwd_grouped_len(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
+                                     const int* order, const int* grp_off, const int* lens, int N, int U, int S, int C, int G,
+                                     float* dlogits, float* dfeat, void* stream);
+
 
 /* --------------------------------------------------------------------------
  * Element-wise stages of HieCoAtten / AttentionNet.  n % 4 == 0, 16-byte aligned pointers.

@@ -776,16 +776,18 @@ int vqf_glimpse_pool_fwd_grouped(const float* feat, const float* logits, const i
   return glimpse_fwd_launch<float>(feat, logits, N, S, C, G, 0, wts, pooled, stream, nullptr, idx, U);
 }
 
-int vqf_glimpse_pool_bwd_grouped(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
-                                 const int* order, const int* grp_off, int N, int U, int S, int C, int G, float* dlogits,
-                                 float* dfeat, void* stream) {
+// lens (vqf_glimpse_pool_bwd_grouped_len; N int32 per QUESTION, null: all S): the softmax backward runs over the real regions; the
+// per-image half needs nothing -- it sums wts, which are exact zeros on padding
+static int glimpse_bwd_grouped(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
+                               const int* order, const int* grp_off, const int* lens, int N, int U, int S, int C, int G,
+                               float* dlogits, float* dfeat, void* stream) {
   if (!idx || !order || !grp_off || ((((uintptr_t)idx) | ((uintptr_t)order) | ((uintptr_t)grp_off)) & 3) || N <= 0 || U <= 0 ||
       S <= 0 || C <= 0)
     return VQF_E_BADARG;
   if (!vqf_glimpse_pool_grouped_supported(N, U, S, C, G)) return VQF_E_UNSUPPORTED;
   if (!aligned16(dpooled) || !aligned16(dfeat)) return VQF_E_ALIGN;
   // the per-question half (dlogits: feat[idx[n]] . dpooled[n], then the softmax backward) on the kernel of the plain form ...
-  int rc = glimpse_bwd_launch<float>(dpooled, dwts_extra, feat, wts, N, S, C, G, 0, dlogits, nullptr, stream, nullptr, idx, U);
+  int rc = glimpse_bwd_launch<float>(dpooled, dwts_extra, feat, wts, N, S, C, G, 0, dlogits, nullptr, stream, lens, idx, U);
   if (rc || !dfeat) return rc;
   // ... and the per-image half: dfeat[u] = the sum over the image's questions, in `order`
   hipStream_t s = (hipStream_t)stream;
@@ -798,6 +800,27 @@ int vqf_glimpse_pool_bwd_grouped(const float* dpooled, const float* dwts_extra, 
   else VQF_GD(1);
 #undef VQF_GD
   return vqf_last_error();
+}
+
+// region counts with shared images: lens (N) int32 per QUESTION (the count of its image), as in the *_len forms
+int vqf_glimpse_pool_fwd_grouped_len(const float* feat, const float* logits, const int* idx, const int* lens, int N, int U, int S, int C,
+                                     int G, float* wts, float* pooled, void* stream) {
+  if (!idx || !lens || ((((uintptr_t)idx) | ((uintptr_t)lens)) & 3) || N <= 0 || U <= 0 || S <= 0 || C <= 0) return VQF_E_BADARG;
+  if (!vqf_glimpse_pool_grouped_supported(N, U, S, C, G)) return VQF_E_UNSUPPORTED;
+  return glimpse_fwd_launch<float>(feat, logits, N, S, C, G, 0, wts, pooled, stream, lens, idx, U);
+}
+
+int vqf_glimpse_pool_bwd_grouped(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
+                                 const int* order, const int* grp_off, int N, int U, int S, int C, int G, float* dlogits,
+                                 float* dfeat, void* stream) {
+  return glimpse_bwd_grouped(dpooled, dwts_extra, feat, wts, idx, order, grp_off, nullptr, N, U, S, C, G, dlogits, dfeat, stream);
+}
+
+int vqf_glimpse_pool_bwd_grouped_len(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
+                                     const int* order, const int* grp_off, const int* lens, int N, int U, int S, int C, int G,
+                                     float* dlogits, float* dfeat, void* stream) {
+  if (!lens || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
+  return glimpse_bwd_grouped(dpooled, dwts_extra, feat, wts, idx, order, grp_off, lens, N, U, S, C, G, dlogits, dfeat, stream);
 }
 
 int vqf_row_block_supported(int N, int U, long long blk) {

@@ -202,14 +202,18 @@ __device__ __forceinline__ void keep_scale20(const uint8_t* __restrict__ keep, u
 // GRP (vqf_mfb_fuse_fwd_grouped: N questions over U shared images): P is (U*L, 5O) and the block of question n reads the rows of
 // image idx[n], clamped to [0, U - 1] here; q, keep / the Philox element index, R and rowssq stay per question.  Nothing else
 // differs: with idx[n] = n the values, the operations and their order are those of the plain kernel.
-template <typename PT, int COAL, bool GRP = false>
+// LEN (vqf_mfb_fuse_fwd_len / _grouped_len: region counts, lens (N) int32): the block reads Lv = clamp(lens[n], 1, L) once (uniform
+// over the block: the wave-private LDS transpose stays convergent), walks l = ls, ls + LS, ... < Lv exactly as without it, and for
+// Lv <= l < L reads nothing and stores a zero R row and zero rowssq partials.  With lens[n] = L it gives the plain kernel's bits.
+template <typename PT, int COAL, bool GRP = false, bool LEN = false>
 __global__ void __launch_bounds__(256)
 mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
                     const float* __restrict__ q,
                     const float* __restrict__ cascade, const uint8_t* __restrict__ keep,
                     uint64_t seed, uint32_t thr, float inv_keep, int L, int O, int LS,
                     float* __restrict__ R, float* __restrict__ rowssq, float* __restrict__ zdrop,
-                    unsigned short* __restrict__ Rb, int ldrb, const int* __restrict__ idx, int U) {
+                    unsigned short* __restrict__ Rb, int ldrb, const int* __restrict__ idx, int U,
+                    const int* __restrict__ lens) {
   // Rb != nullptr: a bf16 copy of R (round-to-nearest-even) with row pitch ldrb >= O, columns O .. ldrb-1 zero: the K-padded A
   // operand of the co-attention conv's bf16 GEMM (BASELINE config 3) straight from the registers that hold R -- no
   // vqf_cast_f32_bf16 pass over the 401 MB tensor.  ldrb / 4 <= 256.
@@ -223,6 +227,7 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
   const int nt = O / TPT;                       // active threads (250 at O = 1000); O / TPT <= 256
   const bool act = tid < nt;
   const long long prow0 = (long long)(GRP ? min(max(idx[n], 0), U - 1) : n) * L;     // first projection row of the sample
+  const int Lw = LEN ? min(max(lens[n], 1), L) : L;                                   // rows the block walks (LEN: the real regions)
   float qq[CPT], pb[CPT], p[CPT], pn[CPT];
   Raw<PT> rn;                                   // COAL: the next row's span of this wave, lane-linear pieces
 #pragma unroll
@@ -230,17 +235,18 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
   if (act) {
     load20(q + (long long)n * W5 + CPT * tid, qq);
     if (pbias) load20(pbias + CPT * tid, pb);
-    if (!COAL && ls < L) load20(P + (prow0 + ls) * W5 + CPT * tid, pn);
+    if (!COAL && ls < Lw) load20(P + (prow0 + ls) * W5 + CPT * tid, pn);
   }
-  if (COAL == 1 && ls < L) raw_load(P + (prow0 + ls) * W5, W5, wave, lane, rn);     // every lane of the wave
+  if (COAL == 1 && ls < Lw) raw_load(P + (prow0 + ls) * W5, W5, wave, lane, rn);     // every lane of the wave
   int it = 0;
-  for (int l = ls; l < L; l += LS, ++it) {
+  int l = ls;
+  for (; l < Lw; l += LS, ++it) {
     const long long row = (long long)n * L + l, prow = prow0 + l;
     const long long e0 = row * W5 + (long long)CPT * tid;
     float ssq = 0.f;
     if (COAL == 1) {
       raw_to_own(rn, tl + wave * WLDS, lane, p);
-      if (l + LS < L) raw_load(P + (prow + LS) * W5, W5, wave, lane, rn);   // prefetch the next row of this block
+      if (l + LS < Lw) raw_load(P + (prow + LS) * W5, W5, wave, lane, rn);   // prefetch the next row of this block
     } else if (COAL == 2) {
       raw_load(P + prow * W5, W5, wave, lane, rn);
       raw_to_own(rn, tl + wave * WLDS, lane, p);
@@ -249,7 +255,7 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
       if (!COAL) {
 #pragma unroll
         for (int i = 0; i < CPT; ++i) p[i] = pn[i];
-        if (l + LS < L) load20(P + (prow + LS) * W5 + CPT * tid, pn);      // prefetch the next row of this block
+        if (l + LS < Lw) load20(P + (prow + LS) * W5 + CPT * tid, pn);      // prefetch the next row of this block
       }
       float sc[CPT], cc[CPT];
       keep_scale20(keep, seed, thr, inv_keep, e0, sc);
@@ -296,12 +302,27 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
     if ((tid & 63) == 0) rowssq[4 * row + (tid >> 6)] = ssq;
 #endif
   }
+  if (LEN) {
+    // the padded rows of this block: nothing read, exact zeros through the stores of the walk (the LEN forms have no zdrop / Rb)
+    for (; l < L; l += LS) {
+      const long long row = (long long)n * L + l;
+      if (act) *reinterpret_cast<f32x4*>(R + row * O + TPT * tid) = f32x4{0.f, 0.f, 0.f, 0.f};
+#if VQF_FUSE_ROWBAR
+      if (tid < 4) rowssq[4 * row + tid] = 0.f;
+#else
+      if ((tid & 63) == 0) rowssq[4 * row + (tid >> 6)] = 0.f;
+#endif
+    }
+  }
 }
 
 // grid (N, LS); block 256.  Each block walks rows l = ls, ls+LS, ... of sample n.
 // GRP (the question-owned pass of vqf_mfb_fuse_bwd_grouped): P is (U*L, 5O), read at the rows of image idx[n] (clamped here), and
 // dP is NOT written -- this pass leaves the dq partials only; mfb_fuse_bwd_image_kernel sums dP over each image's questions.
-template <bool CASC, bool DBIAS, typename DPT, typename PT, bool COAL, bool GRP = false>
+// LEN (region counts, as in the forward): the walk stops at Lv = clamp(lens[n], 1, L); of the rows beyond, dY / Y / P are not read
+// and (plain form) dP gets exact zero rows through the store path of the walk.  A block without a real row still writes its
+// zero dq / bias partials.
+template <bool CASC, bool DBIAS, typename DPT, typename PT, bool COAL, bool GRP = false, bool LEN = false>
 __global__ void __launch_bounds__(256)
 mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdrop,
                     const float* __restrict__ Y,
@@ -311,13 +332,15 @@ mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdr
                     const float* __restrict__ q, const float* __restrict__ cascade,
                     const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep,
                     int L, int O, int LS, DPT* __restrict__ dP, float* __restrict__ dq_part,
-                    float* __restrict__ dcascade, float* __restrict__ db_part, const int* __restrict__ idx, int U) {
+                    float* __restrict__ dcascade, float* __restrict__ db_part, const int* __restrict__ idx, int U,
+                    const int* __restrict__ lens) {
   __shared__ __attribute__((aligned(16))) char tl[COAL ? 4 * WLDS : 16];
   const int n = blockIdx.x, ls = blockIdx.y;
   const int W5 = KP * O;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const float ca = coefA[n], cb = coefB[n], hi = 0.5f * inv[n];
   const long long prow0 = (long long)(GRP ? min(max(idx[n], 0), U - 1) : n) * L;     // first projection row of the sample
+  const int Lw = LEN ? min(max(lens[n], 1), L) : L;                                   // rows the block walks (LEN: the real regions)
   // COAL (O / 4 <= 256: one pass): every lane of a wave takes part in the coalesced P loads / dP stores, threads past
   // O / 4 only skip the arithmetic
   for (int t = threadIdx.x; COAL ? t < 256 : t < O / TPT; t += 256) {
@@ -329,7 +352,8 @@ mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdr
       load20(q + (long long)n * W5 + CPT * t, qq);
       if (pbias) load20(pbias + CPT * t, pb);
     }
-    for (int l = ls; l < L; l += LS) {
+    int l = ls;
+    for (; l < Lw; l += LS) {
       const long long row = (long long)n * L + l, prow = prow0 + l;
       const long long e0 = row * W5 + (long long)CPT * t;
       float p[CPT], sc[CPT], cc[CPT], dp[CPT], dc[CPT], dzx[CPT];
@@ -376,6 +400,16 @@ mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdr
       }
       if (COAL && !GRP) own_store(dP + row * W5, W5, wave, lane, tl + wave * WLDS, dp);
     }
+    if (LEN && !GRP) {
+      float zr[CPT];
+#pragma unroll
+      for (int i = 0; i < CPT; ++i) zr[i] = 0.f;
+      for (; l < L; l += LS) {                           // the padded rows of this block: exact zero dP rows
+        const long long row = (long long)n * L + l;
+        if (COAL) own_store(dP + row * W5, W5, wave, lane, tl + wave * WLDS, zr);
+        else if (act) store20(dP + row * W5 + (long long)CPT * t, zr);
+      }
+    }
     if (act) {
       const long long po = ((long long)n * LS + ls) * W5 + CPT * t;
       store20(dq_part + po, dq);
@@ -392,16 +426,20 @@ mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdr
 // fixed order: no atomics, the same bits on every run, and an image without a question stores exact zeros.  Each row is stored
 // once through own_store (every lane of a wave takes part); the column sums of the rows a block wrote are its db partial.
 // P is not read.  order is clamped to [0, N - 1] and grp_off to [0, N] (kept monotone) where they are read.
+// LEN (region counts per IMAGE, lens (U) int32; every question of image u has that count): Lu = clamp(lens[u], 1, L); a row pair
+// entirely beyond Lu skips the walk over the image's questions and stores zeros, a pair straddling Lu accumulates its real row only.
 constexpr int IRB = 2;              // rows per walk of an image's questions
-template <bool DBIAS>
+template <bool DBIAS, bool LEN = false>
 __global__ void __launch_bounds__(256)
 mfb_fuse_bwd_image_kernel(const float* __restrict__ dY, const float* __restrict__ Y, const float* __restrict__ inv,
                           const float* __restrict__ coefA, const float* __restrict__ coefB, const float* __restrict__ q,
                           const int* __restrict__ order, const int* __restrict__ grp_off,
                           const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep,
-                          int N, int L, int O, int LS, float* __restrict__ dP, float* __restrict__ db_part) {
+                          int N, int L, int O, int LS, float* __restrict__ dP, float* __restrict__ db_part,
+                          const int* __restrict__ lens) {
   __shared__ __attribute__((aligned(16))) char tl[4 * WLDS];
   const int u = blockIdx.x, ls = blockIdx.y;
+  const int Lw = LEN ? min(max(lens[u], 1), L) : L;                                   // rows that take gradient (LEN: the real regions)
   const int W5 = KP * O;
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
   const bool act = t < O / TPT;
@@ -415,7 +453,7 @@ mfb_fuse_bwd_image_kernel(const float* __restrict__ dY, const float* __restrict_
     for (int r = 0; r < IRB; ++r)
 #pragma unroll
       for (int i = 0; i < CPT; ++i) dp[r][i] = 0.f;
-    if (act) {
+    if (act && (!LEN || l0 < Lw)) {
       for (int j = jb; j < je; ++j) {
         const int n = min(max(order[j], 0), N - 1);
         const float ca = coefA[n], cb = coefB[n], hi = 0.5f * inv[n];
@@ -423,7 +461,7 @@ mfb_fuse_bwd_image_kernel(const float* __restrict__ dY, const float* __restrict_
         load20(q + (long long)n * W5 + CPT * t, qq);
 #pragma unroll
         for (int r = 0; r < IRB; ++r) {
-          if (l0 + r < L) {
+          if (l0 + r < Lw) {
             const long long row = (long long)n * L + l0 + r;
             const f32x4 dy = *reinterpret_cast<const f32x4*>(dY + row * O + TPT * t);
             const f32x4 y = *reinterpret_cast<const f32x4*>(Y + row * O + TPT * t);
@@ -501,8 +539,10 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
                      const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O,
                      void* dP, int dp_bf16, float* dq, float* dcascade, float* dbiasP, void* ws,
                      size_t ws_bytes, void* stream, const int* idx = nullptr, const int* order = nullptr,
-                     const int* grp_off = nullptr, int U = 0) {
+                     const int* grp_off = nullptr, int U = 0, const int* lens = nullptr, const int* lens_u = nullptr) {
   // idx != nullptr: the grouped form (vqf_mfb_fuse_bwd_grouped, which has checked its own operands): P and dP are (U*L, 5O)
+  // lens != nullptr: the region-count forms (fp32, no cascade / dzdrop; their entry points have checked lens): lens (N) per sample /
+  // question, lens_u (U) per image in the grouped form
   if (!dY || !Y || !inv || !coefA || !coefB || !P || !q || !dP || !dq || N <= 0 || L <= 0 || O <= 0)
     return VQF_E_BADARG;
   if (O % TPT) return VQF_E_UNSUPPORTED;
@@ -532,29 +572,28 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
 #define VQF_BWD1(C_, D_, T_, PT_, CO_)                                                           \
   VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<C_, D_, T_, PT_, CO_>), grid, dim3(256), 0, s, dY, dzdrop, Y, inv, \
              coefA, coefB, (const PT_*)P, pbias, q, cascade, keep, seed, thr, inv_keep, L, O, LS, (T_*)dP, dq_part, \
-             dcascade, db_part, nullptr, 0)
+             dcascade, db_part, nullptr, 0, nullptr)
 #define VQF_BWD(C_, D_, T_, PT_) do { if (coal) VQF_BWD1(C_, D_, T_, PT_, true); else VQF_BWD1(C_, D_, T_, PT_, false); } while (0)
   if (idx) {
     // question-owned pass: the plain kernel reading P through idx, no dP store, no bias partials (the dq partials only) ...
-    if (coal)
-      VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<false, false, float, float, true, true>), grid, dim3(256), 0, s, dY, nullptr,
-                 Y, inv, coefA, coefB, (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, (float*)nullptr,
-                 dq_part, nullptr, nullptr, idx, U);
-    else
-      VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<false, false, float, float, false, true>), grid, dim3(256), 0, s, dY, nullptr,
-                 Y, inv, coefA, coefB, (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, (float*)nullptr,
-                 dq_part, nullptr, nullptr, idx, U);
+#define VQF_BWDQ(CO_, LEN_)                                                                                                          \
+  VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<false, false, float, float, CO_, true, LEN_>), grid, dim3(256), 0, s, dY, nullptr, \
+             Y, inv, coefA, coefB, (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, (float*)nullptr,         \
+             dq_part, nullptr, nullptr, idx, U, lens)
+    if (lens) { if (coal) VQF_BWDQ(true, true); else VQF_BWDQ(false, true); }
+    else      { if (coal) VQF_BWDQ(true, false); else VQF_BWDQ(false, false); }
+#undef VQF_BWDQ
     int rcg = vqf_last_error();
     if (rcg) return rcg;
     // ... image-owned pass: dP rows and the bias partials of the U*L rows it wrote
     const int LSI = pick_ls_image(U, L);
     db_part = (float*)ws + (size_t)N * LS * W5;                   // [U * LSI][5O], then the reducer's VQF_REDUCE_SPLITS rows
-    if (dbiasP)
-      VQF_LAUNCH(KID_MFB_FUSE_BWD_IMAGE, (mfb_fuse_bwd_image_kernel<true>), dim3(U, LSI), dim3(256), 0, s, dY, Y, inv, coefA, coefB, q,
-                 order, grp_off, keep, seed, thr, inv_keep, N, L, O, LSI, (float*)dP, db_part);
-    else
-      VQF_LAUNCH(KID_MFB_FUSE_BWD_IMAGE, (mfb_fuse_bwd_image_kernel<false>), dim3(U, LSI), dim3(256), 0, s, dY, Y, inv, coefA, coefB, q,
-                 order, grp_off, keep, seed, thr, inv_keep, N, L, O, LSI, (float*)dP, nullptr);
+#define VQF_BWDI(DB_, LEN_)                                                                                                          \
+  VQF_LAUNCH(KID_MFB_FUSE_BWD_IMAGE, (mfb_fuse_bwd_image_kernel<DB_, LEN_>), dim3(U, LSI), dim3(256), 0, s, dY, Y, inv, coefA, coefB, \
+             q, order, grp_off, keep, seed, thr, inv_keep, N, L, O, LSI, (float*)dP, DB_ ? db_part : nullptr, lens_u)
+    if (lens_u) { if (dbiasP) VQF_BWDI(true, true); else VQF_BWDI(false, true); }
+    else        { if (dbiasP) VQF_BWDI(true, false); else VQF_BWDI(false, false); }
+#undef VQF_BWDI
     rcg = vqf_last_error();
     if (rcg) return rcg;
     if (!direct) {
@@ -564,7 +603,16 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
     if (dbiasP) rcg = vqf_colreduce_2stage(db_part, U * LSI, W5, dbiasP, db_part + (size_t)U * LSI * W5, s);
     return rcg;
   }
-  if (p_bf16)       { if (dbiasP) VQF_BWD(false, true, __bf16, __bf16); else VQF_BWD(false, false, __bf16, __bf16); }
+  if (lens) {
+#define VQF_BWDL(D_, CO_)                                                                                                            \
+  VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<false, D_, float, float, CO_, false, true>), grid, dim3(256), 0, s, dY, nullptr,  \
+             Y, inv, coefA, coefB, (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, (float*)dP, dq_part,     \
+             nullptr, db_part, nullptr, 0, lens)
+    if (dbiasP) { if (coal) VQF_BWDL(true, true); else VQF_BWDL(true, false); }
+    else        { if (coal) VQF_BWDL(false, true); else VQF_BWDL(false, false); }
+#undef VQF_BWDL
+  }
+  else if (p_bf16)  { if (dbiasP) VQF_BWD(false, true, __bf16, __bf16); else VQF_BWD(false, false, __bf16, __bf16); }
   else if (dp_bf16) { if (dbiasP) VQF_BWD(false, true, __bf16, float); else VQF_BWD(false, false, __bf16, float); }
   else if (cascade) { if (dbiasP) VQF_BWD(true, true, float, float); else VQF_BWD(true, false, float, float); }
   else              { if (dbiasP) VQF_BWD(false, true, float, float); else VQF_BWD(false, false, float, float); }
@@ -586,7 +634,8 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
 static int fuse_fwd_impl(const void* P, int p_bf16, const float* pbias, const float* q, const float* cascade,
                          const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O, float* R,
                          float* rowssq, float* zdrop, void* stream, void* R_bf16 = nullptr, int ldrb = 0,
-                         const int* idx = nullptr, int U = 0) {
+                         const int* idx = nullptr, int U = 0, const int* lens = nullptr) {
+  // lens != nullptr: the region-count forms (fp32 P, no cascade / zdrop / R_bf16; their entry points have checked lens)
   if (!P || !q || !R || !rowssq || N <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
   if (R_bf16 && (ldrb < O || (ldrb % 4) || ldrb / 4 > 256 || (((uintptr_t)R_bf16) & 7))) return VQF_E_BADARG;
   if ((O % TPT) || O / TPT > 256) return VQF_E_UNSUPPORTED;     // one thread per 4 pooled outputs: O <= 1024 (the reference's 1000)
@@ -603,13 +652,19 @@ static int fuse_fwd_impl(const void* P, int p_bf16, const float* pbias, const fl
 #define VQF_FWD(PT_, CO_)                                                                                             \
   VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<PT_, CO_>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream,         \
              (const PT_*)P, pbias, q, cascade, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, zdrop, (unsigned short*)R_bf16, ldrb, \
-             nullptr, 0)
+             nullptr, 0, nullptr)
 #define VQF_FWDG(CO_)                                                                                                 \
   VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<float, CO_, true>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream, \
-             (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, nullptr, nullptr, 0, idx, U)
-  if (idx)    { if (nopf) VQF_FWDG(2); else if (coal) VQF_FWDG(1); else VQF_FWDG(0); }       // the grouped form (fp32 only)
+             (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, nullptr, nullptr, 0, idx, U, nullptr)
+#define VQF_FWDL(CO_, GRP_)                                                                                           \
+  VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<float, CO_, GRP_, true>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream, \
+             (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, nullptr, nullptr, 0, idx, U, lens)
+  if (lens && idx) { if (nopf) VQF_FWDL(2, true); else if (coal) VQF_FWDL(1, true); else VQF_FWDL(0, true); }     // region counts (fp32 only)
+  else if (lens)   { if (nopf) VQF_FWDL(2, false); else if (coal) VQF_FWDL(1, false); else VQF_FWDL(0, false); }
+  else if (idx) { if (nopf) VQF_FWDG(2); else if (coal) VQF_FWDG(1); else VQF_FWDG(0); }       // the grouped form (fp32 only)
   else if (p_bf16) { if (nopf) VQF_FWD(__bf16, 2); else if (coal) VQF_FWD(__bf16, 1); else VQF_FWD(__bf16, 0); }
   else        { if (nopf) VQF_FWD(float, 2); else if (coal) VQF_FWD(float, 1); else VQF_FWD(float, 0); }
+#undef VQF_FWDL
 #undef VQF_FWDG
 #undef VQF_FWD
   return vqf_last_error();
@@ -678,6 +733,44 @@ int vqf_mfb_fuse_bwd_grouped(const float* dY, const float* Y, const float* inv, 
   if (!ws || ws_bytes < vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O) || !aligned16(ws)) return VQF_E_WORKSPACE;
   return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
                        dbiasP, ws, ws_bytes, stream, idx, order, grp_off, U);
+}
+
+// the region-count forms (lens: int32, 4-byte aligned; the kernels clamp what it holds to [1, L])
+int vqf_mfb_fuse_fwd_len(const float* P, const float* pbias, const float* q, const int* lens, const uint8_t* keep, uint64_t seed,
+                         float p_drop, int N, int L, int O, float* R, float* rowssq, void* stream) {
+  if (!grouped_index_ok(lens)) return VQF_E_BADARG;
+  return fuse_fwd_impl(P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, R, rowssq, nullptr, stream, nullptr, 0, nullptr, 0, lens);
+}
+
+int vqf_mfb_fuse_bwd_len(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB, const float* P,
+                         const float* pbias, const float* q, const int* lens, const uint8_t* keep, uint64_t seed, float p_drop,
+                         int N, int L, int O, float* dP, float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream) {
+  if (!grouped_index_ok(lens)) return VQF_E_BADARG;
+  return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
+                       dbiasP, ws, ws_bytes, stream, nullptr, nullptr, nullptr, 0, lens);
+}
+
+int vqf_mfb_fuse_fwd_grouped_len(const float* P, const float* pbias, const float* q, const int* idx, const int* lens_q,
+                                 const int* lens_u, const uint8_t* keep, uint64_t seed, float p_drop, int N, int U, int L, int O,
+                                 float* R, float* rowssq, void* stream) {
+  if (!grouped_index_ok(idx) || !grouped_index_ok(lens_q) || !grouped_index_ok(lens_u) || N <= 0 || U <= 0 || L <= 0 || O <= 0)
+    return VQF_E_BADARG;
+  if (!vqf_mfb_fuse_grouped_supported(N, U, L, O)) return VQF_E_UNSUPPORTED;
+  return fuse_fwd_impl(P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, R, rowssq, nullptr, stream, nullptr, 0, idx, U, lens_q);
+}
+
+int vqf_mfb_fuse_bwd_grouped_len(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
+                                 const float* P, const float* pbias, const float* q, const int* idx, const int* order,
+                                 const int* grp_off, const int* lens_q, const int* lens_u, const uint8_t* keep, uint64_t seed,
+                                 float p_drop, int N, int U, int L, int O, float* dP, float* dq, float* dbiasP, void* ws,
+                                 size_t ws_bytes, void* stream) {
+  if (!grouped_index_ok(idx) || !grouped_index_ok(order) || !grouped_index_ok(grp_off) || !grouped_index_ok(lens_q) ||
+      !grouped_index_ok(lens_u) || N <= 0 || U <= 0 || L <= 0 || O <= 0)
+    return VQF_E_BADARG;
+  if (!vqf_mfb_fuse_grouped_supported(N, U, L, O)) return VQF_E_UNSUPPORTED;
+  if (!ws || ws_bytes < vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O) || !aligned16(ws)) return VQF_E_WORKSPACE;
+  return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
+                       dbiasP, ws, ws_bytes, stream, idx, order, grp_off, U, lens_q, lens_u);
 }
 
 int vqf_mfb_fuse_bwd_pbf16(const float* dY, const float* Y, const float* inv, const float* coefA,

@@ -129,3 +129,25 @@ def group_batch(image_ids):
             rows.append(n)
         index.append(u)
     return torch.tensor(rows, dtype=torch.int64), torch.tensor(index, dtype=torch.int64)
+
+
+def pad_region_features(features, multiple=1):
+    """The host half of a region-count batch (forward((img, img_length), ...)): features = one (K_i, D) array per image (detector
+    boxes, K_i >= 1, the same D) -> (img (N, Lmax, D) float32, zero-padded on the right, img_length (N,) int64), both CPU
+    tensors.  Lmax is the largest K_i rounded up to a multiple of `multiple`."""
+    arrs = [np.asarray(a, dtype=np.float32) for a in features]
+    if not arrs:
+        raise ValueError("pad_region_features: an empty list")
+    if int(multiple) < 1:
+        raise ValueError("pad_region_features: multiple must be >= 1")
+    if any(a.ndim != 2 or a.shape[0] < 1 for a in arrs):
+        raise ValueError("pad_region_features: every entry must be a (K_i, D) array with K_i >= 1")
+    D = arrs[0].shape[1]
+    if any(a.shape[1] != D for a in arrs):
+        raise ValueError("pad_region_features: mixed channel counts %s" % sorted({a.shape[1] for a in arrs}))
+    m = int(multiple)
+    Lmax = (max(a.shape[0] for a in arrs) + m - 1) // m * m
+    img = torch.zeros((len(arrs), Lmax, D), dtype=torch.float32)
+    for n, a in enumerate(arrs):
+        img[n, :a.shape[0]] = torch.from_numpy(np.ascontiguousarray(a))
+    return img, torch.tensor([a.shape[0] for a in arrs], dtype=torch.int64)

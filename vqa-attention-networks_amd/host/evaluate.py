@@ -127,7 +127,8 @@ def predict(model, img, q, q_length=None, k=5, **fwd_kwargs):
     Runs `model` in eval() mode (dropout off) under torch.no_grad() and puts its `training` flag back; q_length is passed
     only when given; HieCoAtten / HieCoAttenLadder return (logits, attention maps...): the first element is used.
     Further keyword arguments go to the model's forward: predict(model, img (U, L, D), q (N, T), q_length, img_index=idx) asks
-    HieCoAttenLadder N questions about U shared images (idx (N,): the image of each question)."""
+    HieCoAttenLadder N questions about U shared images (idx (N,): the image of each question); predict(model, (img, img_length),
+    q) asks MFB / MHBCoAtt about right-padded region features (img_length: the real regions of each image)."""
     was_training = model.training
     model.eval()
     try:

@@ -198,37 +198,43 @@ class AttHeadFn(torch.autograd.Function):
     grp: None, or (idx, order, grp_off) of grouping._group_index -- the image head of N questions over U shared images: feat is
         (U, S, C) data (no gradient), x stays (N*S, Cin) per question; question n pools the rows of image idx[n]
         (vqf_glimpse_pool_fwd_grouped / _bwd_grouped; under unit_softmax the per-image region sums, gathered).
+    lens: None, or the region counts of the image head (forward((img, img_length), ...); fp32 feat that is data): an int32 (N,) tensor,
+        with grp the pair (lens_q (N,), lens_u (U,)).  The softmax runs over the first lens[n] positions (unit_softmax: weight 1
+        there), the weights beyond are exact zeros and so are their dlogits, so the MLP's backward adds nothing for padded rows.
     returns pooled (N, 2C); the attention weights (N,2,S) are kept on ctx.
     """
 
     @staticmethod
-    def _pool_fwd(feat, logits, unit, grp):
+    def _pool_fwd(feat, logits, unit, grp, lens=None):
         if grp is None:
-            return ops.glimpse_pool_fwd(feat, logits, unit)
+            return ops.glimpse_pool_fwd(feat, logits, unit, lens=lens)
         if unit:      # weights == 1: the region sums of each IMAGE (the existing unit pooling on (U, S, C)), one row block per question
             U, S, _ = feat.shape
             zeros = torch.zeros((U * S, logits.shape[1]), dtype=torch.float32, device=feat.device)
-            _, per_image = ops.glimpse_pool_fwd(feat, zeros, True)
+            _, per_image = ops.glimpse_pool_fwd(feat, zeros, True, lens=None if lens is None else lens[1])
             return None, ops.row_block_gather(per_image, grp[0])
-        return ops.glimpse_pool_fwd_grouped(feat, logits, grp[0])
+        return ops.glimpse_pool_fwd_grouped(feat, logits, grp[0], lens=None if lens is None else lens[0])
 
     @staticmethod
-    def _pool_bwd(dpooled, feat, wts, unit, need_dfeat, grp, NS, G):
+    def _pool_bwd(dpooled, feat, wts, unit, need_dfeat, grp, NS, G, lens=None):
         if grp is None:
-            return ops.glimpse_pool_bwd(dpooled, feat, wts, unit, need_dfeat)
+            return ops.glimpse_pool_bwd(dpooled, feat, wts, unit, need_dfeat, lens=lens)
         if need_dfeat:
             raise ops._l.VqfError("AttHeadFn: with shared images (grp) the feature tensor is data and gets no gradient")
         if unit:      # d(pooled)/d(logits) == 0 under unit weights: the exact zeros the unit kernel writes
             return torch.zeros((NS, G), dtype=torch.float32, device=dpooled.device), None
-        return ops.glimpse_pool_bwd_grouped(dpooled, feat, wts, grp[0], grp[1], grp[2], False)
+        return ops.glimpse_pool_bwd_grouped(dpooled, feat, wts, grp[0], grp[1], grp[2], False, lens=None if lens is None else lens[0])
 
     @staticmethod
-    def forward(ctx, x, feat, w1, b1, wm, bm, w2, b2, unit_softmax, bf16=False, link=None, same_src=False, grp=None):
+    def forward(ctx, x, feat, w1, b1, wm, bm, w2, b2, unit_softmax, bf16=False, link=None, same_src=False, grp=None, lens=None):
         x = _c(x)
         feat = _c(feat)
         ctx.bf16 = bool(bf16)
         ctx.same_src = bool(same_src)
         ctx.grp = grp
+        ctx.lens = lens
+        if lens is not None and (ctx.bf16 or ctx.same_src or feat.dtype != torch.float32 or ctx.needs_input_grad[1]):
+            raise ops._l.VqfError("AttHeadFn: region counts (lens) are fp32 only, for a feature tensor that is data")
         if grp is not None and (ctx.bf16 or ctx.same_src or feat.dtype != torch.float32):
             raise ops._l.VqfError("AttHeadFn: shared images (grp) are fp32 only and never the MLP's own source")
         if ctx.same_src and (x.numel() != feat.numel() or x.shape[-1] != feat.shape[-1] or x.dtype != feat.dtype):
@@ -249,7 +255,7 @@ class AttHeadFn(torch.autograd.Function):
             else:
                 hid1 = ops.gemm_rowscale(x, _w2d(w1), link.inv, link.L, bias=b1, relu=True)
             logits, lin = ops.att_logits_fwd_lin(hid1, _w2d(w2), b2, b1)
-            wts, pooled = AttHeadFn._pool_fwd(feat, logits, unit_softmax, grp)
+            wts, pooled = AttHeadFn._pool_fwd(feat, logits, unit_softmax, grp, lens)
             # (bf16 mode: slot 3 -- no "multilayer" conv with a NormLink -- carries the bf16 copy of w1 to the backward: one cast per step)
             ctx.save_for_backward(x, feat, w1, w1b if ctx.bf16 else None, w2, hid1, None, wts, lin)
             ctx.unit = bool(unit_softmax)
@@ -267,7 +273,7 @@ class AttHeadFn(torch.autograd.Function):
         hid2 = ops.gemm(hid1, _w2d(wm), bias=bm, relu=True) if wm is not None else None
         last = hid2 if hid2 is not None else hid1
         logits = ops.att_logits_fwd(last, _w2d(w2), b2)
-        wts, pooled = AttHeadFn._pool_fwd(feat, logits, unit_softmax, grp)
+        wts, pooled = AttHeadFn._pool_fwd(feat, logits, unit_softmax, grp, lens)
         ctx.save_for_backward(x, feat, w1, wm, w2, hid1, hid2, wts, w1b if ctx.bf16 else None)      # (last slot: the bf16 copy of w1)
         ctx.unit = bool(unit_softmax)
         return pooled
@@ -277,7 +283,8 @@ class AttHeadFn(torch.autograd.Function):
         x, feat, w1, wm, w2, hid1, hid2, wts, lin = ctx.saved_tensors
         dpooled = _c(dpooled)
         need_dfeat = ctx.needs_input_grad[1]
-        dlogits, dfeat = AttHeadFn._pool_bwd(dpooled, feat, wts, ctx.unit, need_dfeat, ctx.grp, hid1.shape[0], _w2d(w2).shape[0])
+        dlogits, dfeat = AttHeadFn._pool_bwd(dpooled, feat, wts, ctx.unit, need_dfeat, ctx.grp, hid1.shape[0], _w2d(w2).shape[0],
+                                             ctx.lens)
         if ctx.link is not None:
             link = ctx.link
             w1b = wm                                       # (slot 3, see forward)
@@ -290,10 +297,10 @@ class AttHeadFn(torch.autograd.Function):
                 d1b = d1s if obf else ops.cast_bf16(d1s)
                 dw1 = ops.gemm_bf16(d1b, x, ta=True, tb=True)[:, :cin].contiguous().view_as(w1)
                 dx = ops.gemm_bf16(d1b, w1b, tb=True, N=cin) if ctx.needs_input_grad[0] else None
-                return dx, dfeat, dw1, db1, None, None, dw2.view_as(w2), db2, None, None, None, None, None
+                return dx, dfeat, dw1, db1, None, None, dw2.view_as(w2), db2, None, None, None, None, None, None
             dw1 = ops.gemm(d1s, x, ta=True, tb=True).view_as(w1)                    # = dpre^T Y
             dx = ops.gemm(d1s, _w2d(w1), tb=True) if ctx.needs_input_grad[0] else None   # dYs = dY / norm
-            return dx, dfeat, dw1, db1, None, None, dw2.view_as(w2), db2, None, None, None, None, None
+            return dx, dfeat, dw1, db1, None, None, dw2.view_as(w2), db2, None, None, None, None, None, None
         last = hid2 if hid2 is not None else hid1
         dlast_pre, dw2, db2, dblast = ops.att_logits_bwd(dlogits, last, _w2d(w2), relu_mask=True)
         dwm = dbm = None
@@ -318,7 +325,7 @@ class AttHeadFn(torch.autograd.Function):
                 dx = None
             else:
                 dx = ops.gemm(d1_pre, _w2d(w1), tb=True) if ctx.needs_input_grad[0] else None
-        return dx, dfeat, dw1, db1, dwm, dbm, dw2.view_as(w2), db2, None, None, None, None, None
+        return dx, dfeat, dw1, db1, dwm, dbm, dw2.view_as(w2), db2, None, None, None, None, None, None
 
 
 def _arm_link(link, inv, L, xb=None):
@@ -348,12 +355,15 @@ class ImgFuseFn(torch.autograd.Function):
     (N,1000,L,1) permutation of the same values, mfb.py:103-106).
     grp (None, or (idx, order, grp_off) of grouping._group_index; fp32 only): img is (U, L, D), the images N questions share.
     The projection and its weight gradient run on U*L rows; the fusion reads P through idx and its backward sums dP per image.
+    lens (None, or the region counts: an int32 (N,) tensor, with grp the pair (lens_q (N,), lens_u (U,)); fp32 only): sample n has
+    lens[n] real regions.  The projection and its weight gradient still run over every row; the fusion reads no padded row of P
+    and hands back exact zero dP rows there, so finite padding cancels in the weight gradient.
     """
 
     BF16_P = True      # bf16 mode: store P in bf16 when the large-tile GEMM applies (A/B switch)
 
     @staticmethod
-    def forward(ctx, img, wi, bi, q, keep, seed, p_drop, bf16=False, link=None, grp=None):
+    def forward(ctx, img, wi, bi, q, keep, seed, p_drop, bf16=False, link=None, grp=None, lens=None):
         img = _c(img)
         q = _c(q)
         N, L, D = img.shape
@@ -361,13 +371,16 @@ class ImgFuseFn(torch.autograd.Function):
         O = wi2.shape[0] // ops.POOL_K
         ctx.bf16 = bool(bf16)
         ctx.grp = grp
+        ctx.lens = lens
+        if lens is not None and (ctx.bf16 or img.dtype != torch.float32):
+            raise ops._l.VqfError("ImgFuseFn: region counts (lens) are fp32 only")
         if grp is not None:
             if ctx.bf16 or img.dtype != torch.float32:
                 raise ops._l.VqfError("ImgFuseFn: shared images (grp) are fp32 only")
             U, N = N, q.shape[0]
             P = ops.gemm(img.view(U * L, D), wi2, bias=bi)                     # once per image
             Y, norm, inv = ops.mfb_fuse_fwd_grouped(P, q, grp[0], N, U, L, O, keep=keep, seed=seed, p_drop=p_drop,
-                                                    normalise=link is None)
+                                                    normalise=link is None, lens=lens)
             ctx.link = _arm_link(link, inv, L, None)
             ctx.save_for_backward(img, wi, q, P, Y, norm, inv, keep)
             ctx.seed, ctx.p_drop, ctx.dims = seed, p_drop, (N, L, D, O)
@@ -384,7 +397,8 @@ class ImgFuseFn(torch.autograd.Function):
         else:
             P = ops.gemm(img.view(N * L, D), wi2, bias=bi)
         rb = [] if (link is not None and P.dtype == torch.bfloat16) else None
-        Y, norm, inv, _ = ops.mfb_fuse_fwd(P, q, N, L, O, keep=keep, seed=seed, p_drop=p_drop, normalise=link is None, r_bf16=rb)
+        Y, norm, inv, _ = ops.mfb_fuse_fwd(P, q, N, L, O, keep=keep, seed=seed, p_drop=p_drop, normalise=link is None, r_bf16=rb,
+                                           lens=lens)
         ctx.link = _arm_link(link, inv, L, rb)
         ctx.save_for_backward(img, wi, q, P, Y, norm, inv, keep)
         ctx.seed, ctx.p_drop, ctx.dims = seed, p_drop, (N, L, D, O)
@@ -398,16 +412,17 @@ class ImgFuseFn(torch.autograd.Function):
             U = img.shape[0]
             dP, dq, dbi = ops.mfb_fuse_bwd_grouped(_c(dY), Y, norm, inv, P, q, ctx.grp[0], ctx.grp[1], ctx.grp[2], N, U, L, O,
                                                    keep=keep, seed=ctx.seed, p_drop=ctx.p_drop, want_dbias=True,
-                                                   lin=_take_lin(ctx.link))
+                                                   lin=_take_lin(ctx.link), lens=ctx.lens)
             dwi = ops.gemm(dP, img.view(U * L, D), ta=True, tb=True).view_as(wi)   # wgrad, K = U*L
-            return None, dwi, dbi, dq, None, None, None, None, None, None
+            return None, dwi, dbi, dq, None, None, None, None, None, None, None
         dP, dq, _, dbi = ops.mfb_fuse_bwd(_c(dY), Y, norm, inv, P, q, N, L, O, keep=keep, seed=ctx.seed,
-                                          p_drop=ctx.p_drop, want_dbias=True, dp_bf16=ctx.bf16, lin=_take_lin(ctx.link))
+                                          p_drop=ctx.p_drop, want_dbias=True, dp_bf16=ctx.bf16, lin=_take_lin(ctx.link),
+                                          lens=ctx.lens)
         if ctx.bf16:                  # dP already is the bf16 A operand of the weight-gradient GEMM
             dwi = ops.gemm_bf16(dP, img, ta=True, tb=True).view_as(wi)
         else:
             dwi = ops.gemm(dP, img.view(N * L, D), ta=True, tb=True).view_as(wi)   # wgrad, K = N*L
-        return None, dwi, dbi, dq, None, None, None, None, None, None
+        return None, dwi, dbi, dq, None, None, None, None, None, None, None
 
 
 class ImgProjFn(torch.autograd.Function):
@@ -521,26 +536,30 @@ class MfbFuseFn(torch.autograd.Function):
     P0 fp32, or bf16 (then dP is handed back in bf16 too: the bf16 mode's projection storage).
     grp (None, or (idx, order, grp_off) of grouping._group_index; fp32 only): P0 is (U*L, 5000), the projection of the U images
     the N questions share; dP comes back (U*L, 5000), summed over each image's questions, so the projection node behind it
-    (ImgProjFn / ImgProjDeferFn / ImgProjLateFn) runs its weight gradient with K = U*L."""
+    (ImgProjFn / ImgProjDeferFn / ImgProjLateFn) runs its weight gradient with K = U*L.
+    lens: the region counts, as in ImgFuseFn (fp32 P0 only): no padded row of P0 is read, the padded rows of dP are exact zeros."""
 
     @staticmethod
-    def forward(ctx, P0, bi, q, keep, seed, p_drop, N, L, link=None, grp=None):
+    def forward(ctx, P0, bi, q, keep, seed, p_drop, N, L, link=None, grp=None, lens=None):
         P0, q = _c(P0), _c(q)
         O = P0.shape[1] // ops.POOL_K
         ctx.grp = grp
+        ctx.lens = lens
+        if lens is not None and P0.dtype != torch.float32:
+            raise ops._l.VqfError("MfbFuseFn: region counts (lens) are fp32 only, got a %s projection" % P0.dtype)
         if grp is not None:
             if P0.dtype != torch.float32:
                 raise ops._l.VqfError("MfbFuseFn: shared images (grp) are fp32 only, got a %s projection" % P0.dtype)
             U = P0.shape[0] // L
             Y, norm, inv = ops.mfb_fuse_fwd_grouped(P0, q, grp[0], N, U, L, O, keep=keep, seed=seed, p_drop=p_drop, pbias=bi,
-                                                    normalise=link is None)
+                                                    normalise=link is None, lens=lens)
             ctx.link = _arm_link(link, inv, L, None)
             ctx.save_for_backward(P0, bi, q, Y, norm, inv, keep)
             ctx.seed, ctx.p_drop, ctx.dims = seed, p_drop, (N, L, O)
             return Y
         rb = [] if (link is not None and P0.dtype == torch.bfloat16) else None
         Y, norm, inv, _ = ops.mfb_fuse_fwd(P0, q, N, L, O, keep=keep, seed=seed, p_drop=p_drop, pbias=bi,
-                                           normalise=link is None, r_bf16=rb)
+                                           normalise=link is None, r_bf16=rb, lens=lens)
         ctx.link = _arm_link(link, inv, L, rb)
         ctx.save_for_backward(P0, bi, q, Y, norm, inv, keep)
         ctx.seed, ctx.p_drop, ctx.dims = seed, p_drop, (N, L, O)
@@ -553,12 +572,12 @@ class MfbFuseFn(torch.autograd.Function):
         if ctx.grp is not None:
             dP, dq, dbi = ops.mfb_fuse_bwd_grouped(_c(dY), Y, norm, inv, P0, q, ctx.grp[0], ctx.grp[1], ctx.grp[2], N,
                                                    P0.shape[0] // L, L, O, keep=keep, seed=ctx.seed, p_drop=ctx.p_drop,
-                                                   want_dbias=True, pbias=bi, lin=_take_lin(ctx.link))
-            return dP, dbi, dq, None, None, None, None, None, None, None
+                                                   want_dbias=True, pbias=bi, lin=_take_lin(ctx.link), lens=ctx.lens)
+            return dP, dbi, dq, None, None, None, None, None, None, None, None
         dP, dq, _, dbi = ops.mfb_fuse_bwd(_c(dY), Y, norm, inv, P0, q, N, L, O, keep=keep, seed=ctx.seed,
                                           p_drop=ctx.p_drop, want_dbias=True, pbias=bi, lin=_take_lin(ctx.link),
-                                          dp_bf16=P0.dtype == torch.bfloat16)
-        return dP, dbi, dq, None, None, None, None, None, None, None
+                                          dp_bf16=P0.dtype == torch.bfloat16, lens=ctx.lens)
+        return dP, dbi, dq, None, None, None, None, None, None, None, None
 
 
 class _Fork:
@@ -1196,24 +1215,26 @@ class LstmBatchFn(torch.autograd.Function):
 
 class UnitPoolFn(torch.autograd.Function):
     """pooled[n, g*C + c] = sum_s feat[n, s, c] for g < G: the glimpse sums under mfb.py:84,118's
-    singleton-axis softmax (weights == 1), without the attention MLP in front (MFB's `pruned` mode)."""
+    singleton-axis softmax (weights == 1), without the attention MLP in front (MFB's `pruned` mode).
+    lens (None, or (N,) int32; fp32 feat): the sum runs over s < lens[n] (weight 0 beyond)."""
 
     @staticmethod
-    def forward(ctx, feat, G):
+    def forward(ctx, feat, G, lens=None):
         feat = _c(feat)
         N, S, C = feat.shape
         logits = torch.zeros((N * S, G), dtype=torch.float32, device=feat.device)     # ignored under unit weights
-        wts, pooled = ops.glimpse_pool_fwd(feat, logits, True)
+        wts, pooled = ops.glimpse_pool_fwd(feat, logits, True, lens=lens)
         ctx.save_for_backward(feat, wts)
+        ctx.lens = lens
         return pooled
 
     @staticmethod
     def backward(ctx, dpooled):
         feat, wts = ctx.saved_tensors
         if not ctx.needs_input_grad[0]:
-            return None, None
-        _, dfeat = ops.glimpse_pool_bwd(_c(dpooled), feat, wts, True, True)
-        return dfeat, None
+            return None, None, None
+        _, dfeat = ops.glimpse_pool_bwd(_c(dpooled), feat, wts, True, True, lens=ctx.lens)
+        return dfeat, None, None
 
 
 class DeadParamsFn(torch.autograd.Function):

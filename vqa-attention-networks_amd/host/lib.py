@@ -147,6 +147,16 @@ SIGNATURES = {
     "vqf_mfb_fuse_bwd_grouped_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "vqf_mfb_fuse_bwd_grouped": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_u64, ctypes.c_float,
                                        c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_p, c_sz, c_p]),
+    # the region-count forms of the image fusion (MFB / MHBCoAtt forward((img, img_length), ...)): lens device int32 pointers (c_p)
+    "vqf_mfb_fuse_fwd_len": (c_i, [c_f, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_f, c_f, c_p]),
+    "vqf_mfb_fuse_bwd_len": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float,
+                                   c_i, c_i, c_i, c_f, c_f, c_f, c_p, c_sz, c_p]),
+    "vqf_mfb_fuse_fwd_grouped_len": (c_i, [c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_f,
+                                           c_p]),
+    "vqf_mfb_fuse_bwd_grouped_len": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_u64, ctypes.c_float,
+                                           c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_p, c_sz, c_p]),
+    "vqf_glimpse_pool_fwd_grouped_len": (c_i, [c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
+    "vqf_glimpse_pool_bwd_grouped_len": (c_i, [c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
     "vqf_lstm_seq_supported": (c_i, [c_i, c_i]),
     "vqf_lstm_seq_ws_bytes": (c_sz, [c_i, c_i]),
     "vqf_lstm_seq_fwd": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_p, c_sz, c_p]),

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .grouping import _group_index, check_img_index
+from .grouping import _group_index, _region_lens, check_img_index, check_img_length
 from .functions import (LinearFn, AttHeadFn, ImgFuseFn, ImgProjFn, ImgProjLateFn, ImgProjDeferFn, MfbFuseFn, FinalMfbFn,
                         LstmBatchFn, UnitPoolFn, DeadParamsFn, NormLink, img_project, embed_tanh, lstm_out_dropout)
 
@@ -53,6 +53,33 @@ def shared_image_groups(who, img_features, questions, img_index, gemm_dtype):
         raise VqfError("%s: img_index needs L <= 1024 regions and a channel count that is a multiple of 4 (got U=%d, N=%d, L=%d, "
                        "D=%d)" % (who, U, N, L, D))
     return _group_index(img_index, U)
+
+
+def image_region_lens(who, img_features, questions, img_length, grp, gemm_dtype):
+    """forward((img, img_length), ...): the refusals of the region-count call and the device-side counts.  img_length: one count per
+    image -- (N,), or (U,) with img_index -- int64 / int32 on the questions' device -> what ImgFuseFn / MfbFuseFn / AttHeadFn take
+    as `lens` (grouping._region_lens: clamped to [1, L] on the device, never read on the host)."""
+    from .lib import VqfError
+    if gemm_dtype != "fp32" or img_features.dtype != torch.float32:
+        raise VqfError("%s: img_length is fp32 only (the region-count fusion kernels have no bf16 form); got gemm_dtype=%r and %s "
+                       "img_features" % (who, gemm_dtype, img_features.dtype))
+    check_img_length(who, img_length, img_features.shape[0], questions.device)
+    if img_features.shape[1] > 1024:
+        raise VqfError("%s: img_length needs L <= 1024 regions (got L=%d)" % (who, img_features.shape[1]))
+    return _region_lens(img_length, img_features.shape[1], None if grp is None else grp[0])
+
+
+def split_region_features(who, img_features):
+    """The region-count call form: img_features given as the pair (img (N, L, D), img_length (N,)) -> (img, img_length); a plain
+    tensor -> (img, None).  forward() keeps its parameter list (the positional call forms are pinned); the counts travel with
+    the features they describe, as data_loader.pad_region_features returns them."""
+    from .lib import VqfError
+    if isinstance(img_features, (tuple, list)):
+        if len(img_features) != 2 or not torch.is_tensor(img_features[0]):
+            raise VqfError("%s: img_features must be a tensor or the pair (img (N, L, D), img_length (N,)), got a %s of %d"
+                           % (who, type(img_features).__name__, len(img_features)))
+        return img_features[0], img_features[1]
+    return img_features, None
 
 
 _warned = set()
@@ -237,12 +264,13 @@ class MFB(nn.Module):
         """Test hook: explicit uint8 keep-masks 'm1' (N*L,5000), 'm2' (N,5000) instead of Philox."""
         self._seeds.keep = masks
 
-    def _forward_pruned(self, img_features, ques_feature, keep, grp=None):
+    def _forward_pruned(self, img_features, ques_feature, keep, grp=None, lens=None):
         """The live part of the reference graph when both softmaxes are over a singleton axis."""
         pm = self.dropout_m.p
         qa = UnitPoolFn.apply(ques_feature, 2)                             # (N, 2H)   mfb.py:85-89 with weights 1
         self._seeds.next(self.training, pm)                                # the regions' dropout draw (unused, keeps the stream)
-        va = UnitPoolFn.apply(img_features, 2)                             # (N, 2D)   mfb.py:119-123 with weights 1
+        # (N, 2D)   mfb.py:119-123 with weights 1 (img_length: on the real regions; per image when the images are shared)
+        va = UnitPoolFn.apply(img_features, 2, lens if grp is None or lens is None else lens[1])
         if grp is not None:                                                # per image (U, 2D), one row block per question
             va = ops.row_block_gather(va, grp[0])
         seed, p = self._seeds.next(self.training, pm)
@@ -260,9 +288,20 @@ class MFB(nn.Module):
     def forward(self, img_features, questions, is_training=True, img_index=None):
         """img_index (None, or (N,) int64 / int32 on the questions' device): img_features holds the U images the batch's N
         questions share, and question n looks at image img_index[n] (any order, repeats, images without a question).  The
-        result is this model on img_features[img_index]; img_conv1d and its weight gradient run once per image."""
+        result is this model on img_features[img_index]; img_conv1d and its weight gradient run once per image.
+        Region counts: img_features may be the PAIR (img, img_length) -- what data_loader.pad_region_features returns, moved to
+        the GPU -- with img_length an int64 / int32 tensor on the questions' device, one count per image ((N,), or (U,) with
+        img_index; fp32 only): img is right-padded to L regions (detector boxes) and image i has img_length[i] real ones, clamped
+        to [1, L] on the device.  A plain tensor, or (img, None), is the existing path.
+        The result is this model on the first img_length[i] regions of each image: the fusion's L2
+        norm, the co-attention softmax (under unit_softmax: the region sum) and every gradient run over the real regions, and
+        no padded row of the projection is read.  The padded rows of img_features may hold any FINITE values: img_conv1d and
+        its weight gradient still run over all L rows and the padding cancels because its dP rows are exact zeros -- a NaN or
+        Inf in a padded row would reach img_conv1d's weight gradient.  data_loader.pad_region_features builds such a batch."""
+        img_features, img_length = split_region_features("MFB", img_features)
         _image_is_data(img_features, self.gemm_dtype)
         grp = None if img_index is None else shared_image_groups("MFB", img_features, questions, img_index, self.gemm_dtype)
+        lens = None if img_length is None else image_region_lens("MFB", img_features, questions, img_length, grp, self.gemm_dtype)
         bf16_img = self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
         bf16_all = self.gemm_dtype == "bf16-all"          # also ques_proj*, img_proj*, the question-attention conv
         # a5 starts first, on the side stream: it only needs the image and its weights
@@ -284,7 +323,7 @@ class MFB(nn.Module):
         L = img_features.shape[1]
         keep = self._seeds.keep
         if self.pruned and self.unit_softmax:
-            return self._forward_pruned(img_features, ques_feature, keep, grp)
+            return self._forward_pruned(img_features, ques_feature, keep, grp, lens)
 
         # a3: question attention                                             mfb.py:73-89
         wm, bm = self._mc('ques_att_multiconv')
@@ -301,15 +340,15 @@ class MFB(nn.Module):
         link = NormLink() if (self.fold_norm and not self.multilayer) else None
         if proj is not None:
             P0 = self._side.join(*proj)
-            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, grp)
+            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, grp, lens)
         else:
             Y = ImgFuseFn.apply(img_features, self.img_conv1d.weight, self.img_conv1d.bias, qp,
-                                k1, seed, pm if k1 is not None else p, bf16_img, link, grp)
+                                k1, seed, pm if k1 is not None else p, bf16_img, link, grp, lens)
         # a7+a8: co-attention over the regions                               mfb.py:109-123
         # (with a link Y is the un-normalised R and 1/norm rides in co_att_conv1's GEMM epilogue)
         wm, bm = self._mc('co_att_multiconv')
         va = AttHeadFn.apply(Y, img_features, self.co_att_conv1.weight, self.co_att_conv1.bias, wm, bm,
-                             self.co_att_conv2.weight, self.co_att_conv2.bias, self.unit_softmax, coatt_bf16, link, False, grp)
+                             self.co_att_conv2.weight, self.co_att_conv2.bias, self.unit_softmax, coatt_bf16, link, False, grp, lens)
         # a9: final MFB block                                                mfb.py:126-135
         seed, p = self._seeds.next(self.training, pm)
         k2 = keep.get('m2')

@@ -10,7 +10,8 @@ import torch.nn as nn
 from . import ops
 from .functions import (LinearFn, Linear2Fn, AttHeadFn, ImgFuseFn, MfbFuseFn, FinalMfbFn, LstmSeqFn, LstmBatchFn, LogSoftmaxRowsFn,
                         NormLink, embed_tanh, embed, lstm_out_dropout)
-from .mfb import _DropSeeds, _image_is_data, _SideStream, _lstm_bf16, batch_first_lstm, warn_once, shared_image_groups
+from .mfb import (_DropSeeds, _image_is_data, _SideStream, _lstm_bf16, batch_first_lstm, warn_once, shared_image_groups,
+                  image_region_lens, split_region_features)
 
 
 class MHBCoAtt(nn.Module):
@@ -52,9 +53,16 @@ class MHBCoAtt(nn.Module):
 
     def forward(self, img_features, questions, glove_matrix=None, is_training=True, img_index=None):
         """img_index: see MFB.forward -- img_features (U, L, D) are the images the N questions share; the batch-axis LSTM
-        recursion runs over the questions in the caller's order, untouched."""
+        recursion runs over the questions in the caller's order, untouched.
+        Region counts: see MFB.forward -- img_features may be the pair (img, img_length), one count per image ((N,), or (U,) with
+        img_index; fp32 only); the fusion's norm and
+        the co-attention softmax run over each image's real regions.  The padded rows of img_features must be FINITE: the
+        projection and its weight gradient still run over them, and they cancel only because their dP rows are exact zeros."""
+        img_features, img_length = split_region_features("MHBCoAtt", img_features)
         _image_is_data(img_features, self.gemm_dtype)
         grp = None if img_index is None else shared_image_groups("MHBCoAtt", img_features, questions, img_index, self.gemm_dtype)
+        lens = None if img_length is None else image_region_lens("MHBCoAtt", img_features, questions, img_length, grp,
+                                                                 self.gemm_dtype)
         N, L, D = img_features.shape
         if grp is not None:
             N = questions.shape[0]
@@ -104,12 +112,12 @@ class MHBCoAtt(nn.Module):
         link = NormLink() if self.fold_norm else None
         if proj is not None:
             P0 = self._side.join(*proj)
-            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, grp)
+            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, grp, lens)
         else:
             Y = ImgFuseFn.apply(img_features, self.img_conv1d.weight, self.img_conv1d.bias, qp,
-                                k1, seed, pm if k1 is not None else p, bf16_img, link, grp)
+                                k1, seed, pm if k1 is not None else p, bf16_img, link, grp, lens)
         va = AttHeadFn.apply(Y, img_features, self.co_att_conv1.weight, self.co_att_conv1.bias, None, None,
-                             self.co_att_conv2.weight, self.co_att_conv2.bias, False, coatt_bf16, link, False, grp)
+                             self.co_att_conv2.weight, self.co_att_conv2.bias, False, coatt_bf16, link, False, grp, lens)
         ys = []
         for tag, qpj, ipj in (('m2', self.ques_proj2, self.img_proj2), ('m3', self.ques_proj3, self.img_proj3)):
             seed, p = self._seeds.next(self.training, pm)

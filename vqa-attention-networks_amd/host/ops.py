@@ -908,8 +908,9 @@ def _pool_grouped_dims(name, feat, G, N):
     return U, S, C
 
 
-def glimpse_pool_fwd_grouped(feat, logits, idx):
-    """feat (U, S, C), logits (N*S, G), idx (N) int32 -> wts (N, G, S), pooled (N, G*C): question n pools the rows of image idx[n]."""
+def glimpse_pool_fwd_grouped(feat, logits, idx, lens=None):
+    """feat (U, S, C), logits (N*S, G), idx (N) int32 -> wts (N, G, S), pooled (N, G*C): question n pools the rows of image idx[n].
+    lens (N) int32 per QUESTION: the softmax runs over the first lens[n] rows, the weights beyond are exact zeros."""
     _chk(logits)
     N, G = idx.shape[0], logits.shape[1]
     U, S, C = _pool_grouped_dims("glimpse_pool_fwd_grouped", feat, G, N)
@@ -918,12 +919,17 @@ def glimpse_pool_fwd_grouped(feat, logits, idx):
         raise _l.VqfError("glimpse_pool_fwd_grouped: logits must be (N*S, G)")
     wts = torch.empty((N, G, S), dtype=torch.float32, device=feat.device)
     pooled = torch.empty((N, G * C), dtype=torch.float32, device=feat.device)
+    if lens is not None:
+        _chk_lens(lens, N, "glimpse_pool_fwd_grouped")
+        _l.check(_lib().vqf_glimpse_pool_fwd_grouped_len(_ptr(feat), _ptr(logits), _ptr(idx), _ptr(lens), N, U, S, C, G, _ptr(wts),
+                                                         _ptr(pooled), _stream()), "vqf_glimpse_pool_fwd_grouped_len")
+        return wts, pooled
     _l.check(_lib().vqf_glimpse_pool_fwd_grouped(_ptr(feat), _ptr(logits), _ptr(idx), N, U, S, C, G, _ptr(wts), _ptr(pooled),
                                                  _stream()), "vqf_glimpse_pool_fwd_grouped")
     return wts, pooled
 
 
-def glimpse_pool_bwd_grouped(dpooled, feat, wts, idx, order, grp_off, want_dfeat, dwts=None):
+def glimpse_pool_bwd_grouped(dpooled, feat, wts, idx, order, grp_off, want_dfeat, dwts=None, lens=None):
     """dpooled (N, G*C), feat (U, S, C), wts (N, G, S) -> (dlogits (N*S, G), dfeat (U, S, C) or None): dfeat[u] sums the questions
     of image u in `order` (fixed summation order; zero rows for an image without a question)."""
     _chk(dpooled, wts, dwts)
@@ -934,6 +940,12 @@ def glimpse_pool_bwd_grouped(dpooled, feat, wts, idx, order, grp_off, want_dfeat
         raise _l.VqfError("glimpse_pool_bwd_grouped: dpooled must be (N, G*C), wts and dwts (N, G, S)")
     dlogits = torch.empty((N * S, G), dtype=torch.float32, device=feat.device)
     dfeat = torch.empty_like(feat) if want_dfeat else None
+    if lens is not None:                         # (N) per question: dlogits of the positions >= lens[n] are exact zeros
+        _chk_lens(lens, N, "glimpse_pool_bwd_grouped")
+        _l.check(_lib().vqf_glimpse_pool_bwd_grouped_len(_ptr(dpooled), _ptr(dwts), _ptr(feat), _ptr(wts), _ptr(idx), _ptr(order),
+                                                         _ptr(grp_off), _ptr(lens), N, U, S, C, G, _ptr(dlogits), _ptr(dfeat),
+                                                         _stream()), "vqf_glimpse_pool_bwd_grouped_len")
+        return dlogits, dfeat
     _l.check(_lib().vqf_glimpse_pool_bwd_grouped(_ptr(dpooled), _ptr(dwts), _ptr(feat), _ptr(wts), _ptr(idx), _ptr(order),
                                                  _ptr(grp_off), N, U, S, C, G, _ptr(dlogits), _ptr(dfeat), _stream()),
              "vqf_glimpse_pool_bwd_grouped")
@@ -1017,15 +1029,21 @@ def _keep_ptr(keep):
 
 
 def mfb_fuse_fwd(P, q, N, L, O, keep=None, seed=0, p_drop=0.0, cascade=None, want_zdrop=False, pbias=None,
-                 normalise=True, r_bf16=None):
+                 normalise=True, r_bf16=None, lens=None):
     """-> (Y normalised (N*L,O), norm (N), inv (N), zdrop or None).  pbias: projection bias added on load.
     P may be bf16 (written by gemm_bf16(out_bf16=True)).  normalise=False: the first output is R, the signed square roots
     WITHOUT the per-sample 1/norm (no vqf_scale_rows pass: the consumer applies inv in its GEMM epilogue).
     r_bf16 (bf16 P, normalise=False only): a list; it receives a (N*L, O rounded up to 32) bf16 copy of R with zero pad columns,
-    written by the same launch (the operand of the consumer's bf16 GEMM)."""
+    written by the same launch (the operand of the consumer's bf16 GEMM).
+    lens (N) int32 (fp32 P, no cascade / zdrop): region counts -- sample n has lens[n] real rows (clamped to [1, L] in the kernel);
+    the padded rows of P are not read, their rows of Y are exact zeros and norm runs over the real rows."""
     (_chk_bf16 if P.dtype == torch.bfloat16 else _chk)(P)
     _chk(q, cascade, pbias)
     dev = P.device
+    if lens is not None:
+        _chk_lens(lens, N, "mfb_fuse_fwd")
+        if P.dtype != torch.float32 or cascade is not None or want_zdrop or r_bf16 is not None:
+            raise _l.VqfError("mfb_fuse_fwd: lens takes an fp32 P without cascade / zdrop / r_bf16")
     R = torch.empty((N * L, O), dtype=torch.float32, device=dev)
     rowssq = torch.empty(N * L * 4, dtype=torch.float32, device=dev)       # four partial sums per row (one per wave)
     zdrop = torch.empty_like(P) if want_zdrop else None
@@ -1041,6 +1059,9 @@ def mfb_fuse_fwd(P, q, N, L, O, keep=None, seed=0, p_drop=0.0, cascade=None, wan
         else:
             _l.check(_lib().vqf_mfb_fuse_fwd_pbf16(_ptr(P), _ptr(pbias), _ptr(q), _keep_ptr(keep), int(seed), float(p_drop),
                                                    N, L, O, _ptr(R), _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_pbf16")
+    elif lens is not None:
+        _l.check(_lib().vqf_mfb_fuse_fwd_len(_ptr(P), _ptr(pbias), _ptr(q), _ptr(lens), _keep_ptr(keep), int(seed), float(p_drop),
+                                             N, L, O, _ptr(R), _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_len")
     else:
         _l.check(_lib().vqf_mfb_fuse_fwd(_ptr(P), _ptr(pbias), _ptr(q), _ptr(cascade), _keep_ptr(keep), int(seed),
                                          float(p_drop), N, L, O, _ptr(R), _ptr(rowssq), _ptr(zdrop), _stream()),
@@ -1055,13 +1076,19 @@ def mfb_fuse_fwd(P, q, N, L, O, keep=None, seed=0, p_drop=0.0, cascade=None, wan
 
 
 def mfb_fuse_bwd(dY, Y, norm, inv, P, q, N, L, O, keep=None, seed=0, p_drop=0.0, cascade=None,
-                 want_dbias=False, dzdrop=None, pbias=None, dp_bf16=False, lin=None):
+                 want_dbias=False, dzdrop=None, pbias=None, dp_bf16=False, lin=None, lens=None):
     """-> (dP (N*L,5O) fp32 | bf16, dq (N,5O), dcascade or None, dbiasP or None).
     lin = (dlogits, lin) of the consumer's attention head: the UN-NORMALISED formulation -- Y is R (mfb_fuse_fwd(normalise=
     False)), dY is dYs = dY / norm, and sum(R * dYs) per sample comes from the head's (N*L, G) tensors instead of a
-    rowdot pass over the (N*L, O) ones (vqf_l2_norm_bwd_coef_lin)."""
+    rowdot pass over the (N*L, O) ones (vqf_l2_norm_bwd_coef_lin).
+    lens (N) int32 (fp32, no cascade / dzdrop), with Y from mfb_fuse_fwd(lens=lens): dY / Y / P are not read on padded rows, whose
+    dP rows are exact zeros; dq and dbiasP sum the real rows."""
     (_chk_bf16 if P.dtype == torch.bfloat16 else _chk)(P)
     _chk(dY, Y, norm, inv, q, cascade, dzdrop, pbias)
+    if lens is not None:
+        _chk_lens(lens, N, "mfb_fuse_bwd")
+        if P.dtype != torch.float32 or dp_bf16 or cascade is not None or dzdrop is not None:
+            raise _l.VqfError("mfb_fuse_bwd: lens takes an fp32 P / dP without cascade / dzdrop")
     if P.dtype == torch.bfloat16 and not dp_bf16:
         raise _l.VqfError("mfb_fuse_bwd: a bf16 P comes with a bf16 dP")
     dev = P.device
@@ -1098,6 +1125,11 @@ def mfb_fuse_bwd(dY, Y, norm, inv, P, q, N, L, O, keep=None, seed=0, p_drop=0.0,
                  "vqf_mfb_fuse_bwd_bf16dp")
         return dP, dq, None, db
     dP = torch.empty_like(P)
+    if lens is not None:
+        _l.check(_lib().vqf_mfb_fuse_bwd_len(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
+                                             _ptr(lens), _keep_ptr(keep), int(seed), float(p_drop), N, L, O, _ptr(dP), _ptr(dq),
+                                             _ptr(db), _ptr(ws), ws.numel(), _stream()), "vqf_mfb_fuse_bwd_len")
+        return dP, dq, None, db
     dc = torch.empty_like(P) if cascade is not None else None
     _l.check(_lib().vqf_mfb_fuse_bwd(_ptr(dY), _ptr(dzdrop), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
                                      _ptr(cascade), _keep_ptr(keep), int(seed), float(p_drop), N, L, O,
@@ -1121,17 +1153,35 @@ def _fuse_grouped_operands(name, P, q, N, U, L, O, pbias):
                           % (name, N, U, L, O))
 
 
-def mfb_fuse_fwd_grouped(P, q, idx, N, U, L, O, keep=None, seed=0, p_drop=0.0, pbias=None, normalise=True):
+def _chk_lens_grouped(name, lens, N, U):
+    """lens of the grouped region-count forms: None, or (lens_q (N,), lens_u (U,)), contiguous int32 GPU tensors"""
+    if lens is None:
+        return None, None
+    if not isinstance(lens, (tuple, list)) or len(lens) != 2:
+        raise _l.VqfError(name + ": lens must be the pair (lens_q (N,), lens_u (U,))")
+    _chk_lens(lens[0], N, name)
+    _chk_lens(lens[1], U, name)
+    return lens[0], lens[1]
+
+
+def mfb_fuse_fwd_grouped(P, q, idx, N, U, L, O, keep=None, seed=0, p_drop=0.0, pbias=None, normalise=True, lens=None):
     """The image fusion of N questions over U shared images: P (U*L, 5*O) fp32, q (N, 5*O), idx (N) int32 (question n reads the
     rows of image idx[n], clamped in the kernel); keep (N*L, 5*O) / the Philox draw stay per question
-    -> (Y (N*L, O), norm (N), inv (N)) as mfb_fuse_fwd on P[idx] would give them, without that tensor."""
+    -> (Y (N*L, O), norm (N), inv (N)) as mfb_fuse_fwd on P[idx] would give them, without that tensor.
+    lens = (lens_q (N,), lens_u (U,)) int32: region counts per image and, gathered, per question (mfb_fuse_fwd's lens)."""
     _fuse_grouped_operands("mfb_fuse_fwd_grouped", P, q, N, U, L, O, pbias)
     _chk_group("mfb_fuse_fwd_grouped", N, U, idx=idx)
+    lens_q, lens_u = _chk_lens_grouped("mfb_fuse_fwd_grouped", lens, N, U)
     dev = P.device
     R = torch.empty((N * L, O), dtype=torch.float32, device=dev)
     rowssq = torch.empty(N * L * 4, dtype=torch.float32, device=dev)
-    _l.check(_lib().vqf_mfb_fuse_fwd_grouped(_ptr(P), _ptr(pbias), _ptr(q), _ptr(idx), _keep_ptr(keep), int(seed), float(p_drop),
-                                             N, U, L, O, _ptr(R), _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_grouped")
+    if lens_q is not None:
+        _l.check(_lib().vqf_mfb_fuse_fwd_grouped_len(_ptr(P), _ptr(pbias), _ptr(q), _ptr(idx), _ptr(lens_q), _ptr(lens_u),
+                                                     _keep_ptr(keep), int(seed), float(p_drop), N, U, L, O, _ptr(R), _ptr(rowssq),
+                                                     _stream()), "vqf_mfb_fuse_fwd_grouped_len")
+    else:
+        _l.check(_lib().vqf_mfb_fuse_fwd_grouped(_ptr(P), _ptr(pbias), _ptr(q), _ptr(idx), _keep_ptr(keep), int(seed), float(p_drop),
+                                                 N, U, L, O, _ptr(R), _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_grouped")
     norm = torch.empty(N, dtype=torch.float32, device=dev)
     inv = torch.empty(N, dtype=torch.float32, device=dev)
     _l.check(_lib().vqf_l2_group_norm(_ptr(rowssq), N, 4 * L, _ptr(norm), _ptr(inv), _stream()), "vqf_l2_group_norm")
@@ -1141,11 +1191,13 @@ def mfb_fuse_fwd_grouped(P, q, idx, N, U, L, O, keep=None, seed=0, p_drop=0.0, p
 
 
 def mfb_fuse_bwd_grouped(dY, Y, norm, inv, P, q, idx, order, grp_off, N, U, L, O, keep=None, seed=0, p_drop=0.0,
-                         want_dbias=False, pbias=None, lin=None):
+                         want_dbias=False, pbias=None, lin=None, lens=None):
     """-> (dP (U*L, 5*O): the sum over each image's questions, added in `order` (zero rows for an image without a question),
-    dq (N, 5*O), dbiasP or None).  lin as in mfb_fuse_bwd.  No (N*L, 5*O) tensor is allocated."""
+    dq (N, 5*O), dbiasP or None).  lin as in mfb_fuse_bwd.  No (N*L, 5*O) tensor is allocated.
+    lens = (lens_q, lens_u) as in mfb_fuse_fwd_grouped: the dP rows beyond an image's count are exact zeros."""
     _fuse_grouped_operands("mfb_fuse_bwd_grouped", P, q, N, U, L, O, pbias)
     _chk_group("mfb_fuse_bwd_grouped", N, U, idx=idx, order=order, grp_off=grp_off)
+    lens_q, lens_u = _chk_lens_grouped("mfb_fuse_bwd_grouped", lens, N, U)
     _chk(dY, Y, norm, inv)
     if tuple(dY.shape) != (N * L, O) or tuple(Y.shape) != (N * L, O):
         raise _l.VqfError("mfb_fuse_bwd_grouped: dY and Y must be (N*L, O)")
@@ -1168,6 +1220,12 @@ def mfb_fuse_bwd_grouped(dY, Y, norm, inv, P, q, idx, order, grp_off, N, U, L, O
     dq = torch.empty((N, POOL_K * O), dtype=torch.float32, device=dev)
     db = torch.empty(POOL_K * O, dtype=torch.float32, device=dev) if want_dbias else None
     ws = workspace(dev, _lib().vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O))
+    if lens_q is not None:
+        _l.check(_lib().vqf_mfb_fuse_bwd_grouped_len(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
+                                                     _ptr(idx), _ptr(order), _ptr(grp_off), _ptr(lens_q), _ptr(lens_u),
+                                                     _keep_ptr(keep), int(seed), float(p_drop), N, U, L, O, _ptr(dP), _ptr(dq),
+                                                     _ptr(db), _ptr(ws), ws.numel(), _stream()), "vqf_mfb_fuse_bwd_grouped_len")
+        return dP, dq, db
     _l.check(_lib().vqf_mfb_fuse_bwd_grouped(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
                                              _ptr(idx), _ptr(order), _ptr(grp_off), _keep_ptr(keep), int(seed), float(p_drop),
                                              N, U, L, O, _ptr(dP), _ptr(dq), _ptr(db), _ptr(ws), ws.numel(), _stream()),
