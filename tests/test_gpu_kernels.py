@@ -141,6 +141,31 @@ def test_gemm_unaligned_views(ops):
     assert _rel(out, A @ B.t()) <= 1e-5
 
 
+def test_gemm_row_strided_views(ops):
+    """the views themselves: lda = ldb = K + 3 with the base one float off 16 bytes, NaN in every float of the buffers outside the
+    views; the output a view with ldc = N + 5 in a buffer of 7.0 that must keep its 7.0 outside the view."""
+    M, N, K = 70, 50, 45
+    A, B = _rand((M, K), 7), _rand((N, K), 8)
+
+    def view(x):
+        rows, ld = x.shape[0], K + 3
+        buf = torch.full((1 + rows * ld + 4,), float("nan"), device="cuda")
+        v = buf[1:1 + rows * ld].view(rows, ld)[:, :K]
+        v.copy_(x.float().cuda())
+        assert v.stride(0) == K + 3 and v.data_ptr() % 16 == 4
+        return v
+
+    ldc = N + 5
+    obuf = torch.full((4 + M * ldc + 4,), 7.0, device="cuda")
+    out = obuf[4:4 + M * ldc].view(M, ldc)[:, :N]
+    assert ops.gemm(view(A), view(B), out=out) is out
+    torch.cuda.synchronize()
+    got = out.clone()
+    out.fill_(7.0)
+    assert bool((obuf == 7).all())
+    assert _rel(got, A @ B.t()) <= 1e-5
+
+
 def test_batched_gemm(ops):
     Bn, M, N, K = 5, 22, 196, 64
     A, B = _rand((Bn, M, K), 9), _rand((Bn, N, K), 10)
