@@ -583,6 +583,40 @@ int vqf_hie_affinity_levels_len(const float* x1, int ldx1, int ldx_level1, const
                                 void* stream);
 int vqf_tanh_bwd_rows_len(const float* dy, const float* y, const int* lens, int N, int T, int L, float* dx, void* stream);
 
+/* Region counts for HieCoAttenLadder (forward((img, img_length), ...); host/hie_ladder.py; additions within ABI 7): the *_regions
+ * forms of the image-side passes of csrc/hie.hip.  rlens (N) int32 on the device, 4-byte aligned, non-NULL (NULL or misaligned:
+ * VQF_E_BADARG): rlens[n] = the real regions of sample n, rows l >= rlens[n] of its L are padding (the kernels clamp what they
+ * read to [0, L]; the host clamps to [1, L] before).  Each runs the kernel template of its plain form with the count test
+ * compiled in (same launch shape, same profiler slot) and gives that form's bits when every count is L.
+ *   hie_affinity_regions / hie_affinity_levels_regions  the arguments of the *_len forms plus rlens; lens (the row counts) may be
+ *       NULL.  out[.., t, l] = (t < lens[n] && l < rlens[n]) ? epi(.) : 0, a select: neither yprev nor a padded y row can leak.
+ *       A wave whose 16 columns all lie at or beyond the count loads no y row, issues no MFMA and stores zeros; no y row at or
+ *       beyond the count is read.
+ *   hie_hv_fwd_regions / hie_rank_add_regions / hie_rank_left_regions  a workgroup walks the rows l0 .. min(l1, rlens[n]) of its
+ *       chunk: nothing of a, z, C / U is read at or beyond the count; the padded `out` rows of the chunk are stored as exact
+ *       zeros (Hv feeds the logit head's weight gradient, dVh the weight-gradient product); part and colpart sum the real rows,
+ *       and a chunk wholly beyond the count writes a zero partial slab and zero column partials.  hv_fwd / rank_left: padd
+ *       (S == 1 only, as in vqf_hie_head_bwd; or NULL) -- the T-row sums are written on top of these rows.
+ *   zero_cols_len  x[r, l] = 0 for l >= rlens[(r / rows_per_sample) % N], in place, on a contiguous (rows, L) tensor with
+ *       rows % (rows_per_sample * N) == 0: (G, N, T, L) with rows_per_sample = T.  The ladder's C and dC on the batched-GEMM
+ *       route (T > 16). */
+int vqf_hie_affinity_regions(const float* x1, int ldx1, const float* y1, int ldy1, const float* x2, int ldx2, const float* y2,
+                             int ldy2, int epi, const float* yprev, const uint8_t* keep, uint64_t seed, float p_drop, const int* lens,
+                             const int* rlens, int N, int L, int E, int T, float* out, void* stream);
+int vqf_hie_affinity_levels_regions(const float* x1, int ldx1, int ldx_level1, const float* y1, int ldy1, int ldy_level1,
+                                    const float* x2, int ldx2, int ldx_level2, const float* y2, int ldy2, int ldy_level2,
+                                    int G, int epi, const float* yprev, const int* lens, const int* rlens, int N, int L, int E,
+                                    int T, float* out, void* stream);
+int vqf_hie_hv_fwd_regions(const float* a, int lda, const float* C, const float* V, int ldv, const uint8_t* keep, uint64_t seed,
+                           float p_drop, const int* rlens, int N, int L, int E, int T, float* out, int ldo, float* part, int ldp,
+                           const float* padd, int ldpa, void* stream);
+int vqf_hie_rank_add_regions(const float* a, int lda, const float* U, const float* V, int ldv, const int* rlens, int N, int L,
+                             int E, int T, float* out, int ldo, float* colpart, int ldcp, void* stream);
+int vqf_hie_rank_left_regions(const float* U, const float* V, int ldv, const float* z, int ldz, const int* rlens, int N, int L,
+                              int E, int T, float* out, int ldo, float* part, int ldp, const float* padd, int ldpa, float* colpart,
+                              int ldcp, void* stream);
+int vqf_zero_cols_len(float* x, const int* rlens, long long rows, int rows_per_sample, int N, int L, void* stream);
+
 /* Guided attention logits (HieCoAttenLadder's alternating co-attention, coatt="alternating"; csrc/hie_ladder_alt.hip; additions
  * within ABI 7).  Xh (N*S, row pitch ldx) holds G <= 3 attention steps over the same rows, step g at columns [g E, (g + 1) E);
  * gp (N, G E) the per-sample guidance rows (NULL: none, H = tanh(Xh)); w (G, E).  The hidden activation

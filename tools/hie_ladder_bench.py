@@ -1,7 +1,7 @@
 """Train step of HieCoAttenLadder (host/hie_ladder.py) at config 4's shapes: forward, CE loss, backward, the project's Adam.
 
     python tools/hie_ladder_bench.py [--batch 256] [--steps 20] [--warmup 5] [--lengths] [--coatt parallel|alternating] [--json OUT]
-                                     [--questions-per-image Q] [--repeats R] [--no-context]
+                                     [--questions-per-image Q] [--repeats R] [--no-context] [--regions MIN,MAX] [--blocks L]
 
 Prints ms / step and QA pairs / s (device events around the timed steps), the step's FLOP count from the shapes with its
 MFMA floor at 157.3 TF/s (fp32 MFMA peak of the MI355X) and the fraction reached, the library profiler's per-kernel table
@@ -15,7 +15,11 @@ tensor of the same size (the parallel mode's Hv pass: the same bytes read) and a
 img_index = arange(N) // Q shuffled with a fixed seed (Q = 1: every question its own image, through the index).  The FLOP table
 stays the per-question model's (what the step would cost without sharing).  --repeats R: R timed windows of --steps steps; the
 line reports their median and the spread (max - min), the run-to-run figure to hold differences against.  --no-context: skip
-the streaming yardsticks and the HieCoAtten step."""
+the streaming yardsticks and the HieCoAtten step.
+--regions MIN,MAX: the region-count call, forward((img, img_length), ...) with seeded counts in [MIN, MAX] (one per image, clipped
+to the run's L; MIN = MAX = L times the masked code route at full counts).  The line adds sum(counts) / (images L), the bound
+on what the image-side affinity and rank-T passes can save (their traffic goes with sum(counts)); the products and the logit
+heads stay dense, and the FLOP table is the dense step's.  --blocks L: regions per image (default 196)."""
 import argparse
 import json
 import os
@@ -107,9 +111,11 @@ def stream_yardsticks(N, L, E, reps=20):
     return {name: {"ms": ms, "bytes": b} for name, ms, b in rows}
 
 
-def timed(model, img, ids, target, steps, warmup, q_len=None, img_index=None, repeats=1):
+def timed(model, img, ids, target, steps, warmup, q_len=None, img_index=None, repeats=1, img_length=None):
     crit = vqa_amd.CrossEntropyLoss()
     opt = vqa_amd.Adam(model.parameters(), lr=1e-4)
+    if img_length is not None:
+        img = (img, img_length)
 
     def step():
         opt.zero_grad(set_to_none=True)
@@ -156,8 +162,10 @@ def main():
                     help="shared images: U = batch / Q images, img_index = arange(N) // Q shuffled (seed 2); 0: no index")
     ap.add_argument("--repeats", type=int, default=1, help="timed windows; the median and the spread (max - min) are reported")
     ap.add_argument("--no-context", action="store_true", help="skip the streaming yardsticks and the HieCoAtten step")
+    ap.add_argument("--regions", default=None, metavar="MIN,MAX", help="region counts: seeded img_length in [MIN, MAX] per image (seed 4)")
+    ap.add_argument("--blocks", type=int, default=196, metavar="L", help="regions per image")
     a = ap.parse_args()
-    N, L, D, E, T, H, O, V = a.batch, 196, 2048, 512, 14, 1024, 1000, 15881
+    N, L, D, E, T, H, O, V = a.batch, a.blocks, 2048, 512, 14, 1024, 1000, 15881
     dev = "cuda:0"
     torch.manual_seed(0)
     Q = a.questions_per_image
@@ -175,7 +183,19 @@ def main():
     q_len = None
     if a.lengths:
         q_len = torch.randint(3, T + 1, (N,), generator=torch.Generator().manual_seed(1)).to(dev)
-    ms, kern = timed(ladder, img, ids, target, a.steps, a.warmup, q_len, img_index, a.repeats)
+    img_length, share = None, None
+    if a.regions:
+        try:
+            lo, hi = (int(v) for v in a.regions.split(","))
+        except ValueError:
+            ap.error("--regions takes MIN,MAX")
+        if not 1 <= lo <= hi:
+            ap.error("--regions: 1 <= MIN <= MAX")
+        lo, hi = min(lo, L), min(hi, L)
+        img_length = torch.randint(lo, hi + 1, (U,), generator=torch.Generator().manual_seed(4)).to(dev)
+        per_q = img_length if img_index is None else img_length[img_index]
+        share = float(per_q.float().sum()) / (N * L)
+    ms, kern = timed(ladder, img, ids, target, a.steps, a.warmup, q_len, img_index, a.repeats, img_length)
     windows = list(timed.windows)
     launches = sum(n for n, _ in kern.values())
     parts, flops = (ladder_flops if a.coatt == "parallel" else ladder_alt_flops)(N, L, D, E, T, H, O)
@@ -184,6 +204,8 @@ def main():
           % (a.coatt, N, L, D, E, T, H, O, "  question lengths in [3, %d], mean %.1f" % (T, float(q_len.float().mean())) if a.lengths else ""))
     if Q:
         print("  shared images: %d questions per image, U = %d images, img_index shuffled" % (Q, U))
+    if a.regions:
+        print("  region counts in [%d, %d]: sum(counts) / (N L) = %.3f (the bound on the affinity and rank-T passes' traffic)" % (lo, hi, share))
     print("  %.3f ms/step   %.0f QA pairs/s   (median of %d windows of %d steps, spread %.3f ms; %d library launches per step)"
           % (ms, N / ms * 1e3, len(windows), a.steps, max(windows) - min(windows), launches))
     print("  %.3f TFLOP/step:" % (flops / 1e12))
@@ -204,7 +226,7 @@ def main():
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         json.dump({"coatt": a.coatt, "questions_per_image": Q, "images": U, "windows_ms": windows, "spread_ms": max(windows) - min(windows),
-                   "launches_per_step": launches, "yardsticks": yard, "lengths": bool(a.lengths), "ms_per_step": ms, "qa_per_s": N / ms * 1e3, "tflop_per_step": flops / 1e12, "floor_ms": floor_ms,
+                   "launches_per_step": launches, "regions": a.regions, "blocks": L, "counts_share": share, "yardsticks": yard, "lengths": bool(a.lengths), "ms_per_step": ms, "qa_per_s": N / ms * 1e3, "tflop_per_step": flops / 1e12, "floor_ms": floor_ms,
                    "fraction_of_floor": floor_ms / ms, "kernels": kern, "hiecoatten_ms_per_step": ms4}, open(a.json, "w"), indent=1)
 
 

@@ -67,6 +67,7 @@ enum VqfKernelId {
   KID_ROW_BLOCK_GATHER,
   KID_ROW_BLOCK_GROUP_SUM,
   KID_MFB_FUSE_BWD_IMAGE,
+  KID_ZERO_COLS,
   KID_COUNT
 };
 

@@ -43,6 +43,7 @@ struct HieArgs {
   const float* dl; const float* w; float* wpart; int ldw;   // HEAD: logit gradient (N*L), head weight (E), partial rows (S*N) of pitch ldw >= E + 4
   float* colpart; int ldcp;                          // ADD / LEFT: per-workgroup column sums of `out` (rows s*N + n, pitch ldcp) or nullptr
   int N, L, E, T, S, Lc;
+  const int* rlens;                                  // REG only: (N) region counts, rows l >= rlens[n] of a sample are padding
 };
 
 __device__ __forceinline__ void keep4v(const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep,
@@ -67,7 +68,11 @@ __device__ __forceinline__ void keep4v(const uint8_t* __restrict__ keep, uint64_
 
 // TMAX: compile-time bound of T (8, 14 or 16: the T-row accumulators are 4 TMAX registers; at 16 the HEAD mode spilled under the
 // 128-register budget of a 1024-thread workgroup)
-template <int MODE, int TMAX>
+// REG (vqf_hie_hv_fwd_regions / _rank_add_regions / _rank_left_regions): the workgroup walks the rows l0 .. min(l1, rlens[n]) of its
+// chunk -- nothing of a, z or U is read at or beyond the count, the prefetch of the next trip included -- and stores exact zeros
+// into the padded `out` rows of the chunk.  A chunk wholly beyond the count still writes its (zero) partial slab and column sums:
+// vqf_hie_slab_sum reads every slab.  The count is one uniform load per workgroup; every branch on it is workgroup-uniform.
+template <int MODE, int TMAX, bool REG = false>
 __global__ void __launch_bounds__(HT) hie_stream_kernel(const HieArgs g) {
   // The rank-T sums of this kernel may contract to fused multiply-adds (the library is built with -ffp-contract=off so that the
   // GEMM kernels and their references add in ONE stated order; these passes have no bit-level counterpart -- the batched-GEMM
@@ -83,13 +88,14 @@ __global__ void __launch_bounds__(HT) hie_stream_kernel(const HieArgs g) {
   const int E = g.E, T = g.T, L = g.L;
   const int CT = E >> 2, RS = HT / CT;
   const int n = blockIdx.y, s = blockIdx.x;
-  const int l0 = s * g.Lc, l1 = min(L, l0 + g.Lc), rows = l1 - l0;
+  const int l0 = s * g.Lc, l1 = min(L, l0 + g.Lc), rows_all = l1 - l0;
+  const int rows = REG ? max(0, min(l1, g.rlens[n]) - l0) : rows_all;      // (uniform) the real rows of this chunk
   const int tid = threadIdx.x, c4 = tid % CT, rs = tid / CT;
   float* Vs = smem;                                          // [T][E]        (RANK)
   float* Us = Vs + (RANK ? T * E : 0);                       // [T][Lc]
   float* red = smem;                                         // [TG][RS][E]: re-uses the operand images behind the main loop
-  if (rows <= 0) return;
-  if (RANK)
+  if (rows_all <= 0) return;
+  if (RANK && rows > 0)
     for (int i = tid; i < T * CT; i += HT) {
       const int t = i / CT, c = i - t * CT;
       *reinterpret_cast<f32x4*>(Vs + t * E + 4 * c) = *reinterpret_cast<const f32x4*>(g.V + (long long)(n * T + t) * g.ldv + 4 * c);
@@ -202,6 +208,9 @@ __global__ void __launch_bounds__(HT) hie_stream_kernel(const HieArgs g) {
         if (COLS) csum += o[q];
       }
   }
+  if (REG)                                                   // the padded rows of the chunk: exact zeros, nothing read
+    for (int r = rows + rs; r < rows_all; r += RS)
+      *reinterpret_cast<f32x4*>(g.out + ((long long)n * L + l0 + r) * g.ldo + 4 * c4) = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // `red` re-uses the LDS of the (T, E) / (T, Lc) operand images: nobody reads them any more behind this barrier
   __syncthreads();
@@ -296,6 +305,12 @@ __global__ void slab_sum_kernel(const float* __restrict__ part, int S, int R, in
 // lens (vqf_hie_affinity_len / vqf_hie_affinity_levels_len; N int32 row counts, null: all T): output rows t >= len[n] are written as zero whatever the
 // operands hold.  The ladder's dC needs it: (dti Vh^T + Qh dtq^T)(1 - C^2) of a padded question row is only zero while both
 // x operands are, and dC feeds dCq, dQ and dV.  One uniform load per workgroup (n = blockIdx.y), a compare per output row.
+//
+// REG (vqf_hie_affinity_regions / vqf_hie_affinity_levels_regions; rlens: N int32 column counts): output columns l >= rlens[n] are
+// written as zero -- a select behind the epilogue, so that neither yprev nor a padded y row can leak -- and dC needs that too:
+// dti . Vh[l] of a padded region is not zero by arithmetic.  A wave whose 16 columns all lie at or beyond the count (a
+// wave-uniform test: the group index is the wave's, the count the workgroup's) issues no y load and no MFMA and stores zeros;
+// the lanes of a partial group read the last real row instead of a padded one, and yprev is not read at a padded column.
 struct AffArgs {
   const float* x1; int ldx1, lvx1; const float* y1; int ldy1, lvy1;     // lv*: column offset of level g is g * lv* (unused for G = 1)
   const float* x2; int ldx2, lvx2; const float* y2; int ldy2, lvy2;
@@ -303,6 +318,7 @@ struct AffArgs {
   const uint8_t* keep; uint64_t seed; uint32_t thr; float inv_keep;     // DROP only
   int N, L, E, T;
   const int* lens;                                                      // null: every one of the T rows is real
+  const int* rlens;                                                     // REG only: (N) column counts, l >= rlens[n] is padding
 };
 
 __device__ __forceinline__ float keep1(const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep, long long idx) {
@@ -315,7 +331,7 @@ __device__ __forceinline__ float keep1(const uint8_t* __restrict__ keep, uint64_
 }
 
 // LDS holds the G x npair (16, E) X images; a wave owns 16 y rows and G accumulators
-template <int EPI, int G, bool DROP>
+template <int EPI, int G, bool DROP, bool REG = false>
 __global__ void __launch_bounds__(1024) hie_affinity_kernel(const AffArgs g) {
   extern __shared__ float smem[];
   const int E = g.E, T = g.T, L = g.L, ES = E + 4;           // + 4: the 16 rows of a b128 fragment read fall on distinct banks
@@ -337,13 +353,15 @@ __global__ void __launch_bounds__(1024) hie_affinity_kernel(const AffArgs g) {
   const int NG = (L + 15) >> 4;
   const int r = lane & 15, kq = lane >> 4;
   const int len = g.lens ? g.lens[n] : T;                               // (uniform) rows len .. T - 1 are padding: stored as zero
+  const int rlen = REG ? max(0, min(g.rlens[n], L)) : L;                // (uniform) columns rlen .. L - 1 are padding: stored as zero
   for (int grp = blockIdx.x * W + wave; grp < NG; grp += gridDim.x * W) {
     const int l = grp * 16 + r;
-    const long long row = (long long)n * L + (l < L ? l : L - 1);      // rows past L: a valid row, result not stored
+    const bool some = !REG || grp * 16 < rlen;                          // (wave-uniform) false: a group of padded columns, nothing read
+    const long long row = (long long)n * L + (l < rlen ? l : rlen - 1);  // rows past L (REG: the count): a valid row, result not stored
     f32x4 acc[G];
 #pragma unroll
     for (int lv = 0; lv < G; ++lv) acc[lv] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int p = 0; p < npair; ++p) {
+    for (int p = 0; p < (some ? npair : 0); ++p) {
       const int lvy = p ? g.lvy2 : g.lvy1;
       const float* y0 = (p ? g.y2 : g.y1) + row * (p ? g.ldy2 : g.ldy1) + 8 * kq;
       for (int k0 = 0; k0 < E; k0 += 256) {
@@ -381,6 +399,10 @@ __global__ void __launch_bounds__(1024) hie_affinity_kernel(const AffArgs g) {
           const int t = 4 * kq + j;                                    // D: rows 4 (lane / 16) + j, column lane % 16
           if (t < T) {
             const long long idx = (((long long)lv * g.N + n) * T + t) * L + l;
+            if (REG && l >= rlen) {                                    // a padded column: zero whatever yprev holds (unread)
+              g.out[idx] = 0.f;
+              continue;
+            }
             const float sc = DROP && EPI ? keep1(g.keep, g.seed, g.thr, g.inv_keep, idx) : 1.0f;
             float v = acc[lv][j];
             if (EPI == 1) {
@@ -424,7 +446,7 @@ size_t lds_bytes(int mode, int E, int T, int Lc) {
   return sizeof(float) * (ops_f > red_f ? ops_f : red_f);
 }
 
-int launch(int mode, HieArgs& g, const uint8_t* keep, uint64_t seed, float p, hipStream_t s) {
+int launch(int mode, HieArgs& g, const uint8_t* keep, uint64_t seed, float p, hipStream_t s, const int* rlens = nullptr) {
   if (!shape_ok(g.N, g.L, g.E, g.T)) return VQF_E_UNSUPPORTED;
   g.S = chunks_for(g.N, g.L);
   g.Lc = (g.L + g.S - 1) / g.S;
@@ -438,6 +460,7 @@ int launch(int mode, HieArgs& g, const uint8_t* keep, uint64_t seed, float p, hi
   g.keep = keep; g.seed = seed;
   g.thr = (keep || p == 0.f) ? 0u : drop_threshold_host(p);
   g.inv_keep = (keep || p > 0.f) ? 1.0f / (1.0f - p) : 1.0f;
+  g.rlens = rlens;
   const dim3 grid(g.S, g.N);
 #define HIE_GO(TM)                                                                                              \
   switch (mode) {                                                                                               \
@@ -446,12 +469,24 @@ int launch(int mode, HieArgs& g, const uint8_t* keep, uint64_t seed, float p, hi
     case MODE_ADD:  VQF_LAUNCH(KID_HIE_ADD, (hie_stream_kernel<MODE_ADD, TM>), grid, dim3(nt), lds, s, g); break;   \
     default:        VQF_LAUNCH(KID_HIE_LEFT, (hie_stream_kernel<MODE_LEFT, TM>), grid, dim3(nt), lds, s, g); break; \
   }
-  if (g.T <= 8) { HIE_GO(8) } else if (g.T <= 14) { HIE_GO(14) } else { HIE_GO(16) }
+#define HIE_GO_REG(TM)                                                                                                \
+  switch (mode) {                                                                                                     \
+    case MODE_FWD:  VQF_LAUNCH(KID_HIE_FWD, (hie_stream_kernel<MODE_FWD, TM, true>), grid, dim3(nt), lds, s, g); break;   \
+    case MODE_ADD:  VQF_LAUNCH(KID_HIE_ADD, (hie_stream_kernel<MODE_ADD, TM, true>), grid, dim3(nt), lds, s, g); break;   \
+    case MODE_LEFT: VQF_LAUNCH(KID_HIE_LEFT, (hie_stream_kernel<MODE_LEFT, TM, true>), grid, dim3(nt), lds, s, g); break; \
+    default: return VQF_E_BADARG;                             /* (the head pass has no region form) */                \
+  }
+  if (rlens) {
+    if (g.T <= 8) { HIE_GO_REG(8) } else if (g.T <= 14) { HIE_GO_REG(14) } else { HIE_GO_REG(16) }
+  } else if (g.T <= 8) { HIE_GO(8) } else if (g.T <= 14) { HIE_GO(14) } else { HIE_GO(16) }
+#undef HIE_GO_REG
 #undef HIE_GO
   return vqf_last_error();
 }
 
 bool rows_ok(const float* p, int ld, int E) { return p && aligned16(p) && ld >= E && (ld % 4) == 0; }
+
+bool counts_ok(const int* p) { return p && !(((uintptr_t)p) & 3); }      // rlens: non-null, 4-byte aligned
 
 bool affinity_shape_ok(int N, int L, int E, int T, int G, int pairs) {
   if (N <= 0 || N > 65535 || L <= 0 || T <= 0 || T > 16 || E <= 0 || (E % 32) || G < 1 || G > 3 || pairs < 1 || pairs > 2)
@@ -459,23 +494,23 @@ bool affinity_shape_ok(int N, int L, int E, int T, int G, int pairs) {
   return (size_t)G * pairs * 16 * (E + 4) * sizeof(float) <= 160 * 1024;
 }
 
-template <int EPI, int G, bool DROP>
+template <int EPI, int G, bool DROP, bool REG>
 int affinity_go(int kid, dim3 grid, dim3 block, int lds, hipStream_t s, const AffArgs& g) {
   static VqfDynLdsFlags lds_set;                   // (one per instantiation: the attribute belongs to the kernel function)
   if (lds > 64 * 1024) {
-    const int rc = vqf_set_dyn_lds((const void*)hie_affinity_kernel<EPI, G, DROP>, lds, lds_set);
+    const int rc = vqf_set_dyn_lds((const void*)hie_affinity_kernel<EPI, G, DROP, REG>, lds, lds_set);
     if (rc != VQF_OK) return rc;
   }
-  VQF_LAUNCH(kid, (hie_affinity_kernel<EPI, G, DROP>), grid, block, lds, s, g);
+  VQF_LAUNCH(kid, (hie_affinity_kernel<EPI, G, DROP, REG>), grid, block, lds, s, g);
   return vqf_last_error();
 }
 
-template <int G, bool DROP>
+template <int G, bool DROP, bool REG>
 int affinity_epi(int epi, int kid, dim3 grid, dim3 block, int lds, hipStream_t s, const AffArgs& g) {
   switch (epi) {
-    case 0:  return affinity_go<0, G, DROP>(kid, grid, block, lds, s, g);
-    case 1:  return affinity_go<1, G, DROP>(kid, grid, block, lds, s, g);
-    default: return affinity_go<2, G, DROP>(kid, grid, block, lds, s, g);
+    case 0:  return affinity_go<0, G, DROP, REG>(kid, grid, block, lds, s, g);
+    case 1:  return affinity_go<1, G, DROP, REG>(kid, grid, block, lds, s, g);
+    default: return affinity_go<2, G, DROP, REG>(kid, grid, block, lds, s, g);
   }
 }
 
@@ -499,11 +534,30 @@ int affinity_launch(int kid, const AffArgs& g, int G, int epi, bool drop, hipStr
   if (W > 16) W = 16;
   const int lds = G * pairs * 16 * (E + 4) * (int)sizeof(float);
   const dim3 grid(S, g.N), block(64 * W);
-  if (drop) return affinity_epi<1, true>(epi, kid, grid, block, lds, s, g);
+  if (g.rlens) {                                   // the region-count forms: the same launch shape, the REG instantiations
+    if (drop) return affinity_epi<1, true, true>(epi, kid, grid, block, lds, s, g);
+    switch (G) {
+      case 1:  return affinity_epi<1, false, true>(epi, kid, grid, block, lds, s, g);
+      case 2:  return affinity_epi<2, false, true>(epi, kid, grid, block, lds, s, g);
+      default: return affinity_epi<3, false, true>(epi, kid, grid, block, lds, s, g);
+    }
+  }
+  if (drop) return affinity_epi<1, true, false>(epi, kid, grid, block, lds, s, g);
   switch (G) {
-    case 1:  return affinity_epi<1, false>(epi, kid, grid, block, lds, s, g);
-    case 2:  return affinity_epi<2, false>(epi, kid, grid, block, lds, s, g);
-    default: return affinity_epi<3, false>(epi, kid, grid, block, lds, s, g);
+    case 1:  return affinity_epi<1, false, false>(epi, kid, grid, block, lds, s, g);
+    case 2:  return affinity_epi<2, false, false>(epi, kid, grid, block, lds, s, g);
+    default: return affinity_epi<3, false, false>(epi, kid, grid, block, lds, s, g);
+  }
+}
+
+// x[r, l] = 0 for l >= rlens[(r / rows_per_sample) % N]: the padded columns of a contiguous (G*N*T, L) tensor, in place
+__global__ void zero_cols_len_kernel(float* __restrict__ x, const int* __restrict__ rlens, long long rows, int rows_per_sample,
+                                     int N, int L) {
+  const long long total = rows * L, stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const long long r = i / L;
+    const int l = (int)(i - r * L), n = (int)((r / rows_per_sample) % N);
+    if (l >= rlens[n]) x[i] = 0.f;
   }
 }
 
@@ -579,6 +633,54 @@ int vqf_hie_rank_left(const float* U, const float* V, int ldv, const float* z, i
   return launch(MODE_LEFT, g, nullptr, 0, 0.f, (hipStream_t)stream);
 }
 
+// ---- the region-count forms of the three passes the ladder launches (rlens: N int32 row counts) ----------------------------------
+int vqf_hie_hv_fwd_regions(const float* a, int lda, const float* C, const float* V, int ldv, const uint8_t* keep, uint64_t seed,
+                           float p_drop, const int* rlens, int N, int L, int E, int T, float* out, int ldo, float* part, int ldp,
+                           const float* padd, int ldpa, void* stream) {
+  if (!counts_ok(rlens) || !C || !rows_ok(part, ldp, E) || (padd && !rows_ok(padd, ldpa, E)) || !rows_ok(a, lda, E) ||
+      !rows_ok(V, ldv, E) || !rows_ok(out, ldo, E) || p_drop < 0.f || p_drop >= 1.f)
+    return VQF_E_BADARG;
+  HieArgs g = {};
+  g.a = a; g.lda = lda; g.out = out; g.ldo = ldo; g.U = C; g.V = V; g.ldv = ldv; g.part = part; g.ldp = ldp;
+  g.padd = padd; g.ldpa = ldpa;
+  g.N = N; g.L = L; g.E = E; g.T = T;
+  return launch(MODE_FWD, g, keep, seed, p_drop, (hipStream_t)stream, rlens);
+}
+
+int vqf_hie_rank_add_regions(const float* a, int lda, const float* U, const float* V, int ldv, const int* rlens, int N, int L,
+                             int E, int T, float* out, int ldo, float* colpart, int ldcp, void* stream) {
+  if (!counts_ok(rlens) || !U || !rows_ok(a, lda, E) || !rows_ok(V, ldv, E) || !rows_ok(out, ldo, E) ||
+      (colpart && !rows_ok(colpart, ldcp, E)))
+    return VQF_E_BADARG;
+  HieArgs g = {};
+  g.a = a; g.lda = lda; g.out = out; g.ldo = ldo; g.U = U; g.V = V; g.ldv = ldv; g.colpart = colpart; g.ldcp = ldcp;
+  g.N = N; g.L = L; g.E = E; g.T = T;
+  return launch(MODE_ADD, g, nullptr, 0, 0.f, (hipStream_t)stream, rlens);
+}
+
+int vqf_hie_rank_left_regions(const float* U, const float* V, int ldv, const float* z, int ldz, const int* rlens, int N, int L,
+                              int E, int T, float* out, int ldo, float* part, int ldp, const float* padd, int ldpa, float* colpart,
+                              int ldcp, void* stream) {
+  if (!counts_ok(rlens) || !U || !rows_ok(part, ldp, E) || (padd && !rows_ok(padd, ldpa, E)) || !rows_ok(z, ldz, E) ||
+      !rows_ok(V, ldv, E) || !rows_ok(out, ldo, E) || (colpart && !rows_ok(colpart, ldcp, E)))
+    return VQF_E_BADARG;
+  HieArgs g = {};
+  g.z = z; g.ldz = ldz; g.out = out; g.ldo = ldo; g.U = U; g.V = V; g.ldv = ldv; g.part = part; g.ldp = ldp;
+  g.padd = padd; g.ldpa = ldpa; g.colpart = colpart; g.ldcp = ldcp;
+  g.N = N; g.L = L; g.E = E; g.T = T;
+  return launch(MODE_LEFT, g, nullptr, 0, 0.f, (hipStream_t)stream, rlens);
+}
+
+int vqf_zero_cols_len(float* x, const int* rlens, long long rows, int rows_per_sample, int N, int L, void* stream) {
+  if (!x || !counts_ok(rlens) || rows <= 0 || rows_per_sample <= 0 || N <= 0 || L <= 0 || rows % ((long long)rows_per_sample * N))
+    return VQF_E_BADARG;
+  long long blocks = (rows * L + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  VQF_LAUNCH(KID_ZERO_COLS, zero_cols_len_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, rlens, rows,
+             rows_per_sample, N, L);
+  return vqf_last_error();
+}
+
 int vqf_hie_affinity_supported(int N, int L, int E, int T, int pairs) { return affinity_shape_ok(N, L, E, T, 1, pairs); }
 
 int vqf_hie_affinity(const float* x1, int ldx1, const float* y1, int ldy1, const float* x2, int ldx2, const float* y2, int ldy2,
@@ -607,6 +709,19 @@ int vqf_hie_affinity_len(const float* x1, int ldx1, const float* y1, int ldy1, c
   return affinity_launch(KID_HIE_AFF, g, 1, epi, true, (hipStream_t)stream);
 }
 
+int vqf_hie_affinity_regions(const float* x1, int ldx1, const float* y1, int ldy1, const float* x2, int ldx2, const float* y2,
+                             int ldy2, int epi, const float* yprev, const uint8_t* keep, uint64_t seed, float p_drop, const int* lens,
+                             const int* rlens, int N, int L, int E, int T, float* out, void* stream) {
+  if (p_drop < 0.f || p_drop >= 1.f || !counts_ok(rlens) || (lens && (((uintptr_t)lens) & 3))) return VQF_E_BADARG;
+  AffArgs g = {};
+  g.x1 = x1; g.ldx1 = ldx1; g.y1 = y1; g.ldy1 = ldy1; g.x2 = x2; g.ldx2 = ldx2; g.y2 = y2; g.ldy2 = ldy2;
+  g.yprev = yprev; g.out = out; g.N = N; g.L = L; g.E = E; g.T = T; g.lens = lens; g.rlens = rlens;
+  g.keep = epi ? keep : nullptr; g.seed = seed;
+  g.thr = (!epi || keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
+  g.inv_keep = (epi && (keep || p_drop > 0.f)) ? 1.0f / (1.0f - p_drop) : 1.0f;
+  return affinity_launch(KID_HIE_AFF, g, 1, epi, true, (hipStream_t)stream);
+}
+
 int vqf_hie_affinity_levels_supported(int N, int L, int E, int T, int G, int pairs) { return affinity_shape_ok(N, L, E, T, G, pairs); }
 
 int vqf_hie_affinity_levels(const float* x1, int ldx1, int ldx_level1, const float* y1, int ldy1, int ldy_level1,
@@ -628,6 +743,18 @@ int vqf_hie_affinity_levels_len(const float* x1, int ldx1, int ldx_level1, const
   g.x1 = x1; g.ldx1 = ldx1; g.lvx1 = ldx_level1; g.y1 = y1; g.ldy1 = ldy1; g.lvy1 = ldy_level1;
   g.x2 = x2; g.ldx2 = ldx2; g.lvx2 = ldx_level2; g.y2 = y2; g.ldy2 = ldy2; g.lvy2 = ldy_level2;
   g.yprev = yprev; g.out = out; g.N = N; g.L = L; g.E = E; g.T = T; g.lens = lens;
+  return affinity_launch(KID_HIE_AFF_LEVELS, g, G, epi, false, (hipStream_t)stream);
+}
+
+int vqf_hie_affinity_levels_regions(const float* x1, int ldx1, int ldx_level1, const float* y1, int ldy1, int ldy_level1,
+                                    const float* x2, int ldx2, int ldx_level2, const float* y2, int ldy2, int ldy_level2,
+                                    int G, int epi, const float* yprev, const int* lens, const int* rlens, int N, int L, int E,
+                                    int T, float* out, void* stream) {
+  if (!counts_ok(rlens) || (lens && (((uintptr_t)lens) & 3))) return VQF_E_BADARG;
+  AffArgs g = {};
+  g.x1 = x1; g.ldx1 = ldx1; g.lvx1 = ldx_level1; g.y1 = y1; g.ldy1 = ldy1; g.lvy1 = ldy_level1;
+  g.x2 = x2; g.ldx2 = ldx2; g.lvx2 = ldx_level2; g.y2 = y2; g.ldy2 = ldy2; g.lvy2 = ldy_level2;
+  g.yprev = yprev; g.out = out; g.N = N; g.L = L; g.E = E; g.T = T; g.lens = lens; g.rlens = rlens;
   return affinity_launch(KID_HIE_AFF_LEVELS, g, G, epi, false, (hipStream_t)stream);
 }
 

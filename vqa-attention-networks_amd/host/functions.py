@@ -833,19 +833,23 @@ class AttPoolFn(torch.autograd.Function):
         return (dx if ctx.needs_input_grad[0] else None), dfeat, dw.view_as(w), db, None
 
 
-def _hie_hv_ti(Vh, C, Qh, drop, N, L, T, Hv, ti, stream):
+def _hie_hv_ti(Vh, C, Qh, drop, N, L, T, Hv, ti, stream, rlens=None):
     """One co-attention level's image side: Hv = dropout(tanh(Vh + C^T Qh)) and the T-row sums ti = C Vh, written into Hv
     (N*L, E) and ti (N*T, E).  Vh, Hv, Qh may be column blocks of wider buffers; C (N, T, L).  stream: ONE pass over Vh
     (csrc/hie.hip) -- one workgroup per sample writes the final sums; small batches cut a sample into S chunks whose
-    partial slabs a second launch sums.  Otherwise the batched-GEMM form."""
+    partial slabs a second launch sums.  Otherwise the batched-GEMM form.
+    rlens ((N,) int32 region counts or None; HieCoAttenLadder; C comes with zero columns at l >= rlens[n]): the streaming pass
+    stops at the count and writes zero Hv rows behind it (vqf_hie_hv_fwd_regions); the batched-GEMM form needs nothing -- its
+    padded Hv rows are finite and never used."""
     E = Vh.shape[1]
     if stream:
+        rk = {} if rlens is None else {"rlens": rlens}
         S = ops.hie_chunks(N, L)
         if S == 1:
-            ops.hie_hv_fwd(Vh, C, Qh, drop, N, L, T, Hv, ti)
+            ops.hie_hv_fwd(Vh, C, Qh, drop, N, L, T, Hv, ti, **rk)
         else:
             part = torch.empty((S, N * T, E), dtype=torch.float32, device=Vh.device)
-            ops.hie_hv_fwd(Vh, C, Qh, drop, N, L, T, Hv, part)
+            ops.hie_hv_fwd(Vh, C, Qh, drop, N, L, T, Hv, part, **rk)
             ops.hie_slab_sum(part, ti)
     else:
         tq = ops.bgemm(C, Qh.view(N, T, E), ta=True, tb=True).view(N * L, E)                # C^T Qh
@@ -853,14 +857,18 @@ def _hie_hv_ti(Vh, C, Qh, drop, N, L, T, Hv, ti, stream):
         ops.bgemm(C, Vh.view(N, L, E), ta=False, tb=True, out=ti.view(N, T, E))             # C Vh
 
 
-def _hie_dc(dti, Vh, Qh, dtq, C, drop, N, L, T, aff, out=None, lens=None):
+def _hie_dc(dti, Vh, Qh, dtq, C, drop, N, L, T, aff, out=None, lens=None, rlens=None):
     """One level's gradient of the affinity's pre-activation: (dti Vh^T + Qh dtq^T) through the backward of
     C = dropout(tanh(.)), (N, T, L).  aff: ONE pass over Vh and dtq (vqf_hie_affinity, two pairs); otherwise two batched
     products and the element-wise backward.  Reads dtq: call it before dtq is updated in place.
     lens ((N,) int32, no dropout; HieCoAttenLadder): the rows t >= lens[n] of the result are zero (the affinity's epilogue, or
-    the element-wise backward's row test: no extra pass)."""
+    the element-wise backward's row test: no extra pass).
+    rlens ((N,) int32 region counts; HieCoAttenLadder): the columns l >= rlens[n] of the result are zero -- dti . Vh[l] of a padded
+    region is not zero by arithmetic -- in the affinity's epilogue (vqf_hie_affinity_regions), or by vqf_zero_cols_len behind the
+    element-wise backward."""
     if aff:
-        return ops.hie_affinity(dti, Vh, N, L, T, x2=Qh, y2=dtq, epi=2, yprev=C, drop=drop, out=out, lens=lens)
+        rk = {} if rlens is None else {"rlens": rlens}
+        return ops.hie_affinity(dti, Vh, N, L, T, x2=Qh, y2=dtq, epi=2, yprev=C, drop=drop, out=out, lens=lens, **rk)
     E = Vh.shape[1]
     dC = ops.bgemm(dti.view(N, T, E), Vh.view(N, L, E), out=out)
     ops.bgemm(Qh.view(N, T, E), dtq.view(N, L, E), out=dC, accumulate=True)
@@ -870,6 +878,8 @@ def _hie_dc(dti, Vh, Qh, dtq, C, drop, N, L, T, aff, out=None, lens=None):
         ops.tanh_bwd_rows_len(dC, C, lens, N, T, out=dC)
     else:
         ops.tanh_dropout_bwd(dC.view(N * T, L), C.view(N * T, L), *drop, out=dC.view(N * T, L))
+    if rlens is not None:
+        ops.zero_cols_len(dC, rlens, T, N, L)
     return dC
 
 

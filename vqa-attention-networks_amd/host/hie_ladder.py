@@ -65,6 +65,27 @@ order (the questions sorted by image, a stable sort) and grp_off (U + 1 group bo
     rank-T streaming kernels the index is out of scope: only img_emb and the tanh / dropout pass are saved there.
 img_index=None is the (N, L, D) model, bit for bit: the same code path, no extra launch.
 
+Region counts.  forward((img (N, L, D), img_length (N,)), ids, ...) -- the pair data_loader.pad_region_features builds from
+detector-box features, as MFB / MHBCoAtt take it; with img_index the pair is (img (U, L, D), img_length (U,)), one count per
+image, and the per-question counts lens_q = lens_u[idx] are one gather on the device.  With rvalid[n, l] = l < len_img[n] (the
+counts clamped to [1, L] on the device, never read on the host) the result of sample n is the model on the first len_img[n]
+regions of its image alone:
+    both modes: av_i = softmax over the real regions, exact zeros elsewhere; v_i sums the real rows; every gradient row of a
+        padded region (dV, dVh, dVX) is an exact zero, so img_emb learns nothing from padding, and the padded rows of img may
+        hold any finite values without changing an output or gradient bit.
+    parallel:   C_i[t, l] = 0 and dC_i[t, l] = 0 for padded l.  dC = (dti Vh^T + Qh dtq^T)(1 - C^2) is NOT zero there by
+        arithmetic (dti . Vh[l] != 0): the affinity's epilogue masks it (vqf_hie_affinity_regions / _levels_regions).  Hq, ti,
+        dQh and dCq then sum the real regions only: the streaming passes walk min(chunk end, count) rows, read nothing behind
+        the count and store zero Hv / dVh rows there (vqf_hie_hv_fwd_regions, _rank_add_regions, _rank_left_regions), so the
+        image-side traffic of the affinity and rank-T passes goes with sum(counts) instead of N L.  T > 16 (batched GEMMs):
+        vqf_zero_cols_len on C after the tanh and on dC; nothing else on that route needs the counts but the pooling.
+    alternating: only step 2's pooling changes (vqf_glimpse_pool_fwd_len / _bwd_len; with img_index the _grouped_len forms with
+        lens_q); the guided-logits backward gives a zero dXh row for a zero dlogits row.  Host wiring, no kernel of its own.
+q_length, img_index, coatt and img_length combine freely.  Dropout masks, explicit or Philox, keep their element indices
+(row, col) over the padded (. * L, E) tensor: the masks of real elements do not depend on the counts.  The img_emb / Vh / VX
+products and the logit heads run on all rows; their padded results are never used.  A plain tensor or (img, None) is the
+model without counts, bit for bit: no extra launch, the same code route.
+
 Stages (every product and every pass over an (N*L, .) or (N*T, .) tensor runs in libvqa_fusion.so):
   * img_emb / word embedding: LinearFn + TanhDropFn, EmbedTanhFn + DropoutFn;
   * phrase level (PhraseFn): the six conv taps as one GEMM, then vqf_phrase_ngram_fwd / _bwd (csrc/hie_ladder.hip);
@@ -82,9 +103,9 @@ import torch.nn as nn
 
 from . import ops
 from .functions import _c, _hie_hv_ti, _hie_dc, _hie_bwd_bgemm, EmbedTanhFn, LinearFn, DropoutFn, TanhDropFn, DropoutBTFn, LstmBatchFn
-from .grouping import _group_index    # noqa: F401  (its home is host/grouping.py; importable from here as before)
+from .grouping import _group_index, _region_lens, check_img_length    # (_group_index: importable from here as before)
 from .lib import VqfError
-from .mfb import _DropSeeds
+from .mfb import _DropSeeds, split_region_features
 
 _NODROP = (None, 0, 0.0)
 
@@ -153,14 +174,19 @@ class LadderCoattFn(torch.autograd.Function):
     in one launch where the LDS holds them, one launch per level otherwise).
     lens ((N,) int32 or None; q0 / q1 / q2 come with zero rows at t >= lens[n]): the question-side poolings take the softmax
     over the real words, and the dC stage writes zero rows for the padded ones on every route -- with those, every other
-    stage's padded rows are zero by its own arithmetic (bias-free products of zero rows, tanh(0) = 0)."""
+    stage's padded rows are zero by its own arithmetic (bias-free products of zero rows, tanh(0) = 0).
+    rlens ((N,) int32 or None: the real regions of each sample's L; V's padded rows hold finite values that must not matter):
+    the *_regions forms of the affinity and of the streaming passes -- zero columns of C and dC, zero rows of Hv and dVh behind
+    the count, nothing read there -- and the image-side pooling over the real regions (vqf_glimpse_pool_fwd_len / _bwd_len);
+    on the batched-GEMM route vqf_zero_cols_len on C and dC, which makes every other padded term a product with an exact zero."""
 
     STREAM = True      # the T-row stages as streaming passes where supported; False: batched GEMMs + element-wise (A/B)
 
     @staticmethod
-    def forward(ctx, V, q0, q1, q2, N, L, T, lens, *w):
+    def forward(ctx, V, q0, q1, q2, N, L, T, lens, rlens, *w):
         E = V.shape[1]
         lk = {} if lens is None else {"lens": lens}
+        rk = {} if rlens is None else {"rlens": rlens}
         M, MT = N * L, N * T
         dev = V.device
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
@@ -178,19 +204,22 @@ class LadderCoattFn(torch.autograd.Function):
             ops.gemm(Q[g], wq2[g], out=CQ[:, 2 * g * E:(2 * g + 2) * E])
         stream = LadderCoattFn.STREAM and ops.hie_stream_supported(N, L, E, T)
         if stream and ops.hie_affinity_levels_supported(N, L, E, T, 3, 1):
-            C = ops.hie_affinity_levels(CQ, 2 * E, V, 0, 3, N, L, T, E, epi=1)      # (3, N, T, L), V read once
+            C = ops.hie_affinity_levels(CQ, 2 * E, V, 0, 3, N, L, T, E, epi=1, **rk)      # (3, N, T, L), V read once
         else:
             C = new(3, N, T, L)
             for g in range(3):
                 ops.bgemm(CQ[:, 2 * g * E:(2 * g + 1) * E].view(N, T, E), V.view(N, L, E), out=C[g])
             ops.tanh_dropout_fwd(C.view(3 * MT, L), None, *_NODROP, out=C.view(3 * MT, L))
+            if rlens is not None:
+                ops.zero_cols_len(C, rlens, T, N, L)
         Hv = new(M, 3 * E)
         Hq = new(3, MT, E)                                                          # ti_i first, then Hq_i in place
         for g in range(3):
             Qh_g, ti_g = CQ[:, (2 * g + 1) * E:(2 * g + 2) * E], Hq[g]
-            _hie_hv_ti(Vh[:, g * E:(g + 1) * E], C[g], Qh_g, _NODROP, N, L, T, Hv[:, g * E:(g + 1) * E], ti_g, stream)
+            _hie_hv_ti(Vh[:, g * E:(g + 1) * E], C[g], Qh_g, _NODROP, N, L, T, Hv[:, g * E:(g + 1) * E], ti_g, stream, **rk)
             ops.tanh_dropout_fwd2d(Qh_g, ti_g, *_NODROP, out=ti_g)
-        av, vcat = ops.glimpse_pool_fwd(V.view(N, L, E), ops.att_logits_fwd(Hv, wblk, zb3), False)   # (N, 3, L), (N, 3E)
+        av, vcat = ops.glimpse_pool_fwd(V.view(N, L, E), ops.att_logits_fwd(Hv, wblk, zb3), False,
+                                        **({} if rlens is None else {"lens": rlens}))                 # (N, 3, L), (N, 3E)
         aq, qo = [], []
         for g in range(3):
             a_g, q_g = ops.glimpse_pool_fwd(Q[g].view(N, T, E), ops.att_logits_fwd(Hq[g], whq[g], zb1), False, **lk)
@@ -198,7 +227,7 @@ class LadderCoattFn(torch.autograd.Function):
             qo.append(q_g)
         ctx.save_for_backward(V, q0, q1, q2, wv_cat, wq2[0], wq2[1], wq2[2], wblk, whq[0], whq[1], whq[2], Vh, CQ, C, Hv, Hq, av,
                               aq[0], aq[1], aq[2])
-        ctx.dims, ctx.stream, ctx.lens = (N, L, T, E), stream, lens
+        ctx.dims, ctx.stream, ctx.lens, ctx.rlens = (N, L, T, E), stream, lens, rlens
         ctx.set_materialize_grads(False)
         return (vcat, qo[0], qo[1], qo[2], av, aq[0], aq[1], aq[2])
 
@@ -212,8 +241,9 @@ class LadderCoattFn(torch.autograd.Function):
         zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
         Q, wq2, whq, aq = (q0, q1, q2), (wq0, wq1, wq2_), (whq0, whq1, whq2), (aq0, aq1, aq2)
         dq, daq = (dq0, dq1, dq2), (daq0, daq1, daq2)
-        stream, lens = ctx.stream, ctx.lens
+        stream, lens, rlens = ctx.stream, ctx.lens, ctx.rlens
         lk = {} if lens is None else {"lens": lens}
+        rk = {} if rlens is None else {"rlens": rlens}
         dCQ = new(MT, 6 * E)                                                        # [dCq_0 | dQh_0 | ...]
         dti = new(MT, 3 * E)
         dQ, dwhq = [], []
@@ -230,19 +260,20 @@ class LadderCoattFn(torch.autograd.Function):
             dwhq.append(dw)
         # image side: one G = 3 pooling backward over V, the block-diagonal head, Hv_i = tanh(Vh_i + tq_i)
         dvc = _c(dvcat) if dvcat is not None else zeros(N, 3 * E)
-        dlv, dV = ops.glimpse_pool_bwd(dvc, V.view(N, L, E), av, False, True, dwts=None if dav is None else _c(dav))
+        dlv, dV = ops.glimpse_pool_bwd(dvc, V.view(N, L, E), av, False, True, dwts=None if dav is None else _c(dav),
+                                       **({} if rlens is None else {"lens": rlens}))
         dV = dV.view(M, E)
         dHv, dwblk, _, _ = ops.att_logits_bwd(dlv, Hv, wblk, relu_mask=False)
         dVh = ops.tanh_dropout_bwd2d(dHv, Hv, *_NODROP, out=dHv)                   # dtq_i = d(Vh_i + tq_i); dVh_i below
         dC = new(3, N, T, L)
         if stream and ops.hie_affinity_levels_supported(N, L, E, T, 3, 2):
             ops.hie_affinity_levels(dti, E, Vh, E, 3, N, L, T, E, x2=CQ[:, E:], lvx2=2 * E, y2=dVh, lvy2=E, epi=2, yprev=C, out=dC,
-                                    **lk)
+                                    **lk, **rk)
         else:                      # per level (E = 512: three levels x two pairs exceed the LDS: one two-pair launch each)
             aff = stream and ops.hie_affinity_supported(N, L, E, T, 2)
             for g in range(3):
                 _hie_dc(dti[:, g * E:(g + 1) * E], Vh[:, g * E:(g + 1) * E], CQ[:, (2 * g + 1) * E:(2 * g + 2) * E],
-                        dVh[:, g * E:(g + 1) * E], C[g], _NODROP, N, L, T, aff, out=dC[g], **lk)
+                        dVh[:, g * E:(g + 1) * E], C[g], _NODROP, N, L, T, aff, out=dC[g], **lk, **rk)
         if stream:
             S = ops.hie_chunks(N, L)
             part, scratch = new(S, MT, E), new(M, E)
@@ -251,12 +282,12 @@ class LadderCoattFn(torch.autograd.Function):
             dcq_g, dqh_g = dCQ[:, 2 * g * E:(2 * g + 1) * E], dCQ[:, (2 * g + 1) * E:(2 * g + 2) * E]
             dti_g, dtq_g = dti[:, g * E:(g + 1) * E], dVh[:, g * E:(g + 1) * E]
             if stream:
-                ops.hie_rank_left(C[g], dti_g, dtq_g, N, L, T, scratch, part)        # C dtq (the T-row sums)
+                ops.hie_rank_left(C[g], dti_g, dtq_g, N, L, T, scratch, part, **rk)  # C dtq (the T-row sums)
                 ops.hie_slab_sum(part, dqh_g, add=dti_g)                            # dQh = dti + C dtq
-                ops.hie_rank_add(dtq_g, C[g], dti_g, N, L, T, dtq_g)                # dVh = dtq + C^T dti   (in place)
-                ops.hie_rank_left(dC[g], cq_g, V, N, L, T, scratch, part)           # dCq = dC V  (T-row sums over V)
+                ops.hie_rank_add(dtq_g, C[g], dti_g, N, L, T, dtq_g, **rk)          # dVh = dtq + C^T dti   (in place)
+                ops.hie_rank_left(dC[g], cq_g, V, N, L, T, scratch, part, **rk)     # dCq = dC V  (T-row sums over V)
                 ops.hie_slab_sum(part, dcq_g)
-                ops.hie_rank_add(dV, dC[g], cq_g, N, L, T, dV)                      # dV += dC^T Cq   (in place)
+                ops.hie_rank_add(dV, dC[g], cq_g, N, L, T, dV, **rk)                # dV += dC^T Cq   (in place)
             else:
                 _hie_bwd_bgemm(C[g], dC[g], dti_g, dtq_g, V, cq_g, dqh_g, dcq_g, dV, N, L, T, True)
         # the concatenated layers: dV += dVh [Wv_0; Wv_1; Wv_2], one weight-gradient product; per level the [Wb; Wq] pair
@@ -268,7 +299,7 @@ class LadderCoattFn(torch.autograd.Function):
             ops.gemm(blk, wq2[g], tb=True, out=dQ[g], accumulate=True)
             dwq2 = ops.gemm(blk, Q[g], ta=True, tb=True)                           # (2E, E) = [dWb; dWq]
             grads += [dwq2[:E], dwv[g * E:(g + 1) * E], dwq2[E:], dwblk[g:g + 1, g * E:(g + 1) * E].contiguous(), dwhq[g]]
-        return (dV, dQ[0], dQ[1], dQ[2], None, None, None, None, *grads)
+        return (dV, dQ[0], dQ[1], dQ[2], None, None, None, None, None, *grads)
 
 
 class LadderAltCoattFn(torch.autograd.Function):
@@ -285,15 +316,19 @@ class LadderAltCoattFn(torch.autograd.Function):
     into the (N*T, 6E) / (N*L, 3E) operands of the weight- and input-gradient products; the bias gradients are column sums of
     the (N, .) dgp.  lens ((N,) int32 or None; q0 / q1 / q2 come with zero rows at t >= lens[n]): the question-side poolings
     take the softmax over the real words and give zero dlogits for the padded ones.
+    rlens (None, or the (N,) int32 region counts of the questions' images -- lens_q = lens_u[idx] with grp): step 2's pooling runs
+    over the real regions (vqf_glimpse_pool_fwd_len / _bwd_len, the _grouped_len forms with grp); its zero dlogits rows give zero
+    dVX rows out of the guided-logits backward.  Host wiring only: no kernel of this mode knows the counts but the pooling.
     grp (None, or (idx, order, grp_off) of _group_index): V is (U*L, E), shared -- VX stays (U*L, 3E), step 2 runs on the grouped
     entry points (question n reads image idx[n]'s rows; dV and dVX sum each image's questions in `order`)."""
 
     PER_LEVEL = 11
 
     @staticmethod
-    def forward(ctx, V, q0, q1, q2, N, L, T, lens, grp, *w):
+    def forward(ctx, V, q0, q1, q2, N, L, T, lens, grp, rlens, *w):
         E = V.shape[1]
         lk = {} if lens is None else {"lens": lens}
+        rk = {} if rlens is None else {"lens": rlens}                               # the image-side pooling's counts
         U = V.shape[0] // L
         MT = N * T
         dev = V.device
@@ -322,10 +357,10 @@ class LadderAltCoattFn(torch.autograd.Function):
         for g in range(3):
             ops.gemm(s[g], img_g[g], out=gpv[:, g * E:(g + 1) * E])
         if grp is None:
-            av, vcat = ops.glimpse_pool_fwd(V.view(N, L, E), ops.guided_logits_fwd(VX, gpv, whimg, N, L), False)   # (N, 3, L), (N, 3E)
+            av, vcat = ops.glimpse_pool_fwd(V.view(N, L, E), ops.guided_logits_fwd(VX, gpv, whimg, N, L), False, **rk)   # (N, 3, L), (N, 3E)
         else:
             av, vcat = ops.glimpse_pool_fwd_grouped(V.view(U, L, E), ops.guided_logits_fwd_grouped(VX, gpv, whimg, grp[0], N, U, L),
-                                                    grp[0])
+                                                    grp[0], **rk)
         # step 3: the question under the attended image
         gpq = new(3, N, E)
         aq, qo = [], []
@@ -337,7 +372,7 @@ class LadderAltCoattFn(torch.autograd.Function):
             qo.append(q_g)
         ctx.save_for_backward(V, q0, q1, q2, wimg, whimg, VX, QX, gpv, gpq, vcat, av, *wq2, *sum_h, *img_g, *que_g, *que_h, *s, *asum,
                               *aq, *(grp or ()))
-        ctx.dims, ctx.lens = (N, L, T, E), lens
+        ctx.dims, ctx.lens, ctx.rlens = (N, L, T, E), lens, rlens
         ctx.set_materialize_grads(False)
         return (vcat, qo[0], qo[1], qo[2], av, aq[0], aq[1], aq[2])
 
@@ -356,6 +391,7 @@ class LadderAltCoattFn(torch.autograd.Function):
         Q, dq, daq = (q0, q1, q2), (dq0, dq1, dq2), (daq0, daq1, daq2)
         lens = ctx.lens
         lk = {} if lens is None else {"lens": lens}
+        rk = {} if ctx.rlens is None else {"lens": ctx.rlens}
         dQX = new(MT, 6 * E)                                                        # [dsum_0 | dque_0 | ...]
         dvc = dvcat.clone(memory_format=torch.contiguous_format) if dvcat is not None else zeros(N, 3 * E)               # dv_i: the answer MLP's plus step 3's
         dQ, g3 = [], []
@@ -373,10 +409,10 @@ class LadderAltCoattFn(torch.autograd.Function):
         # step 2: one G = 3 pooling backward over V, one G = 3 guided-logits backward over VX
         dwts = None if dav is None else _c(dav)
         if not grp:
-            dlv, dV = ops.glimpse_pool_bwd(dvc, V.view(N, L, E), av, False, True, dwts=dwts)
+            dlv, dV = ops.glimpse_pool_bwd(dvc, V.view(N, L, E), av, False, True, dwts=dwts, **rk)
             dVX, dgpv, dwhimg = ops.guided_logits_bwd(dlv, VX, gpv, whimg, N, L)
         else:                       # dV (U, L, E) and dVX (U*L, 3E): each image's questions summed in `order`
-            dlv, dV = ops.glimpse_pool_bwd_grouped(dvc, V.view(U, L, E), av, grp[0], grp[1], grp[2], True, dwts=dwts)
+            dlv, dV = ops.glimpse_pool_bwd_grouped(dvc, V.view(U, L, E), av, grp[0], grp[1], grp[2], True, dwts=dwts, **rk)
             dVX, dgpv, dwhimg = ops.guided_logits_bwd_grouped(dlv, VX, gpv, whimg, grp[1], grp[2], N, U, L)
         dV = dV.view(U * L, E)
         dbimg = ops.colsum(dgpv)
@@ -398,7 +434,7 @@ class LadderAltCoattFn(torch.autograd.Function):
             grads += [dwq2[:E], ops.colsum(dgp), dwsum_h, dwimg[blk], dbimg[blk], dimg_g, dwhimg[g:g + 1], dwq2[E:], g3[g][0],
                       g3[g][1], g3[g][2]]
         ops.multi_add([(dQ[g], dQ1[g], dQ[g]) for g in range(3)])                   # dQ_i: step 3's + the pair's + step 1's
-        return (dV, dQ[0], dQ[1], dQ[2], None, None, None, None, None, *grads)
+        return (dV, dQ[0], dQ[1], dQ[2], None, None, None, None, None, None, *grads)
 
 
 class _Coatt(nn.Module):
@@ -455,6 +491,12 @@ class HieCoAttenLadder(nn.Module):
     with sum_x, sum_h, img_x, img_g, img_h, que_x, que_g, que_h).  Anything else raises ValueError; coatt_mode holds the string.
     Inputs, outputs, masking and the dropout sites are the same in both modes.
 
+    img_features may be the pair (img, img_length): img_length (N,) -- (U,) with img_index, one count per image -- int64 or int32
+    on the questions' device, the real regions of each right-padded image (data_loader.pad_region_features).  Padded regions
+    are then masked at every level (module docstring, "Region counts"): av has exact zeros there, the padded rows of img may
+    hold any finite values.  Values are clamped to [1, L] on the device and never read on the host.  A tensor or (img, None):
+    no masking, bit for bit today's model.  A pair of another arity, counts of a wrong dtype, shape or device raise VqfError.
+
     The image features are data (img_features.requires_grad raises), fp32 on the GPU: CPU tensors and bf16 features raise
     VqfError -- there is no CPU fallback.  Dropout (rate drop_p) is active in train mode only;
     set_keep_masks() supplies explicit uint8 keep-masks for the tests, otherwise the kernels draw Philox masks."""
@@ -493,6 +535,7 @@ class HieCoAttenLadder(nn.Module):
         return DropoutFn.apply(_c(x), keep, seed, self.drop_p if keep is not None else p)
 
     def forward(self, img_features, que_features, q_length=None, img_index=None):
+        img_features, img_length = split_region_features("HieCoAttenLadder", img_features)
         if not img_features.is_cuda or not que_features.is_cuda:
             raise VqfError("HieCoAttenLadder needs GPU tensors (the HIP extension is the only path; no CPU fallback)")
         if img_features.dtype != torch.float32:
@@ -538,6 +581,12 @@ class HieCoAttenLadder(nn.Module):
                 raise VqfError("HieCoAttenLadder: q_length must be on the questions' device (%s), got %s"
                                % (que_features.device, q_length.device))
             lens = q_length.clamp(1, T).to(torch.int32).contiguous()            # O(N), on the device: nothing is read back
+        rlens = None                                                            # per QUESTION: lens_u[idx] with img_index
+        if img_length is not None:
+            check_img_length("HieCoAttenLadder", img_length, U, que_features.device)
+            rlens = _region_lens(img_length, L, None if grp is None else grp[0])   # O(N), on the device: nothing is read back
+            if grp is not None:
+                rlens = rlens[0]
         # V = drop(tanh(img_emb(img)))
         seed, p = self._seeds.next(self.training, self.drop_p)
         keep = self._seeds.keep.get("img") if self.training else None
@@ -561,10 +610,10 @@ class HieCoAttenLadder(nn.Module):
             w = [p_ for c in self.coatt for p_ in (c.sum_x.weight, c.sum_x.bias, c.sum_h.weight, c.img_x.weight, c.img_x.bias,
                                                    c.img_g.weight, c.img_h.weight, c.que_x.weight, c.que_x.bias, c.que_g.weight,
                                                    c.que_h.weight)]
-            vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderAltCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, grp, *w)
+            vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderAltCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, grp, rlens, *w)
         else:
             w = [p_ for c in self.coatt for p_ in (c.Wb.weight, c.Wv.weight, c.Wq.weight, c.whv.weight, c.whq.weight)]
-            vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, *w)
+            vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, rlens, *w)
         v0, v1, v2 = vcat[:, :E], vcat[:, E:2 * E], vcat[:, 2 * E:]
         th = lambda x: TanhDropFn.apply(x, None, None, 0, 0.0)
         lin = lambda x, m: LinearFn.apply(_c(x), m.weight, m.bias, False)

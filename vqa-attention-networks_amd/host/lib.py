@@ -105,6 +105,17 @@ SIGNATURES = {
     "vqf_hie_affinity_levels_len": (c_i, [c_f, c_i, c_i, c_f, c_i, c_i, c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_p, c_i, c_i,
                                           c_i, c_i, c_f, c_p]),
     "vqf_tanh_bwd_rows_len": (c_i, [c_f, c_f, c_p, c_i, c_i, c_i, c_f, c_p]),
+    # the region-count forms of HieCoAttenLadder's image-side passes (lens / rlens: device int32 pointers, c_p)
+    "vqf_hie_affinity_regions": (c_i, [c_f, c_i, c_f, c_i, c_f, c_i, c_f, c_i, c_i, c_f, c_p, c_u64, ctypes.c_float, c_p, c_p, c_i,
+                                       c_i, c_i, c_i, c_f, c_p]),
+    "vqf_hie_affinity_levels_regions": (c_i, [c_f, c_i, c_i, c_f, c_i, c_i, c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_p, c_p,
+                                              c_i, c_i, c_i, c_i, c_f, c_p]),
+    "vqf_hie_hv_fwd_regions": (c_i, [c_f, c_i, c_f, c_f, c_i, c_p, c_u64, ctypes.c_float, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i,
+                                     c_f, c_i, c_p]),
+    "vqf_hie_rank_add_regions": (c_i, [c_f, c_i, c_f, c_f, c_i, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_p]),
+    "vqf_hie_rank_left_regions": (c_i, [c_f, c_f, c_i, c_f, c_i, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_f, c_i, c_f, c_i,
+                                        c_p]),
+    "vqf_zero_cols_len": (c_i, [c_f, c_p, ctypes.c_longlong, c_i, c_i, c_i, c_p]),
     # the guided attention logits of HieCoAttenLadder's alternating co-attention (csrc/hie_ladder_alt.hip)
     "vqf_guided_logits_supported": (c_i, [c_i, c_i, c_i, c_i]),
     "vqf_guided_logits_fwd": (c_i, [c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_p]),

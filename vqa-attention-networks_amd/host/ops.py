@@ -610,13 +610,31 @@ def _part_ld(part, E):
     return part.stride(0)
 
 
-def hie_hv_fwd(a, C, V, drop, N, L, T, out, part):
+def _part_add(part_add, S, what):
+    """part_add of the region-count passes (one chunk per sample only): (N*T, E) rows the T-row sums are written on top of"""
+    _chk2s(part_add)
+    if part_add is not None and S != 1:
+        raise _l.VqfError(what + ": part_add needs one chunk per sample")
+    return _ptr(part_add), (part_add.stride(0) if part_add is not None else 0)
+
+
+def hie_hv_fwd(a, C, V, drop, N, L, T, out, part, rlens=None, part_add=None):
     """out = dropout(tanh(a + C^T V)); part = the sums of C[t,l] a[l,:] over l: (S, N*T, E) per-chunk slabs, or (S == 1) the
-    final (N*T, E) rows"""
+    final (N*T, E) rows.  rlens (N) int32: the rows l >= rlens[n] of a and the columns of C there are not read, those rows of
+    out are zero, part sums the real rows (every slab written); part_add (with rlens, S == 1): the sums land on top of it."""
     _chk2s(a, V, out)
     _chk_ntl(C, N, T, L)
     E = a.shape[1]
     keep, seed, p = drop
+    if rlens is not None:
+        _chk_lens(rlens, N, "hie_hv_fwd")
+        pa, ldpa = _part_add(part_add, 1 if part.dim() == 2 else part.shape[0], "hie_hv_fwd")
+        _l.check(_lib().vqf_hie_hv_fwd_regions(_ptr(a), a.stride(0), _ptr(C), _ptr(V), V.stride(0), _keep_ptr(keep), int(seed),
+                                               float(p), _ptr(rlens), N, L, E, T, _ptr(out), out.stride(0), _ptr(part),
+                                               _part_ld(part, E), pa, ldpa, _stream()), "vqf_hie_hv_fwd_regions")
+        return out
+    if part_add is not None:
+        raise _l.VqfError("hie_hv_fwd: part_add comes with rlens")
     _l.check(_lib().vqf_hie_hv_fwd(_ptr(a), a.stride(0), _ptr(C), _ptr(V), V.stride(0), _keep_ptr(keep), int(seed), float(p),
                                    N, L, E, T, _ptr(out), out.stride(0), _ptr(part), _part_ld(part, E), _stream()), "vqf_hie_hv_fwd")
     return out
@@ -649,20 +667,36 @@ def _colpart(colpart, N, L, E):
     return _ptr(colpart), colpart.stride(0)
 
 
-def hie_rank_add(a, U, V, N, L, T, out, colpart=None):
-    """colpart: (S*N, E) rows (a column block of a wider buffer) receiving each workgroup's column sums of `out`"""
+def hie_rank_add(a, U, V, N, L, T, out, colpart=None, rlens=None):
+    """colpart: (S*N, E) rows (a column block of a wider buffer) receiving each workgroup's column sums of `out`.
+    rlens (N) int32: rows l >= rlens[n] of a and columns of U there unread, those rows of out zero."""
     _chk2s(a, V, out)
     _chk_ntl(U, N, T, L)
     cp, ldcp = _colpart(colpart, N, L, a.shape[1])
+    if rlens is not None:
+        _chk_lens(rlens, N, "hie_rank_add")
+        _l.check(_lib().vqf_hie_rank_add_regions(_ptr(a), a.stride(0), _ptr(U), _ptr(V), V.stride(0), _ptr(rlens), N, L, a.shape[1],
+                                                 T, _ptr(out), out.stride(0), cp, ldcp, _stream()), "vqf_hie_rank_add_regions")
+        return out
     _l.check(_lib().vqf_hie_rank_add(_ptr(a), a.stride(0), _ptr(U), _ptr(V), V.stride(0), N, L, a.shape[1], T, _ptr(out),
                                      out.stride(0), cp, ldcp, _stream()), "vqf_hie_rank_add")
     return out
 
 
-def hie_rank_left(U, V, z, N, L, T, out, part, colpart=None):
+def hie_rank_left(U, V, z, N, L, T, out, part, colpart=None, rlens=None, part_add=None):
+    """out = U^T V; part = the sums of U[t,l] z[l,:] over l (as hie_hv_fwd's); rlens / part_add as in hie_hv_fwd (z for a)."""
     _chk2s(V, z, out)
     _chk_ntl(U, N, T, L)
     cp, ldcp = _colpart(colpart, N, L, z.shape[1])
+    if rlens is not None:
+        _chk_lens(rlens, N, "hie_rank_left")
+        pa, ldpa = _part_add(part_add, 1 if part.dim() == 2 else part.shape[0], "hie_rank_left")
+        _l.check(_lib().vqf_hie_rank_left_regions(_ptr(U), _ptr(V), V.stride(0), _ptr(z), z.stride(0), _ptr(rlens), N, L, z.shape[1],
+                                                  T, _ptr(out), out.stride(0), _ptr(part), _part_ld(part, z.shape[1]), pa, ldpa,
+                                                  cp, ldcp, _stream()), "vqf_hie_rank_left_regions")
+        return out
+    if part_add is not None:
+        raise _l.VqfError("hie_rank_left: part_add comes with rlens")
     _l.check(_lib().vqf_hie_rank_left(_ptr(U), _ptr(V), V.stride(0), _ptr(z), z.stride(0), N, L, z.shape[1], T, _ptr(out),
                                       out.stride(0), _ptr(part), _part_ld(part, z.shape[1]), cp, ldcp, _stream()),
              "vqf_hie_rank_left")
@@ -690,15 +724,23 @@ def _aff_operands(name, x1, y1, x2, y2, yprev, out, dims):
     return out, (x2.stride(0) if x2 is not None else 0), (y2.stride(0) if y2 is not None else 0)
 
 
-def hie_affinity(x1, y1, N, L, T, x2=None, y2=None, epi=0, yprev=None, drop=(None, 0, 0.0), out=None, lens=None):
+def hie_affinity(x1, y1, N, L, T, x2=None, y2=None, epi=0, yprev=None, drop=(None, 0, 0.0), out=None, lens=None, rlens=None):
     """out (N, T, L) = epi(x1 y1^T [+ x2 y2^T]) per sample: x* rows n*T + t, y* rows n*L + l (2-D, rows may be strided).
     epi 0: the sums; 1: dropout(tanh(.)) with `drop` = (keep | None, seed, p); 2: the backward of epi 1 given its output yprev.
-    lens (N) int32: rows t >= lens[n] of out are zero."""
+    lens (N) int32: rows t >= lens[n] of out are zero.  rlens (N) int32: columns l >= rlens[n] of out are zero, the y rows there
+    (and yprev's columns) unread."""
     out, sx2, sy2 = _aff_operands("hie_affinity", x1, y1, x2, y2, yprev, out, (N, T, L))
     E = x1.shape[1]
     if y1.shape[1] != E or (x2 is not None and (x2.shape[1] != E or y2.shape[1] != E)):
         raise _l.VqfError("hie_affinity: operand shapes")
     keep, seed, p = drop
+    if rlens is not None:
+        _chk_lens(lens, N, "hie_affinity")
+        _chk_lens(rlens, N, "hie_affinity")
+        _l.check(_lib().vqf_hie_affinity_regions(_ptr(x1), x1.stride(0), _ptr(y1), y1.stride(0), _ptr(x2), sx2, _ptr(y2), sy2,
+                                                 int(epi), _ptr(yprev), _keep_ptr(keep), int(seed), float(p), _ptr(lens), _ptr(rlens),
+                                                 N, L, E, T, _ptr(out), _stream()), "vqf_hie_affinity_regions")
+        return out
     if lens is not None:
         _chk_lens(lens, N, "hie_affinity")
         _l.check(_lib().vqf_hie_affinity_len(_ptr(x1), x1.stride(0), _ptr(y1), y1.stride(0), _ptr(x2), sx2, _ptr(y2), sy2, int(epi),
@@ -709,6 +751,18 @@ def hie_affinity(x1, y1, N, L, T, x2=None, y2=None, epi=0, yprev=None, drop=(Non
                                      _ptr(yprev), _keep_ptr(keep), int(seed), float(p), N, L, E, T, _ptr(out), _stream()),
              "vqf_hie_affinity")
     return out
+
+
+def zero_cols_len(x, rlens, rows_per_sample, N, L):
+    """x[r, l] = 0 for l >= rlens[(r // rows_per_sample) % N], in place: the padded columns of a contiguous (..., N, T, L) tensor
+    (rows_per_sample = T): the ladder's C and dC on the batched-GEMM route"""
+    _chk(x)
+    _chk_lens(rlens, N, "zero_cols_len")
+    if x.numel() % (rows_per_sample * N * L):
+        raise _l.VqfError("zero_cols_len: a contiguous (G * N * rows_per_sample, L) tensor expected")
+    _l.check(_lib().vqf_zero_cols_len(_ptr(x), _ptr(rlens), x.numel() // L, int(rows_per_sample), int(N), int(L), _stream()),
+             "vqf_zero_cols_len")
+    return x
 
 
 def hie_slab_sum(part, out, add=None):
@@ -773,11 +827,20 @@ def hie_affinity_levels_supported(N, L, E, T, G, pairs=1):
 
 
 def hie_affinity_levels(x1, lvx1, y1, lvy1, G, N, L, T, E, x2=None, lvx2=0, y2=None, lvy2=0, epi=0, yprev=None, out=None,
-                        lens=None):
+                        lens=None, rlens=None):
     """out (G, N, T, L): level g = epi(X1_g Y1_g^T [+ X2_g Y2_g^T]) per sample, X_g = the E columns of x at offset g * lvx (rows
     n*T + t), Y_g those of y at g * lvy (rows n*L + l; lvy = 0: one y shared by the levels).  2-D operands, rows may be strided.
-    epi 0: the sums; 1: tanh; 2: sums * (1 - yprev^2).  lens (N) int32: rows t >= lens[n] of every level are zero."""
+    epi 0: the sums; 1: tanh; 2: sums * (1 - yprev^2).  lens (N) int32: rows t >= lens[n] of every level are zero; rlens (N)
+    int32: columns l >= rlens[n] of every level are zero, the y rows there unread."""
     out, sx2, sy2 = _aff_operands("hie_affinity_levels", x1, y1, x2, y2, yprev, out, (G, N, T, L))
+    if rlens is not None:
+        _chk_lens(lens, N, "hie_affinity_levels")
+        _chk_lens(rlens, N, "hie_affinity_levels")
+        _l.check(_lib().vqf_hie_affinity_levels_regions(_ptr(x1), x1.stride(0), int(lvx1), _ptr(y1), y1.stride(0), int(lvy1),
+                                                        _ptr(x2), sx2, int(lvx2), _ptr(y2), sy2, int(lvy2), int(G), int(epi),
+                                                        _ptr(yprev), _ptr(lens), _ptr(rlens), int(N), int(L), int(E), int(T),
+                                                        _ptr(out), _stream()), "vqf_hie_affinity_levels_regions")
+        return out
     if lens is not None:
         _chk_lens(lens, N, "hie_affinity_levels")
         _l.check(_lib().vqf_hie_affinity_levels_len(_ptr(x1), x1.stride(0), int(lvx1), _ptr(y1), y1.stride(0), int(lvy1),
