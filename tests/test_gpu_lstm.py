@@ -85,7 +85,8 @@ def _seq_inputs(S, B, H, seed):
 def test_bf16_operand_recursion_tracks_fp32(S, B, H):
     """bf16 mode (config 3): W_hh and h / dG enter the MFMA as bf16, everything else fp32.  Against the fp32
     kernels on the same inputs: h within 2e-2 of max|h| (8 mantissa bits, K = H products per gate, recurrent),
-    dgates within 5 % in norm (sanity; bf16 gradients are not a parity target)."""
+    dgates within 5 % in norm (sanity; bf16 gradients are not a parity target).
+    The sharp check of both modes is per step and per element: tests/test_gpu_lstm_seq_kernels.py."""
     import vqa_amd
     ops = vqa_amd.ops
     xw, w_hh, dhs = _seq_inputs(S, B, H, 3 * S + B)
