@@ -742,7 +742,8 @@ int vqf_embed_tanh_bwd(const float* dout, const float* out, const long long* ids
 int vqf_embed_fwd(const float* W, const long long* ids, int T, int V, int E, float* out, void* stream);
 int vqf_embed_bwd(const float* dout, const long long* ids, int T, int V, int E, float* dW, void* stream);
 /* out = dropout(W[ids]) (hieCoAtten.py:27-28: the lookup and its always-on functional dropout) and its weight gradient, one launch each
- * way; the mask is the one vqf_dropout_f32 draws over the flat (T, E) tensor (keep: (T, E) uint8 or NULL + seed / p_drop).  E % 4 == 0. */
+ * way; the mask is the one vqf_dropout_f32 draws over the flat (T, E) tensor (keep: (T, E) uint8 or NULL + seed / p_drop).  Any E
+ * (16-byte accesses when E % 4 == 0, element by element otherwise; the mask index is the flat one either way); bwd: E <= 1024. */
 int vqf_embed_dropout_fwd(const float* W, const long long* ids, int T, int V, int E, const uint8_t* keep, uint64_t seed, float p_drop,
                           float* out, void* stream);
 int vqf_embed_dropout_bwd(const float* dout, const long long* ids, int T, int V, int E, const uint8_t* keep, uint64_t seed, float p_drop,

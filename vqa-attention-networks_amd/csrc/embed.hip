@@ -229,10 +229,10 @@ int vqf_embed_tanh_bwd_len(const float* dout, const float* out, const long long*
 
 // out = dropout(W[ids]) and its weight gradient dW[v] = sum_{t: ids[t] == v} dout[t] * keep / (1 - p): hieCoAtten.py:27-28 in one pass
 // each way.  The mask is the one vqf_dropout_f32 draws over the flat (T, E) tensor (same seed -> same bits as lookup + dropout).
+// Any E: the draw is per element (keep_scale); E % 4 != 0 takes the forward's element-by-element path.
 int vqf_embed_dropout_fwd(const float* W, const long long* ids, int T, int V, int E, const uint8_t* keep, uint64_t seed, float p_drop,
                           float* out, void* stream) {
   if (!W || !ids || !out || T <= 0 || V <= 0 || E <= 0 || p_drop < 0.f || p_drop >= 1.f) return VQF_E_BADARG;
-  if (E % 4) return VQF_E_UNSUPPORTED;
   const uint32_t thr = (keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
   const float inv_keep = (keep || p_drop > 0.f) ? 1.0f / (1.0f - p_drop) : 1.0f;
   vqf_prof_dims(T, V, E);
@@ -244,7 +244,7 @@ int vqf_embed_dropout_fwd(const float* W, const long long* ids, int T, int V, in
 int vqf_embed_dropout_bwd(const float* dout, const long long* ids, int T, int V, int E, const uint8_t* keep, uint64_t seed, float p_drop,
                           float* dW, void* stream) {
   if (!dout || !ids || !dW || T <= 0 || V <= 0 || E <= 0 || p_drop < 0.f || p_drop >= 1.f) return VQF_E_BADARG;
-  if (E > 1024 || (E % 4)) return VQF_E_UNSUPPORTED;
+  if (E > 1024) return VQF_E_UNSUPPORTED;
   const uint32_t thr = (keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
   const float inv_keep = (keep || p_drop > 0.f) ? 1.0f / (1.0f - p_drop) : 1.0f;
   vqf_prof_dims(T, V, E);
