@@ -438,6 +438,48 @@ int vqf_glimpse_pool_bwd_grouped_len(const float* dpooled, const float* dwts_ext
                                      const int* order, const int* grp_off, const int* lens, int N, int U, int S, int C, int G,
                                      float* dlogits, float* dfeat, void* stream);
 
+/* Packed region features (MFB / MHBCoAtt.forward(PackedRegions(rows, offsets, max_regions), ...); additions within ABI 7; fp32 only,
+ * no cascade / zdrop): the loader never pads.  P and dP are (R, 5*O) and the pooled features (R, C): every image's real rows, one
+ * image after the other, R = the sum of the counts (a host int: a shape).  roff is device int32, 4-byte aligned (null or
+ * misaligned, or R <= 0: VQF_E_BADARG): (N + 1) offsets per sample, or (U + 1) per IMAGE in the grouped forms, where question n has
+ * the rows of image idx[n].  L >= the largest count is the padded width of everything that is NOT packed.
+ * Precondition (what data_loader.pack_region_features makes): roff[0] = 0, non-decreasing, roff[last] = R, counts in [1, L].
+ * For memory safety only, the kernels clamp what they read: owner s has  start = clamp(roff[s], 0, R - 1)  and
+ * cnt = clamp(roff[s+1] - roff[s], 1, min(L, R - start));  row l < cnt of its P / dP / feat is row start + l.  Nothing roff, idx,
+ * order or grp_off hold makes a kernel read or write out of range.
+ * Only P, dP and feat are packed.  Y / R stays (N*L, O), rowssq (N*L*4), logits / dlogits (N*S, G), wts (N, G, S), keep (N*L, 5*O),
+ * and the Philox element index stays (n*L + l)*5*O + c: rows l >= cnt of R and their rowssq partials are exact zeros and the masks
+ * are those of the *_len forms, so the result is, bit for bit, that of the *_len / *_grouped_len form on the zero-padded copy with
+ * the counts roff[s+1] - roff[s] (dP: its real rows), and vqf_l2_group_norm, the co-attention head and vqf_rowdot need no change.
+ *   fwd_packed / bwd_packed   the kernels of vqf_mfb_fuse_fwd_len / _bwd_len; ws: vqf_mfb_fuse_bwd_ws_bytes(N, L, O).
+ *   fwd_grouped_packed / bwd_grouped_packed   those of the *_grouped_len forms; a question's count is its image's.  The image-owned
+ *             pass stores every row of every image once (exact zeros for an image without a question) and adds an image's
+ *             questions in `order`: no atomics.  ws: vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O), always.
+ *   glimpse_pool_fwd_packed / _bwd_packed   vqf_glimpse_pool_fwd_len / _grouped_len and the dlogits half of their backward (feat is
+ *             data: no dfeat) on feat (R, C); idx NULL: sample n owns roff[n] .. and U must equal N.  S = L.
+ * Supported: vqf_mfb_fuse_packed_supported(N, U, R, L, O) = vqf_mfb_fuse_grouped_supported(N, U, L, O), L <= 1024 and
+ * 1 <= R < 2^29 (U = N for the plain forms); the pooling: vqf_glimpse_pool_grouped_supported(N, U, S, C, G).  Outside:
+ * VQF_E_UNSUPPORTED; VQF_E_WORKSPACE and VQF_E_ALIGN as in the *_len forms. */
+int vqf_mfb_fuse_packed_supported(int N, int U, int R, int L, int O);
+int vqf_mfb_fuse_fwd_packed(const float* P, const float* pbias, const float* q, const int* roff, const uint8_t* keep, uint64_t seed,
+                            float p_drop, int N, int R, int L, int O, float* Rout, float* rowssq, void* stream);
+int vqf_mfb_fuse_bwd_packed(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB, const float* P,
+                            const float* pbias, const float* q, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop,
+                            int N, int R, int L, int O, float* dP, float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream);
+int vqf_mfb_fuse_fwd_grouped_packed(const float* P, const float* pbias, const float* q, const int* idx, const int* roff,
+                                    const uint8_t* keep, uint64_t seed, float p_drop, int N, int U, int R, int L, int O, float* Rout,
+                                    float* rowssq, void* stream);
+int vqf_mfb_fuse_bwd_grouped_packed(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
+                                    const float* P, const float* pbias, const float* q, const int* idx, const int* order,
+                                    const int* grp_off, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop, int N,
+                                    int U, int R, int L, int O, float* dP, float* dq, float* dbiasP, void* ws, size_t ws_bytes,
+                                    void* stream);
+int vqf_glimpse_pool_fwd_packed(const float* feat, const float* logits, const int* idx, const int* roff, int N, int U, int R, int S,
+                                int C, int G, int unit_softmax, float* wts, float* pooled, void* stream);
+int vqf_glimpse_pool_bwd_packed(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
+                                const int* roff, int N, int U, int R, int S, int C, int G, int unit_softmax, float* dlogits,
+                                void* stream);
+
 
 /* --------------------------------------------------------------------------
  * Element-wise stages of HieCoAtten / AttentionNet.  n % 4 == 0, 16-byte aligned pointers.

@@ -223,17 +223,33 @@ __device__ __forceinline__ int pool_src(const int* __restrict__ idx, int n, int 
   return u < 0 ? 0 : (u >= U ? U - 1 : u);
 }
 
+// The packed forms (PACK; vqf_glimpse_pool_fwd_packed / _bwd_packed): feat is (Rtot, C), the real rows of every image one after
+// the other, and `lens` holds the row offsets roff (owners + 1) instead of counts.  The owner u = pool_src(idx, n, U) has
+// Sv = clamp(roff[u + 1] - roff[u], 1, min(S, Rtot - start)) rows from row start = clamp(roff[u], 0, Rtot - 1): whatever roff
+// holds, the rows read lie inside feat.  logits, wts and dlogits stay (N, S, .) padded; everything else is the lens form.
+// (Without PACK the kernels keep their own address expressions: their code is what it was before the flag.)
+__device__ __forceinline__ void pool_span(const int* __restrict__ roff, const int* __restrict__ idx, int n, int U, int S, int Rtot,
+                                          long long& row0, int& Sv) {
+  const int u = pool_src(idx, n, U);
+  const long long a = roff[u], b = roff[u + 1];
+  const int st = (int)min(max(a, 0LL), (long long)Rtot - 1);
+  row0 = st;
+  Sv = (int)min(max(b - a, 1LL), (long long)min(S, Rtot - st));
+}
+
 // grid (ceil(C/1024), N); thread = 4 consecutive channels
-template <int G, typename FT>
+template <int G, typename FT, bool PACK = false>
 __global__ void glimpse_pool_fwd_kernel(const FT* __restrict__ feat,
                                         const float* __restrict__ logits, int N, int S, int C,
                                         int unit, float* __restrict__ wts,
                                         float* __restrict__ pooled, const int* __restrict__ lens,
-                                        const int* __restrict__ idx, int U) {
+                                        const int* __restrict__ idx, int U, int Rtot) {
   __shared__ float w[G][MAXS];
   const int n = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int Sv = pool_len(lens, n, S);                // (uniform) the sample's real positions
+  long long row0 = 0;
+  int Sv;                                             // (uniform) the sample's real positions
+  if (PACK) pool_span(lens, idx, n, U, S, Rtot, row0, Sv); else Sv = pool_len(lens, n, S);
   if (wave < G) {
     const int g = wave;
     const float* lg = logits + (long long)n * S * G + g;
@@ -258,7 +274,7 @@ __global__ void glimpse_pool_fwd_kernel(const FT* __restrict__ feat,
 
   const int c = (blockIdx.x * blockDim.x + tid) * 4;
   if (c >= C) return;
-  const FT* f = feat + (long long)pool_src(idx, n, U) * S * C + c;
+  const FT* f = PACK ? feat + row0 * C + c : feat + (long long)pool_src(idx, n, U) * S * C + c;
   const bool vec = ((C & 3) == 0) && aligned16_dev(feat) && aligned16_dev(pooled);
   f32x4 a[G];
 #pragma unroll
@@ -300,18 +316,20 @@ __global__ void glimpse_pool_fwd_kernel(const FT* __restrict__ feat,
 
 // block per sample; wave per position s (strided); then the softmax backward.
 // dwts_extra (N,G,S) or null: gradient arriving through the returned attention weights.
-template <int G, typename FT>
+template <int G, typename FT, bool PACK = false>
 __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
                                         const float* __restrict__ dwts_extra,
                                         const FT* __restrict__ feat,
                                         const float* __restrict__ wts, int N, int S, int C, int unit,
                                         float* __restrict__ dlogits, float* __restrict__ dfeat, const int* __restrict__ lens,
-                                        const int* __restrict__ idx, int U) {
+                                        const int* __restrict__ idx, int U, int Rtot) {
   __shared__ float dw[G][MAXS];
   __shared__ float ws[G][MAXS];
   const int n = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwave = blockDim.x >> 6;
-  const int Sv = pool_len(lens, n, S);                // (uniform) positions Sv .. S - 1 are padding: weight 0, gradient 0
+  long long row0 = 0;
+  int Sv;                                             // (uniform) positions Sv .. S - 1 are padding: weight 0, gradient 0
+  if (PACK) pool_span(lens, idx, n, U, S, Rtot, row0, Sv); else Sv = pool_len(lens, n, S);
   for (int i = tid; i < G * S; i += blockDim.x) ws[i / S][i % S] = wts[(long long)n * G * S + i];
   __syncthreads();
   const float* dp = dpooled + (long long)n * G * C;
@@ -329,7 +347,7 @@ __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
       for (int g = 0; g < G; ++g) pr[g][k] = c < C ? *reinterpret_cast<const f32x4*>(dp + g * C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
     for (int s = wave; s < Sv; s += nwave) {
-      const FT* f = feat + ((long long)pool_src(idx, n, U) * S + s) * C;
+      const FT* f = PACK ? feat + (row0 + s) * C : feat + ((long long)pool_src(idx, n, U) * S + s) * C;
       f32x4 x[KC];
 #pragma unroll
       for (int k = 0; k < KC; ++k) {
@@ -348,7 +366,7 @@ __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
     }
   } else
   for (int s = wave; s < S; s += nwave) {
-    const FT* f = feat + ((long long)pool_src(idx, n, U) * S + s) * C;
+    const FT* f = PACK ? feat + (row0 + s) * C : feat + ((long long)pool_src(idx, n, U) * S + s) * C;     // (s >= Sv: not read)
     float* df = dfeat ? dfeat + ((long long)n * S + s) * C : nullptr;
     if (s >= Sv) {                                     // (wave-uniform) a padded row: zero gradient, feat unread
       if (df) {
@@ -513,17 +531,19 @@ namespace {
 // CU, 8 KB in flight: 3.2 TB/s.  Here 1024 threads = RS row slots x C / 4 channel groups; slot rs sums rows rs, rs + RS, ... (two
 // rows per trip in flight), the slots are folded through LDS in slot order: deterministic, a different association than the
 // single chain of the wide kernel (same value to fp32 rounding).
-template <int G, typename FT>
+template <int G, typename FT, bool PACK = false>
 __global__ void __launch_bounds__(1024) glimpse_pool_fwd_rows_kernel(const FT* __restrict__ feat, const float* __restrict__ logits,
                                                                      int N, int S, int C, int unit, float* __restrict__ wts,
                                                                      float* __restrict__ pooled, const int* __restrict__ lens,
-                                                                     const int* __restrict__ idx, int U) {
+                                                                     const int* __restrict__ idx, int U, int Rtot) {
   extern __shared__ float smem_g[];
   float* w = smem_g;                                   // [G][S]
   float* red = smem_g + G * S;                         // [RS][G][C]
   const int n = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int Sv = pool_len(lens, n, S);
+  long long row0 = 0;
+  int Sv;
+  if (PACK) pool_span(lens, idx, n, U, S, Rtot, row0, Sv); else Sv = pool_len(lens, n, S);
   if (wave < G) {
     const int g = wave;
     const float* lg = logits + (long long)n * S * G + g;
@@ -546,7 +566,7 @@ __global__ void __launch_bounds__(1024) glimpse_pool_fwd_rows_kernel(const FT* _
     for (int i = tid; i < G * S; i += blockDim.x) wts[(long long)n * G * S + i] = w[i];
   const int CT = C >> 2, RS = blockDim.x / CT;
   const int c4 = tid % CT, rs = tid / CT;
-  const FT* f = feat + (long long)pool_src(idx, n, U) * S * C + 4 * c4;
+  const FT* f = PACK ? feat + row0 * C + 4 * c4 : feat + (long long)pool_src(idx, n, U) * S * C + 4 * c4;
   f32x4 a[G];
 #pragma unroll
   for (int g = 0; g < G; ++g) a[g] = f32x4{0, 0, 0, 0};
@@ -571,9 +591,11 @@ __global__ void __launch_bounds__(1024) glimpse_pool_fwd_rows_kernel(const FT* _
   }
 }
 
-template <typename FT>
+// PACK: lens is roff and feat (Rtot, C), see pool_span
+template <typename FT, bool PACK = false>
 int glimpse_fwd_launch(const FT* feat, const float* logits, int N, int S, int C, int G, int unit_softmax,
-                       float* wts, float* pooled, void* stream, const int* lens = nullptr, const int* idx = nullptr, int U = 0) {
+                       float* wts, float* pooled, void* stream, const int* lens = nullptr, const int* idx = nullptr, int U = 0,
+                       int Rtot = 0) {
   if (!feat || !logits || !pooled || N <= 0 || S <= 0 || C <= 0 || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
   if (S > MAXS || G < 1 || G > 3 || N > 65535) return VQF_E_UNSUPPORTED;
   dim3 grid((C + 1023) / 1024, N);
@@ -587,34 +609,34 @@ int glimpse_fwd_launch(const FT* feat, const float* logits, int N, int S, int C,
       const size_t lds = sizeof(float) * ((size_t)G * S + (size_t)RS * G * C);
       if (RS >= G && lds <= 64 * 1024) {
         if (G == 3)
-          VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<3, FT>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
-                     unit_softmax, wts, pooled, lens, idx, U);
+          VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<3, FT, PACK>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
+                     unit_softmax, wts, pooled, lens, idx, U, Rtot);
         else if (G == 2)
-          VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<2, FT>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
-                     unit_softmax, wts, pooled, lens, idx, U);
+          VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<2, FT, PACK>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
+                     unit_softmax, wts, pooled, lens, idx, U, Rtot);
         else
-          VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<1, FT>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
-                     unit_softmax, wts, pooled, lens, idx, U);
+          VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<1, FT, PACK>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
+                     unit_softmax, wts, pooled, lens, idx, U, Rtot);
         return vqf_last_error();
       }
     }
   }
   if (G == 3)
-    VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<3, FT>), grid, dim3(256), 0, s, feat, logits, N, S,
-               C, unit_softmax, wts, pooled, lens, idx, U);
+    VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<3, FT, PACK>), grid, dim3(256), 0, s, feat, logits, N, S,
+               C, unit_softmax, wts, pooled, lens, idx, U, Rtot);
   else if (G == 2)
-    VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<2, FT>), grid, dim3(256), 0, s, feat, logits, N, S,
-               C, unit_softmax, wts, pooled, lens, idx, U);
+    VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<2, FT, PACK>), grid, dim3(256), 0, s, feat, logits, N, S,
+               C, unit_softmax, wts, pooled, lens, idx, U, Rtot);
   else
-    VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<1, FT>), grid, dim3(256), 0, s, feat, logits, N, S,
-               C, unit_softmax, wts, pooled, lens, idx, U);
+    VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<1, FT, PACK>), grid, dim3(256), 0, s, feat, logits, N, S,
+               C, unit_softmax, wts, pooled, lens, idx, U, Rtot);
   return vqf_last_error();
 }
 
-template <typename FT>
+template <typename FT, bool PACK = false>
 int glimpse_bwd_launch(const float* dpooled, const float* dwts_extra, const FT* feat, const float* wts, int N,
                        int S, int C, int G, int unit_softmax, float* dlogits, float* dfeat, void* stream,
-                       const int* lens = nullptr, const int* idx = nullptr, int U = 0) {
+                       const int* lens = nullptr, const int* idx = nullptr, int U = 0, int Rtot = 0) {
   if (!dpooled || !feat || !wts || !dlogits || N <= 0 || S <= 0 || C <= 0 || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
   if (S > MAXS || G < 1 || G > 3) return VQF_E_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
@@ -633,14 +655,14 @@ int glimpse_bwd_launch(const float* dpooled, const float* dwts_extra, const FT* 
   }
   const dim3 block(64 * waves);
   if (G == 3)
-    VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<3, FT>), dim3(N), block, 0, s, dpooled,
-               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U);
+    VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<3, FT, PACK>), dim3(N), block, 0, s, dpooled,
+               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U, Rtot);
   else if (G == 2)
-    VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<2, FT>), dim3(N), block, 0, s, dpooled,
-               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U);
+    VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<2, FT, PACK>), dim3(N), block, 0, s, dpooled,
+               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U, Rtot);
   else
-    VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<1, FT>), dim3(N), block, 0, s, dpooled,
-               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U);
+    VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<1, FT, PACK>), dim3(N), block, 0, s, dpooled,
+               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U, Rtot);
   return vqf_last_error();
 }
 
@@ -821,6 +843,30 @@ int vqf_glimpse_pool_bwd_grouped_len(const float* dpooled, const float* dwts_ext
                                      float* dlogits, float* dfeat, void* stream) {
   if (!lens || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
   return glimpse_bwd_grouped(dpooled, dwts_extra, feat, wts, idx, order, grp_off, lens, N, U, S, C, G, dlogits, dfeat, stream);
+}
+
+// the packed forms: feat (R, C) fp32 data (no dfeat), roff (U + 1) int32 row offsets -- (N + 1) with idx NULL, where U = N
+static int packed_pool_args(const int* idx, const int* roff, int N, int U, int R, int S, int C, int G) {
+  if (!roff || ((((uintptr_t)idx) | ((uintptr_t)roff)) & 3) || R <= 0 || N <= 0 || U <= 0 || S <= 0 || C <= 0) return VQF_E_BADARG;
+  if (!idx && U != N) return VQF_E_BADARG;
+  if (!vqf_glimpse_pool_grouped_supported(N, U, S, C, G)) return VQF_E_UNSUPPORTED;
+  return VQF_OK;
+}
+
+int vqf_glimpse_pool_fwd_packed(const float* feat, const float* logits, const int* idx, const int* roff, int N, int U, int R, int S,
+                                int C, int G, int unit_softmax, float* wts, float* pooled, void* stream) {
+  const int rc = packed_pool_args(idx, roff, N, U, R, S, C, G);
+  if (rc) return rc;
+  return glimpse_fwd_launch<float, true>(feat, logits, N, S, C, G, unit_softmax, wts, pooled, stream, roff, idx, U, R);
+}
+
+int vqf_glimpse_pool_bwd_packed(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
+                                const int* roff, int N, int U, int R, int S, int C, int G, int unit_softmax, float* dlogits,
+                                void* stream) {
+  const int rc = packed_pool_args(idx, roff, N, U, R, S, C, G);
+  if (rc) return rc;
+  return glimpse_bwd_launch<float, true>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, nullptr, stream, roff,
+                                         idx, U, R);
 }
 
 int vqf_row_block_supported(int N, int U, long long blk) {

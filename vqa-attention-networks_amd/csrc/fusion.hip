@@ -150,6 +150,16 @@ __device__ __forceinline__ void own_store(__bf16* __restrict__ rowp, int W5, int
   }
 }
 
+// The packed forms (PACK): roff (owners + 1) int32 are row offsets into a (Rtot, .) tensor.  Owner s has cnt rows from row start:
+// start = clamp(roff[s], 0, Rtot - 1), cnt = clamp(roff[s + 1] - roff[s], 1, min(L, Rtot - start)) -- whatever roff holds, rows
+// start .. start + cnt - 1 lie inside the tensor and cnt <= L.  Uniform over the block.
+__device__ __forceinline__ void packed_span(const int* __restrict__ roff, int s, int L, int Rtot, long long& start, int& cnt) {
+  const long long a = roff[s], b = roff[s + 1];
+  const int st = (int)min(max(a, 0LL), (long long)Rtot - 1);
+  start = st;
+  cnt = (int)min(max(b - a, 1LL), (long long)min(L, Rtot - st));
+}
+
 // scale[i] = keep ? 1/(1-p) : 0 for the 20 elements starting at flat index e0 (e0 % 4 == 0)
 __device__ __forceinline__ void keep_scale20(const uint8_t* __restrict__ keep, uint64_t seed,
                                              uint32_t thr, float inv_keep, long long e0,
@@ -205,7 +215,11 @@ __device__ __forceinline__ void keep_scale20(const uint8_t* __restrict__ keep, u
 // LEN (vqf_mfb_fuse_fwd_len / _grouped_len: region counts, lens (N) int32): the block reads Lv = clamp(lens[n], 1, L) once (uniform
 // over the block: the wave-private LDS transpose stays convergent), walks l = ls, ls + LS, ... < Lv exactly as without it, and for
 // Lv <= l < L reads nothing and stores a zero R row and zero rowssq partials.  With lens[n] = L it gives the plain kernel's bits.
-template <typename PT, int COAL, bool GRP = false, bool LEN = false>
+// PACK (vqf_mfb_fuse_fwd_packed / _grouped_packed; with LEN): P is (Rtot, 5O), the real rows of every image one after the other, and
+// `lens` holds the row offsets roff (owners + 1) instead of counts: the owner s (sample n, or image idx[n]) has its rows at
+// packed_span(roff, s) -- row l < Lv of the sample is P row start + l.  R, rowssq, keep / the Philox index stay in the padded
+// coordinates n L + l, so everything else is the LEN form.
+template <typename PT, int COAL, bool GRP = false, bool LEN = false, bool PACK = false>
 __global__ void __launch_bounds__(256)
 mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
                     const float* __restrict__ q,
@@ -213,7 +227,7 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
                     uint64_t seed, uint32_t thr, float inv_keep, int L, int O, int LS,
                     float* __restrict__ R, float* __restrict__ rowssq, float* __restrict__ zdrop,
                     unsigned short* __restrict__ Rb, int ldrb, const int* __restrict__ idx, int U,
-                    const int* __restrict__ lens) {
+                    const int* __restrict__ lens, int Rtot) {
   // Rb != nullptr: a bf16 copy of R (round-to-nearest-even) with row pitch ldrb >= O, columns O .. ldrb-1 zero: the K-padded A
   // operand of the co-attention conv's bf16 GEMM (BASELINE config 3) straight from the registers that hold R -- no
   // vqf_cast_f32_bf16 pass over the 401 MB tensor.  ldrb / 4 <= 256.
@@ -226,8 +240,10 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int nt = O / TPT;                       // active threads (250 at O = 1000); O / TPT <= 256
   const bool act = tid < nt;
-  const long long prow0 = (long long)(GRP ? min(max(idx[n], 0), U - 1) : n) * L;     // first projection row of the sample
-  const int Lw = LEN ? min(max(lens[n], 1), L) : L;                                   // rows the block walks (LEN: the real regions)
+  const int own = GRP ? min(max(idx[n], 0), U - 1) : n;
+  long long prow0 = (long long)own * L;                                               // first projection row of the sample
+  int Lw = (LEN && !PACK) ? min(max(lens[n], 1), L) : L;                              // rows the block walks (LEN: the real regions)
+  if (PACK) packed_span(lens, own, L, Rtot, prow0, Lw);
   float qq[CPT], pb[CPT], p[CPT], pn[CPT];
   Raw<PT> rn;                                   // COAL: the next row's span of this wave, lane-linear pieces
 #pragma unroll
@@ -322,7 +338,9 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
 // LEN (region counts, as in the forward): the walk stops at Lv = clamp(lens[n], 1, L); of the rows beyond, dY / Y / P are not read
 // and (plain form) dP gets exact zero rows through the store path of the walk.  A block without a real row still writes its
 // zero dq / bias partials.
-template <bool CASC, bool DBIAS, typename DPT, typename PT, bool COAL, bool GRP = false, bool LEN = false>
+// PACK (with LEN; `lens` = roff, as in the forward): P and dP are (Rtot, 5O); row l < Lv of the sample reads P row start + l and
+// (plain form) stores dP row start + l -- there is no padded dP row to zero.  dY / Y / the masks stay at n L + l.
+template <bool CASC, bool DBIAS, typename DPT, typename PT, bool COAL, bool GRP = false, bool LEN = false, bool PACK = false>
 __global__ void __launch_bounds__(256)
 mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdrop,
                     const float* __restrict__ Y,
@@ -333,14 +351,16 @@ mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdr
                     const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep,
                     int L, int O, int LS, DPT* __restrict__ dP, float* __restrict__ dq_part,
                     float* __restrict__ dcascade, float* __restrict__ db_part, const int* __restrict__ idx, int U,
-                    const int* __restrict__ lens) {
+                    const int* __restrict__ lens, int Rtot) {
   __shared__ __attribute__((aligned(16))) char tl[COAL ? 4 * WLDS : 16];
   const int n = blockIdx.x, ls = blockIdx.y;
   const int W5 = KP * O;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const float ca = coefA[n], cb = coefB[n], hi = 0.5f * inv[n];
-  const long long prow0 = (long long)(GRP ? min(max(idx[n], 0), U - 1) : n) * L;     // first projection row of the sample
-  const int Lw = LEN ? min(max(lens[n], 1), L) : L;                                   // rows the block walks (LEN: the real regions)
+  const int own = GRP ? min(max(idx[n], 0), U - 1) : n;
+  long long prow0 = (long long)own * L;                                               // first projection row of the sample
+  int Lw = (LEN && !PACK) ? min(max(lens[n], 1), L) : L;                              // rows the block walks (LEN: the real regions)
+  if (PACK) packed_span(lens, own, L, Rtot, prow0, Lw);
   // COAL (O / 4 <= 256: one pass): every lane of a wave takes part in the coalesced P loads / dP stores, threads past
   // O / 4 only skip the arithmetic
   for (int t = threadIdx.x; COAL ? t < 256 : t < O / TPT; t += 256) {
@@ -395,12 +415,12 @@ mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdr
           }
           if (DBIAS) db[i] += dp[i];
         }
-        if (!COAL && !GRP) store20(dP + e0, dp);
+        if (!COAL && !GRP) store20(dP + (PACK ? prow * W5 + (long long)CPT * t : e0), dp);
         if (CASC) store20(dcascade + e0, dc);
       }
-      if (COAL && !GRP) own_store(dP + row * W5, W5, wave, lane, tl + wave * WLDS, dp);
+      if (COAL && !GRP) own_store(dP + (PACK ? prow : row) * W5, W5, wave, lane, tl + wave * WLDS, dp);
     }
-    if (LEN && !GRP) {
+    if (LEN && !GRP && !PACK) {
       float zr[CPT];
 #pragma unroll
       for (int i = 0; i < CPT; ++i) zr[i] = 0.f;
@@ -428,18 +448,22 @@ mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdr
 // P is not read.  order is clamped to [0, N - 1] and grp_off to [0, N] (kept monotone) where they are read.
 // LEN (region counts per IMAGE, lens (U) int32; every question of image u has that count): Lu = clamp(lens[u], 1, L); a row pair
 // entirely beyond Lu skips the walk over the image's questions and stores zeros, a pair straddling Lu accumulates its real row only.
+// PACK (with LEN; `lens` = roff (U + 1)): dP is (Rtot, 5O) and image u owns rows start .. start + Lu - 1 of it: rows l < Lu are
+// stored there (zeros for an image without a question) and there is no row beyond Lu to store.
 constexpr int IRB = 2;              // rows per walk of an image's questions
-template <bool DBIAS, bool LEN = false>
+template <bool DBIAS, bool LEN = false, bool PACK = false>
 __global__ void __launch_bounds__(256)
 mfb_fuse_bwd_image_kernel(const float* __restrict__ dY, const float* __restrict__ Y, const float* __restrict__ inv,
                           const float* __restrict__ coefA, const float* __restrict__ coefB, const float* __restrict__ q,
                           const int* __restrict__ order, const int* __restrict__ grp_off,
                           const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep,
                           int N, int L, int O, int LS, float* __restrict__ dP, float* __restrict__ db_part,
-                          const int* __restrict__ lens) {
+                          const int* __restrict__ lens, int Rtot) {
   __shared__ __attribute__((aligned(16))) char tl[4 * WLDS];
   const int u = blockIdx.x, ls = blockIdx.y;
-  const int Lw = LEN ? min(max(lens[u], 1), L) : L;                                   // rows that take gradient (LEN: the real regions)
+  int Lw = (LEN && !PACK) ? min(max(lens[u], 1), L) : L;                              // rows that take gradient (LEN: the real regions)
+  long long drow0 = (long long)u * L;                                                 // first dP row of the image
+  if (PACK) packed_span(lens, u, L, Rtot, drow0, Lw);
   const int W5 = KP * O;
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
   const bool act = t < O / TPT;
@@ -483,8 +507,8 @@ mfb_fuse_bwd_image_kernel(const float* __restrict__ dY, const float* __restrict_
     }
 #pragma unroll
     for (int r = 0; r < IRB; ++r) {
-      if (l0 + r < L) {                                  // (uniform over the block)
-        own_store(dP + ((long long)u * L + l0 + r) * W5, W5, wave, lane, tl + wave * WLDS, dp[r]);
+      if (l0 + r < (PACK ? Lw : L)) {                    // (uniform over the block)
+        own_store(dP + (drow0 + l0 + r) * W5, W5, wave, lane, tl + wave * WLDS, dp[r]);
         if (DBIAS) {
 #pragma unroll
           for (int i = 0; i < CPT; ++i) db[i] += dp[r][i];
@@ -539,10 +563,13 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
                      const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O,
                      void* dP, int dp_bf16, float* dq, float* dcascade, float* dbiasP, void* ws,
                      size_t ws_bytes, void* stream, const int* idx = nullptr, const int* order = nullptr,
-                     const int* grp_off = nullptr, int U = 0, const int* lens = nullptr, const int* lens_u = nullptr) {
+                     const int* grp_off = nullptr, int U = 0, const int* lens = nullptr, const int* lens_u = nullptr,
+                     const int* roff = nullptr, int Rtot = 0) {
   // idx != nullptr: the grouped form (vqf_mfb_fuse_bwd_grouped, which has checked its own operands): P and dP are (U*L, 5O)
   // lens != nullptr: the region-count forms (fp32, no cascade / dzdrop; their entry points have checked lens): lens (N) per sample /
   // question, lens_u (U) per image in the grouped form
+  // roff != nullptr: the packed forms (fp32; their entry points have checked roff and Rtot): P and dP are (Rtot, 5O), roff (N + 1) per
+  // sample or, grouped, (U + 1) per image; lens / lens_u are not used
   if (!dY || !Y || !inv || !coefA || !coefB || !P || !q || !dP || !dq || N <= 0 || L <= 0 || O <= 0)
     return VQF_E_BADARG;
   if (O % TPT) return VQF_E_UNSUPPORTED;
@@ -572,27 +599,30 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
 #define VQF_BWD1(C_, D_, T_, PT_, CO_)                                                           \
   VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<C_, D_, T_, PT_, CO_>), grid, dim3(256), 0, s, dY, dzdrop, Y, inv, \
              coefA, coefB, (const PT_*)P, pbias, q, cascade, keep, seed, thr, inv_keep, L, O, LS, (T_*)dP, dq_part, \
-             dcascade, db_part, nullptr, 0, nullptr)
+             dcascade, db_part, nullptr, 0, nullptr, 0)
 #define VQF_BWD(C_, D_, T_, PT_) do { if (coal) VQF_BWD1(C_, D_, T_, PT_, true); else VQF_BWD1(C_, D_, T_, PT_, false); } while (0)
   if (idx) {
     // question-owned pass: the plain kernel reading P through idx, no dP store, no bias partials (the dq partials only) ...
-#define VQF_BWDQ(CO_, LEN_)                                                                                                          \
-  VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<false, false, float, float, CO_, true, LEN_>), grid, dim3(256), 0, s, dY, nullptr, \
-             Y, inv, coefA, coefB, (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, (float*)nullptr,         \
-             dq_part, nullptr, nullptr, idx, U, lens)
-    if (lens) { if (coal) VQF_BWDQ(true, true); else VQF_BWDQ(false, true); }
-    else      { if (coal) VQF_BWDQ(true, false); else VQF_BWDQ(false, false); }
+#define VQF_BWDQ(CO_, LEN_, PK_)                                                                                                     \
+  VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<false, false, float, float, CO_, true, LEN_, PK_>), grid, dim3(256), 0, s, dY,    \
+             nullptr, Y, inv, coefA, coefB, (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, (float*)nullptr, \
+             dq_part, nullptr, nullptr, idx, U, PK_ ? roff : lens, Rtot)
+    if (roff)      { if (coal) VQF_BWDQ(true, true, true); else VQF_BWDQ(false, true, true); }
+    else if (lens) { if (coal) VQF_BWDQ(true, true, false); else VQF_BWDQ(false, true, false); }
+    else           { if (coal) VQF_BWDQ(true, false, false); else VQF_BWDQ(false, false, false); }
 #undef VQF_BWDQ
     int rcg = vqf_last_error();
     if (rcg) return rcg;
     // ... image-owned pass: dP rows and the bias partials of the U*L rows it wrote
     const int LSI = pick_ls_image(U, L);
     db_part = (float*)ws + (size_t)N * LS * W5;                   // [U * LSI][5O], then the reducer's VQF_REDUCE_SPLITS rows
-#define VQF_BWDI(DB_, LEN_)                                                                                                          \
-  VQF_LAUNCH(KID_MFB_FUSE_BWD_IMAGE, (mfb_fuse_bwd_image_kernel<DB_, LEN_>), dim3(U, LSI), dim3(256), 0, s, dY, Y, inv, coefA, coefB, \
-             q, order, grp_off, keep, seed, thr, inv_keep, N, L, O, LSI, (float*)dP, DB_ ? db_part : nullptr, lens_u)
-    if (lens_u) { if (dbiasP) VQF_BWDI(true, true); else VQF_BWDI(false, true); }
-    else        { if (dbiasP) VQF_BWDI(true, false); else VQF_BWDI(false, false); }
+#define VQF_BWDI(DB_, LEN_, PK_)                                                                                                     \
+  VQF_LAUNCH(KID_MFB_FUSE_BWD_IMAGE, (mfb_fuse_bwd_image_kernel<DB_, LEN_, PK_>), dim3(U, LSI), dim3(256), 0, s, dY, Y, inv, coefA,   \
+             coefB, q, order, grp_off, keep, seed, thr, inv_keep, N, L, O, LSI, (float*)dP, DB_ ? db_part : nullptr,                 \
+             PK_ ? roff : lens_u, Rtot)
+    if (roff)        { if (dbiasP) VQF_BWDI(true, true, true); else VQF_BWDI(false, true, true); }
+    else if (lens_u) { if (dbiasP) VQF_BWDI(true, true, false); else VQF_BWDI(false, true, false); }
+    else             { if (dbiasP) VQF_BWDI(true, false, false); else VQF_BWDI(false, false, false); }
 #undef VQF_BWDI
     rcg = vqf_last_error();
     if (rcg) return rcg;
@@ -603,13 +633,18 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
     if (dbiasP) rcg = vqf_colreduce_2stage(db_part, U * LSI, W5, dbiasP, db_part + (size_t)U * LSI * W5, s);
     return rcg;
   }
-  if (lens) {
-#define VQF_BWDL(D_, CO_)                                                                                                            \
-  VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<false, D_, float, float, CO_, false, true>), grid, dim3(256), 0, s, dY, nullptr,  \
-             Y, inv, coefA, coefB, (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, (float*)dP, dq_part,     \
-             nullptr, db_part, nullptr, 0, lens)
-    if (dbiasP) { if (coal) VQF_BWDL(true, true); else VQF_BWDL(true, false); }
-    else        { if (coal) VQF_BWDL(false, true); else VQF_BWDL(false, false); }
+  if (lens || roff) {
+#define VQF_BWDL(D_, CO_, PK_)                                                                                                       \
+  VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<false, D_, float, float, CO_, false, true, PK_>), grid, dim3(256), 0, s, dY,      \
+             nullptr, Y, inv, coefA, coefB, (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, (float*)dP,     \
+             dq_part, nullptr, db_part, nullptr, 0, PK_ ? roff : lens, Rtot)
+#define VQF_BWDL2(PK_)                                                                   \
+    do {                                                                                 \
+      if (dbiasP) { if (coal) VQF_BWDL(true, true, PK_); else VQF_BWDL(true, false, PK_); }   \
+      else        { if (coal) VQF_BWDL(false, true, PK_); else VQF_BWDL(false, false, PK_); } \
+    } while (0)
+    if (roff) VQF_BWDL2(true); else VQF_BWDL2(false);
+#undef VQF_BWDL2
 #undef VQF_BWDL
   }
   else if (p_bf16)  { if (dbiasP) VQF_BWD(false, true, __bf16, __bf16); else VQF_BWD(false, false, __bf16, __bf16); }
@@ -634,8 +669,9 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
 static int fuse_fwd_impl(const void* P, int p_bf16, const float* pbias, const float* q, const float* cascade,
                          const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O, float* R,
                          float* rowssq, float* zdrop, void* stream, void* R_bf16 = nullptr, int ldrb = 0,
-                         const int* idx = nullptr, int U = 0, const int* lens = nullptr) {
+                         const int* idx = nullptr, int U = 0, const int* lens = nullptr, const int* roff = nullptr, int Rtot = 0) {
   // lens != nullptr: the region-count forms (fp32 P, no cascade / zdrop / R_bf16; their entry points have checked lens)
+  // roff != nullptr: the packed forms (the same restrictions; P is (Rtot, 5O), roff (N + 1) or, with idx, (U + 1); lens is not used)
   if (!P || !q || !R || !rowssq || N <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
   if (R_bf16 && (ldrb < O || (ldrb % 4) || ldrb / 4 > 256 || (((uintptr_t)R_bf16) & 7))) return VQF_E_BADARG;
   if ((O % TPT) || O / TPT > 256) return VQF_E_UNSUPPORTED;     // one thread per 4 pooled outputs: O <= 1024 (the reference's 1000)
@@ -652,18 +688,24 @@ static int fuse_fwd_impl(const void* P, int p_bf16, const float* pbias, const fl
 #define VQF_FWD(PT_, CO_)                                                                                             \
   VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<PT_, CO_>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream,         \
              (const PT_*)P, pbias, q, cascade, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, zdrop, (unsigned short*)R_bf16, ldrb, \
-             nullptr, 0, nullptr)
+             nullptr, 0, nullptr, 0)
 #define VQF_FWDG(CO_)                                                                                                 \
   VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<float, CO_, true>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream, \
-             (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, nullptr, nullptr, 0, idx, U, nullptr)
+             (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, nullptr, nullptr, 0, idx, U, nullptr, 0)
 #define VQF_FWDL(CO_, GRP_)                                                                                           \
   VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<float, CO_, GRP_, true>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream, \
-             (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, nullptr, nullptr, 0, idx, U, lens)
-  if (lens && idx) { if (nopf) VQF_FWDL(2, true); else if (coal) VQF_FWDL(1, true); else VQF_FWDL(0, true); }     // region counts (fp32 only)
+             (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, nullptr, nullptr, 0, idx, U, lens, 0)
+#define VQF_FWDP(CO_, GRP_)                                                                                           \
+  VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<float, CO_, GRP_, true, true>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream, \
+             (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, nullptr, nullptr, 0, idx, U, roff, Rtot)
+  if (roff && idx) { if (nopf) VQF_FWDP(2, true); else if (coal) VQF_FWDP(1, true); else VQF_FWDP(0, true); }     // packed rows (fp32 only)
+  else if (roff)   { if (nopf) VQF_FWDP(2, false); else if (coal) VQF_FWDP(1, false); else VQF_FWDP(0, false); }
+  else if (lens && idx) { if (nopf) VQF_FWDL(2, true); else if (coal) VQF_FWDL(1, true); else VQF_FWDL(0, true); }     // region counts (fp32 only)
   else if (lens)   { if (nopf) VQF_FWDL(2, false); else if (coal) VQF_FWDL(1, false); else VQF_FWDL(0, false); }
   else if (idx) { if (nopf) VQF_FWDG(2); else if (coal) VQF_FWDG(1); else VQF_FWDG(0); }       // the grouped form (fp32 only)
   else if (p_bf16) { if (nopf) VQF_FWD(__bf16, 2); else if (coal) VQF_FWD(__bf16, 1); else VQF_FWD(__bf16, 0); }
   else        { if (nopf) VQF_FWD(float, 2); else if (coal) VQF_FWD(float, 1); else VQF_FWD(float, 0); }
+#undef VQF_FWDP
 #undef VQF_FWDL
 #undef VQF_FWDG
 #undef VQF_FWD
@@ -771,6 +813,51 @@ int vqf_mfb_fuse_bwd_grouped_len(const float* dY, const float* Y, const float* i
   if (!ws || ws_bytes < vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O) || !aligned16(ws)) return VQF_E_WORKSPACE;
   return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
                        dbiasP, ws, ws_bytes, stream, idx, order, grp_off, U, lens_q, lens_u);
+}
+
+// the packed forms (roff: int32, 4-byte aligned; the kernels clamp what it holds, see packed_span)
+int vqf_mfb_fuse_packed_supported(int N, int U, int R, int L, int O) {
+  return vqf_mfb_fuse_grouped_supported(N, U, L, O) && L <= 1024 && R >= 1 && R < (1 << 29);
+}
+
+int vqf_mfb_fuse_fwd_packed(const float* P, const float* pbias, const float* q, const int* roff, const uint8_t* keep, uint64_t seed,
+                            float p_drop, int N, int R, int L, int O, float* Rout, float* rowssq, void* stream) {
+  if (!grouped_index_ok(roff) || R <= 0 || N <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
+  if (!vqf_mfb_fuse_packed_supported(N, N, R, L, O)) return VQF_E_UNSUPPORTED;
+  return fuse_fwd_impl(P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, Rout, rowssq, nullptr, stream, nullptr, 0, nullptr, 0,
+                       nullptr, roff, R);
+}
+
+int vqf_mfb_fuse_bwd_packed(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB, const float* P,
+                            const float* pbias, const float* q, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop,
+                            int N, int R, int L, int O, float* dP, float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream) {
+  if (!grouped_index_ok(roff) || R <= 0 || N <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
+  if (!vqf_mfb_fuse_packed_supported(N, N, R, L, O)) return VQF_E_UNSUPPORTED;
+  return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
+                       dbiasP, ws, ws_bytes, stream, nullptr, nullptr, nullptr, 0, nullptr, nullptr, roff, R);
+}
+
+int vqf_mfb_fuse_fwd_grouped_packed(const float* P, const float* pbias, const float* q, const int* idx, const int* roff,
+                                    const uint8_t* keep, uint64_t seed, float p_drop, int N, int U, int R, int L, int O, float* Rout,
+                                    float* rowssq, void* stream) {
+  if (!grouped_index_ok(idx) || !grouped_index_ok(roff) || R <= 0 || N <= 0 || U <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
+  if (!vqf_mfb_fuse_packed_supported(N, U, R, L, O)) return VQF_E_UNSUPPORTED;
+  return fuse_fwd_impl(P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, Rout, rowssq, nullptr, stream, nullptr, 0, idx, U,
+                       nullptr, roff, R);
+}
+
+int vqf_mfb_fuse_bwd_grouped_packed(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
+                                    const float* P, const float* pbias, const float* q, const int* idx, const int* order,
+                                    const int* grp_off, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop, int N,
+                                    int U, int R, int L, int O, float* dP, float* dq, float* dbiasP, void* ws, size_t ws_bytes,
+                                    void* stream) {
+  if (!grouped_index_ok(idx) || !grouped_index_ok(order) || !grouped_index_ok(grp_off) || !grouped_index_ok(roff) || R <= 0 ||
+      N <= 0 || U <= 0 || L <= 0 || O <= 0)
+    return VQF_E_BADARG;
+  if (!vqf_mfb_fuse_packed_supported(N, U, R, L, O)) return VQF_E_UNSUPPORTED;
+  if (!ws || ws_bytes < vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O) || !aligned16(ws)) return VQF_E_WORKSPACE;
+  return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
+                       dbiasP, ws, ws_bytes, stream, idx, order, grp_off, U, nullptr, nullptr, roff, R);
 }
 
 int vqf_mfb_fuse_bwd_pbf16(const float* dY, const float* Y, const float* inv, const float* coefA,

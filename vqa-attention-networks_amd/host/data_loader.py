@@ -24,6 +24,7 @@ import torch
 
 from . import ops
 from .lib import VqfError
+from .grouping import PackedRegions
 
 
 class FeatureStager:
@@ -131,23 +132,40 @@ def group_batch(image_ids):
     return torch.tensor(rows, dtype=torch.int64), torch.tensor(index, dtype=torch.int64)
 
 
+def _region_arrays(name, features, multiple):
+    """The input checks pad_region_features and pack_region_features share -> (float32 (K_i, D) arrays, D, Lmax)."""
+    arrs = [np.asarray(a, dtype=np.float32) for a in features]
+    if not arrs:
+        raise ValueError(name + ": an empty list")
+    if int(multiple) < 1:
+        raise ValueError(name + ": multiple must be >= 1")
+    if any(a.ndim != 2 or a.shape[0] < 1 for a in arrs):
+        raise ValueError(name + ": every entry must be a (K_i, D) array with K_i >= 1")
+    D = arrs[0].shape[1]
+    if any(a.shape[1] != D for a in arrs):
+        raise ValueError(name + ": mixed channel counts %s" % sorted({a.shape[1] for a in arrs}))
+    m = int(multiple)
+    return arrs, D, (max(a.shape[0] for a in arrs) + m - 1) // m * m
+
+
 def pad_region_features(features, multiple=1):
     """The host half of a region-count batch (forward((img, img_length), ...)): features = one (K_i, D) array per image (detector
     boxes, K_i >= 1, the same D) -> (img (N, Lmax, D) float32, zero-padded on the right, img_length (N,) int64), both CPU
     tensors.  Lmax is the largest K_i rounded up to a multiple of `multiple`."""
-    arrs = [np.asarray(a, dtype=np.float32) for a in features]
-    if not arrs:
-        raise ValueError("pad_region_features: an empty list")
-    if int(multiple) < 1:
-        raise ValueError("pad_region_features: multiple must be >= 1")
-    if any(a.ndim != 2 or a.shape[0] < 1 for a in arrs):
-        raise ValueError("pad_region_features: every entry must be a (K_i, D) array with K_i >= 1")
-    D = arrs[0].shape[1]
-    if any(a.shape[1] != D for a in arrs):
-        raise ValueError("pad_region_features: mixed channel counts %s" % sorted({a.shape[1] for a in arrs}))
-    m = int(multiple)
-    Lmax = (max(a.shape[0] for a in arrs) + m - 1) // m * m
+    arrs, D, Lmax = _region_arrays("pad_region_features", features, multiple)
     img = torch.zeros((len(arrs), Lmax, D), dtype=torch.float32)
     for n, a in enumerate(arrs):
         img[n, :a.shape[0]] = torch.from_numpy(np.ascontiguousarray(a))
     return img, torch.tensor([a.shape[0] for a in arrs], dtype=torch.int64)
+
+
+def pack_region_features(features, multiple=1):
+    """The host half of a packed batch (forward(PackedRegions, ...)): the same input and the same checks as pad_region_features
+    -> a CPU PackedRegions whose rows (sum K_i, D) float32 are the images' regions one after the other, never padded, with
+    offsets (N + 1,) int64 and max_regions = the largest K_i rounded up to a multiple of `multiple`.  Its .unpack() equals
+    pad_region_features(features, multiple); .to(device) moves it."""
+    arrs, D, Lmax = _region_arrays("pack_region_features", features, multiple)
+    offsets = torch.zeros(len(arrs) + 1, dtype=torch.int64)
+    offsets[1:] = torch.cumsum(torch.tensor([a.shape[0] for a in arrs], dtype=torch.int64), 0)
+    rows = torch.from_numpy(np.ascontiguousarray(np.concatenate(arrs, 0)))
+    return PackedRegions(rows, offsets, Lmax)

@@ -201,11 +201,21 @@ class AttHeadFn(torch.autograd.Function):
     lens: None, or the region counts of the image head (forward((img, img_length), ...); fp32 feat that is data): an int32 (N,) tensor,
         with grp the pair (lens_q (N,), lens_u (U,)).  The softmax runs over the first lens[n] positions (unit_softmax: weight 1
         there), the weights beyond are exact zeros and so are their dlogits, so the MLP's backward adds nothing for padded rows.
+    pack: None, or (roff, L) of the packed call form (forward(PackedRegions, ...); image head, fp32 feat that is data, no lens): feat
+        is (R, C), the real rows of every image, and roff the int32 row offsets -- (N + 1,), with grp (U + 1,) per image.  x, the
+        logits and the weights stay (N, L, .) padded; the pooling reads feat through roff (vqf_glimpse_pool_fwd_packed / _bwd_packed).
     returns pooled (N, 2C); the attention weights (N,2,S) are kept on ctx.
     """
 
     @staticmethod
-    def _pool_fwd(feat, logits, unit, grp, lens=None):
+    def _pool_fwd(feat, logits, unit, grp, lens=None, pack=None):
+        if pack is not None:
+            roff, L = pack
+            if grp is not None and unit:     # the region sums of each IMAGE, one row block per question (as below)
+                U = roff.shape[0] - 1
+                zeros = torch.zeros((U * L, logits.shape[1]), dtype=torch.float32, device=feat.device)
+                return None, ops.row_block_gather(ops.glimpse_pool_fwd_packed(feat, zeros, roff, U, L, True)[1], grp[0])
+            return ops.glimpse_pool_fwd_packed(feat, logits, roff, logits.shape[0] // L, L, unit, idx=None if grp is None else grp[0])
         if grp is None:
             return ops.glimpse_pool_fwd(feat, logits, unit, lens=lens)
         if unit:      # weights == 1: the region sums of each IMAGE (the existing unit pooling on (U, S, C)), one row block per question
@@ -216,7 +226,9 @@ class AttHeadFn(torch.autograd.Function):
         return ops.glimpse_pool_fwd_grouped(feat, logits, grp[0], lens=None if lens is None else lens[0])
 
     @staticmethod
-    def _pool_bwd(dpooled, feat, wts, unit, need_dfeat, grp, NS, G, lens=None):
+    def _pool_bwd(dpooled, feat, wts, unit, need_dfeat, grp, NS, G, lens=None, pack=None):
+        if pack is not None and not (grp is not None and unit):
+            return ops.glimpse_pool_bwd_packed(dpooled, feat, wts, pack[0], unit, idx=None if grp is None else grp[0]), None
         if grp is None:
             return ops.glimpse_pool_bwd(dpooled, feat, wts, unit, need_dfeat, lens=lens)
         if need_dfeat:
@@ -226,13 +238,18 @@ class AttHeadFn(torch.autograd.Function):
         return ops.glimpse_pool_bwd_grouped(dpooled, feat, wts, grp[0], grp[1], grp[2], False, lens=None if lens is None else lens[0])
 
     @staticmethod
-    def forward(ctx, x, feat, w1, b1, wm, bm, w2, b2, unit_softmax, bf16=False, link=None, same_src=False, grp=None, lens=None):
+    def forward(ctx, x, feat, w1, b1, wm, bm, w2, b2, unit_softmax, bf16=False, link=None, same_src=False, grp=None, lens=None,
+                pack=None):
         x = _c(x)
         feat = _c(feat)
         ctx.bf16 = bool(bf16)
         ctx.same_src = bool(same_src)
         ctx.grp = grp
         ctx.lens = lens
+        ctx.pack = pack
+        if pack is not None and (ctx.bf16 or ctx.same_src or feat.dtype != torch.float32 or feat.dim() != 2 or lens is not None
+                                 or ctx.needs_input_grad[1]):
+            raise ops._l.VqfError("AttHeadFn: packed rows (pack) are fp32 only, a 2-D feature tensor that is data, without lens")
         if lens is not None and (ctx.bf16 or ctx.same_src or feat.dtype != torch.float32 or ctx.needs_input_grad[1]):
             raise ops._l.VqfError("AttHeadFn: region counts (lens) are fp32 only, for a feature tensor that is data")
         if grp is not None and (ctx.bf16 or ctx.same_src or feat.dtype != torch.float32):
@@ -255,7 +272,7 @@ class AttHeadFn(torch.autograd.Function):
             else:
                 hid1 = ops.gemm_rowscale(x, _w2d(w1), link.inv, link.L, bias=b1, relu=True)
             logits, lin = ops.att_logits_fwd_lin(hid1, _w2d(w2), b2, b1)
-            wts, pooled = AttHeadFn._pool_fwd(feat, logits, unit_softmax, grp, lens)
+            wts, pooled = AttHeadFn._pool_fwd(feat, logits, unit_softmax, grp, lens, pack)
             # (bf16 mode: slot 3 -- no "multilayer" conv with a NormLink -- carries the bf16 copy of w1 to the backward: one cast per step)
             ctx.save_for_backward(x, feat, w1, w1b if ctx.bf16 else None, w2, hid1, None, wts, lin)
             ctx.unit = bool(unit_softmax)
@@ -273,7 +290,7 @@ class AttHeadFn(torch.autograd.Function):
         hid2 = ops.gemm(hid1, _w2d(wm), bias=bm, relu=True) if wm is not None else None
         last = hid2 if hid2 is not None else hid1
         logits = ops.att_logits_fwd(last, _w2d(w2), b2)
-        wts, pooled = AttHeadFn._pool_fwd(feat, logits, unit_softmax, grp, lens)
+        wts, pooled = AttHeadFn._pool_fwd(feat, logits, unit_softmax, grp, lens, pack)
         ctx.save_for_backward(x, feat, w1, wm, w2, hid1, hid2, wts, w1b if ctx.bf16 else None)      # (last slot: the bf16 copy of w1)
         ctx.unit = bool(unit_softmax)
         return pooled
@@ -284,7 +301,7 @@ class AttHeadFn(torch.autograd.Function):
         dpooled = _c(dpooled)
         need_dfeat = ctx.needs_input_grad[1]
         dlogits, dfeat = AttHeadFn._pool_bwd(dpooled, feat, wts, ctx.unit, need_dfeat, ctx.grp, hid1.shape[0], _w2d(w2).shape[0],
-                                             ctx.lens)
+                                             ctx.lens, ctx.pack)
         if ctx.link is not None:
             link = ctx.link
             w1b = wm                                       # (slot 3, see forward)
@@ -297,10 +314,10 @@ class AttHeadFn(torch.autograd.Function):
                 d1b = d1s if obf else ops.cast_bf16(d1s)
                 dw1 = ops.gemm_bf16(d1b, x, ta=True, tb=True)[:, :cin].contiguous().view_as(w1)
                 dx = ops.gemm_bf16(d1b, w1b, tb=True, N=cin) if ctx.needs_input_grad[0] else None
-                return dx, dfeat, dw1, db1, None, None, dw2.view_as(w2), db2, None, None, None, None, None, None
+                return dx, dfeat, dw1, db1, None, None, dw2.view_as(w2), db2, None, None, None, None, None, None, None
             dw1 = ops.gemm(d1s, x, ta=True, tb=True).view_as(w1)                    # = dpre^T Y
             dx = ops.gemm(d1s, _w2d(w1), tb=True) if ctx.needs_input_grad[0] else None   # dYs = dY / norm
-            return dx, dfeat, dw1, db1, None, None, dw2.view_as(w2), db2, None, None, None, None, None, None
+            return dx, dfeat, dw1, db1, None, None, dw2.view_as(w2), db2, None, None, None, None, None, None, None
         last = hid2 if hid2 is not None else hid1
         dlast_pre, dw2, db2, dblast = ops.att_logits_bwd(dlogits, last, _w2d(w2), relu_mask=True)
         dwm = dbm = None
@@ -325,7 +342,7 @@ class AttHeadFn(torch.autograd.Function):
                 dx = None
             else:
                 dx = ops.gemm(d1_pre, _w2d(w1), tb=True) if ctx.needs_input_grad[0] else None
-        return dx, dfeat, dw1, db1, dwm, dbm, dw2.view_as(w2), db2, None, None, None, None, None, None
+        return dx, dfeat, dw1, db1, dwm, dbm, dw2.view_as(w2), db2, None, None, None, None, None, None, None
 
 
 def _arm_link(link, inv, L, xb=None):
@@ -358,12 +375,15 @@ class ImgFuseFn(torch.autograd.Function):
     lens (None, or the region counts: an int32 (N,) tensor, with grp the pair (lens_q (N,), lens_u (U,)); fp32 only): sample n has
     lens[n] real regions.  The projection and its weight gradient still run over every row; the fusion reads no padded row of P
     and hands back exact zero dP rows there, so finite padding cancels in the weight gradient.
+    pack (None, or (roff, L) of the packed call form; fp32 only, no lens): img is (1, R, D), the real rows of every image one after the
+    other, roff the int32 row offsets ((N + 1,), with grp (U + 1,) per image) and L the padded width of Y.  The projection and its
+    weight gradient run on the R real rows (P and dP are (R, 5000)); Y stays (N*L, 1000) with exact zero rows beyond each count.
     """
 
     BF16_P = True      # bf16 mode: store P in bf16 when the large-tile GEMM applies (A/B switch)
 
     @staticmethod
-    def forward(ctx, img, wi, bi, q, keep, seed, p_drop, bf16=False, link=None, grp=None, lens=None):
+    def forward(ctx, img, wi, bi, q, keep, seed, p_drop, bf16=False, link=None, grp=None, lens=None, pack=None):
         img = _c(img)
         q = _c(q)
         N, L, D = img.shape
@@ -372,6 +392,18 @@ class ImgFuseFn(torch.autograd.Function):
         ctx.bf16 = bool(bf16)
         ctx.grp = grp
         ctx.lens = lens
+        ctx.pack = pack
+        if pack is not None:
+            if ctx.bf16 or img.dtype != torch.float32 or lens is not None:
+                raise ops._l.VqfError("ImgFuseFn: packed rows (pack) are fp32 only and carry their own counts (no lens)")
+            N, L = q.shape[0], pack[1]
+            P = ops.gemm(img.view(-1, D), wi2, bias=bi)                        # the real rows only
+            Y, norm, inv = ops.mfb_fuse_fwd_packed(P, q, pack[0], N, L, O, idx=None if grp is None else grp[0], keep=keep, seed=seed,
+                                                   p_drop=p_drop, normalise=link is None)
+            ctx.link = _arm_link(link, inv, L, None)
+            ctx.save_for_backward(img, wi, q, P, Y, norm, inv, keep)
+            ctx.seed, ctx.p_drop, ctx.dims = seed, p_drop, (N, L, D, O)
+            return Y
         if lens is not None and (ctx.bf16 or img.dtype != torch.float32):
             raise ops._l.VqfError("ImgFuseFn: region counts (lens) are fp32 only")
         if grp is not None:
@@ -408,13 +440,18 @@ class ImgFuseFn(torch.autograd.Function):
     def backward(ctx, dY):
         img, wi, q, P, Y, norm, inv, keep = ctx.saved_tensors
         N, L, D, O = ctx.dims
+        if ctx.pack is not None:
+            dP, dq, dbi = ops.mfb_fuse_bwd_packed(_c(dY), Y, norm, inv, P, q, ctx.pack[0], N, L, O, grp=ctx.grp, keep=keep,
+                                                  seed=ctx.seed, p_drop=ctx.p_drop, want_dbias=True, lin=_take_lin(ctx.link))
+            dwi = ops.gemm(dP, img.view(-1, D), ta=True, tb=True).view_as(wi)      # wgrad, K = R
+            return None, dwi, dbi, dq, None, None, None, None, None, None, None, None
         if ctx.grp is not None:
             U = img.shape[0]
             dP, dq, dbi = ops.mfb_fuse_bwd_grouped(_c(dY), Y, norm, inv, P, q, ctx.grp[0], ctx.grp[1], ctx.grp[2], N, U, L, O,
                                                    keep=keep, seed=ctx.seed, p_drop=ctx.p_drop, want_dbias=True,
                                                    lin=_take_lin(ctx.link), lens=ctx.lens)
             dwi = ops.gemm(dP, img.view(U * L, D), ta=True, tb=True).view_as(wi)   # wgrad, K = U*L
-            return None, dwi, dbi, dq, None, None, None, None, None, None, None
+            return None, dwi, dbi, dq, None, None, None, None, None, None, None, None
         dP, dq, _, dbi = ops.mfb_fuse_bwd(_c(dY), Y, norm, inv, P, q, N, L, O, keep=keep, seed=ctx.seed,
                                           p_drop=ctx.p_drop, want_dbias=True, dp_bf16=ctx.bf16, lin=_take_lin(ctx.link),
                                           lens=ctx.lens)
@@ -422,7 +459,7 @@ class ImgFuseFn(torch.autograd.Function):
             dwi = ops.gemm_bf16(dP, img, ta=True, tb=True).view_as(wi)
         else:
             dwi = ops.gemm(dP, img.view(N * L, D), ta=True, tb=True).view_as(wi)   # wgrad, K = N*L
-        return None, dwi, dbi, dq, None, None, None, None, None, None, None
+        return None, dwi, dbi, dq, None, None, None, None, None, None, None, None
 
 
 class ImgProjFn(torch.autograd.Function):
@@ -537,14 +574,26 @@ class MfbFuseFn(torch.autograd.Function):
     grp (None, or (idx, order, grp_off) of grouping._group_index; fp32 only): P0 is (U*L, 5000), the projection of the U images
     the N questions share; dP comes back (U*L, 5000), summed over each image's questions, so the projection node behind it
     (ImgProjFn / ImgProjDeferFn / ImgProjLateFn) runs its weight gradient with K = U*L.
-    lens: the region counts, as in ImgFuseFn (fp32 P0 only): no padded row of P0 is read, the padded rows of dP are exact zeros."""
+    lens: the region counts, as in ImgFuseFn (fp32 P0 only): no padded row of P0 is read, the padded rows of dP are exact zeros.
+    pack: (roff, L) of the packed call form, as in ImgFuseFn (fp32 P0 only, no lens): P0 and dP are (R, 5000), the real rows."""
 
     @staticmethod
-    def forward(ctx, P0, bi, q, keep, seed, p_drop, N, L, link=None, grp=None, lens=None):
+    def forward(ctx, P0, bi, q, keep, seed, p_drop, N, L, link=None, grp=None, lens=None, pack=None):
         P0, q = _c(P0), _c(q)
         O = P0.shape[1] // ops.POOL_K
         ctx.grp = grp
         ctx.lens = lens
+        ctx.pack = pack
+        if pack is not None:
+            if P0.dtype != torch.float32 or lens is not None:
+                raise ops._l.VqfError("MfbFuseFn: packed rows (pack) are fp32 only and carry their own counts (no lens), got a %s "
+                                      "projection" % P0.dtype)
+            Y, norm, inv = ops.mfb_fuse_fwd_packed(P0, q, pack[0], N, L, O, idx=None if grp is None else grp[0], keep=keep, seed=seed,
+                                                   p_drop=p_drop, pbias=bi, normalise=link is None)
+            ctx.link = _arm_link(link, inv, L, None)
+            ctx.save_for_backward(P0, bi, q, Y, norm, inv, keep)
+            ctx.seed, ctx.p_drop, ctx.dims = seed, p_drop, (N, L, O)
+            return Y
         if lens is not None and P0.dtype != torch.float32:
             raise ops._l.VqfError("MfbFuseFn: region counts (lens) are fp32 only, got a %s projection" % P0.dtype)
         if grp is not None:
@@ -569,15 +618,19 @@ class MfbFuseFn(torch.autograd.Function):
     def backward(ctx, dY):
         P0, bi, q, Y, norm, inv, keep = ctx.saved_tensors
         N, L, O = ctx.dims
+        if ctx.pack is not None:
+            dP, dq, dbi = ops.mfb_fuse_bwd_packed(_c(dY), Y, norm, inv, P0, q, ctx.pack[0], N, L, O, grp=ctx.grp, keep=keep,
+                                                  seed=ctx.seed, p_drop=ctx.p_drop, want_dbias=True, pbias=bi, lin=_take_lin(ctx.link))
+            return dP, dbi, dq, None, None, None, None, None, None, None, None, None
         if ctx.grp is not None:
             dP, dq, dbi = ops.mfb_fuse_bwd_grouped(_c(dY), Y, norm, inv, P0, q, ctx.grp[0], ctx.grp[1], ctx.grp[2], N,
                                                    P0.shape[0] // L, L, O, keep=keep, seed=ctx.seed, p_drop=ctx.p_drop,
                                                    want_dbias=True, pbias=bi, lin=_take_lin(ctx.link), lens=ctx.lens)
-            return dP, dbi, dq, None, None, None, None, None, None, None, None
+            return dP, dbi, dq, None, None, None, None, None, None, None, None, None
         dP, dq, _, dbi = ops.mfb_fuse_bwd(_c(dY), Y, norm, inv, P0, q, N, L, O, keep=keep, seed=ctx.seed,
                                           p_drop=ctx.p_drop, want_dbias=True, pbias=bi, lin=_take_lin(ctx.link),
                                           dp_bf16=P0.dtype == torch.bfloat16, lens=ctx.lens)
-        return dP, dbi, dq, None, None, None, None, None, None, None, None
+        return dP, dbi, dq, None, None, None, None, None, None, None, None, None
 
 
 class _Fork:
@@ -1226,11 +1279,19 @@ class LstmBatchFn(torch.autograd.Function):
 class UnitPoolFn(torch.autograd.Function):
     """pooled[n, g*C + c] = sum_s feat[n, s, c] for g < G: the glimpse sums under mfb.py:84,118's
     singleton-axis softmax (weights == 1), without the attention MLP in front (MFB's `pruned` mode).
-    lens (None, or (N,) int32; fp32 feat): the sum runs over s < lens[n] (weight 0 beyond)."""
+    lens (None, or (N,) int32; fp32 feat): the sum runs over s < lens[n] (weight 0 beyond).
+    pack (None, or (roff, L) of the packed call form): feat is (R, C) data, the real rows of every image; one sum per owner of roff."""
 
     @staticmethod
-    def forward(ctx, feat, G, lens=None):
+    def forward(ctx, feat, G, lens=None, pack=None):
         feat = _c(feat)
+        if pack is not None:
+            if lens is not None or feat.dim() != 2 or ctx.needs_input_grad[0]:
+                raise ops._l.VqfError("UnitPoolFn: packed rows (pack) are a 2-D feature tensor that is data, without lens")
+            roff, L = pack
+            owners = roff.shape[0] - 1
+            logits = torch.zeros((owners * L, G), dtype=torch.float32, device=feat.device)     # ignored under unit weights
+            return ops.glimpse_pool_fwd_packed(feat, logits, roff, owners, L, True)[1]
         N, S, C = feat.shape
         logits = torch.zeros((N * S, G), dtype=torch.float32, device=feat.device)     # ignored under unit weights
         wts, pooled = ops.glimpse_pool_fwd(feat, logits, True, lens=lens)
@@ -1242,9 +1303,9 @@ class UnitPoolFn(torch.autograd.Function):
     def backward(ctx, dpooled):
         feat, wts = ctx.saved_tensors
         if not ctx.needs_input_grad[0]:
-            return None, None, None
+            return None, None, None, None
         _, dfeat = ops.glimpse_pool_bwd(_c(dpooled), feat, wts, True, True, lens=ctx.lens)
-        return dfeat, None, None
+        return dfeat, None, None, None
 
 
 class DeadParamsFn(torch.autograd.Function):

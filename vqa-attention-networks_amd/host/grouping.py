@@ -1,5 +1,6 @@
 """Batches whose questions share images: the index machinery of forward(..., img_index) (HieCoAttenLadder, MFB, MHBCoAtt),
-and the region counts of forward((img, img_length), ...) (MFB, MHBCoAtt).
+the region counts of forward((img, img_length), ...) (MFB, MHBCoAtt) and the packed region features of
+forward(PackedRegions(rows, offsets, max_regions), ...) (MFB, MHBCoAtt).
 
 img_index (N,) says which of the U images of the batch question n looks at.  It is never read on the host: _group_index clamps
 it and derives, on the device, what the grouped kernels of include/vqa_fusion.h take (idx / order / grp_off), and every kernel
@@ -58,3 +59,54 @@ def _region_lens(img_length, L, idx=None):
     if idx is None:
         return lens
     return lens[idx.to(torch.int64)].contiguous(), lens
+
+
+class PackedRegions:
+    """Region features that were never padded (forward(PackedRegions(rows, offsets, max_regions), ...); MFB, MHBCoAtt, fp32):
+    rows (R, D) holds every image's real regions, one image after the other; image i owns rows offsets[i] .. offsets[i + 1] - 1
+    (offsets (N + 1,) int64 / int32 -- (U + 1,) with img_index --, offsets[0] = 0, non-decreasing, offsets[-1] = R, every count
+    in [1, max_regions]); max_regions is a Python int L in [1, 1024], the padded width of what stays per (image, region) slot.
+    The model's result is, by definition, its result on (unpack(), ...): the region-count call.  data_loader.pack_region_features
+    builds one on the CPU; .to(device) moves both tensors.  The models never read offsets on the host."""
+    __slots__ = ("rows", "offsets", "max_regions")
+
+    def __init__(self, rows, offsets, max_regions):
+        self.rows, self.offsets, self.max_regions = rows, offsets, max_regions
+
+    def to(self, device, non_blocking=False):
+        return PackedRegions(self.rows.to(device, non_blocking=non_blocking), self.offsets.to(device, non_blocking=non_blocking),
+                             self.max_regions)
+
+    def unpack(self):
+        """-> (img (N, L, D) zero-padded on the right, img_length (N,) int64) on the tensors' devices: what
+        data_loader.pad_region_features returns for the same features."""
+        off = self.offsets.to(torch.int64)
+        R, D = self.rows.shape
+        N, L = off.numel() - 1, int(self.max_regions)
+        counts = off[1:] - off[:-1]
+        dev = self.rows.device
+        owner = torch.repeat_interleave(torch.arange(N, device=off.device), counts, output_size=R).to(dev)
+        pos = torch.arange(R, device=dev) - off.to(dev)[owner]
+        img = torch.zeros((N, L, D), dtype=self.rows.dtype, device=dev)
+        img[owner, pos] = self.rows
+        return img, counts
+
+
+def check_packed_regions(who, packed, owners, device):
+    """The refusals of forward(PackedRegions, ...) that concern the object itself: rows 2-D fp32, offsets an int64 / int32 tensor of
+    shape (owners + 1,) on the questions' device (owners = N, or U with img_index), max_regions an int in [1, 1024].  Raises VqfError
+    naming what was passed."""
+    rows, off, L = packed.rows, packed.offsets, packed.max_regions
+    if not torch.is_tensor(rows) or rows.dim() != 2 or rows.dtype != torch.float32 or rows.shape[0] < 1:
+        raise VqfError("%s: PackedRegions.rows must be a 2-D fp32 tensor (R, D) with R >= 1, got %s"
+                       % (who, "%s %s" % (rows.dtype, tuple(rows.shape)) if torch.is_tensor(rows) else type(rows).__name__))
+    if not torch.is_tensor(off) or off.dtype not in (torch.int64, torch.int32):
+        raise VqfError("%s: PackedRegions.offsets must be an int64 or int32 tensor, got %s"
+                       % (who, off.dtype if torch.is_tensor(off) else type(off).__name__))
+    if tuple(off.shape) != (owners + 1,):
+        raise VqfError("%s: PackedRegions.offsets must have shape (%d,) (one more than the images), got %s"
+                       % (who, owners + 1, tuple(off.shape)))
+    if off.device != device:
+        raise VqfError("%s: PackedRegions.offsets must be on the questions' device (%s), got %s" % (who, device, off.device))
+    if isinstance(L, bool) or not isinstance(L, int) or not 1 <= L <= 1024:
+        raise VqfError("%s: PackedRegions.max_regions must be a Python int in [1, 1024], got %r" % (who, L))

@@ -168,6 +168,17 @@ SIGNATURES = {
                                            c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_p, c_sz, c_p]),
     "vqf_glimpse_pool_fwd_grouped_len": (c_i, [c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
     "vqf_glimpse_pool_bwd_grouped_len": (c_i, [c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
+    # the packed forms (forward(PackedRegions, ...)): P / dP / feat hold the real rows only, roff device int32 row offsets (c_p)
+    "vqf_mfb_fuse_packed_supported": (c_i, [c_i, c_i, c_i, c_i, c_i]),
+    "vqf_mfb_fuse_fwd_packed": (c_i, [c_f, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
+    "vqf_mfb_fuse_bwd_packed": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float,
+                                      c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_p, c_sz, c_p]),
+    "vqf_mfb_fuse_fwd_grouped_packed": (c_i, [c_f, c_f, c_f, c_p, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_i, c_f, c_f,
+                                              c_p]),
+    "vqf_mfb_fuse_bwd_grouped_packed": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_u64, ctypes.c_float,
+                                              c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_p, c_sz, c_p]),
+    "vqf_glimpse_pool_fwd_packed": (c_i, [c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
+    "vqf_glimpse_pool_bwd_packed": (c_i, [c_f, c_f, c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
     "vqf_lstm_seq_supported": (c_i, [c_i, c_i]),
     "vqf_lstm_seq_ws_bytes": (c_sz, [c_i, c_i]),
     "vqf_lstm_seq_fwd": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_p, c_sz, c_p]),

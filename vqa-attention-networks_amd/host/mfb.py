@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .grouping import _group_index, _region_lens, check_img_index, check_img_length
+from .grouping import _group_index, _region_lens, check_img_index, check_img_length, check_packed_regions, PackedRegions
 from .functions import (LinearFn, AttHeadFn, ImgFuseFn, ImgProjFn, ImgProjLateFn, ImgProjDeferFn, MfbFuseFn, FinalMfbFn,
                         LstmBatchFn, UnitPoolFn, DeadParamsFn, NormLink, img_project, embed_tanh, lstm_out_dropout)
 
@@ -75,11 +75,41 @@ def split_region_features(who, img_features):
     the features they describe, as data_loader.pad_region_features returns them."""
     from .lib import VqfError
     if isinstance(img_features, (tuple, list)):
+        if any(isinstance(t, PackedRegions) for t in img_features):
+            raise VqfError("%s: a PackedRegions carries its own counts and is passed on its own, not inside a pair (img, img_length)"
+                           % who)
         if len(img_features) != 2 or not torch.is_tensor(img_features[0]):
             raise VqfError("%s: img_features must be a tensor or the pair (img (N, L, D), img_length (N,)), got a %s of %d"
                            % (who, type(img_features).__name__, len(img_features)))
         return img_features[0], img_features[1]
     return img_features, None
+
+
+def packed_region_rows(who, packed, questions, img_index, gemm_dtype):
+    """forward(PackedRegions(rows, offsets, max_regions), ...): the refusals of the packed call and what the nodes take
+    -> (rows (R, D), pack = (roff int32 on the device, L), grp or None).  offsets is (N + 1,), or (U + 1,) with img_index; it is
+    converted on the device and never read on the host (the kernels clamp what it holds)."""
+    from .lib import VqfError
+    if gemm_dtype != "fp32":
+        raise VqfError("%s: PackedRegions is fp32 only (the packed fusion kernels have no bf16 form); got gemm_dtype=%r"
+                       % (who, gemm_dtype))
+    N = questions.shape[0]
+    U = N if img_index is None else (packed.offsets.numel() - 1 if torch.is_tensor(packed.offsets) else -1)
+    check_packed_regions(who, packed, U, questions.device)
+    rows, L = packed.rows, packed.max_regions
+    _image_is_data(rows, gemm_dtype)
+    if rows.device != questions.device:
+        raise VqfError("%s: PackedRegions.rows must be on the questions' device (%s), got %s" % (who, questions.device, rows.device))
+    R, D = rows.shape
+    grp = None
+    if img_index is not None:
+        check_img_index(who, img_index, N, U, questions.device)
+        grp = _group_index(img_index, U)
+    if not (1 <= N <= 65535 and ops.mfb_fuse_packed_supported(N, U, R, L, 1000) and ops.glimpse_pool_grouped_supported(N, U, L, D, 2)
+            and (grp is None or ops.row_block_supported(N, U, 2 * D))):
+        raise VqfError("%s: PackedRegions needs at most 65535 questions and images and a channel count that is a multiple of 4 "
+                       "(got U=%d, N=%d, R=%d, L=%d, D=%d)" % (who, U, N, R, L, D))
+    return rows.contiguous(), (packed.offsets.to(torch.int32).contiguous(), L), grp
 
 
 _warned = set()
@@ -264,13 +294,14 @@ class MFB(nn.Module):
         """Test hook: explicit uint8 keep-masks 'm1' (N*L,5000), 'm2' (N,5000) instead of Philox."""
         self._seeds.keep = masks
 
-    def _forward_pruned(self, img_features, ques_feature, keep, grp=None, lens=None):
+    def _forward_pruned(self, img_features, ques_feature, keep, grp=None, lens=None, pack=None):
         """The live part of the reference graph when both softmaxes are over a singleton axis."""
         pm = self.dropout_m.p
         qa = UnitPoolFn.apply(ques_feature, 2)                             # (N, 2H)   mfb.py:85-89 with weights 1
         self._seeds.next(self.training, pm)                                # the regions' dropout draw (unused, keeps the stream)
         # (N, 2D)   mfb.py:119-123 with weights 1 (img_length: on the real regions; per image when the images are shared)
-        va = UnitPoolFn.apply(img_features, 2, lens if grp is None or lens is None else lens[1])
+        # (packed rows: one sum per owner of the row offsets -- per image when the images are shared)
+        va = UnitPoolFn.apply(img_features, 2, lens if grp is None or lens is None else lens[1], pack)
         if grp is not None:                                                # per image (U, 2D), one row block per question
             va = ops.row_block_gather(va, grp[0])
         seed, p = self._seeds.next(self.training, pm)
@@ -297,11 +328,22 @@ class MFB(nn.Module):
         norm, the co-attention softmax (under unit_softmax: the region sum) and every gradient run over the real regions, and
         no padded row of the projection is read.  The padded rows of img_features may hold any FINITE values: img_conv1d and
         its weight gradient still run over all L rows and the padding cancels because its dP rows are exact zeros -- a NaN or
-        Inf in a padded row would reach img_conv1d's weight gradient.  data_loader.pad_region_features builds such a batch."""
-        img_features, img_length = split_region_features("MFB", img_features)
-        _image_is_data(img_features, self.gemm_dtype)
-        grp = None if img_index is None else shared_image_groups("MFB", img_features, questions, img_index, self.gemm_dtype)
-        lens = None if img_length is None else image_region_lens("MFB", img_features, questions, img_length, grp, self.gemm_dtype)
+        Inf in a padded row would reach img_conv1d's weight gradient.  data_loader.pad_region_features builds such a batch.
+        Packed regions: img_features may be a PackedRegions(rows, offsets, max_regions) -- what data_loader.pack_region_features
+        returns, moved to the GPU with .to(device): rows (R, D) fp32 are every image's real regions, one image after the other,
+        never padded; offsets (N + 1,), or (U + 1,) per image with img_index, int64 / int32 on the questions' device; max_regions a
+        Python int L in [1, 1024], at least the largest count (fp32 only).  The result is this model on (packed.unpack(), ...),
+        the region-count call; img_conv1d and its weight gradient run on the R real rows only."""
+        pack = None
+        if isinstance(img_features, PackedRegions):
+            img_features, pack, grp = packed_region_rows("MFB", img_features, questions, img_index, self.gemm_dtype)
+            lens = None
+        else:
+            img_features, img_length = split_region_features("MFB", img_features)
+            _image_is_data(img_features, self.gemm_dtype)
+            grp = None if img_index is None else shared_image_groups("MFB", img_features, questions, img_index, self.gemm_dtype)
+            lens = None if img_length is None else image_region_lens("MFB", img_features, questions, img_length, grp, self.gemm_dtype)
+        img3 = img_features if pack is None else img_features.unsqueeze(0)     # the projection nodes only flatten: rows as (1, R, D)
         bf16_img = self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
         bf16_all = self.gemm_dtype == "bf16-all"          # also ques_proj*, img_proj*, the question-attention conv
         # a5 starts first, on the side stream: it only needs the image and its weights
@@ -310,7 +352,7 @@ class MFB(nn.Module):
         # (a real second stream -- overlap_streams is True -- keeps the bf16 hand-off too: MfbFuseFn takes / returns bf16)
         side = self.overlap_streams and not (bf16_img and self.fuse_bf16_dp and not (self.overlap_streams is True and self.side_bf16)) \
             and not (self.pruned and self.unit_softmax)
-        proj = self._side.project(img_features, self.img_conv1d, bf16_img,
+        proj = self._side.project(img3, self.img_conv1d, bf16_img,
                                   self.overlap_streams == "same-stream", self.side_cu_limit) if side else None
         # a2: question encoder                                               mfb.py:68-70
         # (the lookup writes (T,N,E) directly when the recursion runs on the HIP path: no transposing copy in between)
@@ -320,10 +362,10 @@ class MFB(nn.Module):
         lstm_o = batch_first_lstm(self.lstm, que_embedded, self.use_hip_lstm, _lstm_bf16(self.gemm_dtype), time_major_in=tm)
         ques_feature = lstm_out_dropout(self.dropout_l, lstm_o, self._seeds)   # (N,T,H) contiguous; mfb.py:70
         N, T, H = ques_feature.shape
-        L = img_features.shape[1]
+        L = img_features.shape[1] if pack is None else pack[1]
         keep = self._seeds.keep
         if self.pruned and self.unit_softmax:
-            return self._forward_pruned(img_features, ques_feature, keep, grp, lens)
+            return self._forward_pruned(img_features, ques_feature, keep, grp, lens, pack)
 
         # a3: question attention                                             mfb.py:73-89
         wm, bm = self._mc('ques_att_multiconv')
@@ -340,15 +382,16 @@ class MFB(nn.Module):
         link = NormLink() if (self.fold_norm and not self.multilayer) else None
         if proj is not None:
             P0 = self._side.join(*proj)
-            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, grp, lens)
+            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, grp, lens, pack)
         else:
-            Y = ImgFuseFn.apply(img_features, self.img_conv1d.weight, self.img_conv1d.bias, qp,
-                                k1, seed, pm if k1 is not None else p, bf16_img, link, grp, lens)
+            Y = ImgFuseFn.apply(img3, self.img_conv1d.weight, self.img_conv1d.bias, qp,
+                                k1, seed, pm if k1 is not None else p, bf16_img, link, grp, lens, pack)
         # a7+a8: co-attention over the regions                               mfb.py:109-123
         # (with a link Y is the un-normalised R and 1/norm rides in co_att_conv1's GEMM epilogue)
         wm, bm = self._mc('co_att_multiconv')
         va = AttHeadFn.apply(Y, img_features, self.co_att_conv1.weight, self.co_att_conv1.bias, wm, bm,
-                             self.co_att_conv2.weight, self.co_att_conv2.bias, self.unit_softmax, coatt_bf16, link, False, grp, lens)
+                             self.co_att_conv2.weight, self.co_att_conv2.bias, self.unit_softmax, coatt_bf16, link, False, grp, lens,
+                             pack)
         # a9: final MFB block                                                mfb.py:126-135
         seed, p = self._seeds.next(self.training, pm)
         k2 = keep.get('m2')

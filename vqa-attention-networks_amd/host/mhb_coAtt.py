@@ -11,7 +11,8 @@ from . import ops
 from .functions import (LinearFn, Linear2Fn, AttHeadFn, ImgFuseFn, MfbFuseFn, FinalMfbFn, LstmSeqFn, LstmBatchFn, LogSoftmaxRowsFn,
                         NormLink, embed_tanh, embed, lstm_out_dropout)
 from .mfb import (_DropSeeds, _image_is_data, _SideStream, _lstm_bf16, batch_first_lstm, warn_once, shared_image_groups,
-                  image_region_lens, split_region_features)
+                  image_region_lens, split_region_features, packed_region_rows)
+from .grouping import PackedRegions
 
 
 class MHBCoAtt(nn.Module):
@@ -57,15 +58,23 @@ class MHBCoAtt(nn.Module):
         Region counts: see MFB.forward -- img_features may be the pair (img, img_length), one count per image ((N,), or (U,) with
         img_index; fp32 only); the fusion's norm and
         the co-attention softmax run over each image's real regions.  The padded rows of img_features must be FINITE: the
-        projection and its weight gradient still run over them, and they cancel only because their dP rows are exact zeros."""
-        img_features, img_length = split_region_features("MHBCoAtt", img_features)
-        _image_is_data(img_features, self.gemm_dtype)
-        grp = None if img_index is None else shared_image_groups("MHBCoAtt", img_features, questions, img_index, self.gemm_dtype)
-        lens = None if img_length is None else image_region_lens("MHBCoAtt", img_features, questions, img_length, grp,
-                                                                 self.gemm_dtype)
-        N, L, D = img_features.shape
-        if grp is not None:
-            N = questions.shape[0]
+        projection and its weight gradient still run over them, and they cancel only because their dP rows are exact zeros.
+        Packed regions: see MFB.forward -- img_features may be a PackedRegions(rows, offsets, max_regions) (fp32 only): the real
+        regions of every image, never padded; the result is this model on (packed.unpack(), ...)."""
+        pack = None
+        if isinstance(img_features, PackedRegions):
+            img_features, pack, grp = packed_region_rows("MHBCoAtt", img_features, questions, img_index, self.gemm_dtype)
+            lens, L = None, pack[1]
+            img3 = img_features.unsqueeze(0)                   # the projection nodes only flatten: rows as (1, R, D)
+        else:
+            img_features, img_length = split_region_features("MHBCoAtt", img_features)
+            _image_is_data(img_features, self.gemm_dtype)
+            grp = None if img_index is None else shared_image_groups("MHBCoAtt", img_features, questions, img_index, self.gemm_dtype)
+            lens = None if img_length is None else image_region_lens("MHBCoAtt", img_features, questions, img_length, grp,
+                                                                     self.gemm_dtype)
+            L = img_features.shape[1]
+            img3 = img_features
+        N = questions.shape[0]
         keep = self._seeds.keep
         bf16_img = self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
         bf16_all = self.gemm_dtype == "bf16-all"          # also ques_proj*, img_proj*, the question-attention conv
@@ -73,7 +82,7 @@ class MHBCoAtt(nn.Module):
         # weight-gradient GEMM in bf16 without an fp32 round trip, which is worth more than the stream overlap
         # (a real second stream -- overlap_streams is True -- keeps the bf16 hand-off too: MfbFuseFn takes / returns bf16)
         side = self.overlap_streams and not (bf16_img and self.fuse_bf16_dp and not (self.overlap_streams is True and self.side_bf16))
-        proj = self._side.project(img_features, self.img_conv1d, bf16_img,
+        proj = self._side.project(img3, self.img_conv1d, bf16_img,
                                   self.overlap_streams == "same-stream", self.side_cu_limit) if side else None
         que_embedded = embed_tanh(self.word_embedding, questions)            # (N,T,E)
         if self.cfg.glove:
@@ -112,12 +121,12 @@ class MHBCoAtt(nn.Module):
         link = NormLink() if self.fold_norm else None
         if proj is not None:
             P0 = self._side.join(*proj)
-            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, grp, lens)
+            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, grp, lens, pack)
         else:
-            Y = ImgFuseFn.apply(img_features, self.img_conv1d.weight, self.img_conv1d.bias, qp,
-                                k1, seed, pm if k1 is not None else p, bf16_img, link, grp, lens)
+            Y = ImgFuseFn.apply(img3, self.img_conv1d.weight, self.img_conv1d.bias, qp,
+                                k1, seed, pm if k1 is not None else p, bf16_img, link, grp, lens, pack)
         va = AttHeadFn.apply(Y, img_features, self.co_att_conv1.weight, self.co_att_conv1.bias, None, None,
-                             self.co_att_conv2.weight, self.co_att_conv2.bias, False, coatt_bf16, link, False, grp, lens)
+                             self.co_att_conv2.weight, self.co_att_conv2.bias, False, coatt_bf16, link, False, grp, lens, pack)
         ys = []
         for tag, qpj, ipj in (('m2', self.ques_proj2, self.img_proj2), ('m3', self.ques_proj3, self.img_proj3)):
             seed, p = self._seeds.next(self.training, pm)

@@ -1296,6 +1296,143 @@ def mfb_fuse_bwd_grouped(dY, Y, norm, inv, P, q, idx, order, grp_off, N, U, L, O
     return dP, dq, db
 
 
+# the packed forms (include/vqa_fusion.h "Packed region features"): P / dP / the pooled features hold the real rows of every image, one
+# image after the other; roff = int32 row offsets, (N + 1) per sample or -- with idx -- (U + 1) per image.  The kernels clamp what
+# roff holds; only its type, shape and device are checked here.
+def mfb_fuse_packed_supported(N, U, R, L, O):
+    return bool(_lib().vqf_mfb_fuse_packed_supported(int(N), int(U), int(R), int(L), int(O)))
+
+
+def _packed_operands(name, P, q, roff, N, U, L, O, pbias):
+    _chk(P, q, pbias)
+    R = P.shape[0] if P.dim() == 2 else 0
+    if P.dim() != 2 or R < 1 or P.shape[1] != POOL_K * O or tuple(q.shape) != (N, POOL_K * O) or \
+            (pbias is not None and tuple(pbias.shape) != (POOL_K * O,)):
+        raise _l.VqfError("%s: P must be a contiguous (R, 5*O) tensor with R >= 1, q (N, 5*O) and pbias (5*O,); got P %s, q %s"
+                          % (name, tuple(P.shape), tuple(q.shape)))
+    if not torch.is_tensor(roff) or not roff.is_cuda or roff.dtype != torch.int32 or not roff.is_contiguous() or \
+            tuple(roff.shape) != (U + 1,):
+        raise _l.VqfError("%s: roff must be a contiguous (%d,) int32 GPU tensor of row offsets" % (name, U + 1))
+    if not mfb_fuse_packed_supported(N, U, R, L, O):
+        raise _l.VqfError("%s: N <= 65535, U <= 65535, L <= 1024, O %% 4 == 0 and O <= 1024 are supported (got N=%d, U=%d, R=%d, "
+                          "L=%d, O=%d)" % (name, N, U, R, L, O))
+    return R
+
+
+def mfb_fuse_fwd_packed(P, q, roff, N, L, O, idx=None, keep=None, seed=0, p_drop=0.0, pbias=None, normalise=True):
+    """The image fusion on packed rows: P (R, 5*O) fp32, q (N, 5*O), roff (N + 1) int32 -- with idx (N) int32: (U + 1), question n
+    reads the rows of image idx[n]; keep (N*L, 5*O) / the Philox draw stay in the padded coordinates
+    -> (Y (N*L, O), norm (N), inv (N)): the bits of mfb_fuse_fwd(lens=) / mfb_fuse_fwd_grouped(lens=) on the zero-padded copy of P."""
+    U = N if idx is None else roff.shape[0] - 1
+    R = _packed_operands("mfb_fuse_fwd_packed", P, q, roff, N, U, L, O, pbias)
+    dev = P.device
+    Y = torch.empty((N * L, O), dtype=torch.float32, device=dev)
+    rowssq = torch.empty(N * L * 4, dtype=torch.float32, device=dev)
+    if idx is None:
+        _l.check(_lib().vqf_mfb_fuse_fwd_packed(_ptr(P), _ptr(pbias), _ptr(q), _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop),
+                                                N, R, L, O, _ptr(Y), _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_packed")
+    else:
+        _chk_group("mfb_fuse_fwd_packed", N, U, idx=idx)
+        _l.check(_lib().vqf_mfb_fuse_fwd_grouped_packed(_ptr(P), _ptr(pbias), _ptr(q), _ptr(idx), _ptr(roff), _keep_ptr(keep), int(seed),
+                                                        float(p_drop), N, U, R, L, O, _ptr(Y), _ptr(rowssq), _stream()),
+                 "vqf_mfb_fuse_fwd_grouped_packed")
+    norm = torch.empty(N, dtype=torch.float32, device=dev)
+    inv = torch.empty(N, dtype=torch.float32, device=dev)
+    _l.check(_lib().vqf_l2_group_norm(_ptr(rowssq), N, 4 * L, _ptr(norm), _ptr(inv), _stream()), "vqf_l2_group_norm")
+    if normalise:
+        _l.check(_lib().vqf_scale_rows(_ptr(Y), _ptr(inv), N * L, L, O, _ptr(Y), _stream()), "vqf_scale_rows")
+    return Y, norm, inv
+
+
+def mfb_fuse_bwd_packed(dY, Y, norm, inv, P, q, roff, N, L, O, grp=None, keep=None, seed=0, p_drop=0.0, want_dbias=False, pbias=None,
+                        lin=None):
+    """-> (dP (R, 5*O), dq (N, 5*O), dbiasP or None).  grp = (idx, order, grp_off): roff is per image and dP sums each image's
+    questions in `order` (zero rows for an image without a question).  lin as in mfb_fuse_bwd."""
+    U = N if grp is None else roff.shape[0] - 1
+    R = _packed_operands("mfb_fuse_bwd_packed", P, q, roff, N, U, L, O, pbias)
+    _chk(dY, Y, norm, inv)
+    if tuple(dY.shape) != (N * L, O) or tuple(Y.shape) != (N * L, O):
+        raise _l.VqfError("mfb_fuse_bwd_packed: dY and Y must be (N*L, O)")
+    dev = P.device
+    cA = torch.empty(N, dtype=torch.float32, device=dev)
+    cB = torch.empty(N, dtype=torch.float32, device=dev)
+    if lin is not None:
+        dl, ln = lin
+        _chk(dl, ln)
+        unit = torch.empty(N, dtype=torch.float32, device=dev)
+        _l.check(_lib().vqf_l2_norm_bwd_coef_lin(_ptr(dl), _ptr(ln), dl.shape[1], _ptr(norm), _ptr(inv), N, L, _ptr(cA),
+                                                 _ptr(cB), _ptr(unit), _stream()), "vqf_l2_norm_bwd_coef_lin")
+        inv = unit
+    else:
+        rowdot = torch.empty(N * L, dtype=torch.float32, device=dev)
+        _l.check(_lib().vqf_rowdot(_ptr(Y), _ptr(dY), N * L, O, _ptr(rowdot), _stream()), "vqf_rowdot")
+        _l.check(_lib().vqf_l2_norm_bwd_coef(_ptr(rowdot), _ptr(norm), _ptr(inv), N, L, _ptr(cA), _ptr(cB),
+                                             _stream()), "vqf_l2_norm_bwd_coef")
+    dP = torch.empty_like(P)
+    dq = torch.empty((N, POOL_K * O), dtype=torch.float32, device=dev)
+    db = torch.empty(POOL_K * O, dtype=torch.float32, device=dev) if want_dbias else None
+    if grp is None:
+        ws = workspace(dev, _lib().vqf_mfb_fuse_bwd_ws_bytes(N, L, O))
+        _l.check(_lib().vqf_mfb_fuse_bwd_packed(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
+                                                _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop), N, R, L, O, _ptr(dP), _ptr(dq),
+                                                _ptr(db), _ptr(ws), ws.numel(), _stream()), "vqf_mfb_fuse_bwd_packed")
+        return dP, dq, db
+    idx, order, grp_off = grp
+    _chk_group("mfb_fuse_bwd_packed", N, U, idx=idx, order=order, grp_off=grp_off)
+    ws = workspace(dev, _lib().vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O))
+    _l.check(_lib().vqf_mfb_fuse_bwd_grouped_packed(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
+                                                    _ptr(idx), _ptr(order), _ptr(grp_off), _ptr(roff), _keep_ptr(keep), int(seed),
+                                                    float(p_drop), N, U, R, L, O, _ptr(dP), _ptr(dq), _ptr(db), _ptr(ws), ws.numel(),
+                                                    _stream()), "vqf_mfb_fuse_bwd_grouped_packed")
+    return dP, dq, db
+
+
+def _pool_packed_dims(name, feat, roff, logits_or_wts_G, N, S, idx):
+    _chk(feat)
+    if feat.dim() != 2 or feat.shape[0] < 1:
+        raise _l.VqfError(name + ": feat must be a contiguous (R, C) fp32 GPU tensor with R >= 1")
+    R, C = feat.shape
+    U = N if idx is None else roff.shape[0] - 1
+    if not torch.is_tensor(roff) or not roff.is_cuda or roff.dtype != torch.int32 or not roff.is_contiguous() or \
+            tuple(roff.shape) != (U + 1,):
+        raise _l.VqfError("%s: roff must be a contiguous (%d,) int32 GPU tensor of row offsets" % (name, U + 1))
+    if idx is not None:
+        _chk_group(name, N, U, idx=idx)
+    if not glimpse_pool_grouped_supported(N, U, S, C, logits_or_wts_G):
+        raise _l.VqfError(name + ": N <= 65535, U <= 65535, S <= 1024, C %% 4 == 0 and G in {1, 2, 3} are supported "
+                          "(got N=%d, U=%d, S=%d, C=%d, G=%d)" % (N, U, S, C, logits_or_wts_G))
+    return U, R, C
+
+
+def glimpse_pool_fwd_packed(feat, logits, roff, N, S, unit_softmax, idx=None):
+    """feat (R, C) packed rows, logits (N*S, G), roff (N + 1) int32 -- with idx (N) int32: (U + 1) per image
+    -> wts (N, G, S) (exact zeros beyond the count), pooled (N, G*C): glimpse_pool_fwd(lens=) / _grouped(lens=) on the padded copy."""
+    _chk(logits)
+    G = logits.shape[1]
+    U, R, C = _pool_packed_dims("glimpse_pool_fwd_packed", feat, roff, G, N, S, idx)
+    if logits.shape[0] != N * S:
+        raise _l.VqfError("glimpse_pool_fwd_packed: logits must be (N*S, G)")
+    wts = torch.empty((N, G, S), dtype=torch.float32, device=feat.device)
+    pooled = torch.empty((N, G * C), dtype=torch.float32, device=feat.device)
+    _l.check(_lib().vqf_glimpse_pool_fwd_packed(_ptr(feat), _ptr(logits), _ptr(idx), _ptr(roff), N, U, R, S, C, G,
+                                                int(bool(unit_softmax)), _ptr(wts), _ptr(pooled), _stream()),
+             "vqf_glimpse_pool_fwd_packed")
+    return wts, pooled
+
+
+def glimpse_pool_bwd_packed(dpooled, feat, wts, roff, unit_softmax, idx=None, dwts=None):
+    """dpooled (N, G*C), feat (R, C) data, wts (N, G, S) -> dlogits (N*S, G), exact zeros beyond the count"""
+    _chk(dpooled, wts, dwts)
+    N, G, S = wts.shape
+    U, R, C = _pool_packed_dims("glimpse_pool_bwd_packed", feat, roff, G, N, S, idx)
+    if tuple(dpooled.shape) != (N, G * C) or (dwts is not None and tuple(dwts.shape) != (N, G, S)):
+        raise _l.VqfError("glimpse_pool_bwd_packed: dpooled must be (N, G*C), wts and dwts (N, G, S)")
+    dlogits = torch.empty((N * S, G), dtype=torch.float32, device=feat.device)
+    _l.check(_lib().vqf_glimpse_pool_bwd_packed(_ptr(dpooled), _ptr(dwts), _ptr(feat), _ptr(wts), _ptr(idx), _ptr(roff), N, U, R, S, C,
+                                                G, int(bool(unit_softmax)), _ptr(dlogits), _stream()), "vqf_glimpse_pool_bwd_packed")
+    return dlogits
+
+
 def lstm_seq_supported(B, H):
     return bool(_lib().vqf_lstm_seq_supported(int(B), int(H)))
 
