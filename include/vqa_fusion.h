@@ -519,6 +519,24 @@ int vqf_tanh_dropout_fwd2d(const float* a, int lda, const float* b, int ldb, con
                            int R, int W, float* y, int ldy, void* stream);
 int vqf_tanh_dropout_bwd2d(const float* dy, int lddy, const float* y, int ldy, const uint8_t* keep, uint64_t seed, float p_drop,
                            int R, int W, float* dx, int lddx, void* stream);
+/* The same tanh / dropout pass as the change of layout between packed and padded rows (HieCoAttenLadder.forward(PackedRegions, ...):
+ * V = drop(tanh(img_emb(rows))) with the product on the R real rows; additions within ABI 7).  z / dz are (R, E), the real rows of
+ * every owner, one owner after the other; y / dy are padded (U*L, E).  roff: device int32 (U + 1), 4-byte aligned, the offsets of
+ * "Packed region features" above, clamped in the kernel by the same rule -- owner u has start = clamp(roff[u], 0, R - 1) and
+ * cnt = clamp(roff[u+1] - roff[u], 1, min(L, R - start)) -- so nothing roff holds makes a kernel read or write outside a tensor.
+ *   unpack_fwd: y[u*L + l, :] = tanh(z[start + l, :]) * keep / (1-p) for l < cnt; rows l >= cnt are exact zeros, nothing is read there.
+ *   pack_bwd:   dz[start + l, :] = dy * keep/(1-p) * (1 - tanh^2) of padded row u*L + l (tanh from y), l < cnt; no padded row of
+ *               dy / y is read, and dz has no padded row.
+ * The dropout index of element (l, c) is (u*L + l)*E + c, that of the padded tensor (keep: (U*L, E) uint8): on well-formed offsets
+ * the real rows carry the bits of vqf_tanh_dropout_fwd / _bwd on the zero-padded operands.  One pass, 16-byte accesses.
+ * Supported: vqf_tanh_dropout_unpack_supported(U, R, L, E) = 1 <= U <= 65535, 1 <= R < 2^29, 1 <= L <= 1024, E % 4 == 0 and
+ * 4 <= E <= 65536; outside VQF_E_UNSUPPORTED.  roff null or misaligned, R <= 0 or another extent <= 0: VQF_E_BADARG; z / y / dy / dz
+ * not 16-byte or keep not 4-byte aligned: VQF_E_ALIGN. */
+int vqf_tanh_dropout_unpack_supported(int U, int R, int L, int E);
+int vqf_tanh_dropout_unpack_fwd(const float* z, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop, int U, int R, int L,
+                                int E, float* y, void* stream);
+int vqf_tanh_dropout_pack_bwd(const float* dy, const float* y, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop, int U,
+                              int R, int L, int E, float* dz, void* stream);
 /* --------------------------------------------------------------------------
  * HieCoAtten's co-attention ladder (hieCoAtten.py:32-49): the stages with a tiny inner / outer extent T (words per question)
  * as single streaming passes over the rows of the (N*L, E) tensors (csrc/hie.hip), neighbouring element-wise stage fused in.

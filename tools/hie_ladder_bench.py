@@ -2,6 +2,7 @@
 
     python tools/hie_ladder_bench.py [--batch 256] [--steps 20] [--warmup 5] [--lengths] [--coatt parallel|alternating] [--json OUT]
                                      [--questions-per-image Q] [--repeats R] [--no-context] [--regions MIN,MAX] [--blocks L]
+                                     [--packed [--rounds K] [--forms packed,pair,plain]]
 
 Prints ms / step and QA pairs / s (device events around the timed steps), the step's FLOP count from the shapes with its
 MFMA floor at 157.3 TF/s (fp32 MFMA peak of the MI355X) and the fraction reached, the library profiler's per-kernel table
@@ -19,7 +20,14 @@ the streaming yardsticks and the HieCoAtten step.
 --regions MIN,MAX: the region-count call, forward((img, img_length), ...) with seeded counts in [MIN, MAX] (one per image, clipped
 to the run's L; MIN = MAX = L times the masked code route at full counts).  The line adds sum(counts) / (images L), the bound
 on what the image-side affinity and rank-T passes can save (their traffic goes with sum(counts)); the products and the logit
-heads stay dense, and the FLOP table is the dense step's.  --blocks L: regions per image (default 196)."""
+heads stay dense, and the FLOP table is the dense step's.  --blocks L: regions per image (default 196).
+--packed (with --regions): the three call forms of ONE batch in one process -- forward(PackedRegions(rows, offsets, L), ...) with the
+real rows of the same images, the pair (img, img_length) and the plain tensor -- on one model, alternating: --rounds K rounds (default
+2) of packed, pair, plain in that order, each --repeats windows of --steps steps after --warmup steps of that form.  Prints every
+round's median and spread per form, the median over all windows per form, packed against pair, and from one profiled step per form the
+launch count and the img_emb launches (the projection M = rows, N = E, K = img and its weight gradient M = E, N = img, K = rows: R rows
+packed, U L otherwise) beside the tanh / dropout passes.  --forms: a subset, in the order to run (pair,plain runs on a tree without the
+packed form)."""
 import argparse
 import json
 import os
@@ -150,6 +158,90 @@ def timed(model, img, ids, target, steps, warmup, q_len=None, img_index=None, re
     return ms, ops.prof_report()
 
 
+def compare_forms(model, img, ids, target, q_len, img_index, img_length, forms, steps, warmup, rounds, repeats):
+    """--packed: the call forms of one batch on one model and one optimizer, alternating -> {form: {"rounds": [[ms per window]],
+    "launches": n, "kernels": prof_report(), "img_emb": {...}}}"""
+    ops = vqa_amd.ops
+    U, L, D = img.shape
+    E = model.img_emb.out_features
+    feats = {"plain": img, "pair": (img, img_length)}
+    rows_of = {"plain": U * L, "pair": U * L}
+    if "packed" in forms:
+        off = torch.zeros(U + 1, dtype=torch.int64, device=img.device)
+        off[1:] = torch.cumsum(img_length.to(torch.int64), 0)
+        real = torch.arange(L, device=img.device).unsqueeze(0) < img_length.unsqueeze(1)
+        rows = img[real].contiguous()                                  # (R, D): the real rows, one image after the other
+        feats["packed"] = vqa_amd.PackedRegions(rows, off, L)
+        rows_of["packed"] = rows.shape[0]
+    crit = vqa_amd.CrossEntropyLoss()
+    opt = vqa_amd.Adam(model.parameters(), lr=1e-4)
+
+    def step(f):
+        opt.zero_grad(set_to_none=True)
+        if img_index is not None:
+            out = model(f, ids, q_len, img_index=img_index)
+        else:
+            out = model(f, ids) if q_len is None else model(f, ids, q_len)
+        crit(out[0], target).backward()
+        opt.step()
+
+    res = {f: {"rounds": [], "rows": rows_of[f]} for f in forms}
+    for _ in range(rounds):
+        for f in forms:
+            for _ in range(warmup):
+                step(feats[f])
+            torch.cuda.synchronize()
+            windows = []
+            for _ in range(max(1, repeats)):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(steps):
+                    step(feats[f])
+                b.record()
+                torch.cuda.synchronize()
+                windows.append(a.elapsed_time(b) / steps)
+            res[f]["rounds"].append(windows)
+    for f in forms:                                                    # one profiled step per form, after the timing
+        ops.prof_reset()
+        ops.prof_enable(True)
+        step(feats[f])
+        torch.cuda.synchronize()
+        ops.prof_enable(False)
+        kern = ops.prof_report()
+        M = rows_of[f]
+        gemms = [k for k in kern if k.startswith("gemm_f32_")]
+        res[f]["kernels"] = kern
+        res[f]["launches"] = sum(n for n, _ in kern.values())
+        res[f]["img_emb"] = {"fwd (M=%d, N=%d, K=%d)" % (M, E, D): [ops.prof_shape(k, M, E, D) + (k,) for k in gemms if ops.prof_shape(k, M, E, D)[0]],
+                             "wgrad (M=%d, N=%d, K=%d)" % (E, D, M): [ops.prof_shape(k, E, D, M) + (k,) for k in gemms if ops.prof_shape(k, E, D, M)[0]]}
+    return res
+
+
+def print_forms(res, forms, steps):
+    med = lambda v: sorted(v)[len(v) // 2]
+    for f in forms:
+        for i, w in enumerate(res[f]["rounds"]):
+            print("  %-7s round %d  median %.3f ms  spread %.3f ms  windows %s  launches/step %d"
+                  % (f, i + 1, med(w), max(w) - min(w), " ".join("%.3f" % x for x in w), res[f]["launches"]))
+    allw = {f: [x for w in res[f]["rounds"] for x in w] for f in forms}
+    print("  median over all windows (of %d steps): %s" % (steps, "   ".join("%s %.3f ms" % (f, med(allw[f])) for f in forms)))
+    if "packed" in forms and "pair" in forms:
+        p, q = med(allw["packed"]), med(allw["pair"])
+        print("  packed against pair: %+.3f ms (%+.2f %%); rows of the img_emb products: %d packed, %d padded (%.3f)"
+              % (p - q, (p / q - 1) * 100, res["packed"]["rows"], res["pair"]["rows"], res["packed"]["rows"] / res["pair"]["rows"]))
+    print("  one profiled step per form (ms; event brackets add a few us per launch):")
+    for f in forms:
+        k = res[f]["kernels"]
+        print("    %s:" % f)
+        for what, hits in res[f]["img_emb"].items():
+            for n, ms, name in hits:
+                print("      img_emb %-32s %-22s %d launch  %7.3f ms" % (what, name, n, ms))
+        for name in ("tanh_dropout_fwd", "tanh_dropout_bwd", "tanh_dropout_unpack_fwd", "tanh_dropout_pack_bwd", "splitk_reduce", "colsum"):
+            if name in k:
+                print("      %-28s %4d launches  %7.3f ms" % (name, k[name][0], k[name][1]))
+        print("      %-28s %4d launches  %7.3f ms" % ("all kernels", res[f]["launches"], sum(t for _, t in k.values())))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
@@ -164,6 +256,9 @@ def main():
     ap.add_argument("--no-context", action="store_true", help="skip the streaming yardsticks and the HieCoAtten step")
     ap.add_argument("--regions", default=None, metavar="MIN,MAX", help="region counts: seeded img_length in [MIN, MAX] per image (seed 4)")
     ap.add_argument("--blocks", type=int, default=196, metavar="L", help="regions per image")
+    ap.add_argument("--packed", action="store_true", help="with --regions: time the packed, pair and plain forms alternating in one process")
+    ap.add_argument("--rounds", type=int, default=2, help="--packed: rounds of the forms")
+    ap.add_argument("--forms", default="packed,pair,plain", help="--packed: the forms to time, in order")
     a = ap.parse_args()
     N, L, D, E, T, H, O, V = a.batch, a.blocks, 2048, 512, 14, 1024, 1000, 15881
     dev = "cuda:0"
@@ -195,6 +290,19 @@ def main():
         img_length = torch.randint(lo, hi + 1, (U,), generator=torch.Generator().manual_seed(4)).to(dev)
         per_q = img_length if img_index is None else img_length[img_index]
         share = float(per_q.float().sum()) / (N * L)
+    if a.packed:
+        forms = [f for f in a.forms.split(",") if f]
+        if not a.regions or not forms or any(f not in ("packed", "pair", "plain") for f in forms):
+            ap.error("--packed needs --regions MIN,MAX and --forms out of packed,pair,plain")
+        res = compare_forms(ladder, img, ids, target, q_len, img_index, img_length, forms, a.steps, a.warmup, a.rounds, a.repeats)
+        print("HieCoAttenLadder (coatt=%s) train step, call forms of one batch  B=%d U=%d L=%d img=%d E=%d T=%d%s"
+              % (a.coatt, N, U, L, D, E, T, "  question lengths in [3, %d]" % T if a.lengths else ""))
+        print("  region counts in [%d, %d]: sum(counts) / (N L) = %.3f" % (lo, hi, share))
+        print_forms(res, forms, a.steps)
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            json.dump({"coatt": a.coatt, "regions": a.regions, "blocks": L, "counts_share": share, "forms": res}, open(a.json, "w"), indent=1)
+        return
     ms, kern = timed(ladder, img, ids, target, a.steps, a.warmup, q_len, img_index, a.repeats, img_length)
     windows = list(timed.windows)
     launches = sum(n for n, _ in kern.values())

@@ -68,6 +68,8 @@ enum VqfKernelId {
   KID_ROW_BLOCK_GROUP_SUM,
   KID_MFB_FUSE_BWD_IMAGE,
   KID_ZERO_COLS,
+  KID_TANH_DROP_UNPACK_FWD,
+  KID_TANH_DROP_PACK_BWD,
   KID_COUNT
 };
 

@@ -2,6 +2,7 @@
 //   dropout                      hieCoAtten.py:26,28   networks.py:22,24,55,57   (F.dropout, p=0.5)
 //   y = dropout(tanh(a [+ b]))   hieCoAtten.py:32-33,38-39,45-46
 //   row softmax over the last axis   modules.py:91-92 (Attention_2)
+//   y = dropout(tanh(a)) as the change of layout packed (R, E) <-> padded (U*L, E)   (HieCoAttenLadder on a PackedRegions)
 // Dropout masks are Philox4x32-10(seed, element index / 4), regenerated in the backward, or an
 // explicit uint8 keep-mask (parity tests).
 #include "common.h"
@@ -114,6 +115,49 @@ __global__ void dropout_bt_kernel(const float* __restrict__ x, long long sb_in, 
       for (int j = 0; j < 4; ++j) o[j] = v[j] * sc[j];
     }
     *reinterpret_cast<f32x4*>(y + b * sb_out + t * st_out + 4 * c4) = o;
+  }
+}
+
+// The change of layout between packed and padded rows, in the tanh / dropout pass that runs anyway (HieCoAttenLadder's
+// V = drop(tanh(img_emb(rows))) on a PackedRegions): z / dz hold the Rtot real rows of every owner, one owner after the other;
+// y / dy are the padded (U*L, E) tensors.  Owner u = blockIdx.y has (start, cnt) by packed_span's rule (csrc/fusion.hip), clamped
+// so that nothing roff holds makes the kernel leave a tensor; roff is read uniformly per workgroup.  The dropout index of element
+// (l, c) is that of the padded tensor, (u*L + l)*E + c: the real rows carry the bits of ew_kernel<1> / <2> on the zero-padded copy.
+// BWD false: y[u*L + l] = tanh(z[start + l]) * sc for l < cnt, exact zero rows behind (nothing read there).
+// BWD true:  dz[start + l] = MODE 2 of ew_kernel on padded row u*L + l, l < cnt; no padded row of dy / y is read.
+template <bool BWD>
+__global__ void __launch_bounds__(256)
+tanh_drop_repack_kernel(const float* __restrict__ a, const float* __restrict__ yin, const int* __restrict__ roff,
+                        const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep, int Rtot, int L, int E4,
+                        float* __restrict__ out) {
+  const int u = blockIdx.y;
+  const long long o0 = roff[u], o1 = roff[u + 1];
+  const int start = (int)min(max(o0, 0LL), (long long)Rtot - 1);
+  const int cnt = (int)min(max(o1 - o0, 1LL), (long long)min(L, Rtot - start));
+  const unsigned n4 = (unsigned)(BWD ? cnt : L) * (unsigned)E4;
+  const unsigned stride = gridDim.x * blockDim.x;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const unsigned l = i / (unsigned)E4, c4 = i - l * (unsigned)E4;
+    const long long pad4 = ((long long)u * L + l) * E4 + c4, pk4 = ((long long)start + l) * E4 + c4;
+    f32x4 y = {0.f, 0.f, 0.f, 0.f};
+    if (BWD || (int)l < cnt) {
+      float sc[4];
+      keep4(keep, seed, thr, inv_keep, pad4, sc);
+      if (!BWD) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(a + 4 * pk4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) y[j] = vqf_tanh_fast(x[j]) * sc[j];
+      } else {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(a + 4 * pad4);
+        const f32x4 yy = *reinterpret_cast<const f32x4*>(yin + 4 * pad4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float t = sc[j] > 0.f ? yy[j] * (1.0f / inv_keep) : 0.f;
+          y[j] = x[j] * sc[j] * (1.0f - t * t);
+        }
+      }
+    }
+    *reinterpret_cast<f32x4*>(out + 4 * (BWD ? pk4 : pad4)) = y;
   }
 }
 
@@ -242,6 +286,22 @@ int ew2d_launch(int kid, const float* a, int lda, const float* b, int ldb, const
   return vqf_last_error();
 }
 
+template <bool BWD>
+int tanh_drop_repack_launch(const float* a, const float* yin, const int* roff, const uint8_t* keep, uint64_t seed, float p, int U, int R,
+                            int L, int E, float* out, void* stream) {
+  if (!roff || (((uintptr_t)roff) & 3) || !a || !out || (BWD && !yin) || U <= 0 || R <= 0 || L <= 0 || E <= 0 || p < 0.f || p >= 1.f)
+    return VQF_E_BADARG;
+  if (!vqf_tanh_dropout_unpack_supported(U, R, L, E)) return VQF_E_UNSUPPORTED;
+  if (!aligned16(a) || !aligned16(out) || (BWD && !aligned16(yin)) || (keep && (((uintptr_t)keep) & 3))) return VQF_E_ALIGN;
+  const uint32_t thr = (keep || p == 0.f) ? 0u : drop_threshold_host(p);
+  const float inv_keep = (keep || p > 0.f) ? 1.0f / (1.0f - p) : 1.0f;
+  int chunks = (L * (E / 4) + 255) / 256;                  // L * E / 4 <= 2^24
+  if (chunks > 64) chunks = 64;
+  VQF_LAUNCH(BWD ? KID_TANH_DROP_PACK_BWD : KID_TANH_DROP_UNPACK_FWD, tanh_drop_repack_kernel<BWD>, dim3((unsigned)chunks, (unsigned)U),
+             dim3(256), 0, (hipStream_t)stream, a, yin, roff, keep, seed, thr, inv_keep, R, L, E / 4, out);
+  return vqf_last_error();
+}
+
 }  // namespace
 
 extern "C" {
@@ -304,6 +364,20 @@ int vqf_tanh_dropout_bwd(const float* dy, const float* y, const uint8_t* keep, u
   if (rc) return rc;
   if (!y || !aligned16(y)) return VQF_E_BADARG;
   return ew_launch<2>(KID_TANH_DROP_BWD, dy, y, keep, seed, p_drop, n, dx, stream);
+}
+
+int vqf_tanh_dropout_unpack_supported(int U, int R, int L, int E) {
+  return U >= 1 && U <= 65535 && R >= 1 && R < (1 << 29) && L >= 1 && L <= 1024 && E >= 4 && E <= 65536 && (E % 4) == 0;
+}
+
+int vqf_tanh_dropout_unpack_fwd(const float* z, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop, int U, int R, int L,
+                                int E, float* y, void* stream) {
+  return tanh_drop_repack_launch<false>(z, nullptr, roff, keep, seed, p_drop, U, R, L, E, y, stream);
+}
+
+int vqf_tanh_dropout_pack_bwd(const float* dy, const float* y, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop, int U,
+                              int R, int L, int E, float* dz, void* stream) {
+  return tanh_drop_repack_launch<true>(dy, y, roff, keep, seed, p_drop, U, R, L, E, dz, stream);
 }
 
 int vqf_gate_tanh_sigmoid_fwd(const float* a, const float* b, long long n, float* y, void* stream) {

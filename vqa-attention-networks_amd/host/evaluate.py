@@ -129,7 +129,7 @@ def predict(model, img, q, q_length=None, k=5, **fwd_kwargs):
     Further keyword arguments go to the model's forward: predict(model, img (U, L, D), q (N, T), q_length, img_index=idx) asks
     HieCoAttenLadder N questions about U shared images (idx (N,): the image of each question); predict(model, (img, img_length),
     q) asks MFB / MHBCoAtt / HieCoAttenLadder about right-padded region features (img_length: the real regions of each image);
-    predict(model, PackedRegions(rows, offsets, max_regions), q) asks MFB / MHBCoAtt about region features that were never padded."""
+    predict(model, PackedRegions(rows, offsets, max_regions), q) asks MFB / MHBCoAtt / HieCoAttenLadder about region features that were never padded."""
     was_training = model.training
     model.eval()
     try:

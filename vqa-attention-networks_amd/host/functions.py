@@ -812,6 +812,27 @@ class TanhDropFn(torch.autograd.Function):
         return dx, (dx if ctx.has_b else None), None, None, None
 
 
+class TanhDropUnpackFn(torch.autograd.Function):
+    """y (U*L, E) = dropout(tanh(z)) laid out padded, from z (R, E) packed rows and roff (U + 1) int32 (HieCoAttenLadder on a
+    PackedRegions): the tanh / dropout pass is where the layout changes.  Padded rows of y are exact zeros; the masks are those of
+    TanhDropFn on the padded tensor.  Backward: dz (R, E), the real rows only (vqf_tanh_dropout_pack_bwd)."""
+
+    @staticmethod
+    def forward(ctx, z, roff, U, L, keep, seed, p_drop):
+        z = _c(z)
+        y = ops.tanh_dropout_unpack_fwd(z, roff, U, L, keep=keep, seed=seed, p_drop=p_drop)
+        ctx.save_for_backward(y, roff)
+        ctx.keep, ctx.seed, ctx.p, ctx.dims = keep, seed, p_drop, (U, z.shape[0], L)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, roff = ctx.saved_tensors
+        U, R, L = ctx.dims
+        dz = ops.tanh_dropout_pack_bwd(_c(dy), y, roff, U, R, L, keep=ctx.keep, seed=ctx.seed, p_drop=ctx.p)
+        return dz, None, None, None, None, None, None
+
+
 class GateFn(torch.autograd.Function):
     """y = tanh(a) * sigmoid(b): the gate of Nonlinear_layer (modules.py:103-109), one launch each way."""
 

@@ -1,6 +1,6 @@
 """Batches whose questions share images: the index machinery of forward(..., img_index) (HieCoAttenLadder, MFB, MHBCoAtt),
-the region counts of forward((img, img_length), ...) (MFB, MHBCoAtt) and the packed region features of
-forward(PackedRegions(rows, offsets, max_regions), ...) (MFB, MHBCoAtt).
+the region counts of forward((img, img_length), ...) (MFB, MHBCoAtt, HieCoAttenLadder) and the packed region features of
+forward(PackedRegions(rows, offsets, max_regions), ...) (MFB, MHBCoAtt, HieCoAttenLadder).
 
 img_index (N,) says which of the U images of the batch question n looks at.  It is never read on the host: _group_index clamps
 it and derives, on the device, what the grouped kernels of include/vqa_fusion.h take (idx / order / grp_off), and every kernel
@@ -62,7 +62,8 @@ def _region_lens(img_length, L, idx=None):
 
 
 class PackedRegions:
-    """Region features that were never padded (forward(PackedRegions(rows, offsets, max_regions), ...); MFB, MHBCoAtt, fp32):
+    """Region features that were never padded (forward(PackedRegions(rows, offsets, max_regions), ...); MFB, MHBCoAtt,
+    HieCoAttenLadder, fp32):
     rows (R, D) holds every image's real regions, one image after the other; image i owns rows offsets[i] .. offsets[i + 1] - 1
     (offsets (N + 1,) int64 / int32 -- (U + 1,) with img_index --, offsets[0] = 0, non-decreasing, offsets[-1] = R, every count
     in [1, max_regions]); max_regions is a Python int L in [1, 1024], the padded width of what stays per (image, region) slot.

@@ -86,6 +86,17 @@ q_length, img_index, coatt and img_length combine freely.  Dropout masks, explic
 products and the logit heads run on all rows; their padded results are never used.  A plain tensor or (img, None) is the
 model without counts, bit for bit: no extra launch, the same code route.
 
+Packed regions.  forward(PackedRegions(rows (R, D), offsets, max_regions = L), ids, ...) -- what data_loader.pack_region_features builds:
+every image's real regions, never padded; offsets (N + 1,), or (U + 1,) per image with img_index -- is, by definition, the model on
+(packed.unpack(), ids, ...): the region-count call above.  img_emb runs on the R real rows (so does its weight gradient), and the
+tanh / dropout pass that follows anyway is where the layout changes: vqf_tanh_dropout_unpack_fwd reads (R, E) and writes V as
+(U*L, E) with exact zero rows behind each count, its backward (vqf_tanh_dropout_pack_bwd) returns dZ (R, E) without reading a padded
+row -- as many launches as the pair call, no extra pass over an (N*L, .) tensor.  Dropout indices stay those of the padded tensor
+(set_keep_masks(img=...) stays (U*L, E)); the counts are offsets[1:] - offsets[:-1] through the same clamp as img_length, and from V
+on the code is that of the region-count call (rlens, the *_regions / *_len kernels, RowBlockGatherFn, grp).  offsets is never read
+on the host; the kernels clamp what it holds (include/vqa_fusion.h).  The Vh / VX products, the affinity and the rank-T passes stay
+padded (N*L rows), as in the region-count call; fp32 only.
+
 Stages (every product and every pass over an (N*L, .) or (N*T, .) tensor runs in libvqa_fusion.so):
   * img_emb / word embedding: LinearFn + TanhDropFn, EmbedTanhFn + DropoutFn;
   * phrase level (PhraseFn): the six conv taps as one GEMM, then vqf_phrase_ngram_fwd / _bwd (csrc/hie_ladder.hip);
@@ -102,8 +113,9 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .functions import _c, _hie_hv_ti, _hie_dc, _hie_bwd_bgemm, EmbedTanhFn, LinearFn, DropoutFn, TanhDropFn, DropoutBTFn, LstmBatchFn
-from .grouping import _group_index, _region_lens, check_img_length    # (_group_index: importable from here as before)
+from .functions import (_c, _hie_hv_ti, _hie_dc, _hie_bwd_bgemm, EmbedTanhFn, LinearFn, DropoutFn, TanhDropFn, TanhDropUnpackFn, DropoutBTFn,
+                        LstmBatchFn)
+from .grouping import _group_index, _region_lens, check_img_length, check_packed_regions, PackedRegions    # (_group_index: importable from here as before)
 from .lib import VqfError
 from .mfb import _DropSeeds, split_region_features
 
@@ -497,6 +509,13 @@ class HieCoAttenLadder(nn.Module):
     hold any finite values.  Values are clamped to [1, L] on the device and never read on the host.  A tensor or (img, None):
     no masking, bit for bit today's model.  A pair of another arity, counts of a wrong dtype, shape or device raise VqfError.
 
+    img_features may be a PackedRegions(rows (R, img_size), offsets, max_regions) (grouping.PackedRegions; what
+    data_loader.pack_region_features builds): the real regions of every image, never padded; offsets (N + 1,) -- (U + 1,) with
+    img_index -- int64 or int32 on the questions' device, never read on the host; max_regions a Python int L in [1, 1024].  The
+    result is this model on (packed.unpack(), ...), the pair call, with av (N, 3, L) and exact zeros behind each count; img_emb
+    and its weight gradient run on the R real rows (module docstring, "Packed regions").  A malformed object, rows on another
+    device or of another channel count, more than 65535 images or R >= 2^29 raise VqfError before the first launch.
+
     The image features are data (img_features.requires_grad raises), fp32 on the GPU: CPU tensors and bf16 features raise
     VqfError -- there is no CPU fallback.  Dropout (rate drop_p) is active in train mode only;
     set_keep_masks() supplies explicit uint8 keep-masks for the tests, otherwise the kernels draw Philox masks."""
@@ -523,7 +542,7 @@ class HieCoAttenLadder(nn.Module):
         self._seeds = _DropSeeds()
 
     def set_keep_masks(self, **masks):
-        """Test hook: uint8 keep-masks 'img' (N*L, E) ((U*L, E) with img_index: one mask per image), 'word' (N*T, E), 'ans_w' (N, E), 'ans_p' (N, 2E), 'ans_s' (N, 2E),
+        """Test hook: uint8 keep-masks 'img' (N*L, E) ((U*L, E) with img_index: one mask per image; the same padded shape for a PackedRegions), 'word' (N*T, E), 'ans_w' (N, E), 'ans_p' (N, 2E), 'ans_s' (N, 2E),
         'ans_h' (N, hidden_size); used in train mode in place of the in-kernel draws."""
         self._seeds.keep = masks
 
@@ -534,8 +553,35 @@ class HieCoAttenLadder(nn.Module):
             return x
         return DropoutFn.apply(_c(x), keep, seed, self.drop_p if keep is not None else p)
 
+    def _packed_rows(self, packed, que_features, img_index):
+        """forward(PackedRegions, ...): the refusals of the packed call -> rows (R, D).  offsets is (N + 1,), or (U + 1,) with
+        img_index; nothing here reads a tensor's values."""
+        who = "HieCoAttenLadder"
+        if not torch.is_tensor(que_features) or que_features.dim() != 2:
+            raise VqfError("%s takes (N, T) int64 word ids" % who)
+        owners = que_features.shape[0] if img_index is None else \
+            (packed.offsets.numel() - 1 if torch.is_tensor(packed.offsets) else -1)
+        check_packed_regions(who, packed, owners, que_features.device)
+        rows, L = packed.rows, packed.max_regions
+        if rows.device != que_features.device:
+            raise VqfError("%s: PackedRegions.rows must be on the questions' device (%s), got %s"
+                           % (who, que_features.device, rows.device))
+        R, D = rows.shape
+        if D != self.img_emb.in_features:
+            raise VqfError("%s: PackedRegions.rows must have img_size = %d channels, got %s"
+                           % (who, self.img_emb.in_features, tuple(rows.shape)))
+        E = self.img_emb.out_features
+        if not ops.tanh_dropout_unpack_supported(owners, R, L, E):
+            raise VqfError("%s: PackedRegions takes 1 <= images <= 65535, 1 <= R < 2^29 rows, max_regions <= 1024 and "
+                           "embed_size %% 4 == 0 (got images=%d, R=%d, max_regions=%d, E=%d)" % (who, owners, R, L, E))
+        return rows
+
     def forward(self, img_features, que_features, q_length=None, img_index=None):
-        img_features, img_length = split_region_features("HieCoAttenLadder", img_features)
+        packed = img_features if isinstance(img_features, PackedRegions) else None
+        if packed is not None:                                                  # the refusals of the packed call: none needs a GPU
+            img_features, img_length = self._packed_rows(packed, que_features, img_index), None
+        else:
+            img_features, img_length = split_region_features("HieCoAttenLadder", img_features)
         if not img_features.is_cuda or not que_features.is_cuda:
             raise VqfError("HieCoAttenLadder needs GPU tensors (the HIP extension is the only path; no CPU fallback)")
         if img_features.dtype != torch.float32:
@@ -544,7 +590,10 @@ class HieCoAttenLadder(nn.Module):
             raise VqfError("HieCoAttenLadder: img_features are data (no gradient into the image features)")
         if que_features.dtype != torch.int64:
             raise VqfError("HieCoAttenLadder takes int64 word ids")
-        U, L, D = img_features.shape
+        if packed is None:
+            U, L, D = img_features.shape
+        else:                                                                   # rows (R, D); one owner of offsets per image
+            D, L, U = img_features.shape[1], packed.max_regions, packed.offsets.numel() - 1
         N = U if img_index is None else que_features.shape[0]
         T = que_features.shape[1]
         E = self.img_emb.out_features
@@ -587,11 +636,21 @@ class HieCoAttenLadder(nn.Module):
             rlens = _region_lens(img_length, L, None if grp is None else grp[0])   # O(N), on the device: nothing is read back
             if grp is not None:
                 rlens = rlens[0]
+        if packed is not None:             # O(U), on the device: nothing is read back; the kernels clamp what roff holds
+            off = packed.offsets
+            roff = off.to(torch.int32).contiguous()
+            rlens = _region_lens(off[1:] - off[:-1], L, None if grp is None else grp[0])
+            if grp is not None:
+                rlens = rlens[0]
         # V = drop(tanh(img_emb(img)))
         seed, p = self._seeds.next(self.training, self.drop_p)
         keep = self._seeds.keep.get("img") if self.training else None
-        V = LinearFn.apply(_c(img_features).view(M, D), self.img_emb.weight, self.img_emb.bias, False)
-        V = TanhDropFn.apply(V, None, keep, seed, self.drop_p if keep is not None else p)           # (U*L, E): once per image
+        if packed is None:
+            V = LinearFn.apply(_c(img_features).view(M, D), self.img_emb.weight, self.img_emb.bias, False)
+            V = TanhDropFn.apply(V, None, keep, seed, self.drop_p if keep is not None else p)       # (U*L, E): once per image
+        else:                              # the product on the R real rows; the tanh / dropout pass lays V out padded
+            V = LinearFn.apply(_c(img_features), self.img_emb.weight, self.img_emb.bias, False)      # (R, E)
+            V = TanhDropUnpackFn.apply(V, roff, U, L, keep, seed, self.drop_p if keep is not None else p)   # (U*L, E), zero padded rows
         if grp is not None and not alt:
             V = RowBlockGatherFn.apply(V, grp[0], grp[1], grp[2], L)                                  # (N*L, E)
         # Qw = drop(tanh(word_emb(ids)))

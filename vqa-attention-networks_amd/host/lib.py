@@ -179,6 +179,10 @@ SIGNATURES = {
                                               c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_p, c_sz, c_p]),
     "vqf_glimpse_pool_fwd_packed": (c_i, [c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
     "vqf_glimpse_pool_bwd_packed": (c_i, [c_f, c_f, c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
+    # the tanh / dropout pass as the packed <-> padded change of layout (HieCoAttenLadder.forward(PackedRegions, ...)): roff c_p
+    "vqf_tanh_dropout_unpack_supported": (c_i, [c_i, c_i, c_i, c_i]),
+    "vqf_tanh_dropout_unpack_fwd": (c_i, [c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_p]),
+    "vqf_tanh_dropout_pack_bwd": (c_i, [c_f, c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_p]),
     "vqf_lstm_seq_supported": (c_i, [c_i, c_i]),
     "vqf_lstm_seq_ws_bytes": (c_sz, [c_i, c_i]),
     "vqf_lstm_seq_fwd": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_p, c_sz, c_p]),

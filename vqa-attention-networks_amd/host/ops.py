@@ -472,6 +472,51 @@ def tanh_dropout_bwd(dy, y, keep=None, seed=0, p_drop=0.5, out=None):
     return dx
 
 
+def tanh_dropout_unpack_supported(U, R, L, E):
+    return bool(_lib().vqf_tanh_dropout_unpack_supported(int(U), int(R), int(L), int(E)))
+
+
+def _unpack_operands(name, roff, U, R, L, E):
+    if not torch.is_tensor(roff) or not roff.is_cuda or roff.dtype != torch.int32 or not roff.is_contiguous() or \
+            tuple(roff.shape) != (U + 1,):
+        raise _l.VqfError("%s: roff must be a contiguous (U + 1,) = (%d,) int32 GPU tensor" % (name, U + 1))
+    if not tanh_dropout_unpack_supported(U, R, L, E):
+        raise _l.VqfError("%s: 1 <= U <= 65535 owners, 1 <= R < 2^29 rows, L <= 1024 and E %% 4 == 0, E <= 65536 are supported "
+                          "(got U=%d, R=%d, L=%d, E=%d)" % (name, U, R, L, E))
+
+
+def tanh_dropout_unpack_fwd(z, roff, U, L, keep=None, seed=0, p_drop=0.5):
+    """z (R, E) packed rows, roff (U + 1) int32 -> y (U*L, E) padded: owner u's rows l < its count are dropout(tanh(z[start + l])),
+    the others exact zeros (nothing read there).  Masks in the padded coordinates: keep (U*L, E), Philox index (u*L + l)*E + c."""
+    _chk(z)
+    if z.dim() != 2:
+        raise _l.VqfError("tanh_dropout_unpack_fwd: z must be (R, E)")
+    R, E = z.shape
+    _unpack_operands("tanh_dropout_unpack_fwd", roff, U, R, L, E)
+    if keep is not None and keep.numel() != U * L * E:
+        raise _l.VqfError("tanh_dropout_unpack_fwd: keep must be (U*L, E) = (%d, %d)" % (U * L, E))
+    y = torch.empty((U * L, E), dtype=torch.float32, device=z.device)
+    _l.check(_lib().vqf_tanh_dropout_unpack_fwd(_ptr(z), _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop), U, R, L, E, _ptr(y),
+                                                _stream()), "vqf_tanh_dropout_unpack_fwd")
+    return y
+
+
+def tanh_dropout_pack_bwd(dy, y, roff, U, R, L, keep=None, seed=0, p_drop=0.5):
+    """dy, y (U*L, E) padded, roff (U + 1) int32 -> dz (R, E) packed: the backward of tanh_dropout_unpack_fwd on the real rows; the
+    padded rows of dy / y are not read."""
+    _chk(dy, y)
+    if y.dim() != 2 or y.shape[0] != U * L or dy.shape != y.shape:
+        raise _l.VqfError("tanh_dropout_pack_bwd: dy and y must be (U*L, E)")
+    E = y.shape[1]
+    _unpack_operands("tanh_dropout_pack_bwd", roff, U, R, L, E)
+    if keep is not None and keep.numel() != U * L * E:
+        raise _l.VqfError("tanh_dropout_pack_bwd: keep must be (U*L, E) = (%d, %d)" % (U * L, E))
+    dz = torch.empty((R, E), dtype=torch.float32, device=y.device)
+    _l.check(_lib().vqf_tanh_dropout_pack_bwd(_ptr(dy), _ptr(y), _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop), U, R, L, E,
+                                              _ptr(dz), _stream()), "vqf_tanh_dropout_pack_bwd")
+    return dz
+
+
 def tanh_bwd_rows_len(dy, y, lens, N, T, out=None):
     """dx = dy (1 - y^2) on the rows t < lens[n] of contiguous (N, T, L) tensors, zero on the others (in place allowed)"""
     _chk(dy, y, out)
