@@ -821,6 +821,20 @@ int vqf_embed_tanh_bwd_tm(const float* dout, const float* out, const long long* 
  * layout every kernel above consumes, dst (N, L, D), as fp32 (out_bf16 = 0, bit-exact copy) or
  * bf16 (out_bf16 = 1, round-to-nearest-even).  src and dst must not overlap. */
 int vqf_feat_transpose(const float* src, int N, int D, int L, int out_bf16, void* dst, void* stream);
+/* Packed region features (detector boxes, never padded; "Packed region features" above) from the bytes the H2D copy left to the
+ * tensors the models take (host/data_loader.py::RegionStager; an addition within ABI 7).  src is (R, D), fp32 (src_f16 = 0) or IEEE
+ * fp16 (src_f16 = 1): the real rows of every image, one image after the other.
+ *   roff == NULL  packed output: dst (R, D) fp32 = the same rows, widened (fp32 in: a plain copy).
+ *   roff != NULL  padded output: roff device int32 (U + 1), 4-byte aligned; dst (U*L, D) fp32; row u*L + l is source row start + l
+ *                 for l < cnt and an exact +0.0 row otherwise, nothing behind a count is read.  (start, cnt) by the rule of every
+ *                 packed kernel: start = clamp(roff[u], 0, R - 1), cnt = clamp(roff[u+1] - roff[u], 1, min(L, R - start)) -- nothing
+ *                 roff holds makes the kernel read or write outside a tensor.
+ * The fp16 widening is exact (finite values, +-0, +-inf, subnormals): the bits of numpy's astype(float32).  One pass, HBM-bound:
+ * 16-byte stores, 16-byte (fp32) / 8-byte (fp16) loads, one image per blockIdx.y in the padded form.  src and dst must not overlap.
+ * Supported: 1 <= U <= 65535, 1 <= R < 2^29, 1 <= L <= 1024, D % 4 == 0, 4 <= D <= 65536 (U and L are checked in the packed form
+ * too); outside VQF_E_UNSUPPORTED.  src / dst null, roff misaligned or an extent <= 0: VQF_E_BADARG; dst not 16-byte, fp32 src not
+ * 16-byte or fp16 src not 8-byte aligned: VQF_E_ALIGN. */
+int vqf_region_rows_stage(const void* src, int src_f16, const int* roff, int U, int R, int L, int D, float* dst, void* stream);
 
 /* --------------------------------------------------------------------------
  * Training-step tail (outside the modules, called by the solver loop).

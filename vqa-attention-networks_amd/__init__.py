@@ -28,6 +28,7 @@ def __getattr__(name):
         "KLDivLoss": ".host.train_step", "Adam": ".host.train_step",
         "data_loader": ".host.data_loader", "FeatureStager": ".host.data_loader", "group_batch": ".host.data_loader",
         "pad_region_features": ".host.data_loader", "pack_region_features": ".host.data_loader",
+        "RegionStager": ".host.data_loader", "stage_regions": ".host.data_loader", "pack_into": ".host.data_loader",
         "PackedRegions": ".host.grouping",
         "evaluate": ".host.evaluate", "loss_and_accuracy": ".host.evaluate", "Evaluator": ".host.evaluate",
         "predict": ".host.evaluate", "topk_answers": ".host.evaluate",

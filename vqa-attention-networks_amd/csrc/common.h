@@ -70,6 +70,7 @@ enum VqfKernelId {
   KID_ZERO_COLS,
   KID_TANH_DROP_UNPACK_FWD,
   KID_TANH_DROP_PACK_BWD,
+  KID_REGION_ROWS_STAGE,
   KID_COUNT
 };
 

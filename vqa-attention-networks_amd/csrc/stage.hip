@@ -80,6 +80,52 @@ __global__ __launch_bounds__(256) void feat_transpose_kernel(const float* __rest
   }
 }
 
+// Packed region features (detector boxes, never padded) as the H2D copy left them -> the fp32 tensors the models take.
+// src (Rtot, D) fp32 | IEEE fp16 holds the real rows of every image, one image after the other.  HBM-bound, one pass: per lane one
+// 16-byte (fp32) or 8-byte (fp16) streaming load and one 16-byte streaming store.  The fp16 widening is v_cvt_f32_f16: exact for
+// every finite value, +-0, +-inf and -- the default kernel mode keeps fp16 subnormals -- the subnormals.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+
+template <bool F16>
+__device__ __forceinline__ f32x4 stage_load4(const void* __restrict__ src, long long i4) {
+  if constexpr (F16) {
+    const f16x4 h = vqf_ld_stream(reinterpret_cast<const f16x4*>(src) + i4);
+    return __builtin_convertvector(h, f32x4);
+  } else {
+    return vqf_ld_stream(reinterpret_cast<const f32x4*>(src) + i4);
+  }
+}
+
+// packed output: dst (Rtot, D) = the same rows, widened.  n4 = Rtot * D / 4 < 2^43
+template <bool F16>
+__global__ void __launch_bounds__(256)
+region_rows_widen_kernel(const void* __restrict__ src, long long n4, float* __restrict__ dst) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride)
+    vqf_st_stream(reinterpret_cast<f32x4*>(dst) + i, stage_load4<F16>(src, i));
+}
+
+// padded output: dst (U*L, D); image u = blockIdx.y has (start, cnt) by packed_span's rule (csrc/fusion.hip), read once per
+// workgroup and clamped so that nothing roff holds makes the kernel leave a tensor: start in [0, Rtot - 1], start + cnt <= Rtot,
+// cnt <= L.  Row u*L + l is source row start + l for l < cnt and an exact +0.0 row behind it (nothing read there).
+template <bool F16>
+__global__ void __launch_bounds__(256)
+region_rows_pad_kernel(const void* __restrict__ src, const int* __restrict__ roff, int Rtot, int L, int D4,
+                       float* __restrict__ dst) {
+  const int u = blockIdx.y;
+  const long long o0 = roff[u], o1 = roff[u + 1];
+  const int start = (int)min(max(o0, 0LL), (long long)Rtot - 1);
+  const int cnt = (int)min(max(o1 - o0, 1LL), (long long)min(L, Rtot - start));
+  const unsigned n4 = (unsigned)L * (unsigned)D4;            // <= 2^24
+  const unsigned stride = gridDim.x * blockDim.x;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const unsigned l = i / (unsigned)D4, c4 = i - l * (unsigned)D4;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if ((int)l < cnt) v = stage_load4<F16>(src, ((long long)start + l) * D4 + c4);
+    vqf_st_stream(reinterpret_cast<f32x4*>(dst) + ((long long)u * L + l) * D4 + c4, v);
+  }
+}
+
 }  // namespace
 
 extern "C" int vqf_feat_transpose(const float* src, int N, int D, int L, int out_bf16, void* dst, void* stream) {
@@ -92,5 +138,35 @@ extern "C" int vqf_feat_transpose(const float* src, int N, int D, int L, int out
     VQF_LAUNCH(KID_FEAT_TRANSPOSE, feat_transpose_kernel<true>, grid, dim3(256), 0, s, src, D, L, dst);
   else
     VQF_LAUNCH(KID_FEAT_TRANSPOSE, feat_transpose_kernel<false>, grid, dim3(256), 0, s, src, D, L, dst);
+  return vqf_last_error();
+}
+
+extern "C" int vqf_region_rows_stage(const void* src, int src_f16, const int* roff, int U, int R, int L, int D, float* dst,
+                                     void* stream) {
+  if (!src || !dst || (roff && (((uintptr_t)roff) & 3)) || U <= 0 || R <= 0 || L <= 0 || D <= 0) return VQF_E_BADARG;
+  if (U > 65535 || R >= (1 << 29) || L > 1024 || D < 4 || D > 65536 || (D % 4)) return VQF_E_UNSUPPORTED;
+  if (!aligned16(dst) || (src_f16 ? (((uintptr_t)src) & 7) != 0 : !aligned16(src))) return VQF_E_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  const int D4 = D / 4;
+  if (!roff) {
+    const long long n4 = (long long)R * D4;
+    long long blocks = (n4 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    vqf_prof_dims(R, D, 0);
+    if (src_f16)
+      VQF_LAUNCH(KID_REGION_ROWS_STAGE, region_rows_widen_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, src, n4, dst);
+    else
+      VQF_LAUNCH(KID_REGION_ROWS_STAGE, region_rows_widen_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, src, n4, dst);
+    return vqf_last_error();
+  }
+  int chunks = (L * D4 + 255) / 256;                         // L * D / 4 <= 2^24
+  if (chunks > 64) chunks = 64;
+  vqf_prof_dims(U, L, D);
+  if (src_f16)
+    VQF_LAUNCH(KID_REGION_ROWS_STAGE, region_rows_pad_kernel<true>, dim3((unsigned)chunks, (unsigned)U), dim3(256), 0, s, src, roff,
+               R, L, D4, dst);
+  else
+    VQF_LAUNCH(KID_REGION_ROWS_STAGE, region_rows_pad_kernel<false>, dim3((unsigned)chunks, (unsigned)U), dim3(256), 0, s, src, roff,
+               R, L, D4, dst);
   return vqf_last_error();
 }

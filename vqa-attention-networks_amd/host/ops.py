@@ -1648,6 +1648,45 @@ def feat_transpose(src, out=None, bf16=False):
     return out
 
 
+def region_rows_stage_supported(U, R, L, D):
+    """The shapes vqf_region_rows_stage takes (include/vqa_fusion.h); no GPU needed."""
+    return 1 <= int(U) <= 65535 and 1 <= int(R) < (1 << 29) and 1 <= int(L) <= 1024 and int(D) % 4 == 0 and 4 <= int(D) <= 65536
+
+
+def region_rows_stage(src, roff=None, L=None, out=None):
+    """src (R, D) fp32 | fp16, the real rows of every image one after the other, as the H2D copy left them.
+    roff None -> (R, D) fp32, the same rows widened (a copy for fp32).  roff (U + 1,) int32 with L -> (U, L, D) fp32: image u's rows
+    l < its count are src[start + l], the others exact +0.0 rows (nothing read there); roff is clamped in the kernel."""
+    if not torch.is_tensor(src) or not src.is_cuda:
+        raise _l.VqfError("vqa fusion ops need GPU tensors (HIP extension is the only path; no CPU fallback)")
+    if src.dtype not in (torch.float32, torch.float16) or src.dim() != 2 or not src.is_contiguous():
+        raise _l.VqfError("region_rows_stage: src must be a contiguous (R, D) fp32 or fp16 tensor")
+    R, D = src.shape
+    if roff is None:
+        U, Lk, shape = 1, 1, (R, D)
+    else:
+        if L is None or isinstance(L, bool) or not isinstance(L, int):
+            raise _l.VqfError("region_rows_stage: the padded form needs L (a Python int)")
+        if not torch.is_tensor(roff) or roff.device != src.device or roff.dtype != torch.int32 or not roff.is_contiguous() or \
+                roff.dim() != 1:
+            raise _l.VqfError("region_rows_stage: roff must be a contiguous (U + 1,) int32 tensor on src's device")
+        U, Lk = roff.numel() - 1, L
+        shape = (U, Lk, D)
+    if not region_rows_stage_supported(U, R, Lk, D):
+        raise _l.VqfError("region_rows_stage: 1 <= U <= 65535 images, 1 <= R < 2^29 rows, 1 <= L <= 1024 and D %% 4 == 0, "
+                          "4 <= D <= 65536 are supported (got U=%d, R=%d, L=%d, D=%d)" % (U, R, Lk, D))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    else:
+        _chk(out)
+        if out.device != src.device or out.numel() != math.prod(shape):
+            raise _l.VqfError("region_rows_stage: out must be a contiguous fp32 tensor of %s on src's device (roff has %d entries)"
+                              % (shape, 0 if roff is None else roff.numel()))
+    _l.check(_lib().vqf_region_rows_stage(_ptr(src), 1 if src.dtype == torch.float16 else 0, _ptr(roff), U, R, Lk, D, _ptr(out),
+                                          _stream()), "vqf_region_rows_stage")
+    return out
+
+
 # ---------------------------------------------------------------------------
 # training-step tail (solver.py:25-29,91-94)
 def _loss_ws(N, A, device):
