@@ -537,6 +537,17 @@ int vqf_tanh_dropout_unpack_fwd(const float* z, const int* roff, const uint8_t* 
                                 int E, float* y, void* stream);
 int vqf_tanh_dropout_pack_bwd(const float* dy, const float* y, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop, int U,
                               int R, int L, int E, float* dz, void* stream);
+/* The same pass with BOTH sides packed (HieCoAttenLadder(packed_coatt=True): V stays (R, E); additions within ABI 7): z, y, dy, dz
+ * are all (R, E), roff and its clamp rule as above -- start = clamp(roff[u], 0, R - 1), cnt = clamp(roff[u+1] - roff[u], 1,
+ * min(L, R - start)) -- and only rows start .. start + cnt - 1 of each owner are read or written.
+ *   packed_fwd: y[start + l, :] = tanh(z[start + l, :]) * keep / (1-p);   packed_bwd: dz[start + l, :] from dy / y[start + l, :].
+ * The dropout index of element (l, c) of owner u stays (u*L + l)*E + c and keep stays (U*L, E): row start + l carries the bits of
+ * row u*L + l out of vqf_tanh_dropout_unpack_fwd and of vqf_tanh_dropout_pack_bwd's output.  Supported range, return codes and
+ * alignment: those of the two entry points above (vqf_tanh_dropout_unpack_supported). */
+int vqf_tanh_dropout_packed_fwd(const float* z, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop, int U, int R, int L,
+                                int E, float* y, void* stream);
+int vqf_tanh_dropout_packed_bwd(const float* dy, const float* y, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop, int U,
+                                int R, int L, int E, float* dz, void* stream);
 /* --------------------------------------------------------------------------
  * HieCoAtten's co-attention ladder (hieCoAtten.py:32-49): the stages with a tiny inner / outer extent T (words per question)
  * as single streaming passes over the rows of the (N*L, E) tensors (csrc/hie.hip), neighbouring element-wise stage fused in.
@@ -735,6 +746,41 @@ int vqf_row_block_supported(int N, int U, long long blk);
 int vqf_row_block_gather(const float* src, const int* idx, int N, int U, long long blk, float* dst, void* stream);
 int vqf_row_block_group_sum(const float* src, const int* order, const int* grp_off, int N, int U, long long blk, float* out,
                             void* stream);
+
+/* The packed forms of the alternating image side (HieCoAttenLadder(coatt="alternating", packed_coatt=True) on a PackedRegions;
+ * additions within ABI 7; fp32 only): Xh / dXh (R, row pitch ldx / lddx) and feat / dfeat (R, C) hold the real rows of every
+ * owner, one owner after the other, R = the sum of the counts.  roff: device int32, 4-byte aligned (null or misaligned, or
+ * R <= 0: VQF_E_BADARG), (N + 1) offsets per sample in the plain forms (idx / order / grp_off NULL; U must equal N, else
+ * VQF_E_BADARG), (U + 1) per IMAGE in the grouped forms.  Clamped where it is read by the rule of "Packed region features":
+ * owner u has start = clamp(roff[u], 0, R - 1) and cnt = clamp(roff[u+1] - roff[u], 1, min(L, R - start)), row l < cnt of
+ * its Xh / dXh / feat / dfeat is row start + l, S = L.  Nothing roff, idx, order or grp_off hold makes a kernel read or write
+ * outside a tensor.  logits / dlogits (N*S, G), gp / dgp (N, G E), dw (G, E) and wts (N, G, S) stay in padded coordinates.
+ *   guided_logits_fwd_packed   the kernel of vqf_guided_logits_fwd / _fwd_grouped; gp may be NULL.  Question n reads rows
+ *             start .. start + cnt - 1 of its owner; logits rows s >= cnt are exact zeros, no Xh row is read for them.
+ *   guided_logits_bwd_packed   the kernels of vqf_guided_logits_bwd (order and grp_off both NULL; gp may be NULL) /
+ *             _bwd_grouped (both given, gp not NULL; exactly one of them: VQF_E_BADARG).  The grid keeps the chunks of S and a chunk
+ *             skips its rows >= cnt, so the partial rows -- and with them the order of the dgp and dw sums -- are those of the padded
+ *             kernels; dlogits rows s >= cnt are not read.  An image without a question gets exact zeros on its cnt dXh rows.
+ *             ws: at least vqf_guided_logits_bwd_packed_ws_bytes(N, U, S, E, G).  No atomics: two runs give the same bits.
+ *   glimpse_pool_bwd_packed_dfeat   vqf_glimpse_pool_bwd_packed with the gradient of the packed rows, dfeat (R, C) (not NULL).
+ *             Plain form (idx, order, grp_off all NULL): the kernel of vqf_glimpse_pool_bwd_len writes sample n's cnt dfeat rows at
+ *             start + l.  Grouped form (all three given; otherwise VQF_E_BADARG): dlogits per question, then dfeat[start + l] = the sum
+ *             over image u's questions in `order`, l < cnt; exact zeros for an image without a question.
+ * On well-formed offsets logits, dlogits, dgp and dw equal (value for value, signed zeros aside) those of the plain / _grouped /
+ * _len / _grouped_len entry points on the zero-padded copy with the same counts, and dXh / dfeat equal that run's real rows.
+ * Supported: vqf_guided_logits_packed_supported(N, U, R, S, E, G) = vqf_guided_logits_grouped_supported(N, U, S, E, G) and
+ * 1 <= R < 2^29; the pooling: vqf_glimpse_pool_grouped_supported(N, U, S, C, G).  Outside: VQF_E_UNSUPPORTED; operands not
+ * 16-byte aligned: VQF_E_ALIGN; ws too small: VQF_E_WORKSPACE. */
+int vqf_guided_logits_packed_supported(int N, int U, int R, int S, int E, int G);
+int vqf_guided_logits_fwd_packed(const float* Xh, int ldx, const float* gp, const float* w, const int* idx, const int* roff, int N,
+                                 int U, int R, int S, int E, int G, float* logits, void* stream);
+size_t vqf_guided_logits_bwd_packed_ws_bytes(int N, int U, int S, int E, int G);
+int vqf_guided_logits_bwd_packed(const float* dlogits, const float* Xh, int ldx, const float* gp, const float* w, const int* order,
+                                 const int* grp_off, const int* roff, int N, int U, int R, int S, int E, int G, float* dXh, int lddx,
+                                 float* dgp, float* dw, void* ws, size_t ws_bytes, void* stream);
+int vqf_glimpse_pool_bwd_packed_dfeat(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
+                                      const int* order, const int* grp_off, const int* roff, int N, int U, int R, int S, int C, int G,
+                                      int unit_softmax, float* dlogits, float* dfeat, void* stream);
 
 /* softmax over the last axis of (R,W) and its backward   modules.py:91-92 */
 int vqf_softmax_rows_fwd(const float* x, int R, int W, float* y, void* stream);

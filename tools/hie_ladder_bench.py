@@ -2,7 +2,7 @@
 
     python tools/hie_ladder_bench.py [--batch 256] [--steps 20] [--warmup 5] [--lengths] [--coatt parallel|alternating] [--json OUT]
                                      [--questions-per-image Q] [--repeats R] [--no-context] [--regions MIN,MAX] [--blocks L]
-                                     [--packed [--rounds K] [--forms packed,pair,plain]]
+                                     [--packed [--rounds K] [--forms packed-rows,packed,pair,plain]]
 
 Prints ms / step and QA pairs / s (device events around the timed steps), the step's FLOP count from the shapes with its
 MFMA floor at 157.3 TF/s (fp32 MFMA peak of the MI355X) and the fraction reached, the library profiler's per-kernel table
@@ -27,7 +27,9 @@ real rows of the same images, the pair (img, img_length) and the plain tensor --
 round's median and spread per form, the median over all windows per form, packed against pair, and from one profiled step per form the
 launch count and the img_emb launches (the projection M = rows, N = E, K = img and its weight gradient M = E, N = img, K = rows: R rows
 packed, U L otherwise) beside the tanh / dropout passes.  --forms: a subset, in the order to run (pair,plain runs on a tree without the
-packed form)."""
+packed form).  packed-rows (alternating only): the packed batch on the same model with packed_coatt=True -- the image side of the
+levels on the R rows too; the profiled step then also lists the VX-family products by their row count.  Every form's line adds the
+peak torch.cuda.max_memory_allocated of one step."""
 import argparse
 import json
 import os
@@ -166,17 +168,18 @@ def compare_forms(model, img, ids, target, q_len, img_index, img_length, forms, 
     E = model.img_emb.out_features
     feats = {"plain": img, "pair": (img, img_length)}
     rows_of = {"plain": U * L, "pair": U * L}
-    if "packed" in forms:
+    if "packed" in forms or "packed-rows" in forms:
         off = torch.zeros(U + 1, dtype=torch.int64, device=img.device)
         off[1:] = torch.cumsum(img_length.to(torch.int64), 0)
         real = torch.arange(L, device=img.device).unsqueeze(0) < img_length.unsqueeze(1)
         rows = img[real].contiguous()                                  # (R, D): the real rows, one image after the other
-        feats["packed"] = vqa_amd.PackedRegions(rows, off, L)
-        rows_of["packed"] = rows.shape[0]
+        feats["packed"] = feats["packed-rows"] = vqa_amd.PackedRegions(rows, off, L)
+        rows_of["packed"] = rows_of["packed-rows"] = rows.shape[0]
     crit = vqa_amd.CrossEntropyLoss()
     opt = vqa_amd.Adam(model.parameters(), lr=1e-4)
 
-    def step(f):
+    def step(f, form=None):
+        model.packed_coatt = form == "packed-rows"                     # the keyword of the constructor: read by forward
         opt.zero_grad(set_to_none=True)
         if img_index is not None:
             out = model(f, ids, q_len, img_index=img_index)
@@ -189,26 +192,35 @@ def compare_forms(model, img, ids, target, q_len, img_index, img_length, forms, 
     for _ in range(rounds):
         for f in forms:
             for _ in range(warmup):
-                step(feats[f])
+                step(feats[f], f)
             torch.cuda.synchronize()
             windows = []
             for _ in range(max(1, repeats)):
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 a.record()
                 for _ in range(steps):
-                    step(feats[f])
+                    step(feats[f], f)
                 b.record()
                 torch.cuda.synchronize()
                 windows.append(a.elapsed_time(b) / steps)
             res[f]["rounds"].append(windows)
     for f in forms:                                                    # one profiled step per form, after the timing
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        step(feats[f], f)
+        torch.cuda.synchronize()
+        res[f]["peak_bytes"] = torch.cuda.max_memory_allocated()
         ops.prof_reset()
         ops.prof_enable(True)
-        step(feats[f])
+        step(feats[f], f)
         torch.cuda.synchronize()
         ops.prof_enable(False)
         kern = ops.prof_report()
         M = rows_of[f]
+        Mc = M if f == "packed-rows" else U * L                        # rows of the VX-family products of the alternating levels
+        res[f]["vx"] = {"VX fwd (M=%d, N=%d, K=%d)" % (Mc, 3 * E, E): ops.prof_gemm(0, 0, Mc, 3 * E, E),
+                        "dV += dVX W (M=%d, N=%d, K=%d)" % (Mc, E, 3 * E): ops.prof_gemm(0, 1, Mc, E, 3 * E),
+                        "dW = dVX^T V (M=%d, N=%d, K=%d)" % (3 * E, E, Mc): ops.prof_gemm(1, 1, 3 * E, E, Mc)}
         gemms = [k for k in kern if k.startswith("gemm_f32_")]
         res[f]["kernels"] = kern
         res[f]["launches"] = sum(n for n, _ in kern.values())
@@ -221,14 +233,18 @@ def print_forms(res, forms, steps):
     med = lambda v: sorted(v)[len(v) // 2]
     for f in forms:
         for i, w in enumerate(res[f]["rounds"]):
-            print("  %-7s round %d  median %.3f ms  spread %.3f ms  windows %s  launches/step %d"
-                  % (f, i + 1, med(w), max(w) - min(w), " ".join("%.3f" % x for x in w), res[f]["launches"]))
+            print("  %-11s round %d  median %.3f ms  spread %.3f ms  windows %s  launches/step %d  peak %.1f MB"
+                  % (f, i + 1, med(w), max(w) - min(w), " ".join("%.3f" % x for x in w), res[f]["launches"], res[f]["peak_bytes"] / 1e6))
     allw = {f: [x for w in res[f]["rounds"] for x in w] for f in forms}
     print("  median over all windows (of %d steps): %s" % (steps, "   ".join("%s %.3f ms" % (f, med(allw[f])) for f in forms)))
     if "packed" in forms and "pair" in forms:
         p, q = med(allw["packed"]), med(allw["pair"])
         print("  packed against pair: %+.3f ms (%+.2f %%); rows of the img_emb products: %d packed, %d padded (%.3f)"
               % (p - q, (p / q - 1) * 100, res["packed"]["rows"], res["pair"]["rows"], res["packed"]["rows"] / res["pair"]["rows"]))
+    if "packed-rows" in forms and "packed" in forms:
+        p, q = med(allw["packed-rows"]), med(allw["packed"])
+        print("  packed-rows against packed: %+.3f ms (%+.2f %%); peak memory of one step %.1f MB against %.1f MB"
+              % (p - q, (p / q - 1) * 100, res["packed-rows"]["peak_bytes"] / 1e6, res["packed"]["peak_bytes"] / 1e6))
     print("  one profiled step per form (ms; event brackets add a few us per launch):")
     for f in forms:
         k = res[f]["kernels"]
@@ -236,7 +252,11 @@ def print_forms(res, forms, steps):
         for what, hits in res[f]["img_emb"].items():
             for n, ms, name in hits:
                 print("      img_emb %-32s %-22s %d launch  %7.3f ms" % (what, name, n, ms))
-        for name in ("tanh_dropout_fwd", "tanh_dropout_bwd", "tanh_dropout_unpack_fwd", "tanh_dropout_pack_bwd", "splitk_reduce", "colsum"):
+        for what, (n, ms) in res[f]["vx"].items():
+            print("      %-46s %d launch  %7.3f ms" % (what, n, ms))
+        for name in ("tanh_dropout_fwd", "tanh_dropout_bwd", "tanh_dropout_unpack_fwd", "tanh_dropout_pack_bwd", "tanh_dropout_packed_fwd",
+                     "tanh_dropout_packed_bwd", "guided_logits_fwd", "guided_logits_bwd", "glimpse_pool_fwd", "glimpse_pool_bwd",
+                     "glimpse_dfeat_grouped", "splitk_reduce", "colsum"):
             if name in k:
                 print("      %-28s %4d launches  %7.3f ms" % (name, k[name][0], k[name][1]))
         print("      %-28s %4d launches  %7.3f ms" % ("all kernels", res[f]["launches"], sum(t for _, t in k.values())))
@@ -292,8 +312,10 @@ def main():
         share = float(per_q.float().sum()) / (N * L)
     if a.packed:
         forms = [f for f in a.forms.split(",") if f]
-        if not a.regions or not forms or any(f not in ("packed", "pair", "plain") for f in forms):
-            ap.error("--packed needs --regions MIN,MAX and --forms out of packed,pair,plain")
+        if not a.regions or not forms or any(f not in ("packed-rows", "packed", "pair", "plain") for f in forms):
+            ap.error("--packed needs --regions MIN,MAX and --forms out of packed-rows,packed,pair,plain")
+        if "packed-rows" in forms and a.coatt != "alternating":
+            ap.error("--forms packed-rows needs --coatt alternating")
         res = compare_forms(ladder, img, ids, target, q_len, img_index, img_length, forms, a.steps, a.warmup, a.rounds, a.repeats)
         print("HieCoAttenLadder (coatt=%s) train step, call forms of one batch  B=%d U=%d L=%d img=%d E=%d T=%d%s"
               % (a.coatt, N, U, L, D, E, T, "  question lengths in [3, %d]" % T if a.lengths else ""))

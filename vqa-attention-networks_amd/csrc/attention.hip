@@ -230,11 +230,7 @@ __device__ __forceinline__ int pool_src(const int* __restrict__ idx, int n, int 
 // (Without PACK the kernels keep their own address expressions: their code is what it was before the flag.)
 __device__ __forceinline__ void pool_span(const int* __restrict__ roff, const int* __restrict__ idx, int n, int U, int S, int Rtot,
                                           long long& row0, int& Sv) {
-  const int u = pool_src(idx, n, U);
-  const long long a = roff[u], b = roff[u + 1];
-  const int st = (int)min(max(a, 0LL), (long long)Rtot - 1);
-  row0 = st;
-  Sv = (int)min(max(b - a, 1LL), (long long)min(S, Rtot - st));
+  vqf_packed_span(roff, pool_src(idx, n, U), S, Rtot, row0, Sv);
 }
 
 // grid (ceil(C/1024), N); thread = 4 consecutive channels
@@ -367,9 +363,10 @@ __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
   } else
   for (int s = wave; s < S; s += nwave) {
     const FT* f = PACK ? feat + (row0 + s) * C : feat + ((long long)pool_src(idx, n, U) * S + s) * C;     // (s >= Sv: not read)
-    float* df = dfeat ? dfeat + ((long long)n * S + s) * C : nullptr;
+    // PACK (vqf_glimpse_pool_bwd_packed_dfeat, plain form): dfeat is (Rtot, C) like feat, row start + s; it has no padded rows
+    float* df = dfeat ? (PACK ? dfeat + (row0 + s) * C : dfeat + ((long long)n * S + s) * C) : nullptr;
     if (s >= Sv) {                                     // (wave-uniform) a padded row: zero gradient, feat unread
-      if (df) {
+      if (df && !PACK) {
         if (vec) for (int c = lane * 4; c < C; c += 256) *reinterpret_cast<f32x4*>(df + c) = f32x4{0.f, 0.f, 0.f, 0.f};
         else for (int c = lane; c < C; c += 64) df[c] = 0.f;
       }
@@ -676,12 +673,19 @@ constexpr int GP_Q = 4;          // questions of a group per trip (their dpooled
 
 // dfeat[u, s, c] = sum_{n in group u} sum_g wts[n, g, s] dpooled[n, g C + c].  grid (ceil(S / GP_ROWS), U); a thread owns four
 // channels (and c + 4 blockDim, ...), the weights are workgroup-uniform loads.
-template <int G>
+// PACK (vqf_glimpse_pool_bwd_packed_dfeat, grouped form): dfeat is (Rtot, C), image u's rows l < cnt at start + l by
+// vqf_packed_span's rule; a workgroup whose rows lie behind the count writes nothing (dfeat has no padded rows).
+template <int G, bool PACK = false>
 __global__ void __launch_bounds__(256) glimpse_dfeat_grouped_kernel(const float* __restrict__ dpooled, const float* __restrict__ wts,
                                                                     const int* __restrict__ order, const int* __restrict__ grp_off,
-                                                                    int N, int S, int C, float* __restrict__ dfeat) {
+                                                                    int N, int S, int C, float* __restrict__ dfeat,
+                                                                    const int* __restrict__ roff, int Rtot) {
   const int u = blockIdx.y;
-  const int s0 = blockIdx.x * GP_ROWS, nr = min(GP_ROWS, S - s0);
+  long long row0 = 0;
+  int Sv = S;
+  if (PACK) vqf_packed_span(roff, u, S, Rtot, row0, Sv);
+  const int s0 = blockIdx.x * GP_ROWS, nr = min(GP_ROWS, Sv - s0);
+  if (PACK && nr <= 0) return;
   const int jb = min(max(grp_off[u], 0), N), je = min(max(grp_off[u + 1], jb), N);
   for (int c = threadIdx.x * 4; c < C; c += blockDim.x * 4) {
     f32x4 acc[GP_ROWS];
@@ -712,7 +716,7 @@ __global__ void __launch_bounds__(256) glimpse_dfeat_grouped_kernel(const float*
     }
 #pragma unroll
     for (int r = 0; r < GP_ROWS; ++r)
-      if (r < nr) *reinterpret_cast<f32x4*>(dfeat + ((long long)u * S + s0 + r) * C + c) = acc[r];
+      if (r < nr) *reinterpret_cast<f32x4*>(dfeat + (PACK ? row0 + s0 + r : (long long)u * S + s0 + r) * C + c) = acc[r];
   }
 }
 
@@ -816,7 +820,7 @@ static int glimpse_bwd_grouped(const float* dpooled, const float* dwts_extra, co
   const dim3 grid((S + GP_ROWS - 1) / GP_ROWS, U), block(C / 4 >= 256 ? 256 : ((C / 4 + 63) / 64) * 64);
 #define VQF_GD(G_)                                                                                                      \
   VQF_LAUNCH(KID_GLIMPSE_DFEAT_GROUPED, (glimpse_dfeat_grouped_kernel<G_>), grid, block, 0, s, dpooled, wts, order, grp_off, N, S, C, \
-             dfeat)
+             dfeat, (const int*)nullptr, 0)
   if (G == 3) VQF_GD(3);
   else if (G == 2) VQF_GD(2);
   else VQF_GD(1);
@@ -867,6 +871,35 @@ int vqf_glimpse_pool_bwd_packed(const float* dpooled, const float* dwts_extra, c
   if (rc) return rc;
   return glimpse_bwd_launch<float, true>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, nullptr, stream, roff,
                                          idx, U, R);
+}
+
+// ... and with the gradient of the packed rows: dfeat (R, C) like feat.  Plain form (idx, order, grp_off NULL; U = N): the kernel
+// of vqf_glimpse_pool_bwd_len writing sample n's cnt rows at start + l; grouped form: the dlogits half above, then the per-image sum
+int vqf_glimpse_pool_bwd_packed_dfeat(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
+                                      const int* order, const int* grp_off, const int* roff, int N, int U, int R, int S, int C, int G,
+                                      int unit_softmax, float* dlogits, float* dfeat, void* stream) {
+  if (!dfeat || ((((uintptr_t)order) | ((uintptr_t)grp_off)) & 3) || (idx != nullptr) != (order != nullptr) ||
+      (idx != nullptr) != (grp_off != nullptr))
+    return VQF_E_BADARG;
+  int rc = packed_pool_args(idx, roff, N, U, R, S, C, G);
+  if (rc) return rc;
+  if (!aligned16(dpooled) || !aligned16(feat) || !aligned16(dfeat)) return VQF_E_ALIGN;
+  if (!idx)
+    return glimpse_bwd_launch<float, true>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, dfeat, stream, roff,
+                                           nullptr, U, R);
+  rc = glimpse_bwd_launch<float, true>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, nullptr, stream, roff, idx,
+                                       U, R);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((S + GP_ROWS - 1) / GP_ROWS, U), block(C / 4 >= 256 ? 256 : ((C / 4 + 63) / 64) * 64);
+#define VQF_GD(G_)                                                                                                            \
+  VQF_LAUNCH(KID_GLIMPSE_DFEAT_GROUPED, (glimpse_dfeat_grouped_kernel<G_, true>), grid, block, 0, s, dpooled, wts, order, grp_off, N, \
+             S, C, dfeat, roff, R)
+  if (G == 3) VQF_GD(3);
+  else if (G == 2) VQF_GD(2);
+  else VQF_GD(1);
+#undef VQF_GD
+  return vqf_last_error();
 }
 
 int vqf_row_block_supported(int N, int U, long long blk) {

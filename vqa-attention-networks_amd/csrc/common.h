@@ -71,6 +71,8 @@ enum VqfKernelId {
   KID_TANH_DROP_UNPACK_FWD,
   KID_TANH_DROP_PACK_BWD,
   KID_REGION_ROWS_STAGE,
+  KID_TANH_DROP_PACKED_FWD,
+  KID_TANH_DROP_PACKED_BWD,
   KID_COUNT
 };
 
@@ -188,6 +190,15 @@ template <typename T> __device__ __forceinline__ void vqf_st_stream(T* p, T v) {
 }
 
 __device__ __forceinline__ bool aligned16_dev(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// The span of owner u in a packed (Rtot, .) tensor (include/vqa_fusion.h, "Packed region features"): roff holds owners + 1 row
+// offsets, row0 = clamp(roff[u], 0, Rtot - 1), Sv = clamp(roff[u + 1] - roff[u], 1, min(S, Rtot - row0)) -- whatever roff holds,
+// rows row0 .. row0 + Sv - 1 lie inside the tensor and Sv <= S.
+__device__ __forceinline__ void vqf_packed_span(const int* __restrict__ roff, int u, int S, int Rtot, long long& row0, int& Sv) {
+  const long long a = roff[u], b = roff[u + 1];
+  const int st = (int)min(max(a, 0LL), (long long)Rtot - 1);
+  row0 = st;
+  Sv = (int)min(max(b - a, 1LL), (long long)min(S, Rtot - st));
+}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

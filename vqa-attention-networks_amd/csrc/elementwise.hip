@@ -125,7 +125,9 @@ __global__ void dropout_bt_kernel(const float* __restrict__ x, long long sb_in, 
 // (l, c) is that of the padded tensor, (u*L + l)*E + c: the real rows carry the bits of ew_kernel<1> / <2> on the zero-padded copy.
 // BWD false: y[u*L + l] = tanh(z[start + l]) * sc for l < cnt, exact zero rows behind (nothing read there).
 // BWD true:  dz[start + l] = MODE 2 of ew_kernel on padded row u*L + l, l < cnt; no padded row of dy / y is read.
-template <bool BWD>
+// PACKED (vqf_tanh_dropout_packed_fwd / _bwd): both sides are packed, row start + l of y / dy / dz for l < cnt, and no padded row
+// exists; the dropout index stays that of the padded tensor, so row start + l carries the bits of row u*L + l of the forms above.
+template <bool BWD, bool PACKED = false>
 __global__ void __launch_bounds__(256)
 tanh_drop_repack_kernel(const float* __restrict__ a, const float* __restrict__ yin, const int* __restrict__ roff,
                         const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep, int Rtot, int L, int E4,
@@ -134,13 +136,13 @@ tanh_drop_repack_kernel(const float* __restrict__ a, const float* __restrict__ y
   const long long o0 = roff[u], o1 = roff[u + 1];
   const int start = (int)min(max(o0, 0LL), (long long)Rtot - 1);
   const int cnt = (int)min(max(o1 - o0, 1LL), (long long)min(L, Rtot - start));
-  const unsigned n4 = (unsigned)(BWD ? cnt : L) * (unsigned)E4;
+  const unsigned n4 = (unsigned)((BWD || PACKED) ? cnt : L) * (unsigned)E4;
   const unsigned stride = gridDim.x * blockDim.x;
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     const unsigned l = i / (unsigned)E4, c4 = i - l * (unsigned)E4;
     const long long pad4 = ((long long)u * L + l) * E4 + c4, pk4 = ((long long)start + l) * E4 + c4;
     f32x4 y = {0.f, 0.f, 0.f, 0.f};
-    if (BWD || (int)l < cnt) {
+    if (BWD || PACKED || (int)l < cnt) {
       float sc[4];
       keep4(keep, seed, thr, inv_keep, pad4, sc);
       if (!BWD) {
@@ -148,8 +150,8 @@ tanh_drop_repack_kernel(const float* __restrict__ a, const float* __restrict__ y
 #pragma unroll
         for (int j = 0; j < 4; ++j) y[j] = vqf_tanh_fast(x[j]) * sc[j];
       } else {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(a + 4 * pad4);
-        const f32x4 yy = *reinterpret_cast<const f32x4*>(yin + 4 * pad4);
+        const f32x4 x = *reinterpret_cast<const f32x4*>(a + 4 * (PACKED ? pk4 : pad4));
+        const f32x4 yy = *reinterpret_cast<const f32x4*>(yin + 4 * (PACKED ? pk4 : pad4));
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float t = sc[j] > 0.f ? yy[j] * (1.0f / inv_keep) : 0.f;
@@ -157,7 +159,7 @@ tanh_drop_repack_kernel(const float* __restrict__ a, const float* __restrict__ y
         }
       }
     }
-    *reinterpret_cast<f32x4*>(out + 4 * (BWD ? pk4 : pad4)) = y;
+    *reinterpret_cast<f32x4*>(out + 4 * ((BWD || PACKED) ? pk4 : pad4)) = y;
   }
 }
 
@@ -286,7 +288,7 @@ int ew2d_launch(int kid, const float* a, int lda, const float* b, int ldb, const
   return vqf_last_error();
 }
 
-template <bool BWD>
+template <bool BWD, bool PACKED = false>
 int tanh_drop_repack_launch(const float* a, const float* yin, const int* roff, const uint8_t* keep, uint64_t seed, float p, int U, int R,
                             int L, int E, float* out, void* stream) {
   if (!roff || (((uintptr_t)roff) & 3) || !a || !out || (BWD && !yin) || U <= 0 || R <= 0 || L <= 0 || E <= 0 || p < 0.f || p >= 1.f)
@@ -297,8 +299,9 @@ int tanh_drop_repack_launch(const float* a, const float* yin, const int* roff, c
   const float inv_keep = (keep || p > 0.f) ? 1.0f / (1.0f - p) : 1.0f;
   int chunks = (L * (E / 4) + 255) / 256;                  // L * E / 4 <= 2^24
   if (chunks > 64) chunks = 64;
-  VQF_LAUNCH(BWD ? KID_TANH_DROP_PACK_BWD : KID_TANH_DROP_UNPACK_FWD, tanh_drop_repack_kernel<BWD>, dim3((unsigned)chunks, (unsigned)U),
-             dim3(256), 0, (hipStream_t)stream, a, yin, roff, keep, seed, thr, inv_keep, R, L, E / 4, out);
+  const int kid = PACKED ? (BWD ? KID_TANH_DROP_PACKED_BWD : KID_TANH_DROP_PACKED_FWD)
+                         : (BWD ? KID_TANH_DROP_PACK_BWD : KID_TANH_DROP_UNPACK_FWD);
+  VQF_LAUNCH(kid, (tanh_drop_repack_kernel<BWD, PACKED>), dim3((unsigned)chunks, (unsigned)U), dim3(256), 0, (hipStream_t)stream, a, yin, roff, keep, seed, thr, inv_keep, R, L, E / 4, out);
   return vqf_last_error();
 }
 
@@ -378,6 +381,16 @@ int vqf_tanh_dropout_unpack_fwd(const float* z, const int* roff, const uint8_t* 
 int vqf_tanh_dropout_pack_bwd(const float* dy, const float* y, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop, int U,
                               int R, int L, int E, float* dz, void* stream) {
   return tanh_drop_repack_launch<true>(dy, y, roff, keep, seed, p_drop, U, R, L, E, dz, stream);
+}
+
+int vqf_tanh_dropout_packed_fwd(const float* z, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop, int U, int R, int L,
+                                int E, float* y, void* stream) {
+  return tanh_drop_repack_launch<false, true>(z, nullptr, roff, keep, seed, p_drop, U, R, L, E, y, stream);
+}
+
+int vqf_tanh_dropout_packed_bwd(const float* dy, const float* y, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop, int U,
+                                int R, int L, int E, float* dz, void* stream) {
+  return tanh_drop_repack_launch<true, true>(dy, y, roff, keep, seed, p_drop, U, R, L, E, dz, stream);
 }
 
 int vqf_gate_tanh_sigmoid_fwd(const float* a, const float* b, long long n, float* y, void* stream) {

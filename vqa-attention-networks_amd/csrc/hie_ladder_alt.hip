@@ -27,13 +27,21 @@ inline int gl_rows(int S, int cap) { const int nc = gl_chunks(S, cap); return (S
 // grid (chunks, N), 256 threads.  LDS: [gp[n] (G E) | w (G E)].  idx (N, or null: u = n; the grouped form): question n reads the
 // Xh rows of sample u = idx[n], clamped to [0, U - 1] here, and writes its own logits rows.  A wave takes a row: lane q reads the 16-byte groups
 // q, q + 64, ... of the row's G E contiguous floats (four loads in flight), the group's step is found by comparison.
-template <int G>
+// PACK (vqf_guided_logits_fwd_packed): Xh is (Rtot, ldx), the real rows of every owner one after the other, and roff holds the
+// owners' row offsets; owner u has Sv rows from row0 by vqf_packed_span's rule (common.h), so whatever roff holds the rows read lie
+// inside Xh.  logits stay (N*S, G): rows s >= Sv are written as exact zeros, no Xh row is read for them.
+// (Without PACK the kernels of this file keep their own address expressions: their code is what it was before the flag.)
+template <int G, bool PACK = false>
 __global__ void __launch_bounds__(256) guided_logits_fwd_kernel(const float* __restrict__ Xh, int ldx, const float* __restrict__ gp,
                                                                 const float* __restrict__ w, int S, int E, int rows,
-                                                                float* __restrict__ logits, const int* __restrict__ idx, int U) {
+                                                                float* __restrict__ logits, const int* __restrict__ idx, int U,
+                                                                const int* __restrict__ roff, int Rtot) {
   extern __shared__ __attribute__((aligned(16))) float gl_lds[];
   const int GE = G * E, n = blockIdx.y;
   const int u = idx ? min(max(idx[n], 0), U - 1) : n;               // (uniform) the sample whose Xh rows this question reads
+  long long row0 = 0;
+  int Sv = S;                                                       // (uniform) the owner's real rows
+  if (PACK) vqf_packed_span(roff, u, S, Rtot, row0, Sv);
   float* gs = gl_lds;
   float* ws = gl_lds + GE;
   for (int c = threadIdx.x * 4; c < GE; c += 1024) {
@@ -48,7 +56,11 @@ __global__ void __launch_bounds__(256) guided_logits_fwd_kernel(const float* __r
   constexpr int UNR = 4;
   for (int s = s0 + wave; s < s1; s += 4) {
     const long long r = (long long)n * S + s;
-    const float* x = Xh + ((long long)u * S + s) * ldx;
+    if (PACK && s >= Sv) {                                          // (wave-uniform) behind the count: zero logits, Xh unread
+      if (lane < G) logits[(long long)G * r + lane] = 0.f;
+      continue;
+    }
+    const float* x = PACK ? Xh + (row0 + s) * ldx : Xh + ((long long)u * S + s) * ldx;
     float a[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) a[g] = 0.f;
@@ -84,30 +96,39 @@ __global__ void __launch_bounds__(256) guided_logits_fwd_kernel(const float* __r
 // grid (chunks, N), G E / 4 threads rounded up to whole waves: a thread owns four columns and walks the chunk's rows (four
 // rows in flight), so gp[n], w and the two running sums stay in registers.  part_g / part_w: one row of G E floats per
 // workgroup (row n * chunks + chunk); with one chunk per sample part_g is dgp itself.
-template <int G>
+// PACK (vqf_guided_logits_bwd_packed, plain form): Xh and dXh are (Rtot, .) packed, sample n's Sv rows from row0 (vqf_packed_span);
+// dl stays (N*S, G).  The chunks are those of S: a chunk stops at Sv (rows behind it are neither read nor written, dl included),
+// a chunk wholly behind the count writes zero partial rows -- the partial-row layout, and with it the order of the dgp and dw
+// sums, is that of the padded kernel.
+template <int G, bool PACK = false>
 __global__ void __launch_bounds__(768) guided_logits_bwd_kernel(const float* __restrict__ dl, const float* __restrict__ Xh, int ldx,
                                                                 const float* __restrict__ gp, const float* __restrict__ w, int S,
                                                                 int E, int rows, float* __restrict__ dXh, int ldd,
-                                                                float* __restrict__ part_g, float* __restrict__ part_w) {
+                                                                float* __restrict__ part_g, float* __restrict__ part_w,
+                                                                const int* __restrict__ roff, int Rtot) {
   const int GE = G * E, n = blockIdx.y;
   const int c = threadIdx.x * 4;
   if (c >= GE) return;
-  const int s0 = blockIdx.x * rows, s1 = min(S, s0 + rows);
+  long long row0 = 0;
+  int Sv = S;
+  if (PACK) vqf_packed_span(roff, n, S, Rtot, row0, Sv);
+  const int s0 = blockIdx.x * rows, s1 = min(Sv, s0 + rows);
   const int lv = (G > 1 && c >= E) + (G > 2 && c >= 2 * E);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   const f32x4 gv = gp ? *reinterpret_cast<const f32x4*>(gp + (long long)n * GE + c) : zero;
   const f32x4 wv = *reinterpret_cast<const f32x4*>(w + c);
   f32x4 sg = zero, sw = zero;
   const long long r0 = (long long)n * S;
+  const long long x0 = PACK ? row0 : r0;                           // the first of the sample's rows in Xh / dXh
   constexpr int RB = 4;
   for (int sb = s0; sb < s1; sb += RB) {
     f32x4 x[RB];
     float d[RB];
 #pragma unroll
     for (int q = 0; q < RB; ++q) {
-      const long long r = r0 + min(sb + q, s1 - 1);                // the tail trip re-reads the last row (not used)
-      x[q] = vqf_ld_stream(reinterpret_cast<const f32x4*>(Xh + r * ldx + c));
-      d[q] = dl[(long long)G * r + lv];
+      const int sq = min(sb + q, s1 - 1);                          // the tail trip re-reads the last row (not used)
+      x[q] = vqf_ld_stream(reinterpret_cast<const f32x4*>(Xh + (x0 + sq) * ldx + c));
+      d[q] = dl[(long long)G * (r0 + sq) + lv];
     }
 #pragma unroll
     for (int q = 0; q < RB; ++q) {
@@ -120,7 +141,7 @@ __global__ void __launch_bounds__(768) guided_logits_bwd_kernel(const float* __r
         sg[j] += o[j];
         sw[j] += d[q] * h;
       }
-      *reinterpret_cast<f32x4*>(dXh + (r0 + sb + q) * ldd + c) = o;
+      *reinterpret_cast<f32x4*>(dXh + (x0 + sb + q) * ldd + c) = o;
     }
   }
   const long long prow = ((long long)n * gridDim.x + blockIdx.x) * GE + c;
@@ -134,24 +155,30 @@ __global__ void __launch_bounds__(768) guided_logits_bwd_kernel(const float* __r
 // dXh[u] = the pass's sum, each later pass adds to what the same thread wrote -- a fixed order, no atomics.  part_g: row
 // n * chunks + chunk (each question is in one group: written once); part_w: row u * chunks + chunk.  An empty group writes zero
 // dXh rows and a zero part_w row.  grp_off and order are clamped to [0, N] / [0, N - 1] here: nothing they hold reads out of range.
+// PACK (vqf_guided_logits_bwd_packed, grouped form): Xh and dXh are (Rtot, .) packed, image u's Sv rows from row0; dl stays
+// (N*S, G).  A chunk stops at Sv as in the plain kernel above; an empty group writes zeros on the image's Sv rows.
 constexpr int GL_GRP_Q = 4;
 
-template <int G>
+template <int G, bool PACK = false>
 __global__ void __launch_bounds__(768) guided_logits_bwd_grouped_kernel(const float* __restrict__ dl, const float* __restrict__ Xh,
                                                                         int ldx, const float* __restrict__ gp,
                                                                         const float* __restrict__ w, const int* __restrict__ order,
                                                                         const int* __restrict__ grp_off, int N, int S, int E, int rows,
                                                                         float* __restrict__ dXh, int ldd, float* __restrict__ part_g,
-                                                                        float* __restrict__ part_w) {
+                                                                        float* __restrict__ part_w, const int* __restrict__ roff,
+                                                                        int Rtot) {
   const int GE = G * E, u = blockIdx.y;
   const int c = threadIdx.x * 4;
   if (c >= GE) return;
-  const int s0 = blockIdx.x * rows, s1 = min(S, s0 + rows);
+  long long row0 = 0;
+  int Sv = S;
+  if (PACK) vqf_packed_span(roff, u, S, Rtot, row0, Sv);
+  const int s0 = blockIdx.x * rows, s1 = min(Sv, s0 + rows);
   const int lv = (G > 1 && c >= E) + (G > 2 && c >= 2 * E);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   const f32x4 wv = *reinterpret_cast<const f32x4*>(w + c);
   const int jb = min(max(grp_off[u], 0), N), je = min(max(grp_off[u + 1], jb), N);
-  const long long r0 = (long long)u * S;
+  const long long r0 = PACK ? row0 : (long long)u * S;              // the first of the image's rows in Xh / dXh
   f32x4 sw = zero;
   if (jb == je)
     for (int s = s0; s < s1; ++s) *reinterpret_cast<f32x4*>(dXh + (r0 + s) * ldd + c) = zero;
@@ -212,7 +239,7 @@ int vqf_guided_logits_fwd(const float* Xh, int ldx, const float* gp, const float
   const size_t lds = (size_t)2 * G * E * sizeof(float);
 #define VQF_GL(G_) \
   VQF_LAUNCH(KID_GUIDED_FWD, (guided_logits_fwd_kernel<G_>), grid, dim3(256), lds, s, Xh, ldx, gp, w, S, E, rows, logits, \
-             (const int*)nullptr, N)
+             (const int*)nullptr, N, (const int*)nullptr, 0)
   if (G == 3) VQF_GL(3);
   else if (G == 2) VQF_GL(2);
   else VQF_GL(1);
@@ -236,7 +263,8 @@ int vqf_guided_logits_fwd_grouped(const float* Xh, int ldx, const float* gp, con
   const dim3 grid(gl_chunks(S, rows), N);
   const size_t lds = (size_t)2 * G * E * sizeof(float);
 #define VQF_GL(G_) \
-  VQF_LAUNCH(KID_GUIDED_FWD, (guided_logits_fwd_kernel<G_>), grid, dim3(256), lds, s, Xh, ldx, gp, w, S, E, rows, logits, idx, U)
+  VQF_LAUNCH(KID_GUIDED_FWD, (guided_logits_fwd_kernel<G_>), grid, dim3(256), lds, s, Xh, ldx, gp, w, S, E, rows, logits, idx, U, \
+             (const int*)nullptr, 0)
   if (G == 3) VQF_GL(3);
   else if (G == 2) VQF_GL(2);
   else VQF_GL(1);
@@ -268,7 +296,7 @@ int vqf_guided_logits_bwd(const float* dlogits, const float* Xh, int ldx, const 
   const dim3 grid(chunks, N), block(((GE / 4 + 63) / 64) * 64);
 #define VQF_GL(G_)                                                                                                              \
   VQF_LAUNCH(KID_GUIDED_BWD, (guided_logits_bwd_kernel<G_>), grid, block, 0, s, dlogits, Xh, ldx, gp, w, S, E, rows, dXh, lddx, \
-             part_g, part_w)
+             part_g, part_w, (const int*)nullptr, 0)
   if (G == 3) VQF_GL(3);
   else if (G == 2) VQF_GL(2);
   else VQF_GL(1);
@@ -306,12 +334,89 @@ int vqf_guided_logits_bwd_grouped(const float* dlogits, const float* Xh, int ldx
   const dim3 grid(chunks, U), block(((GE / 4 + 63) / 64) * 64);
 #define VQF_GL(G_)                                                                                                               \
   VQF_LAUNCH(KID_GUIDED_BWD, (guided_logits_bwd_grouped_kernel<G_>), grid, block, 0, s, dlogits, Xh, ldx, gp, w, order, grp_off, \
-             N, S, E, rows, dXh, lddx, part_g, part_w)
+             N, S, E, rows, dXh, lddx, part_g, part_w, (const int*)nullptr, 0)
   if (G == 3) VQF_GL(3);
   else if (G == 2) VQF_GL(2);
   else VQF_GL(1);
 #undef VQF_GL
   int rc = vqf_last_error();
+  if (rc) return rc;
+  if (chunks > 1) {
+    rc = vqf_group_reduce_f32(part_g, N, chunks, GE, dgp, stream);           // dgp[n] = its chunks' rows, in chunk order
+    if (rc) return rc;
+  }
+  return vqf_colreduce_2stage(part_w, U * chunks, GE, dw, scratch, s);
+}
+
+// ---- the packed forms: Xh / dXh (R, .) hold the real rows only, roff (owners + 1) int32 row offsets --------------------------
+int vqf_guided_logits_packed_supported(int N, int U, int R, int S, int E, int G) {
+  return vqf_guided_logits_grouped_supported(N, U, S, E, G) && R >= 1 && R < (1 << 29);
+}
+
+// what both packed entry points refuse first; idx / order / grp_off decide the form (NULL: plain, U must equal N)
+static int guided_packed_args(const int* own, const int* roff, int N, int U, int R, int S, int E, int G) {
+  if (!roff || ((((uintptr_t)own) | ((uintptr_t)roff)) & 3) || R <= 0 || N <= 0 || U <= 0 || S <= 0 || E <= 0 || G <= 0)
+    return VQF_E_BADARG;
+  if (!own && U != N) return VQF_E_BADARG;
+  if (!vqf_guided_logits_packed_supported(N, U, R, S, E, G)) return VQF_E_UNSUPPORTED;
+  return VQF_OK;
+}
+
+int vqf_guided_logits_fwd_packed(const float* Xh, int ldx, const float* gp, const float* w, const int* idx, const int* roff, int N,
+                                 int U, int R, int S, int E, int G, float* logits, void* stream) {
+  if (!Xh || !w || !logits || ldx < G * E || (ldx % 4)) return VQF_E_BADARG;
+  const int rc = guided_packed_args(idx, roff, N, U, R, S, E, G);
+  if (rc) return rc;
+  if (!aligned16(Xh) || !aligned16(gp) || !aligned16(w)) return VQF_E_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  const int rows = gl_rows(S, GL_FWD_ROWS);
+  const dim3 grid(gl_chunks(S, rows), N);
+  const size_t lds = (size_t)2 * G * E * sizeof(float);
+#define VQF_GL(G_)                                                                                                             \
+  VQF_LAUNCH(KID_GUIDED_FWD, (guided_logits_fwd_kernel<G_, true>), grid, dim3(256), lds, s, Xh, ldx, gp, w, S, E, rows, logits, idx, \
+             U, roff, R)
+  if (G == 3) VQF_GL(3);
+  else if (G == 2) VQF_GL(2);
+  else VQF_GL(1);
+#undef VQF_GL
+  return vqf_last_error();
+}
+
+size_t vqf_guided_logits_bwd_packed_ws_bytes(int N, int U, int S, int E, int G) {
+  return vqf_guided_logits_bwd_grouped_ws_bytes(N, U, S, E, G);              // U = N in the plain form: the layout of the plain kernel
+}
+
+int vqf_guided_logits_bwd_packed(const float* dlogits, const float* Xh, int ldx, const float* gp, const float* w, const int* order,
+                                 const int* grp_off, const int* roff, int N, int U, int R, int S, int E, int G, float* dXh, int lddx,
+                                 float* dgp, float* dw, void* ws, size_t ws_bytes, void* stream) {
+  if (!dlogits || !Xh || !w || !dXh || !dgp || !dw || ldx < G * E || lddx < G * E || (ldx % 4) || (lddx % 4) ||
+      (order != nullptr) != (grp_off != nullptr) || (order && !gp) || (((uintptr_t)grp_off) & 3))
+    return VQF_E_BADARG;
+  int rc = guided_packed_args(order, roff, N, U, R, S, E, G);
+  if (rc) return rc;
+  if (!aligned16(Xh) || !aligned16(gp) || !aligned16(w) || !aligned16(dXh) || !aligned16(dgp) || !aligned16(ws)) return VQF_E_ALIGN;
+  if (!ws || ws_bytes < vqf_guided_logits_bwd_packed_ws_bytes(N, U, S, E, G)) return VQF_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const int GE = G * E;
+  const int rows = gl_rows(S, GL_BWD_ROWS), chunks = gl_chunks(S, rows);     // the chunks of S: the padded kernels' partial rows
+  float* part_w = (float*)ws;                                                 // (U * chunks, GE)
+  float* part_g = chunks == 1 ? dgp : part_w + (size_t)U * chunks * GE;       // (N * chunks, GE)
+  float* scratch = part_w + ((size_t)U + N) * chunks * GE;
+  const dim3 grid(chunks, U), block(((GE / 4 + 63) / 64) * 64);
+#define VQF_GL(G_)                                                                                                                  \
+  do {                                                                                                                              \
+    if (order)                                                                                                                      \
+      VQF_LAUNCH(KID_GUIDED_BWD, (guided_logits_bwd_grouped_kernel<G_, true>), grid, block, 0, s, dlogits, Xh, ldx, gp, w, order,   \
+                 grp_off, N, S, E, rows, dXh, lddx, part_g, part_w, roff, R);                                                      \
+    else                                                                                                                            \
+      VQF_LAUNCH(KID_GUIDED_BWD, (guided_logits_bwd_kernel<G_, true>), grid, block, 0, s, dlogits, Xh, ldx, gp, w, S, E, rows, dXh, \
+                 lddx, part_g, part_w, roff, R);                                                                                    \
+  } while (0)
+  if (G == 3) VQF_GL(3);
+  else if (G == 2) VQF_GL(2);
+  else VQF_GL(1);
+#undef VQF_GL
+  rc = vqf_last_error();
   if (rc) return rc;
   if (chunks > 1) {
     rc = vqf_group_reduce_f32(part_g, N, chunks, GE, dgp, stream);           // dgp[n] = its chunks' rows, in chunk order

@@ -51,7 +51,8 @@ const char* const kNames[KID_COUNT] = {
     "lstm_cell_fwd", "lstm_cell_bwd", "embed_tanh_fwd", "embed_tanh_bwd", "hbm_copy", "hbm_read_sweep", "multi_add", "multi_copy", "hie_hv_fwd", "hie_head_bwd", "hie_rank_add", "hie_rank_left", "hie_slab_sum", "hie_affinity",
     "phrase_ngram_fwd", "phrase_ngram_bwd", "hie_affinity_levels", "guided_logits_fwd", "guided_logits_bwd",
     "ce_loss_pred", "answer_match_rows", "topk_rows", "glimpse_dfeat_grouped", "row_block_gather", "row_block_group_sum",
-    "mfb_fuse_bwd_image", "zero_cols_len", "tanh_dropout_unpack_fwd", "tanh_dropout_pack_bwd", "region_rows_stage"};
+    "mfb_fuse_bwd_image", "zero_cols_len", "tanh_dropout_unpack_fwd", "tanh_dropout_pack_bwd", "region_rows_stage",
+    "tanh_dropout_packed_fwd", "tanh_dropout_packed_bwd"};
 
 hipEvent_t get_event() {
   std::lock_guard<std::mutex> lk(g_mu);

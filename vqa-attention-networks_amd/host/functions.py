@@ -833,6 +833,26 @@ class TanhDropUnpackFn(torch.autograd.Function):
         return dz, None, None, None, None, None, None
 
 
+class TanhDropPackedFn(torch.autograd.Function):
+    """y (R, E) = dropout(tanh(z)) with BOTH sides packed (HieCoAttenLadder(packed_coatt=True) on a PackedRegions): the rows of
+    TanhDropUnpackFn without the padded layout.  The masks stay those of the padded tensor (keep (U*L, E), Philox index
+    (u*L + l)*E + c), so row start + l holds the bits of TanhDropUnpackFn's row u*L + l.  Backward: dz (R, E)."""
+
+    @staticmethod
+    def forward(ctx, z, roff, U, L, keep, seed, p_drop):
+        y = ops.tanh_dropout_packed_fwd(_c(z), roff, U, L, keep=keep, seed=seed, p_drop=p_drop)
+        ctx.save_for_backward(y, roff)
+        ctx.keep, ctx.seed, ctx.p, ctx.dims = keep, seed, p_drop, (U, L)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, roff = ctx.saved_tensors
+        U, L = ctx.dims
+        dz = ops.tanh_dropout_packed_bwd(_c(dy), y, roff, U, L, keep=ctx.keep, seed=ctx.seed, p_drop=ctx.p)
+        return dz, None, None, None, None, None, None
+
+
 class GateFn(torch.autograd.Function):
     """y = tanh(a) * sigmoid(b): the gate of Nonlinear_layer (modules.py:103-109), one launch each way."""
 

@@ -97,6 +97,17 @@ on the code is that of the region-count call (rlens, the *_regions / *_len kerne
 on the host; the kernels clamp what it holds (include/vqa_fusion.h).  The Vh / VX products, the affinity and the rank-T passes stay
 padded (N*L rows), as in the region-count call; fp32 only.
 
+Packed co-attention rows.  HieCoAttenLadder(coatt="alternating", packed_coatt=True) -- opt-in, default off -- keeps the whole image
+side of the alternating levels on the R real rows when it is handed a PackedRegions: V stays (R, E) (vqf_tanh_dropout_packed_fwd /
+_bwd: both sides packed, the masks still those of the padded (U*L, E) tensor), VX = V [img_x]^T + b and dVX are (R, 3E), step 2 runs on
+vqf_guided_logits_fwd_packed / _bwd_packed and vqf_glimpse_pool_fwd_packed / _bwd_packed_dfeat (their grouped forms with img_index),
+dV is (R, E), and dV += dVX wimg and dwimg = dVX^T V are products on R rows.  The result is still, by definition, the model on
+(packed.unpack(), ...): av (N, 3, L) with exact zeros behind each count, the same parameters and state_dict, offsets never read on
+the host.  Against packed_coatt=False only the summation order of dwimg (and of the products' K splits) differs, so the two agree
+to rounding, not bit for bit.  What stays padded or untouched: the question side (QX and everything over (N*T, .)), parallel mode
+(its Vh product, affinity and rank-T passes: packed_coatt=True raises ValueError there), bf16, and the HieCoAtten class.  With a
+plain tensor or the pair the keyword changes nothing: the same code path, bit for bit.
+
 Stages (every product and every pass over an (N*L, .) or (N*T, .) tensor runs in libvqa_fusion.so):
   * img_emb / word embedding: LinearFn + TanhDropFn, EmbedTanhFn + DropoutFn;
   * phrase level (PhraseFn): the six conv taps as one GEMM, then vqf_phrase_ngram_fwd / _bwd (csrc/hie_ladder.hip);
@@ -113,7 +124,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .functions import (_c, _hie_hv_ti, _hie_dc, _hie_bwd_bgemm, EmbedTanhFn, LinearFn, DropoutFn, TanhDropFn, TanhDropUnpackFn, DropoutBTFn,
+from .functions import (_c, _hie_hv_ti, _hie_dc, _hie_bwd_bgemm, EmbedTanhFn, LinearFn, DropoutFn, TanhDropFn, TanhDropUnpackFn, TanhDropPackedFn,
+                        DropoutBTFn,
                         LstmBatchFn)
 from .grouping import _group_index, _region_lens, check_img_length, check_packed_regions, PackedRegions    # (_group_index: importable from here as before)
 from .lib import VqfError
@@ -332,16 +344,20 @@ class LadderAltCoattFn(torch.autograd.Function):
     over the real regions (vqf_glimpse_pool_fwd_len / _bwd_len, the _grouped_len forms with grp); its zero dlogits rows give zero
     dVX rows out of the guided-logits backward.  Host wiring only: no kernel of this mode knows the counts but the pooling.
     grp (None, or (idx, order, grp_off) of _group_index): V is (U*L, E), shared -- VX stays (U*L, 3E), step 2 runs on the grouped
-    entry points (question n reads image idx[n]'s rows; dV and dVX sum each image's questions in `order`)."""
+    entry points (question n reads image idx[n]'s rows; dV and dVX sum each image's questions in `order`).
+    roff (None, or the (U + 1,) int32 row offsets of a PackedRegions: HieCoAttenLadder(packed_coatt=True)): the image side on the
+    PACKED rows -- V is (R, E), VX = V [img_x]^T + b and dVX are (R, 3E), dV is (R, E); step 2 runs on vqf_guided_logits_fwd_packed /
+    _bwd_packed and vqf_glimpse_pool_fwd_packed / _bwd_packed_dfeat (with grp their grouped forms), which take the counts from roff
+    (rlens is not used); av stays (N, 3, L) with exact zeros behind each count.  The dV += dVX wimg and dwimg products run on R rows."""
 
     PER_LEVEL = 11
 
     @staticmethod
-    def forward(ctx, V, q0, q1, q2, N, L, T, lens, grp, rlens, *w):
+    def forward(ctx, V, q0, q1, q2, N, L, T, lens, grp, rlens, roff, *w):
         E = V.shape[1]
         lk = {} if lens is None else {"lens": lens}
         rk = {} if rlens is None else {"lens": rlens}                               # the image-side pooling's counts
-        U = V.shape[0] // L
+        U = V.shape[0] // L if roff is None else roff.shape[0] - 1
         MT = N * T
         dev = V.device
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
@@ -353,7 +369,10 @@ class LadderAltCoattFn(torch.autograd.Function):
         whimg = torch.cat(img_h, 0).contiguous()                                    # (3, E)
         wq2 = [torch.cat([sum_x[g], que_x[g]], 0).contiguous() for g in range(3)]   # (2E, E) each
         bq2 = [torch.cat([sum_b[g], que_b[g]], 0).contiguous() for g in range(3)]
-        VX = ops.gemm_rows(V, wimg, L, bias=bimg)                                   # (U*L, 3E) = [img_0 | img_1 | img_2]
+        if roff is None:
+            VX = ops.gemm_rows(V, wimg, L, bias=bimg)                               # (U*L, 3E) = [img_0 | img_1 | img_2]
+        else:
+            VX = ops.gemm(V, wimg, bias=bimg)                                       # (R, 3E): the real rows only
         QX = new(MT, 6 * E)                                                         # [sum_0 | que_0 | sum_1 | que_1 | sum_2 | que_2]
         for g in range(3):
             ops.gemm(Q[g], wq2[g], bias=bq2[g], out=QX[:, 2 * g * E:(2 * g + 2) * E])
@@ -368,7 +387,11 @@ class LadderAltCoattFn(torch.autograd.Function):
         gpv = new(N, 3 * E)
         for g in range(3):
             ops.gemm(s[g], img_g[g], out=gpv[:, g * E:(g + 1) * E])
-        if grp is None:
+        if roff is not None:                                                        # the counts ride in roff
+            idx = None if grp is None else grp[0]
+            av, vcat = ops.glimpse_pool_fwd_packed(V, ops.guided_logits_fwd_packed(VX, gpv, whimg, roff, N, L, idx=idx), roff, N, L,
+                                                   False, idx=idx)
+        elif grp is None:
             av, vcat = ops.glimpse_pool_fwd(V.view(N, L, E), ops.guided_logits_fwd(VX, gpv, whimg, N, L), False, **rk)   # (N, 3, L), (N, 3E)
         else:
             av, vcat = ops.glimpse_pool_fwd_grouped(V.view(U, L, E), ops.guided_logits_fwd_grouped(VX, gpv, whimg, grp[0], N, U, L),
@@ -384,7 +407,7 @@ class LadderAltCoattFn(torch.autograd.Function):
             qo.append(q_g)
         ctx.save_for_backward(V, q0, q1, q2, wimg, whimg, VX, QX, gpv, gpq, vcat, av, *wq2, *sum_h, *img_g, *que_g, *que_h, *s, *asum,
                               *aq, *(grp or ()))
-        ctx.dims, ctx.lens, ctx.rlens = (N, L, T, E), lens, rlens
+        ctx.dims, ctx.lens, ctx.rlens, ctx.roff = (N, L, T, E), lens, rlens, roff
         ctx.set_materialize_grads(False)
         return (vcat, qo[0], qo[1], qo[2], av, aq[0], aq[1], aq[2])
 
@@ -395,7 +418,8 @@ class LadderAltCoattFn(torch.autograd.Function):
         wq2, sum_h, img_g, que_g, que_h, s, asum, aq = (t[12 + 3 * i:15 + 3 * i] for i in range(8))
         grp = t[36:39]                                                              # (idx, order, grp_off), or empty
         N, L, T, E = ctx.dims
-        U = V.shape[0] // L
+        roff = ctx.roff
+        U = V.shape[0] // L if roff is None else roff.shape[0] - 1
         MT = N * T
         dev = V.device
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
@@ -420,13 +444,16 @@ class LadderAltCoattFn(torch.autograd.Function):
             dQ.append(dQg.view(MT, E))
         # step 2: one G = 3 pooling backward over V, one G = 3 guided-logits backward over VX
         dwts = None if dav is None else _c(dav)
-        if not grp:
+        if roff is not None:        # dV (R, E) and dVX (R, 3E): the real rows only
+            dlv, dV = ops.glimpse_pool_bwd_packed_dfeat(dvc, V, av, roff, False, grp=grp or None, dwts=dwts)
+            dVX, dgpv, dwhimg = ops.guided_logits_bwd_packed(dlv, VX, gpv, whimg, roff, N, L, grp=grp or None)
+        elif not grp:
             dlv, dV = ops.glimpse_pool_bwd(dvc, V.view(N, L, E), av, False, True, dwts=dwts, **rk)
             dVX, dgpv, dwhimg = ops.guided_logits_bwd(dlv, VX, gpv, whimg, N, L)
         else:                       # dV (U, L, E) and dVX (U*L, 3E): each image's questions summed in `order`
             dlv, dV = ops.glimpse_pool_bwd_grouped(dvc, V.view(U, L, E), av, grp[0], grp[1], grp[2], True, dwts=dwts, **rk)
             dVX, dgpv, dwhimg = ops.guided_logits_bwd_grouped(dlv, VX, gpv, whimg, grp[1], grp[2], N, U, L)
-        dV = dV.view(U * L, E)
+        dV = dV.view(V.shape[0], E)
         dbimg = ops.colsum(dgpv)
         ops.gemm(dVX, wimg, tb=True, out=dV, accumulate=True)                      # dV += dVX [img_x_0; img_x_1; img_x_2]
         dwimg = ops.gemm(dVX, V, ta=True, tb=True)                                 # (3E, E)
@@ -446,7 +473,7 @@ class LadderAltCoattFn(torch.autograd.Function):
             grads += [dwq2[:E], ops.colsum(dgp), dwsum_h, dwimg[blk], dbimg[blk], dimg_g, dwhimg[g:g + 1], dwq2[E:], g3[g][0],
                       g3[g][1], g3[g][2]]
         ops.multi_add([(dQ[g], dQ1[g], dQ[g]) for g in range(3)])                   # dQ_i: step 3's + the pair's + step 1's
-        return (dV, dQ[0], dQ[1], dQ[2], None, None, None, None, None, None, *grads)
+        return (dV, dQ[0], dQ[1], dQ[2], None, None, None, None, None, None, None, *grads)
 
 
 class _Coatt(nn.Module):
@@ -516,16 +543,28 @@ class HieCoAttenLadder(nn.Module):
     and its weight gradient run on the R real rows (module docstring, "Packed regions").  A malformed object, rows on another
     device or of another channel count, more than 65535 images or R >= 2^29 raise VqfError before the first launch.
 
+    packed_coatt (constructor keyword, default False; stored as self.packed_coatt): True keeps the image side of the ALTERNATING
+    levels on the R packed rows when forward is handed a PackedRegions (V, VX = V [img_x]^T + b, dVX and dV have R rows; module
+    docstring, "Packed co-attention rows").  It is the same model -- the same parameters and state_dict, av (N, 3, L) with exact
+    zeros behind each count, set_keep_masks(img=...) still (U*L, E) -- and agrees with False to rounding (the dwimg sum runs over R
+    rows instead of U*L).  With a plain tensor or the pair it changes nothing, bit for bit.  True with coatt="parallel" raises
+    ValueError at construction: there is nothing to keep packed there.  Shapes outside vqf_guided_logits_packed_supported raise
+    VqfError before the first launch.
+
     The image features are data (img_features.requires_grad raises), fp32 on the GPU: CPU tensors and bf16 features raise
     VqfError -- there is no CPU fallback.  Dropout (rate drop_p) is active in train mode only;
     set_keep_masks() supplies explicit uint8 keep-masks for the tests, otherwise the kernels draw Philox masks."""
 
     def __init__(self, block_num=196, word_num=22, img_size=2048, vocab_size=15881, embed_size=512, hidden_size=1024,
-                 output_size=3000, drop_p=0.5, coatt="parallel"):
+                 output_size=3000, drop_p=0.5, coatt="parallel", packed_coatt=False):
         super(HieCoAttenLadder, self).__init__()
         if coatt not in COATT_MODES:
             raise ValueError("HieCoAttenLadder: coatt must be one of %s, got %r" % (", ".join(COATT_MODES), coatt))
+        if packed_coatt and coatt != "alternating":
+            raise ValueError("HieCoAttenLadder: packed_coatt=True needs coatt='alternating' (parallel mode has no image-side pass "
+                             "that runs on packed rows), got coatt=%r" % (coatt,))
         self.coatt_mode = coatt
+        self.packed_coatt = bool(packed_coatt)
         E = embed_size
         self.img_emb = nn.Linear(img_size, E)
         self.word_emb = nn.Embedding(vocab_size, E)
@@ -604,6 +643,12 @@ class HieCoAttenLadder(nn.Module):
         if alt and not (ops.guided_logits_supported(N, L, E, 3) and ops.guided_logits_supported(N, T, E, 1)):
             raise VqfError("HieCoAttenLadder(coatt='alternating'): embed_size %% 32 == 0, embed_size <= 1024, L <= 1024 and "
                            "N <= 65535 are supported (got E=%d, L=%d, T=%d, N=%d)" % (E, L, T, N))
+        rows_coatt = packed is not None and self.packed_coatt                   # the image side of the co-attention on the R rows
+        if rows_coatt and not (ops.guided_logits_packed_supported(N, U, img_features.shape[0], L, E, 3) and
+                               ops.glimpse_pool_grouped_supported(N, U, L, E, 3)):
+            raise VqfError("HieCoAttenLadder(packed_coatt=True): embed_size %% 32 == 0, embed_size <= 1024, max_regions <= 1024, "
+                           "N <= 65535, 1 <= images <= 65535 and 1 <= R < 2^29 are supported (got E=%d, L=%d, N=%d, images=%d, R=%d)"
+                           % (E, L, N, U, img_features.shape[0]))
         grp = None
         if img_index is not None:
             if not torch.is_tensor(img_index) or img_index.dtype not in (torch.int64, torch.int32):
@@ -636,9 +681,10 @@ class HieCoAttenLadder(nn.Module):
             rlens = _region_lens(img_length, L, None if grp is None else grp[0])   # O(N), on the device: nothing is read back
             if grp is not None:
                 rlens = rlens[0]
-        if packed is not None:             # O(U), on the device: nothing is read back; the kernels clamp what roff holds
+        if packed is not None:            # O(U), on the device: nothing is read back; the kernels clamp what roff holds
             off = packed.offsets
             roff = off.to(torch.int32).contiguous()
+        if packed is not None and not rows_coatt:
             rlens = _region_lens(off[1:] - off[:-1], L, None if grp is None else grp[0])
             if grp is not None:
                 rlens = rlens[0]
@@ -650,7 +696,10 @@ class HieCoAttenLadder(nn.Module):
             V = TanhDropFn.apply(V, None, keep, seed, self.drop_p if keep is not None else p)       # (U*L, E): once per image
         else:                              # the product on the R real rows; the tanh / dropout pass lays V out padded
             V = LinearFn.apply(_c(img_features), self.img_emb.weight, self.img_emb.bias, False)      # (R, E)
-            V = TanhDropUnpackFn.apply(V, roff, U, L, keep, seed, self.drop_p if keep is not None else p)   # (U*L, E), zero padded rows
+            if rows_coatt:                 # V stays (R, E): the masks of the padded tensor on the real rows
+                V = TanhDropPackedFn.apply(V, roff, U, L, keep, seed, self.drop_p if keep is not None else p)
+            else:
+                V = TanhDropUnpackFn.apply(V, roff, U, L, keep, seed, self.drop_p if keep is not None else p)   # (U*L, E), zero padded rows
         if grp is not None and not alt:
             V = RowBlockGatherFn.apply(V, grp[0], grp[1], grp[2], L)                                  # (N*L, E)
         # Qw = drop(tanh(word_emb(ids)))
@@ -669,7 +718,8 @@ class HieCoAttenLadder(nn.Module):
             w = [p_ for c in self.coatt for p_ in (c.sum_x.weight, c.sum_x.bias, c.sum_h.weight, c.img_x.weight, c.img_x.bias,
                                                    c.img_g.weight, c.img_h.weight, c.que_x.weight, c.que_x.bias, c.que_g.weight,
                                                    c.que_h.weight)]
-            vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderAltCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, grp, rlens, *w)
+            vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderAltCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, grp, rlens,
+                                                                         roff if rows_coatt else None, *w)
         else:
             w = [p_ for c in self.coatt for p_ in (c.Wb.weight, c.Wv.weight, c.Wq.weight, c.whv.weight, c.whq.weight)]
             vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, rlens, *w)

@@ -183,6 +183,16 @@ SIGNATURES = {
     "vqf_tanh_dropout_unpack_supported": (c_i, [c_i, c_i, c_i, c_i]),
     "vqf_tanh_dropout_unpack_fwd": (c_i, [c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_p]),
     "vqf_tanh_dropout_pack_bwd": (c_i, [c_f, c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_p]),
+    "vqf_tanh_dropout_packed_fwd": (c_i, [c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_p]),
+    "vqf_tanh_dropout_packed_bwd": (c_i, [c_f, c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_p]),
+    # the packed forms of the alternating image side (HieCoAttenLadder(packed_coatt=True)): Xh / dXh / feat / dfeat (R, .), roff c_p
+    "vqf_guided_logits_packed_supported": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    "vqf_guided_logits_fwd_packed": (c_i, [c_f, c_i, c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
+    "vqf_guided_logits_bwd_packed_ws_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+    "vqf_guided_logits_bwd_packed": (c_i, [c_f, c_f, c_i, c_f, c_f, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_f,
+                                           c_p, c_sz, c_p]),
+    "vqf_glimpse_pool_bwd_packed_dfeat": (c_i, [c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f,
+                                                c_p]),
     "vqf_lstm_seq_supported": (c_i, [c_i, c_i]),
     "vqf_lstm_seq_ws_bytes": (c_sz, [c_i, c_i]),
     "vqf_lstm_seq_fwd": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_p, c_sz, c_p]),

@@ -517,6 +517,38 @@ def tanh_dropout_pack_bwd(dy, y, roff, U, R, L, keep=None, seed=0, p_drop=0.5):
     return dz
 
 
+def tanh_dropout_packed_fwd(z, roff, U, L, keep=None, seed=0, p_drop=0.5):
+    """z (R, E) packed rows, roff (U + 1) int32 -> y (R, E) packed: row start + l is row u*L + l of tanh_dropout_unpack_fwd, bit
+    for bit (masks in the padded coordinates: keep (U*L, E), Philox index (u*L + l)*E + c); no padded row exists."""
+    _chk(z)
+    if z.dim() != 2:
+        raise _l.VqfError("tanh_dropout_packed_fwd: z must be (R, E)")
+    R, E = z.shape
+    _unpack_operands("tanh_dropout_packed_fwd", roff, U, R, L, E)
+    if keep is not None and keep.numel() != U * L * E:
+        raise _l.VqfError("tanh_dropout_packed_fwd: keep must be (U*L, E) = (%d, %d)" % (U * L, E))
+    y = torch.empty((R, E), dtype=torch.float32, device=z.device)
+    _l.check(_lib().vqf_tanh_dropout_packed_fwd(_ptr(z), _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop), U, R, L, E, _ptr(y),
+                                                _stream()), "vqf_tanh_dropout_packed_fwd")
+    return y
+
+
+def tanh_dropout_packed_bwd(dy, y, roff, U, L, keep=None, seed=0, p_drop=0.5):
+    """dy, y (R, E) packed, roff (U + 1) int32 -> dz (R, E) packed: the backward of tanh_dropout_packed_fwd, the bits of
+    tanh_dropout_pack_bwd on the padded operands."""
+    _chk(dy, y)
+    if y.dim() != 2 or dy.shape != y.shape:
+        raise _l.VqfError("tanh_dropout_packed_bwd: dy and y must be (R, E)")
+    R, E = y.shape
+    _unpack_operands("tanh_dropout_packed_bwd", roff, U, R, L, E)
+    if keep is not None and keep.numel() != U * L * E:
+        raise _l.VqfError("tanh_dropout_packed_bwd: keep must be (U*L, E) = (%d, %d)" % (U * L, E))
+    dz = torch.empty((R, E), dtype=torch.float32, device=y.device)
+    _l.check(_lib().vqf_tanh_dropout_packed_bwd(_ptr(dy), _ptr(y), _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop), U, R, L, E,
+                                                _ptr(dz), _stream()), "vqf_tanh_dropout_packed_bwd")
+    return dz
+
+
 def tanh_bwd_rows_len(dy, y, lens, N, T, out=None):
     """dx = dy (1 - y^2) on the rows t < lens[n] of contiguous (N, T, L) tensors, zero on the others (in place allowed)"""
     _chk(dy, y, out)
@@ -1476,6 +1508,86 @@ def glimpse_pool_bwd_packed(dpooled, feat, wts, roff, unit_softmax, idx=None, dw
     _l.check(_lib().vqf_glimpse_pool_bwd_packed(_ptr(dpooled), _ptr(dwts), _ptr(feat), _ptr(wts), _ptr(idx), _ptr(roff), N, U, R, S, C,
                                                 G, int(bool(unit_softmax)), _ptr(dlogits), _stream()), "vqf_glimpse_pool_bwd_packed")
     return dlogits
+
+
+def glimpse_pool_bwd_packed_dfeat(dpooled, feat, wts, roff, unit_softmax, grp=None, dwts=None):
+    """glimpse_pool_bwd_packed with the gradient of the packed rows: -> (dlogits (N*S, G), dfeat (R, C)).  grp None: sample n owns
+    roff[n] ..; grp = (idx, order, grp_off): roff is per image and dfeat sums each image's questions in `order` (zeros for an image
+    without a question).  glimpse_pool_bwd(lens=) / _grouped(lens=) on the padded copy, dfeat its real rows."""
+    _chk(dpooled, wts, dwts)
+    N, G, S = wts.shape
+    idx, order, grp_off = grp if grp is not None else (None, None, None)
+    U, R, C = _pool_packed_dims("glimpse_pool_bwd_packed_dfeat", feat, roff, G, N, S, idx)
+    if grp is not None:
+        _chk_group("glimpse_pool_bwd_packed_dfeat", N, U, order=order, grp_off=grp_off)
+    if tuple(dpooled.shape) != (N, G * C) or (dwts is not None and tuple(dwts.shape) != (N, G, S)):
+        raise _l.VqfError("glimpse_pool_bwd_packed_dfeat: dpooled must be (N, G*C), wts and dwts (N, G, S)")
+    dlogits = torch.empty((N * S, G), dtype=torch.float32, device=feat.device)
+    dfeat = torch.empty_like(feat)
+    _l.check(_lib().vqf_glimpse_pool_bwd_packed_dfeat(_ptr(dpooled), _ptr(dwts), _ptr(feat), _ptr(wts), _ptr(idx), _ptr(order),
+                                                      _ptr(grp_off), _ptr(roff), N, U, R, S, C, G, int(bool(unit_softmax)),
+                                                      _ptr(dlogits), _ptr(dfeat), _stream()), "vqf_glimpse_pool_bwd_packed_dfeat")
+    return dlogits, dfeat
+
+
+# the packed forms of the guided attention logits: xh / dxh (R, G*E) hold the real rows only (include/vqa_fusion.h "The packed forms
+# of the alternating image side").  The kernels clamp what roff and the index arrays hold; only type, shape and device are checked here.
+def guided_logits_packed_supported(N, U, R, S, E, G):
+    return bool(_lib().vqf_guided_logits_packed_supported(int(N), int(U), int(R), int(S), int(E), int(G)))
+
+
+def _guided_packed_operands(name, xh, gp, w, roff, N, S, grouped):
+    _chk2s(xh)
+    _chk(gp, w)
+    G, E = w.shape
+    if xh.dim() != 2 or xh.shape[0] < 1 or xh.shape[1] != G * E or (gp is not None and tuple(gp.shape) != (N, G * E)):
+        raise _l.VqfError(name + ": xh must be (R, G*E) with R >= 1, gp (N, G*E) or None, w (G, E)")
+    R = xh.shape[0]
+    U = roff.shape[0] - 1 if grouped and torch.is_tensor(roff) else N
+    if not torch.is_tensor(roff) or not roff.is_cuda or roff.dtype != torch.int32 or not roff.is_contiguous() or \
+            tuple(roff.shape) != (U + 1,):
+        raise _l.VqfError("%s: roff must be a contiguous (%d,) int32 GPU tensor of row offsets" % (name, U + 1))
+    if not guided_logits_packed_supported(N, U, R, S, E, G):
+        raise _l.VqfError(name + ": E %% 32 == 0, E <= 1024, 1 <= S <= 1024, G in {1, 2, 3}, N <= 65535, U <= 65535 and "
+                          "1 <= R < 2^29 are supported (got N=%d, U=%d, R=%d, S=%d, E=%d, G=%d)" % (N, U, R, S, E, G))
+    return G, E, U, R
+
+
+def guided_logits_fwd_packed(xh, gp, w, roff, N, S, idx=None):
+    """xh (R, G*E) packed rows (rows may be strided), gp (N, G*E) or None, w (G, E), roff (N + 1) int32 -- with idx (N) int32:
+    (U + 1) per image -> logits (N*S, G): guided_logits_fwd / _grouped on the padded copy, exact zeros behind each count."""
+    G, E, U, R = _guided_packed_operands("guided_logits_fwd_packed", xh, gp, w, roff, N, S, idx is not None)
+    if idx is not None:
+        _chk_group("guided_logits_fwd_packed", N, U, idx=idx)
+    out = torch.empty((N * S, G), dtype=torch.float32, device=xh.device)
+    _l.check(_lib().vqf_guided_logits_fwd_packed(_ptr(xh), xh.stride(0), _ptr(gp), _ptr(w), _ptr(idx), _ptr(roff), int(N), U, R, int(S),
+                                                 E, G, _ptr(out), _stream()), "vqf_guided_logits_fwd_packed")
+    return out
+
+
+def guided_logits_bwd_packed(dlogits, xh, gp, w, roff, N, S, grp=None, out=None):
+    """-> (dxh (R, G*E) packed (out: written there, rows may be strided), dgp (N, G*E), dw (G, E)).  grp None: sample n owns
+    roff[n] ..; grp = (idx, order, grp_off): dxh sums each image's questions in `order` (zero rows for an image without a question).
+    dgp and dw are summed in the order of guided_logits_bwd / _grouped on the padded copy; dlogits rows behind a count are not read."""
+    G, E, U, R = _guided_packed_operands("guided_logits_bwd_packed", xh, gp, w, roff, N, S, grp is not None)
+    order, grp_off = (grp[1], grp[2]) if grp is not None else (None, None)
+    if grp is not None:
+        _chk_group("guided_logits_bwd_packed", N, U, order=order, grp_off=grp_off)
+        if gp is None:
+            raise _l.VqfError("guided_logits_bwd_packed: the grouped form needs gp (N, G*E)")
+    _chk(dlogits)
+    _chk2s(out)
+    if tuple(dlogits.shape) != (N * S, G) or (out is not None and tuple(out.shape) != (R, G * E)):
+        raise _l.VqfError("guided_logits_bwd_packed: dlogits must be (N*S, G) and out (R, G*E)")
+    if out is None:
+        out = torch.empty((R, G * E), dtype=torch.float32, device=xh.device)
+    dgp = torch.empty((N, G * E), dtype=torch.float32, device=xh.device)
+    dw = torch.empty((G, E), dtype=torch.float32, device=xh.device)
+    ws = workspace(xh.device, _lib().vqf_guided_logits_bwd_packed_ws_bytes(int(N), U, int(S), E, G))
+    _l.check(_lib().vqf_guided_logits_bwd_packed(_ptr(dlogits), _ptr(xh), xh.stride(0), _ptr(gp), _ptr(w), _ptr(order), _ptr(grp_off),
+                                                 _ptr(roff), int(N), U, R, int(S), E, G, _ptr(out), out.stride(0), _ptr(dgp), _ptr(dw),
+                                                 _ptr(ws), ws.numel(), _stream()), "vqf_guided_logits_bwd_packed")
+    return out, dgp, dw
 
 
 def lstm_seq_supported(B, H):
