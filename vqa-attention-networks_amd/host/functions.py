@@ -184,6 +184,97 @@ class JoinRowsFn(torch.autograd.Function):
         return g[:ctx.n], g[ctx.n:], None
 
 
+# ---------------------------------------------------------------------------------------------
+# One dispatcher pair per kernel family that knows where the image rows are (grouping.RegionLayout: shared images, region
+# counts, packed rows).  Each picks the ops.* wrapper of the layout and is the only place that does; layout None is the plain
+# tensor and takes the calls it always took.  Image tensors behind a layout other than the plain one are fp32.
+# ---------------------------------------------------------------------------------------------
+def _fuse_fwd(P, q, layout, N, L, O, link, **kw):
+    """The MFB fusion over the regions (ops.mfb_fuse_fwd / _grouped / _packed; kw: keep, seed, p_drop, pbias) -> (Y, norm, inv, rb):
+    with a link Y is R without 1/norm, and rb holds the bf16 copy of R a bf16 P's kernel wrote beside it."""
+    if layout is not None and layout.packed:
+        return ops.mfb_fuse_fwd_packed(P, q, layout.roff, N, L, O, idx=layout.idx, normalise=link is None, **kw) + (None,)
+    if layout is not None and layout.grouped:
+        return ops.mfb_fuse_fwd_grouped(P, q, layout.idx, N, layout.U, L, O, normalise=link is None,
+                                        lens=(layout.lens_q, layout.lens_u) if layout.counted else None, **kw) + (None,)
+    rb = [] if (link is not None and P.dtype == torch.bfloat16) else None
+    Y, norm, inv, _ = ops.mfb_fuse_fwd(P, q, N, L, O, normalise=link is None, r_bf16=rb,
+                                       lens=None if layout is None else layout.lens_q, **kw)
+    return Y, norm, inv, rb
+
+
+def _fuse_bwd(dY, Y, norm, inv, P, q, layout, N, L, O, dp_bf16=False, **kw):
+    """-> (dP in P's layout -- summed per image where the images are shared --, dq, dbias); kw: keep, seed, p_drop, pbias, lin"""
+    if layout is not None and layout.packed:
+        return ops.mfb_fuse_bwd_packed(dY, Y, norm, inv, P, q, layout.roff, N, L, O, grp=layout.grp, want_dbias=True, **kw)
+    if layout is not None and layout.grouped:
+        return ops.mfb_fuse_bwd_grouped(dY, Y, norm, inv, P, q, *layout.grp, N, layout.U, L, O, want_dbias=True,
+                                        lens=(layout.lens_q, layout.lens_u) if layout.counted else None, **kw)
+    dP, dq, _, dbi = ops.mfb_fuse_bwd(dY, Y, norm, inv, P, q, N, L, O, want_dbias=True, dp_bf16=dp_bf16,
+                                      lens=None if layout is None else layout.lens_q, **kw)
+    return dP, dq, dbi
+
+
+def _unit_sums(feat, G, layout):
+    """The pooling under unit weights, per OWNER of the rows (the images, shared or not): feat (U, S, C), or (R, C) packed
+    -> (wts, sums (U, G*C)) over each owner's real regions."""
+    U, S = (feat.shape[0], feat.shape[1]) if layout is None else (layout.U, layout.L)
+    zeros = torch.zeros((U * S, G), dtype=torch.float32, device=feat.device)          # the logits: ignored under unit weights
+    if layout is not None and layout.packed:
+        return ops.glimpse_pool_fwd_packed(feat, zeros, layout.roff, U, S, True)
+    return ops.glimpse_pool_fwd(feat, zeros, True, lens=None if layout is None else layout.lens_u)
+
+
+def _pool_fwd(feat, logits, unit, layout):
+    """softmax over a sample's positions + glimpse sums (ops.glimpse_pool_fwd / _grouped / _packed) -> (wts (N, G, S), pooled (N, G*C)).
+    feat (N, S, C); with shared images (U, S, C); packed (R, C).  Shared images under unit weights: the region sums of each IMAGE
+    (the unit pooling on the image tensor), one row block per question; there are no weights to keep."""
+    if layout is None:
+        return ops.glimpse_pool_fwd(feat, logits, unit)
+    if layout.grouped and unit:
+        return None, ops.row_block_gather(_unit_sums(feat, logits.shape[1], layout)[1], layout.idx)
+    if layout.packed:
+        return ops.glimpse_pool_fwd_packed(feat, logits, layout.roff, layout.N, layout.L, unit, idx=layout.idx)
+    if layout.grouped:
+        return ops.glimpse_pool_fwd_grouped(feat, logits, layout.idx, lens=layout.lens_q)
+    return ops.glimpse_pool_fwd(feat, logits, unit, lens=layout.lens_q)
+
+
+def _pool_bwd(dpooled, feat, wts, unit, need_dfeat, layout, dwts=None):
+    """-> (dlogits (N*S, G), dfeat in feat's layout or None): with shared images dfeat sums each image's questions."""
+    if layout is None:
+        return ops.glimpse_pool_bwd(dpooled, feat, wts, unit, need_dfeat, dwts=dwts)
+    if layout.grouped and unit:       # d(pooled)/d(logits) == 0 under unit weights: the exact zeros the unit kernel writes
+        G = dpooled.shape[1] // feat.shape[-1]
+        return torch.zeros((layout.N * layout.L, G), dtype=torch.float32, device=dpooled.device), None
+    if layout.packed and need_dfeat:
+        return ops.glimpse_pool_bwd_packed_dfeat(dpooled, feat, wts, layout.roff, unit, grp=layout.grp, dwts=dwts)
+    if layout.packed:
+        return ops.glimpse_pool_bwd_packed(dpooled, feat, wts, layout.roff, unit, idx=layout.idx, dwts=dwts), None
+    if layout.grouped:
+        return ops.glimpse_pool_bwd_grouped(dpooled, feat, wts, *layout.grp, need_dfeat, dwts=dwts, lens=layout.lens_q)
+    return ops.glimpse_pool_bwd(dpooled, feat, wts, unit, need_dfeat, dwts=dwts, lens=layout.lens_q)
+
+
+def _guided_fwd(xh, gp, w, layout, N, S):
+    """The guided attention logits over the image rows (ops.guided_logits_fwd / _grouped / _packed): xh (N*S, G*E); with shared
+    images (U*S, G*E); packed (R, G*E) -> logits (N*S, G)."""
+    if layout.packed:
+        return ops.guided_logits_fwd_packed(xh, gp, w, layout.roff, N, S, idx=layout.idx)
+    if layout.grouped:
+        return ops.guided_logits_fwd_grouped(xh, gp, w, layout.idx, N, layout.U, S)
+    return ops.guided_logits_fwd(xh, gp, w, N, S)
+
+
+def _guided_bwd(dlogits, xh, gp, w, layout, N, S):
+    """-> (dxh in xh's layout -- summed per image where the images are shared --, dgp (N, G*E), dw (G, E))"""
+    if layout.packed:
+        return ops.guided_logits_bwd_packed(dlogits, xh, gp, w, layout.roff, N, S, grp=layout.grp)
+    if layout.grouped:
+        return ops.guided_logits_bwd_grouped(dlogits, xh, gp, w, layout.order, layout.grp_off, N, layout.U, S)
+    return ops.guided_logits_bwd(dlogits, xh, gp, w, N, S)
+
+
 class AttHeadFn(torch.autograd.Function):
     """Attention MLP + glimpse pooling.
 
@@ -195,65 +286,26 @@ class AttHeadFn(torch.autograd.Function):
         tensor its MLP reads, mfb.py:73-89): the backward then adds the MLP's input gradient onto the pooling's in the GEMM
         epilogue and returns ONE gradient (for feat; None for x) instead of leaving two for autograd to add.  Never inferred
         from pointers: an alias with a different autograd history must keep its own gradient.
-    grp: None, or (idx, order, grp_off) of grouping._group_index -- the image head of N questions over U shared images: feat is
-        (U, S, C) data (no gradient), x stays (N*S, Cin) per question; question n pools the rows of image idx[n]
-        (vqf_glimpse_pool_fwd_grouped / _bwd_grouped; under unit_softmax the per-image region sums, gathered).
-    lens: None, or the region counts of the image head (forward((img, img_length), ...); fp32 feat that is data): an int32 (N,) tensor,
-        with grp the pair (lens_q (N,), lens_u (U,)).  The softmax runs over the first lens[n] positions (unit_softmax: weight 1
-        there), the weights beyond are exact zeros and so are their dlogits, so the MLP's backward adds nothing for padded rows.
-    pack: None, or (roff, L) of the packed call form (forward(PackedRegions, ...); image head, fp32 feat that is data, no lens): feat
-        is (R, C), the real rows of every image, and roff the int32 row offsets -- (N + 1,), with grp (U + 1,) per image.  x, the
-        logits and the weights stay (N, L, .) padded; the pooling reads feat through roff (vqf_glimpse_pool_fwd_packed / _bwd_packed).
+    layout: None (the question head; the plain image tensor), or the grouping.RegionLayout of the image head -- fp32 feat that is
+        data (no gradient), never the MLP's own source.  Shared images: feat is (U, S, C), x stays (N*S, Cin) per question, and
+        question n pools the rows of image idx[n] (under unit_softmax the per-image region sums, gathered).  Region counts: the
+        softmax runs over the first lens_q[n] positions (unit_softmax: weight 1 there), the weights beyond are exact zeros and so
+        are their dlogits, so the MLP's backward adds nothing for padded rows.  Packed rows: feat is (R, C), the real rows of every
+        image, read through roff; x, the logits and the weights stay (N, L, .) padded.  (_pool_fwd / _pool_bwd pick the kernels.)
     returns pooled (N, 2C); the attention weights (N,2,S) are kept on ctx.
     """
 
     @staticmethod
-    def _pool_fwd(feat, logits, unit, grp, lens=None, pack=None):
-        if pack is not None:
-            roff, L = pack
-            if grp is not None and unit:     # the region sums of each IMAGE, one row block per question (as below)
-                U = roff.shape[0] - 1
-                zeros = torch.zeros((U * L, logits.shape[1]), dtype=torch.float32, device=feat.device)
-                return None, ops.row_block_gather(ops.glimpse_pool_fwd_packed(feat, zeros, roff, U, L, True)[1], grp[0])
-            return ops.glimpse_pool_fwd_packed(feat, logits, roff, logits.shape[0] // L, L, unit, idx=None if grp is None else grp[0])
-        if grp is None:
-            return ops.glimpse_pool_fwd(feat, logits, unit, lens=lens)
-        if unit:      # weights == 1: the region sums of each IMAGE (the existing unit pooling on (U, S, C)), one row block per question
-            U, S, _ = feat.shape
-            zeros = torch.zeros((U * S, logits.shape[1]), dtype=torch.float32, device=feat.device)
-            _, per_image = ops.glimpse_pool_fwd(feat, zeros, True, lens=None if lens is None else lens[1])
-            return None, ops.row_block_gather(per_image, grp[0])
-        return ops.glimpse_pool_fwd_grouped(feat, logits, grp[0], lens=None if lens is None else lens[0])
-
-    @staticmethod
-    def _pool_bwd(dpooled, feat, wts, unit, need_dfeat, grp, NS, G, lens=None, pack=None):
-        if pack is not None and not (grp is not None and unit):
-            return ops.glimpse_pool_bwd_packed(dpooled, feat, wts, pack[0], unit, idx=None if grp is None else grp[0]), None
-        if grp is None:
-            return ops.glimpse_pool_bwd(dpooled, feat, wts, unit, need_dfeat, lens=lens)
-        if need_dfeat:
-            raise ops._l.VqfError("AttHeadFn: with shared images (grp) the feature tensor is data and gets no gradient")
-        if unit:      # d(pooled)/d(logits) == 0 under unit weights: the exact zeros the unit kernel writes
-            return torch.zeros((NS, G), dtype=torch.float32, device=dpooled.device), None
-        return ops.glimpse_pool_bwd_grouped(dpooled, feat, wts, grp[0], grp[1], grp[2], False, lens=None if lens is None else lens[0])
-
-    @staticmethod
-    def forward(ctx, x, feat, w1, b1, wm, bm, w2, b2, unit_softmax, bf16=False, link=None, same_src=False, grp=None, lens=None,
-                pack=None):
+    def forward(ctx, x, feat, w1, b1, wm, bm, w2, b2, unit_softmax, bf16=False, link=None, same_src=False, layout=None):
         x = _c(x)
         feat = _c(feat)
         ctx.bf16 = bool(bf16)
         ctx.same_src = bool(same_src)
-        ctx.grp = grp
-        ctx.lens = lens
-        ctx.pack = pack
-        if pack is not None and (ctx.bf16 or ctx.same_src or feat.dtype != torch.float32 or feat.dim() != 2 or lens is not None
-                                 or ctx.needs_input_grad[1]):
-            raise ops._l.VqfError("AttHeadFn: packed rows (pack) are fp32 only, a 2-D feature tensor that is data, without lens")
-        if lens is not None and (ctx.bf16 or ctx.same_src or feat.dtype != torch.float32 or ctx.needs_input_grad[1]):
-            raise ops._l.VqfError("AttHeadFn: region counts (lens) are fp32 only, for a feature tensor that is data")
-        if grp is not None and (ctx.bf16 or ctx.same_src or feat.dtype != torch.float32):
-            raise ops._l.VqfError("AttHeadFn: shared images (grp) are fp32 only and never the MLP's own source")
+        ctx.layout = layout
+        if layout is not None and (ctx.bf16 or ctx.same_src or feat.dtype != torch.float32 or ctx.needs_input_grad[1]
+                                   or feat.dim() != (2 if layout.packed else 3)):
+            raise ops._l.VqfError("AttHeadFn: a region layout (shared images, region counts, packed rows) is fp32 only, for a feature "
+                                  "tensor that is data -- (R, C) when packed -- and never the MLP's own source")
         if ctx.same_src and (x.numel() != feat.numel() or x.shape[-1] != feat.shape[-1] or x.dtype != feat.dtype):
             raise ops._l.VqfError("AttHeadFn: same_src needs x = feat.view(N*S, C)")
         ctx.link = link if (link is not None and link.inv is not None) else None
@@ -272,7 +324,7 @@ class AttHeadFn(torch.autograd.Function):
             else:
                 hid1 = ops.gemm_rowscale(x, _w2d(w1), link.inv, link.L, bias=b1, relu=True)
             logits, lin = ops.att_logits_fwd_lin(hid1, _w2d(w2), b2, b1)
-            wts, pooled = AttHeadFn._pool_fwd(feat, logits, unit_softmax, grp, lens, pack)
+            wts, pooled = _pool_fwd(feat, logits, unit_softmax, layout)
             # (bf16 mode: slot 3 -- no "multilayer" conv with a NormLink -- carries the bf16 copy of w1 to the backward: one cast per step)
             ctx.save_for_backward(x, feat, w1, w1b if ctx.bf16 else None, w2, hid1, None, wts, lin)
             ctx.unit = bool(unit_softmax)
@@ -290,7 +342,7 @@ class AttHeadFn(torch.autograd.Function):
         hid2 = ops.gemm(hid1, _w2d(wm), bias=bm, relu=True) if wm is not None else None
         last = hid2 if hid2 is not None else hid1
         logits = ops.att_logits_fwd(last, _w2d(w2), b2)
-        wts, pooled = AttHeadFn._pool_fwd(feat, logits, unit_softmax, grp, lens, pack)
+        wts, pooled = _pool_fwd(feat, logits, unit_softmax, layout)
         ctx.save_for_backward(x, feat, w1, wm, w2, hid1, hid2, wts, w1b if ctx.bf16 else None)      # (last slot: the bf16 copy of w1)
         ctx.unit = bool(unit_softmax)
         return pooled
@@ -300,8 +352,7 @@ class AttHeadFn(torch.autograd.Function):
         x, feat, w1, wm, w2, hid1, hid2, wts, lin = ctx.saved_tensors
         dpooled = _c(dpooled)
         need_dfeat = ctx.needs_input_grad[1]
-        dlogits, dfeat = AttHeadFn._pool_bwd(dpooled, feat, wts, ctx.unit, need_dfeat, ctx.grp, hid1.shape[0], _w2d(w2).shape[0],
-                                             ctx.lens, ctx.pack)
+        dlogits, dfeat = _pool_bwd(dpooled, feat, wts, ctx.unit, need_dfeat, ctx.layout)
         if ctx.link is not None:
             link = ctx.link
             w1b = wm                                       # (slot 3, see forward)
@@ -314,10 +365,10 @@ class AttHeadFn(torch.autograd.Function):
                 d1b = d1s if obf else ops.cast_bf16(d1s)
                 dw1 = ops.gemm_bf16(d1b, x, ta=True, tb=True)[:, :cin].contiguous().view_as(w1)
                 dx = ops.gemm_bf16(d1b, w1b, tb=True, N=cin) if ctx.needs_input_grad[0] else None
-                return dx, dfeat, dw1, db1, None, None, dw2.view_as(w2), db2, None, None, None, None, None, None, None
+                return dx, dfeat, dw1, db1, None, None, dw2.view_as(w2), db2, None, None, None, None, None
             dw1 = ops.gemm(d1s, x, ta=True, tb=True).view_as(w1)                    # = dpre^T Y
             dx = ops.gemm(d1s, _w2d(w1), tb=True) if ctx.needs_input_grad[0] else None   # dYs = dY / norm
-            return dx, dfeat, dw1, db1, None, None, dw2.view_as(w2), db2, None, None, None, None, None, None, None
+            return dx, dfeat, dw1, db1, None, None, dw2.view_as(w2), db2, None, None, None, None, None
         last = hid2 if hid2 is not None else hid1
         dlast_pre, dw2, db2, dblast = ops.att_logits_bwd(dlogits, last, _w2d(w2), relu_mask=True)
         dwm = dbm = None
@@ -342,7 +393,7 @@ class AttHeadFn(torch.autograd.Function):
                 dx = None
             else:
                 dx = ops.gemm(d1_pre, _w2d(w1), tb=True) if ctx.needs_input_grad[0] else None
-        return dx, dfeat, dw1, db1, dwm, dbm, dw2.view_as(w2), db2, None, None, None, None, None, None, None
+        return dx, dfeat, dw1, db1, dwm, dbm, dw2.view_as(w2), db2, None, None, None, None, None
 
 
 def _arm_link(link, inv, L, xb=None):
@@ -364,62 +415,50 @@ def _take_lin(link):
     return lin
 
 
+def _fuse_node_fwd(ctx, P, pbias, q, keep, seed, p_drop, N, L, link, layout):
+    """The forward MfbFuseFn and ImgFuseFn share behind the projection P: the fusion, the link, what the backward needs on ctx"""
+    O = P.shape[1] // ops.POOL_K
+    Y, norm, inv, rb = _fuse_fwd(P, q, layout, N, L, O, link, keep=keep, seed=seed, p_drop=p_drop, pbias=pbias)
+    ctx.link = _arm_link(link, inv, L, rb)
+    ctx.layout, ctx.seed, ctx.p_drop, ctx.dims = layout, seed, p_drop, (N, L, O)
+    return Y, norm, inv
+
+
+def _fuse_node_bwd(ctx, dY, Y, norm, inv, P, q, keep, pbias, dp_bf16):
+    """-> (dP, dq, dbias): the shared backward of the fusion"""
+    N, L, O = ctx.dims
+    return _fuse_bwd(_c(dY), Y, norm, inv, P, q, ctx.layout, N, L, O, dp_bf16=dp_bf16, keep=keep, seed=ctx.seed, p_drop=ctx.p_drop,
+                     pbias=pbias, lin=_take_lin(ctx.link))
+
+
 class ImgFuseFn(torch.autograd.Function):
     """a5+a6: P = img W^T + b;  Y = L2norm_n(ssqrt(pool5(dropout(P * q[n])))).
 
     img (N,L,D) data (no gradient), wi (5000,D[,1,1]), bi (5000), q (N,5000)
     -> Y (N*L, 1000), row m = n*L + l   (the reference's fusion_normed is the
     (N,1000,L,1) permutation of the same values, mfb.py:103-106).
-    grp (None, or (idx, order, grp_off) of grouping._group_index; fp32 only): img is (U, L, D), the images N questions share.
-    The projection and its weight gradient run on U*L rows; the fusion reads P through idx and its backward sums dP per image.
-    lens (None, or the region counts: an int32 (N,) tensor, with grp the pair (lens_q (N,), lens_u (U,)); fp32 only): sample n has
-    lens[n] real regions.  The projection and its weight gradient still run over every row; the fusion reads no padded row of P
-    and hands back exact zero dP rows there, so finite padding cancels in the weight gradient.
-    pack (None, or (roff, L) of the packed call form; fp32 only, no lens): img is (1, R, D), the real rows of every image one after the
-    other, roff the int32 row offsets ((N + 1,), with grp (U + 1,) per image) and L the padded width of Y.  The projection and its
-    weight gradient run on the R real rows (P and dP are (R, 5000)); Y stays (N*L, 1000) with exact zero rows beyond each count.
+    layout (None, or the grouping.RegionLayout of img; fp32 only).  Shared images: img is (U, L, D); the projection and its weight
+    gradient run on U*L rows, the fusion reads P through idx and its backward sums dP per image.  Region counts: sample n has
+    lens_q[n] real regions; the projection and its weight gradient still run over every row, the fusion reads no padded row of P
+    and hands back exact zero dP rows there, so finite padding cancels in the weight gradient.  Packed rows: img is (1, R, D), the
+    real rows of every image one after the other; the projection and its weight gradient run on the R real rows (P and dP are
+    (R, 5000)); Y stays (N*L, 1000) with exact zero rows beyond each count.  (_fuse_fwd / _fuse_bwd pick the kernels.)
     """
 
     BF16_P = True      # bf16 mode: store P in bf16 when the large-tile GEMM applies (A/B switch)
 
     @staticmethod
-    def forward(ctx, img, wi, bi, q, keep, seed, p_drop, bf16=False, link=None, grp=None, lens=None, pack=None):
-        img = _c(img)
-        q = _c(q)
-        N, L, D = img.shape
+    def forward(ctx, img, wi, bi, q, keep, seed, p_drop, bf16=False, link=None, layout=None):
+        img, q = _c(img), _c(q)
+        D = img.shape[-1]
+        N, L = (img.shape[0], img.shape[1]) if layout is None else (layout.N, layout.L)
         wi2 = _w2d(wi)
-        O = wi2.shape[0] // ops.POOL_K
         ctx.bf16 = bool(bf16)
-        ctx.grp = grp
-        ctx.lens = lens
-        ctx.pack = pack
-        if pack is not None:
-            if ctx.bf16 or img.dtype != torch.float32 or lens is not None:
-                raise ops._l.VqfError("ImgFuseFn: packed rows (pack) are fp32 only and carry their own counts (no lens)")
-            N, L = q.shape[0], pack[1]
-            P = ops.gemm(img.view(-1, D), wi2, bias=bi)                        # the real rows only
-            Y, norm, inv = ops.mfb_fuse_fwd_packed(P, q, pack[0], N, L, O, idx=None if grp is None else grp[0], keep=keep, seed=seed,
-                                                   p_drop=p_drop, normalise=link is None)
-            ctx.link = _arm_link(link, inv, L, None)
-            ctx.save_for_backward(img, wi, q, P, Y, norm, inv, keep)
-            ctx.seed, ctx.p_drop, ctx.dims = seed, p_drop, (N, L, D, O)
-            return Y
-        if lens is not None and (ctx.bf16 or img.dtype != torch.float32):
-            raise ops._l.VqfError("ImgFuseFn: region counts (lens) are fp32 only")
-        if grp is not None:
-            if ctx.bf16 or img.dtype != torch.float32:
-                raise ops._l.VqfError("ImgFuseFn: shared images (grp) are fp32 only")
-            U, N = N, q.shape[0]
-            P = ops.gemm(img.view(U * L, D), wi2, bias=bi)                     # once per image
-            Y, norm, inv = ops.mfb_fuse_fwd_grouped(P, q, grp[0], N, U, L, O, keep=keep, seed=seed, p_drop=p_drop,
-                                                    normalise=link is None, lens=lens)
-            ctx.link = _arm_link(link, inv, L, None)
-            ctx.save_for_backward(img, wi, q, P, Y, norm, inv, keep)
-            ctx.seed, ctx.p_drop, ctx.dims = seed, p_drop, (N, L, D, O)
-            return Y
+        if layout is not None and (ctx.bf16 or img.dtype != torch.float32):
+            raise ops._l.VqfError("ImgFuseFn: a region layout (shared images, region counts, packed rows) is fp32 only")
         if ctx.bf16:
             # bf16 storage of the image tensor and the projection weight, fp32 accumulation
-            img = img.view(N * L, D) if img.dtype == torch.bfloat16 else ops.cast_bf16(img.view(N * L, D))
+            img = img.view(-1, D) if img.dtype == torch.bfloat16 else ops.cast_bf16(img.view(-1, D))
             wb = ops.cast_bf16(wi2)
             # the projection is STORED in bf16 when the large-tile kernel applies (half the bytes of the largest
             # tensor of the step in the GEMM epilogue, the fusion forward and the fusion backward)
@@ -427,39 +466,20 @@ class ImgFuseFn(torch.autograd.Function):
             if P is None:
                 P = ops.gemm_bf16(img, wb, bias=bi)
         else:
-            P = ops.gemm(img.view(N * L, D), wi2, bias=bi)
-        rb = [] if (link is not None and P.dtype == torch.bfloat16) else None
-        Y, norm, inv, _ = ops.mfb_fuse_fwd(P, q, N, L, O, keep=keep, seed=seed, p_drop=p_drop, normalise=link is None, r_bf16=rb,
-                                           lens=lens)
-        ctx.link = _arm_link(link, inv, L, rb)
+            P = ops.gemm(img.view(-1, D), wi2, bias=bi)        # once per image where they are shared; packed: the real rows only
+        Y, norm, inv = _fuse_node_fwd(ctx, P, None, q, keep, seed, p_drop, N, L, link, layout)
         ctx.save_for_backward(img, wi, q, P, Y, norm, inv, keep)
-        ctx.seed, ctx.p_drop, ctx.dims = seed, p_drop, (N, L, D, O)
         return Y
 
     @staticmethod
     def backward(ctx, dY):
         img, wi, q, P, Y, norm, inv, keep = ctx.saved_tensors
-        N, L, D, O = ctx.dims
-        if ctx.pack is not None:
-            dP, dq, dbi = ops.mfb_fuse_bwd_packed(_c(dY), Y, norm, inv, P, q, ctx.pack[0], N, L, O, grp=ctx.grp, keep=keep,
-                                                  seed=ctx.seed, p_drop=ctx.p_drop, want_dbias=True, lin=_take_lin(ctx.link))
-            dwi = ops.gemm(dP, img.view(-1, D), ta=True, tb=True).view_as(wi)      # wgrad, K = R
-            return None, dwi, dbi, dq, None, None, None, None, None, None, None, None
-        if ctx.grp is not None:
-            U = img.shape[0]
-            dP, dq, dbi = ops.mfb_fuse_bwd_grouped(_c(dY), Y, norm, inv, P, q, ctx.grp[0], ctx.grp[1], ctx.grp[2], N, U, L, O,
-                                                   keep=keep, seed=ctx.seed, p_drop=ctx.p_drop, want_dbias=True,
-                                                   lin=_take_lin(ctx.link), lens=ctx.lens)
-            dwi = ops.gemm(dP, img.view(U * L, D), ta=True, tb=True).view_as(wi)   # wgrad, K = U*L
-            return None, dwi, dbi, dq, None, None, None, None, None, None, None, None
-        dP, dq, _, dbi = ops.mfb_fuse_bwd(_c(dY), Y, norm, inv, P, q, N, L, O, keep=keep, seed=ctx.seed,
-                                          p_drop=ctx.p_drop, want_dbias=True, dp_bf16=ctx.bf16, lin=_take_lin(ctx.link),
-                                          lens=ctx.lens)
+        dP, dq, dbi = _fuse_node_bwd(ctx, dY, Y, norm, inv, P, q, keep, None, ctx.bf16)
         if ctx.bf16:                  # dP already is the bf16 A operand of the weight-gradient GEMM
             dwi = ops.gemm_bf16(dP, img, ta=True, tb=True).view_as(wi)
         else:
-            dwi = ops.gemm(dP, img.view(N * L, D), ta=True, tb=True).view_as(wi)   # wgrad, K = N*L
-        return None, dwi, dbi, dq, None, None, None, None, None, None, None, None
+            dwi = ops.gemm(dP, img.view(-1, img.shape[-1]), ta=True, tb=True).view_as(wi)   # wgrad, K = the rows of P
+        return None, dwi, dbi, dq, None, None, None, None, None, None
 
 
 class ImgProjFn(torch.autograd.Function):
@@ -571,66 +591,26 @@ class ImgProjLateFn(torch.autograd.Function):
 class MfbFuseFn(torch.autograd.Function):
     """a6: Y = L2norm_n(ssqrt(pool5(dropout((P0 + bias) * q[n])))) for the L regions of each sample.
     P0 fp32, or bf16 (then dP is handed back in bf16 too: the bf16 mode's projection storage).
-    grp (None, or (idx, order, grp_off) of grouping._group_index; fp32 only): P0 is (U*L, 5000), the projection of the U images
-    the N questions share; dP comes back (U*L, 5000), summed over each image's questions, so the projection node behind it
-    (ImgProjFn / ImgProjDeferFn / ImgProjLateFn) runs its weight gradient with K = U*L.
-    lens: the region counts, as in ImgFuseFn (fp32 P0 only): no padded row of P0 is read, the padded rows of dP are exact zeros.
-    pack: (roff, L) of the packed call form, as in ImgFuseFn (fp32 P0 only, no lens): P0 and dP are (R, 5000), the real rows."""
+    layout (None, or the grouping.RegionLayout of the projected image tensor; fp32 P0 only), as in ImgFuseFn.  Shared images: P0 is
+    (U*L, 5000) and dP comes back (U*L, 5000), summed over each image's questions, so the projection node behind it (ImgProjFn /
+    ImgProjDeferFn / ImgProjLateFn) runs its weight gradient with K = U*L.  Region counts: no padded row of P0 is read, the padded
+    rows of dP are exact zeros.  Packed rows: P0 and dP are (R, 5000), the real rows."""
 
     @staticmethod
-    def forward(ctx, P0, bi, q, keep, seed, p_drop, N, L, link=None, grp=None, lens=None, pack=None):
+    def forward(ctx, P0, bi, q, keep, seed, p_drop, N, L, link=None, layout=None):
         P0, q = _c(P0), _c(q)
-        O = P0.shape[1] // ops.POOL_K
-        ctx.grp = grp
-        ctx.lens = lens
-        ctx.pack = pack
-        if pack is not None:
-            if P0.dtype != torch.float32 or lens is not None:
-                raise ops._l.VqfError("MfbFuseFn: packed rows (pack) are fp32 only and carry their own counts (no lens), got a %s "
-                                      "projection" % P0.dtype)
-            Y, norm, inv = ops.mfb_fuse_fwd_packed(P0, q, pack[0], N, L, O, idx=None if grp is None else grp[0], keep=keep, seed=seed,
-                                                   p_drop=p_drop, pbias=bi, normalise=link is None)
-            ctx.link = _arm_link(link, inv, L, None)
-            ctx.save_for_backward(P0, bi, q, Y, norm, inv, keep)
-            ctx.seed, ctx.p_drop, ctx.dims = seed, p_drop, (N, L, O)
-            return Y
-        if lens is not None and P0.dtype != torch.float32:
-            raise ops._l.VqfError("MfbFuseFn: region counts (lens) are fp32 only, got a %s projection" % P0.dtype)
-        if grp is not None:
-            if P0.dtype != torch.float32:
-                raise ops._l.VqfError("MfbFuseFn: shared images (grp) are fp32 only, got a %s projection" % P0.dtype)
-            U = P0.shape[0] // L
-            Y, norm, inv = ops.mfb_fuse_fwd_grouped(P0, q, grp[0], N, U, L, O, keep=keep, seed=seed, p_drop=p_drop, pbias=bi,
-                                                    normalise=link is None, lens=lens)
-            ctx.link = _arm_link(link, inv, L, None)
-            ctx.save_for_backward(P0, bi, q, Y, norm, inv, keep)
-            ctx.seed, ctx.p_drop, ctx.dims = seed, p_drop, (N, L, O)
-            return Y
-        rb = [] if (link is not None and P0.dtype == torch.bfloat16) else None
-        Y, norm, inv, _ = ops.mfb_fuse_fwd(P0, q, N, L, O, keep=keep, seed=seed, p_drop=p_drop, pbias=bi,
-                                           normalise=link is None, r_bf16=rb, lens=lens)
-        ctx.link = _arm_link(link, inv, L, rb)
+        if layout is not None and P0.dtype != torch.float32:
+            raise ops._l.VqfError("MfbFuseFn: a region layout (shared images, region counts, packed rows) is fp32 only, got a %s "
+                                  "projection" % P0.dtype)
+        Y, norm, inv = _fuse_node_fwd(ctx, P0, bi, q, keep, seed, p_drop, N, L, link, layout)
         ctx.save_for_backward(P0, bi, q, Y, norm, inv, keep)
-        ctx.seed, ctx.p_drop, ctx.dims = seed, p_drop, (N, L, O)
         return Y
 
     @staticmethod
     def backward(ctx, dY):
         P0, bi, q, Y, norm, inv, keep = ctx.saved_tensors
-        N, L, O = ctx.dims
-        if ctx.pack is not None:
-            dP, dq, dbi = ops.mfb_fuse_bwd_packed(_c(dY), Y, norm, inv, P0, q, ctx.pack[0], N, L, O, grp=ctx.grp, keep=keep,
-                                                  seed=ctx.seed, p_drop=ctx.p_drop, want_dbias=True, pbias=bi, lin=_take_lin(ctx.link))
-            return dP, dbi, dq, None, None, None, None, None, None, None, None, None
-        if ctx.grp is not None:
-            dP, dq, dbi = ops.mfb_fuse_bwd_grouped(_c(dY), Y, norm, inv, P0, q, ctx.grp[0], ctx.grp[1], ctx.grp[2], N,
-                                                   P0.shape[0] // L, L, O, keep=keep, seed=ctx.seed, p_drop=ctx.p_drop,
-                                                   want_dbias=True, pbias=bi, lin=_take_lin(ctx.link), lens=ctx.lens)
-            return dP, dbi, dq, None, None, None, None, None, None, None, None, None
-        dP, dq, _, dbi = ops.mfb_fuse_bwd(_c(dY), Y, norm, inv, P0, q, N, L, O, keep=keep, seed=ctx.seed,
-                                          p_drop=ctx.p_drop, want_dbias=True, pbias=bi, lin=_take_lin(ctx.link),
-                                          dp_bf16=P0.dtype == torch.bfloat16, lens=ctx.lens)
-        return dP, dbi, dq, None, None, None, None, None, None, None, None, None
+        dP, dq, dbi = _fuse_node_bwd(ctx, dY, Y, norm, inv, P0, q, keep, bi, P0.dtype == torch.bfloat16)
+        return dP, dbi, dq, None, None, None, None, None, None, None
 
 
 class _Fork:
@@ -1320,33 +1300,26 @@ class LstmBatchFn(torch.autograd.Function):
 class UnitPoolFn(torch.autograd.Function):
     """pooled[n, g*C + c] = sum_s feat[n, s, c] for g < G: the glimpse sums under mfb.py:84,118's
     singleton-axis softmax (weights == 1), without the attention MLP in front (MFB's `pruned` mode).
-    lens (None, or (N,) int32; fp32 feat): the sum runs over s < lens[n] (weight 0 beyond).
-    pack (None, or (roff, L) of the packed call form): feat is (R, C) data, the real rows of every image; one sum per owner of roff."""
+    layout (None, or the grouping.RegionLayout of an image tensor; fp32 feat): one sum per OWNER of the rows -- per image, (U, G*C),
+    where the images are shared -- over its real regions (s < lens_u[u]; packed: feat is (R, C) data, the rows roff gives it)."""
 
     @staticmethod
-    def forward(ctx, feat, G, lens=None, pack=None):
+    def forward(ctx, feat, G, layout=None):
         feat = _c(feat)
-        if pack is not None:
-            if lens is not None or feat.dim() != 2 or ctx.needs_input_grad[0]:
-                raise ops._l.VqfError("UnitPoolFn: packed rows (pack) are a 2-D feature tensor that is data, without lens")
-            roff, L = pack
-            owners = roff.shape[0] - 1
-            logits = torch.zeros((owners * L, G), dtype=torch.float32, device=feat.device)     # ignored under unit weights
-            return ops.glimpse_pool_fwd_packed(feat, logits, roff, owners, L, True)[1]
-        N, S, C = feat.shape
-        logits = torch.zeros((N * S, G), dtype=torch.float32, device=feat.device)     # ignored under unit weights
-        wts, pooled = ops.glimpse_pool_fwd(feat, logits, True, lens=lens)
+        if layout is not None and layout.packed and (feat.dim() != 2 or ctx.needs_input_grad[0]):
+            raise ops._l.VqfError("UnitPoolFn: packed rows are a 2-D feature tensor that is data")
+        wts, pooled = _unit_sums(feat, G, layout)
         ctx.save_for_backward(feat, wts)
-        ctx.lens = lens
+        ctx.layout = layout
         return pooled
 
     @staticmethod
     def backward(ctx, dpooled):
-        feat, wts = ctx.saved_tensors
         if not ctx.needs_input_grad[0]:
-            return None, None, None, None
-        _, dfeat = ops.glimpse_pool_bwd(_c(dpooled), feat, wts, True, True, lens=ctx.lens)
-        return dfeat, None, None, None
+            return None, None, None
+        feat, wts = ctx.saved_tensors
+        _, dfeat = ops.glimpse_pool_bwd(_c(dpooled), feat, wts, True, True, lens=None if ctx.layout is None else ctx.layout.lens_u)
+        return dfeat, None, None
 
 
 class DeadParamsFn(torch.autograd.Function):

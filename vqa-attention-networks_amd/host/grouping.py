@@ -6,6 +6,8 @@ img_index (N,) says which of the U images of the batch question n looks at.  It 
 it and derives, on the device, what the grouped kernels of include/vqa_fusion.h take (idx / order / grp_off), and every kernel
 clamps what it reads from those arrays again.
 """
+import collections
+
 import torch
 
 from .lib import VqfError
@@ -59,6 +61,47 @@ def _region_lens(img_length, L, idx=None):
     if idx is None:
         return lens
     return lens[idx.to(torch.int64)].contiguous(), lens
+
+
+class RegionLayout(collections.namedtuple("_RegionLayout", "N U L R idx order grp_off lens_u lens_q roff offsets grouped counted packed plain grp")):
+    """Where the image rows of a batch are: what forward(..., img_index), forward((img, img_length), ...) and
+    forward(PackedRegions, ...) hand to the nodes, in one immutable object.  N questions, U images (U = N without img_index), L the
+    padded width, R the rows of the image tensor (U * L unless packed).  idx / order / grp_off: _group_index's output, or None
+    without img_index.  lens_u (U,) / lens_q (N,) = lens_u[idx]: _region_lens' counts per image and per question (the same tensor
+    without img_index), or None without img_length.  roff (U + 1,) int32: the row offsets of the packed form (which carries its
+    counts there: no lens), or None; offsets: the tensor roff was converted from, kept for padded().
+    Views, so that no node tests two fields to find its form: grouped (questions share images), counted (region counts beside a
+    padded tensor), packed (the image tensor holds the real rows only), plain (none of the three), grp = (idx, order, grp_off) or
+    None.  Every tensor is made on the device; nothing here reads a tensor's values on the host."""
+    __slots__ = ()
+
+    def __new__(cls, N, U, L, img_index=None, img_length=None, offsets=None, R=None):
+        idx, order, grp_off = (None, None, None) if img_index is None else _group_index(img_index, U)
+        lens_q = lens_u = None
+        if img_length is not None:
+            lens = _region_lens(img_length, L, idx)
+            lens_q, lens_u = (lens, lens) if idx is None else lens
+        roff = None if offsets is None else offsets.to(torch.int32).contiguous()
+        return cls._of(N, U, L, U * L if R is None else R, idx, order, grp_off, lens_u, lens_q, roff, offsets)
+
+    @classmethod
+    def _of(cls, N, U, L, R, idx, order, grp_off, lens_u, lens_q, roff, offsets):
+        grouped, counted, packed = idx is not None, lens_u is not None, roff is not None
+        return tuple.__new__(cls, (N, U, L, R, idx, order, grp_off, lens_u, lens_q, roff, offsets, grouped, counted, packed,
+                                   not (grouped or counted or packed), (idx, order, grp_off) if grouped else None))
+
+    def padded(self):
+        """The same batch after its packed rows were laid out padded, (U*L, .): roff is dropped and the counts are those of the
+        offsets, through img_length's clamp.  Any other layout is returned as it is."""
+        if not self.packed:
+            return self
+        lens = _region_lens(self.offsets[1:] - self.offsets[:-1], self.L, self.idx)
+        lens_q, lens_u = lens if self.grouped else (lens, lens)
+        return self._of(self.N, self.U, self.L, self.U * self.L, self.idx, self.order, self.grp_off, lens_u, lens_q, None, None)
+
+    def per_question(self):
+        """The layout behind a row-block gather of the padded rows (hie_ladder.RowBlockGatherFn): one image per question."""
+        return self._of(self.N, self.N, self.L, self.N * self.L, None, None, None, self.lens_q, self.lens_q, None, None)
 
 
 class PackedRegions:

@@ -93,7 +93,8 @@ tanh / dropout pass that follows anyway is where the layout changes: vqf_tanh_dr
 (U*L, E) with exact zero rows behind each count, its backward (vqf_tanh_dropout_pack_bwd) returns dZ (R, E) without reading a padded
 row -- as many launches as the pair call, no extra pass over an (N*L, .) tensor.  Dropout indices stay those of the padded tensor
 (set_keep_masks(img=...) stays (U*L, E)); the counts are offsets[1:] - offsets[:-1] through the same clamp as img_length, and from V
-on the code is that of the region-count call (rlens, the *_regions / *_len kernels, RowBlockGatherFn, grp).  offsets is never read
+on the code is that of the region-count call (RegionLayout.padded(): the same layout with counts in place of the offsets; the
+*_regions / *_len kernels, RowBlockGatherFn and the grouping).  offsets is never read
 on the host; the kernels clamp what it holds (include/vqa_fusion.h).  The Vh / VX products, the affinity and the rank-T passes stay
 padded (N*L rows), as in the region-count call; fp32 only.
 
@@ -107,6 +108,10 @@ the host.  Against packed_coatt=False only the summation order of dwimg (and of 
 to rounding, not bit for bit.  What stays padded or untouched: the question side (QX and everything over (N*T, .)), parallel mode
 (its Vh product, affinity and rank-T passes: packed_coatt=True raises ValueError there), bf16, and the HieCoAtten class.  With a
 plain tensor or the pair the keyword changes nothing: the same code path, bit for bit.
+
+Where the image rows are -- the index, the counts, the offsets of the four paragraphs above -- travels from forward() to the nodes
+as ONE grouping.RegionLayout, made by mfb.region_layout with every refusal of the call form; padded() and per_question() follow V
+through the unpacking pass and the row-block gather, and functions._guided_fwd / _pool_fwd (and their backwards) pick step 2's kernels.
 
 Stages (every product and every pass over an (N*L, .) or (N*T, .) tensor runs in libvqa_fusion.so):
   * img_emb / word embedding: LinearFn + TanhDropFn, EmbedTanhFn + DropoutFn;
@@ -124,12 +129,11 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .functions import (_c, _hie_hv_ti, _hie_dc, _hie_bwd_bgemm, EmbedTanhFn, LinearFn, DropoutFn, TanhDropFn, TanhDropUnpackFn, TanhDropPackedFn,
-                        DropoutBTFn,
-                        LstmBatchFn)
-from .grouping import _group_index, _region_lens, check_img_length, check_packed_regions, PackedRegions    # (_group_index: importable from here as before)
+from .functions import (_c, _hie_hv_ti, _hie_dc, _hie_bwd_bgemm, _guided_fwd, _guided_bwd, _pool_fwd, _pool_bwd, EmbedTanhFn, LinearFn,
+                        DropoutFn, TanhDropFn, TanhDropUnpackFn, TanhDropPackedFn, DropoutBTFn, LstmBatchFn)
+from .grouping import _group_index, PackedRegions    # (importable from here as before)
 from .lib import VqfError
-from .mfb import _DropSeeds, split_region_features
+from .mfb import _DropSeeds, region_layout
 
 _NODROP = (None, 0, 0.0)
 
@@ -199,7 +203,8 @@ class LadderCoattFn(torch.autograd.Function):
     lens ((N,) int32 or None; q0 / q1 / q2 come with zero rows at t >= lens[n]): the question-side poolings take the softmax
     over the real words, and the dC stage writes zero rows for the padded ones on every route -- with those, every other
     stage's padded rows are zero by its own arithmetic (bias-free products of zero rows, tanh(0) = 0).
-    rlens ((N,) int32 or None: the real regions of each sample's L; V's padded rows hold finite values that must not matter):
+    layout (the grouping.RegionLayout of V: one image per question here, so only its counts matter; rlens below = layout.lens_q,
+    (N,) int32 or None: the real regions of each sample's L; V's padded rows hold finite values that must not matter):
     the *_regions forms of the affinity and of the streaming passes -- zero columns of C and dC, zero rows of Hv and dVh behind
     the count, nothing read there -- and the image-side pooling over the real regions (vqf_glimpse_pool_fwd_len / _bwd_len);
     on the batched-GEMM route vqf_zero_cols_len on C and dC, which makes every other padded term a product with an exact zero."""
@@ -207,8 +212,9 @@ class LadderCoattFn(torch.autograd.Function):
     STREAM = True      # the T-row stages as streaming passes where supported; False: batched GEMMs + element-wise (A/B)
 
     @staticmethod
-    def forward(ctx, V, q0, q1, q2, N, L, T, lens, rlens, *w):
+    def forward(ctx, V, q0, q1, q2, N, L, T, lens, layout, *w):
         E = V.shape[1]
+        rlens = layout.lens_q
         lk = {} if lens is None else {"lens": lens}
         rk = {} if rlens is None else {"rlens": rlens}
         M, MT = N * L, N * T
@@ -340,24 +346,22 @@ class LadderAltCoattFn(torch.autograd.Function):
     into the (N*T, 6E) / (N*L, 3E) operands of the weight- and input-gradient products; the bias gradients are column sums of
     the (N, .) dgp.  lens ((N,) int32 or None; q0 / q1 / q2 come with zero rows at t >= lens[n]): the question-side poolings
     take the softmax over the real words and give zero dlogits for the padded ones.
-    rlens (None, or the (N,) int32 region counts of the questions' images -- lens_q = lens_u[idx] with grp): step 2's pooling runs
-    over the real regions (vqf_glimpse_pool_fwd_len / _bwd_len, the _grouped_len forms with grp); its zero dlogits rows give zero
-    dVX rows out of the guided-logits backward.  Host wiring only: no kernel of this mode knows the counts but the pooling.
-    grp (None, or (idx, order, grp_off) of _group_index): V is (U*L, E), shared -- VX stays (U*L, 3E), step 2 runs on the grouped
-    entry points (question n reads image idx[n]'s rows; dV and dVX sum each image's questions in `order`).
-    roff (None, or the (U + 1,) int32 row offsets of a PackedRegions: HieCoAttenLadder(packed_coatt=True)): the image side on the
-    PACKED rows -- V is (R, E), VX = V [img_x]^T + b and dVX are (R, 3E), dV is (R, E); step 2 runs on vqf_guided_logits_fwd_packed /
-    _bwd_packed and vqf_glimpse_pool_fwd_packed / _bwd_packed_dfeat (with grp their grouped forms), which take the counts from roff
-    (rlens is not used); av stays (N, 3, L) with exact zeros behind each count.  The dV += dVX wimg and dwimg products run on R rows."""
+    layout (the grouping.RegionLayout of V; step 2 runs on functions._guided_fwd / _pool_fwd and their backwards, which pick the
+    kernels).  Region counts: step 2's pooling runs over the real regions (the question's count lens_q = lens_u[idx] where the images
+    are shared); its zero dlogits rows give zero dVX rows out of the guided-logits backward.  Host wiring only: no kernel of this
+    mode knows the counts but the pooling.  Shared images: V is (U*L, E) -- VX stays (U*L, 3E), step 2 runs on the grouped entry
+    points (question n reads image idx[n]'s rows; dV and dVX sum each image's questions in `order`).  Packed rows
+    (HieCoAttenLadder(packed_coatt=True)): the image side on the PACKED rows -- V is (R, E), VX = V [img_x]^T + b and dVX are (R, 3E),
+    dV is (R, E); step 2 runs on the packed entry points (their grouped forms where the images are shared), which take the counts
+    from roff; av stays (N, 3, L) with exact zeros behind each count.  The dV += dVX wimg and dwimg products run on R rows."""
 
     PER_LEVEL = 11
 
     @staticmethod
-    def forward(ctx, V, q0, q1, q2, N, L, T, lens, grp, rlens, roff, *w):
+    def forward(ctx, V, q0, q1, q2, N, L, T, lens, layout, *w):
         E = V.shape[1]
         lk = {} if lens is None else {"lens": lens}
-        rk = {} if rlens is None else {"lens": rlens}                               # the image-side pooling's counts
-        U = V.shape[0] // L if roff is None else roff.shape[0] - 1
+        Vf = V if layout.packed else V.view(layout.U, L, E)                         # what step 2's pooling reads
         MT = N * T
         dev = V.device
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
@@ -369,10 +373,10 @@ class LadderAltCoattFn(torch.autograd.Function):
         whimg = torch.cat(img_h, 0).contiguous()                                    # (3, E)
         wq2 = [torch.cat([sum_x[g], que_x[g]], 0).contiguous() for g in range(3)]   # (2E, E) each
         bq2 = [torch.cat([sum_b[g], que_b[g]], 0).contiguous() for g in range(3)]
-        if roff is None:
-            VX = ops.gemm_rows(V, wimg, L, bias=bimg)                               # (U*L, 3E) = [img_0 | img_1 | img_2]
-        else:
+        if layout.packed:
             VX = ops.gemm(V, wimg, bias=bimg)                                       # (R, 3E): the real rows only
+        else:
+            VX = ops.gemm_rows(V, wimg, L, bias=bimg)                               # (U*L, 3E) = [img_0 | img_1 | img_2]
         QX = new(MT, 6 * E)                                                         # [sum_0 | que_0 | sum_1 | que_1 | sum_2 | que_2]
         for g in range(3):
             ops.gemm(Q[g], wq2[g], bias=bq2[g], out=QX[:, 2 * g * E:(2 * g + 2) * E])
@@ -387,15 +391,7 @@ class LadderAltCoattFn(torch.autograd.Function):
         gpv = new(N, 3 * E)
         for g in range(3):
             ops.gemm(s[g], img_g[g], out=gpv[:, g * E:(g + 1) * E])
-        if roff is not None:                                                        # the counts ride in roff
-            idx = None if grp is None else grp[0]
-            av, vcat = ops.glimpse_pool_fwd_packed(V, ops.guided_logits_fwd_packed(VX, gpv, whimg, roff, N, L, idx=idx), roff, N, L,
-                                                   False, idx=idx)
-        elif grp is None:
-            av, vcat = ops.glimpse_pool_fwd(V.view(N, L, E), ops.guided_logits_fwd(VX, gpv, whimg, N, L), False, **rk)   # (N, 3, L), (N, 3E)
-        else:
-            av, vcat = ops.glimpse_pool_fwd_grouped(V.view(U, L, E), ops.guided_logits_fwd_grouped(VX, gpv, whimg, grp[0], N, U, L),
-                                                    grp[0], **rk)
+        av, vcat = _pool_fwd(Vf, _guided_fwd(VX, gpv, whimg, layout, N, L), False, layout)               # (N, 3, L), (N, 3E)
         # step 3: the question under the attended image
         gpq = new(3, N, E)
         aq, qo = [], []
@@ -406,8 +402,8 @@ class LadderAltCoattFn(torch.autograd.Function):
             aq.append(a_g)
             qo.append(q_g)
         ctx.save_for_backward(V, q0, q1, q2, wimg, whimg, VX, QX, gpv, gpq, vcat, av, *wq2, *sum_h, *img_g, *que_g, *que_h, *s, *asum,
-                              *aq, *(grp or ()))
-        ctx.dims, ctx.lens, ctx.rlens, ctx.roff = (N, L, T, E), lens, rlens, roff
+                              *aq)
+        ctx.dims, ctx.lens, ctx.layout = (N, L, T, E), lens, layout
         ctx.set_materialize_grads(False)
         return (vcat, qo[0], qo[1], qo[2], av, aq[0], aq[1], aq[2])
 
@@ -416,10 +412,9 @@ class LadderAltCoattFn(torch.autograd.Function):
         t = ctx.saved_tensors
         V, q0, q1, q2, wimg, whimg, VX, QX, gpv, gpq, vcat, av = t[:12]
         wq2, sum_h, img_g, que_g, que_h, s, asum, aq = (t[12 + 3 * i:15 + 3 * i] for i in range(8))
-        grp = t[36:39]                                                              # (idx, order, grp_off), or empty
         N, L, T, E = ctx.dims
-        roff = ctx.roff
-        U = V.shape[0] // L if roff is None else roff.shape[0] - 1
+        layout = ctx.layout
+        Vf = V if layout.packed else V.view(layout.U, L, E)
         MT = N * T
         dev = V.device
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
@@ -427,8 +422,7 @@ class LadderAltCoattFn(torch.autograd.Function):
         Q, dq, daq = (q0, q1, q2), (dq0, dq1, dq2), (daq0, daq1, daq2)
         lens = ctx.lens
         lk = {} if lens is None else {"lens": lens}
-        rk = {} if ctx.rlens is None else {"lens": ctx.rlens}
-        dQX = new(MT, 6 * E)                                                        # [dsum_0 | dque_0 | ...]
+        dQX = new(MT, 6 * E)                                                       # [dsum_0 | dque_0 | ...]
         dvc = dvcat.clone(memory_format=torch.contiguous_format) if dvcat is not None else zeros(N, 3 * E)               # dv_i: the answer MLP's plus step 3's
         dQ, g3 = [], []
         # step 3: q_i = aq_i^T Q_i, aq_i = softmax(que_h_i tanh(que_i + v_i que_g_i^T))
@@ -443,16 +437,9 @@ class LadderAltCoattFn(torch.autograd.Function):
             g3.append((ops.colsum(dgp), ops.gemm(dgp, vcat[:, blk], ta=True, tb=True), dwh))   # que_x.bias, que_g, que_h
             dQ.append(dQg.view(MT, E))
         # step 2: one G = 3 pooling backward over V, one G = 3 guided-logits backward over VX
-        dwts = None if dav is None else _c(dav)
-        if roff is not None:        # dV (R, E) and dVX (R, 3E): the real rows only
-            dlv, dV = ops.glimpse_pool_bwd_packed_dfeat(dvc, V, av, roff, False, grp=grp or None, dwts=dwts)
-            dVX, dgpv, dwhimg = ops.guided_logits_bwd_packed(dlv, VX, gpv, whimg, roff, N, L, grp=grp or None)
-        elif not grp:
-            dlv, dV = ops.glimpse_pool_bwd(dvc, V.view(N, L, E), av, False, True, dwts=dwts, **rk)
-            dVX, dgpv, dwhimg = ops.guided_logits_bwd(dlv, VX, gpv, whimg, N, L)
-        else:                       # dV (U, L, E) and dVX (U*L, 3E): each image's questions summed in `order`
-            dlv, dV = ops.glimpse_pool_bwd_grouped(dvc, V.view(U, L, E), av, grp[0], grp[1], grp[2], True, dwts=dwts, **rk)
-            dVX, dgpv, dwhimg = ops.guided_logits_bwd_grouped(dlv, VX, gpv, whimg, grp[1], grp[2], N, U, L)
+        # (dV and dVX come back in V's and VX's layout: packed rows, or each shared image's questions summed in `order`)
+        dlv, dV = _pool_bwd(dvc, Vf, av, False, True, layout, dwts=None if dav is None else _c(dav))
+        dVX, dgpv, dwhimg = _guided_bwd(dlv, VX, gpv, whimg, layout, N, L)
         dV = dV.view(V.shape[0], E)
         dbimg = ops.colsum(dgpv)
         ops.gemm(dVX, wimg, tb=True, out=dV, accumulate=True)                      # dV += dVX [img_x_0; img_x_1; img_x_2]
@@ -473,7 +460,7 @@ class LadderAltCoattFn(torch.autograd.Function):
             grads += [dwq2[:E], ops.colsum(dgp), dwsum_h, dwimg[blk], dbimg[blk], dimg_g, dwhimg[g:g + 1], dwq2[E:], g3[g][0],
                       g3[g][1], g3[g][2]]
         ops.multi_add([(dQ[g], dQ1[g], dQ[g]) for g in range(3)])                   # dQ_i: step 3's + the pair's + step 1's
-        return (dV, dQ[0], dQ[1], dQ[2], None, None, None, None, None, None, None, *grads)
+        return (dV, dQ[0], dQ[1], dQ[2], None, None, None, None, None, *grads)
 
 
 class _Coatt(nn.Module):
@@ -592,79 +579,51 @@ class HieCoAttenLadder(nn.Module):
             return x
         return DropoutFn.apply(_c(x), keep, seed, self.drop_p if keep is not None else p)
 
-    def _packed_rows(self, packed, que_features, img_index):
-        """forward(PackedRegions, ...): the refusals of the packed call -> rows (R, D).  offsets is (N + 1,), or (U + 1,) with
-        img_index; nothing here reads a tensor's values."""
-        who = "HieCoAttenLadder"
-        if not torch.is_tensor(que_features) or que_features.dim() != 2:
-            raise VqfError("%s takes (N, T) int64 word ids" % who)
-        owners = que_features.shape[0] if img_index is None else \
-            (packed.offsets.numel() - 1 if torch.is_tensor(packed.offsets) else -1)
-        check_packed_regions(who, packed, owners, que_features.device)
-        rows, L = packed.rows, packed.max_regions
-        if rows.device != que_features.device:
-            raise VqfError("%s: PackedRegions.rows must be on the questions' device (%s), got %s"
-                           % (who, que_features.device, rows.device))
-        R, D = rows.shape
-        if D != self.img_emb.in_features:
-            raise VqfError("%s: PackedRegions.rows must have img_size = %d channels, got %s"
-                           % (who, self.img_emb.in_features, tuple(rows.shape)))
-        E = self.img_emb.out_features
-        if not ops.tanh_dropout_unpack_supported(owners, R, L, E):
-            raise VqfError("%s: PackedRegions takes 1 <= images <= 65535, 1 <= R < 2^29 rows, max_regions <= 1024 and "
-                           "embed_size %% 4 == 0 (got images=%d, R=%d, max_regions=%d, E=%d)" % (who, owners, R, L, E))
-        return rows
-
-    def forward(self, img_features, que_features, q_length=None, img_index=None):
-        packed = img_features if isinstance(img_features, PackedRegions) else None
-        if packed is not None:                                                  # the refusals of the packed call: none needs a GPU
-            img_features, img_length = self._packed_rows(packed, que_features, img_index), None
-        else:
-            img_features, img_length = split_region_features("HieCoAttenLadder", img_features)
-        if not img_features.is_cuda or not que_features.is_cuda:
+    def _is_data(self, img, que_features):
+        """region_layout's refusals about the tensors themselves: the features are fp32 data on the GPU, the ids int64"""
+        if not img.is_cuda or not que_features.is_cuda:
             raise VqfError("HieCoAttenLadder needs GPU tensors (the HIP extension is the only path; no CPU fallback)")
-        if img_features.dtype != torch.float32:
-            raise VqfError("HieCoAttenLadder takes fp32 img_features (got %s)" % img_features.dtype)
-        if img_features.requires_grad:
+        if img.dtype != torch.float32:
+            raise VqfError("HieCoAttenLadder takes fp32 img_features (got %s)" % img.dtype)
+        if img.requires_grad:
             raise VqfError("HieCoAttenLadder: img_features are data (no gradient into the image features)")
         if que_features.dtype != torch.int64:
             raise VqfError("HieCoAttenLadder takes int64 word ids")
-        if packed is None:
-            U, L, D = img_features.shape
-        else:                                                                   # rows (R, D); one owner of offsets per image
-            D, L, U = img_features.shape[1], packed.max_regions, packed.offsets.numel() - 1
-        N = U if img_index is None else que_features.shape[0]
-        T = que_features.shape[1]
-        E = self.img_emb.out_features
+
+    def _limits(self, T, who, N, U, L, R, D, grouped, counted, packed):
+        """region_layout's refusals about the shapes this model's kernels take; none needs a GPU"""
+        E, alt = self.img_emb.out_features, self.coatt_mode == "alternating"
+        if packed and D != self.img_emb.in_features:
+            raise VqfError("%s: PackedRegions.rows must have img_size = %d channels, got %s" % (who, self.img_emb.in_features, (R, D)))
+        if packed and not ops.tanh_dropout_unpack_supported(U, R, L, E):
+            raise VqfError("%s: PackedRegions takes 1 <= images <= 65535, 1 <= R < 2^29 rows, max_regions <= 1024 and "
+                           "embed_size %% 4 == 0 (got images=%d, R=%d, max_regions=%d, E=%d)" % (who, U, R, L, E))
         if E % 32 or not ops.phrase_ngram_supported(T, E) or L > 1024 or T > 1024:
             raise VqfError("HieCoAttenLadder: embed_size %% 32 == 0, T <= 32 and L <= 1024 are supported (got E=%d, T=%d, L=%d)"
                            % (E, T, L))
-        alt = self.coatt_mode == "alternating"
         if alt and not (ops.guided_logits_supported(N, L, E, 3) and ops.guided_logits_supported(N, T, E, 1)):
             raise VqfError("HieCoAttenLadder(coatt='alternating'): embed_size %% 32 == 0, embed_size <= 1024, L <= 1024 and "
                            "N <= 65535 are supported (got E=%d, L=%d, T=%d, N=%d)" % (E, L, T, N))
-        rows_coatt = packed is not None and self.packed_coatt                   # the image side of the co-attention on the R rows
-        if rows_coatt and not (ops.guided_logits_packed_supported(N, U, img_features.shape[0], L, E, 3) and
-                               ops.glimpse_pool_grouped_supported(N, U, L, E, 3)):
+        if packed and self.packed_coatt and not (ops.guided_logits_packed_supported(N, U, R, L, E, 3) and
+                                                 ops.glimpse_pool_grouped_supported(N, U, L, E, 3)):
             raise VqfError("HieCoAttenLadder(packed_coatt=True): embed_size %% 32 == 0, embed_size <= 1024, max_regions <= 1024, "
                            "N <= 65535, 1 <= images <= 65535 and 1 <= R < 2^29 are supported (got E=%d, L=%d, N=%d, images=%d, R=%d)"
-                           % (E, L, N, U, img_features.shape[0]))
-        grp = None
-        if img_index is not None:
-            if not torch.is_tensor(img_index) or img_index.dtype not in (torch.int64, torch.int32):
-                raise VqfError("HieCoAttenLadder: img_index must be an int64 or int32 tensor")
-            if tuple(img_index.shape) != (N,):
-                raise VqfError("HieCoAttenLadder: img_index must have shape (N,) = (%d,), got %s" % (N, tuple(img_index.shape)))
-            if img_index.device != que_features.device:
-                raise VqfError("HieCoAttenLadder: img_index must be on the questions' device (%s), got %s"
-                               % (que_features.device, img_index.device))
-            ok = (ops.guided_logits_grouped_supported(N, U, L, E, 3) and ops.glimpse_pool_grouped_supported(N, U, L, E, 3)) if alt \
-                else ops.row_block_supported(N, U, L * E)
-            if not ok:
-                raise VqfError("HieCoAttenLadder(img_index): 1 <= U <= 65535 images and N <= 65535 questions are supported "
-                               "(got U=%d, N=%d, L=%d, E=%d)" % (U, N, L, E))
-            grp = _group_index(img_index, U)                                    # O(N), on the device: nothing is read back
-        M, MT = U * L, N * T
+                           % (E, L, N, U, R))
+        if grouped and not ((ops.guided_logits_grouped_supported(N, U, L, E, 3) and ops.glimpse_pool_grouped_supported(N, U, L, E, 3))
+                            if alt else ops.row_block_supported(N, U, L * E)):
+            raise VqfError("HieCoAttenLadder(img_index): 1 <= U <= 65535 images and N <= 65535 questions are supported "
+                           "(got U=%d, N=%d, L=%d, E=%d)" % (U, N, L, E))
+
+    def forward(self, img_features, que_features, q_length=None, img_index=None):
+        if not torch.is_tensor(que_features) or que_features.dim() != 2:
+            raise VqfError("HieCoAttenLadder takes (N, T) int64 word ids")
+        T = que_features.shape[1]
+        img_features, layout = region_layout("HieCoAttenLadder", img_features, que_features, img_index,
+                                             lambda t: self._is_data(t, que_features), lambda *dims: self._limits(T, *dims))
+        N, U, L = layout.N, layout.U, layout.L
+        E = self.img_emb.out_features
+        alt = self.coatt_mode == "alternating"
+        MT = N * T
         lens = None
         if q_length is not None:
             if not torch.is_tensor(q_length) or q_length.dtype not in (torch.int64, torch.int32):
@@ -675,33 +634,20 @@ class HieCoAttenLadder(nn.Module):
                 raise VqfError("HieCoAttenLadder: q_length must be on the questions' device (%s), got %s"
                                % (que_features.device, q_length.device))
             lens = q_length.clamp(1, T).to(torch.int32).contiguous()            # O(N), on the device: nothing is read back
-        rlens = None                                                            # per QUESTION: lens_u[idx] with img_index
-        if img_length is not None:
-            check_img_length("HieCoAttenLadder", img_length, U, que_features.device)
-            rlens = _region_lens(img_length, L, None if grp is None else grp[0])   # O(N), on the device: nothing is read back
-            if grp is not None:
-                rlens = rlens[0]
-        if packed is not None:            # O(U), on the device: nothing is read back; the kernels clamp what roff holds
-            off = packed.offsets
-            roff = off.to(torch.int32).contiguous()
-        if packed is not None and not rows_coatt:
-            rlens = _region_lens(off[1:] - off[:-1], L, None if grp is None else grp[0])
-            if grp is not None:
-                rlens = rlens[0]
-        # V = drop(tanh(img_emb(img)))
+        # V = drop(tanh(img_emb(img))): (U*L, E), once per image; from a PackedRegions the product runs on the R real rows
         seed, p = self._seeds.next(self.training, self.drop_p)
         keep = self._seeds.keep.get("img") if self.training else None
-        if packed is None:
-            V = LinearFn.apply(_c(img_features).view(M, D), self.img_emb.weight, self.img_emb.bias, False)
-            V = TanhDropFn.apply(V, None, keep, seed, self.drop_p if keep is not None else p)       # (U*L, E): once per image
-        else:                              # the product on the R real rows; the tanh / dropout pass lays V out padded
-            V = LinearFn.apply(_c(img_features), self.img_emb.weight, self.img_emb.bias, False)      # (R, E)
-            if rows_coatt:                 # V stays (R, E): the masks of the padded tensor on the real rows
-                V = TanhDropPackedFn.apply(V, roff, U, L, keep, seed, self.drop_p if keep is not None else p)
-            else:
-                V = TanhDropUnpackFn.apply(V, roff, U, L, keep, seed, self.drop_p if keep is not None else p)   # (U*L, E), zero padded rows
-        if grp is not None and not alt:
-            V = RowBlockGatherFn.apply(V, grp[0], grp[1], grp[2], L)                                  # (N*L, E)
+        V = LinearFn.apply(_c(img_features).view(layout.R, -1), self.img_emb.weight, self.img_emb.bias, False)
+        if not layout.packed:
+            V = TanhDropFn.apply(V, None, keep, seed, self.drop_p if keep is not None else p)
+        elif self.packed_coatt:            # V stays (R, E): the masks of the padded tensor on the real rows
+            V = TanhDropPackedFn.apply(V, layout.roff, U, L, keep, seed, self.drop_p if keep is not None else p)
+        else:                              # the tanh / dropout pass lays V out padded, (U*L, E) with zero padded rows
+            V = TanhDropUnpackFn.apply(V, layout.roff, U, L, keep, seed, self.drop_p if keep is not None else p)
+            layout = layout.padded()
+        if layout.grouped and not alt:
+            V = RowBlockGatherFn.apply(V, *layout.grp, L)                                            # (N*L, E)
+            layout = layout.per_question()
         # Qw = drop(tanh(word_emb(ids)))
         qw = EmbedTanhFn.apply(que_features, self.word_emb.weight, True, False, lens).view(MT, E)
         qw = self._drop(qw, "word")
@@ -718,11 +664,10 @@ class HieCoAttenLadder(nn.Module):
             w = [p_ for c in self.coatt for p_ in (c.sum_x.weight, c.sum_x.bias, c.sum_h.weight, c.img_x.weight, c.img_x.bias,
                                                    c.img_g.weight, c.img_h.weight, c.que_x.weight, c.que_x.bias, c.que_g.weight,
                                                    c.que_h.weight)]
-            vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderAltCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, grp, rlens,
-                                                                         roff if rows_coatt else None, *w)
+            vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderAltCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, layout, *w)
         else:
             w = [p_ for c in self.coatt for p_ in (c.Wb.weight, c.Wv.weight, c.Wq.weight, c.whv.weight, c.whq.weight)]
-            vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, rlens, *w)
+            vcat, q0, q1, q2, av, aq0, aq1, aq2 = LadderCoattFn.apply(V, _c(qw), _c(qp), qs, N, L, T, lens, layout, *w)
         v0, v1, v2 = vcat[:, :E], vcat[:, E:2 * E], vcat[:, 2 * E:]
         th = lambda x: TanhDropFn.apply(x, None, None, 0, 0.0)
         lin = lambda x, m: LinearFn.apply(_c(x), m.weight, m.bias, False)

@@ -12,7 +12,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .grouping import _group_index, _region_lens, check_img_index, check_img_length, check_packed_regions, PackedRegions
+from .lib import VqfError
+from .grouping import check_img_index, check_img_length, check_packed_regions, PackedRegions, RegionLayout
 from .functions import (LinearFn, AttHeadFn, ImgFuseFn, ImgProjFn, ImgProjLateFn, ImgProjDeferFn, MfbFuseFn, FinalMfbFn,
                         LstmBatchFn, UnitPoolFn, DeadParamsFn, NormLink, img_project, embed_tanh, lstm_out_dropout)
 
@@ -21,7 +22,6 @@ def _image_is_data(img, gemm_dtype="fp32"):
     """The image grid features are input data on this path (no d/d-image kernels: SURVEY 8a, a5),
     and they must live on the GPU: there is no CPU fallback.  A bf16 feature tensor (bf16 storage,
     data_loader.FeatureStager(bf16=True)) is accepted when the image projection runs in bf16."""
-    from .lib import VqfError
     if not img.is_cuda:
         raise VqfError("vqa fusion modules need GPU tensors (HIP extension is the only path; no CPU fallback)")
     if img.dtype == torch.bfloat16:
@@ -37,43 +37,10 @@ def _image_is_data(img, gemm_dtype="fp32"):
                        "data and does not produce its gradient")
 
 
-def shared_image_groups(who, img_features, questions, img_index, gemm_dtype):
-    """forward(..., img_index): the refusals of the shared-image call and the device-side grouping.  img_features (U, L, D),
-    questions (N, ...), img_index (N,) int64 / int32 on the questions' device -> (idx, order, grp_off) (grouping._group_index:
-    the index is clamped to [0, U - 1] on the device and never read on the host)."""
-    from .lib import VqfError
-    if gemm_dtype != "fp32" or img_features.dtype != torch.float32:
-        raise VqfError("%s: img_index is fp32 only (the grouped fusion kernels have no bf16 form); got gemm_dtype=%r and %s "
-                       "img_features" % (who, gemm_dtype, img_features.dtype))
-    U, L, D = img_features.shape
-    N = questions.shape[0]
-    check_img_index(who, img_index, N, U, questions.device)
-    if not (ops.mfb_fuse_grouped_supported(N, U, L, 1000) and ops.glimpse_pool_grouped_supported(N, U, L, D, 2)
-            and ops.row_block_supported(N, U, 2 * D)):
-        raise VqfError("%s: img_index needs L <= 1024 regions and a channel count that is a multiple of 4 (got U=%d, N=%d, L=%d, "
-                       "D=%d)" % (who, U, N, L, D))
-    return _group_index(img_index, U)
-
-
-def image_region_lens(who, img_features, questions, img_length, grp, gemm_dtype):
-    """forward((img, img_length), ...): the refusals of the region-count call and the device-side counts.  img_length: one count per
-    image -- (N,), or (U,) with img_index -- int64 / int32 on the questions' device -> what ImgFuseFn / MfbFuseFn / AttHeadFn take
-    as `lens` (grouping._region_lens: clamped to [1, L] on the device, never read on the host)."""
-    from .lib import VqfError
-    if gemm_dtype != "fp32" or img_features.dtype != torch.float32:
-        raise VqfError("%s: img_length is fp32 only (the region-count fusion kernels have no bf16 form); got gemm_dtype=%r and %s "
-                       "img_features" % (who, gemm_dtype, img_features.dtype))
-    check_img_length(who, img_length, img_features.shape[0], questions.device)
-    if img_features.shape[1] > 1024:
-        raise VqfError("%s: img_length needs L <= 1024 regions (got L=%d)" % (who, img_features.shape[1]))
-    return _region_lens(img_length, img_features.shape[1], None if grp is None else grp[0])
-
-
 def split_region_features(who, img_features):
     """The region-count call form: img_features given as the pair (img (N, L, D), img_length (N,)) -> (img, img_length); a plain
     tensor -> (img, None).  forward() keeps its parameter list (the positional call forms are pinned); the counts travel with
     the features they describe, as data_loader.pad_region_features returns them."""
-    from .lib import VqfError
     if isinstance(img_features, (tuple, list)):
         if any(isinstance(t, PackedRegions) for t in img_features):
             raise VqfError("%s: a PackedRegions carries its own counts and is passed on its own, not inside a pair (img, img_length)"
@@ -85,31 +52,69 @@ def split_region_features(who, img_features):
     return img_features, None
 
 
-def packed_region_rows(who, packed, questions, img_index, gemm_dtype):
-    """forward(PackedRegions(rows, offsets, max_regions), ...): the refusals of the packed call and what the nodes take
-    -> (rows (R, D), pack = (roff int32 on the device, L), grp or None).  offsets is (N + 1,), or (U + 1,) with img_index; it is
-    converted on the device and never read on the host (the kernels clamp what it holds)."""
-    from .lib import VqfError
-    if gemm_dtype != "fp32":
-        raise VqfError("%s: PackedRegions is fp32 only (the packed fusion kernels have no bf16 form); got gemm_dtype=%r"
-                       % (who, gemm_dtype))
-    N = questions.shape[0]
-    U = N if img_index is None else (packed.offsets.numel() - 1 if torch.is_tensor(packed.offsets) else -1)
-    check_packed_regions(who, packed, U, questions.device)
-    rows, L = packed.rows, packed.max_regions
-    _image_is_data(rows, gemm_dtype)
-    if rows.device != questions.device:
-        raise VqfError("%s: PackedRegions.rows must be on the questions' device (%s), got %s" % (who, questions.device, rows.device))
-    R, D = rows.shape
-    grp = None
+def _fusion_limits(who, N, U, L, R, D, grouped, counted, packed):
+    """region_layout's `limits` of MFB / MHBCoAtt: the shapes their grouped, region-count and packed fusion kernels take."""
+    if packed:
+        if not (1 <= N <= 65535 and ops.mfb_fuse_packed_supported(N, U, R, L, 1000) and ops.glimpse_pool_grouped_supported(N, U, L, D, 2)
+                and (not grouped or ops.row_block_supported(N, U, 2 * D))):
+            raise VqfError("%s: PackedRegions needs at most 65535 questions and images and a channel count that is a multiple of 4 "
+                           "(got U=%d, N=%d, R=%d, L=%d, D=%d)" % (who, U, N, R, L, D))
+        return
+    if grouped and not (ops.mfb_fuse_grouped_supported(N, U, L, 1000) and ops.glimpse_pool_grouped_supported(N, U, L, D, 2)
+                        and ops.row_block_supported(N, U, 2 * D)):
+        raise VqfError("%s: img_index needs L <= 1024 regions and a channel count that is a multiple of 4 (got U=%d, N=%d, L=%d, "
+                       "D=%d)" % (who, U, N, L, D))
+    if counted and L > 1024:
+        raise VqfError("%s: img_length needs L <= 1024 regions (got L=%d)" % (who, L))
+
+
+def region_layout(who, img_features, questions, img_index, is_data, limits, gemm_dtype="fp32"):
+    """The one place that turns a call form into what the nodes take: img_features a tensor (U, L, D), the pair (img, img_length) or
+    a PackedRegions, each with or without img_index -> (img (U, L, D) or rows (R, D), grouping.RegionLayout).  Every refusal of the
+    form is raised here, before the first launch: those of the arguments themselves (grouping.check_*), the fp32-only ones
+    (gemm_dtype: the grouped, region-count and packed kernels have no bf16 form), the model's own about the feature tensor
+    (is_data(t): device, dtype, no gradient) and about the shapes its kernels take (limits(who, N, U, L, R, D, grouped, counted,
+    packed)).  The index, the counts and the offsets are converted on the device and never read on the host (the kernels clamp
+    what they hold).  Without img_index there is one image per question: the layout's N is U."""
+    dev = questions.device
+    if isinstance(img_features, PackedRegions):
+        packed = img_features
+        if gemm_dtype != "fp32":
+            raise VqfError("%s: PackedRegions is fp32 only (the packed fusion kernels have no bf16 form); got gemm_dtype=%r"
+                           % (who, gemm_dtype))
+        N = questions.shape[0]
+        U = N if img_index is None else (packed.offsets.numel() - 1 if torch.is_tensor(packed.offsets) else -1)
+        check_packed_regions(who, packed, U, dev)
+        rows, L = packed.rows, packed.max_regions
+        if rows.device != dev:
+            raise VqfError("%s: PackedRegions.rows must be on the questions' device (%s), got %s" % (who, dev, rows.device))
+        limits(who, N, U, L, rows.shape[0], rows.shape[1], img_index is not None, False, True)
+        is_data(rows)
+        if img_index is not None:
+            check_img_index(who, img_index, N, U, dev)
+        return rows.contiguous(), RegionLayout(N, U, L, img_index, None, packed.offsets, rows.shape[0])
+    img, img_length = split_region_features(who, img_features)
+    is_data(img)
+    U, L, D = img.shape
+    N = U if img_index is None else questions.shape[0]
+    if (img_index is not None or img_length is not None) and (gemm_dtype != "fp32" or img.dtype != torch.float32):
+        raise VqfError("%s: %s is fp32 only (the %s fusion kernels have no bf16 form); got gemm_dtype=%r and %s img_features"
+                       % ((who,) + (("img_index", "grouped") if img_index is not None else ("img_length", "region-count"))
+                          + (gemm_dtype, img.dtype)))
     if img_index is not None:
-        check_img_index(who, img_index, N, U, questions.device)
-        grp = _group_index(img_index, U)
-    if not (1 <= N <= 65535 and ops.mfb_fuse_packed_supported(N, U, R, L, 1000) and ops.glimpse_pool_grouped_supported(N, U, L, D, 2)
-            and (grp is None or ops.row_block_supported(N, U, 2 * D))):
-        raise VqfError("%s: PackedRegions needs at most 65535 questions and images and a channel count that is a multiple of 4 "
-                       "(got U=%d, N=%d, R=%d, L=%d, D=%d)" % (who, U, N, R, L, D))
-    return rows.contiguous(), (packed.offsets.to(torch.int32).contiguous(), L), grp
+        check_img_index(who, img_index, N, U, dev)
+    if img_length is not None:
+        check_img_length(who, img_length, U, dev)
+    limits(who, N, U, L, U * L, D, img_index is not None, img_length is not None, False)
+    return img, RegionLayout(N, U, L, img_index, img_length)
+
+
+def fusion_region_layout(who, img_features, questions, img_index, gemm_dtype):
+    """MFB / MHBCoAtt's call of region_layout -> (img (U, L, D) or rows (R, D), the 3-D tensor the projection nodes flatten -- rows
+    as (1, R, D) --, L, the nodes' layout: None for the plain tensor, whose path takes nothing extra)."""
+    img, layout = region_layout(who, img_features, questions, img_index, lambda t: _image_is_data(t, gemm_dtype), _fusion_limits,
+                                gemm_dtype)
+    return img, (img.unsqueeze(0) if layout.packed else img), layout.L, (None if layout.plain else layout)
 
 
 _warned = set()
@@ -294,16 +299,16 @@ class MFB(nn.Module):
         """Test hook: explicit uint8 keep-masks 'm1' (N*L,5000), 'm2' (N,5000) instead of Philox."""
         self._seeds.keep = masks
 
-    def _forward_pruned(self, img_features, ques_feature, keep, grp=None, lens=None, pack=None):
+    def _forward_pruned(self, img_features, ques_feature, keep, layout=None):
         """The live part of the reference graph when both softmaxes are over a singleton axis."""
         pm = self.dropout_m.p
         qa = UnitPoolFn.apply(ques_feature, 2)                             # (N, 2H)   mfb.py:85-89 with weights 1
         self._seeds.next(self.training, pm)                                # the regions' dropout draw (unused, keeps the stream)
         # (N, 2D)   mfb.py:119-123 with weights 1 (img_length: on the real regions; per image when the images are shared)
         # (packed rows: one sum per owner of the row offsets -- per image when the images are shared)
-        va = UnitPoolFn.apply(img_features, 2, lens if grp is None or lens is None else lens[1], pack)
-        if grp is not None:                                                # per image (U, 2D), one row block per question
-            va = ops.row_block_gather(va, grp[0])
+        va = UnitPoolFn.apply(img_features, 2, layout)
+        if layout is not None and layout.grouped:                          # per image (U, 2D), one row block per question
+            va = ops.row_block_gather(va, layout.idx)
         seed, p = self._seeds.next(self.training, pm)
         k2 = keep.get('m2')
         y = FinalMfbFn.apply(qa, va, self.ques_proj2.weight, self.ques_proj2.bias,
@@ -334,16 +339,7 @@ class MFB(nn.Module):
         never padded; offsets (N + 1,), or (U + 1,) per image with img_index, int64 / int32 on the questions' device; max_regions a
         Python int L in [1, 1024], at least the largest count (fp32 only).  The result is this model on (packed.unpack(), ...),
         the region-count call; img_conv1d and its weight gradient run on the R real rows only."""
-        pack = None
-        if isinstance(img_features, PackedRegions):
-            img_features, pack, grp = packed_region_rows("MFB", img_features, questions, img_index, self.gemm_dtype)
-            lens = None
-        else:
-            img_features, img_length = split_region_features("MFB", img_features)
-            _image_is_data(img_features, self.gemm_dtype)
-            grp = None if img_index is None else shared_image_groups("MFB", img_features, questions, img_index, self.gemm_dtype)
-            lens = None if img_length is None else image_region_lens("MFB", img_features, questions, img_length, grp, self.gemm_dtype)
-        img3 = img_features if pack is None else img_features.unsqueeze(0)     # the projection nodes only flatten: rows as (1, R, D)
+        img_features, img3, L, layout = fusion_region_layout("MFB", img_features, questions, img_index, self.gemm_dtype)
         bf16_img = self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
         bf16_all = self.gemm_dtype == "bf16-all"          # also ques_proj*, img_proj*, the question-attention conv
         # a5 starts first, on the side stream: it only needs the image and its weights
@@ -362,10 +358,9 @@ class MFB(nn.Module):
         lstm_o = batch_first_lstm(self.lstm, que_embedded, self.use_hip_lstm, _lstm_bf16(self.gemm_dtype), time_major_in=tm)
         ques_feature = lstm_out_dropout(self.dropout_l, lstm_o, self._seeds)   # (N,T,H) contiguous; mfb.py:70
         N, T, H = ques_feature.shape
-        L = img_features.shape[1] if pack is None else pack[1]
         keep = self._seeds.keep
         if self.pruned and self.unit_softmax:
-            return self._forward_pruned(img_features, ques_feature, keep, grp, lens, pack)
+            return self._forward_pruned(img_features, ques_feature, keep, layout)
 
         # a3: question attention                                             mfb.py:73-89
         wm, bm = self._mc('ques_att_multiconv')
@@ -382,16 +377,15 @@ class MFB(nn.Module):
         link = NormLink() if (self.fold_norm and not self.multilayer) else None
         if proj is not None:
             P0 = self._side.join(*proj)
-            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, grp, lens, pack)
+            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, layout)
         else:
             Y = ImgFuseFn.apply(img3, self.img_conv1d.weight, self.img_conv1d.bias, qp,
-                                k1, seed, pm if k1 is not None else p, bf16_img, link, grp, lens, pack)
+                                k1, seed, pm if k1 is not None else p, bf16_img, link, layout)
         # a7+a8: co-attention over the regions                               mfb.py:109-123
         # (with a link Y is the un-normalised R and 1/norm rides in co_att_conv1's GEMM epilogue)
         wm, bm = self._mc('co_att_multiconv')
         va = AttHeadFn.apply(Y, img_features, self.co_att_conv1.weight, self.co_att_conv1.bias, wm, bm,
-                             self.co_att_conv2.weight, self.co_att_conv2.bias, self.unit_softmax, coatt_bf16, link, False, grp, lens,
-                             pack)
+                             self.co_att_conv2.weight, self.co_att_conv2.bias, self.unit_softmax, coatt_bf16, link, False, layout)
         # a9: final MFB block                                                mfb.py:126-135
         seed, p = self._seeds.next(self.training, pm)
         k2 = keep.get('m2')

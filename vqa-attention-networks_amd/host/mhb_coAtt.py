@@ -10,9 +10,7 @@ import torch.nn as nn
 from . import ops
 from .functions import (LinearFn, Linear2Fn, AttHeadFn, ImgFuseFn, MfbFuseFn, FinalMfbFn, LstmSeqFn, LstmBatchFn, LogSoftmaxRowsFn,
                         NormLink, embed_tanh, embed, lstm_out_dropout)
-from .mfb import (_DropSeeds, _image_is_data, _SideStream, _lstm_bf16, batch_first_lstm, warn_once, shared_image_groups,
-                  image_region_lens, split_region_features, packed_region_rows)
-from .grouping import PackedRegions
+from .mfb import _DropSeeds, _image_is_data, _SideStream, _lstm_bf16, batch_first_lstm, warn_once, fusion_region_layout
 
 
 class MHBCoAtt(nn.Module):
@@ -61,19 +59,7 @@ class MHBCoAtt(nn.Module):
         projection and its weight gradient still run over them, and they cancel only because their dP rows are exact zeros.
         Packed regions: see MFB.forward -- img_features may be a PackedRegions(rows, offsets, max_regions) (fp32 only): the real
         regions of every image, never padded; the result is this model on (packed.unpack(), ...)."""
-        pack = None
-        if isinstance(img_features, PackedRegions):
-            img_features, pack, grp = packed_region_rows("MHBCoAtt", img_features, questions, img_index, self.gemm_dtype)
-            lens, L = None, pack[1]
-            img3 = img_features.unsqueeze(0)                   # the projection nodes only flatten: rows as (1, R, D)
-        else:
-            img_features, img_length = split_region_features("MHBCoAtt", img_features)
-            _image_is_data(img_features, self.gemm_dtype)
-            grp = None if img_index is None else shared_image_groups("MHBCoAtt", img_features, questions, img_index, self.gemm_dtype)
-            lens = None if img_length is None else image_region_lens("MHBCoAtt", img_features, questions, img_length, grp,
-                                                                     self.gemm_dtype)
-            L = img_features.shape[1]
-            img3 = img_features
+        img_features, img3, L, layout = fusion_region_layout("MHBCoAtt", img_features, questions, img_index, self.gemm_dtype)
         N = questions.shape[0]
         keep = self._seeds.keep
         bf16_img = self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
@@ -121,12 +107,12 @@ class MHBCoAtt(nn.Module):
         link = NormLink() if self.fold_norm else None
         if proj is not None:
             P0 = self._side.join(*proj)
-            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, grp, lens, pack)
+            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, layout)
         else:
             Y = ImgFuseFn.apply(img3, self.img_conv1d.weight, self.img_conv1d.bias, qp,
-                                k1, seed, pm if k1 is not None else p, bf16_img, link, grp, lens, pack)
+                                k1, seed, pm if k1 is not None else p, bf16_img, link, layout)
         va = AttHeadFn.apply(Y, img_features, self.co_att_conv1.weight, self.co_att_conv1.bias, None, None,
-                             self.co_att_conv2.weight, self.co_att_conv2.bias, False, coatt_bf16, link, False, grp, lens, pack)
+                             self.co_att_conv2.weight, self.co_att_conv2.bias, False, coatt_bf16, link, False, layout)
         ys = []
         for tag, qpj, ipj in (('m2', self.ques_proj2, self.img_proj2), ('m3', self.ques_proj3, self.img_proj3)):
             seed, p = self._seeds.next(self.training, pm)

@@ -1168,6 +1168,45 @@ def _keep_ptr(keep):
     return ctypes.c_void_p(keep.data_ptr())
 
 
+def _l2_norm_tail(R, rowssq, N, L, O, normalise):
+    """The tail of every mfb_fuse_fwd*: norm / inv of each sample from the rows' partial sums of squares (four per row) and, with
+    normalise, R scaled by inv in place -> (norm (N), inv (N))."""
+    norm = torch.empty(N, dtype=torch.float32, device=R.device)
+    inv = torch.empty(N, dtype=torch.float32, device=R.device)
+    _l.check(_lib().vqf_l2_group_norm(_ptr(rowssq), N, 4 * L, _ptr(norm), _ptr(inv), _stream()), "vqf_l2_group_norm")
+    if normalise:
+        _l.check(_lib().vqf_scale_rows(_ptr(R), _ptr(inv), N * L, L, O, _ptr(R), _stream()), "vqf_scale_rows")
+    return norm, inv
+
+
+def _l2_norm_bwd_coefs(dY, Y, norm, inv, N, L, O, lin):
+    """The head of every mfb_fuse_bwd*: the two per-sample coefficients of the L2 norm's backward -> (cA (N), cB (N), the inv the
+    fusion backward takes).  lin = (dlogits, lin) of the consumer's attention head (mfb_fuse_bwd): sum(R * dYs) from its (N*L, G)
+    tensors and inv = 1; otherwise a rowdot pass over the (N*L, O) ones."""
+    dev = Y.device
+    cA = torch.empty(N, dtype=torch.float32, device=dev)
+    cB = torch.empty(N, dtype=torch.float32, device=dev)
+    if lin is not None:
+        dl, ln = lin
+        _chk(dl, ln)
+        unit = torch.empty(N, dtype=torch.float32, device=dev)
+        _l.check(_lib().vqf_l2_norm_bwd_coef_lin(_ptr(dl), _ptr(ln), dl.shape[1], _ptr(norm), _ptr(inv), N, L, _ptr(cA),
+                                                 _ptr(cB), _ptr(unit), _stream()), "vqf_l2_norm_bwd_coef_lin")
+        return cA, cB, unit
+    rowdot = torch.empty(N * L, dtype=torch.float32, device=dev)
+    _l.check(_lib().vqf_rowdot(_ptr(Y), _ptr(dY), N * L, O, _ptr(rowdot), _stream()), "vqf_rowdot")
+    _l.check(_lib().vqf_l2_norm_bwd_coef(_ptr(rowdot), _ptr(norm), _ptr(inv), N, L, _ptr(cA), _ptr(cB), _stream()),
+             "vqf_l2_norm_bwd_coef")
+    return cA, cB, inv
+
+
+def _chk_roff(name, roff, U):
+    """roff of the packed forms: a contiguous (U + 1,) int32 GPU tensor of row offsets (the kernels clamp what it holds)"""
+    if not torch.is_tensor(roff) or not roff.is_cuda or roff.dtype != torch.int32 or not roff.is_contiguous() or \
+            tuple(roff.shape) != (U + 1,):
+        raise _l.VqfError("%s: roff must be a contiguous (%d,) int32 GPU tensor of row offsets" % (name, U + 1))
+
+
 def mfb_fuse_fwd(P, q, N, L, O, keep=None, seed=0, p_drop=0.0, cascade=None, want_zdrop=False, pbias=None,
                  normalise=True, r_bf16=None, lens=None):
     """-> (Y normalised (N*L,O), norm (N), inv (N), zdrop or None).  pbias: projection bias added on load.
@@ -1206,13 +1245,7 @@ def mfb_fuse_fwd(P, q, N, L, O, keep=None, seed=0, p_drop=0.0, cascade=None, wan
         _l.check(_lib().vqf_mfb_fuse_fwd(_ptr(P), _ptr(pbias), _ptr(q), _ptr(cascade), _keep_ptr(keep), int(seed),
                                          float(p_drop), N, L, O, _ptr(R), _ptr(rowssq), _ptr(zdrop), _stream()),
                  "vqf_mfb_fuse_fwd")
-    norm = torch.empty(N, dtype=torch.float32, device=dev)
-    inv = torch.empty(N, dtype=torch.float32, device=dev)
-    _l.check(_lib().vqf_l2_group_norm(_ptr(rowssq), N, 4 * L, _ptr(norm), _ptr(inv), _stream()),
-             "vqf_l2_group_norm")
-    if normalise:
-        _l.check(_lib().vqf_scale_rows(_ptr(R), _ptr(inv), N * L, L, O, _ptr(R), _stream()), "vqf_scale_rows")
-    return R, norm, inv, zdrop
+    return (R,) + _l2_norm_tail(R, rowssq, N, L, O, normalise) + (zdrop,)
 
 
 def mfb_fuse_bwd(dY, Y, norm, inv, P, q, N, L, O, keep=None, seed=0, p_drop=0.0, cascade=None,
@@ -1232,20 +1265,7 @@ def mfb_fuse_bwd(dY, Y, norm, inv, P, q, N, L, O, keep=None, seed=0, p_drop=0.0,
     if P.dtype == torch.bfloat16 and not dp_bf16:
         raise _l.VqfError("mfb_fuse_bwd: a bf16 P comes with a bf16 dP")
     dev = P.device
-    cA = torch.empty(N, dtype=torch.float32, device=dev)
-    cB = torch.empty(N, dtype=torch.float32, device=dev)
-    if lin is not None:
-        dl, ln = lin
-        _chk(dl, ln)
-        unit = torch.empty(N, dtype=torch.float32, device=dev)
-        _l.check(_lib().vqf_l2_norm_bwd_coef_lin(_ptr(dl), _ptr(ln), dl.shape[1], _ptr(norm), _ptr(inv), N, L, _ptr(cA),
-                                                 _ptr(cB), _ptr(unit), _stream()), "vqf_l2_norm_bwd_coef_lin")
-        inv = unit
-    else:
-        rowdot = torch.empty(N * L, dtype=torch.float32, device=dev)
-        _l.check(_lib().vqf_rowdot(_ptr(Y), _ptr(dY), N * L, O, _ptr(rowdot), _stream()), "vqf_rowdot")
-        _l.check(_lib().vqf_l2_norm_bwd_coef(_ptr(rowdot), _ptr(norm), _ptr(inv), N, L, _ptr(cA), _ptr(cB),
-                                             _stream()), "vqf_l2_norm_bwd_coef")
+    cA, cB, inv = _l2_norm_bwd_coefs(dY, Y, norm, inv, N, L, O, lin)
     dq = torch.empty((N, POOL_K * O), dtype=torch.float32, device=dev)
     db = torch.empty(POOL_K * O, dtype=torch.float32, device=dev) if want_dbias else None
     ws = workspace(dev, _lib().vqf_mfb_fuse_bwd_ws_bytes(N, L, O))
@@ -1299,9 +1319,10 @@ def _chk_lens_grouped(name, lens, N, U):
         return None, None
     if not isinstance(lens, (tuple, list)) or len(lens) != 2:
         raise _l.VqfError(name + ": lens must be the pair (lens_q (N,), lens_u (U,))")
-    _chk_lens(lens[0], N, name)
-    _chk_lens(lens[1], U, name)
-    return lens[0], lens[1]
+    lens_q, lens_u = lens
+    _chk_lens(lens_q, N, name)
+    _chk_lens(lens_u, U, name)
+    return lens_q, lens_u
 
 
 def mfb_fuse_fwd_grouped(P, q, idx, N, U, L, O, keep=None, seed=0, p_drop=0.0, pbias=None, normalise=True, lens=None):
@@ -1322,12 +1343,7 @@ def mfb_fuse_fwd_grouped(P, q, idx, N, U, L, O, keep=None, seed=0, p_drop=0.0, p
     else:
         _l.check(_lib().vqf_mfb_fuse_fwd_grouped(_ptr(P), _ptr(pbias), _ptr(q), _ptr(idx), _keep_ptr(keep), int(seed), float(p_drop),
                                                  N, U, L, O, _ptr(R), _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_grouped")
-    norm = torch.empty(N, dtype=torch.float32, device=dev)
-    inv = torch.empty(N, dtype=torch.float32, device=dev)
-    _l.check(_lib().vqf_l2_group_norm(_ptr(rowssq), N, 4 * L, _ptr(norm), _ptr(inv), _stream()), "vqf_l2_group_norm")
-    if normalise:
-        _l.check(_lib().vqf_scale_rows(_ptr(R), _ptr(inv), N * L, L, O, _ptr(R), _stream()), "vqf_scale_rows")
-    return R, norm, inv
+    return (R,) + _l2_norm_tail(R, rowssq, N, L, O, normalise)
 
 
 def mfb_fuse_bwd_grouped(dY, Y, norm, inv, P, q, idx, order, grp_off, N, U, L, O, keep=None, seed=0, p_drop=0.0,
@@ -1342,20 +1358,7 @@ def mfb_fuse_bwd_grouped(dY, Y, norm, inv, P, q, idx, order, grp_off, N, U, L, O
     if tuple(dY.shape) != (N * L, O) or tuple(Y.shape) != (N * L, O):
         raise _l.VqfError("mfb_fuse_bwd_grouped: dY and Y must be (N*L, O)")
     dev = P.device
-    cA = torch.empty(N, dtype=torch.float32, device=dev)
-    cB = torch.empty(N, dtype=torch.float32, device=dev)
-    if lin is not None:
-        dl, ln = lin
-        _chk(dl, ln)
-        unit = torch.empty(N, dtype=torch.float32, device=dev)
-        _l.check(_lib().vqf_l2_norm_bwd_coef_lin(_ptr(dl), _ptr(ln), dl.shape[1], _ptr(norm), _ptr(inv), N, L, _ptr(cA),
-                                                 _ptr(cB), _ptr(unit), _stream()), "vqf_l2_norm_bwd_coef_lin")
-        inv = unit
-    else:
-        rowdot = torch.empty(N * L, dtype=torch.float32, device=dev)
-        _l.check(_lib().vqf_rowdot(_ptr(Y), _ptr(dY), N * L, O, _ptr(rowdot), _stream()), "vqf_rowdot")
-        _l.check(_lib().vqf_l2_norm_bwd_coef(_ptr(rowdot), _ptr(norm), _ptr(inv), N, L, _ptr(cA), _ptr(cB),
-                                             _stream()), "vqf_l2_norm_bwd_coef")
+    cA, cB, inv = _l2_norm_bwd_coefs(dY, Y, norm, inv, N, L, O, lin)
     dP = torch.empty_like(P)
     dq = torch.empty((N, POOL_K * O), dtype=torch.float32, device=dev)
     db = torch.empty(POOL_K * O, dtype=torch.float32, device=dev) if want_dbias else None
@@ -1387,9 +1390,7 @@ def _packed_operands(name, P, q, roff, N, U, L, O, pbias):
             (pbias is not None and tuple(pbias.shape) != (POOL_K * O,)):
         raise _l.VqfError("%s: P must be a contiguous (R, 5*O) tensor with R >= 1, q (N, 5*O) and pbias (5*O,); got P %s, q %s"
                           % (name, tuple(P.shape), tuple(q.shape)))
-    if not torch.is_tensor(roff) or not roff.is_cuda or roff.dtype != torch.int32 or not roff.is_contiguous() or \
-            tuple(roff.shape) != (U + 1,):
-        raise _l.VqfError("%s: roff must be a contiguous (%d,) int32 GPU tensor of row offsets" % (name, U + 1))
+    _chk_roff(name, roff, U)
     if not mfb_fuse_packed_supported(N, U, R, L, O):
         raise _l.VqfError("%s: N <= 65535, U <= 65535, L <= 1024, O %% 4 == 0 and O <= 1024 are supported (got N=%d, U=%d, R=%d, "
                           "L=%d, O=%d)" % (name, N, U, R, L, O))
@@ -1413,12 +1414,7 @@ def mfb_fuse_fwd_packed(P, q, roff, N, L, O, idx=None, keep=None, seed=0, p_drop
         _l.check(_lib().vqf_mfb_fuse_fwd_grouped_packed(_ptr(P), _ptr(pbias), _ptr(q), _ptr(idx), _ptr(roff), _keep_ptr(keep), int(seed),
                                                         float(p_drop), N, U, R, L, O, _ptr(Y), _ptr(rowssq), _stream()),
                  "vqf_mfb_fuse_fwd_grouped_packed")
-    norm = torch.empty(N, dtype=torch.float32, device=dev)
-    inv = torch.empty(N, dtype=torch.float32, device=dev)
-    _l.check(_lib().vqf_l2_group_norm(_ptr(rowssq), N, 4 * L, _ptr(norm), _ptr(inv), _stream()), "vqf_l2_group_norm")
-    if normalise:
-        _l.check(_lib().vqf_scale_rows(_ptr(Y), _ptr(inv), N * L, L, O, _ptr(Y), _stream()), "vqf_scale_rows")
-    return Y, norm, inv
+    return (Y,) + _l2_norm_tail(Y, rowssq, N, L, O, normalise)
 
 
 def mfb_fuse_bwd_packed(dY, Y, norm, inv, P, q, roff, N, L, O, grp=None, keep=None, seed=0, p_drop=0.0, want_dbias=False, pbias=None,
@@ -1431,20 +1427,7 @@ def mfb_fuse_bwd_packed(dY, Y, norm, inv, P, q, roff, N, L, O, grp=None, keep=No
     if tuple(dY.shape) != (N * L, O) or tuple(Y.shape) != (N * L, O):
         raise _l.VqfError("mfb_fuse_bwd_packed: dY and Y must be (N*L, O)")
     dev = P.device
-    cA = torch.empty(N, dtype=torch.float32, device=dev)
-    cB = torch.empty(N, dtype=torch.float32, device=dev)
-    if lin is not None:
-        dl, ln = lin
-        _chk(dl, ln)
-        unit = torch.empty(N, dtype=torch.float32, device=dev)
-        _l.check(_lib().vqf_l2_norm_bwd_coef_lin(_ptr(dl), _ptr(ln), dl.shape[1], _ptr(norm), _ptr(inv), N, L, _ptr(cA),
-                                                 _ptr(cB), _ptr(unit), _stream()), "vqf_l2_norm_bwd_coef_lin")
-        inv = unit
-    else:
-        rowdot = torch.empty(N * L, dtype=torch.float32, device=dev)
-        _l.check(_lib().vqf_rowdot(_ptr(Y), _ptr(dY), N * L, O, _ptr(rowdot), _stream()), "vqf_rowdot")
-        _l.check(_lib().vqf_l2_norm_bwd_coef(_ptr(rowdot), _ptr(norm), _ptr(inv), N, L, _ptr(cA), _ptr(cB),
-                                             _stream()), "vqf_l2_norm_bwd_coef")
+    cA, cB, inv = _l2_norm_bwd_coefs(dY, Y, norm, inv, N, L, O, lin)
     dP = torch.empty_like(P)
     dq = torch.empty((N, POOL_K * O), dtype=torch.float32, device=dev)
     db = torch.empty(POOL_K * O, dtype=torch.float32, device=dev) if want_dbias else None
@@ -1470,9 +1453,7 @@ def _pool_packed_dims(name, feat, roff, logits_or_wts_G, N, S, idx):
         raise _l.VqfError(name + ": feat must be a contiguous (R, C) fp32 GPU tensor with R >= 1")
     R, C = feat.shape
     U = N if idx is None else roff.shape[0] - 1
-    if not torch.is_tensor(roff) or not roff.is_cuda or roff.dtype != torch.int32 or not roff.is_contiguous() or \
-            tuple(roff.shape) != (U + 1,):
-        raise _l.VqfError("%s: roff must be a contiguous (%d,) int32 GPU tensor of row offsets" % (name, U + 1))
+    _chk_roff(name, roff, U)
     if idx is not None:
         _chk_group(name, N, U, idx=idx)
     if not glimpse_pool_grouped_supported(N, U, S, C, logits_or_wts_G):
@@ -1544,9 +1525,7 @@ def _guided_packed_operands(name, xh, gp, w, roff, N, S, grouped):
         raise _l.VqfError(name + ": xh must be (R, G*E) with R >= 1, gp (N, G*E) or None, w (G, E)")
     R = xh.shape[0]
     U = roff.shape[0] - 1 if grouped and torch.is_tensor(roff) else N
-    if not torch.is_tensor(roff) or not roff.is_cuda or roff.dtype != torch.int32 or not roff.is_contiguous() or \
-            tuple(roff.shape) != (U + 1,):
-        raise _l.VqfError("%s: roff must be a contiguous (%d,) int32 GPU tensor of row offsets" % (name, U + 1))
+    _chk_roff(name, roff, U)
     if not guided_logits_packed_supported(N, U, R, S, E, G):
         raise _l.VqfError(name + ": E %% 32 == 0, E <= 1024, 1 <= S <= 1024, G in {1, 2, 3}, N <= 65535, U <= 65535 and "
                           "1 <= R < 2^29 are supported (got N=%d, U=%d, R=%d, S=%d, E=%d, G=%d)" % (N, U, R, S, E, G))
