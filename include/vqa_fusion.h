@@ -480,6 +480,41 @@ int vqf_glimpse_pool_bwd_packed(const float* dpooled, const float* dwts_extra, c
                                 const int* roff, int N, int U, int R, int S, int C, int G, int unit_softmax, float* dlogits,
                                 void* stream);
 
+/* The co-attention head on the packed rows (MFB / MHBCoAtt with packed_coatt = True on a PackedRegions without img_index; additions
+ * within ABI 7; fp32, un-grouped): every tensor with one row per (image, region) between the fusion and the pooling holds the R real
+ * rows only -- sample n's row l < cnt is row start + l, (start, cnt) by the clamp above -- so nothing of N*L rows is allocated:
+ *   Rout / Y / dY (R, O), rowssq (4*R), rowdot (R), logits / lin / dlogits (R, G), rowinv (R).
+ * wts and dwts_extra stay (N, G, S) with exact zeros behind each count, keep stays (N*L, 5*O) and the Philox element index stays
+ * (n*L + l)*5*O + c: the masks, the walk over l and the order of every sum are those of the *_packed forms, whose padded tensors
+ * only add exact zeros, so every output has the bits of its *_packed sibling (row-wise outputs: of that sibling's real rows).
+ *   mfb_fuse_fwd_packed_rows / _bwd_packed_rows   the kernels of vqf_mfb_fuse_fwd_packed / _bwd_packed; error codes, supported
+ *             shapes and ws (vqf_mfb_fuse_bwd_ws_bytes(N, L, O)) as there.
+ *   l2_group_norm_packed   vqf_l2_group_norm over the sample's 4*cnt partials; also writes inv[n] to rowinv[start .. start + cnt - 1],
+ *             the per-row scale of vqf_gemm_f32_rowscale / vqf_att_logits_bwd_rowscale (rows_per_scale = 1) and vqf_scale_rows (L = 1).
+ *   l2_norm_bwd_coef_packed / _coef_lin_packed   vqf_l2_norm_bwd_coef / _coef_lin over the sample's rows.
+ *             One wave per sample, element i of a sample in lane i % 64, as in the padded forms.  Null or misaligned roff, N, R or
+ *             L <= 0: VQF_E_BADARG.
+ *   glimpse_pool_fwd_packed_rows / _bwd_packed_rows   vqf_glimpse_pool_fwd_packed / _bwd_packed reading logits / writing dlogits at the
+ *             packed rows; idx must be NULL (given: VQF_E_BADARG) and U = N; G = 1 or 2, the models' heads (G = 3:
+ *             VQF_E_UNSUPPORTED); other error codes as there. */
+int vqf_mfb_fuse_fwd_packed_rows(const float* P, const float* pbias, const float* q, const int* roff, const uint8_t* keep, uint64_t seed,
+                                 float p_drop, int N, int R, int L, int O, float* Rout, float* rowssq, void* stream);
+int vqf_mfb_fuse_bwd_packed_rows(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
+                                 const float* P, const float* pbias, const float* q, const int* roff, const uint8_t* keep, uint64_t seed,
+                                 float p_drop, int N, int R, int L, int O, float* dP, float* dq, float* dbiasP, void* ws,
+                                 size_t ws_bytes, void* stream);
+int vqf_l2_group_norm_packed(const float* rowssq, const int* roff, int N, int R, int L, float* norm, float* inv, float* rowinv,
+                             void* stream);
+int vqf_l2_norm_bwd_coef_packed(const float* rowdot, const int* roff, const float* norm, const float* inv, int N, int R, int L,
+                                float* coefA, float* coefB, void* stream);
+int vqf_l2_norm_bwd_coef_lin_packed(const float* dlogits, const float* lin, int G, const int* roff, const float* norm, const float* inv,
+                                    int N, int R, int L, float* coefA, float* coefB, float* unit, void* stream);
+int vqf_glimpse_pool_fwd_packed_rows(const float* feat, const float* logits, const int* idx, const int* roff, int N, int U, int R, int S,
+                                     int C, int G, int unit_softmax, float* wts, float* pooled, void* stream);
+int vqf_glimpse_pool_bwd_packed_rows(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
+                                     const int* roff, int N, int U, int R, int S, int C, int G, int unit_softmax, float* dlogits,
+                                     void* stream);
+
 
 /* --------------------------------------------------------------------------
  * Element-wise stages of HieCoAtten / AttentionNet.  n % 4 == 0, 16-byte aligned pointers.

@@ -228,13 +228,16 @@ __device__ __forceinline__ int pool_src(const int* __restrict__ idx, int n, int 
 // Sv = clamp(roff[u + 1] - roff[u], 1, min(S, Rtot - start)) rows from row start = clamp(roff[u], 0, Rtot - 1): whatever roff
 // holds, the rows read lie inside feat.  logits, wts and dlogits stay (N, S, .) padded; everything else is the lens form.
 // (Without PACK the kernels keep their own address expressions: their code is what it was before the flag.)
+// LPK (with PACK, idx NULL; vqf_glimpse_pool_fwd_packed_rows / _bwd_packed_rows): logits and dlogits are (Rtot, G) packed rows as
+// well -- position s < Sv of sample n is row start + s, and there is no row behind the count to read or to zero.  wts and
+// dwts_extra stay (N, G, S).
 __device__ __forceinline__ void pool_span(const int* __restrict__ roff, const int* __restrict__ idx, int n, int U, int S, int Rtot,
                                           long long& row0, int& Sv) {
   vqf_packed_span(roff, pool_src(idx, n, U), S, Rtot, row0, Sv);
 }
 
 // grid (ceil(C/1024), N); thread = 4 consecutive channels
-template <int G, typename FT, bool PACK = false>
+template <int G, typename FT, bool PACK = false, bool LPK = false>
 __global__ void glimpse_pool_fwd_kernel(const FT* __restrict__ feat,
                                         const float* __restrict__ logits, int N, int S, int C,
                                         int unit, float* __restrict__ wts,
@@ -248,7 +251,7 @@ __global__ void glimpse_pool_fwd_kernel(const FT* __restrict__ feat,
   if (PACK) pool_span(lens, idx, n, U, S, Rtot, row0, Sv); else Sv = pool_len(lens, n, S);
   if (wave < G) {
     const int g = wave;
-    const float* lg = logits + (long long)n * S * G + g;
+    const float* lg = LPK ? logits + row0 * G + g : logits + (long long)n * S * G + g;
     if (unit) {
       for (int s = lane; s < S; s += 64) w[g][s] = s < Sv ? 1.0f : 0.f;
     } else {
@@ -312,7 +315,7 @@ __global__ void glimpse_pool_fwd_kernel(const FT* __restrict__ feat,
 
 // block per sample; wave per position s (strided); then the softmax backward.
 // dwts_extra (N,G,S) or null: gradient arriving through the returned attention weights.
-template <int G, typename FT, bool PACK = false>
+template <int G, typename FT, bool PACK = false, bool LPK = false>
 __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
                                         const float* __restrict__ dwts_extra,
                                         const FT* __restrict__ feat,
@@ -410,10 +413,10 @@ __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
       for (int s = lane; s < Sv; s += 64) dot += ws[g][s] * dw[g][s];
       dot = wave_sum(dot);
     }
-    for (int s = lane; s < S; s += 64) {
+    for (int s = lane; s < (LPK ? Sv : S); s += 64) {
       // softmax over a singleton axis: y == 1 and dy - sum(dy*y) == 0 exactly
       const float d = (unit || s >= Sv) ? 0.f : ws[g][s] * (dw[g][s] - dot);
-      dlogits[((long long)n * S + s) * G + g] = d;
+      dlogits[((LPK ? row0 : (long long)n * S) + s) * G + g] = d;
     }
   }
 }
@@ -528,7 +531,7 @@ namespace {
 // CU, 8 KB in flight: 3.2 TB/s.  Here 1024 threads = RS row slots x C / 4 channel groups; slot rs sums rows rs, rs + RS, ... (two
 // rows per trip in flight), the slots are folded through LDS in slot order: deterministic, a different association than the
 // single chain of the wide kernel (same value to fp32 rounding).
-template <int G, typename FT, bool PACK = false>
+template <int G, typename FT, bool PACK = false, bool LPK = false>
 __global__ void __launch_bounds__(1024) glimpse_pool_fwd_rows_kernel(const FT* __restrict__ feat, const float* __restrict__ logits,
                                                                      int N, int S, int C, int unit, float* __restrict__ wts,
                                                                      float* __restrict__ pooled, const int* __restrict__ lens,
@@ -543,7 +546,7 @@ __global__ void __launch_bounds__(1024) glimpse_pool_fwd_rows_kernel(const FT* _
   if (PACK) pool_span(lens, idx, n, U, S, Rtot, row0, Sv); else Sv = pool_len(lens, n, S);
   if (wave < G) {
     const int g = wave;
-    const float* lg = logits + (long long)n * S * G + g;
+    const float* lg = LPK ? logits + row0 * G + g : logits + (long long)n * S * G + g;
     if (unit) {
       for (int s = lane; s < S; s += 64) w[g * S + s] = s < Sv ? 1.0f : 0.f;
     } else {
@@ -589,12 +592,13 @@ __global__ void __launch_bounds__(1024) glimpse_pool_fwd_rows_kernel(const FT* _
 }
 
 // PACK: lens is roff and feat (Rtot, C), see pool_span
-template <typename FT, bool PACK = false>
+template <typename FT, bool PACK = false, bool LPK = false>
 int glimpse_fwd_launch(const FT* feat, const float* logits, int N, int S, int C, int G, int unit_softmax,
                        float* wts, float* pooled, void* stream, const int* lens = nullptr, const int* idx = nullptr, int U = 0,
                        int Rtot = 0) {
   if (!feat || !logits || !pooled || N <= 0 || S <= 0 || C <= 0 || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
   if (S > MAXS || G < 1 || G > 3 || N > 65535) return VQF_E_UNSUPPORTED;
+  if (LPK && G == 3) return VQF_E_UNSUPPORTED;      // the packed-rows forms serve the two-glimpse heads: no G = 3 instantiation
   dim3 grid((C + 1023) / 1024, N);
   hipStream_t s = (hipStream_t)stream;
   {
@@ -605,37 +609,39 @@ int glimpse_fwd_launch(const FT* feat, const float* logits, int N, int S, int C,
       const int RS = 1024 / CT;
       const size_t lds = sizeof(float) * ((size_t)G * S + (size_t)RS * G * C);
       if (RS >= G && lds <= 64 * 1024) {
-        if (G == 3)
-          VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<3, FT, PACK>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
-                     unit_softmax, wts, pooled, lens, idx, U, Rtot);
-        else if (G == 2)
-          VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<2, FT, PACK>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
+        if (G == 3) {
+          if constexpr (!LPK)
+            VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<3, FT, PACK, LPK>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
+                       unit_softmax, wts, pooled, lens, idx, U, Rtot);
+        } else if (G == 2)
+          VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<2, FT, PACK, LPK>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
                      unit_softmax, wts, pooled, lens, idx, U, Rtot);
         else
-          VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<1, FT, PACK>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
+          VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<1, FT, PACK, LPK>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
                      unit_softmax, wts, pooled, lens, idx, U, Rtot);
         return vqf_last_error();
       }
     }
   }
-  if (G == 3)
-    VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<3, FT, PACK>), grid, dim3(256), 0, s, feat, logits, N, S,
-               C, unit_softmax, wts, pooled, lens, idx, U, Rtot);
-  else if (G == 2)
-    VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<2, FT, PACK>), grid, dim3(256), 0, s, feat, logits, N, S,
+  if (G == 3) {
+    if constexpr (!LPK)
+      VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<3, FT, PACK, LPK>), grid, dim3(256), 0, s, feat, logits, N, S,
+                 C, unit_softmax, wts, pooled, lens, idx, U, Rtot);
+  } else if (G == 2)
+    VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<2, FT, PACK, LPK>), grid, dim3(256), 0, s, feat, logits, N, S,
                C, unit_softmax, wts, pooled, lens, idx, U, Rtot);
   else
-    VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<1, FT, PACK>), grid, dim3(256), 0, s, feat, logits, N, S,
+    VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<1, FT, PACK, LPK>), grid, dim3(256), 0, s, feat, logits, N, S,
                C, unit_softmax, wts, pooled, lens, idx, U, Rtot);
   return vqf_last_error();
 }
 
-template <typename FT, bool PACK = false>
+template <typename FT, bool PACK = false, bool LPK = false>
 int glimpse_bwd_launch(const float* dpooled, const float* dwts_extra, const FT* feat, const float* wts, int N,
                        int S, int C, int G, int unit_softmax, float* dlogits, float* dfeat, void* stream,
                        const int* lens = nullptr, const int* idx = nullptr, int U = 0, int Rtot = 0) {
   if (!dpooled || !feat || !wts || !dlogits || N <= 0 || S <= 0 || C <= 0 || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
-  if (S > MAXS || G < 1 || G > 3) return VQF_E_UNSUPPORTED;
+  if (S > MAXS || G < 1 || G > 3 || (LPK && G == 3)) return VQF_E_UNSUPPORTED;      // (packed rows: G = 1, 2 only, as in the forward)
   hipStream_t s = (hipStream_t)stream;
   // one workgroup per sample.  A wave keeps ceil(C / 256) 16-byte loads per lane in flight (a row of the grid); about 64 such
   // loads per lane and CU stream best: 8 waves per CU at C = 2048 (the headline: 256 threads per sample, two samples per CU; few
@@ -651,14 +657,15 @@ int glimpse_bwd_launch(const float* dpooled, const float* dwts_extra, const FT* 
     if (want > waves) waves = want > 16 ? 16 : want;
   }
   const dim3 block(64 * waves);
-  if (G == 3)
-    VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<3, FT, PACK>), dim3(N), block, 0, s, dpooled,
-               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U, Rtot);
-  else if (G == 2)
-    VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<2, FT, PACK>), dim3(N), block, 0, s, dpooled,
+  if (G == 3) {
+    if constexpr (!LPK)
+      VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<3, FT, PACK, LPK>), dim3(N), block, 0, s, dpooled,
+                 dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U, Rtot);
+  } else if (G == 2)
+    VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<2, FT, PACK, LPK>), dim3(N), block, 0, s, dpooled,
                dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U, Rtot);
   else
-    VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<1, FT, PACK>), dim3(N), block, 0, s, dpooled,
+    VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<1, FT, PACK, LPK>), dim3(N), block, 0, s, dpooled,
                dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U, Rtot);
   return vqf_last_error();
 }
@@ -871,6 +878,25 @@ int vqf_glimpse_pool_bwd_packed(const float* dpooled, const float* dwts_extra, c
   if (rc) return rc;
   return glimpse_bwd_launch<float, true>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, nullptr, stream, roff,
                                          idx, U, R);
+}
+
+// ... with logits / dlogits (R, G) on the packed rows as well (the co-attention head on the real rows); idx must be NULL
+int vqf_glimpse_pool_fwd_packed_rows(const float* feat, const float* logits, const int* idx, const int* roff, int N, int U, int R, int S,
+                                     int C, int G, int unit_softmax, float* wts, float* pooled, void* stream) {
+  if (idx) return VQF_E_BADARG;
+  const int rc = packed_pool_args(idx, roff, N, U, R, S, C, G);
+  if (rc) return rc;
+  return glimpse_fwd_launch<float, true, true>(feat, logits, N, S, C, G, unit_softmax, wts, pooled, stream, roff, nullptr, U, R);
+}
+
+int vqf_glimpse_pool_bwd_packed_rows(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
+                                     const int* roff, int N, int U, int R, int S, int C, int G, int unit_softmax, float* dlogits,
+                                     void* stream) {
+  if (idx) return VQF_E_BADARG;
+  const int rc = packed_pool_args(idx, roff, N, U, R, S, C, G);
+  if (rc) return rc;
+  return glimpse_bwd_launch<float, true, true>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, nullptr, stream,
+                                               roff, nullptr, U, R);
 }
 
 // ... and with the gradient of the packed rows: dfeat (R, C) like feat.  Plain form (idx, order, grp_off NULL; U = N): the kernel

@@ -219,7 +219,11 @@ __device__ __forceinline__ void keep_scale20(const uint8_t* __restrict__ keep, u
 // `lens` holds the row offsets roff (owners + 1) instead of counts: the owner s (sample n, or image idx[n]) has its rows at
 // packed_span(roff, s) -- row l < Lv of the sample is P row start + l.  R, rowssq, keep / the Philox index stay in the padded
 // coordinates n L + l, so everything else is the LEN form.
-template <typename PT, int COAL, bool GRP = false, bool LEN = false, bool PACK = false>
+// PROWS (vqf_mfb_fuse_fwd_packed_rows; with PACK, un-grouped): R is (Rtot, O) and rowssq (4 Rtot) as well -- row l < Lv of the sample
+// stores R row start + l and its four partials there, and there is no padded row to zero.  keep / the Philox index stay at n L + l.
+// (The output row is spelled `PROWS ? prow : row` at each use: as a named value declared at the top of the row loop it changed the
+// VGPR counts of the instantiations that existed, 164 -> 160 and 166 -> 162 in the COAL = 0 forms.)
+template <typename PT, int COAL, bool GRP = false, bool LEN = false, bool PACK = false, bool PROWS = false>
 __global__ void __launch_bounds__(256)
 mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
                     const float* __restrict__ q,
@@ -294,7 +298,7 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
         const float rt = sqrtf(a);
         r[j] = s < 0.f ? -rt : rt;                 // sqrt(relu(s)) - sqrt(relu(-s))
       }
-      *reinterpret_cast<f32x4*>(R + row * O + TPT * tid) = r;
+      *reinterpret_cast<f32x4*>(R + (PROWS ? prow : row) * O + TPT * tid) = r;
       if (Rb) {
         __bf16 rb[4];
 #pragma unroll
@@ -309,16 +313,18 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
     if ((tid & 63) == 0) red[it & 1][tid >> 6] = ssq;
     __syncthreads();                               // red[] is double-buffered: one barrier per row
     if (tid == 0) {
-      rowssq[4 * row] = (red[it & 1][0] + red[it & 1][1]) + (red[it & 1][2] + red[it & 1][3]);
-      rowssq[4 * row + 1] = 0.f; rowssq[4 * row + 2] = 0.f; rowssq[4 * row + 3] = 0.f;
+      rowssq[4 * (PROWS ? prow : row)] = (red[it & 1][0] + red[it & 1][1]) + (red[it & 1][2] + red[it & 1][3]);
+      rowssq[4 * (PROWS ? prow : row) + 1] = 0.f;
+      rowssq[4 * (PROWS ? prow : row) + 2] = 0.f;
+      rowssq[4 * (PROWS ? prow : row) + 3] = 0.f;
     }
 #else
     // every wave leaves the sum of ITS quarter of the row: no workgroup barrier in the row loop, the four waves of a block drift
     // apart and cover each other's load latency; vqf_l2_group_norm adds the 4 L partials of a sample in a fixed order
-    if ((tid & 63) == 0) rowssq[4 * row + (tid >> 6)] = ssq;
+    if ((tid & 63) == 0) rowssq[4 * (PROWS ? prow : row) + (tid >> 6)] = ssq;
 #endif
   }
-  if (LEN) {
+  if (LEN && !PROWS) {
     // the padded rows of this block: nothing read, exact zeros through the stores of the walk (the LEN forms have no zdrop / Rb)
     for (; l < L; l += LS) {
       const long long row = (long long)n * L + l;
@@ -340,7 +346,9 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
 // zero dq / bias partials.
 // PACK (with LEN; `lens` = roff, as in the forward): P and dP are (Rtot, 5O); row l < Lv of the sample reads P row start + l and
 // (plain form) stores dP row start + l -- there is no padded dP row to zero.  dY / Y / the masks stay at n L + l.
-template <bool CASC, bool DBIAS, typename DPT, typename PT, bool COAL, bool GRP = false, bool LEN = false, bool PACK = false>
+// PROWS (vqf_mfb_fuse_bwd_packed_rows; with PACK, un-grouped): dY and Y are (Rtot, O) too, read at row start + l; the masks stay.
+template <bool CASC, bool DBIAS, typename DPT, typename PT, bool COAL, bool GRP = false, bool LEN = false, bool PACK = false,
+          bool PROWS = false>
 __global__ void __launch_bounds__(256)
 mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdrop,
                     const float* __restrict__ Y,
@@ -385,8 +393,8 @@ mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdr
         raw_to_own(rw, tl + wave * WLDS, lane, p);
       }
       if (act) {
-        const f32x4 dy = *reinterpret_cast<const f32x4*>(dY + row * O + TPT * t);
-        const f32x4 y = *reinterpret_cast<const f32x4*>(Y + row * O + TPT * t);
+        const f32x4 dy = *reinterpret_cast<const f32x4*>(dY + (PROWS ? prow : row) * O + TPT * t);
+        const f32x4 y = *reinterpret_cast<const f32x4*>(Y + (PROWS ? prow : row) * O + TPT * t);
         if (!COAL) load20(P + prow * W5 + CPT * t, p);
         if (pbias) {
 #pragma unroll
@@ -564,7 +572,8 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
                      void* dP, int dp_bf16, float* dq, float* dcascade, float* dbiasP, void* ws,
                      size_t ws_bytes, void* stream, const int* idx = nullptr, const int* order = nullptr,
                      const int* grp_off = nullptr, int U = 0, const int* lens = nullptr, const int* lens_u = nullptr,
-                     const int* roff = nullptr, int Rtot = 0) {
+                     const int* roff = nullptr, int Rtot = 0, bool prows = false) {
+  // prows (with roff, un-grouped): dY and Y are (Rtot, O) packed rows as well (vqf_mfb_fuse_bwd_packed_rows)
   // idx != nullptr: the grouped form (vqf_mfb_fuse_bwd_grouped, which has checked its own operands): P and dP are (U*L, 5O)
   // lens != nullptr: the region-count forms (fp32, no cascade / dzdrop; their entry points have checked lens): lens (N) per sample /
   // question, lens_u (U) per image in the grouped form
@@ -634,16 +643,16 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
     return rcg;
   }
   if (lens || roff) {
-#define VQF_BWDL(D_, CO_, PK_)                                                                                                       \
-  VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<false, D_, float, float, CO_, false, true, PK_>), grid, dim3(256), 0, s, dY,      \
+#define VQF_BWDL(D_, CO_, PK_, PR_)                                                                                                  \
+  VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<false, D_, float, float, CO_, false, true, PK_, PR_>), grid, dim3(256), 0, s, dY, \
              nullptr, Y, inv, coefA, coefB, (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, (float*)dP,     \
              dq_part, nullptr, db_part, nullptr, 0, PK_ ? roff : lens, Rtot)
-#define VQF_BWDL2(PK_)                                                                   \
-    do {                                                                                 \
-      if (dbiasP) { if (coal) VQF_BWDL(true, true, PK_); else VQF_BWDL(true, false, PK_); }   \
-      else        { if (coal) VQF_BWDL(false, true, PK_); else VQF_BWDL(false, false, PK_); } \
+#define VQF_BWDL2(PK_, PR_)                                                                        \
+    do {                                                                                           \
+      if (dbiasP) { if (coal) VQF_BWDL(true, true, PK_, PR_); else VQF_BWDL(true, false, PK_, PR_); }   \
+      else        { if (coal) VQF_BWDL(false, true, PK_, PR_); else VQF_BWDL(false, false, PK_, PR_); } \
     } while (0)
-    if (roff) VQF_BWDL2(true); else VQF_BWDL2(false);
+    if (roff && prows) VQF_BWDL2(true, true); else if (roff) VQF_BWDL2(true, false); else VQF_BWDL2(false, false);
 #undef VQF_BWDL2
 #undef VQF_BWDL
   }
@@ -669,7 +678,9 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
 static int fuse_fwd_impl(const void* P, int p_bf16, const float* pbias, const float* q, const float* cascade,
                          const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O, float* R,
                          float* rowssq, float* zdrop, void* stream, void* R_bf16 = nullptr, int ldrb = 0,
-                         const int* idx = nullptr, int U = 0, const int* lens = nullptr, const int* roff = nullptr, int Rtot = 0) {
+                         const int* idx = nullptr, int U = 0, const int* lens = nullptr, const int* roff = nullptr, int Rtot = 0,
+                         bool prows = false) {
+  // prows (with roff, un-grouped): R and rowssq hold the packed rows as well (vqf_mfb_fuse_fwd_packed_rows)
   // lens != nullptr: the region-count forms (fp32 P, no cascade / zdrop / R_bf16; their entry points have checked lens)
   // roff != nullptr: the packed forms (the same restrictions; P is (Rtot, 5O), roff (N + 1) or, with idx, (U + 1); lens is not used)
   if (!P || !q || !R || !rowssq || N <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
@@ -698,13 +709,18 @@ static int fuse_fwd_impl(const void* P, int p_bf16, const float* pbias, const fl
 #define VQF_FWDP(CO_, GRP_)                                                                                           \
   VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<float, CO_, GRP_, true, true>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream, \
              (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, nullptr, nullptr, 0, idx, U, roff, Rtot)
-  if (roff && idx) { if (nopf) VQF_FWDP(2, true); else if (coal) VQF_FWDP(1, true); else VQF_FWDP(0, true); }     // packed rows (fp32 only)
+#define VQF_FWDR(CO_)                                                                                                 \
+  VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<float, CO_, false, true, true, true>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream, \
+             (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, nullptr, nullptr, 0, nullptr, 0, roff, Rtot)
+  if (roff && prows) { if (nopf) VQF_FWDR(2); else if (coal) VQF_FWDR(1); else VQF_FWDR(0); }                     // packed rows in and out
+  else if (roff && idx) { if (nopf) VQF_FWDP(2, true); else if (coal) VQF_FWDP(1, true); else VQF_FWDP(0, true); }     // packed rows (fp32 only)
   else if (roff)   { if (nopf) VQF_FWDP(2, false); else if (coal) VQF_FWDP(1, false); else VQF_FWDP(0, false); }
   else if (lens && idx) { if (nopf) VQF_FWDL(2, true); else if (coal) VQF_FWDL(1, true); else VQF_FWDL(0, true); }     // region counts (fp32 only)
   else if (lens)   { if (nopf) VQF_FWDL(2, false); else if (coal) VQF_FWDL(1, false); else VQF_FWDL(0, false); }
   else if (idx) { if (nopf) VQF_FWDG(2); else if (coal) VQF_FWDG(1); else VQF_FWDG(0); }       // the grouped form (fp32 only)
   else if (p_bf16) { if (nopf) VQF_FWD(__bf16, 2); else if (coal) VQF_FWD(__bf16, 1); else VQF_FWD(__bf16, 0); }
   else        { if (nopf) VQF_FWD(float, 2); else if (coal) VQF_FWD(float, 1); else VQF_FWD(float, 0); }
+#undef VQF_FWDR
 #undef VQF_FWDP
 #undef VQF_FWDL
 #undef VQF_FWDG
@@ -835,6 +851,25 @@ int vqf_mfb_fuse_bwd_packed(const float* dY, const float* Y, const float* inv, c
   if (!vqf_mfb_fuse_packed_supported(N, N, R, L, O)) return VQF_E_UNSUPPORTED;
   return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
                        dbiasP, ws, ws_bytes, stream, nullptr, nullptr, nullptr, 0, nullptr, nullptr, roff, R);
+}
+
+// ... with the fusion's own rows packed too: Rout (R, O), rowssq (4 R), dY / Y (R, O) (the co-attention head on the real rows)
+int vqf_mfb_fuse_fwd_packed_rows(const float* P, const float* pbias, const float* q, const int* roff, const uint8_t* keep, uint64_t seed,
+                                 float p_drop, int N, int R, int L, int O, float* Rout, float* rowssq, void* stream) {
+  if (!grouped_index_ok(roff) || R <= 0 || N <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
+  if (!vqf_mfb_fuse_packed_supported(N, N, R, L, O)) return VQF_E_UNSUPPORTED;
+  return fuse_fwd_impl(P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, Rout, rowssq, nullptr, stream, nullptr, 0, nullptr, 0,
+                       nullptr, roff, R, true);
+}
+
+int vqf_mfb_fuse_bwd_packed_rows(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
+                                 const float* P, const float* pbias, const float* q, const int* roff, const uint8_t* keep, uint64_t seed,
+                                 float p_drop, int N, int R, int L, int O, float* dP, float* dq, float* dbiasP, void* ws,
+                                 size_t ws_bytes, void* stream) {
+  if (!grouped_index_ok(roff) || R <= 0 || N <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
+  if (!vqf_mfb_fuse_packed_supported(N, N, R, L, O)) return VQF_E_UNSUPPORTED;
+  return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
+                       dbiasP, ws, ws_bytes, stream, nullptr, nullptr, nullptr, 0, nullptr, nullptr, roff, R, true);
 }
 
 int vqf_mfb_fuse_fwd_grouped_packed(const float* P, const float* pbias, const float* q, const int* idx, const int* roff,

@@ -298,6 +298,68 @@ __global__ void l2_norm_bwd_coef_kernel(const float* __restrict__ rowdot,
   }
 }
 
+// The three reducers above for a fusion output that holds the packed rows only (vqf_mfb_fuse_fwd_packed_rows): sample n's rows
+// are start .. start + cnt - 1 by vqf_packed_span's rule.  One wave per sample, element i of the sample in lane i % 64 in ascending
+// order, as above: the padded forms add exact zeros behind the sample's real elements, so these sums are the same bits.
+__global__ void l2_group_norm_packed_kernel(const float* __restrict__ rowssq, const int* __restrict__ roff, int N, int Rtot, int L,
+                                            float* __restrict__ norm, float* __restrict__ inv, float* __restrict__ rowinv) {
+  const int n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (n >= N) return;
+  const int lane = threadIdx.x & 63;
+  long long start;
+  int cnt;
+  vqf_packed_span(roff, n, L, Rtot, start, cnt);
+  float a = 0.f;
+  for (int i = lane; i < 4 * cnt; i += 64) a += rowssq[4 * start + i];
+  a = wave_sum(a);
+  const float nr = sqrtf(a);
+  const float iv = 1.0f / fmaxf(nr, 1e-12f);
+  if (lane == 0) {
+    norm[n] = nr;
+    inv[n] = iv;
+  }
+  for (int l = lane; l < cnt; l += 64) rowinv[start + l] = iv;      // the per-row scale of the consumers (rows_per_scale = 1)
+}
+
+__global__ void l2_norm_bwd_coef_lin_packed_kernel(const float* __restrict__ dl, const float* __restrict__ lin, int G,
+                                                   const int* __restrict__ roff, const float* __restrict__ norm,
+                                                   const float* __restrict__ inv, int N, int Rtot, int L, float* __restrict__ coefA,
+                                                   float* __restrict__ coefB, float* __restrict__ unit) {
+  const int n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (n >= N) return;
+  const int lane = threadIdx.x & 63;
+  long long start;
+  int cnt;
+  vqf_packed_span(roff, n, L, Rtot, start, cnt);
+  float a = 0.f;
+  const long long base = start * G;
+  for (int i = lane; i < cnt * G; i += 64) a += dl[base + i] * lin[base + i];
+  a = wave_sum(a);
+  if (lane == 0) {
+    coefA[n] = 1.0f;
+    unit[n] = 1.0f;
+    coefB[n] = norm[n] > 1e-12f ? inv[n] * inv[n] * a : 0.f;
+  }
+}
+
+__global__ void l2_norm_bwd_coef_packed_kernel(const float* __restrict__ rowdot, const int* __restrict__ roff,
+                                               const float* __restrict__ norm, const float* __restrict__ inv, int N, int Rtot, int L,
+                                               float* __restrict__ coefA, float* __restrict__ coefB) {
+  const int n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (n >= N) return;
+  const int lane = threadIdx.x & 63;
+  long long start;
+  int cnt;
+  vqf_packed_span(roff, n, L, Rtot, start, cnt);
+  float a = 0.f;
+  for (int l = lane; l < cnt; l += 64) a += rowdot[start + l];
+  a = wave_sum(a);
+  if (lane == 0) {
+    coefA[n] = inv[n];
+    coefB[n] = norm[n] > 1e-12f ? inv[n] * a : 0.f;
+  }
+}
+
 }  // namespace
 
 // out[c] = sum_{j<J} in[j, c] with enough workgroups to be bandwidth-bound: rows are folded in
@@ -469,6 +531,37 @@ int vqf_l2_norm_bwd_coef_lin(const float* dlogits, const float* lin, int G, cons
   if (!dlogits || !lin || !norm || !inv || !coefA || !coefB || !unit || N <= 0 || L <= 0 || G <= 0) return VQF_E_BADARG;
   VQF_LAUNCH(KID_L2_BWD_COEF, l2_norm_bwd_coef_lin_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, dlogits,
              lin, G, norm, inv, N, L, coefA, coefB, unit);
+  return vqf_last_error();
+}
+
+// The packed-rows forms (include/vqa_fusion.h "The co-attention head on the packed rows"): rowssq (4 R), rowdot (R), dlogits / lin
+// (R, G) hold the real rows, roff (N + 1) int32 says whose (clamped by vqf_packed_span's rule where it is read).
+static bool packed_reduce_args(const int* roff, int N, int R, int L) {
+  return roff && (((uintptr_t)roff) & 3) == 0 && N > 0 && R > 0 && L > 0;
+}
+
+int vqf_l2_group_norm_packed(const float* rowssq, const int* roff, int N, int R, int L, float* norm, float* inv, float* rowinv,
+                             void* stream) {
+  if (!rowssq || !norm || !inv || !rowinv || !packed_reduce_args(roff, N, R, L)) return VQF_E_BADARG;
+  VQF_LAUNCH(KID_L2_GROUP_NORM, l2_group_norm_packed_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, rowssq, roff, N, R,
+             L, norm, inv, rowinv);
+  return vqf_last_error();
+}
+
+int vqf_l2_norm_bwd_coef_packed(const float* rowdot, const int* roff, const float* norm, const float* inv, int N, int R, int L,
+                                float* coefA, float* coefB, void* stream) {
+  if (!rowdot || !norm || !inv || !coefA || !coefB || !packed_reduce_args(roff, N, R, L)) return VQF_E_BADARG;
+  VQF_LAUNCH(KID_L2_BWD_COEF, l2_norm_bwd_coef_packed_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, rowdot, roff, norm,
+             inv, N, R, L, coefA, coefB);
+  return vqf_last_error();
+}
+
+int vqf_l2_norm_bwd_coef_lin_packed(const float* dlogits, const float* lin, int G, const int* roff, const float* norm, const float* inv,
+                                    int N, int R, int L, float* coefA, float* coefB, float* unit, void* stream) {
+  if (!dlogits || !lin || !norm || !inv || !coefA || !coefB || !unit || G <= 0 || !packed_reduce_args(roff, N, R, L))
+    return VQF_E_BADARG;
+  VQF_LAUNCH(KID_L2_BWD_COEF, l2_norm_bwd_coef_lin_packed_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, dlogits, lin,
+             G, roff, norm, inv, N, R, L, coefA, coefB, unit);
   return vqf_last_error();
 }
 

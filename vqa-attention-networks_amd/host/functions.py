@@ -77,7 +77,9 @@ class NormLink:
     conv GEMM (vqf_gemm_f32_rowscale), scales its stored hidden-layer gradient by it so that dW1 and the gradient it
     returns (dYs = dY / norm) need no further pass, and leaves (dlogits, lin) here, from which the producer's backward gets
     sum(Y * dY) per sample.  Saves the scale_rows pass (forward) and the rowdot pass (backward) over the (N*L, 1000)
-    tensors.  One link per forward call; only valid while the producer's output has exactly this one consumer."""
+    tensors.  One link per forward call; only valid while the producer's output has exactly this one consumer.
+    Where the producer's output holds the packed rows (RegionLayout.rows) the scale is per ROW: inv is rowinv (R,) -- 1/norm of each
+    row's sample, written by vqf_l2_group_norm_packed -- and L is 1; the consumer's calls do not change."""
     __slots__ = ("inv", "L", "lin", "xb")
 
     def __init__(self):
@@ -190,21 +192,28 @@ class JoinRowsFn(torch.autograd.Function):
 # tensor and takes the calls it always took.  Image tensors behind a layout other than the plain one are fp32.
 # ---------------------------------------------------------------------------------------------
 def _fuse_fwd(P, q, layout, N, L, O, link, **kw):
-    """The MFB fusion over the regions (ops.mfb_fuse_fwd / _grouped / _packed; kw: keep, seed, p_drop, pbias) -> (Y, norm, inv, rb):
-    with a link Y is R without 1/norm, and rb holds the bf16 copy of R a bf16 P's kernel wrote beside it."""
+    """The MFB fusion over the regions (ops.mfb_fuse_fwd / _grouped / _packed / _packed_rows; kw: keep, seed, p_drop, pbias)
+    -> (Y, norm, inv, rb, (scale, rows per scale)): with a link Y is R without 1/norm, rb holds the bf16 copy of R a bf16 P's kernel
+    wrote beside it, and the last pair is what the link's consumer scales Y's rows by -- (inv, L), or (rowinv, 1) where Y holds
+    the packed rows (layout.rows)."""
+    if layout is not None and layout.rows:
+        Y, norm, inv, rowinv = ops.mfb_fuse_fwd_packed_rows(P, q, layout.roff, N, L, O, normalise=link is None, **kw)
+        return Y, norm, inv, None, (rowinv, 1)
     if layout is not None and layout.packed:
-        return ops.mfb_fuse_fwd_packed(P, q, layout.roff, N, L, O, idx=layout.idx, normalise=link is None, **kw) + (None,)
+        return ops.mfb_fuse_fwd_packed(P, q, layout.roff, N, L, O, idx=layout.idx, normalise=link is None, **kw) + (None, None)
     if layout is not None and layout.grouped:
         return ops.mfb_fuse_fwd_grouped(P, q, layout.idx, N, layout.U, L, O, normalise=link is None,
-                                        lens=(layout.lens_q, layout.lens_u) if layout.counted else None, **kw) + (None,)
+                                        lens=(layout.lens_q, layout.lens_u) if layout.counted else None, **kw) + (None, None)
     rb = [] if (link is not None and P.dtype == torch.bfloat16) else None
     Y, norm, inv, _ = ops.mfb_fuse_fwd(P, q, N, L, O, normalise=link is None, r_bf16=rb,
                                        lens=None if layout is None else layout.lens_q, **kw)
-    return Y, norm, inv, rb
+    return Y, norm, inv, rb, None
 
 
 def _fuse_bwd(dY, Y, norm, inv, P, q, layout, N, L, O, dp_bf16=False, **kw):
     """-> (dP in P's layout -- summed per image where the images are shared --, dq, dbias); kw: keep, seed, p_drop, pbias, lin"""
+    if layout is not None and layout.rows:
+        return ops.mfb_fuse_bwd_packed_rows(dY, Y, norm, inv, P, q, layout.roff, N, L, O, want_dbias=True, **kw)
     if layout is not None and layout.packed:
         return ops.mfb_fuse_bwd_packed(dY, Y, norm, inv, P, q, layout.roff, N, L, O, grp=layout.grp, want_dbias=True, **kw)
     if layout is not None and layout.grouped:
@@ -233,6 +242,8 @@ def _pool_fwd(feat, logits, unit, layout):
         return ops.glimpse_pool_fwd(feat, logits, unit)
     if layout.grouped and unit:
         return None, ops.row_block_gather(_unit_sums(feat, logits.shape[1], layout)[1], layout.idx)
+    if layout.rows:                   # logits (R, G) on the packed rows
+        return ops.glimpse_pool_fwd_packed_rows(feat, logits, layout.roff, layout.N, layout.L, unit)
     if layout.packed:
         return ops.glimpse_pool_fwd_packed(feat, logits, layout.roff, layout.N, layout.L, unit, idx=layout.idx)
     if layout.grouped:
@@ -247,6 +258,10 @@ def _pool_bwd(dpooled, feat, wts, unit, need_dfeat, layout, dwts=None):
     if layout.grouped and unit:       # d(pooled)/d(logits) == 0 under unit weights: the exact zeros the unit kernel writes
         G = dpooled.shape[1] // feat.shape[-1]
         return torch.zeros((layout.N * layout.L, G), dtype=torch.float32, device=dpooled.device), None
+    if layout.rows and not need_dfeat:        # dlogits (R, G) on the packed rows
+        return ops.glimpse_pool_bwd_packed_rows(dpooled, feat, wts, layout.roff, unit, dwts=dwts), None
+    if layout.rows:
+        raise ops._l.VqfError("the co-attention head on the packed rows pools a feature tensor that is data (no dfeat)")
     if layout.packed and need_dfeat:
         return ops.glimpse_pool_bwd_packed_dfeat(dpooled, feat, wts, layout.roff, unit, grp=layout.grp, dwts=dwts)
     if layout.packed:
@@ -291,7 +306,9 @@ class AttHeadFn(torch.autograd.Function):
         question n pools the rows of image idx[n] (under unit_softmax the per-image region sums, gathered).  Region counts: the
         softmax runs over the first lens_q[n] positions (unit_softmax: weight 1 there), the weights beyond are exact zeros and so
         are their dlogits, so the MLP's backward adds nothing for padded rows.  Packed rows: feat is (R, C), the real rows of every
-        image, read through roff; x, the logits and the weights stay (N, L, .) padded.  (_pool_fwd / _pool_bwd pick the kernels.)
+        image, read through roff; x, the logits and the weights stay (N, L, .) padded.  Packed rows behind the fusion too
+        (layout.rows): x is (R, Cin), so the hidden layers, the logits and every gradient of the MLP are (R, .) -- the products run
+        with M (or K) = R --, and only the weights stay (N, G, L), exact zeros behind each count.  (_pool_fwd / _pool_bwd pick the kernels.)
     returns pooled (N, 2C); the attention weights (N,2,S) are kept on ctx.
     """
 
@@ -418,8 +435,8 @@ def _take_lin(link):
 def _fuse_node_fwd(ctx, P, pbias, q, keep, seed, p_drop, N, L, link, layout):
     """The forward MfbFuseFn and ImgFuseFn share behind the projection P: the fusion, the link, what the backward needs on ctx"""
     O = P.shape[1] // ops.POOL_K
-    Y, norm, inv, rb = _fuse_fwd(P, q, layout, N, L, O, link, keep=keep, seed=seed, p_drop=p_drop, pbias=pbias)
-    ctx.link = _arm_link(link, inv, L, rb)
+    Y, norm, inv, rb, scale = _fuse_fwd(P, q, layout, N, L, O, link, keep=keep, seed=seed, p_drop=p_drop, pbias=pbias)
+    ctx.link = _arm_link(link, *(scale or (inv, L)), rb)
     ctx.layout, ctx.seed, ctx.p_drop, ctx.dims = layout, seed, p_drop, (N, L, O)
     return Y, norm, inv
 
@@ -442,7 +459,8 @@ class ImgFuseFn(torch.autograd.Function):
     lens_q[n] real regions; the projection and its weight gradient still run over every row, the fusion reads no padded row of P
     and hands back exact zero dP rows there, so finite padding cancels in the weight gradient.  Packed rows: img is (1, R, D), the
     real rows of every image one after the other; the projection and its weight gradient run on the R real rows (P and dP are
-    (R, 5000)); Y stays (N*L, 1000) with exact zero rows beyond each count.  (_fuse_fwd / _fuse_bwd pick the kernels.)
+    (R, 5000)); Y stays (N*L, 1000) with exact zero rows beyond each count -- unless layout.rows, where Y and dY are (R, 1000) too.
+    (_fuse_fwd / _fuse_bwd pick the kernels.)
     """
 
     BF16_P = True      # bf16 mode: store P in bf16 when the large-tile GEMM applies (A/B switch)

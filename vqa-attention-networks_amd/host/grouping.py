@@ -63,7 +63,7 @@ def _region_lens(img_length, L, idx=None):
     return lens[idx.to(torch.int64)].contiguous(), lens
 
 
-class RegionLayout(collections.namedtuple("_RegionLayout", "N U L R idx order grp_off lens_u lens_q roff offsets grouped counted packed plain grp")):
+class RegionLayout(collections.namedtuple("_RegionLayout", "N U L R idx order grp_off lens_u lens_q roff offsets grouped counted packed plain grp rows")):
     """Where the image rows of a batch are: what forward(..., img_index), forward((img, img_length), ...) and
     forward(PackedRegions, ...) hand to the nodes, in one immutable object.  N questions, U images (U = N without img_index), L the
     padded width, R the rows of the image tensor (U * L unless packed).  idx / order / grp_off: _group_index's output, or None
@@ -72,7 +72,9 @@ class RegionLayout(collections.namedtuple("_RegionLayout", "N U L R idx order gr
     counts there: no lens), or None; offsets: the tensor roff was converted from, kept for padded().
     Views, so that no node tests two fields to find its form: grouped (questions share images), counted (region counts beside a
     padded tensor), packed (the image tensor holds the real rows only), plain (none of the three), grp = (idx, order, grp_off) or
-    None.  Every tensor is made on the device; nothing here reads a tensor's values on the host."""
+    None.  rows (packed only; see packed_rows()): what the fusion hands on -- its output, the co-attention head's hidden layers and
+    logits, and their gradients -- holds the R real rows as well.  Every tensor is made on the device; nothing here reads a tensor's
+    values on the host."""
     __slots__ = ()
 
     def __new__(cls, N, U, L, img_index=None, img_length=None, offsets=None, R=None):
@@ -85,10 +87,19 @@ class RegionLayout(collections.namedtuple("_RegionLayout", "N U L R idx order gr
         return cls._of(N, U, L, U * L if R is None else R, idx, order, grp_off, lens_u, lens_q, roff, offsets)
 
     @classmethod
-    def _of(cls, N, U, L, R, idx, order, grp_off, lens_u, lens_q, roff, offsets):
+    def _of(cls, N, U, L, R, idx, order, grp_off, lens_u, lens_q, roff, offsets, rows=False):
         grouped, counted, packed = idx is not None, lens_u is not None, roff is not None
         return tuple.__new__(cls, (N, U, L, R, idx, order, grp_off, lens_u, lens_q, roff, offsets, grouped, counted, packed,
-                                   not (grouped or counted or packed), (idx, order, grp_off) if grouped else None))
+                                   not (grouped or counted or packed), (idx, order, grp_off) if grouped else None,
+                                   bool(rows) and packed and not grouped))
+
+    def packed_rows(self):
+        """The same packed batch with the rows BEHIND the fusion packed too (MFB / MHBCoAtt packed_coatt): the fusion's output, the
+        co-attention head's tensors and their gradients are (R, .); the attention weights stay (N, G, L).  Only a packed layout
+        without shared images has that form; any other is returned as it is."""
+        if not self.packed or self.grouped or self.rows:
+            return self
+        return self._of(self.N, self.U, self.L, self.R, None, None, None, None, None, self.roff, self.offsets, True)
 
     def padded(self):
         """The same batch after its packed rows were laid out padded, (U*L, .): roff is dropped and the counts are those of the

@@ -179,6 +179,15 @@ SIGNATURES = {
                                               c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_p, c_sz, c_p]),
     "vqf_glimpse_pool_fwd_packed": (c_i, [c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
     "vqf_glimpse_pool_bwd_packed": (c_i, [c_f, c_f, c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
+    # the co-attention head on the packed rows (MFB / MHBCoAtt packed_coatt): R / Y / dY / rowssq / logits / dlogits hold the real rows
+    "vqf_mfb_fuse_fwd_packed_rows": (c_i, [c_f, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
+    "vqf_mfb_fuse_bwd_packed_rows": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float,
+                                           c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_p, c_sz, c_p]),
+    "vqf_l2_group_norm_packed": (c_i, [c_f, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_p]),
+    "vqf_l2_norm_bwd_coef_packed": (c_i, [c_f, c_p, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_p]),
+    "vqf_l2_norm_bwd_coef_lin_packed": (c_i, [c_f, c_f, c_i, c_p, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_p]),
+    "vqf_glimpse_pool_fwd_packed_rows": (c_i, [c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
+    "vqf_glimpse_pool_bwd_packed_rows": (c_i, [c_f, c_f, c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
     # the tanh / dropout pass as the packed <-> padded change of layout (HieCoAttenLadder.forward(PackedRegions, ...)): roff c_p
     "vqf_tanh_dropout_unpack_supported": (c_i, [c_i, c_i, c_i, c_i]),
     "vqf_tanh_dropout_unpack_fwd": (c_i, [c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_p]),

@@ -109,11 +109,20 @@ def region_layout(who, img_features, questions, img_index, is_data, limits, gemm
     return img, RegionLayout(N, U, L, img_index, img_length)
 
 
-def fusion_region_layout(who, img_features, questions, img_index, gemm_dtype):
+def fusion_region_layout(who, img_features, questions, img_index, gemm_dtype, packed_coatt=False):
     """MFB / MHBCoAtt's call of region_layout -> (img (U, L, D) or rows (R, D), the 3-D tensor the projection nodes flatten -- rows
-    as (1, R, D) --, L, the nodes' layout: None for the plain tensor, whose path takes nothing extra)."""
+    as (1, R, D) --, L, the nodes' layout: None for the plain tensor, whose path takes nothing extra).
+    packed_coatt (the models' attribute): a PackedRegions without img_index gets the layout whose rows BEHIND the fusion are packed
+    too (RegionLayout.packed_rows()); with img_index it is refused here, in front of every other check and of the first launch (a
+    question's rows would be those of its image, and their total is a shape that would have to be read on the host); for a plain
+    tensor or the pair (img, img_length) it changes nothing."""
+    if packed_coatt and img_index is not None and isinstance(img_features, PackedRegions):
+        raise VqfError("%s: packed_coatt = True does not take img_index (the co-attention head on the packed rows has one image per "
+                       "question); set packed_coatt = False for batches whose questions share images" % who)
     img, layout = region_layout(who, img_features, questions, img_index, lambda t: _image_is_data(t, gemm_dtype), _fusion_limits,
                                 gemm_dtype)
+    if packed_coatt:
+        layout = layout.packed_rows()
     return img, (img.unsqueeze(0) if layout.packed else img), layout.L, (None if layout.plain else layout)
 
 
@@ -280,6 +289,11 @@ class MFB(nn.Module):
         # scale pass nor the sum(Y * dY) pass of its backward runs (functions.NormLink).  fp32 co-attention, single hidden
         # layer only; False materialises fusion_normed as round 2 did
         self.fold_norm = True
+        # True: on a PackedRegions (without img_index) everything between the fusion and the pooling -- the fusion's output, co_att_conv1
+        # (and the multilayer conv) with their hidden layers and gradients, the logits -- holds the R real rows only; nothing of N*L
+        # rows is allocated.  Same parameters, same masks, the result of packed_coatt = False up to summation order inside the GEMMs.
+        # No effect on a plain tensor, on the pair (img, img_length) or in the pruned mode; refused together with img_index.
+        self.packed_coatt = False
         # overlap_streams = True only: the persistent image-projection GEMMs use at most this many CUs (a multiple of 8; 0 =
         # all), which leaves the others to the question-side kernels of the main stream (library option gemm_cu_limit)
         self.side_cu_limit = 0
@@ -338,8 +352,14 @@ class MFB(nn.Module):
         returns, moved to the GPU with .to(device): rows (R, D) fp32 are every image's real regions, one image after the other,
         never padded; offsets (N + 1,), or (U + 1,) per image with img_index, int64 / int32 on the questions' device; max_regions a
         Python int L in [1, 1024], at least the largest count (fp32 only).  The result is this model on (packed.unpack(), ...),
-        the region-count call; img_conv1d and its weight gradient run on the R real rows only."""
-        img_features, img3, L, layout = fusion_region_layout("MFB", img_features, questions, img_index, self.gemm_dtype)
+        the region-count call; img_conv1d and its weight gradient run on the R real rows only.
+        packed_coatt = True (an attribute, default False): with a PackedRegions and no img_index the co-attention head runs on the R
+        real rows as well -- the fusion's output, co_att_conv1's input, hidden layer and gradients, the logits -- and only the
+        attention weights keep their (N, 2, L) shape, exact zeros behind each count.  The result is still this model on
+        (packed.unpack(), ...), with the dropout masks of the default form.  Together with img_index it raises VqfError; for a plain
+        tensor, the pair (img, img_length) and the pruned mode it changes nothing."""
+        img_features, img3, L, layout = fusion_region_layout("MFB", img_features, questions, img_index, self.gemm_dtype,
+                                                             self.packed_coatt)
         bf16_img = self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
         bf16_all = self.gemm_dtype == "bf16-all"          # also ques_proj*, img_proj*, the question-attention conv
         # a5 starts first, on the side stream: it only needs the image and its weights

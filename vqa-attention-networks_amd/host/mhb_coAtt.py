@@ -42,6 +42,7 @@ class MHBCoAtt(nn.Module):
         self.overlap_streams = True       # img_conv1d on a side stream, see MFB.overlap_streams
         self.fuse_bf16_dp = True          # see MFB.fuse_bf16_dp
         self.fold_norm = True             # see MFB.fold_norm
+        self.packed_coatt = False         # see MFB.packed_coatt
         self.side_cu_limit = 0            # see MFB.side_cu_limit
         self.side_bf16 = False            # see MFB.side_bf16
         self._side = _SideStream()
@@ -58,8 +59,11 @@ class MHBCoAtt(nn.Module):
         the co-attention softmax run over each image's real regions.  The padded rows of img_features must be FINITE: the
         projection and its weight gradient still run over them, and they cancel only because their dP rows are exact zeros.
         Packed regions: see MFB.forward -- img_features may be a PackedRegions(rows, offsets, max_regions) (fp32 only): the real
-        regions of every image, never padded; the result is this model on (packed.unpack(), ...)."""
-        img_features, img3, L, layout = fusion_region_layout("MHBCoAtt", img_features, questions, img_index, self.gemm_dtype)
+        regions of every image, never padded; the result is this model on (packed.unpack(), ...).
+        packed_coatt = True (an attribute, default False): see MFB.forward -- with a PackedRegions and no img_index the co-attention
+        head runs on the R real rows as well; refused (VqfError) together with img_index, no effect on the other call forms."""
+        img_features, img3, L, layout = fusion_region_layout("MHBCoAtt", img_features, questions, img_index, self.gemm_dtype,
+                                                             self.packed_coatt)
         N = questions.shape[0]
         keep = self._seeds.keep
         bf16_img = self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")

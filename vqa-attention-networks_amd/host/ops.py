@@ -1511,6 +1511,122 @@ def glimpse_pool_bwd_packed_dfeat(dpooled, feat, wts, roff, unit_softmax, grp=No
     return dlogits, dfeat
 
 
+# the co-attention head on the packed rows (include/vqa_fusion.h "The co-attention head on the packed rows"; MFB / MHBCoAtt
+# packed_coatt): the fusion's output, its gradient, rowssq, the logits and their gradient hold the R real rows as well.  Un-grouped.
+def l2_group_norm_packed(rowssq, roff, N, R, L):
+    """rowssq (4*R) packed partials -> (norm (N), inv (N), rowinv (R) = inv of each row's owner)"""
+    _chk(rowssq)
+    _chk_roff("l2_group_norm_packed", roff, N)
+    if rowssq.numel() != 4 * R:
+        raise _l.VqfError("l2_group_norm_packed: rowssq must hold 4*R = %d partials, got %d" % (4 * R, rowssq.numel()))
+    dev = rowssq.device
+    norm = torch.empty(N, dtype=torch.float32, device=dev)
+    inv = torch.empty(N, dtype=torch.float32, device=dev)
+    rowinv = torch.empty(R, dtype=torch.float32, device=dev)
+    _l.check(_lib().vqf_l2_group_norm_packed(_ptr(rowssq), _ptr(roff), N, R, L, _ptr(norm), _ptr(inv), _ptr(rowinv), _stream()),
+             "vqf_l2_group_norm_packed")
+    return norm, inv, rowinv
+
+
+def l2_norm_bwd_coef_packed(rowdot, roff, norm, inv, N, L):
+    """rowdot (R) packed -> (coefA (N), coefB (N)) of vqf_l2_norm_bwd_coef"""
+    _chk(rowdot, norm, inv)
+    _chk_roff("l2_norm_bwd_coef_packed", roff, N)
+    if tuple(norm.shape) != (N,) or tuple(inv.shape) != (N,) or rowdot.dim() != 1:
+        raise _l.VqfError("l2_norm_bwd_coef_packed: rowdot must be (R,), norm and inv (N,)")
+    cA = torch.empty(N, dtype=torch.float32, device=rowdot.device)
+    cB = torch.empty(N, dtype=torch.float32, device=rowdot.device)
+    _l.check(_lib().vqf_l2_norm_bwd_coef_packed(_ptr(rowdot), _ptr(roff), _ptr(norm), _ptr(inv), N, rowdot.shape[0], L, _ptr(cA),
+                                                _ptr(cB), _stream()), "vqf_l2_norm_bwd_coef_packed")
+    return cA, cB
+
+
+def l2_norm_bwd_coef_lin_packed(dlogits, lin, roff, norm, inv, N, L):
+    """dlogits, lin (R, G) packed -> (coefA (N), coefB (N), unit (N)) of vqf_l2_norm_bwd_coef_lin"""
+    _chk(dlogits, lin, norm, inv)
+    _chk_roff("l2_norm_bwd_coef_lin_packed", roff, N)
+    if dlogits.dim() != 2 or dlogits.shape != lin.shape or tuple(norm.shape) != (N,) or tuple(inv.shape) != (N,):
+        raise _l.VqfError("l2_norm_bwd_coef_lin_packed: dlogits and lin must be (R, G), norm and inv (N,)")
+    dev = dlogits.device
+    cA = torch.empty(N, dtype=torch.float32, device=dev)
+    cB = torch.empty(N, dtype=torch.float32, device=dev)
+    unit = torch.empty(N, dtype=torch.float32, device=dev)
+    _l.check(_lib().vqf_l2_norm_bwd_coef_lin_packed(_ptr(dlogits), _ptr(lin), dlogits.shape[1], _ptr(roff), _ptr(norm), _ptr(inv), N,
+                                                    dlogits.shape[0], L, _ptr(cA), _ptr(cB), _ptr(unit), _stream()),
+             "vqf_l2_norm_bwd_coef_lin_packed")
+    return cA, cB, unit
+
+
+def mfb_fuse_fwd_packed_rows(P, q, roff, N, L, O, keep=None, seed=0, p_drop=0.0, pbias=None, normalise=True):
+    """mfb_fuse_fwd_packed with the output on the packed rows: P (R, 5*O), q (N, 5*O), roff (N + 1) int32; keep (N*L, 5*O) / the Philox
+    draw stay in the padded coordinates -> (Y (R, O), norm (N), inv (N), rowinv (R)): the real rows of mfb_fuse_fwd_packed's Y, bit
+    for bit; nothing of N*L rows is allocated.  rowinv[r] = inv of row r's sample (the consumers' per-row scale)."""
+    R = _packed_operands("mfb_fuse_fwd_packed_rows", P, q, roff, N, N, L, O, pbias)
+    dev = P.device
+    Y = torch.empty((R, O), dtype=torch.float32, device=dev)
+    rowssq = torch.empty(R * 4, dtype=torch.float32, device=dev)
+    _l.check(_lib().vqf_mfb_fuse_fwd_packed_rows(_ptr(P), _ptr(pbias), _ptr(q), _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop),
+                                                 N, R, L, O, _ptr(Y), _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_packed_rows")
+    norm, inv, rowinv = l2_group_norm_packed(rowssq, roff, N, R, L)
+    if normalise:
+        _l.check(_lib().vqf_scale_rows(_ptr(Y), _ptr(rowinv), R, 1, O, _ptr(Y), _stream()), "vqf_scale_rows")
+    return Y, norm, inv, rowinv
+
+
+def mfb_fuse_bwd_packed_rows(dY, Y, norm, inv, P, q, roff, N, L, O, keep=None, seed=0, p_drop=0.0, want_dbias=False, pbias=None,
+                             lin=None):
+    """mfb_fuse_bwd_packed with dY / Y (R, O) on the packed rows (and lin = (dlogits, lin) (R, G)) -> (dP (R, 5*O), dq (N, 5*O),
+    dbiasP or None)."""
+    R = _packed_operands("mfb_fuse_bwd_packed_rows", P, q, roff, N, N, L, O, pbias)
+    _chk(dY, Y, norm, inv)
+    if tuple(dY.shape) != (R, O) or tuple(Y.shape) != (R, O):
+        raise _l.VqfError("mfb_fuse_bwd_packed_rows: dY and Y must be (R, O) = (%d, %d)" % (R, O))
+    dev = P.device
+    if lin is not None:
+        cA, cB, inv = l2_norm_bwd_coef_lin_packed(lin[0], lin[1], roff, norm, inv, N, L)
+    else:
+        rowdot = torch.empty(R, dtype=torch.float32, device=dev)
+        _l.check(_lib().vqf_rowdot(_ptr(Y), _ptr(dY), R, O, _ptr(rowdot), _stream()), "vqf_rowdot")
+        cA, cB = l2_norm_bwd_coef_packed(rowdot, roff, norm, inv, N, L)
+    dP = torch.empty_like(P)
+    dq = torch.empty((N, POOL_K * O), dtype=torch.float32, device=dev)
+    db = torch.empty(POOL_K * O, dtype=torch.float32, device=dev) if want_dbias else None
+    ws = workspace(dev, _lib().vqf_mfb_fuse_bwd_ws_bytes(N, L, O))
+    _l.check(_lib().vqf_mfb_fuse_bwd_packed_rows(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
+                                                 _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop), N, R, L, O, _ptr(dP), _ptr(dq),
+                                                 _ptr(db), _ptr(ws), ws.numel(), _stream()), "vqf_mfb_fuse_bwd_packed_rows")
+    return dP, dq, db
+
+
+def glimpse_pool_fwd_packed_rows(feat, logits, roff, N, S, unit_softmax):
+    """glimpse_pool_fwd_packed with logits (R, G) on the packed rows -> wts (N, G, S) (exact zeros beyond the count), pooled (N, G*C)"""
+    _chk(logits)
+    G = logits.shape[1]
+    U, R, C = _pool_packed_dims("glimpse_pool_fwd_packed_rows", feat, roff, G, N, S, None)
+    if logits.shape[0] != R:
+        raise _l.VqfError("glimpse_pool_fwd_packed_rows: logits must be (R, G) = (%d, %d)" % (R, G))
+    wts = torch.empty((N, G, S), dtype=torch.float32, device=feat.device)
+    pooled = torch.empty((N, G * C), dtype=torch.float32, device=feat.device)
+    _l.check(_lib().vqf_glimpse_pool_fwd_packed_rows(_ptr(feat), _ptr(logits), None, _ptr(roff), N, U, R, S, C, G,
+                                                     int(bool(unit_softmax)), _ptr(wts), _ptr(pooled), _stream()),
+             "vqf_glimpse_pool_fwd_packed_rows")
+    return wts, pooled
+
+
+def glimpse_pool_bwd_packed_rows(dpooled, feat, wts, roff, unit_softmax, dwts=None):
+    """dpooled (N, G*C), feat (R, C) data, wts (N, G, S) -> dlogits (R, G) on the packed rows"""
+    _chk(dpooled, wts, dwts)
+    N, G, S = wts.shape
+    U, R, C = _pool_packed_dims("glimpse_pool_bwd_packed_rows", feat, roff, G, N, S, None)
+    if tuple(dpooled.shape) != (N, G * C) or (dwts is not None and tuple(dwts.shape) != (N, G, S)):
+        raise _l.VqfError("glimpse_pool_bwd_packed_rows: dpooled must be (N, G*C), wts and dwts (N, G, S)")
+    dlogits = torch.empty((R, G), dtype=torch.float32, device=feat.device)
+    _l.check(_lib().vqf_glimpse_pool_bwd_packed_rows(_ptr(dpooled), _ptr(dwts), _ptr(feat), _ptr(wts), None, _ptr(roff), N, U, R, S, C,
+                                                     G, int(bool(unit_softmax)), _ptr(dlogits), _stream()),
+             "vqf_glimpse_pool_bwd_packed_rows")
+    return dlogits
+
+
 # the packed forms of the guided attention logits: xh / dxh (R, G*E) hold the real rows only (include/vqa_fusion.h "The packed forms
 # of the alternating image side").  The kernels clamp what roff and the index arrays hold; only type, shape and device are checked here.
 def guided_logits_packed_supported(N, U, R, S, E, G):
