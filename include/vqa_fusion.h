@@ -980,6 +980,48 @@ int vqf_answer_match_rows(const float* logp, const float* target, int N, int A, 
 int vqf_topk_rows_supported(int W, int k);
 int vqf_topk_rows(const float* x, int R, int W, int ldx, int k, int mode, long long* idx, float* val, void* stream);
 
+/* --------------------------------------------------------------------------
+ * Binary cross-entropy with logits on soft answers, with the VQA score in its row pass (vqa_amd.BCEWithLogitsLoss; additions
+ * within ABI 7; fp32).  The criterion of models trained on detector-box features: every question carries the soft scores of its
+ * annotators (min(1, count / 3) on at most ten distinct answers); the number reported is the mean soft score of the predicted
+ * answer.  Two launches: one workgroup per row reads the logits row once, a single-workgroup finish adds the row results in a
+ * fixed order (no atomics).  With c = (float)scale (1 / (N A) for nn.BCEWithLogitsLoss()'s mean, 1 / N for the sum over answers
+ * and the mean over questions):
+ *   row loss  l_n = sum_a [ max(x, 0) - x t + log1p(exp(-|x|)) ]            (no overflow for either sign of x)
+ *   loss[0]   = c * sum_n l_n
+ *   dlogits   (N, A) = (sigma(x) - t) * c, sigma from exp(-|x|) (may be NULL)
+ *   pred[n]   (int64, may be NULL) = arg-max of logits[n, :] by the rules of the evaluation tail above (ties: lowest index;
+ *             a NaN first); a row holding a NaN has a NaN loss
+ *   score[n]  (may be NULL) = t[n, pred[n]]
+ *   rows[0] += N (int64); score_sum[0] += sum_n score[n] (double); loss_sum[0] += N * loss, formed as (N * scale) * the double
+ *             sum of the row losses; acc[0] = THIS call's mean score (fp32).  accumulate == 0 overwrites rows / score_sum /
+ *             loss_sum, != 0 adds to them, as in vqf_ce_loss_pred.  rows, score_sum, loss_sum, acc may be NULL.
+ * Only finite logits are specified (x = -inf with t = 0 gives NaN in torch's formula too).
+ *
+ * vqf_bce_loss         target (N, A) fp32.
+ * vqf_bce_loss_sparse  the target as K slots per row: ids (N, K) int64 (ids64 != 0) or int32, scores (N, K) fp32,
+ *                      1 <= K <= VQF_SOFT_MAX_SLOTS.  A slot whose id is negative or >= A is empty: its score is never used
+ *                      (it may be NaN) and nothing is written for it; the ids are only read on the device.  A repeated id adds
+ *                      its scores.  By definition the call on the dense tensor the slots stand for (zeros, then the live slots
+ *                      added); t is never formed: the row pass runs on a zero target, the live slots subtract s_k x[id_k] from
+ *                      the row loss and, after a workgroup barrier, the first slot of each live id rewrites its own element of
+ *                      the row as (sigma(x) - t) * c, t = that id's scores summed in slot order -- the dense expression, so
+ *                      distinct ids give the dense call's gradient bits; loss within rounding of the dense call's.
+ *                      score[n] = the sum, in slot order, of the scores of the live slots whose id == pred[n] (0 when none).
+ *                      Every store lands inside row n and is an ordinary vector store of that row's workgroup.
+ * ws: vqf_bce_loss_ws_bytes(N) bytes (8 per row; the query needs no GPU).  N < 1, A < 1, K outside 1..VQF_SOFT_MAX_SLOTS, a NULL
+ * logits / target / ids / scores / loss / ws: VQF_E_BADARG, a ws too small: VQF_E_WORKSPACE -- before any GPU call.
+ */
+#define VQF_SOFT_MAX_SLOTS 16
+size_t vqf_bce_loss_ws_bytes(int N);
+int vqf_bce_loss(const float* logits, const float* target, int N, int A, double scale, float* loss, float* dlogits,
+                 long long* pred, float* score, long long* rows, double* score_sum, double* loss_sum, float* acc,
+                 int accumulate, void* ws, size_t ws_bytes, void* stream);
+int vqf_bce_loss_sparse(const float* logits, const void* ids, int ids64, const float* scores, int K, int N, int A,
+                        double scale, float* loss, float* dlogits, long long* pred, float* score, long long* rows,
+                        double* score_sum, double* loss_sum, float* acc, int accumulate, void* ws, size_t ws_bytes,
+                        void* stream);
+
 /* torch.optim.Adam(model.parameters(), lr) of solver.py:29,93 (amsgrad off, maximize off), all
  * tensors of a step in as few launches as possible (VQF_ADAM_MAX_TENSORS per launch):
  *   g += wd*p;  m += (g-m)(1-b1);  v = v*b2 + (1-b2) g g;

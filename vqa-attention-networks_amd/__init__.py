@@ -30,6 +30,7 @@ def __getattr__(name):
         "pad_region_features": ".host.data_loader", "pack_region_features": ".host.data_loader",
         "RegionStager": ".host.data_loader", "stage_regions": ".host.data_loader", "pack_into": ".host.data_loader",
         "PackedRegions": ".host.grouping",
+        "BCEWithLogitsLoss": ".host.train_step", "SoftAnswers": ".host.grouping", "soft_answers": ".host.data_loader",
         "evaluate": ".host.evaluate", "loss_and_accuracy": ".host.evaluate", "Evaluator": ".host.evaluate",
         "predict": ".host.evaluate", "topk_answers": ".host.evaluate",
     }

@@ -73,6 +73,8 @@ enum VqfKernelId {
   KID_REGION_ROWS_STAGE,
   KID_TANH_DROP_PACKED_FWD,
   KID_TANH_DROP_PACKED_BWD,
+  KID_BCE_LOSS,
+  KID_BCE_LOSS_SPARSE,
   KID_COUNT
 };
 

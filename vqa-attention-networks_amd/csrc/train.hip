@@ -7,6 +7,9 @@
 //    with the solver's next lines (solver.py:96-101) riding in them: the row's arg-max, the hit count, the loss total.
 //  * KL divergence (nn.KLDivLoss(), default reduction: mean over all N*A elements):
 //    loss = mean(t * (log t - logp)) with 0 where t == 0; dlogp = -t / (N*A).
+//  * binary cross entropy with logits on soft answers (vqa_amd.BCEWithLogitsLoss; not in the reference, whose solver asserts
+//    hard labels for the models that return logits): one block per row, one read of the row -- row loss, dlogits, the row's
+//    arg-max and the soft score of the predicted answer; the target dense (N,A) or K sparse (id, score) slots per row.
 //  * Adam: m, v, p updated in place in the order of torch's single-tensor path; HBM-bound
 //    (16 B read + 12 B written per element).
 #include "common.h"
@@ -156,6 +159,132 @@ __global__ __launch_bounds__(TR_THREADS) void loss_finish_kernel(const float* __
   }
 }
 
+// ---- BCE with logits on soft answers (vqf_bce_loss / vqf_bce_loss_sparse) -----------------------------------------------
+// sigma(x) from e = exp(-|x|) in (0, 1]: no overflow on either sign
+__device__ __forceinline__ float bce_sigmoid(float x, float e) {
+  const float r = 1.f / (1.f + e);
+  return x >= 0.f ? r : e * r;
+}
+// the soft targets of a row as K (id, score) slots; a slot whose id is outside [0, A) is empty and its score is never used
+struct BceSlots {
+  const void* ids;       // (N, K) int32 or int64
+  const float* scores;   // (N, K)
+  int K, ids64;
+};
+__device__ __forceinline__ long long bce_slot_id(const BceSlots& sl, size_t i) {
+  return sl.ids64 ? ((const long long*)sl.ids)[i] : (long long)((const int*)sl.ids)[i];
+}
+
+// one block per row n, one read of the row: the row loss sum_a [max(x,0) - x t + log1p(exp(-|x|))], dlogits = (sigma(x) - t) c,
+// the arg-max (the key of ce_rows_kernel<true>) and score = t[pred].  SPARSE: the pass runs on a zero target; the live slots then
+// subtract s_k x[id_k] from the row loss (thread 0, slot order) and, after a workgroup barrier, the first slot of each live id
+// rewrites ITS element as (sigma(x) - t) c with t = the sum of that id's scores in slot order: the expression of the dense form,
+// so distinct ids give the dense gradient's bits.  Every such store lands inside row n (0 <= id < A), made by this workgroup.
+template <bool SPARSE>
+__global__ __launch_bounds__(TR_THREADS) void bce_rows_kernel(const float* __restrict__ logits,
+                                                              const float* __restrict__ target, const BceSlots sl, int A,
+                                                              float c, float* __restrict__ rowloss,
+                                                              float* __restrict__ rowscore, float* __restrict__ dlogits,
+                                                              long long* __restrict__ pred, float* __restrict__ score) {
+  __shared__ float sh[4];
+  __shared__ unsigned long long shk[4];
+  const int n = blockIdx.x;
+  const float* x = logits + (size_t)n * A;
+  const float* t = SPARSE ? nullptr : target + (size_t)n * A;
+  float* d = dlogits ? dlogits + (size_t)n * A : nullptr;
+  float s = 0.f;
+  unsigned long long best = 0ull;
+  for (int a = threadIdx.x; a < A; a += TR_THREADS) {
+    const float v = x[a];
+    const float e = expf(-fabsf(v));
+    const float ta = SPARSE ? 0.f : t[a];
+    s += (fmaxf(v, 0.f) - v * ta) + log1pf(e);
+    const unsigned long long key = vqf_argmax_key(v, a);
+    best = key > best ? key : best;
+    if (d) d[a] = (bce_sigmoid(v, e) - ta) * c;
+  }
+  s = block_sum(s, sh);
+  const int p = vqf_argmax_index(vqf_block256_max_u64(best, shk));
+  const size_t k0 = (size_t)n * (SPARSE ? sl.K : 0);
+  if (threadIdx.x == 0) {
+    float sc = 0.f;
+    if (SPARSE) {
+      float corr = 0.f;
+      for (int k = 0; k < sl.K; ++k) {
+        const long long id = bce_slot_id(sl, k0 + k);
+        if (id >= 0 && id < A) {
+          const float sk = sl.scores[k0 + k];
+          corr += sk * x[id];
+          if (id == p) sc += sk;
+        }
+      }
+      s -= corr;
+    } else {
+      sc = t[p];
+    }
+    rowloss[n] = s;
+    rowscore[n] = sc;
+    if (pred) pred[n] = p;
+    if (score) score[n] = sc;
+  }
+  if (SPARSE && d) {
+    __syncthreads();       // the row's sigma(x) c stores above are complete before a slot's element is rewritten
+    const int k = threadIdx.x;
+    if (k < sl.K) {
+      const long long id = bce_slot_id(sl, k0 + k);
+      if (id >= 0 && id < A) {
+        bool first = true;
+        float tk = 0.f;
+        for (int j = 0; j < sl.K; ++j) {
+          if (bce_slot_id(sl, k0 + j) == id) {
+            first = first && j >= k;
+            tk += sl.scores[k0 + j];
+          }
+        }
+        if (first) {
+          const float v = x[id];
+          d[id] = (bce_sigmoid(v, expf(-fabsf(v))) - tk) * c;
+        }
+      }
+    }
+  }
+}
+
+struct BceTotals {
+  long long* rows;       // [0] the rows of the call(s)
+  double* score_sum;     // sum of the rows' scores
+  double* loss_sum;      // N * loss, from the double row sum
+  float* acc;            // the mean score of THIS call
+  int accumulate;        // != 0: rows, score_sum and loss_sum are added to
+};
+
+// loss = c * sum(rowloss[0..N)) in the fixed order of loss_finish_kernel; the totals in double; every total may be NULL
+__global__ __launch_bounds__(TR_THREADS) void bce_finish_kernel(const float* __restrict__ rowloss,
+                                                                const float* __restrict__ rowscore, int N, float c,
+                                                                double row_weight, float* __restrict__ loss,
+                                                                const BceTotals tt) {
+  __shared__ float sh[4];
+  __shared__ double shd[4];
+  float s = 0.f;
+  double ds = 0.0, ss = 0.0;
+  for (int i = threadIdx.x; i < N; i += TR_THREADS) {
+    s += rowloss[i];
+    ds += (double)rowloss[i];
+    ss += (double)rowscore[i];
+  }
+  s = block_sum(s, sh);
+  ds = block_sum(ds, shd);
+  ss = block_sum(ss, shd);
+  if (threadIdx.x == 0) {
+    const bool acc = tt.accumulate != 0;
+    loss[0] = s * c;
+    if (tt.rows) tt.rows[0] = (acc ? tt.rows[0] : 0) + N;
+    if (tt.score_sum) tt.score_sum[0] = (acc ? tt.score_sum[0] : 0.0) + ss;
+    if (tt.loss_sum) tt.loss_sum[0] = (acc ? tt.loss_sum[0] : 0.0) + row_weight * ds;     // row_weight = N * c
+    if (tt.acc) tt.acc[0] = (float)(ss / (double)N);
+  }
+}
+
 // element-wise part of KLDivLoss; each block reduces a contiguous chunk into part[blockIdx.x]
 constexpr int KL_PER_BLOCK = TR_THREADS * 16;
 __global__ __launch_bounds__(TR_THREADS) void kldiv_kernel(const float* __restrict__ logp,
@@ -297,6 +426,47 @@ int vqf_kldiv_loss(const float* logp, const float* target, int N, int A, float* 
   hipLaunchKernelGGL(loss_finish_kernel<false>, dim3(1), dim3(TR_THREADS), 0, s, (const float*)part, (int)parts, inv_n,
                      (const long long*)nullptr, 0, loss, LossTotals{});
   return vqf_last_error();
+}
+
+size_t vqf_bce_loss_ws_bytes(int N) { return N > 0 ? (size_t)N * 2 * sizeof(float) : 0; }
+
+static int bce_loss_launch(bool sparse, const float* logits, const float* target, const BceSlots& sl, int N, int A,
+                           double scale, float* loss, float* dlogits, long long* pred, float* score, long long* rows,
+                           double* score_sum, double* loss_sum, float* acc, int accumulate, void* ws, size_t ws_bytes,
+                           void* stream) {
+  if (N <= 0 || A <= 0) return VQF_E_BADARG;
+  if (sparse ? (!sl.ids || !sl.scores || sl.K < 1 || sl.K > VQF_SOFT_MAX_SLOTS) : !target) return VQF_E_BADARG;
+  if (!logits || !loss || !ws) return VQF_E_BADARG;
+  if (ws_bytes < vqf_bce_loss_ws_bytes(N)) return VQF_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  float* rowloss = (float*)ws;
+  float* rowscore = rowloss + N;
+  const float c = (float)scale;
+  vqf_prof_dims(N, A, sparse ? sl.K : 0);
+  if (sparse)
+    VQF_LAUNCH(KID_BCE_LOSS_SPARSE, bce_rows_kernel<true>, dim3(N), dim3(TR_THREADS), 0, s, logits, target, sl, A, c, rowloss,
+               rowscore, dlogits, pred, score);
+  else
+    VQF_LAUNCH(KID_BCE_LOSS, bce_rows_kernel<false>, dim3(N), dim3(TR_THREADS), 0, s, logits, target, sl, A, c, rowloss,
+               rowscore, dlogits, pred, score);
+  hipLaunchKernelGGL(bce_finish_kernel, dim3(1), dim3(TR_THREADS), 0, s, (const float*)rowloss, (const float*)rowscore, N, c,
+                     (double)N * scale, loss, BceTotals{rows, score_sum, loss_sum, acc, accumulate});
+  return vqf_last_error();
+}
+
+int vqf_bce_loss(const float* logits, const float* target, int N, int A, double scale, float* loss, float* dlogits,
+                 long long* pred, float* score, long long* rows, double* score_sum, double* loss_sum, float* acc,
+                 int accumulate, void* ws, size_t ws_bytes, void* stream) {
+  return bce_loss_launch(false, logits, target, BceSlots{nullptr, nullptr, 0, 0}, N, A, scale, loss, dlogits, pred, score, rows,
+                         score_sum, loss_sum, acc, accumulate, ws, ws_bytes, stream);
+}
+
+int vqf_bce_loss_sparse(const float* logits, const void* ids, int ids64, const float* scores, int K, int N, int A,
+                        double scale, float* loss, float* dlogits, long long* pred, float* score, long long* rows,
+                        double* score_sum, double* loss_sum, float* acc, int accumulate, void* ws, size_t ws_bytes,
+                        void* stream) {
+  return bce_loss_launch(true, logits, nullptr, BceSlots{ids, scores, K, ids64 != 0}, N, A, scale, loss, dlogits, pred, score,
+                         rows, score_sum, loss_sum, acc, accumulate, ws, ws_bytes, stream);
 }
 
 int vqf_adam_step(const VqfAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,

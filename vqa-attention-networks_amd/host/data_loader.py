@@ -29,7 +29,7 @@ import torch
 
 from . import ops
 from .lib import VqfError
-from .grouping import PackedRegions
+from .grouping import PackedRegions, SoftAnswers, SOFT_MAX_SLOTS
 
 
 class FeatureStager:
@@ -174,6 +174,27 @@ def pack_region_features(features, multiple=1):
     offsets[1:] = torch.cumsum(torch.tensor([a.shape[0] for a in arrs], dtype=torch.int64), 0)
     rows = torch.from_numpy(np.ascontiguousarray(np.concatenate(arrs, 0)))
     return PackedRegions(rows, offsets, Lmax)
+
+
+def soft_answers(answer_dicts, slots=10):
+    """The host half of a soft-answer batch (BCEWithLogitsLoss(logits, SoftAnswers)): answer_dicts = one {answer_id: score} dict
+    per question, the `answers` entry the reference's loader reads (data_loader.py:40-42; keys str or int, as there) -> a CPU
+    SoftAnswers with ids (N, slots) int64 and scores (N, slots) float32, each dict's entries in its own order, unused slots
+    id -1 / score 0.  An empty list, a dict with more than `slots` entries or slots outside 1..16: ValueError."""
+    if isinstance(slots, bool) or not isinstance(slots, int) or not 1 <= slots <= SOFT_MAX_SLOTS:
+        raise ValueError("soft_answers: slots must be an int in [1, %d], got %r" % (SOFT_MAX_SLOTS, slots))
+    dicts = list(answer_dicts)
+    if not dicts:
+        raise ValueError("soft_answers: an empty list")
+    ids = np.full((len(dicts), slots), -1, dtype=np.int64)
+    scores = np.zeros((len(dicts), slots), dtype=np.float32)
+    for n, d in enumerate(dicts):
+        if len(d) > slots:
+            raise ValueError("soft_answers: question %d has %d answers, more than the %d slots" % (n, len(d), slots))
+        for k, (a, v) in enumerate(d.items()):
+            ids[n, k] = int(a)
+            scores[n, k] = v
+    return SoftAnswers(torch.from_numpy(ids), torch.from_numpy(scores))
 
 
 def _region_shapes(name, features):

@@ -13,7 +13,7 @@ import torch
 
 from . import ops
 from .lib import VqfError
-from .train_step import CrossEntropyLoss, KLDivLoss, _KlDivLossFn, _times
+from .train_step import BCEWithLogitsLoss, CrossEntropyLoss, KLDivLoss, _KlDivLossFn, _bce_scale, _bce_target, _times
 
 
 class _CeLossPredFn(torch.autograd.Function):
@@ -34,13 +34,38 @@ class _CeLossPredFn(torch.autograd.Function):
         return _times(d, g), None
 
 
+class _BceLossPredFn(torch.autograd.Function):
+    """_BceLossFn of train_step.py (the same loss and gradient bits) that also returns the prediction and the mean soft score"""
+
+    @staticmethod
+    def forward(ctx, logits, target, per_row):
+        want_grad = logits.requires_grad      # of the incoming tensor, as in _BceLossFn
+        logits = logits.contiguous()
+        acc = torch.empty(1, dtype=torch.float32, device=logits.device)
+        loss, d, pred, _ = ops.bce_logits_loss(logits, _bce_target(target), _bce_scale(logits, per_row), want_grad=want_grad,
+                                               acc=acc)
+        ctx.save_for_backward(d)
+        acc = acc.view(())
+        ctx.mark_non_differentiable(pred, acc)
+        return loss.view(()), pred, acc
+
+    @staticmethod
+    def backward(ctx, g, _gpred, _gacc):
+        (d,) = ctx.saved_tensors
+        return _times(d, g), None, None
+
+
 def loss_and_accuracy(criterion, logits, a):
     """solver.py:91 and :96-101 in one call -> (loss, pred, acc).
 
     loss: the differentiable scalar `criterion(logits, a)` gives (same bits, same gradient bits); pred (N,) int64; acc a
     0-dim fp32 GPU tensor, hits / counted rows (rows with target -100 do not count; no counted row: NaN, like the mean of an
-    empty tensor).  pred and acc are not differentiable.  `criterion` is this package's CrossEntropyLoss (a (N,) int64) or
-    KLDivLoss (a (N, A) soft targets, compared through a.max(1)[1] as solver.py:100 does); anything else raises."""
+    empty tensor).  pred and acc are not differentiable.  `criterion` is this package's CrossEntropyLoss (a (N,) int64),
+    KLDivLoss (a (N, A) soft targets, compared through a.max(1)[1] as solver.py:100 does) or BCEWithLogitsLoss (a (N, A) soft
+    scores or a SoftAnswers; acc is then the mean soft score a[n, pred[n]] of the predicted answers, the VQA accuracy, from
+    the loss kernel's own row pass); anything else raises."""
+    if isinstance(criterion, BCEWithLogitsLoss):
+        return _BceLossPredFn.apply(logits, a, criterion.reduction == "batchmean")
     if isinstance(criterion, CrossEntropyLoss):
         return _CeLossPredFn.apply(logits, a)
     if isinstance(criterion, KLDivLoss):
@@ -48,8 +73,8 @@ def loss_and_accuracy(criterion, logits, a):
         acc = torch.empty(1, dtype=torch.float32, device=logits.device)
         pred, _, _ = ops.answer_match_rows(logits.detach().contiguous(), a.contiguous(), want_score=False, acc=acc)
         return loss, pred, acc.view(())
-    raise VqfError("loss_and_accuracy: criterion must be vqa_amd.CrossEntropyLoss or vqa_amd.KLDivLoss, got %s "
-                   "(there is no torch route)" % type(criterion).__name__)
+    raise VqfError("loss_and_accuracy: criterion must be vqa_amd.CrossEntropyLoss, vqa_amd.KLDivLoss or "
+                   "vqa_amd.BCEWithLogitsLoss, got %s (there is no torch route)" % type(criterion).__name__)
 
 
 class Evaluator:
@@ -67,14 +92,28 @@ class Evaluator:
     rows a short last batch does not have; here the divisor is the rows actually seen (with the cross-entropy criterion: the
     rows whose target is not -100).  loss_mean weights every batch by its rows.
     The totals are three device scalars (hits and rows as int64, sums as float64) per process; summing them over the ranks of a
-    multi-GPU run (one all-reduce of the buffer) is left to the caller."""
+    multi-GPU run (one all-reduce of the buffer) is left to the caller.
+
+    With BCEWithLogitsLoss (a: (N, A) soft scores or a SoftAnswers) update() is ONE call of the loss kernel, and result() ->
+    {"rows", "vqa_score": the mean soft score of the predicted answers, "accuracy": the same number (one key for every
+    criterion), "loss_mean", "loss_last"}; there is no "correct": a soft score is not a hit count.  Its totals live in a buffer
+    of their own (rows int64 | score sum, loss sum float64 | last loss fp32)."""
 
     def __init__(self, criterion):
-        if not isinstance(criterion, (CrossEntropyLoss, KLDivLoss)):
-            raise VqfError("Evaluator: criterion must be vqa_amd.CrossEntropyLoss or vqa_amd.KLDivLoss, got %s "
-                           "(there is no torch route)" % type(criterion).__name__)
+        if not isinstance(criterion, (CrossEntropyLoss, KLDivLoss, BCEWithLogitsLoss)):
+            raise VqfError("Evaluator: criterion must be vqa_amd.CrossEntropyLoss, vqa_amd.KLDivLoss or "
+                           "vqa_amd.BCEWithLogitsLoss, got %s (there is no torch route)" % type(criterion).__name__)
         self.soft = isinstance(criterion, KLDivLoss)
+        self.bce = isinstance(criterion, BCEWithLogitsLoss)
+        self._per_row = self.bce and criterion.reduction == "batchmean"
         self._buf = None
+
+    def _bce_views(self, device):
+        # four 8-byte slots: rows (int64) | score sum, loss sum (float64) | last loss (fp32)
+        if self._buf is None or self._buf.device != device:
+            self._buf = torch.zeros(4, dtype=torch.int64, device=device)
+        b = self._buf
+        return b[0:1], b[1:2].view(torch.float64), b[2:3].view(torch.float64), b[3:4].view(torch.float32)[0:1]
 
     def _views(self, device):
         # one buffer of five 8-byte slots: hits, rows (int64) | loss sum, score sum (float64) | last loss (fp32)
@@ -85,8 +124,15 @@ class Evaluator:
 
     @torch.no_grad()
     def update(self, logits, a):
-        counts, loss_sum, score_sum, last = self._views(logits.device)
         logits = logits.detach().contiguous()
+        if self.bce:
+            ops._chk(logits)       # a CPU tensor is refused before the totals are placed on its device
+            scale = _bce_scale(logits, self._per_row)
+            rows, score_sum, loss_sum, last = self._bce_views(logits.device)
+            ops.bce_logits_loss(logits, _bce_target(a), scale, want_grad=False, want_pred=False, rows=rows, score_sum=score_sum,
+                                loss_sum=loss_sum, accumulate=True, loss_out=last)
+            return
+        counts, loss_sum, score_sum, last = self._views(logits.device)
         if self.soft:
             a = a.contiguous()
             ops.kldiv_loss(logits, a, want_grad=False, loss_out=last)
@@ -101,6 +147,13 @@ class Evaluator:
             self._buf.zero_()
 
     def result(self):
+        if self.bce:
+            h = self._buf.cpu() if self._buf is not None else torch.zeros(4, dtype=torch.int64)
+            rows, nan = int(h[0]), float("nan")
+            score = float(h[1:2].view(torch.float64)[0]) / rows if rows else nan
+            return {"rows": rows, "vqa_score": score, "accuracy": score,
+                    "loss_mean": float(h[2:3].view(torch.float64)[0]) / rows if rows else nan,
+                    "loss_last": float(h[3:4].view(torch.float32)[0]) if rows else nan}
         h = self._buf.cpu() if self._buf is not None else torch.zeros(5, dtype=torch.int64)
         correct, rows = int(h[0]), int(h[1])
         nan = float("nan")

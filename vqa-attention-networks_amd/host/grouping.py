@@ -165,3 +165,55 @@ def check_packed_regions(who, packed, owners, device):
         raise VqfError("%s: PackedRegions.offsets must be on the questions' device (%s), got %s" % (who, device, off.device))
     if isinstance(L, bool) or not isinstance(L, int) or not 1 <= L <= 1024:
         raise VqfError("%s: PackedRegions.max_regions must be a Python int in [1, 1024], got %r" % (who, L))
+
+
+SOFT_MAX_SLOTS = 16      # VQF_SOFT_MAX_SLOTS of include/vqa_fusion.h
+
+
+class SoftAnswers:
+    """Sparse soft targets of BCEWithLogitsLoss / ops.bce_logits_loss: ids (N, K) int64 / int32, scores (N, K) fp32, 1 <= K <= 16.
+    Row n holds K (answer id, soft score) slots; a slot whose id is negative or >= A (the logits' width) is empty and its score is
+    ignored; a repeated id adds its scores.  Every call with a SoftAnswers is, by definition, the call with .dense(A).
+    data_loader.soft_answers builds one on the CPU; .to(device) moves both tensors.  The ids are never read on the host."""
+    __slots__ = ("ids", "scores")
+
+    def __init__(self, ids, scores):
+        self.ids, self.scores = ids, scores
+
+    def to(self, device, non_blocking=False):
+        return SoftAnswers(self.ids.to(device, non_blocking=non_blocking), self.scores.to(device, non_blocking=non_blocking))
+
+    def dense(self, A):
+        """-> the (N, A) fp32 tensor the slots stand for, on the tensors' device: zeros, then the live slots added."""
+        check_soft_answers("SoftAnswers.dense", self)
+        A = int(A)
+        ids = self.ids.to(torch.int64)
+        N, K = ids.shape
+        live = (ids >= 0) & (ids < A)
+        rows = torch.arange(N, device=ids.device).unsqueeze(1).expand(N, K)
+        t = torch.zeros((N, A), dtype=torch.float32, device=ids.device)
+        t.index_put_((rows[live], ids[live]), self.scores[live], accumulate=True)
+        return t
+
+
+def check_soft_answers(who, soft, N=None, device=None):
+    """The refusals that concern the SoftAnswers itself: ids an int64 / int32 (N, K) tensor, scores an fp32 tensor of the same
+    shape on the same device, 1 <= K <= 16; with N / device given, that many rows on that device.  Raises VqfError."""
+    ids, sc = soft.ids, soft.scores
+    if not torch.is_tensor(ids) or ids.dtype not in (torch.int64, torch.int32) or ids.dim() != 2:
+        raise VqfError("%s: SoftAnswers.ids must be a 2-D int64 or int32 tensor (N, K), got %s"
+                       % (who, "%s %s" % (ids.dtype, tuple(ids.shape)) if torch.is_tensor(ids) else type(ids).__name__))
+    if not torch.is_tensor(sc) or sc.dtype != torch.float32:
+        raise VqfError("%s: SoftAnswers.scores must be an fp32 tensor, got %s"
+                       % (who, sc.dtype if torch.is_tensor(sc) else type(sc).__name__))
+    if sc.shape != ids.shape:
+        raise VqfError("%s: SoftAnswers.ids and .scores must have the same shape, got %s and %s"
+                       % (who, tuple(ids.shape), tuple(sc.shape)))
+    if not 1 <= ids.shape[1] <= SOFT_MAX_SLOTS:
+        raise VqfError("%s: SoftAnswers holds 1 to %d slots per row, got K = %d" % (who, SOFT_MAX_SLOTS, ids.shape[1]))
+    if sc.device != ids.device:
+        raise VqfError("%s: SoftAnswers.ids and .scores must be on one device, got %s and %s" % (who, ids.device, sc.device))
+    if N is not None and ids.shape[0] != N:
+        raise VqfError("%s: SoftAnswers must have one row per logits row (%d), got %d" % (who, N, ids.shape[0]))
+    if device is not None and ids.device != device:
+        raise VqfError("%s: SoftAnswers must be on the logits' device (%s), got %s" % (who, device, ids.device))

@@ -228,6 +228,11 @@ SIGNATURES = {
     "vqf_answer_match_rows": (c_i, [c_f, c_f, c_i, c_i, c_p, c_p, c_f, c_p, c_p, c_f, c_p, c_f, c_i, c_p, c_sz, c_p]),
     "vqf_topk_rows_supported": (c_i, [c_i, c_i]),
     "vqf_topk_rows": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_p, c_f, c_p]),
+    # BCE with logits on soft answers (csrc/train.hip): scale a double, rows int64, sums double, all device pointers
+    "vqf_bce_loss_ws_bytes": (c_sz, [c_i]),
+    "vqf_bce_loss": (c_i, [c_f, c_f, c_i, c_i, ctypes.c_double, c_f, c_f, c_p, c_f, c_p, c_p, c_p, c_f, c_i, c_p, c_sz, c_p]),
+    "vqf_bce_loss_sparse": (c_i, [c_f, c_p, c_i, c_f, c_i, c_i, c_i, ctypes.c_double, c_f, c_f, c_p, c_f, c_p, c_p, c_p, c_f,
+                                  c_i, c_p, c_sz, c_p]),
     "vqf_adam_step": (c_i, [c_p, c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                             ctypes.c_double, ctypes.c_longlong, c_p]),
     "vqf_hbm_copy": (c_i, [c_p, c_p, ctypes.c_longlong, c_i, c_p]),

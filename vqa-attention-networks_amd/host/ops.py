@@ -9,6 +9,7 @@ import math
 import torch
 
 from . import lib as _l
+from .grouping import SoftAnswers, check_soft_answers
 
 GEMM_RELU = 1
 GEMM_ACCUM = 2
@@ -1918,8 +1919,8 @@ def ce_loss(logits, target, want_grad=True):
 
 
 def _chk_totals(name, dev, accumulate, **bufs):
-    """the device totals of the evaluation tail: counts (2,) int64, sums (1,) float64, acc / loss (1,) float32"""
-    want = {"counts": (torch.int64, 2), "loss_sum": (torch.float64, 1), "score_sum": (torch.float64, 1),
+    """the device totals of the evaluation tail: counts (2,) / rows (1,) int64, sums (1,) float64, acc / loss (1,) float32"""
+    want = {"counts": (torch.int64, 2), "rows": (torch.int64, 1), "loss_sum": (torch.float64, 1), "score_sum": (torch.float64, 1),
             "acc": (torch.float32, 1), "loss": (torch.float32, 1), "loss_out": (torch.float32, 1)}
     for k, t in bufs.items():
         if t is None:
@@ -1975,6 +1976,47 @@ def answer_match_rows(logp, target, want_score=True, counts=None, score_sum=None
                                           _ptr(counts), _ptr(score_sum), _ptr(loss), _ptr(loss_sum), _ptr(acc), acc_flag,
                                           _ptr(ws), nb, _stream()), "vqf_answer_match_rows")
     return pred, tpred, score
+
+
+def bce_logits_loss(logits, target, scale, want_grad=True, want_pred=True, rows=None, score_sum=None, loss_sum=None, acc=None,
+                    accumulate=False, loss_out=None):
+    """-> (loss (1,), dlogits | None, pred (N,) int64 | None, score (N,) fp32 | None): binary cross-entropy with logits on soft
+    answers, loss = scale * the sum over all elements of max(x,0) - x t + log1p(exp(-|x|)), dlogits = (sigmoid(x) - t) * scale,
+    with the row arg-max and score = t[n, pred[n]] from the same row pass.  target: (N, A) fp32, or a SoftAnswers (by
+    definition the call on target.dense(A); the dense tensor is never formed).  rows (1,) int64 = N, score_sum (1,) float64 =
+    the sum of score, loss_sum (1,) float64 = N * loss: written, or added to when `accumulate`; acc (1,) fp32 = this call's
+    mean score."""
+    _chk(logits)
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise _l.VqfError("bce_logits_loss: non-empty logits (N,A) expected")
+    N, A = logits.shape
+    sparse = isinstance(target, SoftAnswers)
+    if sparse:
+        check_soft_answers("bce_logits_loss", target, N, logits.device)
+        ids, scores = target.ids.contiguous(), target.scores.contiguous()
+    else:
+        if not torch.is_tensor(target):
+            raise _l.VqfError("bce_logits_loss: target must be a (N,A) fp32 tensor or a SoftAnswers, got %s"
+                              % type(target).__name__)
+        _chk(target)
+        if target.shape != logits.shape or target.device != logits.device:
+            raise _l.VqfError("bce_logits_loss: logits and targets of the same (N,A) shape on one device expected")
+    acc_flag = _chk_totals("bce_logits_loss", logits.device, accumulate, rows=rows, score_sum=score_sum, loss_sum=loss_sum,
+                           acc=acc, loss_out=loss_out)
+    loss = loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=logits.device)
+    d = torch.empty_like(logits) if want_grad else None
+    pred = torch.empty(N, dtype=torch.int64, device=logits.device) if want_pred else None
+    score = torch.empty(N, dtype=torch.float32, device=logits.device) if want_pred else None
+    nb = int(_lib().vqf_bce_loss_ws_bytes(N))
+    ws = workspace(logits.device, nb)
+    tail = (float(scale), _ptr(loss), _ptr(d), _ptr(pred), _ptr(score), _ptr(rows), _ptr(score_sum), _ptr(loss_sum), _ptr(acc),
+            acc_flag, _ptr(ws), nb, _stream())
+    if sparse:
+        _l.check(_lib().vqf_bce_loss_sparse(_ptr(logits), _ptr(ids), 1 if ids.dtype == torch.int64 else 0, _ptr(scores),
+                                            ids.shape[1], N, A, *tail), "vqf_bce_loss_sparse")
+    else:
+        _l.check(_lib().vqf_bce_loss(_ptr(logits), _ptr(target), N, A, *tail), "vqf_bce_loss")
+    return loss, d, pred, score
 
 
 def topk_rows_supported(W, k):

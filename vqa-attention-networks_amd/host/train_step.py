@@ -11,6 +11,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .lib import VqfError
 
 
 def _times(d, g):
@@ -60,6 +61,52 @@ class KLDivLoss(nn.Module):
 
     def forward(self, logp, target):
         return _KlDivLossFn.apply(logp, target)
+
+
+class _BceLossFn(torch.autograd.Function):
+    """target: a (N, A) fp32 tensor or a SoftAnswers (not a tensor: autograd passes it through); never differentiated"""
+
+    @staticmethod
+    def forward(ctx, logits, target, per_row):
+        want_grad = logits.requires_grad      # of the incoming tensor: grad mode is off here, a contiguous copy would say False
+        logits = logits.contiguous()
+        loss, d, _, _ = ops.bce_logits_loss(logits, _bce_target(target), _bce_scale(logits, per_row), want_grad=want_grad,
+                                            want_pred=False)
+        ctx.save_for_backward(d)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (d,) = ctx.saved_tensors
+        return _times(d, g), None, None
+
+
+def _bce_target(target):
+    """a dense target is made contiguous, as _KlDivLossFn does; a SoftAnswers goes through as it is"""
+    return target.contiguous() if torch.is_tensor(target) else target
+
+
+def _bce_scale(logits, per_row):
+    """c of the criterion: 1 / N ("batchmean") or 1 / (N A) ("mean"), formed in double"""
+    if logits.dim() != 2 or logits.numel() < 1:
+        raise VqfError("BCEWithLogitsLoss: non-empty logits (N,A) expected")
+    return 1.0 / (logits.shape[0] if per_row else logits.numel())
+
+
+class BCEWithLogitsLoss(nn.Module):
+    """Binary cross-entropy with logits on soft answers, the criterion of models trained on detector-box features.
+    reduction "mean": nn.BCEWithLogitsLoss()'s default, the mean over all N*A elements; "batchmean": the sum over answers and
+    the mean over questions.  No weight, pos_weight or other reduction.  forward(logits (N,A) fp32, target) -> scalar, target
+    a (N,A) fp32 tensor of soft scores or a SoftAnswers (by definition the call on target.dense(A))."""
+
+    def __init__(self, reduction="mean"):
+        super().__init__()
+        if reduction not in ("mean", "batchmean"):
+            raise ValueError("BCEWithLogitsLoss: reduction must be 'mean' or 'batchmean', got %r" % (reduction,))
+        self.reduction = reduction
+
+    def forward(self, logits, target):
+        return _BceLossFn.apply(logits, target, self.reduction == "batchmean")
 
 
 def criterion_for(model_name):
