@@ -591,14 +591,26 @@ __global__ void __launch_bounds__(1024) glimpse_pool_fwd_rows_kernel(const FT* _
   }
 }
 
-// PACK: lens is roff and feat (Rtot, C), see pool_span
-template <typename FT, bool PACK = false, bool LPK = false>
+// FT, the layout (VqfRegions, common.h; host side only) and G -> the instantiation, for the three pooling kernels:
+// f(G, PACK, LPK) as compile-time constants.  The packed forms are fp32 only; the packed-rows forms (LPK) serve the two-glimpse
+// heads: no G = 3 instantiation (the launchers refuse it).
+template <typename FT, typename F>
+void glimpse_dispatch(int G, const VqfRegions& rg, F&& f) {
+  if constexpr (std::is_same<FT, float>::value) {
+    if (rg.packed() && rg.rows) return vqf_dispatch_G<false>(G, [&](auto g) { f(g, std::true_type(), std::true_type()); });
+    if (rg.packed()) return vqf_dispatch_G(G, [&](auto g) { f(g, std::true_type(), std::false_type()); });
+  }
+  vqf_dispatch_G(G, [&](auto g) { f(g, std::false_type(), std::false_type()); });
+}
+
+// rg: idx / U (sample n pools image idx[n]), lens (counts) or roff / Rtot (packed: feat (Rtot, C), see pool_span), rows (LPK)
+template <typename FT>
 int glimpse_fwd_launch(const FT* feat, const float* logits, int N, int S, int C, int G, int unit_softmax,
-                       float* wts, float* pooled, void* stream, const int* lens = nullptr, const int* idx = nullptr, int U = 0,
-                       int Rtot = 0) {
-  if (!feat || !logits || !pooled || N <= 0 || S <= 0 || C <= 0 || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
+                       float* wts, float* pooled, void* stream, const VqfRegions& rg) {
+  const int* lens = rg.walk();
+  if (!feat || !logits || !pooled || N <= 0 || S <= 0 || C <= 0 || !VqfRegions::aligned(lens)) return VQF_E_BADARG;
   if (S > MAXS || G < 1 || G > 3 || N > 65535) return VQF_E_UNSUPPORTED;
-  if (LPK && G == 3) return VQF_E_UNSUPPORTED;      // the packed-rows forms serve the two-glimpse heads: no G = 3 instantiation
+  if (rg.rows && G == 3) return VQF_E_UNSUPPORTED;
   dim3 grid((C + 1023) / 1024, N);
   hipStream_t s = (hipStream_t)stream;
   {
@@ -609,39 +621,27 @@ int glimpse_fwd_launch(const FT* feat, const float* logits, int N, int S, int C,
       const int RS = 1024 / CT;
       const size_t lds = sizeof(float) * ((size_t)G * S + (size_t)RS * G * C);
       if (RS >= G && lds <= 64 * 1024) {
-        if (G == 3) {
-          if constexpr (!LPK)
-            VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<3, FT, PACK, LPK>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
-                       unit_softmax, wts, pooled, lens, idx, U, Rtot);
-        } else if (G == 2)
-          VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<2, FT, PACK, LPK>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
-                     unit_softmax, wts, pooled, lens, idx, U, Rtot);
-        else
-          VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<1, FT, PACK, LPK>), dim3(N), dim3(1024), lds, s, feat, logits, N, S, C,
-                     unit_softmax, wts, pooled, lens, idx, U, Rtot);
+        glimpse_dispatch<FT>(G, rg, [&](auto g, auto pack, auto lpk) {
+          VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_rows_kernel<decltype(g)::value, FT, decltype(pack)::value, decltype(lpk)::value>),
+                     dim3(N), dim3(1024), lds, s, feat, logits, N, S, C, unit_softmax, wts, pooled, lens, rg.idx, rg.U, rg.Rtot);
+        });
         return vqf_last_error();
       }
     }
   }
-  if (G == 3) {
-    if constexpr (!LPK)
-      VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<3, FT, PACK, LPK>), grid, dim3(256), 0, s, feat, logits, N, S,
-                 C, unit_softmax, wts, pooled, lens, idx, U, Rtot);
-  } else if (G == 2)
-    VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<2, FT, PACK, LPK>), grid, dim3(256), 0, s, feat, logits, N, S,
-               C, unit_softmax, wts, pooled, lens, idx, U, Rtot);
-  else
-    VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<1, FT, PACK, LPK>), grid, dim3(256), 0, s, feat, logits, N, S,
-               C, unit_softmax, wts, pooled, lens, idx, U, Rtot);
+  glimpse_dispatch<FT>(G, rg, [&](auto g, auto pack, auto lpk) {
+    VQF_LAUNCH(KID_GLIMPSE_FWD, (glimpse_pool_fwd_kernel<decltype(g)::value, FT, decltype(pack)::value, decltype(lpk)::value>), grid,
+               dim3(256), 0, s, feat, logits, N, S, C, unit_softmax, wts, pooled, lens, rg.idx, rg.U, rg.Rtot);
+  });
   return vqf_last_error();
 }
 
-template <typename FT, bool PACK = false, bool LPK = false>
+template <typename FT>
 int glimpse_bwd_launch(const float* dpooled, const float* dwts_extra, const FT* feat, const float* wts, int N,
-                       int S, int C, int G, int unit_softmax, float* dlogits, float* dfeat, void* stream,
-                       const int* lens = nullptr, const int* idx = nullptr, int U = 0, int Rtot = 0) {
-  if (!dpooled || !feat || !wts || !dlogits || N <= 0 || S <= 0 || C <= 0 || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
-  if (S > MAXS || G < 1 || G > 3 || (LPK && G == 3)) return VQF_E_UNSUPPORTED;      // (packed rows: G = 1, 2 only, as in the forward)
+                       int S, int C, int G, int unit_softmax, float* dlogits, float* dfeat, void* stream, const VqfRegions& rg) {
+  const int* lens = rg.walk();
+  if (!dpooled || !feat || !wts || !dlogits || N <= 0 || S <= 0 || C <= 0 || !VqfRegions::aligned(lens)) return VQF_E_BADARG;
+  if (S > MAXS || G < 1 || G > 3 || (rg.rows && G == 3)) return VQF_E_UNSUPPORTED;  // (packed rows: G = 1, 2 only, as in the forward)
   hipStream_t s = (hipStream_t)stream;
   // one workgroup per sample.  A wave keeps ceil(C / 256) 16-byte loads per lane in flight (a row of the grid); about 64 such
   // loads per lane and CU stream best: 8 waves per CU at C = 2048 (the headline: 256 threads per sample, two samples per CU; few
@@ -657,16 +657,10 @@ int glimpse_bwd_launch(const float* dpooled, const float* dwts_extra, const FT* 
     if (want > waves) waves = want > 16 ? 16 : want;
   }
   const dim3 block(64 * waves);
-  if (G == 3) {
-    if constexpr (!LPK)
-      VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<3, FT, PACK, LPK>), dim3(N), block, 0, s, dpooled,
-                 dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U, Rtot);
-  } else if (G == 2)
-    VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<2, FT, PACK, LPK>), dim3(N), block, 0, s, dpooled,
-               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U, Rtot);
-  else
-    VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<1, FT, PACK, LPK>), dim3(N), block, 0, s, dpooled,
-               dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, idx, U, Rtot);
+  glimpse_dispatch<FT>(G, rg, [&](auto g, auto pack, auto lpk) {
+    VQF_LAUNCH(KID_GLIMPSE_BWD, (glimpse_pool_bwd_kernel<decltype(g)::value, FT, decltype(pack)::value, decltype(lpk)::value>), dim3(N),
+               block, 0, s, dpooled, dwts_extra, feat, wts, N, S, C, unit_softmax, dlogits, dfeat, lens, rg.idx, rg.U, rg.Rtot);
+  });
   return vqf_last_error();
 }
 
@@ -758,44 +752,56 @@ __global__ void __launch_bounds__(256) row_block_group_sum_kernel(const f32x4* _
     out[(long long)u * blk4 + i] = acc;
   }
 }
+
+// the per-image half of the grouped backwards: dfeat[u] = the sum over the image's questions, in rg.order; packed: dfeat (Rtot, C)
+int glimpse_dfeat_grouped_launch(const float* dpooled, const float* wts, int N, int S, int C, int G, float* dfeat, void* stream,
+                                 const VqfRegions& rg) {
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((S + GP_ROWS - 1) / GP_ROWS, rg.U), block(C / 4 >= 256 ? 256 : ((C / 4 + 63) / 64) * 64);
+  auto go = [&](auto g, auto pack) {
+    VQF_LAUNCH(KID_GLIMPSE_DFEAT_GROUPED, (glimpse_dfeat_grouped_kernel<decltype(g)::value, decltype(pack)::value>), grid, block, 0, s,
+               dpooled, wts, rg.order, rg.grp_off, N, S, C, dfeat, rg.roff, rg.Rtot);
+  };
+  vqf_dispatch_G(G, [&](auto g) { if (rg.packed()) go(g, std::true_type()); else go(g, std::false_type()); });
+  return vqf_last_error();
+}
 }  // namespace
 
 extern "C" {
 
 int vqf_glimpse_pool_fwd(const float* feat, const float* logits, int N, int S, int C, int G,
                          int unit_softmax, float* wts, float* pooled, void* stream) {
-  return glimpse_fwd_launch<float>(feat, logits, N, S, C, G, unit_softmax, wts, pooled, stream);
+  return glimpse_fwd_launch<float>(feat, logits, N, S, C, G, unit_softmax, wts, pooled, stream, {});
 }
 
 int vqf_glimpse_pool_fwd_bf16(const void* feat, const float* logits, int N, int S, int C, int G,
                               int unit_softmax, float* wts, float* pooled, void* stream) {
-  return glimpse_fwd_launch<__bf16>((const __bf16*)feat, logits, N, S, C, G, unit_softmax, wts, pooled, stream);
+  return glimpse_fwd_launch<__bf16>((const __bf16*)feat, logits, N, S, C, G, unit_softmax, wts, pooled, stream, {});
 }
 
 int vqf_glimpse_pool_bwd(const float* dpooled, const float* dwts_extra, const float* feat,
                          const float* wts, int N, int S, int C, int G, int unit_softmax,
                          float* dlogits, float* dfeat, void* stream) {
-  return glimpse_bwd_launch<float>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, dfeat,
-                                   stream);
+  return glimpse_bwd_launch<float>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, dfeat, stream, {});
 }
 
 int vqf_glimpse_pool_fwd_len(const float* feat, const float* logits, const int* lens, int N, int S, int C, int G,
                              int unit_softmax, float* wts, float* pooled, void* stream) {
   if (!lens) return VQF_E_BADARG;
-  return glimpse_fwd_launch<float>(feat, logits, N, S, C, G, unit_softmax, wts, pooled, stream, lens);
+  return glimpse_fwd_launch<float>(feat, logits, N, S, C, G, unit_softmax, wts, pooled, stream, {.lens = lens});
 }
 
 int vqf_glimpse_pool_bwd_len(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* lens,
                              int N, int S, int C, int G, int unit_softmax, float* dlogits, float* dfeat, void* stream) {
   if (!lens) return VQF_E_BADARG;
-  return glimpse_bwd_launch<float>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, dfeat, stream, lens);
+  return glimpse_bwd_launch<float>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, dfeat, stream, {.lens = lens});
 }
 
 int vqf_glimpse_pool_bwd_bf16(const float* dpooled, const float* dwts_extra, const void* feat,
                               const float* wts, int N, int S, int C, int G, int unit_softmax,
                               float* dlogits, void* stream) {
   return glimpse_bwd_launch<__bf16>(dpooled, dwts_extra, (const __bf16*)feat, wts, N, S, C, G, unit_softmax,
-                                    dlogits, nullptr, stream);
+                                    dlogits, nullptr, stream, {});
 }
 
 int vqf_glimpse_pool_grouped_supported(int N, int U, int S, int C, int G) {
@@ -804,99 +810,85 @@ int vqf_glimpse_pool_grouped_supported(int N, int U, int S, int C, int G) {
 
 int vqf_glimpse_pool_fwd_grouped(const float* feat, const float* logits, const int* idx, int N, int U, int S, int C, int G,
                                  float* wts, float* pooled, void* stream) {
-  if (!idx || (((uintptr_t)idx) & 3) || N <= 0 || U <= 0 || S <= 0 || C <= 0) return VQF_E_BADARG;
+  if (!VqfRegions::ok(idx) || N <= 0 || U <= 0 || S <= 0 || C <= 0) return VQF_E_BADARG;
   if (!vqf_glimpse_pool_grouped_supported(N, U, S, C, G)) return VQF_E_UNSUPPORTED;
-  return glimpse_fwd_launch<float>(feat, logits, N, S, C, G, 0, wts, pooled, stream, nullptr, idx, U);
-}
-
-// lens (vqf_glimpse_pool_bwd_grouped_len; N int32 per QUESTION, null: all S): the softmax backward runs over the real regions; the
-// per-image half needs nothing -- it sums wts, which are exact zeros on padding
-static int glimpse_bwd_grouped(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
-                               const int* order, const int* grp_off, const int* lens, int N, int U, int S, int C, int G,
-                               float* dlogits, float* dfeat, void* stream) {
-  if (!idx || !order || !grp_off || ((((uintptr_t)idx) | ((uintptr_t)order) | ((uintptr_t)grp_off)) & 3) || N <= 0 || U <= 0 ||
-      S <= 0 || C <= 0)
-    return VQF_E_BADARG;
-  if (!vqf_glimpse_pool_grouped_supported(N, U, S, C, G)) return VQF_E_UNSUPPORTED;
-  if (!aligned16(dpooled) || !aligned16(dfeat)) return VQF_E_ALIGN;
-  // the per-question half (dlogits: feat[idx[n]] . dpooled[n], then the softmax backward) on the kernel of the plain form ...
-  int rc = glimpse_bwd_launch<float>(dpooled, dwts_extra, feat, wts, N, S, C, G, 0, dlogits, nullptr, stream, lens, idx, U);
-  if (rc || !dfeat) return rc;
-  // ... and the per-image half: dfeat[u] = the sum over the image's questions, in `order`
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((S + GP_ROWS - 1) / GP_ROWS, U), block(C / 4 >= 256 ? 256 : ((C / 4 + 63) / 64) * 64);
-#define VQF_GD(G_)                                                                                                      \
-  VQF_LAUNCH(KID_GLIMPSE_DFEAT_GROUPED, (glimpse_dfeat_grouped_kernel<G_>), grid, block, 0, s, dpooled, wts, order, grp_off, N, S, C, \
-             dfeat, (const int*)nullptr, 0)
-  if (G == 3) VQF_GD(3);
-  else if (G == 2) VQF_GD(2);
-  else VQF_GD(1);
-#undef VQF_GD
-  return vqf_last_error();
+  return glimpse_fwd_launch<float>(feat, logits, N, S, C, G, 0, wts, pooled, stream, {.idx = idx, .U = U});
 }
 
 // region counts with shared images: lens (N) int32 per QUESTION (the count of its image), as in the *_len forms
 int vqf_glimpse_pool_fwd_grouped_len(const float* feat, const float* logits, const int* idx, const int* lens, int N, int U, int S, int C,
                                      int G, float* wts, float* pooled, void* stream) {
-  if (!idx || !lens || ((((uintptr_t)idx) | ((uintptr_t)lens)) & 3) || N <= 0 || U <= 0 || S <= 0 || C <= 0) return VQF_E_BADARG;
+  if (!VqfRegions::ok(idx) || !VqfRegions::ok(lens) || N <= 0 || U <= 0 || S <= 0 || C <= 0) return VQF_E_BADARG;
   if (!vqf_glimpse_pool_grouped_supported(N, U, S, C, G)) return VQF_E_UNSUPPORTED;
-  return glimpse_fwd_launch<float>(feat, logits, N, S, C, G, 0, wts, pooled, stream, lens, idx, U);
+  return glimpse_fwd_launch<float>(feat, logits, N, S, C, G, 0, wts, pooled, stream, {.idx = idx, .U = U, .lens = lens});
+}
+
+// rg.lens (vqf_glimpse_pool_bwd_grouped_len; N int32 per QUESTION, null: all S): the softmax backward runs over the real regions;
+// the per-image half needs nothing -- it sums wts, which are exact zeros on padding
+static int glimpse_bwd_grouped(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, int N, int S,
+                               int C, int G, float* dlogits, float* dfeat, void* stream, const VqfRegions& rg) {
+  if (!VqfRegions::ok(rg.idx) || !VqfRegions::ok(rg.order) || !VqfRegions::ok(rg.grp_off) || N <= 0 || rg.U <= 0 || S <= 0 || C <= 0)
+    return VQF_E_BADARG;
+  if (!vqf_glimpse_pool_grouped_supported(N, rg.U, S, C, G)) return VQF_E_UNSUPPORTED;
+  if (!aligned16(dpooled) || !aligned16(dfeat)) return VQF_E_ALIGN;
+  // the per-question half (dlogits: feat[idx[n]] . dpooled[n], then the softmax backward) on the kernel of the plain form ...
+  const int rc = glimpse_bwd_launch<float>(dpooled, dwts_extra, feat, wts, N, S, C, G, 0, dlogits, nullptr, stream, rg);
+  if (rc || !dfeat) return rc;
+  return glimpse_dfeat_grouped_launch(dpooled, wts, N, S, C, G, dfeat, stream, rg);      // ... and the per-image half
 }
 
 int vqf_glimpse_pool_bwd_grouped(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
                                  const int* order, const int* grp_off, int N, int U, int S, int C, int G, float* dlogits,
                                  float* dfeat, void* stream) {
-  return glimpse_bwd_grouped(dpooled, dwts_extra, feat, wts, idx, order, grp_off, nullptr, N, U, S, C, G, dlogits, dfeat, stream);
+  return glimpse_bwd_grouped(dpooled, dwts_extra, feat, wts, N, S, C, G, dlogits, dfeat, stream,
+                             {.idx = idx, .order = order, .grp_off = grp_off, .U = U});
 }
 
 int vqf_glimpse_pool_bwd_grouped_len(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
                                      const int* order, const int* grp_off, const int* lens, int N, int U, int S, int C, int G,
                                      float* dlogits, float* dfeat, void* stream) {
-  if (!lens || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
-  return glimpse_bwd_grouped(dpooled, dwts_extra, feat, wts, idx, order, grp_off, lens, N, U, S, C, G, dlogits, dfeat, stream);
+  if (!VqfRegions::ok(lens)) return VQF_E_BADARG;
+  return glimpse_bwd_grouped(dpooled, dwts_extra, feat, wts, N, S, C, G, dlogits, dfeat, stream,
+                             {.idx = idx, .order = order, .grp_off = grp_off, .U = U, .lens = lens});
 }
 
-// the packed forms: feat (R, C) fp32 data (no dfeat), roff (U + 1) int32 row offsets -- (N + 1) with idx NULL, where U = N
-static int packed_pool_args(const int* idx, const int* roff, int N, int U, int R, int S, int C, int G) {
-  if (!roff || ((((uintptr_t)idx) | ((uintptr_t)roff)) & 3) || R <= 0 || N <= 0 || U <= 0 || S <= 0 || C <= 0) return VQF_E_BADARG;
-  if (!idx && U != N) return VQF_E_BADARG;
-  if (!vqf_glimpse_pool_grouped_supported(N, U, S, C, G)) return VQF_E_UNSUPPORTED;
-  return VQF_OK;
+// the packed forms: feat (R, C) fp32 data, roff (U + 1) int32 row offsets -- (N + 1) with idx NULL, where U = N
+static int pool_packed_refusal(const VqfRegions& rg, int N, int S, int C, int G) {
+  if (!rg.packed_ok(rg.idx, N) || N <= 0 || S <= 0 || C <= 0) return VQF_E_BADARG;
+  return vqf_glimpse_pool_grouped_supported(N, rg.U, S, C, G) ? VQF_OK : VQF_E_UNSUPPORTED;
 }
 
 int vqf_glimpse_pool_fwd_packed(const float* feat, const float* logits, const int* idx, const int* roff, int N, int U, int R, int S,
                                 int C, int G, int unit_softmax, float* wts, float* pooled, void* stream) {
-  const int rc = packed_pool_args(idx, roff, N, U, R, S, C, G);
-  if (rc) return rc;
-  return glimpse_fwd_launch<float, true>(feat, logits, N, S, C, G, unit_softmax, wts, pooled, stream, roff, idx, U, R);
+  const VqfRegions rg = {.idx = idx, .U = U, .roff = roff, .Rtot = R};
+  const int rc = pool_packed_refusal(rg, N, S, C, G);
+  return rc ? rc : glimpse_fwd_launch<float>(feat, logits, N, S, C, G, unit_softmax, wts, pooled, stream, rg);
 }
 
 int vqf_glimpse_pool_bwd_packed(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
                                 const int* roff, int N, int U, int R, int S, int C, int G, int unit_softmax, float* dlogits,
                                 void* stream) {
-  const int rc = packed_pool_args(idx, roff, N, U, R, S, C, G);
-  if (rc) return rc;
-  return glimpse_bwd_launch<float, true>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, nullptr, stream, roff,
-                                         idx, U, R);
+  const VqfRegions rg = {.idx = idx, .U = U, .roff = roff, .Rtot = R};
+  const int rc = pool_packed_refusal(rg, N, S, C, G);
+  return rc ? rc : glimpse_bwd_launch<float>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, nullptr, stream, rg);
 }
 
 // ... with logits / dlogits (R, G) on the packed rows as well (the co-attention head on the real rows); idx must be NULL
 int vqf_glimpse_pool_fwd_packed_rows(const float* feat, const float* logits, const int* idx, const int* roff, int N, int U, int R, int S,
                                      int C, int G, int unit_softmax, float* wts, float* pooled, void* stream) {
   if (idx) return VQF_E_BADARG;
-  const int rc = packed_pool_args(idx, roff, N, U, R, S, C, G);
-  if (rc) return rc;
-  return glimpse_fwd_launch<float, true, true>(feat, logits, N, S, C, G, unit_softmax, wts, pooled, stream, roff, nullptr, U, R);
+  const VqfRegions rg = {.U = U, .roff = roff, .Rtot = R, .rows = true};
+  const int rc = pool_packed_refusal(rg, N, S, C, G);
+  return rc ? rc : glimpse_fwd_launch<float>(feat, logits, N, S, C, G, unit_softmax, wts, pooled, stream, rg);
 }
 
 int vqf_glimpse_pool_bwd_packed_rows(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
                                      const int* roff, int N, int U, int R, int S, int C, int G, int unit_softmax, float* dlogits,
                                      void* stream) {
   if (idx) return VQF_E_BADARG;
-  const int rc = packed_pool_args(idx, roff, N, U, R, S, C, G);
-  if (rc) return rc;
-  return glimpse_bwd_launch<float, true, true>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, nullptr, stream,
-                                               roff, nullptr, U, R);
+  const VqfRegions rg = {.U = U, .roff = roff, .Rtot = R, .rows = true};
+  const int rc = pool_packed_refusal(rg, N, S, C, G);
+  return rc ? rc : glimpse_bwd_launch<float>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, nullptr, stream, rg);
 }
 
 // ... and with the gradient of the packed rows: dfeat (R, C) like feat.  Plain form (idx, order, grp_off NULL; U = N): the kernel
@@ -904,28 +896,16 @@ int vqf_glimpse_pool_bwd_packed_rows(const float* dpooled, const float* dwts_ext
 int vqf_glimpse_pool_bwd_packed_dfeat(const float* dpooled, const float* dwts_extra, const float* feat, const float* wts, const int* idx,
                                       const int* order, const int* grp_off, const int* roff, int N, int U, int R, int S, int C, int G,
                                       int unit_softmax, float* dlogits, float* dfeat, void* stream) {
-  if (!dfeat || ((((uintptr_t)order) | ((uintptr_t)grp_off)) & 3) || (idx != nullptr) != (order != nullptr) ||
+  if (!dfeat || !VqfRegions::aligned(order) || !VqfRegions::aligned(grp_off) || (idx != nullptr) != (order != nullptr) ||
       (idx != nullptr) != (grp_off != nullptr))
     return VQF_E_BADARG;
-  int rc = packed_pool_args(idx, roff, N, U, R, S, C, G);
+  const VqfRegions rg = {.idx = idx, .order = order, .grp_off = grp_off, .U = U, .roff = roff, .Rtot = R};
+  int rc = pool_packed_refusal(rg, N, S, C, G);
   if (rc) return rc;
   if (!aligned16(dpooled) || !aligned16(feat) || !aligned16(dfeat)) return VQF_E_ALIGN;
-  if (!idx)
-    return glimpse_bwd_launch<float, true>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, dfeat, stream, roff,
-                                           nullptr, U, R);
-  rc = glimpse_bwd_launch<float, true>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, nullptr, stream, roff, idx,
-                                       U, R);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((S + GP_ROWS - 1) / GP_ROWS, U), block(C / 4 >= 256 ? 256 : ((C / 4 + 63) / 64) * 64);
-#define VQF_GD(G_)                                                                                                            \
-  VQF_LAUNCH(KID_GLIMPSE_DFEAT_GROUPED, (glimpse_dfeat_grouped_kernel<G_, true>), grid, block, 0, s, dpooled, wts, order, grp_off, N, \
-             S, C, dfeat, roff, R)
-  if (G == 3) VQF_GD(3);
-  else if (G == 2) VQF_GD(2);
-  else VQF_GD(1);
-#undef VQF_GD
-  return vqf_last_error();
+  rc = glimpse_bwd_launch<float>(dpooled, dwts_extra, feat, wts, N, S, C, G, unit_softmax, dlogits, idx ? nullptr : dfeat, stream, rg);
+  if (rc || !idx) return rc;
+  return glimpse_dfeat_grouped_launch(dpooled, wts, N, S, C, G, dfeat, stream, rg);
 }
 
 int vqf_row_block_supported(int N, int U, long long blk) {
@@ -933,7 +913,7 @@ int vqf_row_block_supported(int N, int U, long long blk) {
 }
 
 int vqf_row_block_gather(const float* src, const int* idx, int N, int U, long long blk, float* dst, void* stream) {
-  if (!src || !idx || !dst || (((uintptr_t)idx) & 3) || N <= 0 || U <= 0 || blk <= 0) return VQF_E_BADARG;
+  if (!src || !VqfRegions::ok(idx) || !dst || N <= 0 || U <= 0 || blk <= 0) return VQF_E_BADARG;
   if (!vqf_row_block_supported(N, U, blk)) return VQF_E_UNSUPPORTED;
   if (!aligned16(src) || !aligned16(dst)) return VQF_E_ALIGN;
   const long long blk4 = blk / 4;
@@ -945,8 +925,7 @@ int vqf_row_block_gather(const float* src, const int* idx, int N, int U, long lo
 
 int vqf_row_block_group_sum(const float* src, const int* order, const int* grp_off, int N, int U, long long blk, float* out,
                             void* stream) {
-  if (!src || !order || !grp_off || !out || ((((uintptr_t)order) | ((uintptr_t)grp_off)) & 3) || N <= 0 || U <= 0 || blk <= 0)
-    return VQF_E_BADARG;
+  if (!src || !VqfRegions::ok(order) || !VqfRegions::ok(grp_off) || !out || N <= 0 || U <= 0 || blk <= 0) return VQF_E_BADARG;
   if (!vqf_row_block_supported(N, U, blk)) return VQF_E_UNSUPPORTED;
   if (!aligned16(src) || !aligned16(out)) return VQF_E_ALIGN;
   const long long blk4 = blk / 4;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/vqa_fusion.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -135,6 +136,50 @@ static inline int vqf_last_error() {
 }
 
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// Where the image rows of a launch are: what the region-aware entry points (fusion.hip, attention.hip, hie_ladder_alt.hip) hand
+// to their launch functions.  HOST ONLY -- passed by const&, never to a kernel: the kernels keep receiving these scalars and
+// pointers one by one.  An entry point fills the fields of its form and leaves the rest as they are here (the plain form: all of it).
+struct VqfRegions {
+  // the grouped forms (N questions over U shared images; the operand of the image side is (U*L, .)): idx (N) the image of each
+  // question, order (N) the questions sorted by image (stable), grp_off (U + 1) image u's questions order[grp_off[u]] ..
+  const int* idx = nullptr;
+  const int* order = nullptr;
+  const int* grp_off = nullptr;
+  int U = 0;
+  // the region-count forms (fp32; no cascade / zdrop / dzdrop / R_bf16 in the fusion): lens (N) per sample / question, lens_u (U)
+  // per image in the grouped form (lens[n] = lens_u[idx[n]], the caller's gather)
+  const int* lens = nullptr;
+  const int* lens_u = nullptr;
+  // the packed forms (fp32): the image-side operand is (Rtot, .), the real rows of every owner one after the other; roff (N + 1)
+  // row offsets per sample or, grouped, (U + 1) per image (vqf_packed_span below); lens / lens_u are not used
+  const int* roff = nullptr;
+  int Rtot = 0;
+  // with roff, un-grouped: the rows on the question side are packed as well (the fusion's R / rowssq / dY / Y, the pooling's
+  // logits / dlogits): the *_packed_rows entry points
+  bool rows = false;
+
+  bool grouped() const { return idx != nullptr || order != nullptr; }      // (a forward has idx only, a backward may have order only)
+  bool counted() const { return lens != nullptr; }
+  bool packed() const { return roff != nullptr; }
+  // the ONE array a kernel's `lens` parameter receives: the offsets when packed, else the counts (per question / per image)
+  const int* walk() const { return roff ? roff : lens; }
+  const int* walk_u() const { return roff ? roff : lens_u; }
+  // an index / count / offset array: int32, 4-byte aligned; ok = given and aligned, aligned = NULL or aligned
+  static bool aligned(const int* a) { return (((uintptr_t)a) & 3) == 0; }
+  static bool ok(const int* a) { return a && aligned(a); }
+  // the pooling and guided-logits *_packed entry points: roff, R and U given, `own` (idx or order: NULL selects the plain form,
+  // where U must equal N) aligned
+  bool packed_ok(const int* own, int N) const { return ok(roff) && aligned(own) && Rtot > 0 && U > 0 && (own || U == N); }
+};
+
+// The glimpse / level count G = 1, 2, 3 (checked by the caller) as a compile-time constant: f(std::integral_constant<int, G>()).
+// G3 = false: the caller has no G = 3 instantiation (and has refused G = 3).
+template <bool G3 = true, typename F> static inline void vqf_dispatch_G(int G, F&& f) {
+  if (G == 3) { if constexpr (G3) f(std::integral_constant<int, 3>()); }
+  else if (G == 2) f(std::integral_constant<int, 2>());
+  else f(std::integral_constant<int, 1>());
+}
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is per device: a single process may drive several GPUs (the
 // reference wraps the model in nn.DataParallel, solver.py:34-36), so every kernel instantiation that asks for

@@ -562,23 +562,97 @@ int pick_ls_image(int U, int L) {
   return ls;
 }
 
+// ---- launches: the run-time switches become template arguments, each kernel's argument list is written once ---------------------
+// The operands of a launch after the checks; where the image rows are comes in a VqfRegions (common.h), host-side only.  Every
+// function below names the instantiations it can reach, so none exists that nobody launches: the layouts are fp32 only (no bf16
+// with GRP / LEN / PACK), PROWS only un-grouped, CASC only in the plain form, and the question-owned grouped pass has no DBIAS.
+struct FuseFwd {
+  const void* P; const float *pbias, *q, *cascade; const uint8_t* keep; uint64_t seed; uint32_t thr; float inv_keep;
+  int N, L, O, LS; float *R, *rowssq, *zdrop; unsigned short* Rb; int ldrb; hipStream_t s;
+};
+
+template <typename PT, int COAL, bool GRP = false, bool LEN = false, bool PACK = false, bool PROWS = false>
+void fuse_fwd_go(const FuseFwd& a, const VqfRegions& rg) {
+  VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<PT, COAL, GRP, LEN, PACK, PROWS>), dim3(a.N, a.LS), dim3(256), 0, a.s,
+             (const PT*)a.P, a.pbias, a.q, a.cascade, a.keep, a.seed, a.thr, a.inv_keep, a.L, a.O, a.LS, a.R, a.rowssq, a.zdrop, a.Rb,
+             a.ldrb, rg.idx, rg.U, rg.walk(), rg.Rtot);
+}
+
+template <typename PT, int COAL>
+void fuse_fwd_layout(const FuseFwd& a, const VqfRegions& rg) {
+  if constexpr (std::is_same<PT, float>::value) {
+    if (rg.packed() && rg.rows) return fuse_fwd_go<float, COAL, false, true, true, true>(a, rg);     // packed rows in and out
+    if (rg.packed() && rg.grouped()) return fuse_fwd_go<float, COAL, true, true, true>(a, rg);
+    if (rg.packed()) return fuse_fwd_go<float, COAL, false, true, true>(a, rg);
+    if (rg.counted() && rg.grouped()) return fuse_fwd_go<float, COAL, true, true>(a, rg);
+    if (rg.counted()) return fuse_fwd_go<float, COAL, false, true>(a, rg);
+    if (rg.grouped()) return fuse_fwd_go<float, COAL, true>(a, rg);
+  }
+  fuse_fwd_go<PT, COAL>(a, rg);
+}
+
+template <typename PT>
+void fuse_fwd_coal(bool coal, bool nopf, const FuseFwd& a, const VqfRegions& rg) {
+  if (nopf) fuse_fwd_layout<PT, 2>(a, rg); else if (coal) fuse_fwd_layout<PT, 1>(a, rg); else fuse_fwd_layout<PT, 0>(a, rg);
+}
+
+struct FuseBwd {
+  const float *dY, *dzdrop, *Y, *inv, *coefA, *coefB; const void* P; const float *pbias, *q, *cascade; const uint8_t* keep;
+  uint64_t seed; uint32_t thr; float inv_keep; int N, L, O, LS; void* dP; float *dq_part, *dcascade, *db_part; hipStream_t s;
+};
+
+// GRP (the question-owned pass): the plain kernel reading P through idx, no dP store, no bias partials (the dq partials only)
+template <bool CASC, bool DBIAS, typename DPT, typename PT, bool COAL, bool GRP, bool LEN, bool PACK, bool PROWS>
+void fuse_bwd_go(const FuseBwd& a, const VqfRegions& rg) {
+  VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<CASC, DBIAS, DPT, PT, COAL, GRP, LEN, PACK, PROWS>), dim3(a.N, a.LS), dim3(256),
+             0, a.s, a.dY, a.dzdrop, a.Y, a.inv, a.coefA, a.coefB, (const PT*)a.P, a.pbias, a.q, a.cascade, a.keep, a.seed, a.thr,
+             a.inv_keep, a.L, a.O, a.LS, GRP ? (DPT*)nullptr : (DPT*)a.dP, a.dq_part, a.dcascade, GRP ? nullptr : a.db_part, rg.idx,
+             rg.U, rg.walk(), rg.Rtot);
+}
+
+template <bool CASC, typename DPT, typename PT, bool GRP = false, bool LEN = false, bool PACK = false, bool PROWS = false>
+void fuse_bwd_flags(bool dbias, bool coal, const FuseBwd& a, const VqfRegions& rg) {
+  if constexpr (!GRP) {
+    if (dbias && coal) return fuse_bwd_go<CASC, true, DPT, PT, true, GRP, LEN, PACK, PROWS>(a, rg);
+    if (dbias) return fuse_bwd_go<CASC, true, DPT, PT, false, GRP, LEN, PACK, PROWS>(a, rg);
+  }
+  if (coal) fuse_bwd_go<CASC, false, DPT, PT, true, GRP, LEN, PACK, PROWS>(a, rg);
+  else fuse_bwd_go<CASC, false, DPT, PT, false, GRP, LEN, PACK, PROWS>(a, rg);
+}
+
+void fuse_bwd_layout(bool p_bf16, bool dp_bf16, bool dbias, bool coal, const FuseBwd& a, const VqfRegions& rg) {
+  if (rg.grouped() && rg.packed()) fuse_bwd_flags<false, float, float, true, true, true>(false, coal, a, rg);
+  else if (rg.grouped() && rg.counted()) fuse_bwd_flags<false, float, float, true, true>(false, coal, a, rg);
+  else if (rg.grouped()) fuse_bwd_flags<false, float, float, true>(false, coal, a, rg);
+  else if (rg.packed() && rg.rows) fuse_bwd_flags<false, float, float, false, true, true, true>(dbias, coal, a, rg);
+  else if (rg.packed()) fuse_bwd_flags<false, float, float, false, true, true>(dbias, coal, a, rg);
+  else if (rg.counted()) fuse_bwd_flags<false, float, float, false, true>(dbias, coal, a, rg);
+  else if (p_bf16) fuse_bwd_flags<false, __bf16, __bf16>(dbias, coal, a, rg);
+  else if (dp_bf16) fuse_bwd_flags<false, __bf16, float>(dbias, coal, a, rg);
+  else if (a.cascade) fuse_bwd_flags<true, float, float>(dbias, coal, a, rg);
+  else fuse_bwd_flags<false, float, float>(dbias, coal, a, rg);
+}
+
+// the image-owned pass of the grouped forms: dP rows and the bias partials of the rows it wrote; grid (U, LSI)
+template <bool DBIAS, bool LEN, bool PACK>
+void fuse_bwd_image_go(int LSI, const FuseBwd& a, const VqfRegions& rg) {
+  VQF_LAUNCH(KID_MFB_FUSE_BWD_IMAGE, (mfb_fuse_bwd_image_kernel<DBIAS, LEN, PACK>), dim3(rg.U, LSI), dim3(256), 0, a.s, a.dY, a.Y,
+             a.inv, a.coefA, a.coefB, a.q, rg.order, rg.grp_off, a.keep, a.seed, a.thr, a.inv_keep, a.N, a.L, a.O, LSI, (float*)a.dP,
+             DBIAS ? a.db_part : nullptr, rg.walk_u(), rg.Rtot);
+}
+
+template <bool LEN, bool PACK>
+void fuse_bwd_image_flags(bool dbias, int LSI, const FuseBwd& a, const VqfRegions& rg) {
+  if (dbias) fuse_bwd_image_go<true, LEN, PACK>(LSI, a, rg); else fuse_bwd_image_go<false, LEN, PACK>(LSI, a, rg);
+}
+
 }  // namespace
 
-static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, const float* inv,
-                     const float* coefA,
-                     const float* coefB, const void* P, int p_bf16, const float* pbias, const float* q,
-                     const float* cascade,
-                     const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O,
-                     void* dP, int dp_bf16, float* dq, float* dcascade, float* dbiasP, void* ws,
-                     size_t ws_bytes, void* stream, const int* idx = nullptr, const int* order = nullptr,
-                     const int* grp_off = nullptr, int U = 0, const int* lens = nullptr, const int* lens_u = nullptr,
-                     const int* roff = nullptr, int Rtot = 0, bool prows = false) {
-  // prows (with roff, un-grouped): dY and Y are (Rtot, O) packed rows as well (vqf_mfb_fuse_bwd_packed_rows)
-  // idx != nullptr: the grouped form (vqf_mfb_fuse_bwd_grouped, which has checked its own operands): P and dP are (U*L, 5O)
-  // lens != nullptr: the region-count forms (fp32, no cascade / dzdrop; their entry points have checked lens): lens (N) per sample /
-  // question, lens_u (U) per image in the grouped form
-  // roff != nullptr: the packed forms (fp32; their entry points have checked roff and Rtot): P and dP are (Rtot, 5O), roff (N + 1) per
-  // sample or, grouped, (U + 1) per image; lens / lens_u are not used
+// The layout forms (rg not plain) are fp32 without cascade / dzdrop; their entry points have checked the arrays of rg.
+static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, const float* inv, const float* coefA,
+                         const float* coefB, const void* P, int p_bf16, const float* pbias, const float* q, const float* cascade,
+                         const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O, void* dP, int dp_bf16, float* dq,
+                         float* dcascade, float* dbiasP, void* ws, size_t ws_bytes, void* stream, const VqfRegions& rg) {
   if (!dY || !Y || !inv || !coefA || !coefB || !P || !q || !dP || !dq || N <= 0 || L <= 0 || O <= 0)
     return VQF_E_BADARG;
   if (O % TPT) return VQF_E_UNSUPPORTED;
@@ -594,95 +668,42 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
   const int W5 = KP * O;
   const bool direct = (LS == 1);      // dq partial == dq
   if (!direct || dbiasP) {
-    const size_t need = idx ? vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O) : vqf_mfb_fuse_bwd_ws_bytes(N, L, O);
+    const size_t need = rg.grouped() ? vqf_mfb_fuse_bwd_grouped_ws_bytes(N, rg.U, L, O) : vqf_mfb_fuse_bwd_ws_bytes(N, L, O);
     if (!ws || ws_bytes < need || !aligned16(ws)) return VQF_E_WORKSPACE;
   }
-  float* dq_part = direct ? dq : (float*)ws;
-  float* db_part = (float*)ws + (size_t)N * LS * W5;
+  // ws: the dq partials [N * LS][5O], the bias partials ([N * LS] rows, grouped [U * LSI]), the reducer's VQF_REDUCE_SPLITS rows
+  float* db_part = ws ? (float*)ws + (size_t)N * LS * W5 : nullptr;
   const uint32_t thr = (keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
   const float inv_keep = (keep || p_drop > 0.f) ? 1.0f / (1.0f - p_drop) : 1.0f;
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid(N, LS);
   // coalesced P / dP access through the LDS transpose: one pass of 256 threads over the row, whole 16-byte pieces
   const bool coal = fuse_coalesced(true) && O / TPT <= 256 && (W5 % ((p_bf16 || dp_bf16) ? 8 : 4) == 0);
-#define VQF_BWD1(C_, D_, T_, PT_, CO_)                                                           \
-  VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<C_, D_, T_, PT_, CO_>), grid, dim3(256), 0, s, dY, dzdrop, Y, inv, \
-             coefA, coefB, (const PT_*)P, pbias, q, cascade, keep, seed, thr, inv_keep, L, O, LS, (T_*)dP, dq_part, \
-             dcascade, db_part, nullptr, 0, nullptr, 0)
-#define VQF_BWD(C_, D_, T_, PT_) do { if (coal) VQF_BWD1(C_, D_, T_, PT_, true); else VQF_BWD1(C_, D_, T_, PT_, false); } while (0)
-  if (idx) {
-    // question-owned pass: the plain kernel reading P through idx, no dP store, no bias partials (the dq partials only) ...
-#define VQF_BWDQ(CO_, LEN_, PK_)                                                                                                     \
-  VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<false, false, float, float, CO_, true, LEN_, PK_>), grid, dim3(256), 0, s, dY,    \
-             nullptr, Y, inv, coefA, coefB, (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, (float*)nullptr, \
-             dq_part, nullptr, nullptr, idx, U, PK_ ? roff : lens, Rtot)
-    if (roff)      { if (coal) VQF_BWDQ(true, true, true); else VQF_BWDQ(false, true, true); }
-    else if (lens) { if (coal) VQF_BWDQ(true, true, false); else VQF_BWDQ(false, true, false); }
-    else           { if (coal) VQF_BWDQ(true, false, false); else VQF_BWDQ(false, false, false); }
-#undef VQF_BWDQ
-    int rcg = vqf_last_error();
-    if (rcg) return rcg;
-    // ... image-owned pass: dP rows and the bias partials of the U*L rows it wrote
-    const int LSI = pick_ls_image(U, L);
-    db_part = (float*)ws + (size_t)N * LS * W5;                   // [U * LSI][5O], then the reducer's VQF_REDUCE_SPLITS rows
-#define VQF_BWDI(DB_, LEN_, PK_)                                                                                                     \
-  VQF_LAUNCH(KID_MFB_FUSE_BWD_IMAGE, (mfb_fuse_bwd_image_kernel<DB_, LEN_, PK_>), dim3(U, LSI), dim3(256), 0, s, dY, Y, inv, coefA,   \
-             coefB, q, order, grp_off, keep, seed, thr, inv_keep, N, L, O, LSI, (float*)dP, DB_ ? db_part : nullptr,                 \
-             PK_ ? roff : lens_u, Rtot)
-    if (roff)        { if (dbiasP) VQF_BWDI(true, true, true); else VQF_BWDI(false, true, true); }
-    else if (lens_u) { if (dbiasP) VQF_BWDI(true, true, false); else VQF_BWDI(false, true, false); }
-    else             { if (dbiasP) VQF_BWDI(true, false, false); else VQF_BWDI(false, false, false); }
-#undef VQF_BWDI
-    rcg = vqf_last_error();
-    if (rcg) return rcg;
-    if (!direct) {
-      rcg = vqf_group_reduce_f32(dq_part, N, LS, W5, dq, stream);
-      if (rcg) return rcg;
-    }
-    if (dbiasP) rcg = vqf_colreduce_2stage(db_part, U * LSI, W5, dbiasP, db_part + (size_t)U * LSI * W5, s);
-    return rcg;
-  }
-  if (lens || roff) {
-#define VQF_BWDL(D_, CO_, PK_, PR_)                                                                                                  \
-  VQF_LAUNCH(KID_MFB_FUSE_BWD, (mfb_fuse_bwd_kernel<false, D_, float, float, CO_, false, true, PK_, PR_>), grid, dim3(256), 0, s, dY, \
-             nullptr, Y, inv, coefA, coefB, (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, (float*)dP,     \
-             dq_part, nullptr, db_part, nullptr, 0, PK_ ? roff : lens, Rtot)
-#define VQF_BWDL2(PK_, PR_)                                                                        \
-    do {                                                                                           \
-      if (dbiasP) { if (coal) VQF_BWDL(true, true, PK_, PR_); else VQF_BWDL(true, false, PK_, PR_); }   \
-      else        { if (coal) VQF_BWDL(false, true, PK_, PR_); else VQF_BWDL(false, false, PK_, PR_); } \
-    } while (0)
-    if (roff && prows) VQF_BWDL2(true, true); else if (roff) VQF_BWDL2(true, false); else VQF_BWDL2(false, false);
-#undef VQF_BWDL2
-#undef VQF_BWDL
-  }
-  else if (p_bf16)  { if (dbiasP) VQF_BWD(false, true, __bf16, __bf16); else VQF_BWD(false, false, __bf16, __bf16); }
-  else if (dp_bf16) { if (dbiasP) VQF_BWD(false, true, __bf16, float); else VQF_BWD(false, false, __bf16, float); }
-  else if (cascade) { if (dbiasP) VQF_BWD(true, true, float, float); else VQF_BWD(true, false, float, float); }
-  else              { if (dbiasP) VQF_BWD(false, true, float, float); else VQF_BWD(false, false, float, float); }
-#undef VQF_BWD
-#undef VQF_BWD1
+  const FuseBwd a = {dY, dzdrop, Y, inv, coefA, coefB, P, pbias, q, cascade, keep, seed, thr, inv_keep, N, L, O, LS, dP,
+                     direct ? dq : (float*)ws, dcascade, db_part, s};
+  fuse_bwd_layout(p_bf16, dp_bf16, dbiasP != nullptr, coal, a, rg);
   int rc = vqf_last_error();
   if (rc) return rc;
-  if (!direct) {
-    rc = vqf_group_reduce_f32(dq_part, N, LS, W5, dq, stream);
+  int db_rows = N * LS;                                          // bias partial rows: the question side's, or ...
+  if (rg.grouped()) {
+    const int LSI = pick_ls_image(rg.U, L);
+    db_rows = rg.U * LSI;                                        // ... the image-owned pass's, which wrote the dP rows
+    if (rg.packed()) fuse_bwd_image_flags<true, true>(dbiasP != nullptr, LSI, a, rg);
+    else if (rg.counted()) fuse_bwd_image_flags<true, false>(dbiasP != nullptr, LSI, a, rg);
+    else fuse_bwd_image_flags<false, false>(dbiasP != nullptr, LSI, a, rg);
+    rc = vqf_last_error();
     if (rc) return rc;
   }
-  if (dbiasP)
-    rc = vqf_colreduce_2stage(db_part, N * LS, W5, dbiasP, (float*)ws + (size_t)2 * N * LS * W5, s);
+  if (!direct) {
+    rc = vqf_group_reduce_f32(a.dq_part, N, LS, W5, dq, stream);
+    if (rc) return rc;
+  }
+  if (dbiasP) rc = vqf_colreduce_2stage(db_part, db_rows, W5, dbiasP, db_part + (size_t)db_rows * W5, s);
   return rc;
 }
 
-
-
-static int fuse_fwd_impl(const void* P, int p_bf16, const float* pbias, const float* q, const float* cascade,
-                         const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O, float* R,
-                         float* rowssq, float* zdrop, void* stream, void* R_bf16 = nullptr, int ldrb = 0,
-                         const int* idx = nullptr, int U = 0, const int* lens = nullptr, const int* roff = nullptr, int Rtot = 0,
-                         bool prows = false) {
-  // prows (with roff, un-grouped): R and rowssq hold the packed rows as well (vqf_mfb_fuse_fwd_packed_rows)
-  // lens != nullptr: the region-count forms (fp32 P, no cascade / zdrop / R_bf16; their entry points have checked lens)
-  // roff != nullptr: the packed forms (the same restrictions; P is (Rtot, 5O), roff (N + 1) or, with idx, (U + 1); lens is not used)
+static int fuse_fwd_impl(const void* P, int p_bf16, const float* pbias, const float* q, const float* cascade, const uint8_t* keep,
+                         uint64_t seed, float p_drop, int N, int L, int O, float* R, float* rowssq, float* zdrop, void* stream,
+                         void* R_bf16, int ldrb, const VqfRegions& rg) {
   if (!P || !q || !R || !rowssq || N <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
   if (R_bf16 && (ldrb < O || (ldrb % 4) || ldrb / 4 > 256 || (((uintptr_t)R_bf16) & 7))) return VQF_E_BADARG;
   if ((O % TPT) || O / TPT > 256) return VQF_E_UNSUPPORTED;     // one thread per 4 pooled outputs: O <= 1024 (the reference's 1000)
@@ -693,39 +714,25 @@ static int fuse_fwd_impl(const void* P, int p_bf16, const float* pbias, const fl
     return VQF_E_ALIGN;
   const uint32_t thr = (keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
   const float inv_keep = (keep || p_drop > 0.f) ? 1.0f / (1.0f - p_drop) : 1.0f;
-  const int LS = pick_ls_fwd(N, L);
   const bool coal = fuse_coalesced(true) && ((KP * O) % (p_bf16 ? 8 : 4) == 0);
   const bool nopf = coal && g_vqf_opt[VQF_OPT_FUSE_COAL] != 1;   // default: no register prefetch (126 VGPRs, 4 blocks per CU)
-#define VQF_FWD(PT_, CO_)                                                                                             \
-  VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<PT_, CO_>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream,         \
-             (const PT_*)P, pbias, q, cascade, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, zdrop, (unsigned short*)R_bf16, ldrb, \
-             nullptr, 0, nullptr, 0)
-#define VQF_FWDG(CO_)                                                                                                 \
-  VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<float, CO_, true>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream, \
-             (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, nullptr, nullptr, 0, idx, U, nullptr, 0)
-#define VQF_FWDL(CO_, GRP_)                                                                                           \
-  VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<float, CO_, GRP_, true>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream, \
-             (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, nullptr, nullptr, 0, idx, U, lens, 0)
-#define VQF_FWDP(CO_, GRP_)                                                                                           \
-  VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<float, CO_, GRP_, true, true>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream, \
-             (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, nullptr, nullptr, 0, idx, U, roff, Rtot)
-#define VQF_FWDR(CO_)                                                                                                 \
-  VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<float, CO_, false, true, true, true>), dim3(N, LS), dim3(256), 0, (hipStream_t)stream, \
-             (const float*)P, pbias, q, nullptr, keep, seed, thr, inv_keep, L, O, LS, R, rowssq, nullptr, nullptr, 0, nullptr, 0, roff, Rtot)
-  if (roff && prows) { if (nopf) VQF_FWDR(2); else if (coal) VQF_FWDR(1); else VQF_FWDR(0); }                     // packed rows in and out
-  else if (roff && idx) { if (nopf) VQF_FWDP(2, true); else if (coal) VQF_FWDP(1, true); else VQF_FWDP(0, true); }     // packed rows (fp32 only)
-  else if (roff)   { if (nopf) VQF_FWDP(2, false); else if (coal) VQF_FWDP(1, false); else VQF_FWDP(0, false); }
-  else if (lens && idx) { if (nopf) VQF_FWDL(2, true); else if (coal) VQF_FWDL(1, true); else VQF_FWDL(0, true); }     // region counts (fp32 only)
-  else if (lens)   { if (nopf) VQF_FWDL(2, false); else if (coal) VQF_FWDL(1, false); else VQF_FWDL(0, false); }
-  else if (idx) { if (nopf) VQF_FWDG(2); else if (coal) VQF_FWDG(1); else VQF_FWDG(0); }       // the grouped form (fp32 only)
-  else if (p_bf16) { if (nopf) VQF_FWD(__bf16, 2); else if (coal) VQF_FWD(__bf16, 1); else VQF_FWD(__bf16, 0); }
-  else        { if (nopf) VQF_FWD(float, 2); else if (coal) VQF_FWD(float, 1); else VQF_FWD(float, 0); }
-#undef VQF_FWDR
-#undef VQF_FWDP
-#undef VQF_FWDL
-#undef VQF_FWDG
-#undef VQF_FWD
+  const FuseFwd a = {P, pbias, q, cascade, keep, seed, thr, inv_keep, N, L, O, pick_ls_fwd(N, L), R, rowssq, zdrop,
+                     (unsigned short*)R_bf16, ldrb, (hipStream_t)stream};
+  if (p_bf16) fuse_fwd_coal<__bf16>(coal, nopf, a, rg); else fuse_fwd_coal<float>(coal, nopf, a, rg);
   return vqf_last_error();
+}
+
+// the layout forms of the two: fp32 P, no cascade / zdrop / dzdrop / R_bf16
+static int fuse_fwd_regions(const float* P, const float* pbias, const float* q, const uint8_t* keep, uint64_t seed, float p_drop,
+                            int N, int L, int O, float* R, float* rowssq, void* stream, const VqfRegions& rg) {
+  return fuse_fwd_impl(P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, R, rowssq, nullptr, stream, nullptr, 0, rg);
+}
+
+static int fuse_bwd_regions(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB, const float* P,
+                            const float* pbias, const float* q, const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O,
+                            float* dP, float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream, const VqfRegions& rg) {
+  return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
+                       dbiasP, ws, ws_bytes, stream, rg);
 }
 
 extern "C" {
@@ -734,18 +741,20 @@ int vqf_mfb_fuse_fwd(const float* P, const float* pbias, const float* q, const f
                      const uint8_t* keep,
                      uint64_t seed, float p_drop, int N, int L, int O, float* R, float* rowssq,
                      float* zdrop, void* stream) {
-  return fuse_fwd_impl(P, 0, pbias, q, cascade, keep, seed, p_drop, N, L, O, R, rowssq, zdrop, stream);
+  return fuse_fwd_impl(P, 0, pbias, q, cascade, keep, seed, p_drop, N, L, O, R, rowssq, zdrop, stream, nullptr, 0, {});
 }
 
 int vqf_mfb_fuse_fwd_pbf16(const void* P_bf16, const float* pbias, const float* q, const uint8_t* keep, uint64_t seed,
                            float p_drop, int N, int L, int O, float* R, float* rowssq, void* stream) {
-  return fuse_fwd_impl(P_bf16, 1, pbias, q, nullptr, keep, seed, p_drop, N, L, O, R, rowssq, nullptr, stream);
+  return fuse_fwd_impl(P_bf16, 1, pbias, q, nullptr, keep, seed, p_drop, N, L, O, R, rowssq, nullptr, stream, nullptr, 0,
+                       {});
 }
 
 int vqf_mfb_fuse_fwd_pbf16_rb(const void* P_bf16, const float* pbias, const float* q, const uint8_t* keep, uint64_t seed,
                               float p_drop, int N, int L, int O, float* R, void* R_bf16, int ldrb, float* rowssq, void* stream) {
   if (!R_bf16) return VQF_E_BADARG;
-  return fuse_fwd_impl(P_bf16, 1, pbias, q, nullptr, keep, seed, p_drop, N, L, O, R, rowssq, nullptr, stream, R_bf16, ldrb);
+  return fuse_fwd_impl(P_bf16, 1, pbias, q, nullptr, keep, seed, p_drop, N, L, O, R, rowssq, nullptr, stream, R_bf16, ldrb,
+                       {});
 }
 
 size_t vqf_mfb_fuse_bwd_ws_bytes(int N, int L, int O) {
@@ -758,7 +767,7 @@ int vqf_mfb_fuse_bwd(const float* dY, const float* dzdrop, const float* Y, const
                      const float* cascade, const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O,
                      float* dP, float* dq, float* dcascade, float* dbiasP, void* ws, size_t ws_bytes, void* stream) {
   return fuse_bwd_impl(dY, dzdrop, Y, inv, coefA, coefB, P, 0, pbias, q, cascade, keep, seed, p_drop, N, L, O, dP, 0, dq,
-                       dcascade, dbiasP, ws, ws_bytes, stream);
+                       dcascade, dbiasP, ws, ws_bytes, stream, {});
 }
 
 int vqf_mfb_fuse_grouped_supported(int N, int U, int L, int O) {
@@ -766,13 +775,11 @@ int vqf_mfb_fuse_grouped_supported(int N, int U, int L, int O) {
          (long long)N * L < (1LL << 29) && (long long)U * L < (1LL << 29);
 }
 
-static bool grouped_index_ok(const int* a) { return a && (((uintptr_t)a) & 3) == 0; }
-
 int vqf_mfb_fuse_fwd_grouped(const float* P, const float* pbias, const float* q, const int* idx, const uint8_t* keep, uint64_t seed,
                              float p_drop, int N, int U, int L, int O, float* R, float* rowssq, void* stream) {
-  if (!grouped_index_ok(idx) || N <= 0 || U <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
+  if (!VqfRegions::ok(idx) || N <= 0 || U <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
   if (!vqf_mfb_fuse_grouped_supported(N, U, L, O)) return VQF_E_UNSUPPORTED;
-  return fuse_fwd_impl(P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, R, rowssq, nullptr, stream, nullptr, 0, idx, U);
+  return fuse_fwd_regions(P, pbias, q, keep, seed, p_drop, N, L, O, R, rowssq, stream, {.idx = idx, .U = U});
 }
 
 size_t vqf_mfb_fuse_bwd_grouped_ws_bytes(int N, int U, int L, int O) {
@@ -780,41 +787,46 @@ size_t vqf_mfb_fuse_bwd_grouped_ws_bytes(int N, int U, int L, int O) {
   return ((size_t)N * pick_ls(N, L) + (size_t)U * pick_ls_image(U, L) + VQF_REDUCE_SPLITS) * KP * O * sizeof(float);
 }
 
+// the grouped backwards: the image-owned pass carves its bias partials from the workspace whether or not dq needs partials
+static bool grouped_ws_ok(const void* ws, size_t ws_bytes, int N, int U, int L, int O) {
+  return ws && ws_bytes >= vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O) && aligned16(ws);
+}
+
 int vqf_mfb_fuse_bwd_grouped(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
                              const float* P, const float* pbias, const float* q, const int* idx, const int* order,
                              const int* grp_off, const uint8_t* keep, uint64_t seed, float p_drop, int N, int U, int L, int O,
                              float* dP, float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream) {
-  if (!grouped_index_ok(idx) || !grouped_index_ok(order) || !grouped_index_ok(grp_off) || N <= 0 || U <= 0 || L <= 0 || O <= 0)
+  if (!VqfRegions::ok(idx) || !VqfRegions::ok(order) || !VqfRegions::ok(grp_off) || N <= 0 || U <= 0 || L <= 0 || O <= 0)
     return VQF_E_BADARG;
   if (!vqf_mfb_fuse_grouped_supported(N, U, L, O)) return VQF_E_UNSUPPORTED;
-  // the image-owned pass carves its bias partials from the workspace whether or not dq needs partials
-  if (!ws || ws_bytes < vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O) || !aligned16(ws)) return VQF_E_WORKSPACE;
-  return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
-                       dbiasP, ws, ws_bytes, stream, idx, order, grp_off, U);
+  if (!grouped_ws_ok(ws, ws_bytes, N, U, L, O)) return VQF_E_WORKSPACE;
+  return fuse_bwd_regions(dY, Y, inv, coefA, coefB, P, pbias, q, keep, seed, p_drop, N, L, O, dP, dq, dbiasP, ws, ws_bytes, stream,
+                          {.idx = idx, .order = order, .grp_off = grp_off, .U = U});
 }
 
 // the region-count forms (lens: int32, 4-byte aligned; the kernels clamp what it holds to [1, L])
 int vqf_mfb_fuse_fwd_len(const float* P, const float* pbias, const float* q, const int* lens, const uint8_t* keep, uint64_t seed,
                          float p_drop, int N, int L, int O, float* R, float* rowssq, void* stream) {
-  if (!grouped_index_ok(lens)) return VQF_E_BADARG;
-  return fuse_fwd_impl(P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, R, rowssq, nullptr, stream, nullptr, 0, nullptr, 0, lens);
+  if (!VqfRegions::ok(lens)) return VQF_E_BADARG;
+  return fuse_fwd_regions(P, pbias, q, keep, seed, p_drop, N, L, O, R, rowssq, stream, {.lens = lens});
 }
 
 int vqf_mfb_fuse_bwd_len(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB, const float* P,
                          const float* pbias, const float* q, const int* lens, const uint8_t* keep, uint64_t seed, float p_drop,
                          int N, int L, int O, float* dP, float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream) {
-  if (!grouped_index_ok(lens)) return VQF_E_BADARG;
-  return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
-                       dbiasP, ws, ws_bytes, stream, nullptr, nullptr, nullptr, 0, lens);
+  if (!VqfRegions::ok(lens)) return VQF_E_BADARG;
+  return fuse_bwd_regions(dY, Y, inv, coefA, coefB, P, pbias, q, keep, seed, p_drop, N, L, O, dP, dq, dbiasP, ws, ws_bytes, stream,
+                          {.lens = lens});
 }
 
 int vqf_mfb_fuse_fwd_grouped_len(const float* P, const float* pbias, const float* q, const int* idx, const int* lens_q,
                                  const int* lens_u, const uint8_t* keep, uint64_t seed, float p_drop, int N, int U, int L, int O,
                                  float* R, float* rowssq, void* stream) {
-  if (!grouped_index_ok(idx) || !grouped_index_ok(lens_q) || !grouped_index_ok(lens_u) || N <= 0 || U <= 0 || L <= 0 || O <= 0)
+  if (!VqfRegions::ok(idx) || !VqfRegions::ok(lens_q) || !VqfRegions::ok(lens_u) || N <= 0 || U <= 0 || L <= 0 || O <= 0)
     return VQF_E_BADARG;
   if (!vqf_mfb_fuse_grouped_supported(N, U, L, O)) return VQF_E_UNSUPPORTED;
-  return fuse_fwd_impl(P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, R, rowssq, nullptr, stream, nullptr, 0, idx, U, lens_q);
+  return fuse_fwd_regions(P, pbias, q, keep, seed, p_drop, N, L, O, R, rowssq, stream,
+                          {.idx = idx, .U = U, .lens = lens_q, .lens_u = lens_u});
 }
 
 int vqf_mfb_fuse_bwd_grouped_len(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
@@ -822,63 +834,66 @@ int vqf_mfb_fuse_bwd_grouped_len(const float* dY, const float* Y, const float* i
                                  const int* grp_off, const int* lens_q, const int* lens_u, const uint8_t* keep, uint64_t seed,
                                  float p_drop, int N, int U, int L, int O, float* dP, float* dq, float* dbiasP, void* ws,
                                  size_t ws_bytes, void* stream) {
-  if (!grouped_index_ok(idx) || !grouped_index_ok(order) || !grouped_index_ok(grp_off) || !grouped_index_ok(lens_q) ||
-      !grouped_index_ok(lens_u) || N <= 0 || U <= 0 || L <= 0 || O <= 0)
+  if (!VqfRegions::ok(idx) || !VqfRegions::ok(order) || !VqfRegions::ok(grp_off) || !VqfRegions::ok(lens_q) ||
+      !VqfRegions::ok(lens_u) || N <= 0 || U <= 0 || L <= 0 || O <= 0)
     return VQF_E_BADARG;
   if (!vqf_mfb_fuse_grouped_supported(N, U, L, O)) return VQF_E_UNSUPPORTED;
-  if (!ws || ws_bytes < vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O) || !aligned16(ws)) return VQF_E_WORKSPACE;
-  return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
-                       dbiasP, ws, ws_bytes, stream, idx, order, grp_off, U, lens_q, lens_u);
+  if (!grouped_ws_ok(ws, ws_bytes, N, U, L, O)) return VQF_E_WORKSPACE;
+  return fuse_bwd_regions(dY, Y, inv, coefA, coefB, P, pbias, q, keep, seed, p_drop, N, L, O, dP, dq, dbiasP, ws, ws_bytes, stream,
+                          {.idx = idx, .order = order, .grp_off = grp_off, .U = U, .lens = lens_q, .lens_u = lens_u});
 }
 
-// the packed forms (roff: int32, 4-byte aligned; the kernels clamp what it holds, see packed_span)
+// the packed forms (roff: int32, 4-byte aligned; the kernels clamp what it holds, see vqf_packed_span)
 int vqf_mfb_fuse_packed_supported(int N, int U, int R, int L, int O) {
   return vqf_mfb_fuse_grouped_supported(N, U, L, O) && L <= 1024 && R >= 1 && R < (1 << 29);
 }
 
+// what the un-grouped packed entry points refuse themselves
+static int fuse_packed_refusal(const int* roff, int N, int R, int L, int O) {
+  if (!VqfRegions::ok(roff) || R <= 0 || N <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
+  return vqf_mfb_fuse_packed_supported(N, N, R, L, O) ? VQF_OK : VQF_E_UNSUPPORTED;
+}
+
 int vqf_mfb_fuse_fwd_packed(const float* P, const float* pbias, const float* q, const int* roff, const uint8_t* keep, uint64_t seed,
                             float p_drop, int N, int R, int L, int O, float* Rout, float* rowssq, void* stream) {
-  if (!grouped_index_ok(roff) || R <= 0 || N <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
-  if (!vqf_mfb_fuse_packed_supported(N, N, R, L, O)) return VQF_E_UNSUPPORTED;
-  return fuse_fwd_impl(P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, Rout, rowssq, nullptr, stream, nullptr, 0, nullptr, 0,
-                       nullptr, roff, R);
+  const int rc = fuse_packed_refusal(roff, N, R, L, O);
+  return rc ? rc : fuse_fwd_regions(P, pbias, q, keep, seed, p_drop, N, L, O, Rout, rowssq, stream, {.roff = roff, .Rtot = R});
 }
 
 int vqf_mfb_fuse_bwd_packed(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB, const float* P,
                             const float* pbias, const float* q, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop,
                             int N, int R, int L, int O, float* dP, float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream) {
-  if (!grouped_index_ok(roff) || R <= 0 || N <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
-  if (!vqf_mfb_fuse_packed_supported(N, N, R, L, O)) return VQF_E_UNSUPPORTED;
-  return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
-                       dbiasP, ws, ws_bytes, stream, nullptr, nullptr, nullptr, 0, nullptr, nullptr, roff, R);
+  const int rc = fuse_packed_refusal(roff, N, R, L, O);
+  if (rc) return rc;
+  return fuse_bwd_regions(dY, Y, inv, coefA, coefB, P, pbias, q, keep, seed, p_drop, N, L, O, dP, dq, dbiasP, ws, ws_bytes, stream,
+                          {.roff = roff, .Rtot = R});
 }
 
 // ... with the fusion's own rows packed too: Rout (R, O), rowssq (4 R), dY / Y (R, O) (the co-attention head on the real rows)
 int vqf_mfb_fuse_fwd_packed_rows(const float* P, const float* pbias, const float* q, const int* roff, const uint8_t* keep, uint64_t seed,
                                  float p_drop, int N, int R, int L, int O, float* Rout, float* rowssq, void* stream) {
-  if (!grouped_index_ok(roff) || R <= 0 || N <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
-  if (!vqf_mfb_fuse_packed_supported(N, N, R, L, O)) return VQF_E_UNSUPPORTED;
-  return fuse_fwd_impl(P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, Rout, rowssq, nullptr, stream, nullptr, 0, nullptr, 0,
-                       nullptr, roff, R, true);
+  const int rc = fuse_packed_refusal(roff, N, R, L, O);
+  if (rc) return rc;
+  return fuse_fwd_regions(P, pbias, q, keep, seed, p_drop, N, L, O, Rout, rowssq, stream, {.roff = roff, .Rtot = R, .rows = true});
 }
 
 int vqf_mfb_fuse_bwd_packed_rows(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
                                  const float* P, const float* pbias, const float* q, const int* roff, const uint8_t* keep, uint64_t seed,
                                  float p_drop, int N, int R, int L, int O, float* dP, float* dq, float* dbiasP, void* ws,
                                  size_t ws_bytes, void* stream) {
-  if (!grouped_index_ok(roff) || R <= 0 || N <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
-  if (!vqf_mfb_fuse_packed_supported(N, N, R, L, O)) return VQF_E_UNSUPPORTED;
-  return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
-                       dbiasP, ws, ws_bytes, stream, nullptr, nullptr, nullptr, 0, nullptr, nullptr, roff, R, true);
+  const int rc = fuse_packed_refusal(roff, N, R, L, O);
+  if (rc) return rc;
+  return fuse_bwd_regions(dY, Y, inv, coefA, coefB, P, pbias, q, keep, seed, p_drop, N, L, O, dP, dq, dbiasP, ws, ws_bytes, stream,
+                          {.roff = roff, .Rtot = R, .rows = true});
 }
 
 int vqf_mfb_fuse_fwd_grouped_packed(const float* P, const float* pbias, const float* q, const int* idx, const int* roff,
                                     const uint8_t* keep, uint64_t seed, float p_drop, int N, int U, int R, int L, int O, float* Rout,
                                     float* rowssq, void* stream) {
-  if (!grouped_index_ok(idx) || !grouped_index_ok(roff) || R <= 0 || N <= 0 || U <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
+  if (!VqfRegions::ok(idx) || !VqfRegions::ok(roff) || R <= 0 || N <= 0 || U <= 0 || L <= 0 || O <= 0) return VQF_E_BADARG;
   if (!vqf_mfb_fuse_packed_supported(N, U, R, L, O)) return VQF_E_UNSUPPORTED;
-  return fuse_fwd_impl(P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, Rout, rowssq, nullptr, stream, nullptr, 0, idx, U,
-                       nullptr, roff, R);
+  return fuse_fwd_regions(P, pbias, q, keep, seed, p_drop, N, L, O, Rout, rowssq, stream,
+                          {.idx = idx, .U = U, .roff = roff, .Rtot = R});
 }
 
 int vqf_mfb_fuse_bwd_grouped_packed(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
@@ -886,13 +901,13 @@ int vqf_mfb_fuse_bwd_grouped_packed(const float* dY, const float* Y, const float
                                     const int* grp_off, const int* roff, const uint8_t* keep, uint64_t seed, float p_drop, int N,
                                     int U, int R, int L, int O, float* dP, float* dq, float* dbiasP, void* ws, size_t ws_bytes,
                                     void* stream) {
-  if (!grouped_index_ok(idx) || !grouped_index_ok(order) || !grouped_index_ok(grp_off) || !grouped_index_ok(roff) || R <= 0 ||
+  if (!VqfRegions::ok(idx) || !VqfRegions::ok(order) || !VqfRegions::ok(grp_off) || !VqfRegions::ok(roff) || R <= 0 ||
       N <= 0 || U <= 0 || L <= 0 || O <= 0)
     return VQF_E_BADARG;
   if (!vqf_mfb_fuse_packed_supported(N, U, R, L, O)) return VQF_E_UNSUPPORTED;
-  if (!ws || ws_bytes < vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O) || !aligned16(ws)) return VQF_E_WORKSPACE;
-  return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
-                       dbiasP, ws, ws_bytes, stream, idx, order, grp_off, U, nullptr, nullptr, roff, R);
+  if (!grouped_ws_ok(ws, ws_bytes, N, U, L, O)) return VQF_E_WORKSPACE;
+  return fuse_bwd_regions(dY, Y, inv, coefA, coefB, P, pbias, q, keep, seed, p_drop, N, L, O, dP, dq, dbiasP, ws, ws_bytes, stream,
+                          {.idx = idx, .order = order, .grp_off = grp_off, .U = U, .roff = roff, .Rtot = R});
 }
 
 int vqf_mfb_fuse_bwd_pbf16(const float* dY, const float* Y, const float* inv, const float* coefA,
@@ -900,7 +915,7 @@ int vqf_mfb_fuse_bwd_pbf16(const float* dY, const float* Y, const float* inv, co
                            const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O, void* dP_bf16,
                            float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream) {
   return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P_bf16, 1, pbias, q, nullptr, keep, seed, p_drop, N, L, O,
-                       dP_bf16, 1, dq, nullptr, dbiasP, ws, ws_bytes, stream);
+                       dP_bf16, 1, dq, nullptr, dbiasP, ws, ws_bytes, stream, {});
 }
 
 int vqf_mfb_fuse_bwd_bf16dp(const float* dY, const float* Y, const float* inv, const float* coefA,
@@ -908,7 +923,8 @@ int vqf_mfb_fuse_bwd_bf16dp(const float* dY, const float* Y, const float* inv, c
                             const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O, void* dP_bf16,
                             float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream) {
   return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP_bf16, 1,
-                       dq, nullptr, dbiasP, ws, ws_bytes, stream);
+                       dq, nullptr, dbiasP, ws, ws_bytes, stream, {});
 }
 
 }  // extern "C"
+

@@ -446,7 +446,31 @@ size_t lds_bytes(int mode, int E, int T, int Lc) {
   return sizeof(float) * (ops_f > red_f ? ops_f : red_f);
 }
 
-int launch(int mode, HieArgs& g, const uint8_t* keep, uint64_t seed, float p, hipStream_t s, const int* rlens = nullptr) {
+// the mode, the compile-time bound of T (8, 14, 16) and REG (g.rlens given) -> the instantiation
+template <int MODE, bool REG>
+int stream_go(int kid, int nt, size_t lds, hipStream_t s, const HieArgs& g) {
+  auto go = [&](auto tm) {
+    VQF_LAUNCH(kid, (hie_stream_kernel<MODE, decltype(tm)::value, REG>), dim3(g.S, g.N), dim3(nt), lds, s, g);
+  };
+  if (g.T <= 8) go(std::integral_constant<int, 8>());
+  else if (g.T <= 14) go(std::integral_constant<int, 14>());
+  else go(std::integral_constant<int, 16>());
+  return vqf_last_error();
+}
+
+template <bool REG>
+int stream_mode(int mode, int nt, size_t lds, hipStream_t s, const HieArgs& g) {
+  switch (mode) {
+    case MODE_FWD:  return stream_go<MODE_FWD, REG>(KID_HIE_FWD, nt, lds, s, g);
+    case MODE_ADD:  return stream_go<MODE_ADD, REG>(KID_HIE_ADD, nt, lds, s, g);
+    case MODE_LEFT: return stream_go<MODE_LEFT, REG>(KID_HIE_LEFT, nt, lds, s, g);
+  }
+  if constexpr (REG) return VQF_E_BADARG;                    // (the head pass has no region form)
+  else return stream_go<MODE_HEAD, false>(KID_HIE_HEAD, nt, lds, s, g);
+}
+
+// g: the operands, and g.rlens for the region-count forms; the chunking and the dropout fields are filled here
+int launch(int mode, HieArgs& g, const uint8_t* keep, uint64_t seed, float p, hipStream_t s) {
   if (!shape_ok(g.N, g.L, g.E, g.T)) return VQF_E_UNSUPPORTED;
   g.S = chunks_for(g.N, g.L);
   g.Lc = (g.L + g.S - 1) / g.S;
@@ -460,33 +484,10 @@ int launch(int mode, HieArgs& g, const uint8_t* keep, uint64_t seed, float p, hi
   g.keep = keep; g.seed = seed;
   g.thr = (keep || p == 0.f) ? 0u : drop_threshold_host(p);
   g.inv_keep = (keep || p > 0.f) ? 1.0f / (1.0f - p) : 1.0f;
-  g.rlens = rlens;
-  const dim3 grid(g.S, g.N);
-#define HIE_GO(TM)                                                                                              \
-  switch (mode) {                                                                                               \
-    case MODE_FWD:  VQF_LAUNCH(KID_HIE_FWD, (hie_stream_kernel<MODE_FWD, TM>), grid, dim3(nt), lds, s, g); break;   \
-    case MODE_HEAD: VQF_LAUNCH(KID_HIE_HEAD, (hie_stream_kernel<MODE_HEAD, TM>), grid, dim3(nt), lds, s, g); break; \
-    case MODE_ADD:  VQF_LAUNCH(KID_HIE_ADD, (hie_stream_kernel<MODE_ADD, TM>), grid, dim3(nt), lds, s, g); break;   \
-    default:        VQF_LAUNCH(KID_HIE_LEFT, (hie_stream_kernel<MODE_LEFT, TM>), grid, dim3(nt), lds, s, g); break; \
-  }
-#define HIE_GO_REG(TM)                                                                                                \
-  switch (mode) {                                                                                                     \
-    case MODE_FWD:  VQF_LAUNCH(KID_HIE_FWD, (hie_stream_kernel<MODE_FWD, TM, true>), grid, dim3(nt), lds, s, g); break;   \
-    case MODE_ADD:  VQF_LAUNCH(KID_HIE_ADD, (hie_stream_kernel<MODE_ADD, TM, true>), grid, dim3(nt), lds, s, g); break;   \
-    case MODE_LEFT: VQF_LAUNCH(KID_HIE_LEFT, (hie_stream_kernel<MODE_LEFT, TM, true>), grid, dim3(nt), lds, s, g); break; \
-    default: return VQF_E_BADARG;                             /* (the head pass has no region form) */                \
-  }
-  if (rlens) {
-    if (g.T <= 8) { HIE_GO_REG(8) } else if (g.T <= 14) { HIE_GO_REG(14) } else { HIE_GO_REG(16) }
-  } else if (g.T <= 8) { HIE_GO(8) } else if (g.T <= 14) { HIE_GO(14) } else { HIE_GO(16) }
-#undef HIE_GO_REG
-#undef HIE_GO
-  return vqf_last_error();
+  return g.rlens ? stream_mode<true>(mode, nt, lds, s, g) : stream_mode<false>(mode, nt, lds, s, g);
 }
 
 bool rows_ok(const float* p, int ld, int E) { return p && aligned16(p) && ld >= E && (ld % 4) == 0; }
-
-bool counts_ok(const int* p) { return p && !(((uintptr_t)p) & 3); }      // rlens: non-null, 4-byte aligned
 
 bool affinity_shape_ok(int N, int L, int E, int T, int G, int pairs) {
   if (N <= 0 || N > 65535 || L <= 0 || T <= 0 || T > 16 || E <= 0 || (E % 32) || G < 1 || G > 3 || pairs < 1 || pairs > 2)
@@ -587,14 +588,22 @@ int vqf_hie_slab_sum(const float* part, int S, int R, int W, const float* add, i
   return vqf_last_error();
 }
 
+// the operands the streaming passes share (a pass without one gives nullptr / 0); its entry point adds what only it has
+static HieArgs hie_args(const float* a, int lda, const float* z, int ldz, const float* U, const float* V, int ldv, float* out, int ldo,
+                        float* part, int ldp, float* colpart, int ldcp, const float* padd, int ldpa, int N, int L, int E, int T) {
+  HieArgs g = {};
+  g.a = a; g.lda = lda; g.z = z; g.ldz = ldz; g.U = U; g.V = V; g.ldv = ldv; g.out = out; g.ldo = ldo; g.part = part; g.ldp = ldp;
+  g.colpart = colpart; g.ldcp = ldcp; g.padd = padd; g.ldpa = ldpa;
+  g.N = N; g.L = L; g.E = E; g.T = T;
+  return g;
+}
+
 int vqf_hie_hv_fwd(const float* a, int lda, const float* C, const float* V, int ldv, const uint8_t* keep, uint64_t seed,
                    float p_drop, int N, int L, int E, int T, float* out, int ldo, float* part, int ldp, void* stream) {
   if (!C || !rows_ok(part, ldp, E) || !rows_ok(a, lda, E) || !rows_ok(V, ldv, E) || !rows_ok(out, ldo, E) || p_drop < 0.f ||
       p_drop >= 1.f)
     return VQF_E_BADARG;
-  HieArgs g = {};
-  g.a = a; g.lda = lda; g.out = out; g.ldo = ldo; g.U = C; g.V = V; g.ldv = ldv; g.part = part; g.ldp = ldp;
-  g.N = N; g.L = L; g.E = E; g.T = T;
+  HieArgs g = hie_args(a, lda, nullptr, 0, C, V, ldv, out, ldo, part, ldp, nullptr, 0, nullptr, 0, N, L, E, T);
   return launch(MODE_FWD, g, keep, seed, p_drop, (hipStream_t)stream);
 }
 
@@ -604,10 +613,8 @@ int vqf_hie_head_bwd(const float* hv, int ldh, const float* dl, const float* w, 
   if (!C || !dl || !w || !rows_ok(part, ldp, E) || (padd && !rows_ok(padd, ldpa, E)) || !wpart || !aligned16(wpart) || ldw < E + 4 ||
       (ldw % 4) || !rows_ok(hv, ldh, E) || !rows_ok(out, ldo, E) || !aligned16(w) || p_drop < 0.f || p_drop >= 1.f)
     return VQF_E_BADARG;
-  HieArgs g = {};
-  g.a = hv; g.lda = ldh; g.out = out; g.ldo = ldo; g.U = C; g.part = part; g.ldp = ldp; g.padd = padd; g.ldpa = ldpa;
+  HieArgs g = hie_args(hv, ldh, nullptr, 0, C, nullptr, 0, out, ldo, part, ldp, nullptr, 0, padd, ldpa, N, L, E, T);
   g.dl = dl; g.w = w; g.wpart = wpart; g.ldw = ldw;
-  g.N = N; g.L = L; g.E = E; g.T = T;
   return launch(MODE_HEAD, g, keep, seed, p_drop, (hipStream_t)stream);
 }
 
@@ -615,9 +622,7 @@ int vqf_hie_rank_add(const float* a, int lda, const float* U, const float* V, in
                      int ldo, float* colpart, int ldcp, void* stream) {
   if (!U || !rows_ok(a, lda, E) || !rows_ok(V, ldv, E) || !rows_ok(out, ldo, E) || (colpart && !rows_ok(colpart, ldcp, E)))
     return VQF_E_BADARG;
-  HieArgs g = {};
-  g.a = a; g.lda = lda; g.out = out; g.ldo = ldo; g.U = U; g.V = V; g.ldv = ldv; g.colpart = colpart; g.ldcp = ldcp;
-  g.N = N; g.L = L; g.E = E; g.T = T;
+  HieArgs g = hie_args(a, lda, nullptr, 0, U, V, ldv, out, ldo, nullptr, 0, colpart, ldcp, nullptr, 0, N, L, E, T);
   return launch(MODE_ADD, g, nullptr, 0, 0.f, (hipStream_t)stream);
 }
 
@@ -626,10 +631,7 @@ int vqf_hie_rank_left(const float* U, const float* V, int ldv, const float* z, i
   if (!U || !rows_ok(part, ldp, E) || !rows_ok(z, ldz, E) || !rows_ok(V, ldv, E) || !rows_ok(out, ldo, E) ||
       (colpart && !rows_ok(colpart, ldcp, E)))
     return VQF_E_BADARG;
-  HieArgs g = {};
-  g.z = z; g.ldz = ldz; g.out = out; g.ldo = ldo; g.U = U; g.V = V; g.ldv = ldv; g.part = part; g.ldp = ldp;
-  g.colpart = colpart; g.ldcp = ldcp;
-  g.N = N; g.L = L; g.E = E; g.T = T;
+  HieArgs g = hie_args(nullptr, 0, z, ldz, U, V, ldv, out, ldo, part, ldp, colpart, ldcp, nullptr, 0, N, L, E, T);
   return launch(MODE_LEFT, g, nullptr, 0, 0.f, (hipStream_t)stream);
 }
 
@@ -637,42 +639,37 @@ int vqf_hie_rank_left(const float* U, const float* V, int ldv, const float* z, i
 int vqf_hie_hv_fwd_regions(const float* a, int lda, const float* C, const float* V, int ldv, const uint8_t* keep, uint64_t seed,
                            float p_drop, const int* rlens, int N, int L, int E, int T, float* out, int ldo, float* part, int ldp,
                            const float* padd, int ldpa, void* stream) {
-  if (!counts_ok(rlens) || !C || !rows_ok(part, ldp, E) || (padd && !rows_ok(padd, ldpa, E)) || !rows_ok(a, lda, E) ||
+  if (!VqfRegions::ok(rlens) || !C || !rows_ok(part, ldp, E) || (padd && !rows_ok(padd, ldpa, E)) || !rows_ok(a, lda, E) ||
       !rows_ok(V, ldv, E) || !rows_ok(out, ldo, E) || p_drop < 0.f || p_drop >= 1.f)
     return VQF_E_BADARG;
-  HieArgs g = {};
-  g.a = a; g.lda = lda; g.out = out; g.ldo = ldo; g.U = C; g.V = V; g.ldv = ldv; g.part = part; g.ldp = ldp;
-  g.padd = padd; g.ldpa = ldpa;
-  g.N = N; g.L = L; g.E = E; g.T = T;
-  return launch(MODE_FWD, g, keep, seed, p_drop, (hipStream_t)stream, rlens);
+  HieArgs g = hie_args(a, lda, nullptr, 0, C, V, ldv, out, ldo, part, ldp, nullptr, 0, padd, ldpa, N, L, E, T);
+  g.rlens = rlens;
+  return launch(MODE_FWD, g, keep, seed, p_drop, (hipStream_t)stream);
 }
 
 int vqf_hie_rank_add_regions(const float* a, int lda, const float* U, const float* V, int ldv, const int* rlens, int N, int L,
                              int E, int T, float* out, int ldo, float* colpart, int ldcp, void* stream) {
-  if (!counts_ok(rlens) || !U || !rows_ok(a, lda, E) || !rows_ok(V, ldv, E) || !rows_ok(out, ldo, E) ||
+  if (!VqfRegions::ok(rlens) || !U || !rows_ok(a, lda, E) || !rows_ok(V, ldv, E) || !rows_ok(out, ldo, E) ||
       (colpart && !rows_ok(colpart, ldcp, E)))
     return VQF_E_BADARG;
-  HieArgs g = {};
-  g.a = a; g.lda = lda; g.out = out; g.ldo = ldo; g.U = U; g.V = V; g.ldv = ldv; g.colpart = colpart; g.ldcp = ldcp;
-  g.N = N; g.L = L; g.E = E; g.T = T;
-  return launch(MODE_ADD, g, nullptr, 0, 0.f, (hipStream_t)stream, rlens);
+  HieArgs g = hie_args(a, lda, nullptr, 0, U, V, ldv, out, ldo, nullptr, 0, colpart, ldcp, nullptr, 0, N, L, E, T);
+  g.rlens = rlens;
+  return launch(MODE_ADD, g, nullptr, 0, 0.f, (hipStream_t)stream);
 }
 
 int vqf_hie_rank_left_regions(const float* U, const float* V, int ldv, const float* z, int ldz, const int* rlens, int N, int L,
                               int E, int T, float* out, int ldo, float* part, int ldp, const float* padd, int ldpa, float* colpart,
                               int ldcp, void* stream) {
-  if (!counts_ok(rlens) || !U || !rows_ok(part, ldp, E) || (padd && !rows_ok(padd, ldpa, E)) || !rows_ok(z, ldz, E) ||
+  if (!VqfRegions::ok(rlens) || !U || !rows_ok(part, ldp, E) || (padd && !rows_ok(padd, ldpa, E)) || !rows_ok(z, ldz, E) ||
       !rows_ok(V, ldv, E) || !rows_ok(out, ldo, E) || (colpart && !rows_ok(colpart, ldcp, E)))
     return VQF_E_BADARG;
-  HieArgs g = {};
-  g.z = z; g.ldz = ldz; g.out = out; g.ldo = ldo; g.U = U; g.V = V; g.ldv = ldv; g.part = part; g.ldp = ldp;
-  g.padd = padd; g.ldpa = ldpa; g.colpart = colpart; g.ldcp = ldcp;
-  g.N = N; g.L = L; g.E = E; g.T = T;
-  return launch(MODE_LEFT, g, nullptr, 0, 0.f, (hipStream_t)stream, rlens);
+  HieArgs g = hie_args(nullptr, 0, z, ldz, U, V, ldv, out, ldo, part, ldp, colpart, ldcp, padd, ldpa, N, L, E, T);
+  g.rlens = rlens;
+  return launch(MODE_LEFT, g, nullptr, 0, 0.f, (hipStream_t)stream);
 }
 
 int vqf_zero_cols_len(float* x, const int* rlens, long long rows, int rows_per_sample, int N, int L, void* stream) {
-  if (!x || !counts_ok(rlens) || rows <= 0 || rows_per_sample <= 0 || N <= 0 || L <= 0 || rows % ((long long)rows_per_sample * N))
+  if (!x || !VqfRegions::ok(rlens) || rows <= 0 || rows_per_sample <= 0 || N <= 0 || L <= 0 || rows % ((long long)rows_per_sample * N))
     return VQF_E_BADARG;
   long long blocks = (rows * L + 255) / 256;
   if (blocks > 8192) blocks = 8192;
@@ -683,43 +680,48 @@ int vqf_zero_cols_len(float* x, const int* rlens, long long rows, int rows_per_s
 
 int vqf_hie_affinity_supported(int N, int L, int E, int T, int pairs) { return affinity_shape_ok(N, L, E, T, 1, pairs); }
 
-int vqf_hie_affinity(const float* x1, int ldx1, const float* y1, int ldy1, const float* x2, int ldx2, const float* y2, int ldy2,
-                     int epi, const float* yprev, const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int E, int T,
-                     float* out, void* stream) {
-  if (p_drop < 0.f || p_drop >= 1.f) return VQF_E_BADARG;
+// the operands every affinity form shares (lv*: 0 outside the levels forms); its entry point adds g.lens / g.rlens
+static AffArgs aff_args(const float* x1, int ldx1, int lvx1, const float* y1, int ldy1, int lvy1, const float* x2, int ldx2, int lvx2,
+                        const float* y2, int ldy2, int lvy2, const float* yprev, float* out, int N, int L, int E, int T) {
   AffArgs g = {};
-  g.x1 = x1; g.ldx1 = ldx1; g.y1 = y1; g.ldy1 = ldy1; g.x2 = x2; g.ldx2 = ldx2; g.y2 = y2; g.ldy2 = ldy2;
+  g.x1 = x1; g.ldx1 = ldx1; g.lvx1 = lvx1; g.y1 = y1; g.ldy1 = ldy1; g.lvy1 = lvy1;
+  g.x2 = x2; g.ldx2 = ldx2; g.lvx2 = lvx2; g.y2 = y2; g.ldy2 = ldy2; g.lvy2 = lvy2;
   g.yprev = yprev; g.out = out; g.N = N; g.L = L; g.E = E; g.T = T;
+  return g;
+}
+
+// vqf_hie_affinity*: one level with the dropout epilogue (epi = 0 has none); `g` holds the operands and g.lens / g.rlens
+static int affinity_drop_launch(AffArgs& g, int epi, const uint8_t* keep, uint64_t seed, float p_drop, void* stream) {
   g.keep = epi ? keep : nullptr; g.seed = seed;
   g.thr = (!epi || keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
   g.inv_keep = (epi && (keep || p_drop > 0.f)) ? 1.0f / (1.0f - p_drop) : 1.0f;
   return affinity_launch(KID_HIE_AFF, g, 1, epi, true, (hipStream_t)stream);
+}
+
+int vqf_hie_affinity(const float* x1, int ldx1, const float* y1, int ldy1, const float* x2, int ldx2, const float* y2, int ldy2,
+                     int epi, const float* yprev, const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int E, int T,
+                     float* out, void* stream) {
+  if (p_drop < 0.f || p_drop >= 1.f) return VQF_E_BADARG;
+  AffArgs g = aff_args(x1, ldx1, 0, y1, ldy1, 0, x2, ldx2, 0, y2, ldy2, 0, yprev, out, N, L, E, T);
+  return affinity_drop_launch(g, epi, keep, seed, p_drop, stream);
 }
 
 int vqf_hie_affinity_len(const float* x1, int ldx1, const float* y1, int ldy1, const float* x2, int ldx2, const float* y2, int ldy2,
                          int epi, const float* yprev, const uint8_t* keep, uint64_t seed, float p_drop, const int* lens, int N, int L,
                          int E, int T, float* out, void* stream) {
-  if (p_drop < 0.f || p_drop >= 1.f || !lens || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
-  AffArgs g = {};
-  g.x1 = x1; g.ldx1 = ldx1; g.y1 = y1; g.ldy1 = ldy1; g.x2 = x2; g.ldx2 = ldx2; g.y2 = y2; g.ldy2 = ldy2;
-  g.yprev = yprev; g.out = out; g.N = N; g.L = L; g.E = E; g.T = T; g.lens = lens;
-  g.keep = epi ? keep : nullptr; g.seed = seed;
-  g.thr = (!epi || keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
-  g.inv_keep = (epi && (keep || p_drop > 0.f)) ? 1.0f / (1.0f - p_drop) : 1.0f;
-  return affinity_launch(KID_HIE_AFF, g, 1, epi, true, (hipStream_t)stream);
+  if (p_drop < 0.f || p_drop >= 1.f || !VqfRegions::ok(lens)) return VQF_E_BADARG;
+  AffArgs g = aff_args(x1, ldx1, 0, y1, ldy1, 0, x2, ldx2, 0, y2, ldy2, 0, yprev, out, N, L, E, T);
+  g.lens = lens;
+  return affinity_drop_launch(g, epi, keep, seed, p_drop, stream);
 }
 
 int vqf_hie_affinity_regions(const float* x1, int ldx1, const float* y1, int ldy1, const float* x2, int ldx2, const float* y2,
                              int ldy2, int epi, const float* yprev, const uint8_t* keep, uint64_t seed, float p_drop, const int* lens,
                              const int* rlens, int N, int L, int E, int T, float* out, void* stream) {
-  if (p_drop < 0.f || p_drop >= 1.f || !counts_ok(rlens) || (lens && (((uintptr_t)lens) & 3))) return VQF_E_BADARG;
-  AffArgs g = {};
-  g.x1 = x1; g.ldx1 = ldx1; g.y1 = y1; g.ldy1 = ldy1; g.x2 = x2; g.ldx2 = ldx2; g.y2 = y2; g.ldy2 = ldy2;
-  g.yprev = yprev; g.out = out; g.N = N; g.L = L; g.E = E; g.T = T; g.lens = lens; g.rlens = rlens;
-  g.keep = epi ? keep : nullptr; g.seed = seed;
-  g.thr = (!epi || keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
-  g.inv_keep = (epi && (keep || p_drop > 0.f)) ? 1.0f / (1.0f - p_drop) : 1.0f;
-  return affinity_launch(KID_HIE_AFF, g, 1, epi, true, (hipStream_t)stream);
+  if (p_drop < 0.f || p_drop >= 1.f || !VqfRegions::ok(rlens) || !VqfRegions::aligned(lens)) return VQF_E_BADARG;
+  AffArgs g = aff_args(x1, ldx1, 0, y1, ldy1, 0, x2, ldx2, 0, y2, ldy2, 0, yprev, out, N, L, E, T);
+  g.lens = lens; g.rlens = rlens;
+  return affinity_drop_launch(g, epi, keep, seed, p_drop, stream);
 }
 
 int vqf_hie_affinity_levels_supported(int N, int L, int E, int T, int G, int pairs) { return affinity_shape_ok(N, L, E, T, G, pairs); }
@@ -727,10 +729,8 @@ int vqf_hie_affinity_levels_supported(int N, int L, int E, int T, int G, int pai
 int vqf_hie_affinity_levels(const float* x1, int ldx1, int ldx_level1, const float* y1, int ldy1, int ldy_level1,
                             const float* x2, int ldx2, int ldx_level2, const float* y2, int ldy2, int ldy_level2,
                             int G, int epi, const float* yprev, int N, int L, int E, int T, float* out, void* stream) {
-  AffArgs g = {};
-  g.x1 = x1; g.ldx1 = ldx1; g.lvx1 = ldx_level1; g.y1 = y1; g.ldy1 = ldy1; g.lvy1 = ldy_level1;
-  g.x2 = x2; g.ldx2 = ldx2; g.lvx2 = ldx_level2; g.y2 = y2; g.ldy2 = ldy2; g.lvy2 = ldy_level2;
-  g.yprev = yprev; g.out = out; g.N = N; g.L = L; g.E = E; g.T = T;
+  const AffArgs g = aff_args(x1, ldx1, ldx_level1, y1, ldy1, ldy_level1, x2, ldx2, ldx_level2, y2, ldy2, ldy_level2, yprev, out, N, L,
+                             E, T);
   return affinity_launch(KID_HIE_AFF_LEVELS, g, G, epi, false, (hipStream_t)stream);
 }
 
@@ -738,11 +738,9 @@ int vqf_hie_affinity_levels_len(const float* x1, int ldx1, int ldx_level1, const
                                 const float* x2, int ldx2, int ldx_level2, const float* y2, int ldy2, int ldy_level2,
                                 int G, int epi, const float* yprev, const int* lens, int N, int L, int E, int T, float* out,
                                 void* stream) {
-  if (!lens || (((uintptr_t)lens) & 3)) return VQF_E_BADARG;
-  AffArgs g = {};
-  g.x1 = x1; g.ldx1 = ldx1; g.lvx1 = ldx_level1; g.y1 = y1; g.ldy1 = ldy1; g.lvy1 = ldy_level1;
-  g.x2 = x2; g.ldx2 = ldx2; g.lvx2 = ldx_level2; g.y2 = y2; g.ldy2 = ldy2; g.lvy2 = ldy_level2;
-  g.yprev = yprev; g.out = out; g.N = N; g.L = L; g.E = E; g.T = T; g.lens = lens;
+  if (!VqfRegions::ok(lens)) return VQF_E_BADARG;
+  AffArgs g = aff_args(x1, ldx1, ldx_level1, y1, ldy1, ldy_level1, x2, ldx2, ldx_level2, y2, ldy2, ldy_level2, yprev, out, N, L, E, T);
+  g.lens = lens;
   return affinity_launch(KID_HIE_AFF_LEVELS, g, G, epi, false, (hipStream_t)stream);
 }
 
@@ -750,11 +748,9 @@ int vqf_hie_affinity_levels_regions(const float* x1, int ldx1, int ldx_level1, c
                                     const float* x2, int ldx2, int ldx_level2, const float* y2, int ldy2, int ldy_level2,
                                     int G, int epi, const float* yprev, const int* lens, const int* rlens, int N, int L, int E,
                                     int T, float* out, void* stream) {
-  if (!counts_ok(rlens) || (lens && (((uintptr_t)lens) & 3))) return VQF_E_BADARG;
-  AffArgs g = {};
-  g.x1 = x1; g.ldx1 = ldx1; g.lvx1 = ldx_level1; g.y1 = y1; g.ldy1 = ldy1; g.lvy1 = ldy_level1;
-  g.x2 = x2; g.ldx2 = ldx2; g.lvx2 = ldx_level2; g.y2 = y2; g.ldy2 = ldy2; g.lvy2 = ldy_level2;
-  g.yprev = yprev; g.out = out; g.N = N; g.L = L; g.E = E; g.T = T; g.lens = lens; g.rlens = rlens;
+  if (!VqfRegions::ok(rlens) || !VqfRegions::aligned(lens)) return VQF_E_BADARG;
+  AffArgs g = aff_args(x1, ldx1, ldx_level1, y1, ldy1, ldy_level1, x2, ldx2, ldx_level2, y2, ldy2, ldy_level2, yprev, out, N, L, E, T);
+  g.lens = lens; g.rlens = rlens;
   return affinity_launch(KID_HIE_AFF_LEVELS, g, G, epi, false, (hipStream_t)stream);
 }
 

@@ -219,6 +219,59 @@ __global__ void __launch_bounds__(768) guided_logits_bwd_grouped_kernel(const fl
   *reinterpret_cast<f32x4*>(part_w + ((long long)u * gridDim.x + blockIdx.x) * GE + c) = sw;
 }
 
+// ---- the launchers of every form, behind the refusals of its entry point.  rg (VqfRegions, common.h; host side only) says where
+// the Xh rows are: U owners (the plain forms fill U = N), idx / order + grp_off when questions share them, roff / Rtot when packed.
+int guided_fwd_launch(const float* Xh, int ldx, const float* gp, const float* w, int N, int S, int E, int G, float* logits,
+                      void* stream, const VqfRegions& rg) {
+  if (!aligned16(Xh) || !aligned16(gp) || !aligned16(w)) return VQF_E_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  const int rows = gl_rows(S, GL_FWD_ROWS);
+  const dim3 grid(gl_chunks(S, rows), N);
+  const size_t lds = (size_t)2 * G * E * sizeof(float);
+  auto go = [&](auto g, auto pack) {
+    VQF_LAUNCH(KID_GUIDED_FWD, (guided_logits_fwd_kernel<decltype(g)::value, decltype(pack)::value>), grid, dim3(256), lds, s, Xh,
+               ldx, gp, w, S, E, rows, logits, rg.idx, rg.U, rg.roff, rg.Rtot);
+  };
+  vqf_dispatch_G(G, [&](auto g) { if (rg.packed()) go(g, std::true_type()); else go(g, std::false_type()); });
+  return vqf_last_error();
+}
+
+// ws: part_w (U * chunks rows of G E), then part_g (N * chunks rows; dgp itself with one chunk), then the reducer's
+// VQF_REDUCE_SPLITS rows.  The plain form is U = N: part_w, part_g with nb = N * chunks rows each, the layout it always had.
+// The chunks are those of S in the packed forms too: the padded kernels' partial rows.
+int guided_bwd_launch(const float* dlogits, const float* Xh, int ldx, const float* gp, const float* w, int N, int S, int E, int G,
+                      float* dXh, int lddx, float* dgp, float* dw, void* ws, size_t ws_bytes, void* stream, const VqfRegions& rg) {
+  if (!aligned16(Xh) || !aligned16(gp) || !aligned16(w) || !aligned16(dXh) || !aligned16(dgp) || !aligned16(ws)) return VQF_E_ALIGN;
+  if (!ws || ws_bytes < vqf_guided_logits_bwd_grouped_ws_bytes(N, rg.U, S, E, G)) return VQF_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const int GE = G * E, U = rg.U;
+  const int rows = gl_rows(S, GL_BWD_ROWS), chunks = gl_chunks(S, rows);
+  float* part_w = (float*)ws;
+  float* part_g = chunks == 1 ? dgp : part_w + (size_t)U * chunks * GE;
+  float* scratch = part_w + ((size_t)U + N) * chunks * GE;
+  const dim3 grid(chunks, U), block(((GE / 4 + 63) / 64) * 64);
+  auto own = [&](auto g, auto pack) {
+    VQF_LAUNCH(KID_GUIDED_BWD, (guided_logits_bwd_kernel<decltype(g)::value, decltype(pack)::value>), grid, block, 0, s, dlogits, Xh,
+               ldx, gp, w, S, E, rows, dXh, lddx, part_g, part_w, rg.roff, rg.Rtot);
+  };
+  auto shared = [&](auto g, auto pack) {
+    VQF_LAUNCH(KID_GUIDED_BWD, (guided_logits_bwd_grouped_kernel<decltype(g)::value, decltype(pack)::value>), grid, block, 0, s,
+               dlogits, Xh, ldx, gp, w, rg.order, rg.grp_off, N, S, E, rows, dXh, lddx, part_g, part_w, rg.roff, rg.Rtot);
+  };
+  vqf_dispatch_G(G, [&](auto g) {
+    if (rg.grouped()) { if (rg.packed()) shared(g, std::true_type()); else shared(g, std::false_type()); }
+    else if (rg.packed()) own(g, std::true_type());
+    else own(g, std::false_type());
+  });
+  int rc = vqf_last_error();
+  if (rc) return rc;
+  if (chunks > 1) {
+    rc = vqf_group_reduce_f32(part_g, N, chunks, GE, dgp, stream);           // dgp[n] = its chunks' rows, in chunk order
+    if (rc) return rc;
+  }
+  return vqf_colreduce_2stage(part_w, U * chunks, GE, dw, scratch, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -232,19 +285,7 @@ int vqf_guided_logits_fwd(const float* Xh, int ldx, const float* gp, const float
                           void* stream) {
   if (!Xh || !w || !logits || N <= 0 || S <= 0 || E <= 0 || G <= 0 || ldx < G * E || (ldx % 4)) return VQF_E_BADARG;
   if (!vqf_guided_logits_supported(N, S, E, G)) return VQF_E_UNSUPPORTED;
-  if (!aligned16(Xh) || !aligned16(gp) || !aligned16(w)) return VQF_E_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
-  const int rows = gl_rows(S, GL_FWD_ROWS);
-  const dim3 grid(gl_chunks(S, rows), N);
-  const size_t lds = (size_t)2 * G * E * sizeof(float);
-#define VQF_GL(G_) \
-  VQF_LAUNCH(KID_GUIDED_FWD, (guided_logits_fwd_kernel<G_>), grid, dim3(256), lds, s, Xh, ldx, gp, w, S, E, rows, logits, \
-             (const int*)nullptr, N, (const int*)nullptr, 0)
-  if (G == 3) VQF_GL(3);
-  else if (G == 2) VQF_GL(2);
-  else VQF_GL(1);
-#undef VQF_GL
-  return vqf_last_error();
+  return guided_fwd_launch(Xh, ldx, gp, w, N, S, E, G, logits, stream, {.U = N});
 }
 
 int vqf_guided_logits_grouped_supported(int N, int U, int S, int E, int G) {
@@ -253,23 +294,11 @@ int vqf_guided_logits_grouped_supported(int N, int U, int S, int E, int G) {
 
 int vqf_guided_logits_fwd_grouped(const float* Xh, int ldx, const float* gp, const float* w, const int* idx, int N, int U, int S,
                                   int E, int G, float* logits, void* stream) {
-  if (!Xh || !gp || !w || !idx || !logits || N <= 0 || U <= 0 || S <= 0 || E <= 0 || G <= 0 || ldx < G * E || (ldx % 4) ||
-      (((uintptr_t)idx) & 3))
+  if (!Xh || !gp || !w || !VqfRegions::ok(idx) || !logits || N <= 0 || U <= 0 || S <= 0 || E <= 0 || G <= 0 || ldx < G * E ||
+      (ldx % 4))
     return VQF_E_BADARG;
   if (!vqf_guided_logits_grouped_supported(N, U, S, E, G)) return VQF_E_UNSUPPORTED;
-  if (!aligned16(Xh) || !aligned16(gp) || !aligned16(w)) return VQF_E_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
-  const int rows = gl_rows(S, GL_FWD_ROWS);
-  const dim3 grid(gl_chunks(S, rows), N);
-  const size_t lds = (size_t)2 * G * E * sizeof(float);
-#define VQF_GL(G_) \
-  VQF_LAUNCH(KID_GUIDED_FWD, (guided_logits_fwd_kernel<G_>), grid, dim3(256), lds, s, Xh, ldx, gp, w, S, E, rows, logits, idx, U, \
-             (const int*)nullptr, 0)
-  if (G == 3) VQF_GL(3);
-  else if (G == 2) VQF_GL(2);
-  else VQF_GL(1);
-#undef VQF_GL
-  return vqf_last_error();
+  return guided_fwd_launch(Xh, ldx, gp, w, N, S, E, G, logits, stream, {.idx = idx, .U = U});
 }
 
 size_t vqf_guided_logits_bwd_ws_bytes(int N, int S, int E, int G) {
@@ -284,30 +313,7 @@ int vqf_guided_logits_bwd(const float* dlogits, const float* Xh, int ldx, const 
       (ldx % 4) || (lddx % 4))
     return VQF_E_BADARG;
   if (!vqf_guided_logits_supported(N, S, E, G)) return VQF_E_UNSUPPORTED;
-  if (!aligned16(Xh) || !aligned16(gp) || !aligned16(w) || !aligned16(dXh) || !aligned16(dgp) || !aligned16(ws)) return VQF_E_ALIGN;
-  if (!ws || ws_bytes < vqf_guided_logits_bwd_ws_bytes(N, S, E, G)) return VQF_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  const int GE = G * E;
-  const int rows = gl_rows(S, GL_BWD_ROWS), chunks = gl_chunks(S, rows);
-  const int nb = N * chunks;
-  float* part_w = (float*)ws;
-  float* part_g = chunks == 1 ? dgp : part_w + (size_t)nb * GE;
-  float* scratch = part_w + (size_t)2 * nb * GE;
-  const dim3 grid(chunks, N), block(((GE / 4 + 63) / 64) * 64);
-#define VQF_GL(G_)                                                                                                              \
-  VQF_LAUNCH(KID_GUIDED_BWD, (guided_logits_bwd_kernel<G_>), grid, block, 0, s, dlogits, Xh, ldx, gp, w, S, E, rows, dXh, lddx, \
-             part_g, part_w, (const int*)nullptr, 0)
-  if (G == 3) VQF_GL(3);
-  else if (G == 2) VQF_GL(2);
-  else VQF_GL(1);
-#undef VQF_GL
-  int rc = vqf_last_error();
-  if (rc) return rc;
-  if (chunks > 1) {
-    rc = vqf_group_reduce_f32(part_g, N, chunks, GE, dgp, stream);           // dgp[n] = its chunks' rows, in chunk order
-    if (rc) return rc;
-  }
-  return vqf_colreduce_2stage(part_w, nb, GE, dw, scratch, s);
+  return guided_bwd_launch(dlogits, Xh, ldx, gp, w, N, S, E, G, dXh, lddx, dgp, dw, ws, ws_bytes, stream, {.U = N});
 }
 
 size_t vqf_guided_logits_bwd_grouped_ws_bytes(int N, int U, int S, int E, int G) {
@@ -319,33 +325,12 @@ size_t vqf_guided_logits_bwd_grouped_ws_bytes(int N, int U, int S, int E, int G)
 int vqf_guided_logits_bwd_grouped(const float* dlogits, const float* Xh, int ldx, const float* gp, const float* w, const int* order,
                                   const int* grp_off, int N, int U, int S, int E, int G, float* dXh, int lddx, float* dgp, float* dw,
                                   void* ws, size_t ws_bytes, void* stream) {
-  if (!dlogits || !Xh || !gp || !w || !order || !grp_off || !dXh || !dgp || !dw || N <= 0 || U <= 0 || S <= 0 || E <= 0 || G <= 0 ||
-      ldx < G * E || lddx < G * E || (ldx % 4) || (lddx % 4) || (((uintptr_t)order) & 3) || (((uintptr_t)grp_off) & 3))
+  if (!dlogits || !Xh || !gp || !w || !VqfRegions::ok(order) || !VqfRegions::ok(grp_off) || !dXh || !dgp || !dw || N <= 0 ||
+      U <= 0 || S <= 0 || E <= 0 || G <= 0 || ldx < G * E || lddx < G * E || (ldx % 4) || (lddx % 4))
     return VQF_E_BADARG;
   if (!vqf_guided_logits_grouped_supported(N, U, S, E, G)) return VQF_E_UNSUPPORTED;
-  if (!aligned16(Xh) || !aligned16(gp) || !aligned16(w) || !aligned16(dXh) || !aligned16(dgp) || !aligned16(ws)) return VQF_E_ALIGN;
-  if (!ws || ws_bytes < vqf_guided_logits_bwd_grouped_ws_bytes(N, U, S, E, G)) return VQF_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  const int GE = G * E;
-  const int rows = gl_rows(S, GL_BWD_ROWS), chunks = gl_chunks(S, rows);
-  float* part_w = (float*)ws;                                                 // (U * chunks, GE)
-  float* part_g = chunks == 1 ? dgp : part_w + (size_t)U * chunks * GE;       // (N * chunks, GE)
-  float* scratch = part_w + ((size_t)U + N) * chunks * GE;
-  const dim3 grid(chunks, U), block(((GE / 4 + 63) / 64) * 64);
-#define VQF_GL(G_)                                                                                                               \
-  VQF_LAUNCH(KID_GUIDED_BWD, (guided_logits_bwd_grouped_kernel<G_>), grid, block, 0, s, dlogits, Xh, ldx, gp, w, order, grp_off, \
-             N, S, E, rows, dXh, lddx, part_g, part_w, (const int*)nullptr, 0)
-  if (G == 3) VQF_GL(3);
-  else if (G == 2) VQF_GL(2);
-  else VQF_GL(1);
-#undef VQF_GL
-  int rc = vqf_last_error();
-  if (rc) return rc;
-  if (chunks > 1) {
-    rc = vqf_group_reduce_f32(part_g, N, chunks, GE, dgp, stream);           // dgp[n] = its chunks' rows, in chunk order
-    if (rc) return rc;
-  }
-  return vqf_colreduce_2stage(part_w, U * chunks, GE, dw, scratch, s);
+  return guided_bwd_launch(dlogits, Xh, ldx, gp, w, N, S, E, G, dXh, lddx, dgp, dw, ws, ws_bytes, stream,
+                           {.order = order, .grp_off = grp_off, .U = U});
 }
 
 // ---- the packed forms: Xh / dXh (R, .) hold the real rows only, roff (owners + 1) int32 row offsets --------------------------
@@ -353,33 +338,18 @@ int vqf_guided_logits_packed_supported(int N, int U, int R, int S, int E, int G)
   return vqf_guided_logits_grouped_supported(N, U, S, E, G) && R >= 1 && R < (1 << 29);
 }
 
-// what both packed entry points refuse first; idx / order / grp_off decide the form (NULL: plain, U must equal N)
-static int guided_packed_args(const int* own, const int* roff, int N, int U, int R, int S, int E, int G) {
-  if (!roff || ((((uintptr_t)own) | ((uintptr_t)roff)) & 3) || R <= 0 || N <= 0 || U <= 0 || S <= 0 || E <= 0 || G <= 0)
-    return VQF_E_BADARG;
-  if (!own && U != N) return VQF_E_BADARG;
-  if (!vqf_guided_logits_packed_supported(N, U, R, S, E, G)) return VQF_E_UNSUPPORTED;
-  return VQF_OK;
+// what both packed entry points refuse after their operands; own = idx / order decides the form (NULL: plain, U must equal N)
+static int guided_packed_refusal(const int* own, const VqfRegions& rg, int N, int S, int E, int G) {
+  if (!rg.packed_ok(own, N) || N <= 0 || S <= 0 || E <= 0 || G <= 0) return VQF_E_BADARG;
+  return vqf_guided_logits_packed_supported(N, rg.U, rg.Rtot, S, E, G) ? VQF_OK : VQF_E_UNSUPPORTED;
 }
 
 int vqf_guided_logits_fwd_packed(const float* Xh, int ldx, const float* gp, const float* w, const int* idx, const int* roff, int N,
                                  int U, int R, int S, int E, int G, float* logits, void* stream) {
   if (!Xh || !w || !logits || ldx < G * E || (ldx % 4)) return VQF_E_BADARG;
-  const int rc = guided_packed_args(idx, roff, N, U, R, S, E, G);
-  if (rc) return rc;
-  if (!aligned16(Xh) || !aligned16(gp) || !aligned16(w)) return VQF_E_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
-  const int rows = gl_rows(S, GL_FWD_ROWS);
-  const dim3 grid(gl_chunks(S, rows), N);
-  const size_t lds = (size_t)2 * G * E * sizeof(float);
-#define VQF_GL(G_)                                                                                                             \
-  VQF_LAUNCH(KID_GUIDED_FWD, (guided_logits_fwd_kernel<G_, true>), grid, dim3(256), lds, s, Xh, ldx, gp, w, S, E, rows, logits, idx, \
-             U, roff, R)
-  if (G == 3) VQF_GL(3);
-  else if (G == 2) VQF_GL(2);
-  else VQF_GL(1);
-#undef VQF_GL
-  return vqf_last_error();
+  const VqfRegions rg = {.idx = idx, .U = U, .roff = roff, .Rtot = R};
+  const int rc = guided_packed_refusal(idx, rg, N, S, E, G);
+  return rc ? rc : guided_fwd_launch(Xh, ldx, gp, w, N, S, E, G, logits, stream, rg);
 }
 
 size_t vqf_guided_logits_bwd_packed_ws_bytes(int N, int U, int S, int E, int G) {
@@ -390,39 +360,12 @@ int vqf_guided_logits_bwd_packed(const float* dlogits, const float* Xh, int ldx,
                                  const int* grp_off, const int* roff, int N, int U, int R, int S, int E, int G, float* dXh, int lddx,
                                  float* dgp, float* dw, void* ws, size_t ws_bytes, void* stream) {
   if (!dlogits || !Xh || !w || !dXh || !dgp || !dw || ldx < G * E || lddx < G * E || (ldx % 4) || (lddx % 4) ||
-      (order != nullptr) != (grp_off != nullptr) || (order && !gp) || (((uintptr_t)grp_off) & 3))
+      (order != nullptr) != (grp_off != nullptr) || (order && !gp) || !VqfRegions::aligned(grp_off))
     return VQF_E_BADARG;
-  int rc = guided_packed_args(order, roff, N, U, R, S, E, G);
-  if (rc) return rc;
-  if (!aligned16(Xh) || !aligned16(gp) || !aligned16(w) || !aligned16(dXh) || !aligned16(dgp) || !aligned16(ws)) return VQF_E_ALIGN;
-  if (!ws || ws_bytes < vqf_guided_logits_bwd_packed_ws_bytes(N, U, S, E, G)) return VQF_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  const int GE = G * E;
-  const int rows = gl_rows(S, GL_BWD_ROWS), chunks = gl_chunks(S, rows);     // the chunks of S: the padded kernels' partial rows
-  float* part_w = (float*)ws;                                                 // (U * chunks, GE)
-  float* part_g = chunks == 1 ? dgp : part_w + (size_t)U * chunks * GE;       // (N * chunks, GE)
-  float* scratch = part_w + ((size_t)U + N) * chunks * GE;
-  const dim3 grid(chunks, U), block(((GE / 4 + 63) / 64) * 64);
-#define VQF_GL(G_)                                                                                                                  \
-  do {                                                                                                                              \
-    if (order)                                                                                                                      \
-      VQF_LAUNCH(KID_GUIDED_BWD, (guided_logits_bwd_grouped_kernel<G_, true>), grid, block, 0, s, dlogits, Xh, ldx, gp, w, order,   \
-                 grp_off, N, S, E, rows, dXh, lddx, part_g, part_w, roff, R);                                                      \
-    else                                                                                                                            \
-      VQF_LAUNCH(KID_GUIDED_BWD, (guided_logits_bwd_kernel<G_, true>), grid, block, 0, s, dlogits, Xh, ldx, gp, w, S, E, rows, dXh, \
-                 lddx, part_g, part_w, roff, R);                                                                                    \
-  } while (0)
-  if (G == 3) VQF_GL(3);
-  else if (G == 2) VQF_GL(2);
-  else VQF_GL(1);
-#undef VQF_GL
-  rc = vqf_last_error();
-  if (rc) return rc;
-  if (chunks > 1) {
-    rc = vqf_group_reduce_f32(part_g, N, chunks, GE, dgp, stream);           // dgp[n] = its chunks' rows, in chunk order
-    if (rc) return rc;
-  }
-  return vqf_colreduce_2stage(part_w, U * chunks, GE, dw, scratch, s);
+  const VqfRegions rg = {.order = order, .grp_off = grp_off, .U = U, .roff = roff, .Rtot = R};
+  const int rc = guided_packed_refusal(order, rg, N, S, E, G);
+  return rc ? rc : guided_bwd_launch(dlogits, Xh, ldx, gp, w, N, S, E, G, dXh, lddx, dgp, dw, ws, ws_bytes, stream, rg);
 }
 
 }  // extern "C"
+
