@@ -1038,6 +1038,33 @@ typedef struct VqfAdamTensor {
 int vqf_adam_step(const VqfAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
                   double weight_decay, long long step, void* stream);
 
+/* Gradient-norm clipping (torch.nn.utils.clip_grad_norm_, norm_type 2, error_if_nonfinite off) and the optimizer steps that read
+ * the clip coefficient from the device.  Nothing is read back to the host; no atomics: the same gradients give the same bits.
+ *   vqf_grad_norm_clip   norm[0] = (float)sqrt(sum of g^2 over every tensor), coef[0] = min(1, max_norm / (norm + 1e-6)) in fp32
+ *                        as torch forms it (reciprocal, times (float)max_norm, clamp): norm NaN -> coef NaN, norm Inf -> coef 0,
+ *                        all-zero gradients -> norm 0, coef 1.  Only `grad` and `n` of each descriptor are read.  One partial
+ *                        sum per 4096 elements of a tensor goes to ws (fp32; vqf_grad_norm_ws_bytes), VQF_ADAM_MAX_TENSORS
+ *                        tensors per launch, then one single-workgroup launch adds the partials in double in a fixed order.
+ *                        max_norm > 0 (+inf allowed: coef 1 for a finite norm); norm / coef: device pointers.
+ *   vqf_grad_scale       grad[i] *= scale[0] for every tensor (one fp32 multiply; writes through `grad`); scale: device pointer.
+ *   vqf_adam_step_scaled vqf_adam_step on g * grad_scale[0] (one fp32 rounding, before weight decay); the gradient in memory is
+ *                        not written.  grad_scale: a non-NULL device pointer (the coef of vqf_grad_norm_clip): the bits of
+ *                        vqf_grad_scale followed by vqf_adam_step.
+ *   vqf_adamax_step      torch.optim.Adamax (single-tensor path); the exp_avg_sq slot of the descriptor holds exp_inf:
+ *                          g += wd*p;  m += (g-m)(1-b1);  u = max(u*b2, |g| + eps);  p -= lr/(1-b1^step) * m / u
+ *                        grad_scale: NULL, or as above.
+ * count < 0, a negative n, a NULL tensors / norm / coef / scale / needed pointer of a non-empty tensor, max_norm <= 0 or NaN,
+ * step < 1: VQF_E_BADARG; a ws too small: VQF_E_WORKSPACE; norm / coef / ws / scale not 4-byte aligned: VQF_E_ALIGN -- before
+ * any GPU call (of the launch at hand: VQF_ADAM_MAX_TENSORS tensors).  Empty tensors (n == 0) are skipped. */
+size_t vqf_grad_norm_ws_bytes(const VqfAdamTensor* tensors, int count);
+int vqf_grad_norm_clip(const VqfAdamTensor* tensors, int count, double max_norm, float* norm, float* coef, void* ws,
+                       size_t ws_bytes, void* stream);
+int vqf_grad_scale(const VqfAdamTensor* tensors, int count, const float* scale, void* stream);
+int vqf_adam_step_scaled(const VqfAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
+                         double weight_decay, long long step, const float* grad_scale, void* stream);
+int vqf_adamax_step(const VqfAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
+                    double weight_decay, long long step, const float* grad_scale, void* stream);
+
 /* --------------------------------------------------------------------------
  * HBM yardsticks (measurement only; bench.py's `hbm_yardsticks`): what a plain streaming kernel of this library reaches,
  * in the units the HBM-bound stages above are priced in.  16 bytes per lane, grid-stride, the launch shape that streams 2 GB

@@ -26,6 +26,7 @@ def __getattr__(name):
         "ops": ".host.ops", "functions": ".host.functions", "parallel": ".host.parallel",
         "train_step": ".host.train_step", "CrossEntropyLoss": ".host.train_step",
         "KLDivLoss": ".host.train_step", "Adam": ".host.train_step",
+        "Adamax": ".host.train_step", "clip_grad_norm_": ".host.train_step",
         "data_loader": ".host.data_loader", "FeatureStager": ".host.data_loader", "group_batch": ".host.data_loader",
         "pad_region_features": ".host.data_loader", "pack_region_features": ".host.data_loader",
         "RegionStager": ".host.data_loader", "stage_regions": ".host.data_loader", "pack_into": ".host.data_loader",

@@ -76,6 +76,10 @@ enum VqfKernelId {
   KID_TANH_DROP_PACKED_BWD,
   KID_BCE_LOSS,
   KID_BCE_LOSS_SPARSE,
+  KID_GRAD_SUMSQ,
+  KID_GRAD_SCALE,
+  KID_ADAM_SCALED,
+  KID_ADAMAX,
   KID_COUNT
 };
 

@@ -52,7 +52,8 @@ const char* const kNames[KID_COUNT] = {
     "phrase_ngram_fwd", "phrase_ngram_bwd", "hie_affinity_levels", "guided_logits_fwd", "guided_logits_bwd",
     "ce_loss_pred", "answer_match_rows", "topk_rows", "glimpse_dfeat_grouped", "row_block_gather", "row_block_group_sum",
     "mfb_fuse_bwd_image", "zero_cols_len", "tanh_dropout_unpack_fwd", "tanh_dropout_pack_bwd", "region_rows_stage",
-    "tanh_dropout_packed_fwd", "tanh_dropout_packed_bwd", "bce_loss", "bce_loss_sparse"};
+    "tanh_dropout_packed_fwd", "tanh_dropout_packed_bwd", "bce_loss", "bce_loss_sparse",
+    "grad_sumsq", "grad_scale", "adam_step_scaled", "adamax_step"};
 
 hipEvent_t get_event() {
   std::lock_guard<std::mutex> lk(g_mu);

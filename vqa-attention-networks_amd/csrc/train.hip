@@ -11,7 +11,10 @@
 //    hard labels for the models that return logits): one block per row, one read of the row -- row loss, dlogits, the row's
 //    arg-max and the soft score of the predicted answer; the target dense (N,A) or K sparse (id, score) slots per row.
 //  * Adam: m, v, p updated in place in the order of torch's single-tensor path; HBM-bound
-//    (16 B read + 12 B written per element).
+//    (16 B read + 12 B written per element).  Adamax (torch.optim.Adamax; not in the reference) is the same kernel template.
+//  * gradient-norm clipping (torch.nn.utils.clip_grad_norm_, norm_type 2; not in the reference): a multi-tensor sum of squares
+//    (4 B read per element, one partial per block, no atomics), a single-block finish in double that leaves the norm and the
+//    clip coefficient on the device, an in-place multi-tensor scale -- or the optimizer kernel reading the coefficient itself.
 #include "common.h"
 #include <math.h>
 
@@ -306,7 +309,7 @@ __global__ __launch_bounds__(TR_THREADS) void kldiv_kernel(const float* __restri
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// ---- Adam -------------------------------------------------------------------
+// ---- Adam / Adamax, gradient-norm clipping ------------------------------------
 constexpr int ADAM_MAX_TENSORS = VQF_ADAM_MAX_TENSORS;
 constexpr int ADAM_CHUNK = TR_THREADS * 16;      // elements per block
 struct AdamTable {
@@ -318,7 +321,9 @@ struct AdamTable {
   int block0[ADAM_MAX_TENSORS + 1];   // first block of tensor i
   int count;
 };
+// Adamax reads beta2, one_m_beta1, eps, wd and step_size (= clr = lr / (1 - beta1^step)); v holds exp_inf
 struct AdamHyper { float beta1, beta2, one_m_beta1, one_m_beta2, eps, wd, step_size, bc2_sqrt; };
+constexpr int RULE_ADAM = 0, RULE_ADAMAX = 1;
 
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamHyper& h) {
   if (h.wd != 0.f) g = g + h.wd * p;
@@ -327,8 +332,24 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
   float denom = sqrtf(v) / h.bc2_sqrt + h.eps;
   p = p - h.step_size * (m / denom);               // param.addcdiv_(exp_avg, denom, -step_size)
 }
+__device__ __forceinline__ void adamax_one(float& p, float g, float& m, float& u, const AdamHyper& h) {
+  if (h.wd != 0.f) g = g + h.wd * p;
+  m = m + (g - m) * h.one_m_beta1;                 // exp_avg.lerp_(grad, 1 - beta1)
+  const float a = u * h.beta2, b = fabsf(g) + h.eps;
+  u = (b > a || b != b) ? b : a;                   // torch.maximum(exp_inf.mul_(beta2), grad.abs().add_(eps)): NaN on either side stays
+  p = p - h.step_size * (m / u);                   // param.addcdiv_(exp_avg, exp_inf, -clr)
+}
+template <int RULE>
+__device__ __forceinline__ void optim_one(float& p, float g, float& m, float& v, const AdamHyper& h) {
+  if (RULE == RULE_ADAMAX) adamax_one(p, g, m, v, h); else adam_one(p, g, m, v, h);
+}
 
-__global__ __launch_bounds__(TR_THREADS) void adam_kernel(const AdamTable tb, const AdamHyper h) {
+// SCALED: the gradient the update sees is g * *grad_scale (one fp32 rounding, before weight decay; the clip coefficient of
+// grad_norm_finish_kernel, loaded once per block); the gradient in memory is not written.
+// Scale: empty (vqf_adam_step's kernel is <RULE_ADAM>, under the kernel arguments it has always had), or one const float*.
+template <int RULE, typename... Scale>
+__global__ __launch_bounds__(TR_THREADS) void adam_kernel(const AdamTable tb, const AdamHyper h, Scale... grad_scale) {
+  constexpr bool SCALED = sizeof...(Scale) != 0;
   // block -> tensor (uniform scan of <= 32 entries held in kernarg SGPRs)
   int ti = 0;
   const int b = blockIdx.x;
@@ -340,6 +361,8 @@ __global__ __launch_bounds__(TR_THREADS) void adam_kernel(const AdamTable tb, co
   const long long n = tb.n[ti];
   const long long base = (long long)(b - tb.block0[ti]) * ADAM_CHUNK;
   const bool vec = aligned16_dev(p) && aligned16_dev(g) && aligned16_dev(m) && aligned16_dev(v);
+  float gs = 1.f;
+  if constexpr (SCALED) gs = *(grad_scale, ...);
   if (vec && base + ADAM_CHUNK <= n) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -349,7 +372,9 @@ __global__ __launch_bounds__(TR_THREADS) void adam_kernel(const AdamTable tb, co
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float pe = pp[e], me = mm[e], ve = vv[e];
-        adam_one(pe, gg[e], me, ve, h);
+        float ge = gg[e];
+        if constexpr (SCALED) ge = ge * gs;
+        optim_one<RULE>(pe, ge, me, ve, h);
         pp[e] = pe; mm[e] = me; vv[e] = ve;
       }
       *(f32x4*)(p + i) = pp; *(f32x4*)(m + i) = mm; *(f32x4*)(v + i) = vv;
@@ -359,12 +384,176 @@ __global__ __launch_bounds__(TR_THREADS) void adam_kernel(const AdamTable tb, co
       long long i = base + j * TR_THREADS + threadIdx.x;
       if (i < n) {
         float pp = p[i], mm = m[i], vv = v[i];
-        adam_one(pp, g[i], mm, vv, h);
+        float ge = g[i];
+        if constexpr (SCALED) ge = ge * gs;
+        optim_one<RULE>(pp, ge, mm, vv, h);
         p[i] = pp; m[i] = mm; v[i] = vv;
       }
     }
   }
 }
+
+// The gradients of a launch of the norm / scale passes: the block -> tensor mapping of adam_kernel.
+struct GradTable {
+  float* g[ADAM_MAX_TENSORS];
+  long long n[ADAM_MAX_TENSORS];
+  int block0[ADAM_MAX_TENSORS + 1];
+  int count;
+};
+
+// part[blockIdx.x] = the sum of the squares of this block's ADAM_CHUNK elements: 16 squares and adds per thread in index order
+// (either path), the wave butterfly, the four wave sums in order.  No atomics: the same memory gives the same bits.
+__global__ __launch_bounds__(TR_THREADS) void grad_sumsq_kernel(const GradTable tb, float* __restrict__ part) {
+  __shared__ float sh[4];
+  int ti = 0;
+  const int b = blockIdx.x;
+  while (ti + 1 < tb.count && b >= tb.block0[ti + 1]) ++ti;
+  const float* __restrict__ g = tb.g[ti];
+  const long long n = tb.n[ti];
+  const long long base = (long long)(b - tb.block0[ti]) * ADAM_CHUNK;
+  float s = 0.f;
+  if (aligned16_dev(g) && base + ADAM_CHUNK <= n) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long long i = base + (long long)(j * TR_THREADS + threadIdx.x) * 4;
+      const f32x4 x = *(const f32x4*)(g + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s += x[e] * x[e];
+    }
+  } else {
+    for (int j = 0; j < 16; ++j) {
+      const long long i = base + j * TR_THREADS + threadIdx.x;
+      if (i < n) {
+        const float x = g[i];
+        s += x * x;
+      }
+    }
+  }
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) part[b] = s;
+}
+
+// one workgroup: norm = (float)sqrt(sum of part[0..P) in double, fixed order), coef = min(1, max_norm / (norm + 1e-6)) in fp32 as
+// torch.nn.utils.clip_grad_norm_ forms it -- `max_norm / tensor` is tensor.reciprocal() * max_norm, then clamp(max = 1), which
+// keeps a NaN (norm NaN -> coef NaN) and turns norm = Inf into 0
+__global__ __launch_bounds__(TR_THREADS) void grad_norm_finish_kernel(const float* __restrict__ part, long long P,
+                                                                      float max_norm, float* __restrict__ norm,
+                                                                      float* __restrict__ coef) {
+  __shared__ double shd[4];
+  double s = 0.0;
+  long long i = threadIdx.x;
+  for (; i + 7LL * TR_THREADS < P; i += 8LL * TR_THREADS) {      // eight loads in flight (the pass is latency-bound), added in index order
+    float x[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) x[k] = part[i + (long long)k * TR_THREADS];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += (double)x[k];
+  }
+  for (; i < P; i += TR_THREADS) s += (double)part[i];
+  s = block_sum(s, shd);
+  if (threadIdx.x == 0) {
+    const float nm = (float)sqrt(s);
+    float c = (1.0f / (nm + 1e-6f)) * max_norm;
+    if (c > 1.0f) c = 1.0f;
+    norm[0] = nm;
+    coef[0] = c;
+  }
+}
+
+// g *= *scale, one fp32 multiply per element
+__global__ __launch_bounds__(TR_THREADS) void grad_scale_kernel(const GradTable tb, const float* __restrict__ scale) {
+  int ti = 0;
+  const int b = blockIdx.x;
+  while (ti + 1 < tb.count && b >= tb.block0[ti + 1]) ++ti;
+  float* __restrict__ g = tb.g[ti];
+  const long long n = tb.n[ti];
+  const long long base = (long long)(b - tb.block0[ti]) * ADAM_CHUNK;
+  const float c = *scale;
+  if (aligned16_dev(g) && base + ADAM_CHUNK <= n) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long long i = base + (long long)(j * TR_THREADS + threadIdx.x) * 4;
+      f32x4 x = *(const f32x4*)(g + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) x[e] = x[e] * c;
+      *(f32x4*)(g + i) = x;
+    }
+  } else {
+    for (int j = 0; j < 16; ++j) {
+      const long long i = base + j * TR_THREADS + threadIdx.x;
+      if (i < n) g[i] = g[i] * c;
+    }
+  }
+}
+
+// The next launch's worth of `tensors` from index i on: up to ADAM_MAX_TENSORS non-empty entries whose blocks fit one grid.
+// ALL: every pointer of a descriptor is needed (the optimizer steps); otherwise grad and n only.  Returns VQF_OK with
+// tb.count == 0 when nothing is left.
+template <typename Table, typename Put>
+int next_table(const VqfAdamTensor* tensors, int count, int& i, bool all, Table& tb, long long& blocks, Put put) {
+  tb.count = 0;
+  blocks = 0;
+  while (i < count && tb.count < ADAM_MAX_TENSORS) {
+    const VqfAdamTensor& t = tensors[i];
+    if (t.n < 0) return VQF_E_BADARG;
+    if (t.n == 0) { ++i; continue; }
+    if (!t.grad || (all && (!t.param || !t.exp_avg || !t.exp_avg_sq))) return VQF_E_BADARG;
+    const long long nb = (t.n + ADAM_CHUNK - 1) / ADAM_CHUNK;
+    if (blocks + nb > 0x7fffffffLL) break;
+    const int k = tb.count++;
+    put(k, &t);
+    tb.n[k] = t.n;
+    tb.block0[k] = (int)blocks;
+    blocks += nb;
+    ++i;
+  }
+  if (tb.count == 0) return i < count ? VQF_E_UNSUPPORTED : VQF_OK;   // a single tensor too large for one grid
+  tb.block0[tb.count] = (int)blocks;
+  for (int k = tb.count; k < ADAM_MAX_TENSORS; ++k) {
+    put(k, nullptr);
+    tb.n[k] = 0;
+    tb.block0[k + 1] = (int)blocks;
+  }
+  return VQF_OK;
+}
+
+int optim_step(int rule, const VqfAdamTensor* tensors, int count, const AdamHyper& h, const float* grad_scale,
+               hipStream_t s) {
+  int i = 0;
+  while (i < count) {
+    AdamTable tb;
+    long long blocks = 0;
+    const int st = next_table(tensors, count, i, true, tb, blocks, [&](int k, const VqfAdamTensor* t) {
+      tb.p[k] = t ? t->param : nullptr; tb.g[k] = t ? t->grad : nullptr;
+      tb.m[k] = t ? t->exp_avg : nullptr; tb.v[k] = t ? t->exp_avg_sq : nullptr;
+    });
+    if (st) return st;
+    if (tb.count == 0) break;
+    vqf_prof_dims(tb.count, (int)(blocks > 0x7fffffff ? 0x7fffffff : blocks), 0);
+    const dim3 grid((unsigned)blocks), block(TR_THREADS);
+    if (rule == RULE_ADAMAX) {
+      if (grad_scale) VQF_LAUNCH(KID_ADAMAX, (adam_kernel<RULE_ADAMAX, const float*>), grid, block, 0, s, tb, h, grad_scale);
+      else VQF_LAUNCH(KID_ADAMAX, adam_kernel<RULE_ADAMAX>, grid, block, 0, s, tb, h);
+    } else {
+      if (grad_scale) VQF_LAUNCH(KID_ADAM_SCALED, (adam_kernel<RULE_ADAM, const float*>), grid, block, 0, s, tb, h, grad_scale);
+      else VQF_LAUNCH(KID_ADAM, adam_kernel<RULE_ADAM>, grid, block, 0, s, tb, h);
+    }
+    const int rc = vqf_last_error();
+    if (rc) return rc;
+  }
+  return VQF_OK;
+}
+
+// the blocks (= partials) of all of `tensors`, or -1 for a negative size
+long long grad_blocks(const VqfAdamTensor* tensors, int count) {
+  long long blocks = 0;
+  for (int i = 0; i < count; ++i) {
+    if (tensors[i].n < 0) return -1;
+    blocks += (tensors[i].n + ADAM_CHUNK - 1) / ADAM_CHUNK;
+  }
+  return blocks;
+}
+bool aligned4(const void* p) { return (((uintptr_t)p) & 3) == 0; }
 
 }  // namespace
 
@@ -469,12 +658,7 @@ int vqf_bce_loss_sparse(const float* logits, const void* ids, int ids64, const f
                          rows, score_sum, loss_sum, acc, accumulate, ws, ws_bytes, stream);
 }
 
-int vqf_adam_step(const VqfAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
-                  double weight_decay, long long step, void* stream) {
-  if (count < 0 || step < 1) return VQF_E_BADARG;
-  if (count && !tensors) return VQF_E_BADARG;
-  hipStream_t s = (hipStream_t)stream;
-  AdamHyper h;
+static void adam_hyper(double lr, double beta1, double beta2, double eps, double weight_decay, long long step, AdamHyper& h) {
   // hyper-parameters are combined in double and rounded once, as torch does with its Python scalars
   const double bc1 = 1.0 - pow(beta1, (double)step);
   const double bc2 = 1.0 - pow(beta2, (double)step);
@@ -483,36 +667,91 @@ int vqf_adam_step(const VqfAdamTensor* tensors, int count, double lr, double bet
   h.eps = (float)eps; h.wd = (float)weight_decay;
   h.step_size = (float)(lr / bc1);
   h.bc2_sqrt = (float)sqrt(bc2);
+}
+
+int vqf_adam_step(const VqfAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, long long step, void* stream) {
+  if (count < 0 || step < 1) return VQF_E_BADARG;
+  if (count && !tensors) return VQF_E_BADARG;
+  AdamHyper h;
+  adam_hyper(lr, beta1, beta2, eps, weight_decay, step, h);
+  return optim_step(RULE_ADAM, tensors, count, h, nullptr, (hipStream_t)stream);
+}
+
+int vqf_adam_step_scaled(const VqfAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
+                         double weight_decay, long long step, const float* grad_scale, void* stream) {
+  if (count < 0 || step < 1) return VQF_E_BADARG;
+  if ((count && !tensors) || !grad_scale) return VQF_E_BADARG;
+  if (!aligned4(grad_scale)) return VQF_E_ALIGN;
+  AdamHyper h;
+  adam_hyper(lr, beta1, beta2, eps, weight_decay, step, h);
+  return optim_step(RULE_ADAM, tensors, count, h, grad_scale, (hipStream_t)stream);
+}
+
+int vqf_adamax_step(const VqfAdamTensor* tensors, int count, double lr, double beta1, double beta2, double eps,
+                    double weight_decay, long long step, const float* grad_scale, void* stream) {
+  if (count < 0 || step < 1) return VQF_E_BADARG;
+  if (count && !tensors) return VQF_E_BADARG;
+  if (!aligned4(grad_scale)) return VQF_E_ALIGN;
+  AdamHyper h;
+  adam_hyper(lr, beta1, beta2, eps, weight_decay, step, h);      // step_size = clr = lr / (1 - beta1^step)
+  return optim_step(RULE_ADAMAX, tensors, count, h, grad_scale, (hipStream_t)stream);
+}
+
+size_t vqf_grad_norm_ws_bytes(const VqfAdamTensor* tensors, int count) {
+  if (count <= 0 || !tensors) return 0;
+  const long long blocks = grad_blocks(tensors, count);
+  return blocks > 0 ? (size_t)blocks * sizeof(float) : 0;
+}
+
+int vqf_grad_norm_clip(const VqfAdamTensor* tensors, int count, double max_norm, float* norm, float* coef, void* ws,
+                       size_t ws_bytes, void* stream) {
+  if (count < 0 || (count && !tensors) || !norm || !coef) return VQF_E_BADARG;
+  if (!(max_norm > 0.0)) return VQF_E_BADARG;                    // (a NaN is refused as well)
+  const long long total = grad_blocks(tensors, count);
+  if (total < 0) return VQF_E_BADARG;
+  for (int i = 0; i < count; ++i)
+    if (tensors[i].n > 0 && !tensors[i].grad) return VQF_E_BADARG;
+  if (total > 0 && !ws) return VQF_E_BADARG;
+  if (ws_bytes < (size_t)total * sizeof(float)) return VQF_E_WORKSPACE;
+  if (!aligned4(norm) || !aligned4(coef) || !aligned4(ws)) return VQF_E_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  float* part = (float*)ws;
+  long long done = 0;
   int i = 0;
   while (i < count) {
-    AdamTable tb;
-    tb.count = 0;
+    GradTable tb;
     long long blocks = 0;
-    while (i < count && tb.count < ADAM_MAX_TENSORS) {
-      const VqfAdamTensor& t = tensors[i];
-      if (t.n < 0) return VQF_E_BADARG;
-      if (t.n == 0) { ++i; continue; }
-      if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq) return VQF_E_BADARG;
-      long long nb = (t.n + ADAM_CHUNK - 1) / ADAM_CHUNK;
-      if (blocks + nb > 0x7fffffffLL) break;
-      const int k = tb.count++;
-      tb.p[k] = t.param; tb.g[k] = t.grad; tb.m[k] = t.exp_avg; tb.v[k] = t.exp_avg_sq; tb.n[k] = t.n;
-      tb.block0[k] = (int)blocks;
-      blocks += nb;
-      ++i;
-    }
-    if (tb.count == 0) {
-      if (i < count) return VQF_E_UNSUPPORTED;   // a single tensor too large for one grid
-      break;
-    }
-    tb.block0[tb.count] = (int)blocks;
-    for (int k = tb.count; k < ADAM_MAX_TENSORS; ++k) {
-      tb.p[k] = nullptr; tb.g[k] = nullptr; tb.m[k] = nullptr; tb.v[k] = nullptr; tb.n[k] = 0;
-      tb.block0[k + 1] = (int)blocks;
-    }
-    vqf_prof_dims(tb.count, (int)(blocks > 0x7fffffff ? 0x7fffffff : blocks), 0);
-    VQF_LAUNCH(KID_ADAM, adam_kernel, dim3((unsigned)blocks), dim3(TR_THREADS), 0, s, tb, h);
-    int rc = vqf_last_error();
+    const int st = next_table(tensors, count, i, false, tb, blocks,
+                              [&](int k, const VqfAdamTensor* t) { tb.g[k] = t ? const_cast<float*>(t->grad) : nullptr; });
+    if (st) return st;
+    if (tb.count == 0) break;
+    vqf_prof_dims(tb.count, (int)blocks, 0);
+    VQF_LAUNCH(KID_GRAD_SUMSQ, grad_sumsq_kernel, dim3((unsigned)blocks), dim3(TR_THREADS), 0, s, tb, part + done);
+    const int rc = vqf_last_error();
+    if (rc) return rc;
+    done += blocks;
+  }
+  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(TR_THREADS), 0, s, (const float*)part, done, (float)max_norm, norm,
+                     coef);
+  return vqf_last_error();
+}
+
+int vqf_grad_scale(const VqfAdamTensor* tensors, int count, const float* scale, void* stream) {
+  if (count < 0 || (count && !tensors) || !scale) return VQF_E_BADARG;
+  if (!aligned4(scale)) return VQF_E_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  int i = 0;
+  while (i < count) {
+    GradTable tb;
+    long long blocks = 0;
+    const int st = next_table(tensors, count, i, false, tb, blocks,
+                              [&](int k, const VqfAdamTensor* t) { tb.g[k] = t ? const_cast<float*>(t->grad) : nullptr; });
+    if (st) return st;
+    if (tb.count == 0) break;
+    vqf_prof_dims(tb.count, (int)blocks, 0);
+    VQF_LAUNCH(KID_GRAD_SCALE, grad_scale_kernel, dim3((unsigned)blocks), dim3(TR_THREADS), 0, s, tb, scale);
+    const int rc = vqf_last_error();
     if (rc) return rc;
   }
   return VQF_OK;

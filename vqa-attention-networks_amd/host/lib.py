@@ -235,6 +235,15 @@ SIGNATURES = {
                                   c_i, c_p, c_sz, c_p]),
     "vqf_adam_step": (c_i, [c_p, c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                             ctypes.c_double, ctypes.c_longlong, c_p]),
+    # gradient-norm clipping and the steps that read its coefficient (csrc/train.hip): tensors a host AdamTensor array,
+    # max_norm a double, norm / coef / scale device fp32 pointers
+    "vqf_grad_norm_ws_bytes": (c_sz, [c_p, c_i]),
+    "vqf_grad_norm_clip": (c_i, [c_p, c_i, ctypes.c_double, c_f, c_f, c_p, c_sz, c_p]),
+    "vqf_grad_scale": (c_i, [c_p, c_i, c_f, c_p]),
+    "vqf_adam_step_scaled": (c_i, [c_p, c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                   ctypes.c_double, ctypes.c_longlong, c_f, c_p]),
+    "vqf_adamax_step": (c_i, [c_p, c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                              ctypes.c_double, ctypes.c_longlong, c_f, c_p]),
     "vqf_hbm_copy": (c_i, [c_p, c_p, ctypes.c_longlong, c_i, c_p]),
     "vqf_hbm_read_sweep_blocks": (c_i, [ctypes.c_longlong]),
     "vqf_hbm_read_sweep": (c_i, [c_p, ctypes.c_longlong, c_i, c_f, c_p]),

@@ -2058,22 +2058,91 @@ def kldiv_loss(logp, target, want_grad=True, loss_out=None):
     return loss, d
 
 
-def adam_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0):
-    """In-place torch.optim.Adam update of every tensor in the lists (one launch per 32 tensors)."""
+def _optim_table(what, params, grads, exp_avgs, second):
     n = len(params)
-    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == n):
-        raise _l.VqfError("adam_step: list lengths differ")
-    if n == 0:
-        return
-    tab = (_l.AdamTensor * n)()
-    for i, (p, g, m, v) in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs)):
+    if not (len(grads) == len(exp_avgs) == len(second) == n):
+        raise _l.VqfError("%s: list lengths differ" % what)
+    tab = (_l.AdamTensor * max(n, 1))()
+    for i, (p, g, m, v) in enumerate(zip(params, grads, exp_avgs, second)):
         _chk(p, g, m, v)
         if not (p.numel() == g.numel() == m.numel() == v.numel()):
-            raise _l.VqfError("adam_step: tensor %d: sizes differ" % i)
+            raise _l.VqfError("%s: tensor %d: sizes differ" % (what, i))
         tab[i].param, tab[i].grad = p.data_ptr(), g.data_ptr()
         tab[i].exp_avg, tab[i].exp_avg_sq, tab[i].n = m.data_ptr(), v.data_ptr(), p.numel()
-    _l.check(_lib().vqf_adam_step(ctypes.cast(tab, ctypes.c_void_p), n, float(lr), float(beta1), float(beta2),
-                                  float(eps), float(weight_decay), int(step), _stream()), "vqf_adam_step")
+    return tab, n
+
+
+def _chk_device_scalar(what, t, device):
+    """a one-element fp32 tensor on `device`: what the kernels read a scale / clip coefficient from"""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.numel() == 1 and t.device == device):
+        raise _l.VqfError("%s: a one-element fp32 tensor on %s expected" % (what, device))
+
+
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
+              grad_scale=None):
+    """In-place torch.optim.Adam update of every tensor in the lists (one launch per 32 tensors).  grad_scale: a one-element
+    fp32 GPU tensor (the coefficient of grad_norm_clip); the update then sees g * grad_scale, the gradients stay as they are."""
+    tab, n = _optim_table("adam_step", params, grads, exp_avgs, exp_avg_sqs)
+    if n == 0:
+        return
+    args = (ctypes.cast(tab, ctypes.c_void_p), n, float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+            int(step))
+    if grad_scale is None:
+        _l.check(_lib().vqf_adam_step(*args, _stream()), "vqf_adam_step")
+    else:
+        _chk_device_scalar("adam_step: grad_scale", grad_scale, params[0].device)
+        _l.check(_lib().vqf_adam_step_scaled(*args, _ptr(grad_scale), _stream()), "vqf_adam_step_scaled")
+
+
+def adamax_step(params, grads, exp_avgs, exp_infs, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
+                grad_scale=None):
+    """In-place torch.optim.Adamax update of every tensor in the lists (one launch per 32 tensors); grad_scale as in adam_step."""
+    tab, n = _optim_table("adamax_step", params, grads, exp_avgs, exp_infs)
+    if n == 0:
+        return
+    if grad_scale is not None:
+        _chk_device_scalar("adamax_step: grad_scale", grad_scale, params[0].device)
+    _l.check(_lib().vqf_adamax_step(ctypes.cast(tab, ctypes.c_void_p), n, float(lr), float(beta1), float(beta2), float(eps),
+                                    float(weight_decay), int(step), _ptr(grad_scale), _stream()), "vqf_adamax_step")
+
+
+def _grad_table(what, grads):
+    """-> (VqfAdamTensor array with grad and n filled in, count, device): fp32 contiguous GPU tensors on one device"""
+    n = len(grads)
+    tab = (_l.AdamTensor * max(n, 1))()
+    for i, g in enumerate(grads):
+        _chk(g)
+        if g.device != grads[0].device:
+            raise _l.VqfError("%s: gradients on one device expected" % what)
+        tab[i].grad, tab[i].n = g.data_ptr(), g.numel()
+    return tab, n, (grads[0].device if n else None)
+
+
+def grad_norm_clip(grads, max_norm):
+    """-> (norm, coef), 0-d fp32 GPU tensors: the 2-norm over every tensor of `grads` and min(1, max_norm / (norm + 1e-6)) as
+    torch.nn.utils.clip_grad_norm_ forms it in fp32.  Nothing is scaled and nothing is read back; two calls on the same
+    memory give the same bits."""
+    max_norm = float(max_norm)
+    if not max_norm > 0.0:
+        raise ValueError("grad_norm_clip: max_norm must be > 0, got %r" % (max_norm,))
+    tab, n, device = _grad_table("grad_norm_clip", grads)
+    if n == 0:
+        raise _l.VqfError("grad_norm_clip: no gradients")
+    out = torch.empty(2, dtype=torch.float32, device=device)
+    nb = int(_lib().vqf_grad_norm_ws_bytes(ctypes.cast(tab, ctypes.c_void_p), n))
+    ws = workspace(device, nb)
+    _l.check(_lib().vqf_grad_norm_clip(ctypes.cast(tab, ctypes.c_void_p), n, max_norm, _ptr(out), out.data_ptr() + 4, _ptr(ws),
+                                       nb, _stream()), "vqf_grad_norm_clip")
+    return out[0], out[1]
+
+
+def grad_scale_(grads, scale):
+    """g *= scale for every tensor of `grads`, in place; scale: a one-element fp32 GPU tensor (one fp32 multiply per element)."""
+    tab, n, device = _grad_table("grad_scale_", grads)
+    if n == 0:
+        return
+    _chk_device_scalar("grad_scale_: scale", scale, device)
+    _l.check(_lib().vqf_grad_scale(ctypes.cast(tab, ctypes.c_void_p), n, _ptr(scale), _stream()), "vqf_grad_scale")
 
 
 # ---------------------------------------------------------------------------
