@@ -86,50 +86,66 @@ class NormLink:
         self.inv, self.L, self.lin, self.xb = None, 0, None, None    # xb: the producer's bf16 copy of R (K padded to 32), bf16 modes
 
 
+class _Dense:
+    """The dense layer LinearFn, FinalMfbFn and both forms of AttHeadFn share: y = x W^T (+ b)(relu) in fp32, or with bf16
+    operands / fp32 accumulate (bias, ReLU and every reduction stay fp32).  bf16 needs every extent in `dims` -- those that
+    become a K or a K-major row extent -- to be a multiple of 8, else the layer stays fp32 (_bf16_ok).  operand() is the cast
+    (columns zero-padded to pad_to: 8, or 32 for the K of the attention head's first layer; a tensor that already is bf16 is
+    taken as it is); fwd / dx / dw are the three products on operands as operand() returned them, which is what a backward
+    saves, and one operand(dy) serves dx and dw.  Every step is one launch, so a node with two layers (FinalMfbFn) keeps its launch order.
+    kw: the explicit extents of a site whose operands are padded (K=, N=) and out= / accumulate=."""
+    __slots__ = ("bf16",)
+
+    def __init__(self, bf16, dims=()):
+        self.bf16 = bool(bf16) and _bf16_ok(*dims)
+
+    def operand(self, t, pad_to=8):
+        return ops.cast_bf16(t, pad_to) if (self.bf16 and t.dtype != torch.bfloat16) else t
+
+    def fwd(self, x, w, bias=None, relu=False, scale=None, **kw):
+        """scale: (rowscale, rows per scale), the epilogue of the head behind a NormLink"""
+        if scale is not None:
+            return (ops.gemm_bf16_rowscale if self.bf16 else ops.gemm_rowscale)(x, w, *scale, bias=bias, relu=relu, **kw)
+        return (ops.gemm_bf16 if self.bf16 else ops.gemm)(x, w, bias=bias, relu=relu, **kw)
+
+    def dx(self, dy, w, **kw):
+        """dX = dY W   (M,K)"""
+        return (ops.gemm_bf16 if self.bf16 else ops.gemm)(dy, w, tb=True, **kw)
+
+    def dw(self, dy, x, like):
+        """dW = dY^T X   (N,K) in the parameter's shape, without the pad columns of a padded x"""
+        g = (ops.gemm_bf16 if self.bf16 else ops.gemm)(dy, x, ta=True, tb=True)
+        cin = like[0].numel()
+        return (g if g.shape[1] == cin else g[:, :cin].contiguous()).view_as(like)
+
+
 class LinearFn(torch.autograd.Function):
     """y = x @ W^T + b  (optionally relu).  x (M,K), W (N,K).
-    bf16 (gemm_dtype "bf16-all"): bf16 operands / fp32 accumulate in the forward, the dgrad and the weight gradient
-    (operands cast once per use by vqf_cast_f32_bf16; bias, ReLU and every reduction stay fp32)."""
+    bf16 (gemm_dtype "bf16-all"): bf16 operands / fp32 accumulate in the forward, the dgrad and the weight gradient (_Dense)."""
 
     @staticmethod
     def forward(ctx, x, w, b, relu=False, bf16=False):
-        x = _c(x)
-        w2 = _w2d(w)
-        bf16 = bool(bf16) and _bf16_ok(x.shape[0], x.shape[1], w2.shape[0])
-        if bf16:
-            xb, wb = ops.cast_bf16(x), ops.cast_bf16(w2)
-            y = ops.gemm_bf16(xb, wb, bias=b, relu=relu)
-            ctx.save_for_backward(xb, w, y if relu else None, wb)
-        else:
-            y = ops.gemm(x, w2, bias=b, relu=relu)
-            ctx.save_for_backward(x, w, y if relu else None, None)
-        ctx.has_bias = b is not None
-        ctx.relu = relu
-        ctx.bf16 = bf16
+        x, w2 = _c(x), _w2d(w)
+        d = _Dense(bf16, dims=(x.shape[0], x.shape[1], w2.shape[0]))
+        x, wo = d.operand(x), d.operand(w2)
+        y = d.fwd(x, wo, b, relu)
+        ctx.save_for_backward(x, w, y if relu else None, wo if d.bf16 else None)
+        ctx.has_bias, ctx.relu, ctx.bf16 = b is not None, relu, d.bf16
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w, y, wb = ctx.saved_tensors
-        w2 = _w2d(w)
+        d = _Dense(ctx.bf16)
         dy = _c(dy)
         db = None
         if ctx.relu:
             dy, db = ops.relu_bwd(dy, y, want_bias=ctx.has_bias)
         elif ctx.has_bias and ctx.needs_input_grad[2]:
             db = ops.colsum(dy)
-        dx = dw = None
-        if ctx.bf16:
-            dyb = ops.cast_bf16(dy)
-            if ctx.needs_input_grad[0]:
-                dx = ops.gemm_bf16(dyb, wb, tb=True)                         # dX = dY W      (M,K)
-            if ctx.needs_input_grad[1]:
-                dw = ops.gemm_bf16(dyb, x, ta=True, tb=True).view_as(w)      # dW = dY^T X    (N,K)
-            return dx, dw, db, None, None
-        if ctx.needs_input_grad[0]:
-            dx = ops.gemm(dy, w2, tb=True)                       # dX = dY W      (M,K)
-        if ctx.needs_input_grad[1]:
-            dw = ops.gemm(dy, x, ta=True, tb=True).view_as(w)    # dW = dY^T X    (N,K)
+        dy = d.operand(dy)
+        dx = d.dx(dy, wb if d.bf16 else _w2d(w)) if ctx.needs_input_grad[0] else None
+        dw = d.dw(dy, x, w) if ctx.needs_input_grad[1] else None
         return dx, dw, db, None, None
 
 
@@ -316,100 +332,72 @@ class AttHeadFn(torch.autograd.Function):
     def forward(ctx, x, feat, w1, b1, wm, bm, w2, b2, unit_softmax, bf16=False, link=None, same_src=False, layout=None):
         x = _c(x)
         feat = _c(feat)
-        ctx.bf16 = bool(bf16)
         ctx.same_src = bool(same_src)
         ctx.layout = layout
-        if layout is not None and (ctx.bf16 or ctx.same_src or feat.dtype != torch.float32 or ctx.needs_input_grad[1]
+        if layout is not None and (bool(bf16) or ctx.same_src or feat.dtype != torch.float32 or ctx.needs_input_grad[1]
                                    or feat.dim() != (2 if layout.packed else 3)):
             raise ops._l.VqfError("AttHeadFn: a region layout (shared images, region counts, packed rows) is fp32 only, for a feature "
                                   "tensor that is data -- (R, C) when packed -- and never the MLP's own source")
         if ctx.same_src and (x.numel() != feat.numel() or x.shape[-1] != feat.shape[-1] or x.dtype != feat.dtype):
             raise ops._l.VqfError("AttHeadFn: same_src needs x = feat.view(N*S, C)")
-        ctx.link = link if (link is not None and link.inv is not None) else None
-        if ctx.link is not None:
-            # x is the UN-NORMALISED fusion output: 1/norm of the sample goes into the conv GEMM's epilogue, and the logit
-            # kernel also returns the part of each logit that is linear in x (NormLink)
-            if wm is not None or b1 is None:
-                raise ops._l.VqfError("AttHeadFn: a NormLink needs the single-hidden-layer head with a bias")
-            ctx.bf16 = ctx.bf16 and _bf16_ok(_w2d(w1).shape[0], _w2d(w1).shape[1])
-            if ctx.bf16:       # bf16 operands (BASELINE config 3): the un-normalised R is cast, 1/norm rides in the bf16 GEMM's epilogue
-                w1b = ops.cast_bf16(_w2d(w1), 32)
-                xb = link.xb if (link.xb is not None and link.xb.shape == (x.shape[0], w1b.shape[1])) else ops.cast_bf16(x, 32)
-                link.xb = None
-                hid1 = ops.gemm_bf16_rowscale(xb, w1b, link.inv, link.L, bias=b1, relu=True, K=xb.shape[1])
-                x = xb
-            else:
-                hid1 = ops.gemm_rowscale(x, _w2d(w1), link.inv, link.L, bias=b1, relu=True)
+        ctx.link = link = link if (link is not None and link.inv is not None) else None
+        if link is not None and (wm is not None or b1 is None):
+            raise ops._l.VqfError("AttHeadFn: a NormLink needs the single-hidden-layer head with a bias")
+        # bf16 operands, fp32 accumulate (BASELINE config 3), K padded to a multiple of 32; the entry point wants the hidden width
+        # and, for the dgrad's N = C_in columns, the input width to be multiples of 8, else the head stays fp32
+        w1_2 = _w2d(w1)
+        d = _Dense(bf16, dims=w1_2.shape)
+        ctx.bf16 = d.bf16
+        hid2 = lin = None
+        if link is not None:
+            # x is the UN-NORMALISED fusion output: 1/norm of the sample (link.inv) rides in the conv GEMM's epilogue, and the logit
+            # kernel also returns the part of each logit that is linear in x (NormLink).  bf16: the producer's own bf16 copy of x
+            # is the operand where it left one of the padded shape
+            w1o = d.operand(w1_2, 32)
+            if d.bf16:
+                xb, link.xb = link.xb, None
+                x = xb if (xb is not None and xb.shape == (x.shape[0], w1o.shape[1])) else d.operand(x, 32)
+            hid1 = d.fwd(x, w1o, b1, True, scale=(link.inv, link.L), **({"K": x.shape[1]} if d.bf16 else {}))
             logits, lin = ops.att_logits_fwd_lin(hid1, _w2d(w2), b2, b1)
-            wts, pooled = _pool_fwd(feat, logits, unit_softmax, layout)
-            # (bf16 mode: slot 3 -- no "multilayer" conv with a NormLink -- carries the bf16 copy of w1 to the backward: one cast per step)
-            ctx.save_for_backward(x, feat, w1, w1b if ctx.bf16 else None, w2, hid1, None, wts, lin)
-            ctx.unit = bool(unit_softmax)
-            return pooled
-        # (the bf16 GEMM entry point wants K and every K-major operand's row extent to be multiples of 8: here the hidden
-        #  width and, for the dgrad's N = C_in columns, the input width; else the head stays fp32, like LinearFn / FinalMfbFn)
-        ctx.bf16 = ctx.bf16 and _bf16_ok(_w2d(w1).shape[0], _w2d(w1).shape[1])
-        if ctx.bf16:
-            # bf16 operands, fp32 accumulate (BASELINE config 3); K padded to a multiple of 32
-            xb, w1b = ops.cast_bf16(x, 32), ops.cast_bf16(_w2d(w1), 32)
-            hid1 = ops.gemm_bf16(xb, w1b, K=xb.shape[1], bias=b1, relu=True)
-            x = xb                                      # the backward only needs the bf16 copy
         else:
-            hid1 = ops.gemm(x, _w2d(w1), bias=b1, relu=True)
-        hid2 = ops.gemm(hid1, _w2d(wm), bias=bm, relu=True) if wm is not None else None
-        last = hid2 if hid2 is not None else hid1
-        logits = ops.att_logits_fwd(last, _w2d(w2), b2)
+            x, w1o = d.operand(x, 32), d.operand(w1_2, 32)      # the backward only needs the operand
+            hid1 = d.fwd(x, w1o, b1, True, **({"K": x.shape[1]} if d.bf16 else {}))
+            hid2 = ops.gemm(hid1, _w2d(wm), bias=bm, relu=True) if wm is not None else None
+            logits = ops.att_logits_fwd(hid2 if hid2 is not None else hid1, _w2d(w2), b2)
         wts, pooled = _pool_fwd(feat, logits, unit_softmax, layout)
-        ctx.save_for_backward(x, feat, w1, wm, w2, hid1, hid2, wts, w1b if ctx.bf16 else None)      # (last slot: the bf16 copy of w1)
+        # x: the first layer's operand; wm, hid2: the "multilayer" conv (never with a link); lin: link only; w1b: w1's bf16 copy (bf16
+        # only).  (tests/node_harness.py reads the kernel's ReLU decisions from hid1 by position)
+        ctx.save_for_backward(x, feat, w1, wm, w2, hid1, hid2, wts, lin, w1o if d.bf16 else None)
         ctx.unit = bool(unit_softmax)
         return pooled
 
     @staticmethod
     def backward(ctx, dpooled):
-        x, feat, w1, wm, w2, hid1, hid2, wts, lin = ctx.saved_tensors
-        dpooled = _c(dpooled)
-        need_dfeat = ctx.needs_input_grad[1]
-        dlogits, dfeat = _pool_bwd(dpooled, feat, wts, ctx.unit, need_dfeat, ctx.layout)
+        x, feat, w1, wm, w2, hid1, hid2, wts, lin, w1b = ctx.saved_tensors
+        d = _Dense(ctx.bf16)
+        dlogits, dfeat = _pool_bwd(_c(dpooled), feat, wts, ctx.unit, ctx.needs_input_grad[1], ctx.layout)
+        dwm = dbm = None
         if ctx.link is not None:
             link = ctx.link
-            w1b = wm                                       # (slot 3, see forward)
-            obf = ctx.bf16 and hid1.shape[1] % 8 == 0 and w2.shape[0] == 2          # the kernel stores bf16 rows itself: no cast launch
-            d1s, dw2, db2, db1 = ops.att_logits_bwd(dlogits, hid1, _w2d(w2), relu_mask=True, rowscale=link.inv,
-                                                    rows_per_scale=link.L, out_bf16=obf)   # stored rows already times 1/norm
+            obf = d.bf16 and hid1.shape[1] % 8 == 0 and w2.shape[0] == 2          # the kernel stores bf16 rows itself: no cast launch
+            d1, dw2, db2, db1 = ops.att_logits_bwd(dlogits, hid1, _w2d(w2), relu_mask=True, rowscale=link.inv,
+                                                   rows_per_scale=link.L, out_bf16=obf)   # stored rows already times 1/norm
             link.lin = (dlogits, lin)                                               # -> sum(Y * dY) in the producer's backward
-            if ctx.bf16:
-                cin = _w2d(w1).shape[1]
-                d1b = d1s if obf else ops.cast_bf16(d1s)
-                dw1 = ops.gemm_bf16(d1b, x, ta=True, tb=True)[:, :cin].contiguous().view_as(w1)
-                dx = ops.gemm_bf16(d1b, w1b, tb=True, N=cin) if ctx.needs_input_grad[0] else None
-                return dx, dfeat, dw1, db1, None, None, dw2.view_as(w2), db2, None, None, None, None, None
-            dw1 = ops.gemm(d1s, x, ta=True, tb=True).view_as(w1)                    # = dpre^T Y
-            dx = ops.gemm(d1s, _w2d(w1), tb=True) if ctx.needs_input_grad[0] else None   # dYs = dY / norm
-            return dx, dfeat, dw1, db1, None, None, dw2.view_as(w2), db2, None, None, None, None, None
-        last = hid2 if hid2 is not None else hid1
-        dlast_pre, dw2, db2, dblast = ops.att_logits_bwd(dlogits, last, _w2d(w2), relu_mask=True)
-        dwm = dbm = None
-        if hid2 is not None:
-            dwm = ops.gemm(dlast_pre, hid1, ta=True, tb=True).view_as(wm)
-            dbm = dblast
-            dhid1 = ops.gemm(dlast_pre, _w2d(wm), tb=True)
-            d1_pre, db1 = ops.relu_bwd(dhid1, hid1, want_bias=True)
+        elif hid2 is not None:
+            dm, dw2, db2, dbm = ops.att_logits_bwd(dlogits, hid2, _w2d(w2), relu_mask=True)
+            dwm = ops.gemm(dm, hid1, ta=True, tb=True).view_as(wm)
+            d1, db1 = ops.relu_bwd(ops.gemm(dm, _w2d(wm), tb=True), hid1, want_bias=True)
         else:
-            d1_pre, db1 = dlast_pre, dblast
-        if ctx.bf16:
-            cin = _w2d(w1).shape[1]
-            d1b = ops.cast_bf16(d1_pre)
-            dw1 = ops.gemm_bf16(d1b, x, ta=True, tb=True)[:, :cin].contiguous().view_as(w1)
-            dx = None
-            if ctx.needs_input_grad[0]:
-                dx = ops.gemm_bf16(d1b, lin, tb=True, N=cin)                  # lin: slot 8 = w1's bf16 copy in this form
-        else:
-            dw1 = ops.gemm(d1_pre, x, ta=True, tb=True).view_as(w1)
-            if ctx.same_src and dfeat is not None:
-                ops.gemm(d1_pre, _w2d(w1), tb=True, out=dfeat.view(x.shape), accumulate=True)     # dfeat += dx: one gradient for the shared source
-                dx = None
-            else:
-                dx = ops.gemm(d1_pre, _w2d(w1), tb=True) if ctx.needs_input_grad[0] else None
+            d1, dw2, db2, db1 = ops.att_logits_bwd(dlogits, hid1, _w2d(w2), relu_mask=True)
+        # the first layer: dw1 = d1^T x and dx = d1 w1 (with a link d1 carries 1/norm, so dx = dY / norm)
+        d1 = d.operand(d1)
+        dw1 = d.dw(d1, x, w1)
+        w1o = w1b if d.bf16 else _w2d(w1)
+        dx = None
+        if ctx.same_src and dfeat is not None and ctx.link is None and not d.bf16:
+            d.dx(d1, w1o, out=dfeat.view(x.shape), accumulate=True)     # dfeat += dx: one gradient for the shared source
+        elif ctx.needs_input_grad[0]:
+            dx = d.dx(d1, w1o, **({"N": w1[0].numel()} if d.bf16 else {}))
         return dx, dfeat, dw1, db1, dwm, dbm, dw2.view_as(w2), db2, None, None, None, None, None
 
 
@@ -448,6 +436,40 @@ def _fuse_node_bwd(ctx, dY, Y, norm, inv, P, q, keep, pbias, dp_bf16):
                      pbias=pbias, lin=_take_lin(ctx.link))
 
 
+def _img_proj(img, wi, bf16, bias=None, store_bf16=True, out=None):
+    """a5, the one place that forms P = img W^T (+ bias): img (., ., D) flattened to rows -> (P, the 2-D image operand as the GEMM
+    consumed it, which is what the weight gradient takes).  bf16: bf16 storage of the image tensor (a bf16 batch is used as it
+    is, no per-step cast) and of the weight, fp32 accumulation; with store_bf16 P itself is STORED in bf16 when the large-tile
+    kernel applies and ImgFuseFn.BF16_P allows (half the bytes of the largest tensor of the step in the GEMM epilogue, the
+    fusion forward and the fusion backward)."""
+    img = _c(img)
+    img2 = img.view(-1, img.shape[-1])
+    if not bf16:
+        return ops.gemm(img2, _w2d(wi), bias=bias, out=out), img2
+    if img2.dtype != torch.bfloat16:
+        img2 = ops.cast_bf16(img2)
+    wb = ops.cast_bf16(_w2d(wi))
+    P = ops.gemm_bf16(img2, wb, bias=bias, out_bf16=True) if (store_bf16 and ImgFuseFn.BF16_P) else None
+    if P is None:
+        P = ops.gemm_bf16(img2, wb, bias=bias)
+    return P, img2
+
+
+def _img_wgrad(dP, img2, wi):
+    """The projection's weight gradient dW = dP^T img2, K = the rows of P, for img2 as _img_proj returned it: a bf16 image operand
+    takes dP in bf16 -- as the fusion's backward wrote it (no cast pass), or cast here."""
+    dP = _c(dP)
+    if img2.dtype == torch.bfloat16:
+        return ops.gemm_bf16(dP if dP.dtype == torch.bfloat16 else ops.cast_bf16(dP), img2, ta=True, tb=True).view_as(wi)
+    return ops.gemm(dP, img2, ta=True, tb=True).view_as(wi)
+
+
+def _cu_bracket(cu_limit):
+    """cu_limit > 0: the persistent large-tile GEMMs inside the block leave the other CUs to kernels of other streams (library
+    option gemm_cu_limit).  0: the option is left alone, so a limit the user set with ops.set_option / VQF_GEMM_CU_LIMIT applies."""
+    return ops.options(gemm_cu_limit=cu_limit) if cu_limit else ops.options()
+
+
 class ImgFuseFn(torch.autograd.Function):
     """a5+a6: P = img W^T + b;  Y = L2norm_n(ssqrt(pool5(dropout(P * q[n])))).
 
@@ -468,36 +490,20 @@ class ImgFuseFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, wi, bi, q, keep, seed, p_drop, bf16=False, link=None, layout=None):
         img, q = _c(img), _c(q)
-        D = img.shape[-1]
         N, L = (img.shape[0], img.shape[1]) if layout is None else (layout.N, layout.L)
-        wi2 = _w2d(wi)
         ctx.bf16 = bool(bf16)
         if layout is not None and (ctx.bf16 or img.dtype != torch.float32):
             raise ops._l.VqfError("ImgFuseFn: a region layout (shared images, region counts, packed rows) is fp32 only")
-        if ctx.bf16:
-            # bf16 storage of the image tensor and the projection weight, fp32 accumulation
-            img = img.view(-1, D) if img.dtype == torch.bfloat16 else ops.cast_bf16(img.view(-1, D))
-            wb = ops.cast_bf16(wi2)
-            # the projection is STORED in bf16 when the large-tile kernel applies (half the bytes of the largest
-            # tensor of the step in the GEMM epilogue, the fusion forward and the fusion backward)
-            P = ops.gemm_bf16(img, wb, bias=bi, out_bf16=True) if ImgFuseFn.BF16_P else None
-            if P is None:
-                P = ops.gemm_bf16(img, wb, bias=bi)
-        else:
-            P = ops.gemm(img.view(-1, D), wi2, bias=bi)        # once per image where they are shared; packed: the real rows only
+        P, img2 = _img_proj(img, wi, ctx.bf16, bias=bi)     # once per image where they are shared; packed: the real rows only
         Y, norm, inv = _fuse_node_fwd(ctx, P, None, q, keep, seed, p_drop, N, L, link, layout)
-        ctx.save_for_backward(img, wi, q, P, Y, norm, inv, keep)
+        ctx.save_for_backward(img2, wi, q, P, Y, norm, inv, keep)
         return Y
 
     @staticmethod
     def backward(ctx, dY):
-        img, wi, q, P, Y, norm, inv, keep = ctx.saved_tensors
-        dP, dq, dbi = _fuse_node_bwd(ctx, dY, Y, norm, inv, P, q, keep, None, ctx.bf16)
-        if ctx.bf16:                  # dP already is the bf16 A operand of the weight-gradient GEMM
-            dwi = ops.gemm_bf16(dP, img, ta=True, tb=True).view_as(wi)
-        else:
-            dwi = ops.gemm(dP, img.view(-1, img.shape[-1]), ta=True, tb=True).view_as(wi)   # wgrad, K = the rows of P
-        return None, dwi, dbi, dq, None, None, None, None, None, None
+        img2, wi, q, P, Y, norm, inv, keep = ctx.saved_tensors
+        dP, dq, dbi = _fuse_node_bwd(ctx, dY, Y, norm, inv, P, q, keep, None, ctx.bf16)   # bf16: dP comes back in bf16
+        return None, _img_wgrad(dP, img2, wi), dbi, dq, None, None, None, None, None, None
 
 
 class ImgProjFn(torch.autograd.Function):
@@ -508,29 +514,14 @@ class ImgProjFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, img, wi, bf16=False):
-        img = _c(img)
-        N, L, D = img.shape
-        wi2 = _w2d(wi)
-        ctx.bf16 = bool(bf16)
-        if ctx.bf16:
-            # bf16 feature storage (FeatureStager(bf16=True)): the batch is used as it is, no per-step cast
-            img2 = img.view(N * L, D) if img.dtype == torch.bfloat16 else ops.cast_bf16(img.view(N * L, D))
-            P0 = ops.gemm_bf16(img2, ops.cast_bf16(wi2))
-        else:
-            img2 = img.view(N * L, D)
-            P0 = ops.gemm(img2, wi2)
+        P0, img2 = _img_proj(img, wi, bool(bf16), store_bf16=False)        # (this node hands on an fp32 P0 in the bf16 mode too)
         ctx.save_for_backward(img2, wi)
         return P0
 
     @staticmethod
     def backward(ctx, dP):
         img2, wi = ctx.saved_tensors
-        dP = _c(dP)
-        if ctx.bf16:
-            dwi = ops.gemm_bf16(ops.cast_bf16(dP), img2, ta=True, tb=True).view_as(wi)
-        else:
-            dwi = ops.gemm(dP, img2, ta=True, tb=True).view_as(wi)            # wgrad, K = N*L
-        return None, dwi, None
+        return None, _img_wgrad(dP, img2, wi), None
 
 
 class ImgProjDeferFn(torch.autograd.Function):
@@ -550,34 +541,19 @@ class ImgProjDeferFn(torch.autograd.Function):
 
     @staticmethod
     def fill(P0, img, wi):
-        img = _c(img)
-        ops.gemm(img.view(-1, img.shape[-1]), _w2d(wi), out=P0.detach())
+        _img_proj(img, wi, False, out=P0.detach())
 
     @staticmethod
     def backward(ctx, dP):
         img2, wi = ctx.saved_tensors
-        return None, ops.gemm(_c(dP), img2, ta=True, tb=True).view_as(wi)            # wgrad, K = N*L
+        return None, _img_wgrad(dP, img2, wi)
 
 
 def img_project(img, wi, bf16, cu_limit=0):
     """a5 without an autograd node: P0 = img W^T (no bias), fp32 or -- bf16 operands -- STORED in bf16 when the large-tile
-    kernel applies.  Returns (P0, img2d as the GEMM consumed it).  cu_limit > 0: the persistent large-tile GEMM leaves
-    the other CUs to kernels of other streams (library option gemm_cu_limit)."""
-    img = _c(img)
-    N, L, D = img.shape
-    wi2 = _w2d(wi)
-    # (no limit asked for: the option is left alone, so a limit the user set with ops.set_option / VQF_GEMM_CU_LIMIT applies)
-    with (ops.options(gemm_cu_limit=cu_limit) if cu_limit else ops.options()):
-        if bf16:
-            img2 = img.view(N * L, D) if img.dtype == torch.bfloat16 else ops.cast_bf16(img.view(N * L, D))
-            wb = ops.cast_bf16(wi2)
-            P0 = ops.gemm_bf16(img2, wb, out_bf16=True) if ImgFuseFn.BF16_P else None
-            if P0 is None:
-                P0 = ops.gemm_bf16(img2, wb)
-        else:
-            img2 = img.view(N * L, D)
-            P0 = ops.gemm(img2, wi2)
-    return P0, img2
+    kernel applies (_img_proj).  Returns (P0, img2d as the GEMM consumed it).  cu_limit: _cu_bracket."""
+    with _cu_bracket(cu_limit):
+        return _img_proj(img, wi, bf16)
 
 
 class ImgProjLateFn(torch.autograd.Function):
@@ -596,14 +572,8 @@ class ImgProjLateFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dP):
         img2, wi = ctx.saved_tensors
-        dP = _c(dP)
-        with (ops.options(gemm_cu_limit=ctx.cu_limit) if ctx.cu_limit else ops.options()):
-            if img2.dtype == torch.bfloat16:
-                dPb = dP if dP.dtype == torch.bfloat16 else ops.cast_bf16(dP)
-                dwi = ops.gemm_bf16(dPb, img2, ta=True, tb=True).view_as(wi)
-            else:
-                dwi = ops.gemm(dP, img2, ta=True, tb=True).view_as(wi)            # wgrad, K = N*L
-        return None, None, dwi, None
+        with _cu_bracket(ctx.cu_limit):
+            return None, None, _img_wgrad(dP, img2, wi), None
 
 
 class MfbFuseFn(torch.autograd.Function):
@@ -673,28 +643,21 @@ class FinalMfbFn(torch.autograd.Function):
         qa, va = _c(qa), _c(va)
         N = qa.shape[0]
         O = wq.shape[0] // ops.POOL_K
-        wq2, wv2 = _w2d(wq), _w2d(wv)
-        bf16 = bool(bf16) and _bf16_ok(N, qa.shape[1], va.shape[1], wq2.shape[0])
-        if bf16:            # "bf16-all": both projections with bf16 operands, fp32 accumulate
-            qa_s, va_s, wqb, wvb = ops.cast_bf16(qa), ops.cast_bf16(va), ops.cast_bf16(wq2), ops.cast_bf16(wv2)
-            qq = ops.gemm_bf16(qa_s, wqb, bias=bq)
-            vv = ops.gemm_bf16(va_s, wvb, bias=bv)
-        elif FinalMfbFn.TWO_STREAMS:
-            qa_s, va_s, wqb, wvb = qa, va, None, None
+        d = _Dense(bf16, dims=(N, qa.shape[1], va.shape[1], wq.shape[0]))      # "bf16-all": both projections with bf16 operands
+        qa, va, wqo, wvo = d.operand(qa), d.operand(va), d.operand(_w2d(wq)), d.operand(_w2d(wv))
+        if FinalMfbFn.TWO_STREAMS and not d.bf16:          # the image-side product beside the question-side one
             with _Fork(qa.device) as f:
-                vv = ops.gemm(va, wv2, bias=bv)
-            qq = ops.gemm(qa, wq2, bias=bq)
+                vv = d.fwd(va, wvo, bv)
+            qq = d.fwd(qa, wqo, bq)
             f.join(vv)
         else:
-            qa_s, va_s, wqb, wvb = qa, va, None, None
-            qq = ops.gemm(qa, wq2, bias=bq)
-            vv = ops.gemm(va, wv2, bias=bv)
+            qq, vv = d.fwd(qa, wqo, bq), d.fwd(va, wvo, bv)
         if cascade is not None:
             cascade = _c(cascade)
         y, norm, inv, zdrop = ops.mfb_fuse_fwd(vv, qq, N, 1, O, keep=keep, seed=seed, p_drop=p_drop,
                                                cascade=cascade, want_zdrop=want_zdrop)
-        ctx.save_for_backward(qa_s, va_s, wq, wv, qq, vv, y, norm, inv, keep, cascade, wqb, wvb)
-        ctx.seed, ctx.p_drop, ctx.dims, ctx.bf16 = seed, p_drop, (N, O), bf16
+        ctx.save_for_backward(qa, va, wq, wv, qq, vv, y, norm, inv, keep, cascade, *((wqo, wvo) if d.bf16 else (None, None)))
+        ctx.seed, ctx.p_drop, ctx.dims, ctx.bf16 = seed, p_drop, (N, O), d.bf16
         if want_zdrop:
             return y, zdrop
         return y
@@ -706,31 +669,20 @@ class FinalMfbFn(torch.autograd.Function):
         dvv, dqq, dcasc, _ = ops.mfb_fuse_bwd(_c(dy), y, norm, inv, vv, qq, N, 1, O, keep=keep,
                                               seed=ctx.seed, p_drop=ctx.p_drop, cascade=cascade,
                                               dzdrop=None if dz is None else _c(dz))
-        if ctx.bf16:
-            dqb, dvb = ops.cast_bf16(dqq), ops.cast_bf16(dvv)
-            dqa = ops.gemm_bf16(dqb, wqb, tb=True) if ctx.needs_input_grad[0] else None
-            dva = ops.gemm_bf16(dvb, wvb, tb=True) if ctx.needs_input_grad[1] else None
-            dwq = ops.gemm_bf16(dqb, qa, ta=True, tb=True).view_as(wq)
-            dwv = ops.gemm_bf16(dvb, va, ta=True, tb=True).view_as(wv)
-        elif FinalMfbFn.TWO_STREAMS:
-            wq2, wv2 = _w2d(wq), _w2d(wv)
+        d = _Dense(ctx.bf16)
+        dqo, dvo = d.operand(dqq), d.operand(dvv)
+        wqo, wvo = (wqb, wvb) if d.bf16 else (_w2d(wq), _w2d(wv))
+        need_q, need_v = ctx.needs_input_grad[:2]
+        if FinalMfbFn.TWO_STREAMS and not d.bf16:          # each side's three launches together, the image side's on the second stream
             with _Fork(dqq.device) as f:
-                dva = ops.gemm(dvv, wv2, tb=True) if ctx.needs_input_grad[1] else None
-                dwv = ops.gemm(dvv, va, ta=True, tb=True).view_as(wv)
-                dbv = ops.colsum(dvv)
-            dqa = ops.gemm(dqq, wq2, tb=True) if ctx.needs_input_grad[0] else None
-            dwq = ops.gemm(dqq, qa, ta=True, tb=True).view_as(wq)
-            dbq = ops.colsum(dqq)
+                dva, dwv, dbv = (d.dx(dvo, wvo) if need_v else None), d.dw(dvo, va, wv), ops.colsum(dvv)
+            dqa, dwq, dbq = (d.dx(dqo, wqo) if need_q else None), d.dw(dqo, qa, wq), ops.colsum(dqq)
             f.join(dva, dwv, dbv)
-            return dqa, dva, dwq, dbq, dwv, dbv, None, None, None, dcasc, None, None
         else:
-            wq2, wv2 = _w2d(wq), _w2d(wv)
-            dqa = ops.gemm(dqq, wq2, tb=True) if ctx.needs_input_grad[0] else None
-            dva = ops.gemm(dvv, wv2, tb=True) if ctx.needs_input_grad[1] else None
-            dwq = ops.gemm(dqq, qa, ta=True, tb=True).view_as(wq)
-            dwv = ops.gemm(dvv, va, ta=True, tb=True).view_as(wv)
-        dbq = ops.colsum(dqq)
-        dbv = ops.colsum(dvv)
+            dqa = d.dx(dqo, wqo) if need_q else None
+            dva = d.dx(dvo, wvo) if need_v else None
+            dwq, dwv = d.dw(dqo, qa, wq), d.dw(dvo, va, wv)
+            dbq, dbv = ops.colsum(dqq), ops.colsum(dvv)
         return dqa, dva, dwq, dbq, dwv, dbv, None, None, None, dcasc, None, None
 
 
@@ -780,14 +732,12 @@ class DropoutBTFn(torch.autograd.Function):
 def lstm_out_dropout(module, x, seeds, tag="l"):
     """dropout_l / lstm_dropout of the reference modules on the HIP path: rate = the nn.Dropout's p in train mode, 0 in eval
     (then the pass only makes x contiguous); an explicit (B*T, H) keep-mask under `tag` replaces the in-kernel Philox draw."""
-    p = float(module.p) if module.training else 0.0
-    keep = seeds.keep.get(tag)
     if x.dim() == 3 and x.is_cuda and x.dtype == torch.float32 and x.stride(2) == 1 and x.shape[2] % 4 == 0 \
             and all(s % 4 == 0 for s in x.stride()[:2]) and x.data_ptr() % 16 == 0:
-        if p <= 0.0 and keep is None and x.is_contiguous():
+        keep, seed, rate = seeds.draw(tag, module.training, float(module.p) if module.training else 0.0)   # (rate 0 draws nothing)
+        if rate <= 0.0 and keep is None and x.is_contiguous():
             return x
-        seed, pp = seeds.next(module.training, p)
-        return DropoutBTFn.apply(x, keep, seed, p if keep is not None else pp)
+        return DropoutBTFn.apply(x, keep, seed, rate)
     return module(x).contiguous()
 
 
@@ -1198,6 +1148,36 @@ def _lstm_in_proj_bwd(dgb, xb, wb, I, need_dx):
     return dx, dw
 
 
+def _lstm_flag(bf16):
+    """The Lstm*Fn precision flag (mfb._lstm_bf16) -> (bf16 operands in the recurrent products, "bf16-all": also in the input
+    projection and the weight gradients): False -> (False, False), True -> (True, False), "all" -> (True, True)."""
+    return bool(bf16), bf16 == "all"
+
+
+def _lstm_param_grads(ctx, dg, dgb, hh_bf16):
+    """The tail both LSTM nodes' backward share, from the gate gradients dg (S,B,4H) of the whole sequence: dX, dW_ih (bf16
+    operands where the forward's input projection had them, ctx.bf16_proj), dW_hh = sum_t dG_t^T h_{t-1} (bf16 operands where the
+    node says so, hh_bf16), the bias gradient and its copy for b_hh.  dgb: dg as (S*B, 4H) bf16, or None where neither needs it.
+    -> the node's six gradients."""
+    x, w_ih, w_hh, hs, _, _, xb, wb = ctx.saved_tensors
+    S, B, I = x.shape
+    H = w_hh.shape[1]
+    dg2 = dg.view(S * B, 4 * H)
+    if ctx.bf16_proj:
+        dx, dw_ih = _lstm_in_proj_bwd(dgb, xb, wb, I, ctx.needs_input_grad[0])
+    else:
+        dx = ops.gemm(dg2, _c(w_ih), tb=True) if ctx.needs_input_grad[0] else None
+        dw_ih = ops.gemm(dg2, x.view(S * B, I), ta=True, tb=True)
+    if S == 1:
+        dw_hh = torch.zeros_like(w_hh)
+    elif hh_bf16:                        # bf16 modes: the 60-GFLOP recurrent weight gradient takes bf16 operands too
+        dw_hh = ops.gemm_bf16(dgb[B:], ops.cast_bf16(hs[:-1].reshape((S - 1) * B, H)), ta=True, tb=True)
+    else:
+        dw_hh = ops.gemm(dg[1:].reshape((S - 1) * B, 4 * H), hs[:-1].reshape((S - 1) * B, H), ta=True, tb=True)
+    db = ops.colsum(dg2) if ctx.has_bias else None
+    return (dx.view(S, B, I) if dx is not None else None), dw_ih, dw_hh, db, _copy_of(db), None
+
+
 class LstmSeqFn(torch.autograd.Function):
     """Single-layer LSTM over dim 0 of x (S,B,I) -> hs (S,B,H), zero initial state.
 
@@ -1211,8 +1191,8 @@ class LstmSeqFn(torch.autograd.Function):
         S, B, I = x.shape
         H = w_hh.shape[1]
         bias = _bias_sum(b_ih, b_hh)
-        ctx.bf16 = bool(bf16)          # bf16 operands in the recurrent product (bf16 modes)
-        ctx.bf16_proj = bf16 == "all" and H % 8 == 0       # "bf16-all": also in the input projection and its gradients
+        ctx.bf16, all_ = _lstm_flag(bf16)
+        ctx.bf16_proj = all_ and H % 8 == 0
         xw, xb, wb = _lstm_in_proj(x.view(S * B, I), w_ih, bias, ctx.bf16_proj)
         xw = xw.view(S, B, 4 * H)
         hs, cs, gates = ops.lstm_seq_fwd(xw, _c(w_hh), bf16=ctx.bf16)
@@ -1222,27 +1202,11 @@ class LstmSeqFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dhs):
-        x, w_ih, w_hh, hs, cs, gates, xb, wb = ctx.saved_tensors
-        S, B, I = x.shape
+        _, _, w_hh, _, cs, gates, _, _ = ctx.saved_tensors
         H = w_hh.shape[1]
         dg = ops.lstm_seq_bwd(_c(dhs), gates, cs, _c(w_hh), bf16=ctx.bf16)                # (S,B,4H)
-        dg2 = dg.view(S * B, 4 * H)
-        dgb = ops.cast_bf16(dg2) if ctx.bf16 and H % 8 == 0 else None      # one cast serves every bf16 gradient product
-        if ctx.bf16_proj:
-            dx, dw_ih = _lstm_in_proj_bwd(dgb, xb, wb, I, ctx.needs_input_grad[0])
-            dx = dx.view(S, B, I) if dx is not None else None
-        else:
-            dx = ops.gemm(dg2, _c(w_ih), tb=True).view(S, B, I) if ctx.needs_input_grad[0] else None
-            dw_ih = ops.gemm(dg2, x.view(S * B, I), ta=True, tb=True)
-        if S > 1:
-            if dgb is not None:              # bf16 modes: the 60-GFLOP recurrent weight gradient takes bf16 operands too
-                dw_hh = ops.gemm_bf16(dgb[B:], ops.cast_bf16(hs[:-1].reshape((S - 1) * B, H)), ta=True, tb=True)
-            else:
-                dw_hh = ops.gemm(dg[1:].reshape((S - 1) * B, 4 * H), hs[:-1].reshape((S - 1) * B, H), ta=True, tb=True)
-        else:
-            dw_hh = torch.zeros_like(w_hh)
-        db = ops.colsum(dg2) if ctx.has_bias else None
-        return dx, dw_ih, dw_hh, db, _copy_of(db), None
+        dgb = ops.cast_bf16(dg.view(-1, 4 * H)) if ctx.bf16 and H % 8 == 0 else None      # one cast serves every bf16 gradient product
+        return _lstm_param_grads(ctx, dg, dgb, dgb is not None)
 
 
 class LstmBatchFn(torch.autograd.Function):
@@ -1261,8 +1225,9 @@ class LstmBatchFn(torch.autograd.Function):
         T, B, I = x.shape
         H = w_hh.shape[1]
         bias = _bias_sum(b_ih, b_hh)
-        ctx.bf16 = bool(bf16) and H % 8 == 0
-        ctx.bf16_proj = ctx.bf16 and bf16 == "all"          # "bf16-all": input projection and every weight gradient too
+        rec, all_ = _lstm_flag(bf16)
+        ctx.bf16 = rec and H % 8 == 0
+        ctx.bf16_proj = ctx.bf16 and all_
         whh = ops.cast_bf16(_c(w_hh)) if ctx.bf16 else _c(w_hh)
         gates, xb, wb = _lstm_in_proj(x.view(T * B, I), w_ih, bias, ctx.bf16_proj)
         gates = gates.view(T, B, 4 * H)                     # pre-activations -> activated in place
@@ -1285,8 +1250,8 @@ class LstmBatchFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dhs):
-        x, w_ih, w_hh, hs, cs, gates, xb, wb = ctx.saved_tensors
-        T, B, I = x.shape
+        x, _, w_hh, _, cs, gates, _, _ = ctx.saved_tensors
+        T, B, _ = x.shape
         H = w_hh.shape[1]
         dhs = _c(dhs)
         whh = ops.cast_bf16(_c(w_hh)) if ctx.bf16 else _c(w_hh)
@@ -1297,22 +1262,8 @@ class LstmBatchFn(torch.autograd.Function):
             ops.lstm_cell_bwd(dhs[t], dh, gates[t], cs[t], cs[t - 1] if t else None, t == T - 1, dc, dG[t])
             if t > 0:                                                               # dG_t W_hh  (B,H)
                 dh = ops.gemm_bf16(ops.cast_bf16(dG[t]), whh, tb=True) if ctx.bf16 else ops.gemm(dG[t], whh, tb=True)
-        dG2 = dG.view(T * B, 4 * H)
-        if ctx.bf16_proj:
-            dGb = ops.cast_bf16(dG2)
-            dx, dw_ih = _lstm_in_proj_bwd(dGb, xb, wb, I, ctx.needs_input_grad[0])
-            dx = dx.view(T, B, I) if dx is not None else None
-        else:
-            dx = ops.gemm(dG2, _c(w_ih), tb=True).view(T, B, I) if ctx.needs_input_grad[0] else None
-            dw_ih = ops.gemm(dG2, x.view(T * B, I), ta=True, tb=True)
-        if T > 1 and ctx.bf16_proj and B % 8 == 0:
-            dw_hh = ops.gemm_bf16(dGb[B:], ops.cast_bf16(hs[:-1].reshape((T - 1) * B, H)), ta=True, tb=True)
-        elif T > 1:
-            dw_hh = ops.gemm(dG[1:].reshape((T - 1) * B, 4 * H), hs[:-1].reshape((T - 1) * B, H), ta=True, tb=True)
-        else:
-            dw_hh = torch.zeros_like(w_hh)
-        db = ops.colsum(dG2) if ctx.has_bias else None
-        return dx, dw_ih, dw_hh, db, _copy_of(db), None
+        dGb = ops.cast_bf16(dG.view(T * B, 4 * H)) if ctx.bf16_proj else None
+        return _lstm_param_grads(ctx, dG, dGb, ctx.bf16_proj and B % 8 == 0)
 
 
 class UnitPoolFn(torch.autograd.Function):

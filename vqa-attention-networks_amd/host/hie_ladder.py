@@ -572,12 +572,15 @@ class HieCoAttenLadder(nn.Module):
         'ans_h' (N, hidden_size); used in train mode in place of the in-kernel draws."""
         self._seeds.keep = masks
 
+    def _draw(self, tag):
+        """(keep, seed, rate) of one dropout site: one draw per tag and call, the same order always; masks count in train mode only"""
+        return self._seeds.draw(tag if self.training else None, self.training, self.drop_p)
+
     def _drop(self, x, tag):
-        seed, p = self._seeds.next(self.training, self.drop_p)                  # one draw per tag and call: the same order always
-        keep = self._seeds.keep.get(tag) if self.training else None
-        if keep is None and p <= 0.0:
+        keep, seed, rate = self._draw(tag)
+        if keep is None and rate <= 0.0:
             return x
-        return DropoutFn.apply(_c(x), keep, seed, self.drop_p if keep is not None else p)
+        return DropoutFn.apply(_c(x), keep, seed, rate)
 
     def _is_data(self, img, que_features):
         """region_layout's refusals about the tensors themselves: the features are fp32 data on the GPU, the ids int64"""
@@ -635,15 +638,14 @@ class HieCoAttenLadder(nn.Module):
                                % (que_features.device, q_length.device))
             lens = q_length.clamp(1, T).to(torch.int32).contiguous()            # O(N), on the device: nothing is read back
         # V = drop(tanh(img_emb(img))): (U*L, E), once per image; from a PackedRegions the product runs on the R real rows
-        seed, p = self._seeds.next(self.training, self.drop_p)
-        keep = self._seeds.keep.get("img") if self.training else None
+        drop = self._draw("img")
         V = LinearFn.apply(_c(img_features).view(layout.R, -1), self.img_emb.weight, self.img_emb.bias, False)
         if not layout.packed:
-            V = TanhDropFn.apply(V, None, keep, seed, self.drop_p if keep is not None else p)
+            V = TanhDropFn.apply(V, None, *drop)
         elif self.packed_coatt:            # V stays (R, E): the masks of the padded tensor on the real rows
-            V = TanhDropPackedFn.apply(V, layout.roff, U, L, keep, seed, self.drop_p if keep is not None else p)
+            V = TanhDropPackedFn.apply(V, layout.roff, U, L, *drop)
         else:                              # the tanh / dropout pass lays V out padded, (U*L, E) with zero padded rows
-            V = TanhDropUnpackFn.apply(V, layout.roff, U, L, keep, seed, self.drop_p if keep is not None else p)
+            V = TanhDropUnpackFn.apply(V, layout.roff, U, L, *drop)
             layout = layout.padded()
         if layout.grouped and not alt:
             V = RowBlockGatherFn.apply(V, *layout.grp, L)                                            # (N*L, E)

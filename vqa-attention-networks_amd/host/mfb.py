@@ -231,6 +231,35 @@ class _DropSeeds:
         # one 63-bit seed per call from torch's CPU generator: reproducible under manual_seed
         return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()), p
 
+    def draw(self, tag, training, p):
+        """One dropout site's arguments -> (keep, seed, rate): the explicit keep-mask under `tag` if the test gave one, else one
+        seed from the stream (next); the rate is p with a mask, else the drawn rate (0 outside training).  One call = one draw,
+        with or without a mask, so the seed stream does not depend on the masks."""
+        seed, rate = self.next(training, p)
+        keep = self.keep.get(tag)
+        return keep, seed, (p if keep is not None else rate)
+
+
+def project_aside(model, img3, bf16_img):
+    """MFB / MHBCoAtt: start a5 first -- it only needs the image and its weights -- as its own node (model._side: on the side
+    stream, or on the caller's for overlap_streams = "same-stream") -> what join_or_fuse takes, or None for projection + fusion in
+    one node (ImgFuseFn).  The bf16 modes keep the one node (fuse_bf16_dp): its backward hands dP to the weight-gradient GEMM in
+    bf16 without an fp32 round trip, which is worth more than the stream overlap; a real second stream -- overlap_streams is
+    True -- with side_bf16 keeps the bf16 hand-off too (MfbFuseFn takes / returns bf16)."""
+    ov = model.overlap_streams
+    if not ov or (bf16_img and model.fuse_bf16_dp and not (ov is True and model.side_bf16)):
+        return None
+    return model._side.project(img3, model.img_conv1d, bf16_img, ov == "same-stream", model.side_cu_limit)
+
+
+def join_or_fuse(model, proj, img3, qp, drop, bf16_img, N, L, link, layout):
+    """a5+a6: the MFB fusion over the regions behind project_aside's projection (joined here), or projection + fusion as one node;
+    drop = (keep, seed, rate).  -> Y (N*L, 1000); with a link the un-normalised R"""
+    conv = model.img_conv1d
+    if proj is not None:
+        return MfbFuseFn.apply(model._side.join(*proj), conv.bias, qp, *drop, N, L, link, layout)
+    return ImgFuseFn.apply(img3, conv.weight, conv.bias, qp, *drop, bf16_img, link, layout)
+
 
 class MFB(nn.Module):
     def __init__(self, cfg):
@@ -313,7 +342,7 @@ class MFB(nn.Module):
         """Test hook: explicit uint8 keep-masks 'm1' (N*L,5000), 'm2' (N,5000) instead of Philox."""
         self._seeds.keep = masks
 
-    def _forward_pruned(self, img_features, ques_feature, keep, layout=None):
+    def _forward_pruned(self, img_features, ques_feature, layout=None):
         """The live part of the reference graph when both softmaxes are over a singleton axis."""
         pm = self.dropout_m.p
         qa = UnitPoolFn.apply(ques_feature, 2)                             # (N, 2H)   mfb.py:85-89 with weights 1
@@ -323,10 +352,8 @@ class MFB(nn.Module):
         va = UnitPoolFn.apply(img_features, 2, layout)
         if layout is not None and layout.grouped:                          # per image (U, 2D), one row block per question
             va = ops.row_block_gather(va, layout.idx)
-        seed, p = self._seeds.next(self.training, pm)
-        k2 = keep.get('m2')
         y = FinalMfbFn.apply(qa, va, self.ques_proj2.weight, self.ques_proj2.bias,
-                             self.img_proj2.weight, self.img_proj2.bias, k2, seed, pm if k2 is not None else p)
+                             self.img_proj2.weight, self.img_proj2.bias, *self._seeds.draw('m2', self.training, pm))
         out = LinearFn.apply(y, self.linear_pred.weight, self.linear_pred.bias)
         dead = [self.ques_att_conv1, self.ques_att_conv2, self.ques_proj1, self.img_conv1d, self.co_att_conv1,
                 self.co_att_conv2]
@@ -362,14 +389,8 @@ class MFB(nn.Module):
                                                              self.packed_coatt)
         bf16_img = self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
         bf16_all = self.gemm_dtype == "bf16-all"          # also ques_proj*, img_proj*, the question-attention conv
-        # a5 starts first, on the side stream: it only needs the image and its weights
-        # bf16 mode keeps projection + fusion in one autograd node (ImgFuseFn): its backward hands dP to the
-        # weight-gradient GEMM in bf16 without an fp32 round trip, which is worth more than the stream overlap
-        # (a real second stream -- overlap_streams is True -- keeps the bf16 hand-off too: MfbFuseFn takes / returns bf16)
-        side = self.overlap_streams and not (bf16_img and self.fuse_bf16_dp and not (self.overlap_streams is True and self.side_bf16)) \
-            and not (self.pruned and self.unit_softmax)
-        proj = self._side.project(img3, self.img_conv1d, bf16_img,
-                                  self.overlap_streams == "same-stream", self.side_cu_limit) if side else None
+        # a5 starts first where it is its own node; the pruned mode has no projection
+        proj = None if (self.pruned and self.unit_softmax) else project_aside(self, img3, bf16_img)
         # a2: question encoder                                               mfb.py:68-70
         # (the lookup writes (T,N,E) directly when the recursion runs on the HIP path: no transposing copy in between)
         tm = questions.dim() == 2 and hip_batch_lstm_ok(self.lstm, questions.is_cuda and self.word_embedding.weight.dtype == torch.float32,
@@ -378,9 +399,8 @@ class MFB(nn.Module):
         lstm_o = batch_first_lstm(self.lstm, que_embedded, self.use_hip_lstm, _lstm_bf16(self.gemm_dtype), time_major_in=tm)
         ques_feature = lstm_out_dropout(self.dropout_l, lstm_o, self._seeds)   # (N,T,H) contiguous; mfb.py:70
         N, T, H = ques_feature.shape
-        keep = self._seeds.keep
         if self.pruned and self.unit_softmax:
-            return self._forward_pruned(img_features, ques_feature, keep, layout)
+            return self._forward_pruned(img_features, ques_feature, layout)
 
         # a3: question attention                                             mfb.py:73-89
         wm, bm = self._mc('ques_att_multiconv')
@@ -391,26 +411,16 @@ class MFB(nn.Module):
         qp = LinearFn.apply(qa, self.ques_proj1.weight, self.ques_proj1.bias, False, bf16_all)
         # a5+a6: image projection + MFB fusion over the regions             mfb.py:95-106
         pm = self.dropout_m.p
-        seed, p = self._seeds.next(self.training, pm)
-        k1 = keep.get('m1')
         coatt_bf16 = self.gemm_dtype in ("bf16", "bf16-att", "bf16-all")
         link = NormLink() if (self.fold_norm and not self.multilayer) else None
-        if proj is not None:
-            P0 = self._side.join(*proj)
-            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, layout)
-        else:
-            Y = ImgFuseFn.apply(img3, self.img_conv1d.weight, self.img_conv1d.bias, qp,
-                                k1, seed, pm if k1 is not None else p, bf16_img, link, layout)
+        Y = join_or_fuse(self, proj, img3, qp, self._seeds.draw('m1', self.training, pm), bf16_img, N, L, link, layout)
         # a7+a8: co-attention over the regions                               mfb.py:109-123
         # (with a link Y is the un-normalised R and 1/norm rides in co_att_conv1's GEMM epilogue)
         wm, bm = self._mc('co_att_multiconv')
         va = AttHeadFn.apply(Y, img_features, self.co_att_conv1.weight, self.co_att_conv1.bias, wm, bm,
                              self.co_att_conv2.weight, self.co_att_conv2.bias, self.unit_softmax, coatt_bf16, link, False, layout)
         # a9: final MFB block                                                mfb.py:126-135
-        seed, p = self._seeds.next(self.training, pm)
-        k2 = keep.get('m2')
-        y = FinalMfbFn.apply(qa, va, self.ques_proj2.weight, self.ques_proj2.bias,
-                             self.img_proj2.weight, self.img_proj2.bias, k2, seed,
-                             pm if k2 is not None else p, None, False, bf16_all)
+        y = FinalMfbFn.apply(qa, va, self.ques_proj2.weight, self.ques_proj2.bias, self.img_proj2.weight, self.img_proj2.bias,
+                             *self._seeds.draw('m2', self.training, pm), None, False, bf16_all)
         # a10: classifier; the reference computes a softmax and discards it  mfb.py:137-140
         return LinearFn.apply(y, self.linear_pred.weight, self.linear_pred.bias)

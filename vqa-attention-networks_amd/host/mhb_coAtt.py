@@ -8,9 +8,10 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .functions import (LinearFn, Linear2Fn, AttHeadFn, ImgFuseFn, MfbFuseFn, FinalMfbFn, LstmSeqFn, LstmBatchFn, LogSoftmaxRowsFn,
-                        NormLink, embed_tanh, embed, lstm_out_dropout)
-from .mfb import _DropSeeds, _image_is_data, _SideStream, _lstm_bf16, batch_first_lstm, warn_once, fusion_region_layout
+from .functions import (LinearFn, Linear2Fn, AttHeadFn, FinalMfbFn, LstmSeqFn, LstmBatchFn, LogSoftmaxRowsFn, NormLink, embed_tanh,
+                        embed, lstm_out_dropout)
+from .mfb import (_DropSeeds, _image_is_data, _SideStream, _lstm_bf16, batch_first_lstm, warn_once, fusion_region_layout, project_aside,
+                  join_or_fuse)
 
 
 class MHBCoAtt(nn.Module):
@@ -65,15 +66,9 @@ class MHBCoAtt(nn.Module):
         img_features, img3, L, layout = fusion_region_layout("MHBCoAtt", img_features, questions, img_index, self.gemm_dtype,
                                                              self.packed_coatt)
         N = questions.shape[0]
-        keep = self._seeds.keep
         bf16_img = self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
         bf16_all = self.gemm_dtype == "bf16-all"          # also ques_proj*, img_proj*, the question-attention conv
-        # bf16 mode keeps projection + fusion in one autograd node (ImgFuseFn): its backward hands dP to the
-        # weight-gradient GEMM in bf16 without an fp32 round trip, which is worth more than the stream overlap
-        # (a real second stream -- overlap_streams is True -- keeps the bf16 hand-off too: MfbFuseFn takes / returns bf16)
-        side = self.overlap_streams and not (bf16_img and self.fuse_bf16_dp and not (self.overlap_streams is True and self.side_bf16))
-        proj = self._side.project(img3, self.img_conv1d, bf16_img,
-                                  self.overlap_streams == "same-stream", self.side_cu_limit) if side else None
+        proj = project_aside(self, img3, bf16_img)
         que_embedded = embed_tanh(self.word_embedding, questions)            # (N,T,E)
         if self.cfg.glove:
             assert glove_matrix is not None, 'glove should not be NoneType.'
@@ -105,24 +100,15 @@ class MHBCoAtt(nn.Module):
                              self.ques_att_conv2.weight, self.ques_att_conv2.bias, False, bf16_all, None, True)
         qp = LinearFn.apply(qa, self.ques_proj1.weight, self.ques_proj1.bias, False, bf16_all)
         pm = self.dropout_m.p
-        seed, p = self._seeds.next(self.training, pm)
-        k1 = keep.get('m1')
         coatt_bf16 = self.gemm_dtype in ("bf16", "bf16-att", "bf16-all")
         link = NormLink() if self.fold_norm else None
-        if proj is not None:
-            P0 = self._side.join(*proj)
-            Y = MfbFuseFn.apply(P0, self.img_conv1d.bias, qp, k1, seed, pm if k1 is not None else p, N, L, link, layout)
-        else:
-            Y = ImgFuseFn.apply(img3, self.img_conv1d.weight, self.img_conv1d.bias, qp,
-                                k1, seed, pm if k1 is not None else p, bf16_img, link, layout)
+        Y = join_or_fuse(self, proj, img3, qp, self._seeds.draw('m1', self.training, pm), bf16_img, N, L, link, layout)
         va = AttHeadFn.apply(Y, img_features, self.co_att_conv1.weight, self.co_att_conv1.bias, None, None,
                              self.co_att_conv2.weight, self.co_att_conv2.bias, False, coatt_bf16, link, False, layout)
         ys = []
         for tag, qpj, ipj in (('m2', self.ques_proj2, self.img_proj2), ('m3', self.ques_proj3, self.img_proj3)):
-            seed, p = self._seeds.next(self.training, pm)
-            kk = keep.get(tag)
-            ys.append(FinalMfbFn.apply(qa, va, qpj.weight, qpj.bias, ipj.weight, ipj.bias, kk, seed,
-                                       pm if kk is not None else p, None, False, bf16_all))
+            ys.append(FinalMfbFn.apply(qa, va, qpj.weight, qpj.bias, ipj.weight, ipj.bias, *self._seeds.draw(tag, self.training, pm),
+                                       None, False, bf16_all))
         # :147-148  linear_pred(cat((att_normed_2, att_normed_3), 1)): the concatenation is never materialised
         logits = Linear2Fn.apply(ys[0], ys[1], self.linear_pred.weight, self.linear_pred.bias)
         return LogSoftmaxRowsFn.apply(logits)                                # :149-151 (implicit dim = 1 on the 2-D logits)
@@ -159,7 +145,6 @@ class MHB(nn.Module):
 
     def forward(self, img_feature, questions, q_length):
         batch_size, max_len = questions.size()
-        keep = self._seeds.keep
         # AvgPool2d(14,14) over the (N,C,14,14) view == mean over the 196 regions   :178-180
         # (the glimpse kernel with unit weights sums the regions; fp32 or bf16 feature storage)
         img3 = img_feature.reshape(batch_size, -1, self.cfg.img_feature_channel)
@@ -182,16 +167,10 @@ class MHB(nn.Module):
         lstm_out = lstm_outs[idx, torch.arange(batch_size, device=lstm_outs.device)]   # :185-186
         lstm_out = lstm_out_dropout(self.lstm_dropout, lstm_out.unsqueeze(1), self._seeds).squeeze(1)      # :188
         pm = self.mfb_dropout.p
-        seed, p = self._seeds.next(self.training, pm)
-        k1 = keep.get('m1')
-        mhb_1, z1 = FinalMfbFn.apply(lstm_out, i_mean, self.linear_q_1.weight, self.linear_q_1.bias,
-                                     self.linear_i_1.weight, self.linear_i_1.bias, k1, seed,
-                                     pm if k1 is not None else p, None, True)       # :190-199
-        seed, p = self._seeds.next(self.training, pm)
-        k2 = keep.get('m2')
-        mhb_2 = FinalMfbFn.apply(lstm_out, i_mean, self.linear_q_2.weight, self.linear_q_2.bias,
-                                 self.linear_i_2.weight, self.linear_i_2.bias, k2, seed,
-                                 pm if k2 is not None else p, z1, False)             # :201-211
+        mhb_1, z1 = FinalMfbFn.apply(lstm_out, i_mean, self.linear_q_1.weight, self.linear_q_1.bias, self.linear_i_1.weight,
+                                     self.linear_i_1.bias, *self._seeds.draw('m1', self.training, pm), None, True)     # :190-199
+        mhb_2 = FinalMfbFn.apply(lstm_out, i_mean, self.linear_q_2.weight, self.linear_q_2.bias, self.linear_i_2.weight,
+                                 self.linear_i_2.bias, *self._seeds.draw('m2', self.training, pm), z1, False)          # :201-211
         # :213-214  linear_out(cat((mhb_1, mhb_2), 1)) without the concatenated tensor (:214 names mhb_22: see the class docstring)
         logits = Linear2Fn.apply(mhb_1, mhb_2, self.linear_out.weight, self.linear_out.bias)
         return LogSoftmaxRowsFn.apply(logits)                                # :215-217

@@ -32,11 +32,10 @@ class _AlwaysDropout:
         self._seeds = _DropSeeds()
 
     def _drop(self, x, tag):
-        explicit = self._seeds.keep.get(tag)
-        if explicit is None and self.drop_p <= 0.0:
+        keep, seed, rate = self._seeds.draw(tag, True, self.drop_p)        # always on; (a rate of 0 draws nothing)
+        if keep is None and rate <= 0.0:
             return x
-        seed, rate = self._seeds.next(True, self.drop_p)
-        return DropoutFn.apply(x, explicit, seed, self.drop_p if explicit is not None else rate)
+        return DropoutFn.apply(x, keep, seed, rate)
 
     def _drop_tokens(self, emb, tag):
         """dropout over a (N, T, E) embedding, applied on its flat (N*T, E) view."""
