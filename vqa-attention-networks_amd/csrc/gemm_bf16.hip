@@ -17,7 +17,7 @@
 // Requirements (else VQF_E_UNSUPPORTED and the caller uses the fp32 kernel): 16-byte aligned
 // bases, leading dimensions % 8 == 0; K-contiguous operand: K % 8 == 0; K-major operand: its row
 // extent % 8 == 0 and >= 8.
-#include "common.h"
+#include "gemm_host.h"
 
 namespace {
 
@@ -252,14 +252,6 @@ __global__ void __launch_bounds__(NTHREADS, 4) gemm_bf16_kernel(GemmArgs g) {
   }
 }
 
-template <bool TA, bool TB>
-int launch(const GemmArgs& g, dim3 grid, hipStream_t s) {
-  static VqfDynLdsFlags attr = {};
-  if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_bf16_kernel<TA, TB>), SMEM_BYTES, attr)) return e;
-  VQF_LAUNCH(KID_GEMM_BF16, (gemm_bf16_kernel<TA, TB>), grid, dim3(NTHREADS), SMEM_BYTES, s, g);
-  return vqf_last_error();
-}
-
 // y[r, c] = bf16(x[r, c]) for c < C, 0 for C <= c < ldy   (round-to-nearest-even, NaN kept).  One launch whatever R (round 4:
 // a workgroup per row with 8 columns per thread -- half of its threads idle at 1024 columns -- and one launch per 65535 rows)
 __global__ void cast_bf16_kernel(const float* __restrict__ x, int R, int C, int ldx,
@@ -335,21 +327,8 @@ static int gemm_bf16_impl(int ta, int tb, int M, int N, int K, const void* A, in
   const long long tiles = (long long)g.tiles_m * g.tiles_n;
   const int ktiles = (K + BK - 1) / BK;
   int splits = 1;
-  const int slots = 512;
-  if (ws && !rowscale && tiles < 1024 && ktiles >= 32) {
-    double best = 1e30;
-    for (int sp = 1; sp <= 16; ++sp) {
-      if (ktiles / sp < 16) break;
-      if ((size_t)sp * M * N * sizeof(float) > ws_bytes) break;
-      const double blocks = (double)tiles * sp;
-      const double rounds = (double)((long long)((blocks + slots - 1) / slots));
-      const double cost = rounds / sp * (1.0 + 0.01 * sp);
-      if (cost < best - 1e-12) { best = cost; splits = sp; }
-    }
-  }
-  const int kt_per = (ktiles + splits - 1) / splits;
-  g.kchunk = kt_per * BK;
-  splits = (K + g.kchunk - 1) / g.kchunk;
+  if (ws && !rowscale && tiles < 1024 && ktiles >= 32) splits = vqf_tile128_splits(tiles, ktiles, M, N, ws_bytes);
+  splits = vqf_splitk_chunks(K, BK, splits, &g.kchunk);
   if (splits > 1) {
     g.slab = (float*)ws;
     if (vqf_opt(VQF_OPT_GEMM_SPLITK_FUSED, 0) == 1) g.cnt = vqf_splitk_counters((int)tiles);
@@ -357,17 +336,10 @@ static int gemm_bf16_impl(int ta, int tb, int M, int N, int K, const void* A, in
   if (g_vqf_prof_on) vqf_prof_dims(M, N, K);
   vqf_stat_bump(VQF_STAT_GEMM_BF16_TILE128);
   dim3 grid((unsigned)tiles, (unsigned)splits);
-  int rc;
-  if (!ta && !tb) rc = launch<false, false>(g, grid, s);
-  else if (!ta && tb) rc = launch<false, true>(g, grid, s);
-  else if (ta && !tb) rc = launch<true, false>(g, grid, s);
-  else rc = launch<true, true>(g, grid, s);
-  if (rc != VQF_OK) {
-    vqf_splitk_counters_clear(g.cnt, (int)tiles, s);
-    return rc;
-  }
-  if (splits > 1 && !g.cnt) rc = vqf_splitk_reduce((const float*)ws, splits, M, N, C, ldc, bias, flags, s);
-  return rc;
+  const int rc = vqf_dispatch_ta_tb<false>(ta, tb, [&](auto TA, auto TB) {
+    return vqf_launch_dyn_lds<&gemm_bf16_kernel<TA(), TB()>>(KID_GEMM_BF16, grid, dim3(NTHREADS), SMEM_BYTES, s, g);
+  });
+  return vqf_splitk_finish(rc, g.cnt, (int)tiles, (const float*)ws, splits, M, N, C, ldc, bias, flags, s);
 }
 
 int vqf_cast_f32_bf16(const float* x, int R, int C, int ldx, void* y, int ldy, void* stream) {

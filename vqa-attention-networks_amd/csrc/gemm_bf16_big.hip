@@ -36,8 +36,7 @@
 //     can run these GEMMs beside the LSTM recursion.
 // Preconditions (else the caller falls back to gemm_bf16.hip): K % 32 == 0, M >= 256, N >= 128, no
 // accumulate flag, a K-major operand's row extent % 8 == 0; 16-byte aligned bases, lda/ldb % 8 == 0.
-#include "common.h"
-#include <algorithm>
+#include "gemm_host.h"
 #include <stdlib.h>
 
 namespace {
@@ -54,7 +53,6 @@ constexpr int SLOT_BYTES = 2 * OP_BYTES;               // 32 KB
 constexpr int NSLOT = 5;                               // slab s lives in slot s % 5: all 160 KB of LDS
 constexpr int SMEM_BIG = NSLOT * SLOT_BYTES;
 constexpr int NG = OP_BYTES / (NT * 16);               // 2 LDS-DMA instructions per thread per operand per slab
-constexpr int GROUP_M = 8;
 // ping-pong loop knobs (compile-time; tools/build_variant.sh for A/Bs)
 #ifndef VQF_PP_TAIL
 #define VQF_PP_TAIL 0          // MFMAs of a slab issued AFTER the barrier that ends M: the partner's MFMAs start behind them
@@ -153,7 +151,7 @@ __device__ __forceinline__ bf16x8 read_frag(const char* s, int row0, int ks, int
 }
 
 // ---- tile order: split index slowest; bijective XCD remap (blocks b and b + 8 share an XCD's L2: each XCD walks a
-// contiguous run of the linear order), then groups of GROUP_M row tiles x all column tiles, row tile fastest
+// contiguous run of the linear order), then groups of group_m row tiles x all column tiles, row tile fastest
 struct TileCoord { int z, m0, n0, kbeg; };
 // JOINT form (split-K launches, round 5): the remap runs over all splits x tiles items, so an XCD's contiguous run walks whole
 // groups of group_m = 32 / tiles_n row tiles x ALL column tiles of ONE split -- 32 tiles, one per CU of the XCD, that share
@@ -218,7 +216,7 @@ __global__ void __launch_bounds__(NT, 2) gemm_bf16_big_kernel(const BigArgs g) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;             // rows wr*128 .. +127, columns wc*64 .. +63
 
-  // ---- tile order: split index slowest; bijective XCD remap, then groups of GROUP_M row tiles, m fastest
+  // ---- tile order: split index slowest; bijective XCD remap, then groups of group_m row tiles, m fastest
   const TileCoord tc = tile_coord(g, blockIdx.x);
   const int z = tc.z, m0 = tc.m0, n0 = tc.n0, kbeg = tc.kbeg;
   const int S = (min(g.K, kbeg + g.kchunk) - kbeg) / TK;       // slabs of this split
@@ -701,52 +699,18 @@ int pick_splits(int tiles, int K, int M, int N, size_t ws_bytes) {
   return best;
 }
 
-// Row tiles per group of the tile order.  An XCD (private L2) works on a contiguous run of the order: the ~32 tiles
-// resident at a time when one split covers the chip, or its tiles / 8 share of EACH split for the few-tile split-K
-// launches (the image projection's weight gradient: 160 tiles -> 20 per XCD and split).  A run of `share` tiles
-// walked row-tile-fastest in groups of gm covers gm A panels + share / gm B panels: pick the gm in 4..8 that minimises
-// that, preferring one that divides the run (5 x 4 for the weight gradient: 12.3 -> 10.0 GB beyond L2, PMC).
-int pick_group_m(int tiles_m, int tiles_n, int splits) {
-  const int ntiles = tiles_m * tiles_n;
-  const int share = (splits > 1 && ntiles / 8 < 32) ? (ntiles / 8 > 0 ? ntiles / 8 : 1) : 32;
-  int best = GROUP_M, best_cost = 1 << 30;
-  for (int gm = 8; gm >= 4; --gm) {
-    const int cost = 4 * (gm + (share + gm - 1) / gm) + (share % gm ? 2 : 0) + (tiles_m % gm ? 1 : 0);
-    if (cost < best_cost) { best_cost = cost; best = gm; }
-  }
-  return best;
-}
-
 template <bool TA, bool TB>
 int launch(const BigArgs& g, hipStream_t s) {
-  // > 64 KB of dynamic LDS needs the attribute, once per device and instantiation (common.h)
-  static VqfDynLdsFlags attr = {}, attr_pp = {};
   const int loopf = vqf_opt(VQF_OPT_GEMM_BF16_LOOP, 1);  // A/B switch (tools/gemm_bf16_ab.py flips it in one process):
   const bool pingpong = loopf != 0;                    // 0 selects the lockstep kernel of round 1
   // the ping-pong kernels run as persistent workgroups, one per CU (VQF_GEMM_BF16_PERSIST=0: one workgroup per item)
   const int total = g.tiles_m * g.tiles_n * g.splits;
-  int nwg = total;
-  if (vqf_opt(VQF_OPT_GEMM_BF16_PERSIST, 1) != 0) {
-    int cus = vqf_cu_count() & ~7;                     // a multiple of 8 keeps every workgroup's items on its own XCD
-    const int lim = vqf_opt(VQF_OPT_GEMM_CU_LIMIT, 0) & ~7;
-    if (lim >= 8 && lim < cus) cus = lim;
-    if (cus >= 8 && total > cus) nwg = cus;
-  }
-  if (pingpong && !TA && !TB && loopf != 3) {          // VQF_OPT_GEMM_BF16_LOOP = 3: the 32x32x16 ping-pong loop also for (0,0)
-    static VqfDynLdsFlags attr16 = {};
-    if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_bf16_pp16_kernel), SMEM_BIG, attr16)) return e;
-    VQF_LAUNCH(KID_GEMM_BF16, gemm_bf16_pp16_kernel, dim3(nwg), dim3(NT), SMEM_BIG, s, g);
-    return vqf_last_error();
-  }
-  if (pingpong) {
-    if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_bf16_pp_kernel<TA, TB>), SMEM_BIG, attr_pp)) return e;
-    VQF_LAUNCH(KID_GEMM_BF16, (gemm_bf16_pp_kernel<TA, TB>), dim3(nwg), dim3(NT), SMEM_BIG, s, g);
-    return vqf_last_error();
-  }
-  if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_bf16_big_kernel<TA, TB>), SMEM_BIG, attr)) return e;
-  VQF_LAUNCH(KID_GEMM_BF16, (gemm_bf16_big_kernel<TA, TB>), dim3(g.tiles_m * g.tiles_n * g.splits), dim3(NT), SMEM_BIG,
-             s, g);
-  return vqf_last_error();
+  const dim3 grid(vqf_persistent_grid(total, vqf_opt(VQF_OPT_GEMM_BF16_PERSIST, 1) != 0, true)), block(NT);
+  // (> 64 KB of dynamic LDS needs the attribute, once per device and instantiation: gemm_host.h)
+  if (pingpong && !TA && !TB && loopf != 3)            // VQF_OPT_GEMM_BF16_LOOP = 3: the 32x32x16 ping-pong loop also for (0,0)
+    return vqf_launch_dyn_lds<&gemm_bf16_pp16_kernel>(KID_GEMM_BF16, grid, block, SMEM_BIG, s, g);
+  if (pingpong) return vqf_launch_dyn_lds<&gemm_bf16_pp_kernel<TA, TB>>(KID_GEMM_BF16, grid, block, SMEM_BIG, s, g);
+  return vqf_launch_dyn_lds<&gemm_bf16_big_kernel<TA, TB>>(KID_GEMM_BF16, dim3(total), block, SMEM_BIG, s, g);
 }
 
 bool big_applies(int ta, int tb, int M, int N, int K, int flags) {
@@ -788,30 +752,21 @@ int vqf_gemm_bf16_big_try(int ta, int tb, int M, int N, int K, const void* A, in
   g.tiles_n = (N + TN - 1) / TN;
   const int tiles = g.tiles_m * g.tiles_n;
   int splits = (flags & VQF_GEMM_OUT_BF16) ? 1 : pick_splits(tiles, K, M, N, (ws && aligned16(ws)) ? ws_bytes : 0);
-  const int slabs = K / TK;
-  const int per = (slabs + splits - 1) / splits;
-  g.kchunk = per * TK;
-  splits = (K + g.kchunk - 1) / g.kchunk;
+  splits = vqf_splitk_chunks(K, TK, splits, &g.kchunk);      // (K % TK == 0: big_applies)
   g.splits = splits;
   g.cnt = nullptr; g.Cfinal = C; g.ldc_final = ldc;
   if (splits > 1) {
     g.C = (float*)ws; g.ldc = N;
     if (tiles >= 64 && vqf_opt(VQF_OPT_GEMM_SPLITK_FUSED, 1) != 0) g.cnt = vqf_splitk_counters(tiles);   // (as gemm_f32_big.hip)
   }
-  g.group_m = pick_group_m(g.tiles_m, g.tiles_n, splits);
-  g.joint = 0;
-  if (splits > 1 && g.tiles_n <= 32 && 32 % g.tiles_n == 0 && vqf_opt(VQF_OPT_GEMM_SPLITK_ORDER, 0) == 1) {
-    g.joint = 1;                                        // an XCD's 32 CUs take group_m row tiles x all column tiles of one split
-    g.group_m = std::min(g.tiles_m, 32 / g.tiles_n);
-  }
+  g.group_m = vqf_pick_group_m(g.tiles_m, g.tiles_n, splits);
+  g.joint = vqf_splitk_joint_order(g.tiles_m, g.tiles_n, splits, &g.group_m);
 #ifdef VQF_PP_STAMPS
   g.dbg = (splits == 1 && ws && ws_bytes >= (size_t)tiles * 8 * 8 * 8) ? (unsigned long long*)ws : nullptr;
 #endif
   vqf_prof_dims(M, N, K);
   vqf_stat_bump(VQF_STAT_GEMM_BF16_BIG);
-  if (ta) *rc = tb ? launch<true, true>(g, s) : launch<true, false>(g, s);
-  else    *rc = tb ? launch<false, true>(g, s) : launch<false, false>(g, s);
-  if (*rc != VQF_OK) vqf_splitk_counters_clear(g.cnt, tiles, s);
-  if (*rc == VQF_OK && splits > 1 && !g.cnt) *rc = vqf_splitk_reduce((const float*)ws, splits, M, N, C, ldc, bias, flags, s);
+  *rc = vqf_dispatch_ta_tb(ta, tb, [&](auto TA, auto TB) { return launch<TA(), TB()>(g, s); });
+  *rc = vqf_splitk_finish(*rc, g.cnt, tiles, (const float*)ws, splits, M, N, C, ldc, bias, flags, s);
   return 1;
 }

@@ -26,7 +26,7 @@
 //     128-row slab of the (N*196, 2048) image tensor hit that XCD's L2.
 //   * split-K (grid.y) with a deterministic slab reduction for the wgrad
 //     shapes (few output tiles, K = N*196).
-#include "common.h"
+#include "gemm_host.h"
 #include <atomic>
 
 namespace {
@@ -481,22 +481,18 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ slab, int splits,
   }
 }
 
-template <bool TA, bool TB, bool FAST>
-int launch_gemm_impl(const GemmArgs& g, dim3 grid, hipStream_t s, int kid) {
-  static VqfDynLdsFlags attr = {};   // 72 KB of dynamic LDS: the attribute is needed on EVERY device this process uses
-  if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_f32_kernel<TA, TB, FAST>), SMEM_BYTES, attr)) return e;
-  VQF_LAUNCH(kid, (gemm_f32_kernel<TA, TB, FAST>), grid, dim3(NTHREADS), SMEM_BYTES, s, g);
-  return vqf_last_error();
-}
-
 template <bool TA, bool TB>
 int launch_gemm(const GemmArgs& g, dim3 grid, hipStream_t s, int kid) {
   // fast (clamped, unguarded) loaders need vector-aligned operands; K-major operands also need
   // the row extent to be a multiple of 4 and at least 4
   const bool okA = g.vecA && (!TA || (g.M % 4 == 0 && g.M >= 4));
   const bool okB = g.vecB && (!TB || (g.N % 4 == 0 && g.N >= 4));
-  if (okA && okB) return launch_gemm_impl<TA, TB, true>(g, grid, s, kid);
-  return launch_gemm_impl<TA, TB, false>(g, grid, s, kid);
+  // 72 KB of dynamic LDS: the attribute is needed on EVERY device this process uses
+  if (okA && okB) return vqf_launch_dyn_lds<&gemm_f32_kernel<TA, TB, true>>(kid, grid, dim3(NTHREADS), SMEM_BYTES, s, g);
+  return vqf_launch_dyn_lds<&gemm_f32_kernel<TA, TB, false>>(kid, grid, dim3(NTHREADS), SMEM_BYTES, s, g);
+}
+int launch_gemm(int ta, int tb, const GemmArgs& g, dim3 grid, hipStream_t s) {
+  return vqf_dispatch_ta_tb<false>(ta, tb, [&](auto TA, auto TB) { return launch_gemm<TA(), TB()>(g, grid, s, vqf_gemm_kid(ta, tb)); });
 }
 
 }  // namespace
@@ -549,58 +545,6 @@ extern "C" size_t vqf_gemm_f32_ws_bytes(int ta, int tb, int M, int N, int K) {
   return vqf_gemm_f32_big_ws_bytes(ta, tb, M, N, K);
 }
 
-static int gemm_tile128(int ta, int tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
-                        int ldc, const float* bias, int flags, const float* rowscale, int rps, int row0, void* ws,
-                        size_t ws_bytes, hipStream_t s);
-
-extern "C" int vqf_gemm_f32_big_rows(int ta, int tb, int M, int N, int K) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  return vqf_gemm_f32_big_rows_impl(ta, tb, M, N, K, 0, (size_t)1 << 40);
-}
-
-extern "C" int vqf_gemm_f32(int ta, int tb, int M, int N, int K, const float* A, int lda,
-                            const float* B, int ldb, float* C, int ldc, const float* bias,
-                            int flags, void* ws, size_t ws_bytes, void* stream) {
-  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || lda <= 0 || ldb <= 0 || ldc < N)
-    return VQF_E_BADARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (aligned16(A) && aligned16(B) && (lda % 4 == 0) && (ldb % 4 == 0)) {
-    int rc = VQF_OK, done = 0;
-    // large shapes take the 256x256-tile LDS-DMA kernel (gemm_f32_big.hip) ...
-    if (vqf_gemm_f32_big_try(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, nullptr, 1, ws, ws_bytes, s, &rc, &done)) {
-      if (rc != VQF_OK || done >= M) return rc;
-      // ... mid-size ones its whole-rounds row block only (ta == 0 there): the remaining rows follow below
-      // (always the 128x128 kernel, without split-K: it adds a row's k in the same order, so the split product has the bits of the unsplit one)
-      A += (size_t)done * lda; C += (size_t)done * ldc; M -= done;
-      ws = nullptr; ws_bytes = 0;
-    }
-    // small-M products (the LSTM's recurrent GEMMs): one tile per wave, no split-K slabs / reduce launch (gemm_f32_wave.hip)
-    else if (vqf_gemm_f32_wave_try(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, s, &rc)) return rc;
-    // the M = 512 forward projections: one round of 128x80 tiles, no K slices (gemm_f32_n80.hip)
-    else if (!ta && !tb && vqf_gemm_f32_n80_try(M, N, K, A, lda, B, ldb, C, ldc, bias, flags, s, &rc)) return rc;
-  }
-  return gemm_tile128(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, nullptr, 1, 0, ws, ws_bytes, s);
-}
-
-extern "C" int vqf_gemm_f32_rowscale(int ta, int tb, int M, int N, int K, const float* A, int lda, const float* B,
-                                     int ldb, float* C, int ldc, const float* bias, int flags, const float* rowscale,
-                                     int rows_per_scale, void* stream) {
-  if (!A || !B || !C || !rowscale || rows_per_scale <= 0 || M <= 0 || N <= 0 || K <= 0 || lda <= 0 || ldb <= 0 || ldc < N)
-    return VQF_E_BADARG;
-  if (flags & VQF_GEMM_ACCUM) return VQF_E_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  int row0 = 0;
-  if (aligned16(A) && aligned16(B) && (lda % 4 == 0) && (ldb % 4 == 0)) {
-    int rc = VQF_OK, done = 0;
-    if (vqf_gemm_f32_big_try(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, rowscale, rows_per_scale, nullptr, 0, s, &rc,
-                             &done)) {
-      if (rc != VQF_OK || done >= M) return rc;
-      A += (size_t)done * lda; C += (size_t)done * ldc; M -= done; row0 = done;
-    }
-  }
-  return gemm_tile128(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, rowscale, rows_per_scale, row0, nullptr, 0, s);
-}
-
 // the 128x128-tile kernel of this file (ws == nullptr: no split-K)
 static int gemm_tile128(int ta, int tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
                         int ldc, const float* bias, int flags, const float* rowscale, int rps, int row0, void* ws,
@@ -615,33 +559,17 @@ static int gemm_tile128(int ta, int tb, int M, int N, int K, const float* A, int
   g.vecA = aligned16(A) && (lda % 4 == 0);
   g.vecB = aligned16(B) && (ldb % 4 == 0);
 
-  // split-K: only when the output has too few tiles to fill the chip and K is deep.  Two
-  // workgroups per CU already keep the matrix pipe busy (the others only cover bubbles), so the
-  // wave-quantisation model uses 512 slots; measured: img_conv1d wgrad (640 tiles) 134 TF at 4
-  // splits vs 124 TF at 8.
+  // split-K: only when the output has too few tiles to fill the chip and K is deep (the cost model: gemm_host.h)
   const long long tiles = (long long)g.tiles_m * g.tiles_n;
   const int ktiles = (K + BK - 1) / BK;
   int splits = 1;
-  const int slots = 512;
   // (a chip-filling output with a short K is not split either: 5000 x 2048 x 512, 640 tiles -- two slices + the 123 MB slab
   //  reduce 130 us, unsplit 110, tools/gemm_m512_probe.py)
   // (nor a product that fills most of the CUs once with K <= 512: 3584 x 1024 x 512, 224 tiles -- two slices + reduce 59-61 us,
   //  unsplit 52-53, tools/small_gemm_splitk_ab.py)
-  if (ws && tiles < 1024 && ktiles >= 32 && !(tiles >= 512 && K <= 1024) && !(tiles >= 192 && tiles <= 256 && K <= 512)) {
-    double best = 1e30;
-    for (int sp = 1; sp <= 16; ++sp) {
-      if (ktiles / sp < 16) break;
-      if ((size_t)sp * M * N * sizeof(float) > ws_bytes) break;
-      const double blocks = (double)tiles * sp;
-      const double rounds = (double)((long long)((blocks + slots - 1) / slots));
-      // time ~ rounds * (per-block work ~ 1/sp) ; small penalty per split for the reduce pass
-      const double cost = rounds / sp * (1.0 + 0.01 * sp);
-      if (cost < best - 1e-12) { best = cost; splits = sp; }
-    }
-  }
-  int kt_per = (ktiles + splits - 1) / splits;
-  g.kchunk = kt_per * BK;
-  splits = (K + g.kchunk - 1) / g.kchunk;
+  if (ws && tiles < 1024 && ktiles >= 32 && !(tiles >= 512 && K <= 1024) && !(tiles >= 192 && tiles <= 256 && K <= 512))
+    splits = vqf_tile128_splits(tiles, ktiles, M, N, ws_bytes);
+  splits = vqf_splitk_chunks(K, BK, splits, &g.kchunk);
   if (splits > 1) {
     g.slab = (float*)ws;
     // option gemm_splitk_fused = 1: combined inside this launch by each tile's last-arriving workgroup.  NOT the default for
@@ -653,20 +581,58 @@ static int gemm_tile128(int ta, int tb, int M, int N, int K, const float* A, int
   }
 
   dim3 grid((unsigned)tiles, (unsigned)splits);
-  const int kid = KID_GEMM_A0B0 + 2 * (ta ? 1 : 0) + (tb ? 1 : 0);
   if (g_vqf_prof_on) vqf_prof_dims(M, N, K);
   vqf_stat_bump(VQF_STAT_GEMM_F32_TILE128);
-  int rc;
-  if (!ta && !tb) rc = launch_gemm<false, false>(g, grid, s, kid);
-  else if (!ta && tb) rc = launch_gemm<false, true>(g, grid, s, kid);
-  else if (ta && !tb) rc = launch_gemm<true, false>(g, grid, s, kid);
-  else rc = launch_gemm<true, true>(g, grid, s, kid);
-  if (rc != VQF_OK) {
-    vqf_splitk_counters_clear(g.cnt, (int)tiles, s);
-    return rc;
+  const int rc = launch_gemm(ta, tb, g, grid, s);
+  return vqf_splitk_finish(rc, g.cnt, (int)tiles, (const float*)ws, splits, M, N, C, ldc, bias, flags, s);
+}
+
+extern "C" int vqf_gemm_f32_big_rows(int ta, int tb, int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  return vqf_gemm_f32_big_rows_impl(ta, tb, M, N, K, 0, (size_t)1 << 40);
+}
+
+// Both entry points: rowscale == nullptr is the plain product, the only one with a workspace (split-K) and the only one the
+// per-wave and the 128x80 kernels take (the epilogue scale lives in the large-tile and the 128x128 kernels).
+static int gemm_f32_impl(int ta, int tb, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
+                         int ldc, const float* bias, int flags, const float* rowscale, int rps, void* ws, size_t ws_bytes,
+                         hipStream_t s) {
+  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || lda <= 0 || ldb <= 0 || ldc < N)
+    return VQF_E_BADARG;
+  if (rowscale && (flags & VQF_GEMM_ACCUM)) return VQF_E_UNSUPPORTED;
+  int row0 = 0;
+  if (aligned16(A) && aligned16(B) && (lda % 4 == 0) && (ldb % 4 == 0)) {
+    int rc = VQF_OK, done = 0;
+    // large shapes take the 256x256-tile LDS-DMA kernel (gemm_f32_big.hip) ...
+    if (vqf_gemm_f32_big_try(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, rowscale, rps, ws, ws_bytes, s, &rc, &done)) {
+      if (rc != VQF_OK || done >= M) return rc;
+      // ... mid-size ones its whole-rounds row block only (ta == 0 there): the remaining rows follow below
+      // (always the 128x128 kernel, without split-K: it adds a row's k in the same order, so the split product has the bits of the unsplit one)
+      A += (size_t)done * lda; C += (size_t)done * ldc; M -= done;
+      if (rowscale) row0 = done;
+      ws = nullptr; ws_bytes = 0;
+    } else if (!rowscale) {
+      // small-M products (the LSTM's recurrent GEMMs): one tile per wave, no split-K slabs / reduce launch (gemm_f32_wave.hip)
+      if (vqf_gemm_f32_wave_try(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, s, &rc)) return rc;
+      // the M = 512 forward projections: one round of 128x80 tiles, no K slices (gemm_f32_n80.hip)
+      if (!ta && !tb && vqf_gemm_f32_n80_try(M, N, K, A, lda, B, ldb, C, ldc, bias, flags, s, &rc)) return rc;
+    }
   }
-  if (splits > 1 && !g.cnt) rc = vqf_splitk_reduce((const float*)ws, splits, M, N, C, ldc, bias, flags, s);
-  return rc;
+  return gemm_tile128(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, rowscale, rps, row0, ws, ws_bytes, s);
+}
+
+extern "C" int vqf_gemm_f32(int ta, int tb, int M, int N, int K, const float* A, int lda,
+                            const float* B, int ldb, float* C, int ldc, const float* bias,
+                            int flags, void* ws, size_t ws_bytes, void* stream) {
+  return gemm_f32_impl(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, nullptr, 1, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int vqf_gemm_f32_rowscale(int ta, int tb, int M, int N, int K, const float* A, int lda, const float* B,
+                                     int ldb, float* C, int ldc, const float* bias, int flags, const float* rowscale,
+                                     int rows_per_scale, void* stream) {
+  if (!rowscale || rows_per_scale <= 0) return VQF_E_BADARG;
+  return gemm_f32_impl(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, rowscale, rows_per_scale, nullptr, 0,
+                       (hipStream_t)stream);
 }
 
 // Batched form (grid.z = batch, no bias, no split-K): the per-sample products of
@@ -689,11 +655,6 @@ extern "C" int vqf_gemm_f32_batched(int ta, int tb, int batch, int M, int N, int
   g.vecB = aligned16(B) && (ldb % 4 == 0) && (strideB % 4 == 0);
   g.kchunk = ((K + BK - 1) / BK) * BK;
   dim3 grid((unsigned)(g.tiles_m * g.tiles_n), 1, (unsigned)batch);
-  hipStream_t s = (hipStream_t)stream;
-  const int kid = KID_GEMM_A0B0 + 2 * (ta ? 1 : 0) + (tb ? 1 : 0);
   vqf_stat_bump(VQF_STAT_GEMM_F32_TILE128);
-  if (!ta && !tb) return launch_gemm<false, false>(g, grid, s, kid);
-  if (!ta && tb) return launch_gemm<false, true>(g, grid, s, kid);
-  if (ta && !tb) return launch_gemm<true, false>(g, grid, s, kid);
-  return launch_gemm<true, true>(g, grid, s, kid);
+  return launch_gemm(ta, tb, g, grid, (hipStream_t)stream);
 }

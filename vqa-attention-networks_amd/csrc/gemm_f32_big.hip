@@ -28,8 +28,7 @@
 //     waves 0-3 (2).
 // Preconditions (else the caller uses gemm_f32.hip): K % 4 == 0 (a last slab shorter than 16 k is zero-filled), M >= 256, N >= 128, >= 1024 workgroups (tiles x
 // splits), no accumulate flag, 16-byte aligned bases, lda/ldb % 4 == 0, a K-major operand's row extent % 4 == 0.
-#include "common.h"
-#include <algorithm>
+#include "gemm_host.h"
 #include <stdlib.h>
 
 namespace {
@@ -49,10 +48,6 @@ constexpr int SLOT_BYTES = 2 * OP_BYTES;
 constexpr int NSLOT = VQF_F32BIG_NSLOT;                // slab s lives in slot s % NSLOT
 constexpr int SMEM_BIG = NSLOT * SLOT_BYTES;
 constexpr int NG = OP_BYTES / (NT * 16);               // 2 LDS-DMA instructions per thread per operand per slab
-#ifndef VQF_F32BIG_GROUP_M
-#define VQF_F32BIG_GROUP_M 8
-#endif
-constexpr int GROUP_M = VQF_F32BIG_GROUP_M;
 #ifndef VQF_F32BIG_DEFAULT_MODE
 #define VQF_F32BIG_DEFAULT_MODE 2     // loop form when the option gemm_f32_loop is unset (see k_loop)
 #endif
@@ -462,7 +457,7 @@ __global__ void __launch_bounds__(NT, 2) gemm_f32_big_kernel(const BigArgs g) {
   // NSLOT-1 slabs right behind its own output stores, and the next K loop starts on landed data instead of paying a
   // workgroup turn-around (7.8 us per 467-us tile of the image projection: tools/f32_clock.py) plus a cold prologue.
   // ---- work-item order, PHASE 1 (column tiles 0 .. tiles_n_full-1): split index slowest; bijective XCD remap, then groups
-  // of GROUP_M row tiles, m fastest.  PHASE 2 (only when the last column tile is short and the host split it off): its
+  // of group_m row tiles, m fastest.  PHASE 2 (only when the last column tile is short and the host split it off): its
   // tiles_m edge tiles cost a fraction of a full tile (see the wave map above), so they are dealt at the end, starting at
   // the workgroups that drew one full tile fewer in phase 1 (edge_w0, edge_wn: the host picks the deal that minimises
   // the longest workgroup).
@@ -678,22 +673,6 @@ int pick_splits(int tiles, int K, int M, int N, size_t ws_bytes) {
   return best;
 }
 
-// Row tiles per group of the tile order.  An XCD (private L2) works on a contiguous run of the order: the ~32 tiles
-// resident at a time when one split covers the chip, or its tiles / 8 share of EACH split for the few-tile split-K
-// launches (the image projection's weight gradient: 160 tiles -> 20 per XCD and split).  A run of `share` tiles
-// walked row-tile-fastest in groups of gm covers gm A panels + share / gm B panels: pick the gm in 4..8 that minimises
-// that, preferring one that divides the run (5 x 4 for the weight gradient: 12.3 -> 10.0 GB beyond L2, PMC).
-int pick_group_m(int tiles_m, int tiles_n, int splits) {
-  const int ntiles = tiles_m * tiles_n;
-  const int share = (splits > 1 && ntiles / 8 < 32) ? (ntiles / 8 > 0 ? ntiles / 8 : 1) : 32;
-  int best = GROUP_M, best_cost = 1 << 30;
-  for (int gm = 8; gm >= 4; --gm) {
-    const int cost = 4 * (gm + (share + gm - 1) / gm) + (share % gm ? 2 : 0) + (tiles_m % gm ? 1 : 0);
-    if (cost < best_cost) { best_cost = cost; best = gm; }
-  }
-  return best;
-}
-
 // Phase 2 of the work order: which workgroups take the short edge tiles (kernel header).  Costs in eighths of a full tile:
 // a full tile keeps every SIMD busy for 8 units, an edge tile for nj0 + nj1 (one wave of each column strip per SIMD).
 // After phase 1 the first h = F % G workgroups hold one full tile more than the others ("light").  Two deals are priced
@@ -718,45 +697,22 @@ void deal_edge_tiles(BigArgs& g, int G) {
 
 template <bool TA, bool TB>
 int launch(const BigArgs& g_in, hipStream_t s) {
-  // > 64 KB of dynamic LDS needs the attribute, once per device and instantiation (common.h)
-  static VqfDynLdsFlags attr = {}, attr_pp = {};
   const int lo = vqf_opt(VQF_OPT_GEMM_F32_LOOP, VQF_F32BIG_DEFAULT_MODE);   // A/B switch: 0 lockstep, 1 ping-pong, 2 staggered lockstep
   const int mode = (lo >= 0 && lo <= 2) ? lo : VQF_F32BIG_DEFAULT_MODE;
-  const int kid = KID_GEMM_A0B0 + 2 * (TA ? 1 : 0) + (TB ? 1 : 0);
+  const int kid = vqf_gemm_kid(TA, TB);
   // persistent workgroups: one per CU, each walking its share of the work items (VQF_OPT_GEMM_F32_PERSIST = 0: one
   // workgroup per item, as in round 1); VQF_OPT_GEMM_CU_LIMIT leaves part of the chip to other streams
   const int total = g_in.tiles_m * g_in.tiles_n * g_in.splits;
-  int nwg = total;
-  if (vqf_opt(VQF_OPT_GEMM_F32_PERSIST, 1) != 0) {
-    int cus = vqf_cu_count() & ~7;                     // a multiple of 8 keeps every workgroup's items on its own XCD
-    const int lim = vqf_opt(VQF_OPT_GEMM_CU_LIMIT, 0) & ~7;
-    if (lim >= 8 && lim < cus) cus = lim;
-    if (cus >= 8 && total > cus) nwg = cus;
-  }
-  const dim3 grid(nwg);
+  const int nwg = vqf_persistent_grid(total, vqf_opt(VQF_OPT_GEMM_F32_PERSIST, 1) != 0, true);
+  const dim3 grid(nwg), block(NT);
   BigArgs g = g_in;
   deal_edge_tiles(g, nwg);
-  if (g.sk_tail > 0) {                                 // stream-K tail: one loop form (the default one)
-    static VqfDynLdsFlags attr_sk = {};
-    if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_f32_big_kernel<TA, TB, VQF_F32BIG_DEFAULT_MODE, true>), SMEM_BIG, attr_sk))
-      return e;
-    VQF_LAUNCH(kid, (gemm_f32_big_kernel<TA, TB, VQF_F32BIG_DEFAULT_MODE, true>), grid, dim3(NT), SMEM_BIG, s, g);
-    return vqf_last_error();
-  }
-  if (mode == 1) {
-    if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_f32_big_kernel<TA, TB, 1>), SMEM_BIG, attr_pp)) return e;
-    VQF_LAUNCH(kid, (gemm_f32_big_kernel<TA, TB, 1>), grid, dim3(NT), SMEM_BIG, s, g);
-    return vqf_last_error();
-  }
-  if (mode == 2) {
-    static VqfDynLdsFlags attr_st = {};
-    if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_f32_big_kernel<TA, TB, 2>), SMEM_BIG, attr_st)) return e;
-    VQF_LAUNCH(kid, (gemm_f32_big_kernel<TA, TB, 2>), grid, dim3(NT), SMEM_BIG, s, g);
-    return vqf_last_error();
-  }
-  if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_f32_big_kernel<TA, TB, 0>), SMEM_BIG, attr)) return e;
-  VQF_LAUNCH(kid, (gemm_f32_big_kernel<TA, TB, 0>), grid, dim3(NT), SMEM_BIG, s, g);
-  return vqf_last_error();
+  // (> 64 KB of dynamic LDS needs the attribute, once per device and instantiation: gemm_host.h)
+  if (g.sk_tail > 0)                                   // stream-K tail: one loop form (the default one)
+    return vqf_launch_dyn_lds<&gemm_f32_big_kernel<TA, TB, VQF_F32BIG_DEFAULT_MODE, true>>(kid, grid, block, SMEM_BIG, s, g);
+  if (mode == 1) return vqf_launch_dyn_lds<&gemm_f32_big_kernel<TA, TB, 1>>(kid, grid, block, SMEM_BIG, s, g);
+  if (mode == 2) return vqf_launch_dyn_lds<&gemm_f32_big_kernel<TA, TB, 2>>(kid, grid, block, SMEM_BIG, s, g);
+  return vqf_launch_dyn_lds<&gemm_f32_big_kernel<TA, TB, 0>>(kid, grid, block, SMEM_BIG, s, g);
 }
 
 #ifndef F32BIG_MIN_K
@@ -891,9 +847,7 @@ int vqf_gemm_f32_big_try(int ta, int tb, int M, int N, int K, const float* A, in
   int splits = whole ? pick_splits(tiles, K, Mb, N, ws_ok) : 1;
   if (splits > 1 && (rowscale || (K % TK))) return 0;        // (neither occurs: split-K shapes are the deep-K weight gradients)
   const int slabs = (K + TK - 1) / TK;
-  const int per = (slabs + splits - 1) / splits;
-  g.kchunk = per * TK;
-  splits = (K + g.kchunk - 1) / g.kchunk;
+  splits = vqf_splitk_chunks(K, TK, splits, &g.kchunk);
   g.splits = splits;
   g.cnt = nullptr; g.Cfinal = C; g.ldc_final = ldc;
   g.sk_tail = 0; g.sk_fw = 0; g.sk_V = 0; g.sk_q = 0; g.sk_slab = nullptr;
@@ -921,21 +875,15 @@ int vqf_gemm_f32_big_try(int ta, int tb, int M, int N, int K, const float* A, in
   const bool edge_opt = !tb && splits == 1 && g.tiles_n > 1 && rem > 0 && rem <= 192 && vqf_opt(VQF_OPT_GEMM_F32_EDGE, 1) != 0;
   g.tiles_n_full = edge_opt ? g.tiles_n - 1 : g.tiles_n;
   g.edge_w0 = 0; g.edge_wn = 1;
-  g.group_m = pick_group_m(g.tiles_m, g.tiles_n_full, splits);
-  g.joint = 0;
-  if (splits > 1 && g.sk_tail == 0 && g.tiles_n <= 32 && 32 % g.tiles_n == 0 && vqf_opt(VQF_OPT_GEMM_SPLITK_ORDER, 0) == 1) {
-    g.joint = 1;                                        // an XCD's 32 CUs take group_m row tiles x all column tiles of one split
-    g.group_m = std::min(g.tiles_m, 32 / g.tiles_n);
-  }
+  g.group_m = vqf_pick_group_m(g.tiles_m, g.tiles_n_full, splits);
+  g.joint = g.sk_tail == 0 ? vqf_splitk_joint_order(g.tiles_m, g.tiles_n, splits, &g.group_m) : 0;
 #ifdef VQF_F32BIG_CLOCK
   g.dbg = (splits == 1 && ws && ws_bytes >= (size_t)tiles * 2 * 8 * 8) ? (unsigned long long*)ws : nullptr;
 #endif
   vqf_prof_dims(Mb, N, K);
   vqf_stat_bump(VQF_STAT_GEMM_F32_BIG);
-  if (ta) *rc = tb ? launch<true, true>(g, s) : launch<true, false>(g, s);
-  else    *rc = tb ? launch<false, true>(g, s) : launch<false, false>(g, s);
-  if (*rc != VQF_OK) vqf_splitk_counters_clear(g.cnt, g.sk_tail > 0 ? g.sk_tail : tiles, s);
-  if (*rc == VQF_OK && splits > 1 && !g.cnt) *rc = vqf_splitk_reduce((const float*)ws, splits, Mb, N, C, ldc, bias, flags, s);
+  *rc = vqf_dispatch_ta_tb(ta, tb, [&](auto TA, auto TB) { return launch<TA(), TB()>(g, s); });
+  *rc = vqf_splitk_finish(*rc, g.cnt, g.sk_tail > 0 ? g.sk_tail : tiles, (const float*)ws, splits, Mb, N, C, ldc, bias, flags, s);
   *rows_done = Mb;
   return 1;
 }

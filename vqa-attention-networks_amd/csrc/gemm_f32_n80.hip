@@ -19,7 +19,7 @@
 // load and masked on store).
 // The same kernel with FOUR column tiles = the four gates of 16 hidden units is the fused LSTM forward step
 // (gemm_f32_n80_kernel<4, true>, vqf_lstm_step16_try below; mfb.py:69).
-#include "common.h"
+#include "gemm_host.h"
 
 namespace {
 
@@ -234,6 +234,14 @@ __global__ void __launch_bounds__(NT, 1) gemm_f32_n80_kernel(const N80Args g) {
   }
 }
 
+// Workgroups of a launch of `tiles` tiles, or 0 when they are not one round that fills most of the chip (a chip whose CU count
+// is unknown counts as 256 CUs): the tile count rounded up to whole XCDs.
+int one_round_grid(long long tiles) {
+  const int n = vqf_cu_count(), cus = n > 0 ? n : 256;
+  if (tiles > cus || tiles * 10 < (long long)cus * 8) return 0;
+  return ((int)tiles + 7) & ~7;
+}
+
 }  // namespace
 
 // 1 (and *rc set) when the kernel took the product; 0: not its shape.  Used by vqf_gemm_f32 for ta == tb == 0.
@@ -243,20 +251,16 @@ int vqf_gemm_f32_n80_try(int M, int N, int K, const float* A, int lda, const flo
   if ((flags & ~VQF_GEMM_RELU) || (K % 128) || K < 512 || !aligned16(A) || !aligned16(B) || (lda % 4) || (ldb % 4)) return 0;
   const int tiles_m = (M + TM - 1) / TM, tiles_n = (N + TN - 1) / TN;
   const long long tiles = (long long)tiles_m * tiles_n;
-  const int cus = vqf_cu_count() > 0 ? vqf_cu_count() : 256;
   // one round that fills most of the chip; with fewer tiles the 128x128 kernel's K slices win, with more its whole tiles do
-  if (tiles > cus || tiles * 10 < (long long)cus * 8 || M > 1024) return 0;
+  const int nwg = one_round_grid(tiles);
+  if (!nwg || M > 1024) return 0;
   if (vqf_opt(VQF_OPT_GEMM_CU_LIMIT, 0) >= 8) return 0;    // (a CU-limited side stream keeps its persistent kernels)
   N80Args g;
   g.A = A; g.B = B; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.flags = flags;
   g.tiles_m = tiles_m; g.tiles = (int)tiles;
-  const int nwg = ((int)tiles + 7) & ~7;
   vqf_prof_dims(M, N, K);
   vqf_stat_bump(VQF_STAT_GEMM_F32_N80);
-  static VqfDynLdsFlags attr = {};
-  if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_f32_n80_kernel<5, false>), NSLOT * slot_bytes(5), attr)) { *rc = e; return 1; }
-  VQF_LAUNCH(KID_GEMM_A0B0, (gemm_f32_n80_kernel<5, false>), dim3(nwg), dim3(NT), NSLOT * slot_bytes(5), s, g);
-  *rc = vqf_last_error();
+  *rc = vqf_launch_dyn_lds<&gemm_f32_n80_kernel<5, false>>(KID_GEMM_A0B0, dim3(nwg), dim3(NT), NSLOT * slot_bytes(5), s, g);
   return 1;
 }
 
@@ -267,18 +271,14 @@ int vqf_lstm_step16_try(const float* h_prev, const float* w_hh, float* gates, co
   if ((B % TM) || (H % 128) || H < 512) return 0;          // whole row tiles (the cell has no edge guards), K = H in 128-k units
   const int tiles_m = B / TM, tiles_n = H / 16;
   const long long tiles = (long long)tiles_m * tiles_n;
-  const int cus = vqf_cu_count() > 0 ? vqf_cu_count() : 256;
-  if (tiles > cus || tiles * 10 < (long long)cus * 8) return 0;
+  const int nwg = one_round_grid(tiles);
+  if (!nwg) return 0;
   N80Args g = {};
   g.A = h_prev; g.B = w_hh; g.C = gates; g.M = B; g.N = 4 * H; g.K = H; g.lda = H; g.ldb = H; g.ldc = 4 * H;
   g.tiles_m = tiles_m; g.tiles = (int)tiles;
   g.c_prev = c_prev; g.c_out = c_out; g.h_out = h_out; g.H = H;
-  const int nwg = ((int)tiles + 7) & ~7;
   vqf_prof_dims(B, 4 * H, H);
   vqf_stat_bump(VQF_STAT_GEMM_F32_N80);
-  static VqfDynLdsFlags attr = {};
-  if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_f32_n80_kernel<4, true>), NSLOT * slot_bytes(4), attr)) { *rc = e; return 1; }
-  VQF_LAUNCH(KID_LSTM_CELL_FWD, (gemm_f32_n80_kernel<4, true>), dim3(nwg), dim3(NT), NSLOT * slot_bytes(4), s, g);
-  *rc = vqf_last_error();
+  *rc = vqf_launch_dyn_lds<&gemm_f32_n80_kernel<4, true>>(KID_LSTM_CELL_FWD, dim3(nwg), dim3(NT), NSLOT * slot_bytes(4), s, g);
   return 1;
 }

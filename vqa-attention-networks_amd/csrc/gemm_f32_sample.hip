@@ -19,7 +19,7 @@
 // + e), the ragged rows included: the same bits as gemm_f32.hip / gemm_f32_big.hip on the same operands.
 // B: K-contiguous (N, K) (forward products) or K-major (K, N) (input gradients).  Preconditions: N % 256 == 0, K % 16 == 0,
 // 16-byte aligned bases, lda / ldb / ldc % 4 == 0.
-#include "common.h"
+#include "gemm_host.h"
 
 namespace {
 
@@ -339,23 +339,13 @@ int vqf_gemm_f32_sample(int tb, int NS, int L, int N, int K, const float* A, int
   g.A = A; g.B = B; g.C = C; g.bias = bias;
   g.NS = NS; g.L = L; g.M = NS * L; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.flags = flags;
   g.tiles_n = N / TN;
-  const int items = NS * g.tiles_n;
-  int cus = vqf_cu_count();
-  const int lim = vqf_opt(VQF_OPT_GEMM_CU_LIMIT, 0) & ~7;
-  if (lim >= 8 && lim < cus) cus = lim;
-  const int nwg = items < cus ? items : cus;
+  const int nwg = vqf_persistent_grid(NS * g.tiles_n, true, false);
   hipStream_t s = (hipStream_t)stream;
   vqf_prof_dims(g.M, N, K);
   vqf_stat_bump(VQF_STAT_GEMM_F32_SAMPLE);
-  static VqfDynLdsFlags attr0 = {}, attr1 = {};
-  if (tb) {
-    if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_f32_sample_kernel<true>), SMEM, attr1)) return e;
-    VQF_LAUNCH(KID_GEMM_A0B1, gemm_f32_sample_kernel<true>, dim3(nwg), dim3(NT), SMEM, s, g);
-  } else {
-    if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_f32_sample_kernel<false>), SMEM, attr0)) return e;
-    VQF_LAUNCH(KID_GEMM_A0B0, gemm_f32_sample_kernel<false>, dim3(nwg), dim3(NT), SMEM, s, g);
-  }
-  return vqf_last_error();
+  return vqf_dispatch_bool(tb, [&](auto TB) {
+    return vqf_launch_dyn_lds<&gemm_f32_sample_kernel<TB()>>(vqf_gemm_kid(0, TB()), dim3(nwg), dim3(NT), SMEM, s, g);
+  });
 }
 
 }  // extern "C"

@@ -21,7 +21,7 @@
 // two accumulator tiles are 8 contiguous output bytes.
 // Preconditions (else the caller uses gemm_f32.hip): A K-contiguous, K % 16 == 0 (K % 64 for WK = 4), 16-byte
 // aligned bases, lda/ldb % 4 == 0, N % 4 == 0 for a K-major B.
-#include "common.h"
+#include "gemm_host.h"
 #include <stdlib.h>
 
 namespace {
@@ -414,11 +414,8 @@ __global__ void __launch_bounds__(NT, 1) gemm_f32_wave_shb_kernel(const WaveArgs
 
 template <bool TB, int NSL>
 int launch_shb(const WaveArgs& g, int nwg, hipStream_t s) {
-  static VqfDynLdsFlags attr = {};
   constexpr int SMEM_SHB = NSL * (4 * A_BYTES + B_BYTES);
-  if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_f32_wave_shb_kernel<TB, NSL>), SMEM_SHB, attr)) return e;
-  VQF_LAUNCH(KID_GEMM_A0B0 + (TB ? 1 : 0), (gemm_f32_wave_shb_kernel<TB, NSL>), dim3(nwg), dim3(NT), SMEM_SHB, s, g);
-  return vqf_last_error();
+  return vqf_launch_dyn_lds<&gemm_f32_wave_shb_kernel<TB, NSL>>(vqf_gemm_kid(0, TB), dim3(nwg), dim3(NT), SMEM_SHB, s, g);
 }
 
 // ---- one LSTM step of the question encoder in ONE launch (mfb.py:69; host/functions.py::LstmBatchFn) --------------------------
@@ -549,20 +546,9 @@ __global__ void __launch_bounds__(NT, 1) gemm_f32_lstm_fwd_kernel(const WaveArgs
   }
 }
 
-int launch_lstm_fwd(const WaveArgs& g, int nwg, hipStream_t s) {
-  static VqfDynLdsFlags attr = {};
-  constexpr int SMEM_SHB = 6 * (4 * A_BYTES + B_BYTES);
-  if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_f32_lstm_fwd_kernel), SMEM_SHB, attr)) return e;
-  VQF_LAUNCH(KID_LSTM_CELL_FWD, gemm_f32_lstm_fwd_kernel, dim3(nwg), dim3(NT), SMEM_SHB, s, g);
-  return vqf_last_error();
-}
-
 template <bool TB, int WK>
 int launch(const WaveArgs& g, int nwg, hipStream_t s) {
-  static VqfDynLdsFlags attr = {};
-  if (int e = vqf_set_dyn_lds(reinterpret_cast<const void*>(&gemm_f32_wave_kernel<TB, WK>), SMEM_WAVE, attr)) return e;
-  VQF_LAUNCH(KID_GEMM_A0B0 + (TB ? 1 : 0), (gemm_f32_wave_kernel<TB, WK>), dim3(nwg), dim3(NT), SMEM_WAVE, s, g);
-  return vqf_last_error();
+  return vqf_launch_dyn_lds<&gemm_f32_wave_kernel<TB, WK>>(vqf_gemm_kid(0, TB), dim3(nwg), dim3(NT), SMEM_WAVE, s, g);
 }
 
 }  // namespace
@@ -629,5 +615,7 @@ extern "C" int vqf_lstm_step_fwd(const float* h_prev, const float* w_hh, float* 
   g.c_prev = c_prev; g.c_out = c_out; g.h_out = h_out; g.H = H;
   vqf_prof_dims(B, 4 * H, H);
   vqf_stat_bump(VQF_STAT_GEMM_F32_WAVE);
-  return launch_lstm_fwd(g, g.tiles_m * g.tiles_n / 4, (hipStream_t)stream);
+  constexpr int SMEM_SHB = 6 * (4 * A_BYTES + B_BYTES);      // (the kernel's NSL = 6 slots)
+  return vqf_launch_dyn_lds<&gemm_f32_lstm_fwd_kernel>(KID_LSTM_CELL_FWD, dim3(g.tiles_m * g.tiles_n / 4), dim3(NT), SMEM_SHB,
+                                                       (hipStream_t)stream, g);
 }
