@@ -209,31 +209,21 @@ template <> __device__ __forceinline__ f32x4 load4<__bf16>(const __bf16* p) {
 // lens (vqf_glimpse_pool_fwd_len / _bwd_len; N int32, null: all S): the softmax of sample n runs over its first lens[n]
 // positions only (maximum, sum and weighted rows: a padded position enters none of them, so there is no inf - inf); the
 // weights beyond are exact zeros, and so are their dlogits and dfeat rows in the backward.
-__device__ __forceinline__ int pool_len(const int* __restrict__ lens, int n, int S) {
-  if (!lens) return S;
-  const int len = lens[n];
-  return len < 1 ? 1 : (len > S ? S : len);
-}
-
+// The count is vqf_region_count(lens, n, S).
 // idx (the grouped forms, vqf_glimpse_pool_*_grouped; N int32, null: u = n): sample n pools the feature rows of image
-// u = idx[n], clamped to [0, U - 1] here (feat is (U, S, C)); logits, wts, pooled and dlogits stay per sample.
-__device__ __forceinline__ int pool_src(const int* __restrict__ idx, int n, int U) {
-  if (!idx) return n;
-  const int u = idx[n];
-  return u < 0 ? 0 : (u >= U ? U - 1 : u);
-}
-
+// u = vqf_region_owner(idx, n, U) (feat is (U, S, C)); logits, wts, pooled and dlogits stay per sample.
+//
 // The packed forms (PACK; vqf_glimpse_pool_fwd_packed / _bwd_packed): feat is (Rtot, C), the real rows of every image one after
-// the other, and `lens` holds the row offsets roff (owners + 1) instead of counts.  The owner u = pool_src(idx, n, U) has
-// Sv = clamp(roff[u + 1] - roff[u], 1, min(S, Rtot - start)) rows from row start = clamp(roff[u], 0, Rtot - 1): whatever roff
-// holds, the rows read lie inside feat.  logits, wts and dlogits stay (N, S, .) padded; everything else is the lens form.
+// the other, and `lens` holds the row offsets roff (owners + 1) instead of counts.  The owner u has Sv rows from row start by
+// vqf_packed_span's rule: whatever roff holds, the rows read lie inside feat.  logits, wts and dlogits stay (N, S, .) padded;
+// everything else is the lens form.
 // (Without PACK the kernels keep their own address expressions: their code is what it was before the flag.)
 // LPK (with PACK, idx NULL; vqf_glimpse_pool_fwd_packed_rows / _bwd_packed_rows): logits and dlogits are (Rtot, G) packed rows as
 // well -- position s < Sv of sample n is row start + s, and there is no row behind the count to read or to zero.  wts and
 // dwts_extra stay (N, G, S).
 __device__ __forceinline__ void pool_span(const int* __restrict__ roff, const int* __restrict__ idx, int n, int U, int S, int Rtot,
                                           long long& row0, int& Sv) {
-  vqf_packed_span(roff, pool_src(idx, n, U), S, Rtot, row0, Sv);
+  vqf_packed_span(roff, vqf_region_owner(idx, n, U), S, Rtot, row0, Sv);
 }
 
 // grid (ceil(C/1024), N); thread = 4 consecutive channels
@@ -248,7 +238,7 @@ __global__ void glimpse_pool_fwd_kernel(const FT* __restrict__ feat,
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   long long row0 = 0;
   int Sv;                                             // (uniform) the sample's real positions
-  if (PACK) pool_span(lens, idx, n, U, S, Rtot, row0, Sv); else Sv = pool_len(lens, n, S);
+  if (PACK) pool_span(lens, idx, n, U, S, Rtot, row0, Sv); else Sv = vqf_region_count(lens, n, S);
   if (wave < G) {
     const int g = wave;
     const float* lg = LPK ? logits + row0 * G + g : logits + (long long)n * S * G + g;
@@ -273,7 +263,7 @@ __global__ void glimpse_pool_fwd_kernel(const FT* __restrict__ feat,
 
   const int c = (blockIdx.x * blockDim.x + tid) * 4;
   if (c >= C) return;
-  const FT* f = PACK ? feat + row0 * C + c : feat + (long long)pool_src(idx, n, U) * S * C + c;
+  const FT* f = PACK ? feat + row0 * C + c : feat + (long long)vqf_region_owner(idx, n, U) * S * C + c;
   const bool vec = ((C & 3) == 0) && aligned16_dev(feat) && aligned16_dev(pooled);
   f32x4 a[G];
 #pragma unroll
@@ -328,7 +318,7 @@ __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwave = blockDim.x >> 6;
   long long row0 = 0;
   int Sv;                                             // (uniform) positions Sv .. S - 1 are padding: weight 0, gradient 0
-  if (PACK) pool_span(lens, idx, n, U, S, Rtot, row0, Sv); else Sv = pool_len(lens, n, S);
+  if (PACK) pool_span(lens, idx, n, U, S, Rtot, row0, Sv); else Sv = vqf_region_count(lens, n, S);
   for (int i = tid; i < G * S; i += blockDim.x) ws[i / S][i % S] = wts[(long long)n * G * S + i];
   __syncthreads();
   const float* dp = dpooled + (long long)n * G * C;
@@ -346,7 +336,7 @@ __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
       for (int g = 0; g < G; ++g) pr[g][k] = c < C ? *reinterpret_cast<const f32x4*>(dp + g * C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
     for (int s = wave; s < Sv; s += nwave) {
-      const FT* f = PACK ? feat + (row0 + s) * C : feat + ((long long)pool_src(idx, n, U) * S + s) * C;
+      const FT* f = PACK ? feat + (row0 + s) * C : feat + ((long long)vqf_region_owner(idx, n, U) * S + s) * C;
       f32x4 x[KC];
 #pragma unroll
       for (int k = 0; k < KC; ++k) {
@@ -365,7 +355,7 @@ __global__ void glimpse_pool_bwd_kernel(const float* __restrict__ dpooled,
     }
   } else
   for (int s = wave; s < S; s += nwave) {
-    const FT* f = PACK ? feat + (row0 + s) * C : feat + ((long long)pool_src(idx, n, U) * S + s) * C;     // (s >= Sv: not read)
+    const FT* f = PACK ? feat + (row0 + s) * C : feat + ((long long)vqf_region_owner(idx, n, U) * S + s) * C;     // (s >= Sv: not read)
     // PACK (vqf_glimpse_pool_bwd_packed_dfeat, plain form): dfeat is (Rtot, C) like feat, row start + s; it has no padded rows
     float* df = dfeat ? (PACK ? dfeat + (row0 + s) * C : dfeat + ((long long)n * S + s) * C) : nullptr;
     if (s >= Sv) {                                     // (wave-uniform) a padded row: zero gradient, feat unread
@@ -543,7 +533,7 @@ __global__ void __launch_bounds__(1024) glimpse_pool_fwd_rows_kernel(const FT* _
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   long long row0 = 0;
   int Sv;
-  if (PACK) pool_span(lens, idx, n, U, S, Rtot, row0, Sv); else Sv = pool_len(lens, n, S);
+  if (PACK) pool_span(lens, idx, n, U, S, Rtot, row0, Sv); else Sv = vqf_region_count(lens, n, S);
   if (wave < G) {
     const int g = wave;
     const float* lg = LPK ? logits + row0 * G + g : logits + (long long)n * S * G + g;
@@ -566,7 +556,7 @@ __global__ void __launch_bounds__(1024) glimpse_pool_fwd_rows_kernel(const FT* _
     for (int i = tid; i < G * S; i += blockDim.x) wts[(long long)n * G * S + i] = w[i];
   const int CT = C >> 2, RS = blockDim.x / CT;
   const int c4 = tid % CT, rs = tid / CT;
-  const FT* f = PACK ? feat + row0 * C + 4 * c4 : feat + (long long)pool_src(idx, n, U) * S * C + 4 * c4;
+  const FT* f = PACK ? feat + row0 * C + 4 * c4 : feat + (long long)vqf_region_owner(idx, n, U) * S * C + 4 * c4;
   f32x4 a[G];
 #pragma unroll
   for (int g = 0; g < G; ++g) a[g] = f32x4{0, 0, 0, 0};
@@ -603,7 +593,7 @@ void glimpse_dispatch(int G, const VqfRegions& rg, F&& f) {
   vqf_dispatch_G(G, [&](auto g) { f(g, std::false_type(), std::false_type()); });
 }
 
-// rg: idx / U (sample n pools image idx[n]), lens (counts) or roff / Rtot (packed: feat (Rtot, C), see pool_span), rows (LPK)
+// rg: idx / U (sample n pools image idx[n]), lens (counts) or roff / Rtot (packed: feat (Rtot, C), see vqf_packed_span), rows (LPK)
 template <typename FT>
 int glimpse_fwd_launch(const FT* feat, const float* logits, int N, int S, int C, int G, int unit_softmax,
                        float* wts, float* pooled, void* stream, const VqfRegions& rg) {
@@ -687,7 +677,8 @@ __global__ void __launch_bounds__(256) glimpse_dfeat_grouped_kernel(const float*
   if (PACK) vqf_packed_span(roff, u, S, Rtot, row0, Sv);
   const int s0 = blockIdx.x * GP_ROWS, nr = min(GP_ROWS, Sv - s0);
   if (PACK && nr <= 0) return;
-  const int jb = min(max(grp_off[u], 0), N), je = min(max(grp_off[u + 1], jb), N);
+  int jb, je;
+  vqf_group_range(grp_off, u, N, jb, je);
   for (int c = threadIdx.x * 4; c < C; c += blockDim.x * 4) {
     f32x4 acc[GP_ROWS];
 #pragma unroll
@@ -697,7 +688,7 @@ __global__ void __launch_bounds__(256) glimpse_dfeat_grouped_kernel(const float*
       f32x4 p[GP_Q][G];
 #pragma unroll
       for (int q = 0; q < GP_Q; ++q) {                              // past the group's end: the last question again (not used)
-        nn[q] = min(max(order[min(j0 + q, je - 1)], 0), N - 1);
+        nn[q] = vqf_group_member(order, j0 + q, je, N);
 #pragma unroll
         for (int g = 0; g < G; ++g) p[q][g] = *reinterpret_cast<const f32x4*>(dpooled + ((long long)nn[q] * G + g) * C + c);
       }
@@ -725,7 +716,7 @@ __global__ void __launch_bounds__(256) glimpse_dfeat_grouped_kernel(const float*
 __global__ void __launch_bounds__(256) row_block_gather_kernel(const f32x4* __restrict__ src, const int* __restrict__ idx, int U,
                                                                long long blk4, f32x4* __restrict__ dst) {
   const int n = blockIdx.y;
-  const f32x4* s = src + (long long)pool_src(idx, n, U) * blk4;
+  const f32x4* s = src + (long long)vqf_region_owner(idx, n, U) * blk4;
   f32x4* d = dst + (long long)n * blk4;
   const long long step = (long long)gridDim.x * 256;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < blk4; i += step) d[i] = s[i];
@@ -736,7 +727,8 @@ __global__ void __launch_bounds__(256) row_block_group_sum_kernel(const f32x4* _
                                                                   const int* __restrict__ grp_off, int N, long long blk4,
                                                                   f32x4* __restrict__ out) {
   const int u = blockIdx.y;
-  const int jb = min(max(grp_off[u], 0), N), je = min(max(grp_off[u + 1], jb), N);
+  int jb, je;
+  vqf_group_range(grp_off, u, N, jb, je);
   const long long step = (long long)gridDim.x * 256;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < blk4; i += step) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -744,7 +736,7 @@ __global__ void __launch_bounds__(256) row_block_group_sum_kernel(const f32x4* _
       f32x4 x[GP_Q];
 #pragma unroll
       for (int q = 0; q < GP_Q; ++q)
-        x[q] = src[(long long)min(max(order[min(j0 + q, je - 1)], 0), N - 1) * blk4 + i];
+        x[q] = src[(long long)vqf_group_member(order, j0 + q, je, N) * blk4 + i];
 #pragma unroll
       for (int q = 0; q < GP_Q; ++q)
         if (j0 + q < je) acc += x[q];

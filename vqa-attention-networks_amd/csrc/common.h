@@ -241,15 +241,47 @@ template <typename T> __device__ __forceinline__ void vqf_st_stream(T* p, T v) {
 }
 
 __device__ __forceinline__ bool aligned16_dev(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// The memory-safety clamps of the region forms: whatever roff / idx / lens / grp_off / order hold, nothing leaves a tensor.  Every
+// kernel that reads one of these arrays goes through its helper.  The sizes S, U, N, Rtot are >= 1 (the launchers refuse anything
+// else).  __host__ __device__: tools/region_clamp_check.cpp walks the five exhaustively on the host.
 // The span of owner u in a packed (Rtot, .) tensor (include/vqa_fusion.h, "Packed region features"): roff holds owners + 1 row
 // offsets, row0 = clamp(roff[u], 0, Rtot - 1), Sv = clamp(roff[u + 1] - roff[u], 1, min(S, Rtot - row0)) -- whatever roff holds,
 // rows row0 .. row0 + Sv - 1 lie inside the tensor and Sv <= S.
-__device__ __forceinline__ void vqf_packed_span(const int* __restrict__ roff, int u, int S, int Rtot, long long& row0, int& Sv) {
+__host__ __device__ __forceinline__ void vqf_packed_span(const int* __restrict__ roff, int u, int S, int Rtot, long long& row0,
+                                                         int& Sv) {
   const long long a = roff[u], b = roff[u + 1];
   const int st = (int)min(max(a, 0LL), (long long)Rtot - 1);
   row0 = st;
   Sv = (int)min(max(b - a, 1LL), (long long)min(S, Rtot - st));
 }
+// The owner of question / sample n among U images: idx[n] clamped into 0 .. U - 1; idx null: n itself (the plain form, U == N).
+__host__ __device__ __forceinline__ int vqf_region_owner(const int* __restrict__ idx, int n, int U) {
+  if (!idx) return n;
+  const int u = idx[n];
+  return u < 0 ? 0 : (u >= U ? U - 1 : u);
+}
+// The real rows of sample n out of S: lens[n] clamped into 1 .. S (row 0 is always real, so no softmax is empty); lens null: S.
+__host__ __device__ __forceinline__ int vqf_region_count(const int* __restrict__ lens, int n, int S) {
+  if (!lens) return S;
+  const int len = lens[n];
+  return len < 1 ? 1 : (len > S ? S : len);
+}
+// Image u's questions among N are order[jb] .. order[je - 1]: 0 <= jb <= je <= N whatever grp_off (U + 1) holds.
+__host__ __device__ __forceinline__ void vqf_group_range(const int* grp_off, int u, int N, int& jb, int& je) {
+  jb = min(max(grp_off[u], 0), N);
+  je = min(max(grp_off[u + 1], jb), N);
+}
+// Member j of a non-empty group jb .. je - 1: a question in 0 .. N - 1, read at order[min(j, je - 1)] (an unrolled walk may ask
+// past the group's end: it gets the last member again, and discards it).
+__host__ __device__ __forceinline__ int vqf_group_member(const int* order, int j, int je, int N) {
+  return min(max(order[min(j, je - 1)], 0), N - 1);
+}
+
+// 1 / (1 + exp(-x)) with libm's expf: the LSTM gates (lstm.hip, lstm_cell.hip, the fused steps of gemm_f32_n80.hip and
+// gemm_f32_wave.hip -- forward and backward chain on these bits) and the tanh-sigmoid gate of elementwise.hip.
+__device__ __forceinline__ float vqf_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -287,6 +319,30 @@ __device__ __forceinline__ unsigned long long vqf_block256_max_u64(unsigned long
   __syncthreads();
   const unsigned long long a = sh[0] > sh[1] ? sh[0] : sh[1], b = sh[2] > sh[3] ? sh[2] : sh[3];
   return a > b ? a : b;
+}
+// The sum / maximum of a 256-thread workgroup (train.hip, eval.hip; T = float, double, long long): the xor butterfly of wave_sum
+// inside each wave, then the four wave results as sh[0] + sh[1] + sh[2] + sh[3] -- the bits of every loss, norm and total depend
+// on that order.  sh: 4 elements; result on all threads.
+template <typename T> __device__ __forceinline__ T vqf_block256_sum(T v, T* sh) {
+  if constexpr (std::is_same<T, float>::value) {
+    v = wave_sum(v);                   // (the same butterfly; spelled as the call, the float kernels of train.hip keep their bytes)
+  } else {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  }
+  const int w = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[w] = v;
+  __syncthreads();
+  return sh[0] + sh[1] + sh[2] + sh[3];
+}
+__device__ __forceinline__ float vqf_block256_max(float v, float* sh) {
+  v = wave_max(v);
+  const int w = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[w] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
 }
 
 // Split-K combined inside the GEMM launch (cdna_hip_programming.md, "In-launch split-K reduction"): every K-slice workgroup
@@ -413,8 +469,73 @@ __device__ __forceinline__ uint4 philox4x32_10(uint64_t ctr, uint64_t seed) {
   }
   return make_uint4(c0, c1, c2, c3);
 }
+// THE dropout draw: every forward / backward pair of the library agrees on it, wherever the two kernels live.  Element e of the
+// flat tensor takes word e & 3 of Philox call e >> 2 and is kept iff that word >= thr; a kept element is scaled by inv_keep, a
+// dropped one by 0.  An explicit uint8 keep-mask (parity tests) replaces the draw; thr == 0 without one: no dropout, scale 1.
+// (fusion.hip's keep_scale20 is the one other rule: 16-bit words, five calls per 20 elements.)
+// The scales of elements 4 i4 .. 4 i4 + 3 (keep: 4-byte aligned).
+__device__ __forceinline__ void vqf_keep4(const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep,
+                                          long long i4, f32x4& sc) {
+#ifdef VQF_HIE_DIAG_NOPHILOX                           // (diagnostic build: what the Philox draw costs the passes; wrong masks)
+  if (!keep && thr != 0u) { sc = f32x4{inv_keep, inv_keep, inv_keep, inv_keep}; return; }
+#endif
+  if (keep) {
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(keep + 4 * i4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sc[j] = ((w >> (8 * j)) & 0xFFu) ? inv_keep : 0.f;
+  } else if (thr != 0u) {
+    const uint4 r = philox4x32_10((uint64_t)i4, seed);
+    sc[0] = r.x >= thr ? inv_keep : 0.f;
+    sc[1] = r.y >= thr ? inv_keep : 0.f;
+    sc[2] = r.z >= thr ? inv_keep : 0.f;
+    sc[3] = r.w >= thr ? inv_keep : 0.f;
+  } else {
+    sc = f32x4{1.f, 1.f, 1.f, 1.f};
+  }
+}
+// The scale of element e alone.
+__device__ __forceinline__ float vqf_keep1(const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep,
+                                           long long e) {
+  if (keep) return keep[e] ? inv_keep : 0.f;
+  if (thr == 0u) return 1.0f;
+  const uint4 r = philox4x32_10((uint64_t)(e >> 2), seed);
+  const uint32_t w = (e & 3) == 0 ? r.x : (e & 3) == 1 ? r.y : (e & 3) == 2 ? r.z : r.w;
+  return w >= thr ? inv_keep : 0.f;
+}
+
+// The three modes of the tanh / dropout passes (elementwise.hip) on four elements, sc from vqf_keep4:
+//   MODE 0: y = x * sc                               (dropout forward; also its backward with x = dy)
+//   MODE 1: y = tanh(x) * sc                         (x: the caller's a [+ b])
+//   MODE 2: dx = x * sc * (1 - t^2), t = yy / sc     (backward of MODE 1: x = dy, yy = its output y)
+template <int MODE>
+__device__ __forceinline__ f32x4 vqf_tanh_drop(const f32x4 x, const f32x4 yy, const f32x4 sc, float inv_keep) {
+  f32x4 y;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (MODE == 0) {
+      y[j] = x[j] * sc[j];
+    } else if (MODE == 1) {
+      y[j] = vqf_tanh_fast(x[j]) * sc[j];
+    } else {
+      const float t = sc[j] > 0.f ? yy[j] * (1.0f / inv_keep) : 0.f;
+      y[j] = x[j] * sc[j] * (1.0f - t * t);
+    }
+  }
+  return y;
+}
+
 // keep iff uniform(0,1) >= p  <=>  u32 >= p * 2^32   (host side; passed to the kernels)
 static inline uint32_t drop_threshold_host(float p) {
   double t = (double)p * 4294967296.0;
   return t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
+}
+// The two scalars every dropout kernel takes.  thr == 0 says "no Philox draw": an explicit keep-mask, p == 0, or the dropout of
+// this launch switched off (`on` false: hie.hip's affinity pass without its epilogue).  inv_keep = 1 / (1 - p) with a mask or a
+// draw, else 1.
+struct VqfDrop { uint32_t thr; float inv_keep; };
+static inline VqfDrop vqf_drop(const uint8_t* keep, float p, bool on = true) {
+  VqfDrop d;
+  d.thr = (!on || keep || p == 0.f) ? 0u : drop_threshold_host(p);
+  d.inv_keep = (on && (keep || p > 0.f)) ? 1.0f / (1.0f - p) : 1.0f;
+  return d;
 }

@@ -9,51 +9,23 @@
 
 namespace {
 
-__device__ __forceinline__ void keep4(const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr,
-                                      float inv_keep, long long i4, float (&sc)[4]) {
-  if (keep) {
-    const uint32_t w = *reinterpret_cast<const uint32_t*>(keep + 4 * i4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sc[j] = ((w >> (8 * j)) & 0xFFu) ? inv_keep : 0.f;
-  } else if (thr != 0u) {
-    const uint4 r = philox4x32_10((uint64_t)i4, seed);
-    sc[0] = r.x >= thr ? inv_keep : 0.f;
-    sc[1] = r.y >= thr ? inv_keep : 0.f;
-    sc[2] = r.z >= thr ? inv_keep : 0.f;
-    sc[3] = r.w >= thr ? inv_keep : 0.f;
-  } else {
-    sc[0] = sc[1] = sc[2] = sc[3] = 1.0f;
-  }
-}
-
-// MODE 0: y = x * sc                      (dropout forward; also its backward with x = dy)
+// The modes of vqf_tanh_drop (common.h) over a flat tensor:
+// MODE 0: y = a * sc                      (dropout forward; also its backward with a = dy)
 // MODE 1: y = tanh(a + b) * sc            (b may be null)
-// MODE 2: dx = dy * sc * (1 - t^2), t = y / sc   (backward of MODE 1 given its output y)
+// MODE 2: dx = a * sc * (1 - t^2), t = b / sc    (backward of MODE 1: a = dy, b = its output y)
 template <int MODE>
 __global__ void ew_kernel(const float* __restrict__ a, const float* __restrict__ b,
                           const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr,
                           float inv_keep, long long n4, float* __restrict__ out) {
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float sc[4];
-    keep4(keep, seed, thr, inv_keep, i, sc);
+    f32x4 sc;
+    vqf_keep4(keep, seed, thr, inv_keep, i, sc);
     f32x4 x = *reinterpret_cast<const f32x4*>(a + 4 * i);
-    f32x4 y;
-    if (MODE == 0) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = x[j] * sc[j];
-    } else if (MODE == 1) {
-      if (b) x += *reinterpret_cast<const f32x4*>(b + 4 * i);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = vqf_tanh_fast(x[j]) * sc[j];
-    } else {
-      const f32x4 yy = *reinterpret_cast<const f32x4*>(b + 4 * i);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float t = sc[j] > 0.f ? yy[j] * (1.0f / inv_keep) : 0.f;
-        y[j] = x[j] * sc[j] * (1.0f - t * t);
-      }
-    }
+    f32x4 yy = {0.f, 0.f, 0.f, 0.f};
+    if (MODE == 1 && b) x += *reinterpret_cast<const f32x4*>(b + 4 * i);
+    if (MODE == 2) yy = *reinterpret_cast<const f32x4*>(b + 4 * i);
+    const f32x4 y = vqf_tanh_drop<MODE>(x, yy, sc, inv_keep);
     *reinterpret_cast<f32x4*>(out + 4 * i) = y;
   }
 }
@@ -69,25 +41,13 @@ __global__ void ew2d_kernel(const float* __restrict__ a, int lda, const float* _
   const unsigned stride = gridDim.x * blockDim.x;
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     const unsigned r = i / (unsigned)W4, c4 = i - r * (unsigned)W4;
-    float sc[4];
-    keep4(keep, seed, thr, inv_keep, (long long)i, sc);
+    f32x4 sc;
+    vqf_keep4(keep, seed, thr, inv_keep, (long long)i, sc);
     f32x4 x = *reinterpret_cast<const f32x4*>(a + (long long)r * lda + 4 * c4);
-    f32x4 y;
-    if (MODE == 0) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = x[j] * sc[j];
-    } else if (MODE == 1) {
-      if (b) x += *reinterpret_cast<const f32x4*>(b + (long long)r * ldb + 4 * c4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = vqf_tanh_fast(x[j]) * sc[j];
-    } else {
-      const f32x4 yy = *reinterpret_cast<const f32x4*>(b + (long long)r * ldb + 4 * c4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float t = sc[j] > 0.f ? yy[j] * (1.0f / inv_keep) : 0.f;
-        y[j] = x[j] * sc[j] * (1.0f - t * t);
-      }
-    }
+    f32x4 yy = {0.f, 0.f, 0.f, 0.f};
+    if (MODE == 1 && b) x += *reinterpret_cast<const f32x4*>(b + (long long)r * ldb + 4 * c4);
+    if (MODE == 2) yy = *reinterpret_cast<const f32x4*>(b + (long long)r * ldb + 4 * c4);
+    const f32x4 y = vqf_tanh_drop<MODE>(x, yy, sc, inv_keep);
     *reinterpret_cast<f32x4*>(out + (long long)r * ldo + 4 * c4) = y;
   }
 }
@@ -106,13 +66,12 @@ __global__ void dropout_bt_kernel(const float* __restrict__ x, long long sb_in, 
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     const unsigned r = i / (unsigned)H4, c4 = i - r * (unsigned)H4;
     const unsigned b = r / (unsigned)T, t = r - b * (unsigned)T;
-    float sc[4];
-    keep4(keep, seed, thr, inv_keep, (long long)i, sc);
+    f32x4 sc;
+    vqf_keep4(keep, seed, thr, inv_keep, (long long)i, sc);
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
     if (!lens || (int)t < lens[b]) {
       const f32x4 v = *reinterpret_cast<const f32x4*>(x + b * sb_in + t * st_in + 4 * c4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = v[j] * sc[j];
+      o = v * sc;
     }
     *reinterpret_cast<f32x4*>(y + b * sb_out + t * st_out + 4 * c4) = o;
   }
@@ -120,8 +79,8 @@ __global__ void dropout_bt_kernel(const float* __restrict__ x, long long sb_in, 
 
 // The change of layout between packed and padded rows, in the tanh / dropout pass that runs anyway (HieCoAttenLadder's
 // V = drop(tanh(img_emb(rows))) on a PackedRegions): z / dz hold the Rtot real rows of every owner, one owner after the other;
-// y / dy are the padded (U*L, E) tensors.  Owner u = blockIdx.y has (start, cnt) by packed_span's rule (csrc/fusion.hip), clamped
-// so that nothing roff holds makes the kernel leave a tensor; roff is read uniformly per workgroup.  The dropout index of element
+// y / dy are the padded (U*L, E) tensors.  Owner u = blockIdx.y has (start, cnt) by vqf_packed_span's rule (common.h): nothing
+// roff holds makes the kernel leave a tensor; roff is read uniformly per workgroup.  The dropout index of element
 // (l, c) is that of the padded tensor, (u*L + l)*E + c: the real rows carry the bits of ew_kernel<1> / <2> on the zero-padded copy.
 // BWD false: y[u*L + l] = tanh(z[start + l]) * sc for l < cnt, exact zero rows behind (nothing read there).
 // BWD true:  dz[start + l] = MODE 2 of ew_kernel on padded row u*L + l, l < cnt; no padded row of dy / y is read.
@@ -133,31 +92,22 @@ tanh_drop_repack_kernel(const float* __restrict__ a, const float* __restrict__ y
                         const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep, int Rtot, int L, int E4,
                         float* __restrict__ out) {
   const int u = blockIdx.y;
-  const long long o0 = roff[u], o1 = roff[u + 1];
-  const int start = (int)min(max(o0, 0LL), (long long)Rtot - 1);
-  const int cnt = (int)min(max(o1 - o0, 1LL), (long long)min(L, Rtot - start));
+  long long start;
+  int cnt;
+  vqf_packed_span(roff, u, L, Rtot, start, cnt);
   const unsigned n4 = (unsigned)((BWD || PACKED) ? cnt : L) * (unsigned)E4;
   const unsigned stride = gridDim.x * blockDim.x;
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     const unsigned l = i / (unsigned)E4, c4 = i - l * (unsigned)E4;
-    const long long pad4 = ((long long)u * L + l) * E4 + c4, pk4 = ((long long)start + l) * E4 + c4;
+    const long long pad4 = ((long long)u * L + l) * E4 + c4, pk4 = (start + l) * E4 + c4;
     f32x4 y = {0.f, 0.f, 0.f, 0.f};
     if (BWD || PACKED || (int)l < cnt) {
-      float sc[4];
-      keep4(keep, seed, thr, inv_keep, pad4, sc);
-      if (!BWD) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(a + 4 * pk4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) y[j] = vqf_tanh_fast(x[j]) * sc[j];
-      } else {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(a + 4 * (PACKED ? pk4 : pad4));
-        const f32x4 yy = *reinterpret_cast<const f32x4*>(yin + 4 * (PACKED ? pk4 : pad4));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float t = sc[j] > 0.f ? yy[j] * (1.0f / inv_keep) : 0.f;
-          y[j] = x[j] * sc[j] * (1.0f - t * t);
-        }
-      }
+      f32x4 sc;
+      vqf_keep4(keep, seed, thr, inv_keep, pad4, sc);
+      const f32x4 x = *reinterpret_cast<const f32x4*>(a + 4 * ((BWD && !PACKED) ? pad4 : pk4));
+      f32x4 yy = {0.f, 0.f, 0.f, 0.f};
+      if (BWD) yy = *reinterpret_cast<const f32x4*>(yin + 4 * (PACKED ? pk4 : pad4));
+      y = vqf_tanh_drop<BWD ? 2 : 1>(x, yy, sc, inv_keep);
     }
     *reinterpret_cast<f32x4*>(out + 4 * ((BWD || PACKED) ? pk4 : pad4)) = y;
   }
@@ -177,7 +127,7 @@ __global__ void gate_kernel(const float* __restrict__ a, const float* __restrict
     if (BWD) g = *reinterpret_cast<const f32x4*>(dy + 4 * i);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float t = tanhf(x[j]), sg = 1.0f / (1.0f + expf(-z[j]));
+      const float t = tanhf(x[j]), sg = vqf_sigmoid(z[j]);
       if (BWD) {
         r1[j] = g[j] * sg * (1.0f - t * t);
         r2[j] = g[j] * t * sg * (1.0f - sg);
@@ -262,13 +212,12 @@ int ew_args_ok(const void* a, const void* out, const uint8_t* keep, float p, lon
 template <int MODE>
 int ew_launch(int kid, const float* a, const float* b, const uint8_t* keep, uint64_t seed, float p,
               long long n, float* out, void* stream) {
-  const uint32_t thr = (keep || p == 0.f) ? 0u : drop_threshold_host(p);
-  const float inv_keep = (keep || p > 0.f) ? 1.0f / (1.0f - p) : 1.0f;
+  const VqfDrop d = vqf_drop(keep, p);
   const long long n4 = n / 4;
   long long blocks = (n4 + 255) / 256;
   if (blocks > 16384) blocks = 16384;
   VQF_LAUNCH(kid, ew_kernel<MODE>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, keep,
-             seed, thr, inv_keep, n4, out);
+             seed, d.thr, d.inv_keep, n4, out);
   return vqf_last_error();
 }
 
@@ -279,12 +228,11 @@ int ew2d_launch(int kid, const float* a, int lda, const float* b, int ldb, const
   if ((W % 4) || (lda % 4) || (ldo % 4) || (b && (ldb % 4)) || (long long)R * (W / 4) >= (1LL << 31)) return VQF_E_UNSUPPORTED;
   if (lda < W || ldo < W || (b && ldb < W)) return VQF_E_BADARG;
   if (!aligned16(a) || !aligned16(out) || (b && !aligned16(b)) || (keep && (((uintptr_t)keep) & 3))) return VQF_E_ALIGN;
-  const uint32_t thr = (keep || p == 0.f) ? 0u : drop_threshold_host(p);
-  const float inv_keep = (keep || p > 0.f) ? 1.0f / (1.0f - p) : 1.0f;
+  const VqfDrop d = vqf_drop(keep, p);
   long long blocks = ((long long)R * (W / 4) + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  VQF_LAUNCH(kid, ew2d_kernel<MODE>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, lda, b, ldb, keep, seed, thr,
-             inv_keep, R, W / 4, out, ldo);
+  VQF_LAUNCH(kid, ew2d_kernel<MODE>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, lda, b, ldb, keep, seed, d.thr,
+             d.inv_keep, R, W / 4, out, ldo);
   return vqf_last_error();
 }
 
@@ -295,13 +243,12 @@ int tanh_drop_repack_launch(const float* a, const float* yin, const int* roff, c
     return VQF_E_BADARG;
   if (!vqf_tanh_dropout_unpack_supported(U, R, L, E)) return VQF_E_UNSUPPORTED;
   if (!aligned16(a) || !aligned16(out) || (BWD && !aligned16(yin)) || (keep && (((uintptr_t)keep) & 3))) return VQF_E_ALIGN;
-  const uint32_t thr = (keep || p == 0.f) ? 0u : drop_threshold_host(p);
-  const float inv_keep = (keep || p > 0.f) ? 1.0f / (1.0f - p) : 1.0f;
+  const VqfDrop d = vqf_drop(keep, p);
   int chunks = (L * (E / 4) + 255) / 256;                  // L * E / 4 <= 2^24
   if (chunks > 64) chunks = 64;
   const int kid = PACKED ? (BWD ? KID_TANH_DROP_PACKED_BWD : KID_TANH_DROP_PACKED_FWD)
                          : (BWD ? KID_TANH_DROP_PACK_BWD : KID_TANH_DROP_UNPACK_FWD);
-  VQF_LAUNCH(kid, (tanh_drop_repack_kernel<BWD, PACKED>), dim3((unsigned)chunks, (unsigned)U), dim3(256), 0, (hipStream_t)stream, a, yin, roff, keep, seed, thr, inv_keep, R, L, E / 4, out);
+  VQF_LAUNCH(kid, (tanh_drop_repack_kernel<BWD, PACKED>), dim3((unsigned)chunks, (unsigned)U), dim3(256), 0, (hipStream_t)stream, a, yin, roff, keep, seed, d.thr, d.inv_keep, R, L, E / 4, out);
   return vqf_last_error();
 }
 
@@ -315,12 +262,11 @@ static int dropout_bt_launch(const float* x, long long sb_in, long long st_in, c
   if ((H % 4) || (sb_in % 4) || (st_in % 4) || (sb_out % 4) || (st_out % 4) || (long long)B * T * (H / 4) >= (1LL << 31))
     return VQF_E_UNSUPPORTED;
   if (!aligned16(x) || !aligned16(y) || (keep && (((uintptr_t)keep) & 3))) return VQF_E_ALIGN;
-  const uint32_t thr = (keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
-  const float inv_keep = (keep || p_drop > 0.f) ? 1.0f / (1.0f - p_drop) : 1.0f;
+  const VqfDrop d = vqf_drop(keep, p_drop);
   long long blocks = ((long long)B * T * (H / 4) + 255) / 256;
   if (blocks > 16384) blocks = 16384;
   VQF_LAUNCH(KID_DROPOUT, dropout_bt_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, sb_in, st_in, keep, seed,
-             thr, inv_keep, B, T, H / 4, y, sb_out, st_out, lens);
+             d.thr, d.inv_keep, B, T, H / 4, y, sb_out, st_out, lens);
   return vqf_last_error();
 }
 

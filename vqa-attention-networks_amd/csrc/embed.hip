@@ -32,16 +32,6 @@ __device__ __forceinline__ bool tok_real(const int* __restrict__ lens, int tok, 
   return tok - n * Tq < lens[n];
 }
 
-// keep scale of element e of the flat (T, E) tensor: the draw of the element-wise dropout kernels (elementwise.hip keep4: one Philox
-// call per 4 consecutive elements, or an explicit uint8 keep-mask)
-__device__ __forceinline__ float keep_scale(const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep, long long e) {
-  if (keep) return keep[e] ? inv_keep : 0.f;
-  if (thr == 0u) return 1.0f;
-  const uint4 r = philox4x32_10((uint64_t)(e >> 2), seed);
-  const uint32_t w = (e & 3) == 0 ? r.x : (e & 3) == 1 ? r.y : (e & 3) == 2 ? r.z : r.w;
-  return w >= thr ? inv_keep : 0.f;
-}
-
 // DROP: out = dropout(W[ids]) (hieCoAtten.py:27-28: the lookup and its always-on functional dropout in one pass)
 template <bool TANH, bool DROP = false>
 __global__ void embed_fwd_kernel(const float* __restrict__ W, const long long* __restrict__ ids, int T, int V, int E,
@@ -62,14 +52,14 @@ __global__ void embed_fwd_kernel(const float* __restrict__ W, const long long* _
       if (TANH) y = f32x4{tanhf(x[0]), tanhf(x[1]), tanhf(x[2]), tanhf(x[3])};
       if (DROP) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) y[j] *= keep_scale(keep, seed, thr, inv_keep, (long long)t * E + c + j);
+        for (int j = 0; j < 4; ++j) y[j] *= vqf_keep1(keep, seed, thr, inv_keep, (long long)t * E + c + j);
       }
       *reinterpret_cast<f32x4*>(o + c) = y;
     }
   } else {
     for (int c = lane; c < E; c += 64) {
       float y = ok ? (TANH ? tanhf(w[c]) : w[c]) : 0.f;
-      if (DROP) y *= keep_scale(keep, seed, thr, inv_keep, (long long)t * E + c);
+      if (DROP) y *= vqf_keep1(keep, seed, thr, inv_keep, (long long)t * E + c);
       o[c] = y;
     }
   }
@@ -134,7 +124,7 @@ __global__ void __launch_bounds__(256) embed_bwd_kernel(const float* __restrict_
                 const float y = out[row + c];
                 acc[r][k] += dout[row + c] * (1.0f - y * y);
               } else if (DROP) {
-                acc[r][k] += dout[row + c] * keep_scale(keep, seed, thr, inv_keep, row + c);
+                acc[r][k] += dout[row + c] * vqf_keep1(keep, seed, thr, inv_keep, row + c);
               } else {
                 acc[r][k] += dout[row + c];
               }
@@ -229,15 +219,14 @@ int vqf_embed_tanh_bwd_len(const float* dout, const float* out, const long long*
 
 // out = dropout(W[ids]) and its weight gradient dW[v] = sum_{t: ids[t] == v} dout[t] * keep / (1 - p): hieCoAtten.py:27-28 in one pass
 // each way.  The mask is the one vqf_dropout_f32 draws over the flat (T, E) tensor (same seed -> same bits as lookup + dropout).
-// Any E: the draw is per element (keep_scale); E % 4 != 0 takes the forward's element-by-element path.
+// Any E: the draw is per element (vqf_keep1); E % 4 != 0 takes the forward's element-by-element path.
 int vqf_embed_dropout_fwd(const float* W, const long long* ids, int T, int V, int E, const uint8_t* keep, uint64_t seed, float p_drop,
                           float* out, void* stream) {
   if (!W || !ids || !out || T <= 0 || V <= 0 || E <= 0 || p_drop < 0.f || p_drop >= 1.f) return VQF_E_BADARG;
-  const uint32_t thr = (keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
-  const float inv_keep = (keep || p_drop > 0.f) ? 1.0f / (1.0f - p_drop) : 1.0f;
+  const VqfDrop d = vqf_drop(keep, p_drop);
   vqf_prof_dims(T, V, E);
   VQF_LAUNCH(KID_EMBED_FWD, (embed_fwd_kernel<false, true>), dim3((T + 3) / 4), dim3(256), 0, (hipStream_t)stream, W, ids, T, V, E, out, 0,
-             keep, seed, thr, inv_keep);
+             keep, seed, d.thr, d.inv_keep);
   return vqf_last_error();
 }
 
@@ -245,13 +234,12 @@ int vqf_embed_dropout_bwd(const float* dout, const long long* ids, int T, int V,
                           float* dW, void* stream) {
   if (!dout || !ids || !dW || T <= 0 || V <= 0 || E <= 0 || p_drop < 0.f || p_drop >= 1.f) return VQF_E_BADARG;
   if (E > 1024) return VQF_E_UNSUPPORTED;
-  const uint32_t thr = (keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
-  const float inv_keep = (keep || p_drop > 0.f) ? 1.0f / (1.0f - p_drop) : 1.0f;
+  const VqfDrop d = vqf_drop(keep, p_drop);
   vqf_prof_dims(T, V, E);
   const float* none = nullptr;
   const int rv = embed_rows_per_wg(V);
   VQF_LAUNCH(KID_EMBED_BWD, (embed_bwd_kernel<false, true>), dim3((V + rv - 1) / rv), dim3(256), 0, (hipStream_t)stream, dout, none, ids, T,
-             V, E, rv, dW, 0, keep, seed, thr, inv_keep);
+             V, E, rv, dW, 0, keep, seed, d.thr, d.inv_keep);
   return vqf_last_error();
 }
 

@@ -14,17 +14,6 @@ namespace {
 
 constexpr int EV_THREADS = 256;
 
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* sh) {   // sh: >= 4 elements; result on all threads
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[w] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
 // this lane's share of the arg-max of x[0..A): 16-byte loads where the row starts on a 16-byte boundary (a maximum does not
 // depend on the order it is taken in)
 __device__ __forceinline__ unsigned long long row_argmax_key(const float* __restrict__ x, int A) {
@@ -88,8 +77,8 @@ __global__ __launch_bounds__(EV_THREADS) void match_finish_kernel(const int* __r
     ss += (double)rowscore[i];
     hits += hit[i];
   }
-  ss = block_sum(ss, shd);
-  hits = block_sum(hits, shl);
+  ss = vqf_block256_sum(ss, shd);
+  hits = vqf_block256_sum(hits, shl);
   if (threadIdx.x == 0) {
     const bool acc = tt.accumulate != 0;
     if (tt.counts) {
@@ -134,7 +123,7 @@ __global__ __launch_bounds__(EV_THREADS) void topk_rows_kernel(const float* __re
     mx = fmaxf(fmaxf(shf[0], shf[1]), fmaxf(shf[2], shf[3]));
     se = 0.f;
     for (int a = threadIdx.x; a < W; a += EV_THREADS) se += expf(row[a] - mx);
-    se = block_sum(se, shf);
+    se = vqf_block256_sum(se, shf);
   }
 
   unsigned long long bound = ~0ull;  // above every key

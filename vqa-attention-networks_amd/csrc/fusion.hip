@@ -150,15 +150,8 @@ __device__ __forceinline__ void own_store(__bf16* __restrict__ rowp, int W5, int
   }
 }
 
-// The packed forms (PACK): roff (owners + 1) int32 are row offsets into a (Rtot, .) tensor.  Owner s has cnt rows from row start:
-// start = clamp(roff[s], 0, Rtot - 1), cnt = clamp(roff[s + 1] - roff[s], 1, min(L, Rtot - start)) -- whatever roff holds, rows
-// start .. start + cnt - 1 lie inside the tensor and cnt <= L.  Uniform over the block.
-__device__ __forceinline__ void packed_span(const int* __restrict__ roff, int s, int L, int Rtot, long long& start, int& cnt) {
-  const long long a = roff[s], b = roff[s + 1];
-  const int st = (int)min(max(a, 0LL), (long long)Rtot - 1);
-  start = st;
-  cnt = (int)min(max(b - a, 1LL), (long long)min(L, Rtot - st));
-}
+// The packed forms (PACK): roff (owners + 1) int32 are row offsets into a (Rtot, .) tensor; owner s has cnt rows from row start by
+// vqf_packed_span's rule (common.h), uniform over the block.
 
 // scale[i] = keep ? 1/(1-p) : 0 for the 20 elements starting at flat index e0 (e0 % 4 == 0)
 __device__ __forceinline__ void keep_scale20(const uint8_t* __restrict__ keep, uint64_t seed,
@@ -217,7 +210,7 @@ __device__ __forceinline__ void keep_scale20(const uint8_t* __restrict__ keep, u
 // Lv <= l < L reads nothing and stores a zero R row and zero rowssq partials.  With lens[n] = L it gives the plain kernel's bits.
 // PACK (vqf_mfb_fuse_fwd_packed / _grouped_packed; with LEN): P is (Rtot, 5O), the real rows of every image one after the other, and
 // `lens` holds the row offsets roff (owners + 1) instead of counts: the owner s (sample n, or image idx[n]) has its rows at
-// packed_span(roff, s) -- row l < Lv of the sample is P row start + l.  R, rowssq, keep / the Philox index stay in the padded
+// vqf_packed_span(roff, s) -- row l < Lv of the sample is P row start + l.  R, rowssq, keep / the Philox index stay in the padded
 // coordinates n L + l, so everything else is the LEN form.
 // PROWS (vqf_mfb_fuse_fwd_packed_rows; with PACK, un-grouped): R is (Rtot, O) and rowssq (4 Rtot) as well -- row l < Lv of the sample
 // stores R row start + l and its four partials there, and there is no padded row to zero.  keep / the Philox index stay at n L + l.
@@ -244,10 +237,11 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int nt = O / TPT;                       // active threads (250 at O = 1000); O / TPT <= 256
   const bool act = tid < nt;
+  // (vqf_region_owner's / vqf_region_count's rules, common.h, restated: GRP / LEN say that the array is given, so no null test)
   const int own = GRP ? min(max(idx[n], 0), U - 1) : n;
   long long prow0 = (long long)own * L;                                               // first projection row of the sample
   int Lw = (LEN && !PACK) ? min(max(lens[n], 1), L) : L;                              // rows the block walks (LEN: the real regions)
-  if (PACK) packed_span(lens, own, L, Rtot, prow0, Lw);
+  if (PACK) vqf_packed_span(lens, own, L, Rtot, prow0, Lw);
   float qq[CPT], pb[CPT], p[CPT], pn[CPT];
   Raw<PT> rn;                                   // COAL: the next row's span of this wave, lane-linear pieces
 #pragma unroll
@@ -365,10 +359,11 @@ mfb_fuse_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dzdr
   const int W5 = KP * O;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const float ca = coefA[n], cb = coefB[n], hi = 0.5f * inv[n];
+  // (vqf_region_owner's / vqf_region_count's rules, common.h, restated: GRP / LEN say that the array is given, so no null test)
   const int own = GRP ? min(max(idx[n], 0), U - 1) : n;
   long long prow0 = (long long)own * L;                                               // first projection row of the sample
   int Lw = (LEN && !PACK) ? min(max(lens[n], 1), L) : L;                              // rows the block walks (LEN: the real regions)
-  if (PACK) packed_span(lens, own, L, Rtot, prow0, Lw);
+  if (PACK) vqf_packed_span(lens, own, L, Rtot, prow0, Lw);
   // COAL (O / 4 <= 256: one pass): every lane of a wave takes part in the coalesced P loads / dP stores, threads past
   // O / 4 only skip the arithmetic
   for (int t = threadIdx.x; COAL ? t < 256 : t < O / TPT; t += 256) {
@@ -469,13 +464,15 @@ mfb_fuse_bwd_image_kernel(const float* __restrict__ dY, const float* __restrict_
                           const int* __restrict__ lens, int Rtot) {
   __shared__ __attribute__((aligned(16))) char tl[4 * WLDS];
   const int u = blockIdx.x, ls = blockIdx.y;
+  // (vqf_region_count's rule, common.h, restated: LEN says that lens is given, so no null test)
   int Lw = (LEN && !PACK) ? min(max(lens[u], 1), L) : L;                              // rows that take gradient (LEN: the real regions)
   long long drow0 = (long long)u * L;                                                 // first dP row of the image
-  if (PACK) packed_span(lens, u, L, Rtot, drow0, Lw);
+  if (PACK) vqf_packed_span(lens, u, L, Rtot, drow0, Lw);
   const int W5 = KP * O;
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
   const bool act = t < O / TPT;
-  const int jb = min(max(grp_off[u], 0), N), je = min(max(grp_off[u + 1], jb), N);
+  int jb, je;
+  vqf_group_range(grp_off, u, N, jb, je);
   float db[CPT];
 #pragma unroll
   for (int i = 0; i < CPT; ++i) db[i] = 0.f;
@@ -487,7 +484,7 @@ mfb_fuse_bwd_image_kernel(const float* __restrict__ dY, const float* __restrict_
       for (int i = 0; i < CPT; ++i) dp[r][i] = 0.f;
     if (act && (!LEN || l0 < Lw)) {
       for (int j = jb; j < je; ++j) {
-        const int n = min(max(order[j], 0), N - 1);
+        const int n = vqf_group_member(order, j, je, N);
         const float ca = coefA[n], cb = coefB[n], hi = 0.5f * inv[n];
         float qq[CPT];
         load20(q + (long long)n * W5 + CPT * t, qq);
@@ -673,12 +670,11 @@ static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, c
   }
   // ws: the dq partials [N * LS][5O], the bias partials ([N * LS] rows, grouped [U * LSI]), the reducer's VQF_REDUCE_SPLITS rows
   float* db_part = ws ? (float*)ws + (size_t)N * LS * W5 : nullptr;
-  const uint32_t thr = (keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
-  const float inv_keep = (keep || p_drop > 0.f) ? 1.0f / (1.0f - p_drop) : 1.0f;
+  const VqfDrop d = vqf_drop(keep, p_drop);
   hipStream_t s = (hipStream_t)stream;
   // coalesced P / dP access through the LDS transpose: one pass of 256 threads over the row, whole 16-byte pieces
   const bool coal = fuse_coalesced(true) && O / TPT <= 256 && (W5 % ((p_bf16 || dp_bf16) ? 8 : 4) == 0);
-  const FuseBwd a = {dY, dzdrop, Y, inv, coefA, coefB, P, pbias, q, cascade, keep, seed, thr, inv_keep, N, L, O, LS, dP,
+  const FuseBwd a = {dY, dzdrop, Y, inv, coefA, coefB, P, pbias, q, cascade, keep, seed, d.thr, d.inv_keep, N, L, O, LS, dP,
                      direct ? dq : (float*)ws, dcascade, db_part, s};
   fuse_bwd_layout(p_bf16, dp_bf16, dbiasP != nullptr, coal, a, rg);
   int rc = vqf_last_error();
@@ -712,11 +708,10 @@ static int fuse_fwd_impl(const void* P, int p_bf16, const float* pbias, const fl
       (cascade && !aligned16(cascade)) ||
       (zdrop && !aligned16(zdrop)) || (keep && (((uintptr_t)keep) & 3)))
     return VQF_E_ALIGN;
-  const uint32_t thr = (keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
-  const float inv_keep = (keep || p_drop > 0.f) ? 1.0f / (1.0f - p_drop) : 1.0f;
+  const VqfDrop d = vqf_drop(keep, p_drop);
   const bool coal = fuse_coalesced(true) && ((KP * O) % (p_bf16 ? 8 : 4) == 0);
   const bool nopf = coal && g_vqf_opt[VQF_OPT_FUSE_COAL] != 1;   // default: no register prefetch (126 VGPRs, 4 blocks per CU)
-  const FuseFwd a = {P, pbias, q, cascade, keep, seed, thr, inv_keep, N, L, O, pick_ls_fwd(N, L), R, rowssq, zdrop,
+  const FuseFwd a = {P, pbias, q, cascade, keep, seed, d.thr, d.inv_keep, N, L, O, pick_ls_fwd(N, L), R, rowssq, zdrop,
                      (unsigned short*)R_bf16, ldrb, (hipStream_t)stream};
   if (p_bf16) fuse_fwd_coal<__bf16>(coal, nopf, a, rg); else fuse_fwd_coal<float>(coal, nopf, a, rg);
   return vqf_last_error();

@@ -38,7 +38,6 @@ struct N80Args {
   const float* c_prev; float* c_out; float* h_out; int H;      // CELL (the fused LSTM step)
 };
 
-__device__ __forceinline__ float sigm_f(float x) { return 1.0f / (1.0f + expf(-x)); }     // lstm_cell.hip's sigm
 
 // chunk XOR of LDS row rho.  ds_read_b128 serves a wave in four NON-contiguous groups of 16 lanes ({0-3, 12-15, 20-27}, {4-11,
 // 16-19, 28-31} and the same + 32: MI355X_MICROARCH.md, LDS table), i.e. with lane = (c, kq) a group holds all 16 rows c, rows
@@ -202,10 +201,10 @@ __global__ void __launch_bounds__(NT, 1) gemm_f32_n80_kernel(const N80Args g) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const long long row = m0 + 16 * wave + 4 * kq + j;
-      const float ig = sigm_f(acc[0][j] + oldg[0][j]);
-      const float fg = sigm_f(acc[1][j] + oldg[1][j]);
+      const float ig = vqf_sigmoid(acc[0][j] + oldg[0][j]);
+      const float fg = vqf_sigmoid(acc[1][j] + oldg[1][j]);
       const float gg = tanhf(acc[2 % NTC][j] + oldg[2][j]);
-      const float og = sigm_f(acc[3 % NTC][j] + oldg[3][j]);
+      const float og = vqf_sigmoid(acc[3 % NTC][j] + oldg[3][j]);
       float* pg = g.C + row * g.ldc + u;
       pg[0] = ig; pg[g.H] = fg; pg[2 * g.H] = gg; pg[3 * g.H] = og;
       const float cn = fg * cpv[j] + ig * gg;

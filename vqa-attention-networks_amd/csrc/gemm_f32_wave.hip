@@ -428,7 +428,6 @@ int launch_shb(const WaveArgs& g, int nwg, hipStream_t s) {
 // same unit and swap (f, o) for (i, g) with one cross-lane move each, lanes cm < 16 update c and h.  The old gate values, and
 // c_{t-1}, are fetched at kernel entry like the accumulating product's C.  Per element the same arithmetic in the same order as
 // vqf_gemm_f32(ACCUM) + vqf_lstm_cell_fwd: bit-identical, 14 launches and a 16 MB round trip per step fewer.
-__device__ __forceinline__ float sigm_f(float x) { return 1.0f / (1.0f + expf(-x)); }     // lstm_cell.hip's sigm
 
 __global__ void __launch_bounds__(NT, 1) gemm_f32_lstm_fwd_kernel(const WaveArgs g) {
   constexpr int NSL = 6;
@@ -531,9 +530,9 @@ __global__ void __launch_bounds__(NT, 1) gemm_f32_lstm_fwd_kernel(const WaveArgs
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const int row = m0 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-    const float a0 = sigm_f(acc[0][e] + old0[e]);                         // i | f
+    const float a0 = vqf_sigmoid(acc[0][e] + old0[e]);                    // i | f
     const float p1 = acc[1][e] + old1[e];
-    const float a1 = lo ? tanhf(p1) : sigm_f(p1);                         // g | o
+    const float a1 = lo ? tanhf(p1) : vqf_sigmoid(p1);                    // g | o
     float* pc = g.C + (long long)row * g.ldc + col0;
     pc[0] = a0;
     pc[2 * H] = a1;

@@ -46,26 +46,6 @@ struct HieArgs {
   const int* rlens;                                  // REG only: (N) region counts, rows l >= rlens[n] of a sample are padding
 };
 
-__device__ __forceinline__ void keep4v(const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep,
-                                       long long i4, f32x4& sc) {
-#ifdef VQF_HIE_DIAG_NOPHILOX                           // (diagnostic build: what the Philox draw costs the passes; wrong masks)
-  if (!keep && thr != 0u) { sc = f32x4{inv_keep, inv_keep, inv_keep, inv_keep}; return; }
-#endif
-  if (keep) {
-    const uint32_t w = *reinterpret_cast<const uint32_t*>(keep + 4 * i4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sc[j] = ((w >> (8 * j)) & 0xFFu) ? inv_keep : 0.f;
-  } else if (thr != 0u) {
-    const uint4 r = philox4x32_10((uint64_t)i4, seed);       // the draw of the flat element-wise kernels (elementwise.hip)
-    sc[0] = r.x >= thr ? inv_keep : 0.f;
-    sc[1] = r.y >= thr ? inv_keep : 0.f;
-    sc[2] = r.z >= thr ? inv_keep : 0.f;
-    sc[3] = r.w >= thr ? inv_keep : 0.f;
-  } else {
-    sc = f32x4{1.f, 1.f, 1.f, 1.f};
-  }
-}
-
 // TMAX: compile-time bound of T (8, 14 or 16: the T-row accumulators are 4 TMAX registers; at 16 the HEAD mode spilled under the
 // 128-register budget of a 1024-thread workgroup)
 // REG (vqf_hie_hv_fwd_regions / _rank_add_regions / _rank_left_regions): the workgroup walks the rows l0 .. min(l1, rlens[n]) of its
@@ -155,7 +135,7 @@ __global__ void __launch_bounds__(HT) hie_stream_kernel(const HieArgs g) {
       for (int q = 0; q < NR; ++q) {
         const float d = dd[q];
         f32x4 sc;
-        keep4v(g.keep, g.seed, g.thr, g.inv_keep, m[q] * CT + c4, sc);
+        vqf_keep4(g.keep, g.seed, g.thr, g.inv_keep, m[q] * CT + c4, sc);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float t = sc[j] > 0.f ? x[q][j] * keep_q : 0.f;       // tanh value back from the stored tanh * keep / (1 - p)
@@ -191,7 +171,7 @@ __global__ void __launch_bounds__(HT) hie_stream_kernel(const HieArgs g) {
 #pragma unroll
         for (int q = 0; q < NR; ++q) {
           f32x4 sc;
-          keep4v(g.keep, g.seed, g.thr, g.inv_keep, m[q] * CT + c4, sc);
+          vqf_keep4(g.keep, g.seed, g.thr, g.inv_keep, m[q] * CT + c4, sc);
 #pragma unroll
 #ifdef VQF_HIE_DIAG_NOTANH
           for (int j = 0; j < 4; ++j) o[q][j] = o[q][j] * sc[j];
@@ -321,15 +301,6 @@ struct AffArgs {
   const int* rlens;                                                     // REG only: (N) column counts, l >= rlens[n] is padding
 };
 
-__device__ __forceinline__ float keep1(const uint8_t* __restrict__ keep, uint64_t seed, uint32_t thr, float inv_keep, long long idx) {
-  if (keep) return keep[idx] ? inv_keep : 0.f;
-  if (thr == 0u) return 1.0f;
-  const uint4 r = philox4x32_10((uint64_t)(idx >> 2), seed);
-  const int j = (int)(idx & 3);
-  const uint32_t v = j == 0 ? r.x : j == 1 ? r.y : j == 2 ? r.z : r.w;
-  return v >= thr ? inv_keep : 0.f;
-}
-
 // LDS holds the G x npair (16, E) X images; a wave owns 16 y rows and G accumulators
 template <int EPI, int G, bool DROP, bool REG = false>
 __global__ void __launch_bounds__(1024) hie_affinity_kernel(const AffArgs g) {
@@ -403,7 +374,7 @@ __global__ void __launch_bounds__(1024) hie_affinity_kernel(const AffArgs g) {
               g.out[idx] = 0.f;
               continue;
             }
-            const float sc = DROP && EPI ? keep1(g.keep, g.seed, g.thr, g.inv_keep, idx) : 1.0f;
+            const float sc = DROP && EPI ? vqf_keep1(g.keep, g.seed, g.thr, g.inv_keep, idx) : 1.0f;
             float v = acc[lv][j];
             if (EPI == 1) {
               v = vqf_tanh_fast(v) * sc;
@@ -482,8 +453,8 @@ int launch(int mode, HieArgs& g, const uint8_t* keep, uint64_t seed, float p, hi
   if (g.S > 1 && (g.padd || (g.part && g.ldp != g.E))) return VQF_E_BADARG;     // several chunks: contiguous slabs, summed by vqf_hie_slab_sum
   const int nt = threads_for(g.E, g.Lc);
   g.keep = keep; g.seed = seed;
-  g.thr = (keep || p == 0.f) ? 0u : drop_threshold_host(p);
-  g.inv_keep = (keep || p > 0.f) ? 1.0f / (1.0f - p) : 1.0f;
+  const VqfDrop d = vqf_drop(keep, p);
+  g.thr = d.thr; g.inv_keep = d.inv_keep;
   return g.rlens ? stream_mode<true>(mode, nt, lds, s, g) : stream_mode<false>(mode, nt, lds, s, g);
 }
 
@@ -693,8 +664,8 @@ static AffArgs aff_args(const float* x1, int ldx1, int lvx1, const float* y1, in
 // vqf_hie_affinity*: one level with the dropout epilogue (epi = 0 has none); `g` holds the operands and g.lens / g.rlens
 static int affinity_drop_launch(AffArgs& g, int epi, const uint8_t* keep, uint64_t seed, float p_drop, void* stream) {
   g.keep = epi ? keep : nullptr; g.seed = seed;
-  g.thr = (!epi || keep || p_drop == 0.f) ? 0u : drop_threshold_host(p_drop);
-  g.inv_keep = (epi && (keep || p_drop > 0.f)) ? 1.0f / (1.0f - p_drop) : 1.0f;
+  const VqfDrop d = vqf_drop(keep, p_drop, epi != 0);
+  g.thr = d.thr; g.inv_keep = d.inv_keep;
   return affinity_launch(KID_HIE_AFF, g, 1, epi, true, (hipStream_t)stream);
 }
 

@@ -26,12 +26,6 @@ namespace {
 constexpr int PH_TMAX = 32;
 
 // one thread per (row, 4 columns); rows r = n * T + t
-__device__ __forceinline__ int row_len(const int* __restrict__ lens, int n, int T) {
-  if (!lens) return T;
-  const int len = lens[n];
-  return len < 1 ? 1 : (len > T ? T : len);
-}
-
 __global__ void phrase_ngram_fwd_kernel(const float* __restrict__ Z, int ldz, const float* __restrict__ bias, int NT, int T,
                                         int E, float* __restrict__ Qp, int ldq, uint8_t* __restrict__ idx,
                                         const int* __restrict__ lens) {
@@ -39,7 +33,7 @@ __global__ void phrase_ngram_fwd_kernel(const float* __restrict__ Z, int ldz, co
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)NT * CT) return;
   const int r = (int)(i / CT), c = 4 * (int)(i - (long long)r * CT);
-  const int t = r % T, len = row_len(lens, r / T, T);
+  const int t = r % T, len = vqf_region_count(lens, r / T, T);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   if (t >= len) {                                   // a padded row: zero, no winner
     *reinterpret_cast<f32x4*>(Qp + (long long)r * ldq + c) = zero;
@@ -84,7 +78,7 @@ __global__ void phrase_ngram_bwd_kernel(const float* __restrict__ dQp, int ldd, 
   if (i >= (long long)NT * CT) return;
   const int r = (int)(i / CT), c = 4 * (int)(i - (long long)r * CT);
   const int t = r % T;
-  const bool real = t < row_len(lens, r / T, T);  // a padded row of Z entered no window: its dZ is zero
+  const bool real = t < vqf_region_count(lens, r / T, T);  // a padded row of Z entered no window: its dZ is zero
   f32x4 du[3];
   uint32_t win[3];
 #pragma unroll
@@ -125,7 +119,7 @@ __global__ void tanh_bwd_rows_len_kernel(const float* __restrict__ dy, const flo
     for (int j = 0; j < 4; ++j) {
       const long long row = (4 * i + j) / L;
       const int n = (int)(row / T), t = (int)(row - (long long)n * T);
-      o[j] = t < row_len(lens, n, T) ? d[j] * (1.0f - v[j] * v[j]) : 0.f;
+      o[j] = t < vqf_region_count(lens, n, T) ? d[j] * (1.0f - v[j] * v[j]) : 0.f;
     }
     *reinterpret_cast<f32x4*>(dx + 4 * i) = o;
   }

@@ -38,6 +38,8 @@ __global__ void __launch_bounds__(256) guided_logits_fwd_kernel(const float* __r
                                                                 const int* __restrict__ roff, int Rtot) {
   extern __shared__ __attribute__((aligned(16))) float gl_lds[];
   const int GE = G * E, n = blockIdx.y;
+  // (vqf_region_owner's rule, common.h, restated: through the helper the scalar prologue of all six instantiations came out in another
+  // order -- same registers -- and no bench reaches G = 2)
   const int u = idx ? min(max(idx[n], 0), U - 1) : n;               // (uniform) the sample whose Xh rows this question reads
   long long row0 = 0;
   int Sv = S;                                                       // (uniform) the owner's real rows
@@ -177,7 +179,8 @@ __global__ void __launch_bounds__(768) guided_logits_bwd_grouped_kernel(const fl
   const int lv = (G > 1 && c >= E) + (G > 2 && c >= 2 * E);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   const f32x4 wv = *reinterpret_cast<const f32x4*>(w + c);
-  const int jb = min(max(grp_off[u], 0), N), je = min(max(grp_off[u + 1], jb), N);
+  int jb, je;
+  vqf_group_range(grp_off, u, N, jb, je);
   const long long r0 = PACK ? row0 : (long long)u * S;              // the first of the image's rows in Xh / dXh
   f32x4 sw = zero;
   if (jb == je)
@@ -188,7 +191,7 @@ __global__ void __launch_bounds__(768) guided_logits_bwd_grouped_kernel(const fl
     f32x4 gv[GL_GRP_Q], sg[GL_GRP_Q];
 #pragma unroll
     for (int q = 0; q < GL_GRP_Q; ++q) {                            // past the group's end: the last question again (not used)
-      nn[q] = min(max(order[min(j0 + q, je - 1)], 0), N - 1);
+      nn[q] = vqf_group_member(order, j0 + q, je, N);
       gv[q] = *reinterpret_cast<const f32x4*>(gp + (long long)nn[q] * GE + c);
       sg[q] = zero;
     }

@@ -43,8 +43,6 @@ constexpr int UPB = 4;           // hidden units per workgroup = 16 gate columns
 constexpr int FWD_WAVES = 4;     // forward: K = H split over 4 waves
 constexpr int BWD_WAVES = 8;     // backward: K = 4H split over 8 waves
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // ---- one-time packing of W_hh into the two fragment-major images ---------------------------------
 __global__ void pack_w_fwd_kernel(const float* __restrict__ w_hh, int H, float* __restrict__ wf) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;    // float4 index
@@ -133,10 +131,10 @@ lstm_step_fwd_kernel(const float* __restrict__ xw_s, const float* __restrict__ w
 #pragma unroll
         for (int k = 0; k < 4; ++k) pre[k] += part[w][ob >> 4][ob & 15][4 * k + ou];
     }
-    const float gi = sigmoidf_(pre[0] + xq[0]);
-    const float gf = sigmoidf_(pre[1] + xq[1]);
+    const float gi = vqf_sigmoid(pre[0] + xq[0]);
+    const float gf = vqf_sigmoid(pre[1] + xq[1]);
     const float gg = tanhf(pre[2] + xq[2]);
-    const float go = sigmoidf_(pre[3] + xq[3]);
+    const float go = vqf_sigmoid(pre[3] + xq[3]);
     const float c = gf * cpq + gi * gg;
     const float h = go * tanhf(c);
     h_out[(long long)ob * H + ocol] = h;
@@ -319,10 +317,10 @@ lstm_step_fwd_bf16_kernel(const float* __restrict__ xw_s, const __bf16* __restri
 #pragma unroll
         for (int k = 0; k < 4; ++k) pre[k] += part[w][ob >> 4][ob & 15][4 * k + ou];
     }
-    const float gi = sigmoidf_(pre[0] + xq[0]);
-    const float gf = sigmoidf_(pre[1] + xq[1]);
+    const float gi = vqf_sigmoid(pre[0] + xq[0]);
+    const float gf = vqf_sigmoid(pre[1] + xq[1]);
     const float gg = tanhf(pre[2] + xq[2]);
-    const float go = sigmoidf_(pre[3] + xq[3]);
+    const float go = vqf_sigmoid(pre[3] + xq[3]);
     const float c = gf * cpq + gi * gg;
     const float h = go * tanhf(c);
     h_out[(long long)ob * H + ocol] = h;

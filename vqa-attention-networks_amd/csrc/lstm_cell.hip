@@ -8,8 +8,6 @@
 
 namespace {
 
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // gates (B,4H): pre-activations in, ACTIVATED gates out (kept for the backward)
 __global__ void __launch_bounds__(256) lstm_cell_fwd_kernel(float* __restrict__ gates, const float* __restrict__ c_prev,
                                                             int B, int H, float* __restrict__ c_out,
@@ -26,7 +24,7 @@ __global__ void __launch_bounds__(256) lstm_cell_fwd_kernel(float* __restrict__ 
   f32x4 c, h;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    gi[e] = sigm(gi[e]); gf[e] = sigm(gf[e]); gg[e] = tanhf(gg[e]); go[e] = sigm(go[e]);
+    gi[e] = vqf_sigmoid(gi[e]); gf[e] = vqf_sigmoid(gf[e]); gg[e] = tanhf(gg[e]); go[e] = vqf_sigmoid(go[e]);
     c[e] = gf[e] * cp[e] + gi[e] * gg[e];
     h[e] = go[e] * tanhf(c[e]);
   }

@@ -105,23 +105,22 @@ region_rows_widen_kernel(const void* __restrict__ src, long long n4, float* __re
     vqf_st_stream(reinterpret_cast<f32x4*>(dst) + i, stage_load4<F16>(src, i));
 }
 
-// padded output: dst (U*L, D); image u = blockIdx.y has (start, cnt) by packed_span's rule (csrc/fusion.hip), read once per
-// workgroup and clamped so that nothing roff holds makes the kernel leave a tensor: start in [0, Rtot - 1], start + cnt <= Rtot,
-// cnt <= L.  Row u*L + l is source row start + l for l < cnt and an exact +0.0 row behind it (nothing read there).
+// padded output: dst (U*L, D); image u = blockIdx.y has (start, cnt) by vqf_packed_span's rule (common.h), read once per
+// workgroup.  Row u*L + l is source row start + l for l < cnt and an exact +0.0 row behind it (nothing read there).
 template <bool F16>
 __global__ void __launch_bounds__(256)
 region_rows_pad_kernel(const void* __restrict__ src, const int* __restrict__ roff, int Rtot, int L, int D4,
                        float* __restrict__ dst) {
   const int u = blockIdx.y;
-  const long long o0 = roff[u], o1 = roff[u + 1];
-  const int start = (int)min(max(o0, 0LL), (long long)Rtot - 1);
-  const int cnt = (int)min(max(o1 - o0, 1LL), (long long)min(L, Rtot - start));
+  long long start;
+  int cnt;
+  vqf_packed_span(roff, u, L, Rtot, start, cnt);
   const unsigned n4 = (unsigned)L * (unsigned)D4;            // <= 2^24
   const unsigned stride = gridDim.x * blockDim.x;
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     const unsigned l = i / (unsigned)D4, c4 = i - l * (unsigned)D4;
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if ((int)l < cnt) v = stage_load4<F16>(src, ((long long)start + l) * D4 + c4);
+    if ((int)l < cnt) v = stage_load4<F16>(src, (start + l) * D4 + c4);
     vqf_st_stream(reinterpret_cast<f32x4*>(dst) + ((long long)u * L + l) * D4 + c4, v);
   }
 }

@@ -22,43 +22,6 @@ namespace {
 
 constexpr int TR_THREADS = 256;
 
-__device__ __forceinline__ float block_sum(float v, float* sh) {   // sh: >= 4 floats; result on all threads
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[w] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-__device__ __forceinline__ float block_max(float v, float* sh) {
-  v = wave_max(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[w] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
-
-// 4-wave block reductions of the totals below (sh: >= 4 elements; result on all threads)
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[w] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-__device__ __forceinline__ long long block_sum(long long v, long long* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[w] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
 // one block per row n.  PRED: the row's argmax rides in the pass that finds the maximum for the log-sum-exp, as one
 // (value, index) key per lane (vqf_argmax_key: ties to the lowest index, NaN above everything); loss and dlogits keep the
 // arithmetic and the reduction order of the plain form, so both instantiations give the same bits.
@@ -74,7 +37,7 @@ __global__ __launch_bounds__(TR_THREADS) void ce_rows_kernel(const float* __rest
   // rows that count (every block recomputes it: N int64 loads out of L2)
   float cnt = 0.f;
   for (int i = threadIdx.x; i < N; i += TR_THREADS) cnt += (target[i] != -100) ? 1.f : 0.f;
-  cnt = block_sum(cnt, sh);
+  cnt = vqf_block256_sum(cnt, sh);
   const float inv_cnt = cnt > 0.f ? 1.f / cnt : 0.f;
 
   const float* x = logits + (size_t)n * A;
@@ -88,10 +51,10 @@ __global__ __launch_bounds__(TR_THREADS) void ce_rows_kernel(const float* __rest
       best = key > best ? key : best;
     }
   }
-  mx = block_max(mx, sh);
+  mx = vqf_block256_max(mx, sh);
   float se = 0.f;
   for (int a = threadIdx.x; a < A; a += TR_THREADS) se += expf(x[a] - mx);
-  se = block_sum(se, sh);
+  se = vqf_block256_sum(se, sh);
   const float lse = mx + logf(se);
   const long long t = target[n];
   const bool live = (t != -100);
@@ -130,11 +93,11 @@ __global__ __launch_bounds__(TR_THREADS) void loss_finish_kernel(const float* __
   __shared__ float sh[4];
   float s = 0.f;
   for (int i = threadIdx.x; i < P; i += TR_THREADS) s += part[i];
-  s = block_sum(s, sh);
+  s = vqf_block256_sum(s, sh);
   if (target) {
     float cnt = 0.f;
     for (int i = threadIdx.x; i < N; i += TR_THREADS) cnt += (target[i] != -100) ? 1.f : 0.f;
-    cnt = block_sum(cnt, sh);
+    cnt = vqf_block256_sum(cnt, sh);
     scale = 1.f / cnt;       // 0/0 -> NaN like torch when every row is ignored
   }
   if (threadIdx.x == 0) loss[0] = s * scale;
@@ -148,9 +111,9 @@ __global__ __launch_bounds__(TR_THREADS) void loss_finish_kernel(const float* __
       hits += tt.hit[i];
       rows += (target[i] != -100) ? 1 : 0;
     }
-    ds = block_sum(ds, shd);
-    hits = block_sum(hits, shl);
-    rows = block_sum(rows, shl);
+    ds = vqf_block256_sum(ds, shd);
+    hits = vqf_block256_sum(hits, shl);
+    rows = vqf_block256_sum(rows, shl);
     if (threadIdx.x == 0) {
       if (tt.counts) {
         tt.counts[0] = (tt.accumulate ? tt.counts[0] : 0) + hits;
@@ -206,7 +169,7 @@ __global__ __launch_bounds__(TR_THREADS) void bce_rows_kernel(const float* __res
     best = key > best ? key : best;
     if (d) d[a] = (bce_sigmoid(v, e) - ta) * c;
   }
-  s = block_sum(s, sh);
+  s = vqf_block256_sum(s, sh);
   const int p = vqf_argmax_index(vqf_block256_max_u64(best, shk));
   const size_t k0 = (size_t)n * (SPARSE ? sl.K : 0);
   if (threadIdx.x == 0) {
@@ -275,9 +238,9 @@ __global__ __launch_bounds__(TR_THREADS) void bce_finish_kernel(const float* __r
     ds += (double)rowloss[i];
     ss += (double)rowscore[i];
   }
-  s = block_sum(s, sh);
-  ds = block_sum(ds, shd);
-  ss = block_sum(ss, shd);
+  s = vqf_block256_sum(s, sh);
+  ds = vqf_block256_sum(ds, shd);
+  ss = vqf_block256_sum(ss, shd);
   if (threadIdx.x == 0) {
     const bool acc = tt.accumulate != 0;
     loss[0] = s * c;
@@ -305,7 +268,7 @@ __global__ __launch_bounds__(TR_THREADS) void kldiv_kernel(const float* __restri
       if (dlogp) dlogp[i] = -t * inv_n;
     }
   }
-  s = block_sum(s, sh);
+  s = vqf_block256_sum(s, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -429,7 +392,7 @@ __global__ __launch_bounds__(TR_THREADS) void grad_sumsq_kernel(const GradTable 
       }
     }
   }
-  s = block_sum(s, sh);
+  s = vqf_block256_sum(s, sh);
   if (threadIdx.x == 0) part[b] = s;
 }
 
@@ -450,7 +413,7 @@ __global__ __launch_bounds__(TR_THREADS) void grad_norm_finish_kernel(const floa
     for (int k = 0; k < 8; ++k) s += (double)x[k];
   }
   for (; i < P; i += TR_THREADS) s += (double)part[i];
-  s = block_sum(s, shd);
+  s = vqf_block256_sum(s, shd);
   if (threadIdx.x == 0) {
     const float nm = (float)sqrt(s);
     float c = (1.0f / (nm + 1e-6f)) * max_norm;
