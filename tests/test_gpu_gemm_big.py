@@ -53,6 +53,12 @@ def _rel(out, ref):
     return float((out.double() - ref).abs().max() / (ref.abs().max() + 1e-300))
 
 
+def _worst_ratio(out, ref, terms, k):
+    """per ELEMENT |out - ref| over (k + 1) 2^-24 sum |terms| (the bound of tests/gemm_ref.py; terms: fp64 sum_k |a b| + |bias| of
+    each element, k: the additions a term passes through), its largest value"""
+    return float(((out.double() - ref).abs() / ((k + 1) * 2.0 ** -24 * terms).clamp_min(1e-300)).max())
+
+
 # (M, N, K, what): >= 64 tiles of 256x256 each so that vqf_gemm_bf16 routes to gemm_bf16_big.hip
 BF16_BIG = [
     (2104, 2200, 96, "ragged M and N tails, 3 slabs (shorter than the 4-deep copy pipeline)"),
@@ -475,10 +481,14 @@ def test_per_sample_tile_gemm_vs_fp64_and_the_other_kernels(NS, L, N, K, tb):
         with ops.options(gemm_f32_sample=2):                                     # also the batches too small for it to pay
             C = ops.gemm_rows(A, Bm, L, tb=tb, bias=bias, relu=relu, out=outbuf[:, :N])
         ref = A.double() @ (Bm.double() if tb else Bm.double().t()) + bias.double()
+        terms = A.double().abs() @ (Bm.double().abs() if tb else Bm.double().abs().t()) + bias.double().abs()
         if relu:
             ref = torch.relu(ref)
         tol = 2e-6 * max(1.0, K ** 0.5 / 8)
         assert float((C.double() - ref).norm() / ref.norm()) <= tol
+        worst = _worst_ratio(C, ref, terms, K + 1)                               # per element: K accumulates and the bias
+        print("per-sample tiles NS %d L %d N %d K %d tb %d relu %d: worst err/bound %.3f" % (NS, L, N, K, tb, relu, worst))
+        assert worst <= 1.0
         rag = torch.cat([torch.arange(n * L + 192, (n + 1) * L) for n in range(NS)]).cuda() if L > 192 else None
         if rag is not None:                                                      # the 4x4x1 rows on their own
             assert float((C[rag].double() - ref[rag]).norm() / ref[rag].norm()) <= tol
@@ -509,6 +519,7 @@ def test_one_round_128x80_gemm_vs_fp64_and_the_128x128_kernel(M, N, K):
     Bm = (torch.randn((N, K + 8), generator=g) * 0.05).cuda()[:, :K]
     bias = torch.randn(N, generator=g).cuda()
     ref0 = A.double() @ Bm.double().t() + bias.double()
+    terms = A.double().abs() @ Bm.double().abs().t() + bias.double().abs()
     tol = 2e-6 * max(1.0, K ** 0.5 / 8)
     n0 = ops.stat("gemm_f32_n80")
     for relu in (False, True):
@@ -516,6 +527,9 @@ def test_one_round_128x80_gemm_vs_fp64_and_the_128x128_kernel(M, N, K):
         C = ops.gemm(A, Bm, bias=bias, relu=relu, out=outbuf[:M, :N])
         ref = torch.relu(ref0) if relu else ref0
         assert float((C.double() - ref).norm() / ref.norm()) <= tol
+        worst = _worst_ratio(C, ref, terms, K + 1)                               # per element: K accumulates (no K slices) and the bias
+        print("128x80 tiles %d x %d x %d relu %d: worst err/bound %.3f" % (M, N, K, relu, worst))
+        assert worst <= 1.0
         er, ec = (M - 1) // 128 * 128, (N - 1) // 80 * 80                        # the edge tiles
         assert float((C[er:].double() - ref[er:]).norm() / ref[er:].norm()) <= tol
         assert float((C[:, ec:].double() - ref[:, ec:]).norm() / ref[:, ec:].norm()) <= tol
