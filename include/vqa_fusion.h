@@ -349,6 +349,8 @@ int vqf_l2_norm_bwd_coef_lin(const float* dlogits, const float* lin, int G, cons
  *   dcascade[m,c] = dz * P * q          (if cascade != NULL)
  *   dbias_P[c] = sum_m dP[m,c]          (if dbiasP != NULL; this is d pbias as well)
  * P is taken as P + pbias wherever it appears when pbias != NULL.
+ * O % 4 == 0, else VQF_E_UNSUPPORTED -- WITHOUT the forward's O <= 1024: Y is an operand here, and past O / 4 = 256 a thread
+ * walks columns 20 t, 20 (t + 256), ... on the direct (not LDS-transposed) access (tests/test_gpu_mfb_fuse_kernels.py: O = 1028).
  * ws: at least vqf_mfb_fuse_bwd_ws_bytes(N,L,O). */
 size_t vqf_mfb_fuse_bwd_ws_bytes(int N, int L, int O);
 int vqf_mfb_fuse_bwd(const float* dY, const float* dzdrop, const float* Y, const float* inv,
