@@ -517,6 +517,56 @@ int vqf_glimpse_pool_bwd_packed_rows(const float* dpooled, const float* dwts_ext
                                      const int* roff, int N, int U, int R, int S, int C, int G, int unit_softmax, float* dlogits,
                                      void* stream);
 
+/* The bf16 image projection on counted and packed regions (MFB / MHBCoAtt with regions_bf16 = True on the pair (img, img_length) or a
+ * PackedRegions without img_index; additions within ABI 7; un-grouped, no cascade / zdrop).  What is bf16: the operands of img_conv1d
+ * and of its weight gradient (fp32 accumulation), dP, and P where the large-tile bf16 GEMM stored it so.  What is not: q, pbias, R /
+ * Y / dY, rowssq, dq, dbiasP, every sum, the region features the pooling reads, and the masks -- keep stays (N*L, 5*O) and the Philox
+ * element index (n*L + l)*5*O + c, so the masks are those of the fp32 forms.
+ *   fwd_{len,packed,packed_rows}_pbf16   vqf_mfb_fuse_fwd_{len,packed,packed_rows} reading a bf16 P: R and rowssq have the bits the
+ *             fp32 form gives on the same (bf16-representable) values.
+ *   bwd_{len,packed,packed_rows}_pbf16 / _bf16dp   the backward of those forms writing dP in bf16 (round-to-nearest-even of the fp32
+ *             form's values), beside a bf16 P (_pbf16) or an fp32 P (_bf16dp); dq and dbiasP are summed from the unrounded values.
+ *             dP_rows >= the rows the kernels own (R packed, N*L counted; below: VQF_E_BADARG) is the allocated row count of dP: rows
+ *             R .. dP_rows - 1 are left as exact zeros (+0.0), so that the weight gradient dW = dP^T rows may run with K = dP_rows
+ *             rounded up to the large-tile kernel's K % 32 == 0.  The padded dP rows of the counted form are exact zeros as well.
+ *   cast_f32_bf16_rows   vqf_cast_f32_bf16 into a y of y_rows >= R rows (below: VQF_E_BADARG), rows R .. y_rows - 1 exact zeros: the
+ *             other operand of that weight gradient.  Zeros in one operand would not do: 0 * NaN from uninitialised memory is NaN.
+ * Null or misaligned lens / roff, sizes <= 0: VQF_E_BADARG; O % 4 != 0 and the shapes outside vqf_mfb_fuse_packed_supported:
+ * VQF_E_UNSUPPORTED; VQF_E_ALIGN, VQF_E_WORKSPACE (vqf_mfb_fuse_bwd_ws_bytes(N, L, O)) as in the fp32 forms.  The 16-byte pieces of
+ * the coalesced access need 5*O % 8 == 0 in bf16; for other O the direct access runs. */
+int vqf_mfb_fuse_fwd_len_pbf16(const void* P_bf16, const float* pbias, const float* q, const int* lens, const uint8_t* keep,
+                               uint64_t seed, float p_drop, int N, int L, int O, float* R, float* rowssq, void* stream);
+int vqf_mfb_fuse_fwd_packed_pbf16(const void* P_bf16, const float* pbias, const float* q, const int* roff, const uint8_t* keep,
+                                  uint64_t seed, float p_drop, int N, int R, int L, int O, float* Rout, float* rowssq, void* stream);
+int vqf_mfb_fuse_fwd_packed_rows_pbf16(const void* P_bf16, const float* pbias, const float* q, const int* roff, const uint8_t* keep,
+                                       uint64_t seed, float p_drop, int N, int R, int L, int O, float* Rout, float* rowssq,
+                                       void* stream);
+int vqf_mfb_fuse_bwd_len_pbf16(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
+                               const void* P_bf16, const float* pbias, const float* q, const int* lens, const uint8_t* keep,
+                               uint64_t seed, float p_drop, int N, int L, int O, void* dP_bf16, int dP_rows, float* dq, float* dbiasP,
+                               void* ws, size_t ws_bytes, void* stream);
+int vqf_mfb_fuse_bwd_len_bf16dp(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
+                                const float* P, const float* pbias, const float* q, const int* lens, const uint8_t* keep, uint64_t seed,
+                                float p_drop, int N, int L, int O, void* dP_bf16, int dP_rows, float* dq, float* dbiasP, void* ws,
+                                size_t ws_bytes, void* stream);
+int vqf_mfb_fuse_bwd_packed_pbf16(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
+                                  const void* P_bf16, const float* pbias, const float* q, const int* roff, const uint8_t* keep,
+                                  uint64_t seed, float p_drop, int N, int R, int L, int O, void* dP_bf16, int dP_rows, float* dq,
+                                  float* dbiasP, void* ws, size_t ws_bytes, void* stream);
+int vqf_mfb_fuse_bwd_packed_bf16dp(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
+                                   const float* P, const float* pbias, const float* q, const int* roff, const uint8_t* keep,
+                                   uint64_t seed, float p_drop, int N, int R, int L, int O, void* dP_bf16, int dP_rows, float* dq,
+                                   float* dbiasP, void* ws, size_t ws_bytes, void* stream);
+int vqf_mfb_fuse_bwd_packed_rows_pbf16(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
+                                       const void* P_bf16, const float* pbias, const float* q, const int* roff, const uint8_t* keep,
+                                       uint64_t seed, float p_drop, int N, int R, int L, int O, void* dP_bf16, int dP_rows, float* dq,
+                                       float* dbiasP, void* ws, size_t ws_bytes, void* stream);
+int vqf_mfb_fuse_bwd_packed_rows_bf16dp(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB,
+                                        const float* P, const float* pbias, const float* q, const int* roff, const uint8_t* keep,
+                                        uint64_t seed, float p_drop, int N, int R, int L, int O, void* dP_bf16, int dP_rows, float* dq,
+                                        float* dbiasP, void* ws, size_t ws_bytes, void* stream);
+int vqf_cast_f32_bf16_rows(const float* x, int R, int C, int ldx, void* y, int ldy, int y_rows, void* stream);
+
 
 /* --------------------------------------------------------------------------
  * Element-wise stages of HieCoAtten / AttentionNet.  n % 4 == 0, 16-byte aligned pointers.

@@ -1,7 +1,8 @@
 """Packed region features (forward(PackedRegions, ...)): what the MFB train step costs when the loader never pads.
 
     python tools/mfb_packed_bench.py [--batch 512] [--regions 100] [--steps 6] [--warmup 3] [--rounds 2]
-                                     [--forms packed-rows,packed,pair,plain] [--out profiles/mfb_packed_bench.txt]
+                                     [--forms packed-rows-bf16,packed-bf16,packed-rows,packed,pair,plain]
+                                     [--out profiles/mfb_packed_bench.txt]
 
 Setup: N = --batch, L = --regions, D = 2048, the counts of tools/mfb_regions_bench.py (uniform in 10 .. L, seed 1), MFB with the
 live softmax, fp32, the train step of bench.py (forward, loss, backward, the project's Adam).  The forms named in --forms run
@@ -10,13 +11,16 @@ ALTERNATELY in one process (form A's window, form B's window, ..., --rounds time
 the rows the projection runs on and rows / (N L).
   packed   forward(PackedRegions(rows (R, D), offsets, L), q): the projection and its weight gradient on R = sum(counts) rows
   packed-rows   the same call with model.packed_coatt = True: the fusion's output and the co-attention head on the R rows as well
+  packed-bf16 / packed-rows-bf16   those two with model.regions_bf16 = True: img_conv1d and its weight gradient with bf16 operands,
+           P and dP stored in bf16 (the rows are cast per step); everything else fp32
   pair     forward((img (N, L, D), img_length), q): the same batch, zero-padded
   plain    forward(img, q): the padded tensor without counts (a different result: every padded row counts as a region)
 --forms pair,plain uses nothing the packed form added: the same file run from a checkout of the commit before it gives the
 yardstick (and, run twice, the run-to-run spread) those two forms have to stay inside.
 The two projection launches come from a kernel trace in a run of its own (one form per run, e.g. --forms packed --rounds 1).
 After the windows: the peak of torch's allocator over one step of each form (above what is allocated before the step), and, with
-both packed forms named, the largest difference of their logits on the timed batch in eval mode (summation order inside the GEMMs).
+both packed forms named, the largest difference of their logits on the timed batch in eval mode (summation order inside the GEMMs);
+with packed and packed-bf16 named, the same for those two (bf16 rounding of the projection's operands and of P).
 """
 import argparse
 import os
@@ -45,7 +49,7 @@ def main():
     a = ap.parse_args()
     N, L, dev = a.batch, a.regions, "cuda:0"
     forms = a.forms.split(",")
-    assert forms and all(f in ("packed-rows", "packed", "pair", "plain") for f in forms)
+    assert forms and all(f in ("packed-rows-bf16", "packed-bf16", "packed-rows", "packed", "pair", "plain") for f in forms)
     lines = []
 
     def say(s=""):
@@ -73,16 +77,18 @@ def main():
     valid = torch.arange(L)[None, :] < counts[:, None]
     img = (torch.rand(N, L, D, generator=g) * valid[:, :, None]).to(dev)               # zero-padded, as pad_region_features makes it
     feats = {"pair": (img, counts.to(dev)), "plain": img}
-    rows_of = {"pair": N * L, "plain": N * L, "packed": R, "packed-rows": R}
-    if "packed" in forms or "packed-rows" in forms:
+    packed_forms = ("packed", "packed-rows", "packed-bf16", "packed-rows-bf16")
+    rows_of = {"pair": N * L, "plain": N * L, **{f: R for f in packed_forms}}
+    if any(f in forms for f in packed_forms):
         off = torch.zeros(N + 1, dtype=torch.int64)
         off[1:] = torch.cumsum(counts, 0)
-        feats["packed"] = feats["packed-rows"] = vqa_amd.PackedRegions(img[valid.to(dev)].contiguous(), off.to(dev), L)
+        feats.update(dict.fromkeys(packed_forms, vqa_amd.PackedRegions(img[valid.to(dev)].contiguous(), off.to(dev), L)))
     crit = vqa_amd.CrossEntropyLoss()
     opt = vqa_amd.Adam(model.parameters(), lr=1e-4)
 
     def step(f):
-        model.packed_coatt = f == "packed-rows"
+        model.packed_coatt = f.startswith("packed-rows")
+        model.regions_bf16 = f.endswith("-bf16")
         opt.zero_grad(set_to_none=True)
         crit(model(feats[f], ids), target).backward()
         opt.step()
@@ -102,18 +108,23 @@ def main():
             torch.cuda.synchronize()
             w[f].append(t0.elapsed_time(t1) / a.steps)
     say()
-    say("%-11s  ms/step median (spread)   windows                      projection rows   rows / (N L)" % "form")
+    say("%-16s  ms/step median (spread)   windows                      projection rows   rows / (N L)" % "form")
     med = {}
     for f in forms:
         s = sorted(w[f])
         med[f] = 0.5 * (s[(len(s) - 1) // 2] + s[len(s) // 2])
-        say("%-11s  %9.3f (%.3f)          %-28s %9d        %.3f" % (f, med[f], s[-1] - s[0], " ".join("%.3f" % x for x in w[f]), rows_of[f],
+        say("%-16s  %9.3f (%.3f)          %-28s %9d        %.3f" % (f, med[f], s[-1] - s[0], " ".join("%.3f" % x for x in w[f]), rows_of[f],
                                                                    rows_of[f] / (N * L)))
     if "packed" in med and "pair" in med:
         say("packed / pair = %.3f" % (med["packed"] / med["pair"]))
     if "packed-rows" in med and "packed" in med:
         say("packed-rows - packed = %.3f ms / step, per round: %s" % (med["packed-rows"] - med["packed"],
                                                                      " ".join("%.3f" % (x - y) for x, y in zip(w["packed-rows"], w["packed"]))))
+    for f in ("packed", "packed-rows"):
+        if f in med and f + "-bf16" in med:
+            say("%s-bf16 / %s = %.3f (%.3f ms / step less), per round: %s"
+                % (f, f, med[f + "-bf16"] / med[f], med[f] - med[f + "-bf16"],
+                   " ".join("%.3f" % (y - x) for x, y in zip(w[f + "-bf16"], w[f]))))
     say()
     for f in forms:                                   # the allocator's peak over one step, above what the step starts from
         opt.zero_grad(set_to_none=True)
@@ -122,7 +133,7 @@ def main():
         base = torch.cuda.memory_allocated()
         step(f)
         torch.cuda.synchronize()
-        say("%-11s  peak memory of one step above its start: %.1f MB" % (f, (torch.cuda.max_memory_allocated() - base) / 1e6))
+        say("%-16s  peak memory of one step above its start: %.1f MB" % (f, (torch.cuda.max_memory_allocated() - base) / 1e6))
     if "packed-rows" in forms and "packed" in forms:
         model.eval()
         with torch.no_grad():
@@ -131,6 +142,14 @@ def main():
             model.packed_coatt = True
             o1 = model(feats["packed"], ids)
         say("logits, eval mode: max |packed-rows - packed| / max |packed| = %.2e" % float((o1 - o0).abs().max() / o0.abs().max()))
+    if "packed-bf16" in forms and "packed" in forms:
+        model.eval()
+        with torch.no_grad():
+            model.packed_coatt, model.regions_bf16 = False, False
+            o0 = model(feats["packed"], ids)
+            model.regions_bf16 = True
+            o1 = model(feats["packed"], ids)
+        say("logits, eval mode: max |packed-bf16 - packed| / max |packed| = %.2e" % float((o1 - o0).abs().max() / o0.abs().max()))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

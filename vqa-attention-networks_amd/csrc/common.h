@@ -177,6 +177,16 @@ struct VqfRegions {
   bool packed_ok(const int* own, int N) const { return ok(roff) && aligned(own) && Rtot > 0 && U > 0 && (own || U == N); }
 };
 
+// fusion.hip: the image fusion's bf16 forms on an un-grouped layout (rg counted, packed or packed rows; the caller has checked its
+// arrays) -- a bf16 P in the forward, a bf16 dP beside a bf16 (p_bf16) or an fp32 P in the backward.  The launch functions of the
+// entry points in fusion_regions_bf16.hip; everything else is checked as in the fp32 forms.
+int vqf_fuse_fwd_regions_bf16(const void* P_bf16, const float* pbias, const float* q, const uint8_t* keep, uint64_t seed, float p_drop,
+                              int N, int L, int O, float* R, float* rowssq, void* stream, const VqfRegions& rg);
+int vqf_fuse_bwd_regions_bf16(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB, const void* P,
+                              int p_bf16, const float* pbias, const float* q, const uint8_t* keep, uint64_t seed, float p_drop, int N,
+                              int L, int O, void* dP_bf16, float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream,
+                              const VqfRegions& rg);
+
 // The glimpse / level count G = 1, 2, 3 (checked by the caller) as a compile-time constant: f(std::integral_constant<int, G>()).
 // G3 = false: the caller has no G = 3 instantiation (and has refused G = 3).
 template <bool G3 = true, typename F> static inline void vqf_dispatch_G(int G, F&& f) {

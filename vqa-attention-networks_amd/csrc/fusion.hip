@@ -561,8 +561,8 @@ int pick_ls_image(int U, int L) {
 
 // ---- launches: the run-time switches become template arguments, each kernel's argument list is written once ---------------------
 // The operands of a launch after the checks; where the image rows are comes in a VqfRegions (common.h), host-side only.  Every
-// function below names the instantiations it can reach, so none exists that nobody launches: the layouts are fp32 only (no bf16
-// with GRP / LEN / PACK), PROWS only un-grouped, CASC only in the plain form, and the question-owned grouped pass has no DBIAS.
+// function below names the instantiations it can reach, so none exists that nobody launches: the grouped layouts are fp32 only (no bf16
+// with GRP; the un-grouped LEN / PACK / PROWS forms take a bf16 P and / or a bf16 dP too), PROWS only un-grouped, CASC only in the plain form, and the question-owned grouped pass has no DBIAS.
 struct FuseFwd {
   const void* P; const float *pbias, *q, *cascade; const uint8_t* keep; uint64_t seed; uint32_t thr; float inv_keep;
   int N, L, O, LS; float *R, *rowssq, *zdrop; unsigned short* Rb; int ldrb; hipStream_t s;
@@ -584,6 +584,10 @@ void fuse_fwd_layout(const FuseFwd& a, const VqfRegions& rg) {
     if (rg.counted() && rg.grouped()) return fuse_fwd_go<float, COAL, true, true>(a, rg);
     if (rg.counted()) return fuse_fwd_go<float, COAL, false, true>(a, rg);
     if (rg.grouped()) return fuse_fwd_go<float, COAL, true>(a, rg);
+  } else {                                                                                           // bf16 P: the un-grouped layouts
+    if (rg.packed() && rg.rows) return fuse_fwd_go<__bf16, COAL, false, true, true, true>(a, rg);
+    if (rg.packed()) return fuse_fwd_go<__bf16, COAL, false, true, true>(a, rg);
+    if (rg.counted()) return fuse_fwd_go<__bf16, COAL, false, true>(a, rg);
   }
   fuse_fwd_go<PT, COAL>(a, rg);
 }
@@ -617,10 +621,23 @@ void fuse_bwd_flags(bool dbias, bool coal, const FuseBwd& a, const VqfRegions& r
   else fuse_bwd_go<CASC, false, DPT, PT, false, GRP, LEN, PACK, PROWS>(a, rg);
 }
 
+// bf16 dP on an un-grouped layout (region counts, packed, packed rows), beside a bf16 or an fp32 P
+template <typename PT>
+void fuse_bwd_layout_bf16_p(bool dbias, bool coal, const FuseBwd& a, const VqfRegions& rg) {
+  if (rg.packed() && rg.rows) fuse_bwd_flags<false, __bf16, PT, false, true, true, true>(dbias, coal, a, rg);
+  else if (rg.packed()) fuse_bwd_flags<false, __bf16, PT, false, true, true>(dbias, coal, a, rg);
+  else fuse_bwd_flags<false, __bf16, PT, false, true>(dbias, coal, a, rg);
+}
+
+void fuse_bwd_layout_bf16(bool p_bf16, bool dbias, bool coal, const FuseBwd& a, const VqfRegions& rg) {
+  if (p_bf16) fuse_bwd_layout_bf16_p<__bf16>(dbias, coal, a, rg); else fuse_bwd_layout_bf16_p<float>(dbias, coal, a, rg);
+}
+
 void fuse_bwd_layout(bool p_bf16, bool dp_bf16, bool dbias, bool coal, const FuseBwd& a, const VqfRegions& rg) {
   if (rg.grouped() && rg.packed()) fuse_bwd_flags<false, float, float, true, true, true>(false, coal, a, rg);
   else if (rg.grouped() && rg.counted()) fuse_bwd_flags<false, float, float, true, true>(false, coal, a, rg);
   else if (rg.grouped()) fuse_bwd_flags<false, float, float, true>(false, coal, a, rg);
+  else if (dp_bf16 && (rg.packed() || rg.counted())) fuse_bwd_layout_bf16(p_bf16, dbias, coal, a, rg);
   else if (rg.packed() && rg.rows) fuse_bwd_flags<false, float, float, false, true, true, true>(dbias, coal, a, rg);
   else if (rg.packed()) fuse_bwd_flags<false, float, float, false, true, true>(dbias, coal, a, rg);
   else if (rg.counted()) fuse_bwd_flags<false, float, float, false, true>(dbias, coal, a, rg);
@@ -645,7 +662,7 @@ void fuse_bwd_image_flags(bool dbias, int LSI, const FuseBwd& a, const VqfRegion
 
 }  // namespace
 
-// The layout forms (rg not plain) are fp32 without cascade / dzdrop; their entry points have checked the arrays of rg.
+// The layout forms (rg not plain) have no cascade / dzdrop and are fp32 when grouped; their entry points have checked the arrays of rg.
 static int fuse_bwd_impl(const float* dY, const float* dzdrop, const float* Y, const float* inv, const float* coefA,
                          const float* coefB, const void* P, int p_bf16, const float* pbias, const float* q, const float* cascade,
                          const uint8_t* keep, uint64_t seed, float p_drop, int N, int L, int O, void* dP, int dp_bf16, float* dq,
@@ -728,6 +745,23 @@ static int fuse_bwd_regions(const float* dY, const float* Y, const float* inv, c
                             float* dP, float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream, const VqfRegions& rg) {
   return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, 0, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP, 0, dq, nullptr,
                        dbiasP, ws, ws_bytes, stream, rg);
+}
+
+// The bf16 forms of the un-grouped layouts (common.h; their entry points and argument checks live in fusion_regions_bf16.hip): a
+// bf16 P in the forward; a bf16 dP beside a bf16 or an fp32 P in the backward.  rg: counted, packed or packed rows, checked there.
+int vqf_fuse_fwd_regions_bf16(const void* P_bf16, const float* pbias, const float* q, const uint8_t* keep, uint64_t seed, float p_drop,
+                              int N, int L, int O, float* R, float* rowssq, void* stream, const VqfRegions& rg) {
+  if (rg.grouped() || !(rg.counted() || rg.packed())) return VQF_E_BADARG;
+  return fuse_fwd_impl(P_bf16, 1, pbias, q, nullptr, keep, seed, p_drop, N, L, O, R, rowssq, nullptr, stream, nullptr, 0, rg);
+}
+
+int vqf_fuse_bwd_regions_bf16(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB, const void* P,
+                              int p_bf16, const float* pbias, const float* q, const uint8_t* keep, uint64_t seed, float p_drop, int N,
+                              int L, int O, void* dP_bf16, float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream,
+                              const VqfRegions& rg) {
+  if (rg.grouped() || !(rg.counted() || rg.packed())) return VQF_E_BADARG;
+  return fuse_bwd_impl(dY, nullptr, Y, inv, coefA, coefB, P, p_bf16, pbias, q, nullptr, keep, seed, p_drop, N, L, O, dP_bf16, 1, dq,
+                       nullptr, dbiasP, ws, ws_bytes, stream, rg);
 }
 
 extern "C" {

@@ -205,22 +205,27 @@ class JoinRowsFn(torch.autograd.Function):
 # ---------------------------------------------------------------------------------------------
 # One dispatcher pair per kernel family that knows where the image rows are (grouping.RegionLayout: shared images, region
 # counts, packed rows).  Each picks the ops.* wrapper of the layout and is the only place that does; layout None is the plain
-# tensor and takes the calls it always took.  Image tensors behind a layout other than the plain one are fp32.
+# tensor and takes the calls it always took.  Image tensors behind a layout other than the plain one are fp32 -- but for P and dP of
+# the un-grouped layouts (the models' regions_bf16): the wrappers pick the bf16 entry points by P.dtype and dp_bf16, a bf16 P / dP has
+# ops.pad_rows(layout.R) rows (the weight gradient's K, zero behind the layout.R real ones).
 # ---------------------------------------------------------------------------------------------
 def _fuse_fwd(P, q, layout, N, L, O, link, **kw):
     """The MFB fusion over the regions (ops.mfb_fuse_fwd / _grouped / _packed / _packed_rows; kw: keep, seed, p_drop, pbias)
     -> (Y, norm, inv, rb, (scale, rows per scale)): with a link Y is R without 1/norm, rb holds the bf16 copy of R a bf16 P's kernel
     wrote beside it, and the last pair is what the link's consumer scales Y's rows by -- (inv, L), or (rowinv, 1) where Y holds
     the packed rows (layout.rows)."""
+    if layout is not None and P.dtype == torch.bfloat16:                  # un-grouped (the nodes refuse bf16 with shared images)
+        kw["regions_bf16"] = True
     if layout is not None and layout.rows:
-        Y, norm, inv, rowinv = ops.mfb_fuse_fwd_packed_rows(P, q, layout.roff, N, L, O, normalise=link is None, **kw)
+        Y, norm, inv, rowinv = ops.mfb_fuse_fwd_packed_rows(P, q, layout.roff, N, L, O, normalise=link is None, R=layout.R, **kw)
         return Y, norm, inv, None, (rowinv, 1)
     if layout is not None and layout.packed:
-        return ops.mfb_fuse_fwd_packed(P, q, layout.roff, N, L, O, idx=layout.idx, normalise=link is None, **kw) + (None, None)
+        return ops.mfb_fuse_fwd_packed(P, q, layout.roff, N, L, O, idx=layout.idx, normalise=link is None, R=layout.R,
+                                       **kw) + (None, None)
     if layout is not None and layout.grouped:
         return ops.mfb_fuse_fwd_grouped(P, q, layout.idx, N, layout.U, L, O, normalise=link is None,
                                         lens=(layout.lens_q, layout.lens_u) if layout.counted else None, **kw) + (None, None)
-    rb = [] if (link is not None and P.dtype == torch.bfloat16) else None
+    rb = [] if (link is not None and P.dtype == torch.bfloat16 and layout is None) else None   # (no bf16 copy of R with counts)
     Y, norm, inv, _ = ops.mfb_fuse_fwd(P, q, N, L, O, normalise=link is None, r_bf16=rb,
                                        lens=None if layout is None else layout.lens_q, **kw)
     return Y, norm, inv, rb, None
@@ -228,14 +233,18 @@ def _fuse_fwd(P, q, layout, N, L, O, link, **kw):
 
 def _fuse_bwd(dY, Y, norm, inv, P, q, layout, N, L, O, dp_bf16=False, **kw):
     """-> (dP in P's layout -- summed per image where the images are shared --, dq, dbias); kw: keep, seed, p_drop, pbias, lin"""
+    if layout is not None and dp_bf16:                                    # un-grouped (the nodes refuse bf16 with shared images)
+        kw.update(regions_bf16=True, dp_bf16=True, dp_rows=ops.pad_rows(layout.R))
     if layout is not None and layout.rows:
-        return ops.mfb_fuse_bwd_packed_rows(dY, Y, norm, inv, P, q, layout.roff, N, L, O, want_dbias=True, **kw)
+        return ops.mfb_fuse_bwd_packed_rows(dY, Y, norm, inv, P, q, layout.roff, N, L, O, want_dbias=True, R=layout.R, **kw)
     if layout is not None and layout.packed:
-        return ops.mfb_fuse_bwd_packed(dY, Y, norm, inv, P, q, layout.roff, N, L, O, grp=layout.grp, want_dbias=True, **kw)
+        return ops.mfb_fuse_bwd_packed(dY, Y, norm, inv, P, q, layout.roff, N, L, O, grp=layout.grp, want_dbias=True, R=layout.R,
+                                       **kw)
     if layout is not None and layout.grouped:
         return ops.mfb_fuse_bwd_grouped(dY, Y, norm, inv, P, q, *layout.grp, N, layout.U, L, O, want_dbias=True,
                                         lens=(layout.lens_q, layout.lens_u) if layout.counted else None, **kw)
-    dP, dq, _, dbi = ops.mfb_fuse_bwd(dY, Y, norm, inv, P, q, N, L, O, want_dbias=True, dp_bf16=dp_bf16,
+    kw.setdefault("dp_bf16", dp_bf16)
+    dP, dq, _, dbi = ops.mfb_fuse_bwd(dY, Y, norm, inv, P, q, N, L, O, want_dbias=True,
                                       lens=None if layout is None else layout.lens_q, **kw)
     return dP, dq, dbi
 
@@ -436,31 +445,49 @@ def _fuse_node_bwd(ctx, dY, Y, norm, inv, P, q, keep, pbias, dp_bf16):
                      pbias=pbias, lin=_take_lin(ctx.link))
 
 
-def _img_proj(img, wi, bf16, bias=None, store_bf16=True, out=None):
+def _img_proj(img, wi, bf16, bias=None, store_bf16=True, out=None, pad_k=False):
     """a5, the one place that forms P = img W^T (+ bias): img (., ., D) flattened to rows -> (P, the 2-D image operand as the GEMM
     consumed it, which is what the weight gradient takes).  bf16: bf16 storage of the image tensor (a bf16 batch is used as it
     is, no per-step cast) and of the weight, fp32 accumulation; with store_bf16 P itself is STORED in bf16 when the large-tile
     kernel applies and ImgFuseFn.BF16_P allows (half the bytes of the largest tensor of the step in the GEMM epilogue, the
-    fusion forward and the fusion backward)."""
+    fusion forward and the fusion backward).
+    pad_k (bf16 on a region layout, whose row count R is whatever the counts add up to): the bf16 image operand comes back with
+    ops.pad_rows(R) rows, exact zeros behind the R real ones, so that the weight gradient's K is a multiple of 32 and takes the
+    large-tile kernel; the product keeps M = R, and a bf16 P has the padded row count too (zero rows no kernel reads: the gradient
+    autograd hands back for it is the padded dP).  Where R is a multiple of 32 this is the call without pad_k."""
     img = _c(img)
     img2 = img.view(-1, img.shape[-1])
     if not bf16:
         return ops.gemm(img2, _w2d(wi), bias=bias, out=out), img2
+    R = img2.shape[0]
     if img2.dtype != torch.bfloat16:
-        img2 = ops.cast_bf16(img2)
+        img2 = ops.cast_bf16(img2, pad_rows_to=ops.K_PAD_ROWS if pad_k else None)
     wb = ops.cast_bf16(_w2d(wi))
-    P = ops.gemm_bf16(img2, wb, bias=bias, out_bf16=True) if (store_bf16 and ImgFuseFn.BF16_P) else None
+    P = None
+    if store_bf16 and ImgFuseFn.BF16_P:
+        if img2.shape[0] != R:
+            Pp = torch.empty((img2.shape[0], wb.shape[0]), dtype=torch.bfloat16, device=img2.device)
+            if ops.gemm_bf16(img2, wb, bias=bias, M=R, out=Pp[:R], out_bf16=True) is not None:
+                Pp[R:].zero_()
+                P = Pp
+        else:
+            P = ops.gemm_bf16(img2, wb, bias=bias, out_bf16=True)
     if P is None:
-        P = ops.gemm_bf16(img2, wb, bias=bias)
+        P = ops.gemm_bf16(img2, wb, bias=bias, M=R)
     return P, img2
 
 
 def _img_wgrad(dP, img2, wi):
     """The projection's weight gradient dW = dP^T img2, K = the rows of P, for img2 as _img_proj returned it: a bf16 image operand
-    takes dP in bf16 -- as the fusion's backward wrote it (no cast pass), or cast here."""
+    takes dP in bf16 -- as the fusion's backward wrote it (no cast pass), or cast here (to img2's rows where _img_proj padded them:
+    both operands' tails are exact zeros)."""
     dP = _c(dP)
     if img2.dtype == torch.bfloat16:
-        return ops.gemm_bf16(dP if dP.dtype == torch.bfloat16 else ops.cast_bf16(dP), img2, ta=True, tb=True).view_as(wi)
+        if dP.dtype != torch.bfloat16:
+            dP = ops.cast_bf16(dP, pad_rows_to=ops.K_PAD_ROWS if img2.shape[0] != dP.shape[0] else None)
+        if dP.shape[0] != img2.shape[0]:
+            raise ops._l.VqfError("image projection weight gradient: dP has %d rows, the bf16 image operand %d" % (dP.shape[0], img2.shape[0]))
+        return ops.gemm_bf16(dP, img2, ta=True, tb=True).view_as(wi)
     return ops.gemm(dP, img2, ta=True, tb=True).view_as(wi)
 
 
@@ -476,7 +503,9 @@ class ImgFuseFn(torch.autograd.Function):
     img (N,L,D) data (no gradient), wi (5000,D[,1,1]), bi (5000), q (N,5000)
     -> Y (N*L, 1000), row m = n*L + l   (the reference's fusion_normed is the
     (N,1000,L,1) permutation of the same values, mfb.py:103-106).
-    layout (None, or the grouping.RegionLayout of img; fp32 only).  Shared images: img is (U, L, D); the projection and its weight
+    layout (None, or the grouping.RegionLayout of img; img itself fp32; bf16 -- the models' regions_bf16 -- only where no images are
+    shared: bf16 operands for the projection and its weight gradient, dP and, where the large-tile GEMM applies, P stored in bf16,
+    both operands of the weight gradient zero-padded to K % 32 == 0 rows).  Shared images: img is (U, L, D); the projection and its weight
     gradient run on U*L rows, the fusion reads P through idx and its backward sums dP per image.  Region counts: sample n has
     lens_q[n] real regions; the projection and its weight gradient still run over every row, the fusion reads no padded row of P
     and hands back exact zero dP rows there, so finite padding cancels in the weight gradient.  Packed rows: img is (1, R, D), the
@@ -492,9 +521,11 @@ class ImgFuseFn(torch.autograd.Function):
         img, q = _c(img), _c(q)
         N, L = (img.shape[0], img.shape[1]) if layout is None else (layout.N, layout.L)
         ctx.bf16 = bool(bf16)
-        if layout is not None and (ctx.bf16 or img.dtype != torch.float32):
-            raise ops._l.VqfError("ImgFuseFn: a region layout (shared images, region counts, packed rows) is fp32 only")
-        P, img2 = _img_proj(img, wi, ctx.bf16, bias=bi)     # once per image where they are shared; packed: the real rows only
+        if layout is not None and ((ctx.bf16 and layout.grouped) or img.dtype != torch.float32):
+            raise ops._l.VqfError("ImgFuseFn: a region layout (shared images, region counts, packed rows) takes fp32 features, and "
+                                  "shared images are fp32 only")
+        # once per image where they are shared; packed: the real rows only
+        P, img2 = _img_proj(img, wi, ctx.bf16, bias=bi, pad_k=layout is not None)
         Y, norm, inv = _fuse_node_fwd(ctx, P, None, q, keep, seed, p_drop, N, L, link, layout)
         ctx.save_for_backward(img2, wi, q, P, Y, norm, inv, keep)
         return Y
@@ -513,15 +544,16 @@ class ImgProjFn(torch.autograd.Function):
     stream, concurrently with the question-side backward and the gradient all-reduce."""
 
     @staticmethod
-    def forward(ctx, img, wi, bf16=False):
-        P0, img2 = _img_proj(img, wi, bool(bf16), store_bf16=False)        # (this node hands on an fp32 P0 in the bf16 mode too)
+    def forward(ctx, img, wi, bf16=False, pad_k=False):
+        # (this node hands on an fp32 P0 in the bf16 mode too; pad_k: _img_proj)
+        P0, img2 = _img_proj(img, wi, bool(bf16), store_bf16=False, pad_k=pad_k)
         ctx.save_for_backward(img2, wi)
         return P0
 
     @staticmethod
     def backward(ctx, dP):
         img2, wi = ctx.saved_tensors
-        return None, _img_wgrad(dP, img2, wi), None
+        return None, _img_wgrad(dP, img2, wi), None, None
 
 
 class ImgProjDeferFn(torch.autograd.Function):
@@ -549,11 +581,11 @@ class ImgProjDeferFn(torch.autograd.Function):
         return None, _img_wgrad(dP, img2, wi)
 
 
-def img_project(img, wi, bf16, cu_limit=0):
+def img_project(img, wi, bf16, cu_limit=0, pad_k=False):
     """a5 without an autograd node: P0 = img W^T (no bias), fp32 or -- bf16 operands -- STORED in bf16 when the large-tile
-    kernel applies (_img_proj).  Returns (P0, img2d as the GEMM consumed it).  cu_limit: _cu_bracket."""
+    kernel applies (_img_proj; pad_k as there).  Returns (P0, img2d as the GEMM consumed it).  cu_limit: _cu_bracket."""
     with _cu_bracket(cu_limit):
-        return _img_proj(img, wi, bf16)
+        return _img_proj(img, wi, bf16, pad_k=pad_k)
 
 
 class ImgProjLateFn(torch.autograd.Function):
@@ -579,7 +611,8 @@ class ImgProjLateFn(torch.autograd.Function):
 class MfbFuseFn(torch.autograd.Function):
     """a6: Y = L2norm_n(ssqrt(pool5(dropout((P0 + bias) * q[n])))) for the L regions of each sample.
     P0 fp32, or bf16 (then dP is handed back in bf16 too: the bf16 mode's projection storage).
-    layout (None, or the grouping.RegionLayout of the projected image tensor; fp32 P0 only), as in ImgFuseFn.  Shared images: P0 is
+    layout (None, or the grouping.RegionLayout of the projected image tensor; a bf16 P0 only where no images are shared, and then
+    with ops.pad_rows(layout.R) rows, as dP), as in ImgFuseFn.  Shared images: P0 is
     (U*L, 5000) and dP comes back (U*L, 5000), summed over each image's questions, so the projection node behind it (ImgProjFn /
     ImgProjDeferFn / ImgProjLateFn) runs its weight gradient with K = U*L.  Region counts: no padded row of P0 is read, the padded
     rows of dP are exact zeros.  Packed rows: P0 and dP are (R, 5000), the real rows."""
@@ -587,9 +620,10 @@ class MfbFuseFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, P0, bi, q, keep, seed, p_drop, N, L, link=None, layout=None):
         P0, q = _c(P0), _c(q)
-        if layout is not None and P0.dtype != torch.float32:
-            raise ops._l.VqfError("MfbFuseFn: a region layout (shared images, region counts, packed rows) is fp32 only, got a %s "
-                                  "projection" % P0.dtype)
+        if layout is not None and P0.dtype != torch.float32 and (layout.grouped or P0.shape[0] != ops.pad_rows(layout.R)):
+            raise ops._l.VqfError("MfbFuseFn: shared images are fp32 only, and a bf16 projection on a region layout has the rows of "
+                                  "the layout rounded up to a multiple of %d; got a %s projection of %d rows"
+                                  % (ops.K_PAD_ROWS, P0.dtype, P0.shape[0]))
         Y, norm, inv = _fuse_node_fwd(ctx, P0, bi, q, keep, seed, p_drop, N, L, link, layout)
         ctx.save_for_backward(P0, bi, q, Y, norm, inv, keep)
         return Y

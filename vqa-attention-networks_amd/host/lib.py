@@ -183,6 +183,24 @@ SIGNATURES = {
     "vqf_mfb_fuse_fwd_packed_rows": (c_i, [c_f, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
     "vqf_mfb_fuse_bwd_packed_rows": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float,
                                            c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_p, c_sz, c_p]),
+    # the bf16 image projection on counted / packed regions (MFB / MHBCoAtt regions_bf16; csrc/fusion_regions_bf16.hip): a bf16 P and /
+    # or a bf16 dP of dP_rows rows (the int behind dP), zero behind the real ones
+    "vqf_mfb_fuse_fwd_len_pbf16": (c_i, [c_p, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_f, c_f, c_p]),
+    "vqf_mfb_fuse_fwd_packed_pbf16": (c_i, [c_p, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
+    "vqf_mfb_fuse_fwd_packed_rows_pbf16": (c_i, [c_p, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
+    "vqf_mfb_fuse_bwd_len_pbf16": (c_i, [c_f, c_f, c_f, c_f, c_f, c_p, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float,
+                                         c_i, c_i, c_i, c_p, c_i, c_f, c_f, c_p, c_sz, c_p]),
+    "vqf_mfb_fuse_bwd_len_bf16dp": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float,
+                                          c_i, c_i, c_i, c_p, c_i, c_f, c_f, c_p, c_sz, c_p]),
+    "vqf_mfb_fuse_bwd_packed_pbf16": (c_i, [c_f, c_f, c_f, c_f, c_f, c_p, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float,
+                                            c_i, c_i, c_i, c_i, c_p, c_i, c_f, c_f, c_p, c_sz, c_p]),
+    "vqf_mfb_fuse_bwd_packed_bf16dp": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float,
+                                             c_i, c_i, c_i, c_i, c_p, c_i, c_f, c_f, c_p, c_sz, c_p]),
+    "vqf_mfb_fuse_bwd_packed_rows_pbf16": (c_i, [c_f, c_f, c_f, c_f, c_f, c_p, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float,
+                                                 c_i, c_i, c_i, c_i, c_p, c_i, c_f, c_f, c_p, c_sz, c_p]),
+    "vqf_mfb_fuse_bwd_packed_rows_bf16dp": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float,
+                                                  c_i, c_i, c_i, c_i, c_p, c_i, c_f, c_f, c_p, c_sz, c_p]),
+    "vqf_cast_f32_bf16_rows": (c_i, [c_f, c_i, c_i, c_i, c_p, c_i, c_i, c_p]),
     "vqf_l2_group_norm_packed": (c_i, [c_f, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_p]),
     "vqf_l2_norm_bwd_coef_packed": (c_i, [c_f, c_p, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_p]),
     "vqf_l2_norm_bwd_coef_lin_packed": (c_i, [c_f, c_f, c_i, c_p, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_p]),

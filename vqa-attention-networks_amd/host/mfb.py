@@ -109,16 +109,51 @@ def region_layout(who, img_features, questions, img_index, is_data, limits, gemm
     return img, RegionLayout(N, U, L, img_index, img_length)
 
 
-def fusion_region_layout(who, img_features, questions, img_index, gemm_dtype, packed_coatt=False):
+def regions_bf16_applies(who, img_features, img_index, gemm_dtype, regions_bf16):
+    """The models' regions_bf16 attribute on one call -> whether the image projection of this call runs in bf16.  regions_bf16: False,
+    or the projection's output width 5*O (True stands for the models' 5000).  It applies with gemm_dtype "fp32" (any other value
+    keeps its own meaning and its own refusals) to a PackedRegions or a pair (img, img_length) with counts; a plain tensor is not
+    touched.  Its two refusals are raised here, before anything looks at a device: together with img_index (the grouped fusion
+    backward has an image-owned pass of its own, which stays fp32), and a channel count D or a width 5*O that is no multiple of 8
+    (the bf16 GEMM entry's extents)."""
+    if not regions_bf16 or gemm_dtype != "fp32":
+        return False
+    if isinstance(img_features, PackedRegions):
+        feat = img_features.rows
+    elif isinstance(img_features, (tuple, list)) and len(img_features) == 2 and img_features[1] is not None:
+        feat = img_features[0]
+    else:
+        return False
+    if img_index is not None:
+        raise VqfError("%s: regions_bf16 = True does not take img_index (the fusion backward over shared images is fp32 only); set "
+                       "regions_bf16 = False for batches whose questions share images" % who)
+    W5 = 5000 if regions_bf16 is True else int(regions_bf16)
+    D = feat.shape[-1] if torch.is_tensor(feat) and feat.dim() >= 2 else 8         # (not a feature tensor: region_layout says so)
+    if D % 8 or W5 % 8:
+        raise VqfError("%s: regions_bf16 = True needs a channel count D and a projection width 5*O that are multiples of 8 (the bf16 "
+                       "GEMM's extents); got D=%d, 5*O=%d" % (who, D, W5))
+    return True
+
+
+def regions_bf16_on(regions_bf16, gemm_dtype, layout):
+    """regions_bf16_applies behind fusion_region_layout, which has made its refusals: read off the nodes' layout"""
+    return bool(regions_bf16) and gemm_dtype == "fp32" and layout is not None and not layout.grouped and \
+        (layout.packed or layout.counted)
+
+
+def fusion_region_layout(who, img_features, questions, img_index, gemm_dtype, packed_coatt=False, regions_bf16=False):
     """MFB / MHBCoAtt's call of region_layout -> (img (U, L, D) or rows (R, D), the 3-D tensor the projection nodes flatten -- rows
     as (1, R, D) --, L, the nodes' layout: None for the plain tensor, whose path takes nothing extra).
     packed_coatt (the models' attribute): a PackedRegions without img_index gets the layout whose rows BEHIND the fusion are packed
     too (RegionLayout.packed_rows()); with img_index it is refused here, in front of every other check and of the first launch (a
     question's rows would be those of its image, and their total is a shape that would have to be read on the host); for a plain
-    tensor or the pair (img, img_length) it changes nothing."""
+    tensor or the pair (img, img_length) it changes nothing.
+    regions_bf16 (the models' attribute, as regions_bf16_applies takes it): that function's two refusals are raised here, behind the
+    one above and in front of everything else; the layout itself does not change (the models ask regions_bf16_on)."""
     if packed_coatt and img_index is not None and isinstance(img_features, PackedRegions):
         raise VqfError("%s: packed_coatt = True does not take img_index (the co-attention head on the packed rows has one image per "
                        "question); set packed_coatt = False for batches whose questions share images" % who)
+    regions_bf16_applies(who, img_features, img_index, gemm_dtype, regions_bf16)
     img, layout = region_layout(who, img_features, questions, img_index, lambda t: _image_is_data(t, gemm_dtype), _fusion_limits,
                                 gemm_dtype)
     if packed_coatt:
@@ -176,7 +211,7 @@ class _SideStream:
     def __init__(self):
         self.streams = {}
 
-    def project(self, img, conv, bf16, same_stream=False, cu_limit=0):
+    def project(self, img, conv, bf16, same_stream=False, cu_limit=0, pad_k=False):
         dev = img.device
         if same_stream:
             # the projection stays its own autograd node but runs on the caller's stream: created first, its
@@ -185,7 +220,7 @@ class _SideStream:
             if not bf16 and _SideStream.DEFER and img.dtype == torch.float32:
                 # ... and its PRODUCT is issued by join(), behind the question encoder (functions.ImgProjDeferFn)
                 return ("defer", ImgProjDeferFn.apply(img, conv.weight), img, conv.weight), None
-            return ImgProjFn.apply(img, conv.weight, bf16), None
+            return ImgProjFn.apply(img, conv.weight, bf16, pad_k), None
         # a second stream: the product is computed NOW, without an autograd node; join() creates the node late, so that
         # its backward (the weight gradient) is issued early in the backward pass (functions.ImgProjLateFn) and overlaps
         # the question-side backward the way the product overlaps the question-side forward
@@ -195,7 +230,7 @@ class _SideStream:
         cur = torch.cuda.current_stream(dev)
         side.wait_stream(cur)                    # inputs / weights produced on the caller's stream
         with torch.cuda.stream(side), torch.no_grad():
-            P0, img2 = img_project(img, conv.weight, bf16, cu_limit)
+            P0, img2 = img_project(img, conv.weight, bf16, cu_limit, pad_k)
         return (P0, img2, conv.weight, cu_limit), side
 
     DEFER = True       # one-stream form: issue the projection's product behind the question encoder (A/B switch)
@@ -240,16 +275,17 @@ class _DropSeeds:
         return keep, seed, (p if keep is not None else rate)
 
 
-def project_aside(model, img3, bf16_img):
+def project_aside(model, img3, bf16_img, pad_k=False):
     """MFB / MHBCoAtt: start a5 first -- it only needs the image and its weights -- as its own node (model._side: on the side
     stream, or on the caller's for overlap_streams = "same-stream") -> what join_or_fuse takes, or None for projection + fusion in
     one node (ImgFuseFn).  The bf16 modes keep the one node (fuse_bf16_dp): its backward hands dP to the weight-gradient GEMM in
     bf16 without an fp32 round trip, which is worth more than the stream overlap; a real second stream -- overlap_streams is
-    True -- with side_bf16 keeps the bf16 hand-off too (MfbFuseFn takes / returns bf16)."""
+    True -- with side_bf16 keeps the bf16 hand-off too (MfbFuseFn takes / returns bf16).  pad_k: the bf16 projection of a region
+    layout (regions_bf16), whose operands of the weight gradient are zero-padded to K % 32 == 0 rows (functions._img_proj)."""
     ov = model.overlap_streams
     if not ov or (bf16_img and model.fuse_bf16_dp and not (ov is True and model.side_bf16)):
         return None
-    return model._side.project(img3, model.img_conv1d, bf16_img, ov == "same-stream", model.side_cu_limit)
+    return model._side.project(img3, model.img_conv1d, bf16_img, ov == "same-stream", model.side_cu_limit, pad_k)
 
 
 def join_or_fuse(model, proj, img3, qp, drop, bf16_img, N, L, link, layout):
@@ -323,6 +359,13 @@ class MFB(nn.Module):
         # rows is allocated.  Same parameters, same masks, the result of packed_coatt = False up to summation order inside the GEMMs.
         # No effect on a plain tensor, on the pair (img, img_length) or in the pruned mode; refused together with img_index.
         self.packed_coatt = False
+        # True: on a PackedRegions or the pair (img, img_length), without img_index and with gemm_dtype "fp32", img_conv1d and its weight
+        # gradient take bf16 operands with fp32 accumulation, dP is stored in bf16 and so is P where the large-tile bf16 GEMM applies
+        # (gemm_dtype "bf16-img" on the region layouts; parity 3e-2).  The rows are cast per step; everything else -- the question
+        # side, the co-attention head, the pooling, the norms, the masks, the loss -- stays fp32, and the dropout masks are those of
+        # the fp32 form.  No effect on a plain tensor or with any other gemm_dtype; refused together with img_index, and for a
+        # channel count that is no multiple of 8.
+        self.regions_bf16 = False
         # overlap_streams = True only: the persistent image-projection GEMMs use at most this many CUs (a multiple of 8; 0 =
         # all), which leaves the others to the question-side kernels of the main stream (library option gemm_cu_limit)
         self.side_cu_limit = 0
@@ -384,13 +427,20 @@ class MFB(nn.Module):
         real rows as well -- the fusion's output, co_att_conv1's input, hidden layer and gradients, the logits -- and only the
         attention weights keep their (N, 2, L) shape, exact zeros behind each count.  The result is still this model on
         (packed.unpack(), ...), with the dropout masks of the default form.  Together with img_index it raises VqfError; for a plain
-        tensor, the pair (img, img_length) and the pruned mode it changes nothing."""
+        tensor, the pair (img, img_length) and the pruned mode it changes nothing.
+        regions_bf16 = True (an attribute, default False): with gemm_dtype "fp32", a PackedRegions or the pair (img, img_length) and
+        no img_index, img_conv1d and its weight gradient take bf16 operands with fp32 accumulation (the fp32 rows are cast per
+        step), dP is stored in bf16, and so is P where the large-tile bf16 GEMM applies -- gemm_dtype "bf16-img" on the region
+        layouts, within 3e-2 of the fp32 form.  Everything else stays fp32: the question side, the co-attention head, the pooling,
+        the norms, the loss; the dropout masks are those of the fp32 form.  Together with img_index, or with a channel count that is
+        no multiple of 8, it raises VqfError; a plain tensor is not touched, and any other gemm_dtype keeps its meaning."""
         img_features, img3, L, layout = fusion_region_layout("MFB", img_features, questions, img_index, self.gemm_dtype,
-                                                             self.packed_coatt)
-        bf16_img = self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
+                                                             self.packed_coatt, self.regions_bf16 and self.img_conv1d.out_channels)
+        bf16_regions = regions_bf16_on(self.regions_bf16, self.gemm_dtype, layout)
+        bf16_img = bf16_regions or self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
         bf16_all = self.gemm_dtype == "bf16-all"          # also ques_proj*, img_proj*, the question-attention conv
         # a5 starts first where it is its own node; the pruned mode has no projection
-        proj = None if (self.pruned and self.unit_softmax) else project_aside(self, img3, bf16_img)
+        proj = None if (self.pruned and self.unit_softmax) else project_aside(self, img3, bf16_img, bf16_regions)
         # a2: question encoder                                               mfb.py:68-70
         # (the lookup writes (T,N,E) directly when the recursion runs on the HIP path: no transposing copy in between)
         tm = questions.dim() == 2 and hip_batch_lstm_ok(self.lstm, questions.is_cuda and self.word_embedding.weight.dtype == torch.float32,

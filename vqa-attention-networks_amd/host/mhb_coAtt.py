@@ -10,7 +10,7 @@ import torch.nn as nn
 from . import ops
 from .functions import (LinearFn, Linear2Fn, AttHeadFn, FinalMfbFn, LstmSeqFn, LstmBatchFn, LogSoftmaxRowsFn, NormLink, embed_tanh,
                         embed, lstm_out_dropout)
-from .mfb import (_DropSeeds, _image_is_data, _SideStream, _lstm_bf16, batch_first_lstm, warn_once, fusion_region_layout, project_aside,
+from .mfb import (_DropSeeds, _image_is_data, _SideStream, _lstm_bf16, batch_first_lstm, warn_once, fusion_region_layout, regions_bf16_on, project_aside,
                   join_or_fuse)
 
 
@@ -44,6 +44,7 @@ class MHBCoAtt(nn.Module):
         self.fuse_bf16_dp = True          # see MFB.fuse_bf16_dp
         self.fold_norm = True             # see MFB.fold_norm
         self.packed_coatt = False         # see MFB.packed_coatt
+        self.regions_bf16 = False         # see MFB.regions_bf16
         self.side_cu_limit = 0            # see MFB.side_cu_limit
         self.side_bf16 = False            # see MFB.side_bf16
         self._side = _SideStream()
@@ -62,13 +63,19 @@ class MHBCoAtt(nn.Module):
         Packed regions: see MFB.forward -- img_features may be a PackedRegions(rows, offsets, max_regions) (fp32 only): the real
         regions of every image, never padded; the result is this model on (packed.unpack(), ...).
         packed_coatt = True (an attribute, default False): see MFB.forward -- with a PackedRegions and no img_index the co-attention
-        head runs on the R real rows as well; refused (VqfError) together with img_index, no effect on the other call forms."""
+        head runs on the R real rows as well; refused (VqfError) together with img_index, no effect on the other call forms.
+        regions_bf16 = True (an attribute, default False): see MFB.forward -- with gemm_dtype "fp32", a PackedRegions or the pair
+        (img, img_length) and no img_index, img_conv1d and its weight gradient take bf16 operands with fp32 accumulation and dP
+        (and P, where the large-tile bf16 GEMM applies) is stored in bf16; the question side, the co-attention head, the pooling,
+        the norms, the masks and the loss stay fp32.  Refused (VqfError) together with img_index and for a channel count that is
+        no multiple of 8; no effect on a plain tensor."""
         img_features, img3, L, layout = fusion_region_layout("MHBCoAtt", img_features, questions, img_index, self.gemm_dtype,
-                                                             self.packed_coatt)
+                                                             self.packed_coatt, self.regions_bf16 and self.img_conv1d.out_channels)
         N = questions.shape[0]
-        bf16_img = self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
+        bf16_regions = regions_bf16_on(self.regions_bf16, self.gemm_dtype, layout)
+        bf16_img = bf16_regions or self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
         bf16_all = self.gemm_dtype == "bf16-all"          # also ques_proj*, img_proj*, the question-attention conv
-        proj = project_aside(self, img3, bf16_img)
+        proj = project_aside(self, img3, bf16_img, bf16_regions)
         que_embedded = embed_tanh(self.word_embedding, questions)            # (N,T,E)
         if self.cfg.glove:
             assert glove_matrix is not None, 'glove should not be NoneType.'

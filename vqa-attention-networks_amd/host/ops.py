@@ -206,12 +206,25 @@ def _chk_bf16(*ts):
             raise _l.VqfError("bf16 GPU tensor with contiguous rows expected")
 
 
-def cast_bf16(x, pad_to=8):
-    """fp32 (R,C) -> bf16 (R, C rounded up to a multiple of pad_to), zero-padded columns."""
+K_PAD_ROWS = 32      # the large-tile bf16 GEMM takes K % 32 == 0: the row padding of a weight gradient's operands (regions_bf16)
+
+
+def pad_rows(R, to=K_PAD_ROWS):
+    return (R + to - 1) // to * to
+
+
+def cast_bf16(x, pad_to=8, pad_rows_to=None):
+    """fp32 (R,C) -> bf16 (R, C rounded up to a multiple of pad_to), zero-padded columns.
+    pad_rows_to: the result has R rounded up to a multiple of it rows, rows R .. exact zeros (vqf_cast_f32_bf16_rows) -- an operand
+    of a weight gradient whose K = R must be a multiple of 32; where R already is one this is the call without it."""
     _chk(x)
     R, C = x.shape
     Cp = (C + pad_to - 1) // pad_to * pad_to
-    y = torch.empty((R, Cp), dtype=torch.bfloat16, device=x.device)
+    Rp = pad_rows(R, pad_rows_to) if pad_rows_to else R
+    y = torch.empty((Rp, Cp), dtype=torch.bfloat16, device=x.device)
+    if Rp != R:
+        _l.check(_lib().vqf_cast_f32_bf16_rows(_ptr(x), R, C, x.stride(0), _ptr(y), Cp, Rp, _stream()), "vqf_cast_f32_bf16_rows")
+        return y
     _l.check(_lib().vqf_cast_f32_bf16(_ptr(x), R, C, x.stride(0), _ptr(y), Cp, _stream()), "vqf_cast_f32_bf16")
     return y
 
@@ -1209,28 +1222,34 @@ def _chk_roff(name, roff, U):
 
 
 def mfb_fuse_fwd(P, q, N, L, O, keep=None, seed=0, p_drop=0.0, cascade=None, want_zdrop=False, pbias=None,
-                 normalise=True, r_bf16=None, lens=None):
+                 normalise=True, r_bf16=None, lens=None, regions_bf16=False):
     """-> (Y normalised (N*L,O), norm (N), inv (N), zdrop or None).  pbias: projection bias added on load.
     P may be bf16 (written by gemm_bf16(out_bf16=True)).  normalise=False: the first output is R, the signed square roots
     WITHOUT the per-sample 1/norm (no vqf_scale_rows pass: the consumer applies inv in its GEMM epilogue).
     r_bf16 (bf16 P, normalise=False only): a list; it receives a (N*L, O rounded up to 32) bf16 copy of R with zero pad columns,
     written by the same launch (the operand of the consumer's bf16 GEMM).
-    lens (N) int32 (fp32 P, no cascade / zdrop): region counts -- sample n has lens[n] real rows (clamped to [1, L] in the kernel);
-    the padded rows of P are not read, their rows of Y are exact zeros and norm runs over the real rows."""
+    lens (N) int32 (no cascade / zdrop / r_bf16): region counts -- sample n has lens[n] real rows (clamped to [1, L] in the kernel);
+    the padded rows of P are not read, their rows of Y are exact zeros and norm runs over the real rows.  P fp32 -- or, with
+    regions_bf16 (the models' attribute), bf16 (vqf_mfb_fuse_fwd_len_pbf16; P may have more than N*L rows: the K padding of the
+    weight gradient)."""
     (_chk_bf16 if P.dtype == torch.bfloat16 else _chk)(P)
     _chk(q, cascade, pbias)
     dev = P.device
     if lens is not None:
         _chk_lens(lens, N, "mfb_fuse_fwd")
-        if P.dtype != torch.float32 or cascade is not None or want_zdrop or r_bf16 is not None:
-            raise _l.VqfError("mfb_fuse_fwd: lens takes an fp32 P without cascade / zdrop / r_bf16")
+        if (P.dtype != torch.float32 and not regions_bf16) or cascade is not None or want_zdrop or r_bf16 is not None:
+            raise _l.VqfError("mfb_fuse_fwd: lens takes an fp32 P (a bf16 one with regions_bf16) without cascade / zdrop / r_bf16")
     R = torch.empty((N * L, O), dtype=torch.float32, device=dev)
     rowssq = torch.empty(N * L * 4, dtype=torch.float32, device=dev)       # four partial sums per row (one per wave)
     zdrop = torch.empty_like(P) if want_zdrop else None
     if P.dtype == torch.bfloat16:      # the projection itself stored in bf16 (bf16 mode of the image fusion)
         if cascade is not None or want_zdrop:
             raise _l.VqfError("mfb_fuse_fwd: a bf16 P is only available without cascade / zdrop")
-        if r_bf16 is not None and not normalise and (O + 31) // 32 * 32 <= 1024:
+        if lens is not None:
+            _l.check(_lib().vqf_mfb_fuse_fwd_len_pbf16(_ptr(P), _ptr(pbias), _ptr(q), _ptr(lens), _keep_ptr(keep), int(seed),
+                                                       float(p_drop), N, L, O, _ptr(R), _ptr(rowssq), _stream()),
+                     "vqf_mfb_fuse_fwd_len_pbf16")
+        elif r_bf16 is not None and not normalise and (O + 31) // 32 * 32 <= 1024:
             Rb = torch.empty((N * L, (O + 31) // 32 * 32), dtype=torch.bfloat16, device=dev)
             _l.check(_lib().vqf_mfb_fuse_fwd_pbf16_rb(_ptr(P), _ptr(pbias), _ptr(q), _keep_ptr(keep), int(seed), float(p_drop),
                                                       N, L, O, _ptr(R), ctypes.c_void_p(Rb.data_ptr()), Rb.shape[1], _ptr(rowssq),
@@ -1250,19 +1269,21 @@ def mfb_fuse_fwd(P, q, N, L, O, keep=None, seed=0, p_drop=0.0, cascade=None, wan
 
 
 def mfb_fuse_bwd(dY, Y, norm, inv, P, q, N, L, O, keep=None, seed=0, p_drop=0.0, cascade=None,
-                 want_dbias=False, dzdrop=None, pbias=None, dp_bf16=False, lin=None, lens=None):
+                 want_dbias=False, dzdrop=None, pbias=None, dp_bf16=False, lin=None, lens=None, dp_rows=None, regions_bf16=False):
     """-> (dP (N*L,5O) fp32 | bf16, dq (N,5O), dcascade or None, dbiasP or None).
     lin = (dlogits, lin) of the consumer's attention head: the UN-NORMALISED formulation -- Y is R (mfb_fuse_fwd(normalise=
     False)), dY is dYs = dY / norm, and sum(R * dYs) per sample comes from the head's (N*L, G) tensors instead of a
     rowdot pass over the (N*L, O) ones (vqf_l2_norm_bwd_coef_lin).
-    lens (N) int32 (fp32, no cascade / dzdrop), with Y from mfb_fuse_fwd(lens=lens): dY / Y / P are not read on padded rows, whose
-    dP rows are exact zeros; dq and dbiasP sum the real rows."""
+    lens (N) int32 (no cascade / dzdrop), with Y from mfb_fuse_fwd(lens=lens): dY / Y / P are not read on padded rows, whose
+    dP rows are exact zeros; dq and dbiasP sum the real rows.  With regions_bf16 (the models' attribute) and dp_bf16, P fp32 or
+    bf16: dP is bf16 with dp_rows >= N*L rows (default: those of P), exact zeros from row N*L on -- the K padding of the weight
+    gradient (vqf_mfb_fuse_bwd_len_pbf16 / _bf16dp)."""
     (_chk_bf16 if P.dtype == torch.bfloat16 else _chk)(P)
     _chk(dY, Y, norm, inv, q, cascade, dzdrop, pbias)
     if lens is not None:
         _chk_lens(lens, N, "mfb_fuse_bwd")
-        if P.dtype != torch.float32 or dp_bf16 or cascade is not None or dzdrop is not None:
-            raise _l.VqfError("mfb_fuse_bwd: lens takes an fp32 P / dP without cascade / dzdrop")
+        if ((P.dtype != torch.float32 or dp_bf16) and not regions_bf16) or cascade is not None or dzdrop is not None:
+            raise _l.VqfError("mfb_fuse_bwd: lens takes an fp32 P / dP (bf16 ones with regions_bf16) without cascade / dzdrop")
     if P.dtype == torch.bfloat16 and not dp_bf16:
         raise _l.VqfError("mfb_fuse_bwd: a bf16 P comes with a bf16 dP")
     dev = P.device
@@ -1273,6 +1294,14 @@ def mfb_fuse_bwd(dY, Y, norm, inv, P, q, N, L, O, keep=None, seed=0, p_drop=0.0,
     if dp_bf16:                       # bf16 mode of the image fusion: dP goes straight to the wgrad GEMM
         if cascade is not None or dzdrop is not None:
             raise _l.VqfError("mfb_fuse_bwd: bf16 dP is only available without cascade / dzdrop")
+        if lens is not None:
+            rows = max(P.shape[0], N * L) if dp_rows is None else int(dp_rows)
+            dP = torch.empty((rows, P.shape[1]), dtype=torch.bfloat16, device=dev)
+            fn = "vqf_mfb_fuse_bwd_len_pbf16" if P.dtype == torch.bfloat16 else "vqf_mfb_fuse_bwd_len_bf16dp"
+            _l.check(getattr(_lib(), fn)(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q), _ptr(lens),
+                                         _keep_ptr(keep), int(seed), float(p_drop), N, L, O, _ptr(dP), rows, _ptr(dq), _ptr(db),
+                                         _ptr(ws), ws.numel(), _stream()), fn)
+            return dP, dq, None, db
         dP = torch.empty(P.shape, dtype=torch.bfloat16, device=dev)
         if P.dtype == torch.bfloat16:
             _l.check(_lib().vqf_mfb_fuse_bwd_pbf16(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias),
@@ -1384,10 +1413,18 @@ def mfb_fuse_packed_supported(N, U, R, L, O):
     return bool(_lib().vqf_mfb_fuse_packed_supported(int(N), int(U), int(R), int(L), int(O)))
 
 
-def _packed_operands(name, P, q, roff, N, U, L, O, pbias):
-    _chk(P, q, pbias)
-    R = P.shape[0] if P.dim() == 2 else 0
-    if P.dim() != 2 or R < 1 or P.shape[1] != POOL_K * O or tuple(q.shape) != (N, POOL_K * O) or \
+def _packed_operands(name, P, q, roff, N, U, L, O, pbias, R=None, regions_bf16=False):
+    """-> R, the real rows of P: P.shape[0], or the R given where P (bf16) has more rows behind them (the K padding of the weight
+    gradient).  regions_bf16: a bf16 P is taken (the un-grouped forms' vqf_mfb_fuse_*_packed*_pbf16)."""
+    if regions_bf16 and P.dtype == torch.bfloat16:
+        _chk_bf16(P)
+        if not P.is_contiguous():
+            raise _l.VqfError(name + ": contiguous tensor expected")
+    else:
+        _chk(P)
+    _chk(q, pbias)
+    R = (P.shape[0] if P.dim() == 2 else 0) if R is None else int(R)
+    if P.dim() != 2 or R < 1 or R > P.shape[0] or P.shape[1] != POOL_K * O or tuple(q.shape) != (N, POOL_K * O) or \
             (pbias is not None and tuple(pbias.shape) != (POOL_K * O,)):
         raise _l.VqfError("%s: P must be a contiguous (R, 5*O) tensor with R >= 1, q (N, 5*O) and pbias (5*O,); got P %s, q %s"
                           % (name, tuple(P.shape), tuple(q.shape)))
@@ -1398,18 +1435,41 @@ def _packed_operands(name, P, q, roff, N, U, L, O, pbias):
     return R
 
 
-def mfb_fuse_fwd_packed(P, q, roff, N, L, O, idx=None, keep=None, seed=0, p_drop=0.0, pbias=None, normalise=True):
+def _fuse_bwd_packed_bf16(entry, dY, Y, inv, cA, cB, P, pbias, q, roff, keep, seed, p_drop, N, R, L, O, dp_rows, dq, db):
+    """The bf16-dP call of mfb_fuse_bwd_packed / _packed_rows (entry + "_pbf16" beside a bf16 P, "_bf16dp" beside an fp32 one)
+    -> (dP bf16 (dp_rows, 5*O) with exact zero rows behind the R real ones, dq, db)"""
+    rows = P.shape[0] if dp_rows is None else int(dp_rows)
+    dP = torch.empty((rows, P.shape[1]), dtype=torch.bfloat16, device=P.device)
+    ws = workspace(P.device, _lib().vqf_mfb_fuse_bwd_ws_bytes(N, L, O))
+    fn = entry + ("_pbf16" if P.dtype == torch.bfloat16 else "_bf16dp")
+    _l.check(getattr(_lib(), fn)(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q), _ptr(roff),
+                                 _keep_ptr(keep), int(seed), float(p_drop), N, R, L, O, _ptr(dP), rows, _ptr(dq), _ptr(db), _ptr(ws),
+                                 ws.numel(), _stream()), fn)
+    return dP, dq, db
+
+
+def _no_bf16_grouped(name, P, grouped):
+    if grouped and P.dtype == torch.bfloat16:
+        raise _l.VqfError(name + ": a bf16 P / dP is un-grouped only (the grouped fusion kernels are fp32)")
+
+
+def mfb_fuse_fwd_packed(P, q, roff, N, L, O, idx=None, keep=None, seed=0, p_drop=0.0, pbias=None, normalise=True, R=None,
+                        regions_bf16=False):
     """The image fusion on packed rows: P (R, 5*O) fp32, q (N, 5*O), roff (N + 1) int32 -- with idx (N) int32: (U + 1), question n
     reads the rows of image idx[n]; keep (N*L, 5*O) / the Philox draw stay in the padded coordinates
-    -> (Y (N*L, O), norm (N), inv (N)): the bits of mfb_fuse_fwd(lens=) / mfb_fuse_fwd_grouped(lens=) on the zero-padded copy of P."""
+    -> (Y (N*L, O), norm (N), inv (N)): the bits of mfb_fuse_fwd(lens=) / mfb_fuse_fwd_grouped(lens=) on the zero-padded copy of P.
+    regions_bf16 (the models' attribute; without idx): P may be bf16 (vqf_mfb_fuse_fwd_packed_pbf16) and hold more than the R real
+    rows given."""
     U = N if idx is None else roff.shape[0] - 1
-    R = _packed_operands("mfb_fuse_fwd_packed", P, q, roff, N, U, L, O, pbias)
+    _no_bf16_grouped("mfb_fuse_fwd_packed", P, idx is not None)
+    R = _packed_operands("mfb_fuse_fwd_packed", P, q, roff, N, U, L, O, pbias, R, regions_bf16)
     dev = P.device
     Y = torch.empty((N * L, O), dtype=torch.float32, device=dev)
     rowssq = torch.empty(N * L * 4, dtype=torch.float32, device=dev)
     if idx is None:
-        _l.check(_lib().vqf_mfb_fuse_fwd_packed(_ptr(P), _ptr(pbias), _ptr(q), _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop),
-                                                N, R, L, O, _ptr(Y), _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_packed")
+        fn = "vqf_mfb_fuse_fwd_packed_pbf16" if P.dtype == torch.bfloat16 else "vqf_mfb_fuse_fwd_packed"
+        _l.check(getattr(_lib(), fn)(_ptr(P), _ptr(pbias), _ptr(q), _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop),
+                                     N, R, L, O, _ptr(Y), _ptr(rowssq), _stream()), fn)
     else:
         _chk_group("mfb_fuse_fwd_packed", N, U, idx=idx)
         _l.check(_lib().vqf_mfb_fuse_fwd_grouped_packed(_ptr(P), _ptr(pbias), _ptr(q), _ptr(idx), _ptr(roff), _keep_ptr(keep), int(seed),
@@ -1419,19 +1479,27 @@ def mfb_fuse_fwd_packed(P, q, roff, N, L, O, idx=None, keep=None, seed=0, p_drop
 
 
 def mfb_fuse_bwd_packed(dY, Y, norm, inv, P, q, roff, N, L, O, grp=None, keep=None, seed=0, p_drop=0.0, want_dbias=False, pbias=None,
-                        lin=None):
+                        lin=None, dp_bf16=False, R=None, dp_rows=None, regions_bf16=False):
     """-> (dP (R, 5*O), dq (N, 5*O), dbiasP or None).  grp = (idx, order, grp_off): roff is per image and dP sums each image's
-    questions in `order` (zero rows for an image without a question).  lin as in mfb_fuse_bwd."""
+    questions in `order` (zero rows for an image without a question).  lin as in mfb_fuse_bwd.
+    regions_bf16 (the models' attribute) with dp_bf16 (without grp; P fp32 or bf16, of which R rows are real): dP is bf16 with dp_rows >= R rows (default: those of P), exact
+    zeros from row R on -- the K padding of the weight gradient (vqf_mfb_fuse_bwd_packed_pbf16 / _bf16dp)."""
     U = N if grp is None else roff.shape[0] - 1
-    R = _packed_operands("mfb_fuse_bwd_packed", P, q, roff, N, U, L, O, pbias)
+    _no_bf16_grouped("mfb_fuse_bwd_packed", P, grp is not None)
+    R = _packed_operands("mfb_fuse_bwd_packed", P, q, roff, N, U, L, O, pbias, R, regions_bf16)
     _chk(dY, Y, norm, inv)
     if tuple(dY.shape) != (N * L, O) or tuple(Y.shape) != (N * L, O):
         raise _l.VqfError("mfb_fuse_bwd_packed: dY and Y must be (N*L, O)")
+    if (dp_bf16 and (grp is not None or not regions_bf16)) or (P.dtype == torch.bfloat16 and not dp_bf16):
+        raise _l.VqfError("mfb_fuse_bwd_packed: a bf16 dP needs regions_bf16 and no grp, and a bf16 P comes with a bf16 dP")
     dev = P.device
     cA, cB, inv = _l2_norm_bwd_coefs(dY, Y, norm, inv, N, L, O, lin)
-    dP = torch.empty_like(P)
     dq = torch.empty((N, POOL_K * O), dtype=torch.float32, device=dev)
     db = torch.empty(POOL_K * O, dtype=torch.float32, device=dev) if want_dbias else None
+    if dp_bf16:
+        return _fuse_bwd_packed_bf16("vqf_mfb_fuse_bwd_packed", dY, Y, inv, cA, cB, P, pbias, q, roff, keep, seed, p_drop, N, R, L, O,
+                                     dp_rows, dq, db)
+    dP = torch.empty_like(P)
     if grp is None:
         ws = workspace(dev, _lib().vqf_mfb_fuse_bwd_ws_bytes(N, L, O))
         _l.check(_lib().vqf_mfb_fuse_bwd_packed(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
@@ -1558,16 +1626,19 @@ def l2_norm_bwd_coef_lin_packed(dlogits, lin, roff, norm, inv, N, L):
     return cA, cB, unit
 
 
-def mfb_fuse_fwd_packed_rows(P, q, roff, N, L, O, keep=None, seed=0, p_drop=0.0, pbias=None, normalise=True):
+def mfb_fuse_fwd_packed_rows(P, q, roff, N, L, O, keep=None, seed=0, p_drop=0.0, pbias=None, normalise=True, R=None,
+                             regions_bf16=False):
     """mfb_fuse_fwd_packed with the output on the packed rows: P (R, 5*O), q (N, 5*O), roff (N + 1) int32; keep (N*L, 5*O) / the Philox
     draw stay in the padded coordinates -> (Y (R, O), norm (N), inv (N), rowinv (R)): the real rows of mfb_fuse_fwd_packed's Y, bit
-    for bit; nothing of N*L rows is allocated.  rowinv[r] = inv of row r's sample (the consumers' per-row scale)."""
-    R = _packed_operands("mfb_fuse_fwd_packed_rows", P, q, roff, N, N, L, O, pbias)
+    for bit; nothing of N*L rows is allocated.  rowinv[r] = inv of row r's sample (the consumers' per-row scale).
+    regions_bf16: P may be bf16 (vqf_mfb_fuse_fwd_packed_rows_pbf16) and hold more than the R real rows given."""
+    R = _packed_operands("mfb_fuse_fwd_packed_rows", P, q, roff, N, N, L, O, pbias, R, regions_bf16)
     dev = P.device
     Y = torch.empty((R, O), dtype=torch.float32, device=dev)
     rowssq = torch.empty(R * 4, dtype=torch.float32, device=dev)
-    _l.check(_lib().vqf_mfb_fuse_fwd_packed_rows(_ptr(P), _ptr(pbias), _ptr(q), _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop),
-                                                 N, R, L, O, _ptr(Y), _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_packed_rows")
+    fn = "vqf_mfb_fuse_fwd_packed_rows_pbf16" if P.dtype == torch.bfloat16 else "vqf_mfb_fuse_fwd_packed_rows"
+    _l.check(getattr(_lib(), fn)(_ptr(P), _ptr(pbias), _ptr(q), _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop),
+                                 N, R, L, O, _ptr(Y), _ptr(rowssq), _stream()), fn)
     norm, inv, rowinv = l2_group_norm_packed(rowssq, roff, N, R, L)
     if normalise:
         _l.check(_lib().vqf_scale_rows(_ptr(Y), _ptr(rowinv), R, 1, O, _ptr(Y), _stream()), "vqf_scale_rows")
@@ -1575,10 +1646,12 @@ def mfb_fuse_fwd_packed_rows(P, q, roff, N, L, O, keep=None, seed=0, p_drop=0.0,
 
 
 def mfb_fuse_bwd_packed_rows(dY, Y, norm, inv, P, q, roff, N, L, O, keep=None, seed=0, p_drop=0.0, want_dbias=False, pbias=None,
-                             lin=None):
+                             lin=None, dp_bf16=False, R=None, dp_rows=None, regions_bf16=False):
     """mfb_fuse_bwd_packed with dY / Y (R, O) on the packed rows (and lin = (dlogits, lin) (R, G)) -> (dP (R, 5*O), dq (N, 5*O),
-    dbiasP or None)."""
-    R = _packed_operands("mfb_fuse_bwd_packed_rows", P, q, roff, N, N, L, O, pbias)
+    dbiasP or None); regions_bf16 / dp_bf16 / R / dp_rows as there (vqf_mfb_fuse_bwd_packed_rows_pbf16 / _bf16dp)."""
+    R = _packed_operands("mfb_fuse_bwd_packed_rows", P, q, roff, N, N, L, O, pbias, R, regions_bf16)
+    if (dp_bf16 and not regions_bf16) or (P.dtype == torch.bfloat16 and not dp_bf16):
+        raise _l.VqfError("mfb_fuse_bwd_packed_rows: a bf16 dP needs regions_bf16, and a bf16 P comes with a bf16 dP")
     _chk(dY, Y, norm, inv)
     if tuple(dY.shape) != (R, O) or tuple(Y.shape) != (R, O):
         raise _l.VqfError("mfb_fuse_bwd_packed_rows: dY and Y must be (R, O) = (%d, %d)" % (R, O))
@@ -1589,9 +1662,12 @@ def mfb_fuse_bwd_packed_rows(dY, Y, norm, inv, P, q, roff, N, L, O, keep=None, s
         rowdot = torch.empty(R, dtype=torch.float32, device=dev)
         _l.check(_lib().vqf_rowdot(_ptr(Y), _ptr(dY), R, O, _ptr(rowdot), _stream()), "vqf_rowdot")
         cA, cB = l2_norm_bwd_coef_packed(rowdot, roff, norm, inv, N, L)
-    dP = torch.empty_like(P)
     dq = torch.empty((N, POOL_K * O), dtype=torch.float32, device=dev)
     db = torch.empty(POOL_K * O, dtype=torch.float32, device=dev) if want_dbias else None
+    if dp_bf16:
+        return _fuse_bwd_packed_bf16("vqf_mfb_fuse_bwd_packed_rows", dY, Y, inv, cA, cB, P, pbias, q, roff, keep, seed, p_drop, N, R, L,
+                                     O, dp_rows, dq, db)
+    dP = torch.empty_like(P)
     ws = workspace(dev, _lib().vqf_mfb_fuse_bwd_ws_bytes(N, L, O))
     _l.check(_lib().vqf_mfb_fuse_bwd_packed_rows(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
                                                  _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop), N, R, L, O, _ptr(dP), _ptr(dq),
