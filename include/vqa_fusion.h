@@ -567,6 +567,26 @@ int vqf_mfb_fuse_bwd_packed_rows_bf16dp(const float* dY, const float* Y, const f
                                         float* dbiasP, void* ws, size_t ws_bytes, void* stream);
 int vqf_cast_f32_bf16_rows(const float* x, int R, int C, int ldx, void* y, int ldy, int y_rows, void* stream);
 
+/* The bf16 co-attention head on the same call forms (MFB / MHBCoAtt with regions_bf16_coatt = True beside regions_bf16; additions
+ * within ABI 7): vqf_mfb_fuse_fwd_{len,packed,packed_rows}_pbf16 with the bf16 copy of R that vqf_mfb_fuse_fwd_pbf16_rb writes on a
+ * plain tensor -- the A operand of co_att_conv1's bf16 GEMM and the B operand of its weight gradient, from the registers that hold R,
+ * without a cast pass.  R_bf16 is (rb_rows, ldrb) bf16 in R's own row coordinates: rows = N*L for len / packed, R for packed_rows;
+ * rb_rows >= rows is its allocated row count (the weight gradient's K, rounded up to 32 by the caller), ldrb >= O rounded up to 32,
+ * ldrb % 4 == 0, ldrb <= 1024.  Element (r, c < O) is the round-to-nearest-even of the fp32 R[r, c] the same launch stores; columns
+ * O .. ldrb - 1, every row behind a count (len / packed) and rows `rows` .. rb_rows - 1 (a memset behind the launch) are exact zeros
+ * (+0.0).  R and rowssq have the bits of the forms without _rb; with every count equal to L the len form gives
+ * vqf_mfb_fuse_fwd_pbf16_rb's bits.  Errors as the forms without _rb, and: R_bf16 null, ldrb below the padded width or outside the
+ * bounds above, rb_rows < rows: VQF_E_BADARG; R_bf16 not 16-byte aligned: VQF_E_ALIGN -- all before anything is launched. */
+int vqf_mfb_fuse_fwd_len_pbf16_rb(const void* P_bf16, const float* pbias, const float* q, const int* lens, const uint8_t* keep,
+                                  uint64_t seed, float p_drop, int N, int L, int O, float* R, void* R_bf16, int ldrb, int rb_rows,
+                                  float* rowssq, void* stream);
+int vqf_mfb_fuse_fwd_packed_pbf16_rb(const void* P_bf16, const float* pbias, const float* q, const int* roff, const uint8_t* keep,
+                                     uint64_t seed, float p_drop, int N, int R, int L, int O, float* Rout, void* R_bf16, int ldrb,
+                                     int rb_rows, float* rowssq, void* stream);
+int vqf_mfb_fuse_fwd_packed_rows_pbf16_rb(const void* P_bf16, const float* pbias, const float* q, const int* roff, const uint8_t* keep,
+                                          uint64_t seed, float p_drop, int N, int R, int L, int O, float* Rout, void* R_bf16, int ldrb,
+                                          int rb_rows, float* rowssq, void* stream);
+
 
 /* --------------------------------------------------------------------------
  * Element-wise stages of HieCoAtten / AttentionNet.  n % 4 == 0, 16-byte aligned pointers.

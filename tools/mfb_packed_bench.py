@@ -1,7 +1,7 @@
 """Packed region features (forward(PackedRegions, ...)): what the MFB train step costs when the loader never pads.
 
     python tools/mfb_packed_bench.py [--batch 512] [--regions 100] [--steps 6] [--warmup 3] [--rounds 2]
-                                     [--forms packed-rows-bf16,packed-bf16,packed-rows,packed,pair,plain]
+                                     [--forms packed-rows-bf16-coatt,packed-bf16-coatt,packed-rows-bf16,packed-bf16,packed-rows,packed,pair,plain]
                                      [--out profiles/mfb_packed_bench.txt]
 
 Setup: N = --batch, L = --regions, D = 2048, the counts of tools/mfb_regions_bench.py (uniform in 10 .. L, seed 1), MFB with the
@@ -13,6 +13,8 @@ the rows the projection runs on and rows / (N L).
   packed-rows   the same call with model.packed_coatt = True: the fusion's output and the co-attention head on the R rows as well
   packed-bf16 / packed-rows-bf16   those two with model.regions_bf16 = True: img_conv1d and its weight gradient with bf16 operands,
            P and dP stored in bf16 (the rows are cast per step); everything else fp32
+  packed-bf16-coatt / packed-rows-bf16-coatt   those two with model.regions_bf16_coatt = True as well: co_att_conv1's forward, input
+           gradient and weight gradient with bf16 operands too (the fusion kernel's own bf16 copy of R, the hidden gradient stored in bf16)
   pair     forward((img (N, L, D), img_length), q): the same batch, zero-padded
   plain    forward(img, q): the padded tensor without counts (a different result: every padded row counts as a region)
 --forms pair,plain uses nothing the packed form added: the same file run from a checkout of the commit before it gives the
@@ -20,7 +22,8 @@ yardstick (and, run twice, the run-to-run spread) those two forms have to stay i
 The two projection launches come from a kernel trace in a run of its own (one form per run, e.g. --forms packed --rounds 1).
 After the windows: the peak of torch's allocator over one step of each form (above what is allocated before the step), and, with
 both packed forms named, the largest difference of their logits on the timed batch in eval mode (summation order inside the GEMMs);
-with packed and packed-bf16 named, the same for those two (bf16 rounding of the projection's operands and of P).
+with packed and packed-bf16 named, the same for those two (bf16 rounding of the projection's operands and of P); with packed-bf16 and
+packed-bf16-coatt named, for those two (bf16 rounding of co_att_conv1's operands).
 """
 import argparse
 import os
@@ -49,7 +52,8 @@ def main():
     a = ap.parse_args()
     N, L, dev = a.batch, a.regions, "cuda:0"
     forms = a.forms.split(",")
-    assert forms and all(f in ("packed-rows-bf16", "packed-bf16", "packed-rows", "packed", "pair", "plain") for f in forms)
+    assert forms and all(f in ("packed-rows-bf16-coatt", "packed-bf16-coatt", "packed-rows-bf16", "packed-bf16", "packed-rows", "packed",
+                               "pair", "plain") for f in forms)
     lines = []
 
     def say(s=""):
@@ -77,7 +81,7 @@ def main():
     valid = torch.arange(L)[None, :] < counts[:, None]
     img = (torch.rand(N, L, D, generator=g) * valid[:, :, None]).to(dev)               # zero-padded, as pad_region_features makes it
     feats = {"pair": (img, counts.to(dev)), "plain": img}
-    packed_forms = ("packed", "packed-rows", "packed-bf16", "packed-rows-bf16")
+    packed_forms = ("packed", "packed-rows", "packed-bf16", "packed-rows-bf16", "packed-bf16-coatt", "packed-rows-bf16-coatt")
     rows_of = {"pair": N * L, "plain": N * L, **{f: R for f in packed_forms}}
     if any(f in forms for f in packed_forms):
         off = torch.zeros(N + 1, dtype=torch.int64)
@@ -88,7 +92,8 @@ def main():
 
     def step(f):
         model.packed_coatt = f.startswith("packed-rows")
-        model.regions_bf16 = f.endswith("-bf16")
+        model.regions_bf16 = "-bf16" in f
+        model.regions_bf16_coatt = f.endswith("-coatt")
         opt.zero_grad(set_to_none=True)
         crit(model(feats[f], ids), target).backward()
         opt.step()
@@ -108,12 +113,12 @@ def main():
             torch.cuda.synchronize()
             w[f].append(t0.elapsed_time(t1) / a.steps)
     say()
-    say("%-16s  ms/step median (spread)   windows                      projection rows   rows / (N L)" % "form")
+    say("%-22s  ms/step median (spread)   windows                      projection rows   rows / (N L)" % "form")
     med = {}
     for f in forms:
         s = sorted(w[f])
         med[f] = 0.5 * (s[(len(s) - 1) // 2] + s[len(s) // 2])
-        say("%-16s  %9.3f (%.3f)          %-28s %9d        %.3f" % (f, med[f], s[-1] - s[0], " ".join("%.3f" % x for x in w[f]), rows_of[f],
+        say("%-22s  %9.3f (%.3f)          %-28s %9d        %.3f" % (f, med[f], s[-1] - s[0], " ".join("%.3f" % x for x in w[f]), rows_of[f],
                                                                    rows_of[f] / (N * L)))
     if "packed" in med and "pair" in med:
         say("packed / pair = %.3f" % (med["packed"] / med["pair"]))
@@ -125,6 +130,11 @@ def main():
             say("%s-bf16 / %s = %.3f (%.3f ms / step less), per round: %s"
                 % (f, f, med[f + "-bf16"] / med[f], med[f] - med[f + "-bf16"],
                    " ".join("%.3f" % (y - x) for x, y in zip(w[f + "-bf16"], w[f]))))
+    for f in ("packed-bf16", "packed-rows-bf16"):
+        if f in med and f + "-coatt" in med:
+            say("%s-coatt / %s = %.3f (%.3f ms / step less), per round: %s"
+                % (f, f, med[f + "-coatt"] / med[f], med[f] - med[f + "-coatt"],
+                   " ".join("%.3f" % (y - x) for x, y in zip(w[f + "-coatt"], w[f]))))
     say()
     for f in forms:                                   # the allocator's peak over one step, above what the step starts from
         opt.zero_grad(set_to_none=True)
@@ -133,7 +143,7 @@ def main():
         base = torch.cuda.memory_allocated()
         step(f)
         torch.cuda.synchronize()
-        say("%-16s  peak memory of one step above its start: %.1f MB" % (f, (torch.cuda.max_memory_allocated() - base) / 1e6))
+        say("%-22s  peak memory of one step above its start: %.1f MB" % (f, (torch.cuda.max_memory_allocated() - base) / 1e6))
     if "packed-rows" in forms and "packed" in forms:
         model.eval()
         with torch.no_grad():
@@ -150,6 +160,15 @@ def main():
             model.regions_bf16 = True
             o1 = model(feats["packed"], ids)
         say("logits, eval mode: max |packed-bf16 - packed| / max |packed| = %.2e" % float((o1 - o0).abs().max() / o0.abs().max()))
+    if "packed-bf16-coatt" in forms and "packed-bf16" in forms:
+        model.eval()
+        with torch.no_grad():
+            model.packed_coatt, model.regions_bf16, model.regions_bf16_coatt = False, True, False
+            o0 = model(feats["packed"], ids)
+            model.regions_bf16_coatt = True
+            o1 = model(feats["packed"], ids)
+        say("logits, eval mode: max |packed-bf16-coatt - packed-bf16| / max |packed-bf16| = %.2e"
+            % float((o1 - o0).abs().max() / o0.abs().max()))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

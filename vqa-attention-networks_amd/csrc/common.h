@@ -181,7 +181,8 @@ struct VqfRegions {
 // arrays) -- a bf16 P in the forward, a bf16 dP beside a bf16 (p_bf16) or an fp32 P in the backward.  The launch functions of the
 // entry points in fusion_regions_bf16.hip; everything else is checked as in the fp32 forms.
 int vqf_fuse_fwd_regions_bf16(const void* P_bf16, const float* pbias, const float* q, const uint8_t* keep, uint64_t seed, float p_drop,
-                              int N, int L, int O, float* R, float* rowssq, void* stream, const VqfRegions& rg);
+                              int N, int L, int O, float* R, float* rowssq, void* stream, const VqfRegions& rg,
+                              void* R_bf16 = nullptr, int ldrb = 0);
 int vqf_fuse_bwd_regions_bf16(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB, const void* P,
                               int p_bf16, const float* pbias, const float* q, const uint8_t* keep, uint64_t seed, float p_drop, int N,
                               int L, int O, void* dP_bf16, float* dq, float* dbiasP, void* ws, size_t ws_bytes, void* stream,

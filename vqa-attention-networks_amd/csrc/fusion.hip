@@ -216,7 +216,10 @@ __device__ __forceinline__ void keep_scale20(const uint8_t* __restrict__ keep, u
 // stores R row start + l and its four partials there, and there is no padded row to zero.  keep / the Philox index stay at n L + l.
 // (The output row is spelled `PROWS ? prow : row` at each use: as a named value declared at the top of the row loop it changed the
 // VGPR counts of the instantiations that existed, 164 -> 160 and 166 -> 162 in the COAL = 0 forms.)
-template <typename PT, int COAL, bool GRP = false, bool LEN = false, bool PACK = false, bool PROWS = false>
+// RBL (vqf_mfb_fuse_fwd_{len,packed,packed_rows}_pbf16_rb; with LEN, un-grouped, bf16 P, Rb given): the bf16 copy of R on a region
+// layout, in R's own row coordinates -- row start + l with PROWS, n L + l otherwise, where the rows behind the count get zero Rb rows
+// beside their zero R rows.  A compile-time flag, so that the instantiations without it keep their code.
+template <typename PT, int COAL, bool GRP = false, bool LEN = false, bool PACK = false, bool PROWS = false, bool RBL = false>
 __global__ void __launch_bounds__(256)
 mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
                     const float* __restrict__ q,
@@ -297,10 +300,10 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
         __bf16 rb[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) rb[j] = (__bf16)r[j];
-        *reinterpret_cast<uint2*>(Rb + row * ldrb + TPT * tid) = *reinterpret_cast<const uint2*>(rb);
+        *reinterpret_cast<uint2*>(Rb + ((RBL && PROWS) ? prow : row) * ldrb + TPT * tid) = *reinterpret_cast<const uint2*>(rb);
       }
     } else if (Rb && TPT * tid < ldrb) {
-      *reinterpret_cast<uint2*>(Rb + row * ldrb + TPT * tid) = make_uint2(0u, 0u);
+      *reinterpret_cast<uint2*>(Rb + ((RBL && PROWS) ? prow : row) * ldrb + TPT * tid) = make_uint2(0u, 0u);
     }
     ssq = wave_sum(ssq);
 #if VQF_FUSE_ROWBAR
@@ -319,10 +322,12 @@ mfb_fuse_fwd_kernel(const PT* __restrict__ P, const float* __restrict__ pbias,
 #endif
   }
   if (LEN && !PROWS) {
-    // the padded rows of this block: nothing read, exact zeros through the stores of the walk (the LEN forms have no zdrop / Rb)
+    // the padded rows of this block: nothing read, exact zeros through the stores of the walk (the LEN forms have no zdrop; RBL: the
+    // whole pitch of the Rb row, pad columns included)
     for (; l < L; l += LS) {
       const long long row = (long long)n * L + l;
       if (act) *reinterpret_cast<f32x4*>(R + row * O + TPT * tid) = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (RBL && TPT * tid < ldrb) *reinterpret_cast<uint2*>(Rb + row * ldrb + TPT * tid) = make_uint2(0u, 0u);
 #if VQF_FUSE_ROWBAR
       if (tid < 4) rowssq[4 * row + tid] = 0.f;
 #else
@@ -562,15 +567,15 @@ int pick_ls_image(int U, int L) {
 // ---- launches: the run-time switches become template arguments, each kernel's argument list is written once ---------------------
 // The operands of a launch after the checks; where the image rows are comes in a VqfRegions (common.h), host-side only.  Every
 // function below names the instantiations it can reach, so none exists that nobody launches: the grouped layouts are fp32 only (no bf16
-// with GRP; the un-grouped LEN / PACK / PROWS forms take a bf16 P and / or a bf16 dP too), PROWS only un-grouped, CASC only in the plain form, and the question-owned grouped pass has no DBIAS.
+// with GRP; the un-grouped LEN / PACK / PROWS forms take a bf16 P -- with the bf16 copy of R: RBL -- and / or a bf16 dP too), PROWS only un-grouped, CASC only in the plain form, and the question-owned grouped pass has no DBIAS.
 struct FuseFwd {
   const void* P; const float *pbias, *q, *cascade; const uint8_t* keep; uint64_t seed; uint32_t thr; float inv_keep;
   int N, L, O, LS; float *R, *rowssq, *zdrop; unsigned short* Rb; int ldrb; hipStream_t s;
 };
 
-template <typename PT, int COAL, bool GRP = false, bool LEN = false, bool PACK = false, bool PROWS = false>
+template <typename PT, int COAL, bool GRP = false, bool LEN = false, bool PACK = false, bool PROWS = false, bool RBL = false>
 void fuse_fwd_go(const FuseFwd& a, const VqfRegions& rg) {
-  VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<PT, COAL, GRP, LEN, PACK, PROWS>), dim3(a.N, a.LS), dim3(256), 0, a.s,
+  VQF_LAUNCH(KID_MFB_FUSE_FWD, (mfb_fuse_fwd_kernel<PT, COAL, GRP, LEN, PACK, PROWS, RBL>), dim3(a.N, a.LS), dim3(256), 0, a.s,
              (const PT*)a.P, a.pbias, a.q, a.cascade, a.keep, a.seed, a.thr, a.inv_keep, a.L, a.O, a.LS, a.R, a.rowssq, a.zdrop, a.Rb,
              a.ldrb, rg.idx, rg.U, rg.walk(), rg.Rtot);
 }
@@ -585,6 +590,11 @@ void fuse_fwd_layout(const FuseFwd& a, const VqfRegions& rg) {
     if (rg.counted()) return fuse_fwd_go<float, COAL, false, true>(a, rg);
     if (rg.grouped()) return fuse_fwd_go<float, COAL, true>(a, rg);
   } else {                                                                                           // bf16 P: the un-grouped layouts
+    if (a.Rb) {                                                                                      // ... with the bf16 copy of R
+      if (rg.packed() && rg.rows) return fuse_fwd_go<__bf16, COAL, false, true, true, true, true>(a, rg);
+      if (rg.packed()) return fuse_fwd_go<__bf16, COAL, false, true, true, false, true>(a, rg);
+      if (rg.counted()) return fuse_fwd_go<__bf16, COAL, false, true, false, false, true>(a, rg);
+    }
     if (rg.packed() && rg.rows) return fuse_fwd_go<__bf16, COAL, false, true, true, true>(a, rg);
     if (rg.packed()) return fuse_fwd_go<__bf16, COAL, false, true, true>(a, rg);
     if (rg.counted()) return fuse_fwd_go<__bf16, COAL, false, true>(a, rg);
@@ -748,11 +758,13 @@ static int fuse_bwd_regions(const float* dY, const float* Y, const float* inv, c
 }
 
 // The bf16 forms of the un-grouped layouts (common.h; their entry points and argument checks live in fusion_regions_bf16.hip): a
-// bf16 P in the forward; a bf16 dP beside a bf16 or an fp32 P in the backward.  rg: counted, packed or packed rows, checked there.
+// bf16 P in the forward (R_bf16 / ldrb: the bf16 copy of R in R's rows, or null); a bf16 dP beside a bf16 or an fp32 P in the
+// backward.  rg: counted, packed or packed rows, checked there.
 int vqf_fuse_fwd_regions_bf16(const void* P_bf16, const float* pbias, const float* q, const uint8_t* keep, uint64_t seed, float p_drop,
-                              int N, int L, int O, float* R, float* rowssq, void* stream, const VqfRegions& rg) {
+                              int N, int L, int O, float* R, float* rowssq, void* stream, const VqfRegions& rg, void* R_bf16,
+                              int ldrb) {
   if (rg.grouped() || !(rg.counted() || rg.packed())) return VQF_E_BADARG;
-  return fuse_fwd_impl(P_bf16, 1, pbias, q, nullptr, keep, seed, p_drop, N, L, O, R, rowssq, nullptr, stream, nullptr, 0, rg);
+  return fuse_fwd_impl(P_bf16, 1, pbias, q, nullptr, keep, seed, p_drop, N, L, O, R, rowssq, nullptr, stream, R_bf16, ldrb, rg);
 }
 
 int vqf_fuse_bwd_regions_bf16(const float* dY, const float* Y, const float* inv, const float* coefA, const float* coefB, const void* P,

@@ -79,11 +79,15 @@ class NormLink:
     sum(Y * dY) per sample.  Saves the scale_rows pass (forward) and the rowdot pass (backward) over the (N*L, 1000)
     tensors.  One link per forward call; only valid while the producer's output has exactly this one consumer.
     Where the producer's output holds the packed rows (RegionLayout.rows) the scale is per ROW: inv is rowinv (R,) -- 1/norm of each
-    row's sample, written by vqf_l2_group_norm_packed -- and L is 1; the consumer's calls do not change."""
-    __slots__ = ("inv", "L", "lin", "xb")
+    row's sample, written by vqf_l2_group_norm_packed -- and L is 1; the consumer's calls do not change.
+    want_xb: the consumer's request for the producer's bf16 copy of R on a REGION layout (the models' regions_bf16_coatt: the head
+    behind the link runs in bf16).  On a plain tensor a bf16 P always leaves the copy; on a region layout only when asked, so that
+    regions_bf16 alone keeps its launches."""
+    __slots__ = ("inv", "L", "lin", "xb", "want_xb")
 
-    def __init__(self):
+    def __init__(self, want_xb=False):
         self.inv, self.L, self.lin, self.xb = None, 0, None, None    # xb: the producer's bf16 copy of R (K padded to 32), bf16 modes
+        self.want_xb = bool(want_xb)
 
 
 class _Dense:
@@ -99,8 +103,9 @@ class _Dense:
     def __init__(self, bf16, dims=()):
         self.bf16 = bool(bf16) and _bf16_ok(*dims)
 
-    def operand(self, t, pad_to=8):
-        return ops.cast_bf16(t, pad_to) if (self.bf16 and t.dtype != torch.bfloat16) else t
+    def operand(self, t, pad_to=8, pad_rows_to=None):
+        """pad_rows_to: the rows zero-padded as well (ops.cast_bf16): an operand of a weight gradient whose K is a region layout's row count"""
+        return ops.cast_bf16(t, pad_to, pad_rows_to) if (self.bf16 and t.dtype != torch.bfloat16) else t
 
     def fwd(self, x, w, bias=None, relu=False, scale=None, **kw):
         """scale: (rowscale, rows per scale), the epilogue of the head behind a NormLink"""
@@ -212,20 +217,22 @@ class JoinRowsFn(torch.autograd.Function):
 def _fuse_fwd(P, q, layout, N, L, O, link, **kw):
     """The MFB fusion over the regions (ops.mfb_fuse_fwd / _grouped / _packed / _packed_rows; kw: keep, seed, p_drop, pbias)
     -> (Y, norm, inv, rb, (scale, rows per scale)): with a link Y is R without 1/norm, rb holds the bf16 copy of R a bf16 P's kernel
-    wrote beside it, and the last pair is what the link's consumer scales Y's rows by -- (inv, L), or (rowinv, 1) where Y holds
-    the packed rows (layout.rows)."""
+    wrote beside it (on a region layout only where the link asks for it, want_xb: ops.pad_rows(rows of Y) rows, zero behind the real
+    ones), and the last pair is what the link's consumer scales Y's rows by -- (inv, L), or (rowinv, 1) where Y holds the packed rows
+    (layout.rows)."""
     if layout is not None and P.dtype == torch.bfloat16:                  # un-grouped (the nodes refuse bf16 with shared images)
         kw["regions_bf16"] = True
+    rb = [] if (link is not None and P.dtype == torch.bfloat16 and (layout is None or (link.want_xb and not layout.grouped))) else None
     if layout is not None and layout.rows:
-        Y, norm, inv, rowinv = ops.mfb_fuse_fwd_packed_rows(P, q, layout.roff, N, L, O, normalise=link is None, R=layout.R, **kw)
-        return Y, norm, inv, None, (rowinv, 1)
+        Y, norm, inv, rowinv = ops.mfb_fuse_fwd_packed_rows(P, q, layout.roff, N, L, O, normalise=link is None, R=layout.R,
+                                                            **(kw if rb is None else dict(kw, r_bf16=rb)))
+        return Y, norm, inv, rb, (rowinv, 1)
     if layout is not None and layout.packed:
         return ops.mfb_fuse_fwd_packed(P, q, layout.roff, N, L, O, idx=layout.idx, normalise=link is None, R=layout.R,
-                                       **kw) + (None, None)
+                                       **(kw if rb is None else dict(kw, r_bf16=rb))) + (rb, None)
     if layout is not None and layout.grouped:
         return ops.mfb_fuse_fwd_grouped(P, q, layout.idx, N, layout.U, L, O, normalise=link is None,
                                         lens=(layout.lens_q, layout.lens_u) if layout.counted else None, **kw) + (None, None)
-    rb = [] if (link is not None and P.dtype == torch.bfloat16 and layout is None) else None   # (no bf16 copy of R with counts)
     Y, norm, inv, _ = ops.mfb_fuse_fwd(P, q, N, L, O, normalise=link is None, r_bf16=rb,
                                        lens=None if layout is None else layout.lens_q, **kw)
     return Y, norm, inv, rb, None
@@ -327,7 +334,10 @@ class AttHeadFn(torch.autograd.Function):
         epilogue and returns ONE gradient (for feat; None for x) instead of leaving two for autograd to add.  Never inferred
         from pointers: an alias with a different autograd history must keep its own gradient.
     layout: None (the question head; the plain image tensor), or the grouping.RegionLayout of the image head -- fp32 feat that is
-        data (no gradient), never the MLP's own source.  Shared images: feat is (U, S, C), x stays (N*S, Cin) per question, and
+        data (no gradient), never the MLP's own source; bf16 (the models' regions_bf16_coatt) only where no images are shared: the
+        first layer's three products then run as on a plain tensor, but both bf16 operands of its weight gradient -- x and d1 --
+        have ops.pad_rows(rows) rows, exact zeros behind the real ones (K % 32 == 0: _img_proj / _img_wgrad's rule), while the
+        forward and dx keep M = the real rows.  Shared images: feat is (U, S, C), x stays (N*S, Cin) per question, and
         question n pools the rows of image idx[n] (under unit_softmax the per-image region sums, gathered).  Region counts: the
         softmax runs over the first lens_q[n] positions (unit_softmax: weight 1 there), the weights beyond are exact zeros and so
         are their dlogits, so the MLP's backward adds nothing for padded rows.  Packed rows: feat is (R, C), the real rows of every
@@ -343,10 +353,10 @@ class AttHeadFn(torch.autograd.Function):
         feat = _c(feat)
         ctx.same_src = bool(same_src)
         ctx.layout = layout
-        if layout is not None and (bool(bf16) or ctx.same_src or feat.dtype != torch.float32 or ctx.needs_input_grad[1]
-                                   or feat.dim() != (2 if layout.packed else 3)):
-            raise ops._l.VqfError("AttHeadFn: a region layout (shared images, region counts, packed rows) is fp32 only, for a feature "
-                                  "tensor that is data -- (R, C) when packed -- and never the MLP's own source")
+        if layout is not None and ((bool(bf16) and layout.grouped) or ctx.same_src or feat.dtype != torch.float32
+                                   or ctx.needs_input_grad[1] or feat.dim() != (2 if layout.packed else 3)):
+            raise ops._l.VqfError("AttHeadFn: a region layout (shared images, region counts, packed rows) is fp32 only where images are "
+                                  "shared, for an fp32 feature tensor that is data -- (R, C) when packed -- and never the MLP's own source")
         if ctx.same_src and (x.numel() != feat.numel() or x.shape[-1] != feat.shape[-1] or x.dtype != feat.dtype):
             raise ops._l.VqfError("AttHeadFn: same_src needs x = feat.view(N*S, C)")
         ctx.link = link = link if (link is not None and link.inv is not None) else None
@@ -357,6 +367,8 @@ class AttHeadFn(torch.autograd.Function):
         w1_2 = _w2d(w1)
         d = _Dense(bf16, dims=w1_2.shape)
         ctx.bf16 = d.bf16
+        rows = x.shape[0]
+        ctx.pad = pad = ops.K_PAD_ROWS if (d.bf16 and layout is not None) else None    # the row padding of the weight gradient's operands
         hid2 = lin = None
         if link is not None:
             # x is the UN-NORMALISED fusion output: 1/norm of the sample (link.inv) rides in the conv GEMM's epilogue, and the logit
@@ -365,12 +377,12 @@ class AttHeadFn(torch.autograd.Function):
             w1o = d.operand(w1_2, 32)
             if d.bf16:
                 xb, link.xb = link.xb, None
-                x = xb if (xb is not None and xb.shape == (x.shape[0], w1o.shape[1])) else d.operand(x, 32)
-            hid1 = d.fwd(x, w1o, b1, True, scale=(link.inv, link.L), **({"K": x.shape[1]} if d.bf16 else {}))
+                x = xb if (xb is not None and xb.shape == (ops.pad_rows(rows) if pad else rows, w1o.shape[1])) else d.operand(x, 32, pad)
+            hid1 = d.fwd(x, w1o, b1, True, scale=(link.inv, link.L), **({"K": x.shape[1], "M": rows} if d.bf16 else {}))
             logits, lin = ops.att_logits_fwd_lin(hid1, _w2d(w2), b2, b1)
         else:
-            x, w1o = d.operand(x, 32), d.operand(w1_2, 32)      # the backward only needs the operand
-            hid1 = d.fwd(x, w1o, b1, True, **({"K": x.shape[1]} if d.bf16 else {}))
+            x, w1o = d.operand(x, 32, pad), d.operand(w1_2, 32)      # the backward only needs the operand
+            hid1 = d.fwd(x, w1o, b1, True, **({"K": x.shape[1], "M": rows} if d.bf16 else {}))
             hid2 = ops.gemm(hid1, _w2d(wm), bias=bm, relu=True) if wm is not None else None
             logits = ops.att_logits_fwd(hid2 if hid2 is not None else hid1, _w2d(w2), b2)
         wts, pooled = _pool_fwd(feat, logits, unit_softmax, layout)
@@ -390,7 +402,8 @@ class AttHeadFn(torch.autograd.Function):
             link = ctx.link
             obf = d.bf16 and hid1.shape[1] % 8 == 0 and w2.shape[0] == 2          # the kernel stores bf16 rows itself: no cast launch
             d1, dw2, db2, db1 = ops.att_logits_bwd(dlogits, hid1, _w2d(w2), relu_mask=True, rowscale=link.inv,
-                                                   rows_per_scale=link.L, out_bf16=obf)   # stored rows already times 1/norm
+                                                   rows_per_scale=link.L, out_bf16=obf,   # stored rows already times 1/norm
+                                                   pad_rows_to=ctx.pad if obf else None)
             link.lin = (dlogits, lin)                                               # -> sum(Y * dY) in the producer's backward
         elif hid2 is not None:
             dm, dw2, db2, dbm = ops.att_logits_bwd(dlogits, hid2, _w2d(w2), relu_mask=True)
@@ -399,14 +412,14 @@ class AttHeadFn(torch.autograd.Function):
         else:
             d1, dw2, db2, db1 = ops.att_logits_bwd(dlogits, hid1, _w2d(w2), relu_mask=True)
         # the first layer: dw1 = d1^T x and dx = d1 w1 (with a link d1 carries 1/norm, so dx = dY / norm)
-        d1 = d.operand(d1)
+        d1 = d.operand(d1, 8, ctx.pad)
         dw1 = d.dw(d1, x, w1)
         w1o = w1b if d.bf16 else _w2d(w1)
         dx = None
         if ctx.same_src and dfeat is not None and ctx.link is None and not d.bf16:
             d.dx(d1, w1o, out=dfeat.view(x.shape), accumulate=True)     # dfeat += dx: one gradient for the shared source
         elif ctx.needs_input_grad[0]:
-            dx = d.dx(d1, w1o, **({"N": w1[0].numel()} if d.bf16 else {}))
+            dx = d.dx(d1, w1o, **({"N": w1[0].numel(), "M": hid1.shape[0]} if d.bf16 else {}))
         return dx, dfeat, dw1, db1, dwm, dbm, dw2.view_as(w2), db2, None, None, None, None, None
 
 

@@ -201,6 +201,13 @@ SIGNATURES = {
     "vqf_mfb_fuse_bwd_packed_rows_bf16dp": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float,
                                                   c_i, c_i, c_i, c_i, c_p, c_i, c_f, c_f, c_p, c_sz, c_p]),
     "vqf_cast_f32_bf16_rows": (c_i, [c_f, c_i, c_i, c_i, c_p, c_i, c_i, c_p]),
+    # ... with the bf16 copy of R (regions_bf16_coatt): R_bf16, its pitch and its allocated rows behind R
+    "vqf_mfb_fuse_fwd_len_pbf16_rb": (c_i, [c_p, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_f, c_p, c_i, c_i, c_f,
+                                            c_p]),
+    "vqf_mfb_fuse_fwd_packed_pbf16_rb": (c_i, [c_p, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_p, c_i, c_i,
+                                               c_f, c_p]),
+    "vqf_mfb_fuse_fwd_packed_rows_pbf16_rb": (c_i, [c_p, c_f, c_f, c_p, c_p, c_u64, ctypes.c_float, c_i, c_i, c_i, c_i, c_f, c_p, c_i,
+                                                    c_i, c_f, c_p]),
     "vqf_l2_group_norm_packed": (c_i, [c_f, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_p]),
     "vqf_l2_norm_bwd_coef_packed": (c_i, [c_f, c_p, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_p]),
     "vqf_l2_norm_bwd_coef_lin_packed": (c_i, [c_f, c_f, c_i, c_p, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_p]),

@@ -141,6 +141,21 @@ def regions_bf16_on(regions_bf16, gemm_dtype, layout):
         (layout.packed or layout.counted)
 
 
+def regions_bf16_coatt_check(who, img_features, img_index, gemm_dtype, regions_bf16, regions_bf16_coatt):
+    """The models' regions_bf16_coatt attribute on one call, in front of fusion_region_layout (regions_bf16: as regions_bf16_applies
+    takes it, whose own refusals speak first, with their texts).  The attribute rides on regions_bf16: on a region form -- a
+    PackedRegions or the pair (img, img_length) with counts -- where regions_bf16 does not apply (it is False, or gemm_dtype is not
+    "fp32") the call is refused here, before anything looks at a device, instead of running the head in fp32 behind the user's
+    back.  A plain tensor is not touched, and without the attribute nothing is looked at."""
+    if not regions_bf16_coatt or regions_bf16_applies(who, img_features, img_index, gemm_dtype, regions_bf16):
+        return
+    if isinstance(img_features, PackedRegions) or (isinstance(img_features, (tuple, list)) and len(img_features) == 2
+                                                   and img_features[1] is not None):
+        raise VqfError("%s: regions_bf16_coatt = True needs regions_bf16 = True and gemm_dtype \"fp32\" on a PackedRegions or the pair "
+                       "(img, img_length): the bf16 co-attention head on a region layout runs behind the bf16 image projection "
+                       "only; set regions_bf16 = True, or regions_bf16_coatt = False" % who)
+
+
 def fusion_region_layout(who, img_features, questions, img_index, gemm_dtype, packed_coatt=False, regions_bf16=False):
     """MFB / MHBCoAtt's call of region_layout -> (img (U, L, D) or rows (R, D), the 3-D tensor the projection nodes flatten -- rows
     as (1, R, D) --, L, the nodes' layout: None for the plain tensor, whose path takes nothing extra).
@@ -366,6 +381,13 @@ class MFB(nn.Module):
         # the fp32 form.  No effect on a plain tensor or with any other gemm_dtype; refused together with img_index, and for a
         # channel count that is no multiple of 8.
         self.regions_bf16 = False
+        # True (with regions_bf16 = True, on the calls where that one takes effect): co_att_conv1's three products -- the forward, dx =
+        # d1 W1 and dW1 = d1^T x -- take bf16 operands with fp32 accumulation too, exactly as gemm_dtype "bf16-att" runs them on a
+        # plain tensor: the 1/norm row scale in the GEMM epilogue, the fusion kernel's own bf16 copy of R as the operand, the hidden
+        # gradient stored in bf16.  The multilayer conv, the logits, the softmax, the pooling, the norms, biases, ReLU and every
+        # reduction stay fp32; masks and parameters do not change.  On a region form where regions_bf16 does not apply (it is False,
+        # or another gemm_dtype) the call raises VqfError; no effect on a plain tensor or in the pruned mode.
+        self.regions_bf16_coatt = False
         # overlap_streams = True only: the persistent image-projection GEMMs use at most this many CUs (a multiple of 8; 0 =
         # all), which leaves the others to the question-side kernels of the main stream (library option gemm_cu_limit)
         self.side_cu_limit = 0
@@ -433,10 +455,21 @@ class MFB(nn.Module):
         step), dP is stored in bf16, and so is P where the large-tile bf16 GEMM applies -- gemm_dtype "bf16-img" on the region
         layouts, within 3e-2 of the fp32 form.  Everything else stays fp32: the question side, the co-attention head, the pooling,
         the norms, the loss; the dropout masks are those of the fp32 form.  Together with img_index, or with a channel count that is
-        no multiple of 8, it raises VqfError; a plain tensor is not touched, and any other gemm_dtype keeps its meaning."""
+        no multiple of 8, it raises VqfError; a plain tensor is not touched, and any other gemm_dtype keeps its meaning.
+        regions_bf16_coatt = True (an attribute, default False): on exactly the calls where regions_bf16 takes effect, co_att_conv1's
+        forward, input gradient and weight gradient take bf16 operands with fp32 accumulation as well, as gemm_dtype "bf16-att" runs
+        them on a plain tensor (within 3e-2 of regions_bf16 alone).  The multilayer conv, the logits, the masked softmax, the
+        pooling, the norms, the question side, the final blocks and the loss stay fp32; masks, parameters and the (N, 2, L)
+        attention weights with exact zeros behind each count do not change.  On a PackedRegions or a pair (img, img_length) where
+        regions_bf16 does not apply -- regions_bf16 = False, or a gemm_dtype other than "fp32" -- it raises VqfError before the first
+        launch (no silent fp32 head); a plain tensor and the pruned mode are not touched."""
+        coatt_regions = bool(self.regions_bf16_coatt) and not (self.pruned and self.unit_softmax)
+        regions_bf16_coatt_check("MFB", img_features, img_index, self.gemm_dtype, self.regions_bf16 and self.img_conv1d.out_channels,
+                                 coatt_regions)
         img_features, img3, L, layout = fusion_region_layout("MFB", img_features, questions, img_index, self.gemm_dtype,
                                                              self.packed_coatt, self.regions_bf16 and self.img_conv1d.out_channels)
         bf16_regions = regions_bf16_on(self.regions_bf16, self.gemm_dtype, layout)
+        coatt_regions = coatt_regions and bf16_regions
         bf16_img = bf16_regions or self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
         bf16_all = self.gemm_dtype == "bf16-all"          # also ques_proj*, img_proj*, the question-attention conv
         # a5 starts first where it is its own node; the pruned mode has no projection
@@ -461,8 +494,8 @@ class MFB(nn.Module):
         qp = LinearFn.apply(qa, self.ques_proj1.weight, self.ques_proj1.bias, False, bf16_all)
         # a5+a6: image projection + MFB fusion over the regions             mfb.py:95-106
         pm = self.dropout_m.p
-        coatt_bf16 = self.gemm_dtype in ("bf16", "bf16-att", "bf16-all")
-        link = NormLink() if (self.fold_norm and not self.multilayer) else None
+        coatt_bf16 = coatt_regions or self.gemm_dtype in ("bf16", "bf16-att", "bf16-all")
+        link = NormLink(want_xb=coatt_regions) if (self.fold_norm and not self.multilayer) else None
         Y = join_or_fuse(self, proj, img3, qp, self._seeds.draw('m1', self.training, pm), bf16_img, N, L, link, layout)
         # a7+a8: co-attention over the regions                               mfb.py:109-123
         # (with a link Y is the un-normalised R and 1/norm rides in co_att_conv1's GEMM epilogue)

@@ -10,8 +10,8 @@ import torch.nn as nn
 from . import ops
 from .functions import (LinearFn, Linear2Fn, AttHeadFn, FinalMfbFn, LstmSeqFn, LstmBatchFn, LogSoftmaxRowsFn, NormLink, embed_tanh,
                         embed, lstm_out_dropout)
-from .mfb import (_DropSeeds, _image_is_data, _SideStream, _lstm_bf16, batch_first_lstm, warn_once, fusion_region_layout, regions_bf16_on, project_aside,
-                  join_or_fuse)
+from .mfb import (_DropSeeds, _image_is_data, _SideStream, _lstm_bf16, batch_first_lstm, warn_once, fusion_region_layout, regions_bf16_on,
+                  regions_bf16_coatt_check, project_aside, join_or_fuse)
 
 
 class MHBCoAtt(nn.Module):
@@ -45,6 +45,7 @@ class MHBCoAtt(nn.Module):
         self.fold_norm = True             # see MFB.fold_norm
         self.packed_coatt = False         # see MFB.packed_coatt
         self.regions_bf16 = False         # see MFB.regions_bf16
+        self.regions_bf16_coatt = False   # see MFB.regions_bf16_coatt
         self.side_cu_limit = 0            # see MFB.side_cu_limit
         self.side_bf16 = False            # see MFB.side_bf16
         self._side = _SideStream()
@@ -68,11 +69,20 @@ class MHBCoAtt(nn.Module):
         (img, img_length) and no img_index, img_conv1d and its weight gradient take bf16 operands with fp32 accumulation and dP
         (and P, where the large-tile bf16 GEMM applies) is stored in bf16; the question side, the co-attention head, the pooling,
         the norms, the masks and the loss stay fp32.  Refused (VqfError) together with img_index and for a channel count that is
-        no multiple of 8; no effect on a plain tensor."""
+        no multiple of 8; no effect on a plain tensor.
+        regions_bf16_coatt = True (an attribute, default False): see MFB.forward -- on exactly the calls where regions_bf16 takes
+        effect, co_att_conv1's forward, input gradient and weight gradient take bf16 operands with fp32 accumulation too, as
+        gemm_dtype "bf16-att" runs them on a plain tensor; everything else stays as under regions_bf16.  Refused (VqfError, before
+        the first launch) on a PackedRegions or a pair (img, img_length) where regions_bf16 does not apply (regions_bf16 = False, or
+        a gemm_dtype other than "fp32"); no effect on a plain tensor."""
+        coatt_regions = bool(self.regions_bf16_coatt)
+        regions_bf16_coatt_check("MHBCoAtt", img_features, img_index, self.gemm_dtype,
+                                 self.regions_bf16 and self.img_conv1d.out_channels, coatt_regions)
         img_features, img3, L, layout = fusion_region_layout("MHBCoAtt", img_features, questions, img_index, self.gemm_dtype,
                                                              self.packed_coatt, self.regions_bf16 and self.img_conv1d.out_channels)
         N = questions.shape[0]
         bf16_regions = regions_bf16_on(self.regions_bf16, self.gemm_dtype, layout)
+        coatt_regions = coatt_regions and bf16_regions
         bf16_img = bf16_regions or self.gemm_dtype in ("bf16", "bf16-img", "bf16-all")
         bf16_all = self.gemm_dtype == "bf16-all"          # also ques_proj*, img_proj*, the question-attention conv
         proj = project_aside(self, img3, bf16_img, bf16_regions)
@@ -107,8 +117,8 @@ class MHBCoAtt(nn.Module):
                              self.ques_att_conv2.weight, self.ques_att_conv2.bias, False, bf16_all, None, True)
         qp = LinearFn.apply(qa, self.ques_proj1.weight, self.ques_proj1.bias, False, bf16_all)
         pm = self.dropout_m.p
-        coatt_bf16 = self.gemm_dtype in ("bf16", "bf16-att", "bf16-all")
-        link = NormLink() if self.fold_norm else None
+        coatt_bf16 = coatt_regions or self.gemm_dtype in ("bf16", "bf16-att", "bf16-all")
+        link = NormLink(want_xb=coatt_regions) if self.fold_norm else None
         Y = join_or_fuse(self, proj, img3, qp, self._seeds.draw('m1', self.training, pm), bf16_img, N, L, link, layout)
         va = AttHeadFn.apply(Y, img_features, self.co_att_conv1.weight, self.co_att_conv1.bias, None, None,
                              self.co_att_conv2.weight, self.co_att_conv2.bias, False, coatt_bf16, link, False, layout)

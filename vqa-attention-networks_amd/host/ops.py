@@ -260,14 +260,17 @@ def gemm_bf16(a, b, ta=False, tb=False, bias=None, relu=False, M=None, N=None, K
     return out
 
 
-def gemm_bf16_rowscale(a, b, rowscale, rows_per_scale, bias=None, relu=False, K=None):
-    """gemm_rowscale with bf16 operands: C fp32 = relu?(rowscale[m // rows_per_scale] * (a @ b^T) + bias), a (M, >=K), b (N, >=K)"""
+def gemm_bf16_rowscale(a, b, rowscale, rows_per_scale, bias=None, relu=False, K=None, M=None):
+    """gemm_rowscale with bf16 operands: C fp32 = relu?(rowscale[m // rows_per_scale] * (a @ b^T) + bias), a (>=M, >=K), b (N, >=K)
+    (M: the real rows of an a whose row count is padded, a weight gradient's K)"""
     _chk_bf16(a, b)
     _chk(rowscale, bias)
-    M, N = a.shape[0], b.shape[0]
+    N = b.shape[0]
+    if M is None:
+        M = a.shape[0]
     if K is None:
         K = a.shape[1]
-    if b.shape[1] < K or a.shape[1] < K or rowscale.numel() * rows_per_scale < M:
+    if b.shape[1] < K or a.shape[1] < K or a.shape[0] < M or M < 1 or rowscale.numel() * rows_per_scale < M:
         raise _l.VqfError("gemm_bf16_rowscale: shape mismatch")
     out = torch.empty((M, N), dtype=torch.float32, device=a.device)
     _l.check(_lib().vqf_gemm_bf16_rowscale(0, 0, M, N, K, _ptr(a), a.stride(0), _ptr(b), b.stride(0), _ptr(out), N, _ptr(bias),
@@ -351,9 +354,11 @@ def att_logits_fwd_lin(hid, w2, b2, b1):
     return out, lin
 
 
-def att_logits_bwd(dlogits, hid, w2, relu_mask=True, rowscale=None, rows_per_scale=1, out_bf16=False):
+def att_logits_bwd(dlogits, hid, w2, relu_mask=True, rowscale=None, rows_per_scale=1, out_bf16=False, pad_rows_to=None):
     """rowscale (per row group of rows_per_scale rows): the stored dhid_pre is scaled by it, the bias sums are not.
-    out_bf16 (two glimpses, through the ReLU, Hh % 8 == 0): dhid_pre is stored as bf16 (the operand of the bf16 gradient GEMMs)."""
+    out_bf16 (two glimpses, through the ReLU, Hh % 8 == 0): dhid_pre is stored as bf16 (the operand of the bf16 gradient GEMMs).
+    pad_rows_to (out_bf16 only): dhid_pre has M rounded up to a multiple of it rows, exact zeros behind the M the kernel writes (the
+    K padding of the layer's weight gradient on a region layout, as cast_bf16(pad_rows_to=))."""
     _chk(dlogits, hid, w2, rowscale)
     M, Hh = hid.shape
     G = w2.shape[0]
@@ -364,7 +369,9 @@ def att_logits_bwd(dlogits, hid, w2, relu_mask=True, rowscale=None, rows_per_sca
     if out_bf16:
         if not relu_mask or G != 2 or Hh % 8:
             raise _l.VqfError("att_logits_bwd: bf16 output needs the two-glimpse head through its ReLU and Hh % 8 == 0")
-        dpre = torch.empty((M, Hh), dtype=torch.bfloat16, device=hid.device)
+        dpre = torch.empty((pad_rows(M, pad_rows_to) if pad_rows_to else M, Hh), dtype=torch.bfloat16, device=hid.device)
+        if dpre.shape[0] != M:
+            dpre[M:].zero_()
         _l.check(_lib().vqf_att_logits_bwd_rowscale_obf16(_ptr(dlogits), _ptr(hid), _ptr(w2), _ptr(rowscale), int(rows_per_scale),
                                                           M, Hh, G, ctypes.c_void_p(dpre.data_ptr()), _ptr(dw2), _ptr(db2), _ptr(db1),
                                                           _ptr(ws), ws.numel(), _stream()), "vqf_att_logits_bwd_rowscale_obf16")
@@ -1221,6 +1228,16 @@ def _chk_roff(name, roff, U):
         raise _l.VqfError("%s: roff must be a contiguous (%d,) int32 GPU tensor of row offsets" % (name, U + 1))
 
 
+def _rb_alloc(rows, O, dev):
+    """the bf16 copy of R of the region forms' _rb kernels: (pad_rows(rows), O rounded up to 32), written whole by the call"""
+    return torch.empty((pad_rows(rows), (O + 31) // 32 * 32), dtype=torch.bfloat16, device=dev)
+
+
+def _rb_packed_ok(name, P, r_bf16, normalise, grouped=False):
+    if r_bf16 is not None and (P.dtype != torch.bfloat16 or normalise or grouped):
+        raise _l.VqfError(name + ": r_bf16 needs a bf16 P, normalise=False and no idx")
+
+
 def mfb_fuse_fwd(P, q, N, L, O, keep=None, seed=0, p_drop=0.0, cascade=None, want_zdrop=False, pbias=None,
                  normalise=True, r_bf16=None, lens=None, regions_bf16=False):
     """-> (Y normalised (N*L,O), norm (N), inv (N), zdrop or None).  pbias: projection bias added on load.
@@ -1228,24 +1245,33 @@ def mfb_fuse_fwd(P, q, N, L, O, keep=None, seed=0, p_drop=0.0, cascade=None, wan
     WITHOUT the per-sample 1/norm (no vqf_scale_rows pass: the consumer applies inv in its GEMM epilogue).
     r_bf16 (bf16 P, normalise=False only): a list; it receives a (N*L, O rounded up to 32) bf16 copy of R with zero pad columns,
     written by the same launch (the operand of the consumer's bf16 GEMM).
-    lens (N) int32 (no cascade / zdrop / r_bf16): region counts -- sample n has lens[n] real rows (clamped to [1, L] in the kernel);
+    lens (N) int32 (no cascade / zdrop; r_bf16 only beside a bf16 P): region counts -- sample n has lens[n] real rows (clamped to [1, L] in the kernel);
     the padded rows of P are not read, their rows of Y are exact zeros and norm runs over the real rows.  P fp32 -- or, with
     regions_bf16 (the models' attribute), bf16 (vqf_mfb_fuse_fwd_len_pbf16; P may have more than N*L rows: the K padding of the
-    weight gradient)."""
+    weight gradient).  With r_bf16 too (regions_bf16_coatt; normalise=False) the copy has pad_rows(N*L) rows: zero rows behind each
+    count and behind N*L (vqf_mfb_fuse_fwd_len_pbf16_rb)."""
     (_chk_bf16 if P.dtype == torch.bfloat16 else _chk)(P)
     _chk(q, cascade, pbias)
     dev = P.device
     if lens is not None:
         _chk_lens(lens, N, "mfb_fuse_fwd")
-        if (P.dtype != torch.float32 and not regions_bf16) or cascade is not None or want_zdrop or r_bf16 is not None:
-            raise _l.VqfError("mfb_fuse_fwd: lens takes an fp32 P (a bf16 one with regions_bf16) without cascade / zdrop / r_bf16")
+        if (P.dtype != torch.float32 and not regions_bf16) or cascade is not None or want_zdrop or \
+                (r_bf16 is not None and (P.dtype != torch.bfloat16 or normalise)):
+            raise _l.VqfError("mfb_fuse_fwd: lens takes an fp32 P (a bf16 one with regions_bf16) without cascade / zdrop, and r_bf16 "
+                              "only beside a bf16 P with normalise=False")
     R = torch.empty((N * L, O), dtype=torch.float32, device=dev)
     rowssq = torch.empty(N * L * 4, dtype=torch.float32, device=dev)       # four partial sums per row (one per wave)
     zdrop = torch.empty_like(P) if want_zdrop else None
     if P.dtype == torch.bfloat16:      # the projection itself stored in bf16 (bf16 mode of the image fusion)
         if cascade is not None or want_zdrop:
             raise _l.VqfError("mfb_fuse_fwd: a bf16 P is only available without cascade / zdrop")
-        if lens is not None:
+        if lens is not None and r_bf16 is not None:
+            Rb = _rb_alloc(N * L, O, dev)
+            _l.check(_lib().vqf_mfb_fuse_fwd_len_pbf16_rb(_ptr(P), _ptr(pbias), _ptr(q), _ptr(lens), _keep_ptr(keep), int(seed),
+                                                          float(p_drop), N, L, O, _ptr(R), _ptr(Rb), Rb.shape[1], Rb.shape[0],
+                                                          _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_len_pbf16_rb")
+            r_bf16.append(Rb)
+        elif lens is not None:
             _l.check(_lib().vqf_mfb_fuse_fwd_len_pbf16(_ptr(P), _ptr(pbias), _ptr(q), _ptr(lens), _keep_ptr(keep), int(seed),
                                                        float(p_drop), N, L, O, _ptr(R), _ptr(rowssq), _stream()),
                      "vqf_mfb_fuse_fwd_len_pbf16")
@@ -1454,19 +1480,27 @@ def _no_bf16_grouped(name, P, grouped):
 
 
 def mfb_fuse_fwd_packed(P, q, roff, N, L, O, idx=None, keep=None, seed=0, p_drop=0.0, pbias=None, normalise=True, R=None,
-                        regions_bf16=False):
+                        regions_bf16=False, r_bf16=None):
     """The image fusion on packed rows: P (R, 5*O) fp32, q (N, 5*O), roff (N + 1) int32 -- with idx (N) int32: (U + 1), question n
     reads the rows of image idx[n]; keep (N*L, 5*O) / the Philox draw stay in the padded coordinates
     -> (Y (N*L, O), norm (N), inv (N)): the bits of mfb_fuse_fwd(lens=) / mfb_fuse_fwd_grouped(lens=) on the zero-padded copy of P.
     regions_bf16 (the models' attribute; without idx): P may be bf16 (vqf_mfb_fuse_fwd_packed_pbf16) and hold more than the R real
-    rows given."""
+    rows given.  r_bf16 (a list; bf16 P, normalise=False, no idx): it receives the (pad_rows(N*L), O rounded up to 32) bf16 copy of
+    Y the same launch wrote, zero rows behind each count and behind N*L (vqf_mfb_fuse_fwd_packed_pbf16_rb)."""
     U = N if idx is None else roff.shape[0] - 1
     _no_bf16_grouped("mfb_fuse_fwd_packed", P, idx is not None)
+    _rb_packed_ok("mfb_fuse_fwd_packed", P, r_bf16, normalise, idx is not None)
     R = _packed_operands("mfb_fuse_fwd_packed", P, q, roff, N, U, L, O, pbias, R, regions_bf16)
     dev = P.device
     Y = torch.empty((N * L, O), dtype=torch.float32, device=dev)
     rowssq = torch.empty(N * L * 4, dtype=torch.float32, device=dev)
-    if idx is None:
+    if r_bf16 is not None:
+        Rb = _rb_alloc(N * L, O, dev)
+        _l.check(_lib().vqf_mfb_fuse_fwd_packed_pbf16_rb(_ptr(P), _ptr(pbias), _ptr(q), _ptr(roff), _keep_ptr(keep), int(seed),
+                                                         float(p_drop), N, R, L, O, _ptr(Y), _ptr(Rb), Rb.shape[1], Rb.shape[0],
+                                                         _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_packed_pbf16_rb")
+        r_bf16.append(Rb)
+    elif idx is None:
         fn = "vqf_mfb_fuse_fwd_packed_pbf16" if P.dtype == torch.bfloat16 else "vqf_mfb_fuse_fwd_packed"
         _l.check(getattr(_lib(), fn)(_ptr(P), _ptr(pbias), _ptr(q), _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop),
                                      N, R, L, O, _ptr(Y), _ptr(rowssq), _stream()), fn)
@@ -1627,18 +1661,28 @@ def l2_norm_bwd_coef_lin_packed(dlogits, lin, roff, norm, inv, N, L):
 
 
 def mfb_fuse_fwd_packed_rows(P, q, roff, N, L, O, keep=None, seed=0, p_drop=0.0, pbias=None, normalise=True, R=None,
-                             regions_bf16=False):
+                             regions_bf16=False, r_bf16=None):
     """mfb_fuse_fwd_packed with the output on the packed rows: P (R, 5*O), q (N, 5*O), roff (N + 1) int32; keep (N*L, 5*O) / the Philox
     draw stay in the padded coordinates -> (Y (R, O), norm (N), inv (N), rowinv (R)): the real rows of mfb_fuse_fwd_packed's Y, bit
     for bit; nothing of N*L rows is allocated.  rowinv[r] = inv of row r's sample (the consumers' per-row scale).
-    regions_bf16: P may be bf16 (vqf_mfb_fuse_fwd_packed_rows_pbf16) and hold more than the R real rows given."""
+    regions_bf16: P may be bf16 (vqf_mfb_fuse_fwd_packed_rows_pbf16) and hold more than the R real rows given.  r_bf16 (a list; bf16
+    P, normalise=False): it receives the (pad_rows(R), O rounded up to 32) bf16 copy of Y the same launch wrote, zero rows behind R
+    (vqf_mfb_fuse_fwd_packed_rows_pbf16_rb)."""
+    _rb_packed_ok("mfb_fuse_fwd_packed_rows", P, r_bf16, normalise)
     R = _packed_operands("mfb_fuse_fwd_packed_rows", P, q, roff, N, N, L, O, pbias, R, regions_bf16)
     dev = P.device
     Y = torch.empty((R, O), dtype=torch.float32, device=dev)
     rowssq = torch.empty(R * 4, dtype=torch.float32, device=dev)
-    fn = "vqf_mfb_fuse_fwd_packed_rows_pbf16" if P.dtype == torch.bfloat16 else "vqf_mfb_fuse_fwd_packed_rows"
-    _l.check(getattr(_lib(), fn)(_ptr(P), _ptr(pbias), _ptr(q), _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop),
-                                 N, R, L, O, _ptr(Y), _ptr(rowssq), _stream()), fn)
+    if r_bf16 is not None:
+        Rb = _rb_alloc(R, O, dev)
+        _l.check(_lib().vqf_mfb_fuse_fwd_packed_rows_pbf16_rb(_ptr(P), _ptr(pbias), _ptr(q), _ptr(roff), _keep_ptr(keep), int(seed),
+                                                              float(p_drop), N, R, L, O, _ptr(Y), _ptr(Rb), Rb.shape[1], Rb.shape[0],
+                                                              _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_packed_rows_pbf16_rb")
+        r_bf16.append(Rb)
+    else:
+        fn = "vqf_mfb_fuse_fwd_packed_rows_pbf16" if P.dtype == torch.bfloat16 else "vqf_mfb_fuse_fwd_packed_rows"
+        _l.check(getattr(_lib(), fn)(_ptr(P), _ptr(pbias), _ptr(q), _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop),
+                                     N, R, L, O, _ptr(Y), _ptr(rowssq), _stream()), fn)
     norm, inv, rowinv = l2_group_norm_packed(rowssq, roff, N, R, L)
     if normalise:
         _l.check(_lib().vqf_scale_rows(_ptr(Y), _ptr(rowinv), R, 1, O, _ptr(Y), _stream()), "vqf_scale_rows")
