@@ -260,6 +260,13 @@ def _cases():
         mfb_case("mfb/fp32/packed-coatt", form="packed", attrs={"packed_coatt": True}),
         mfb_case("mfb/fp32/packed-coatt/multilayer", model_name="mfb-multilayer", form="packed", attrs={"packed_coatt": True}),
     ]
+    # regions_bf16: a bf16 P / dP on the region forms (N = 128: enough rows for the GEMM that stores P in bf16); regions_bf16_coatt:
+    # the bf16 copy of R as well
+    for tail, attrs in (("regions-bf16", {"regions_bf16": True}), ("regions-bf16-coatt", {"regions_bf16": True, "regions_bf16_coatt": True})):
+        big = dict(N=128, hidden=256, form="packed")
+        c += [mfb_case("mfb/fp32/N128/H256/pair/" + tail, N=128, hidden=256, form="pair", attrs=attrs),
+              mfb_case("mfb/fp32/N128/H256/packed/" + tail, attrs=attrs, **big),
+              mfb_case("mfb/fp32/N128/H256/packed-coatt/" + tail, attrs=dict(attrs, packed_coatt=True), **big)]
     co = dict(cls="MHBCoAtt", model_name="mhb_coAtt", hidden=256)
     c += [
         mfb_case("mhbcoatt/fp32", **co),
@@ -368,6 +375,11 @@ def _check_branches(logs):
         assert has("mfb/fp32/index", "mfb_fuse_fwd_grouped") and has("mfb/fp32/pair", "mfb_fuse_fwd", "lens=(8,)")
         assert has("mfb/fp32/packed", "mfb_fuse_fwd_packed") and has("mfb/fp32/packed-coatt", "mfb_fuse_fwd_packed_rows")
         assert has("mfb/fp32/packed-index", "mfb_fuse_fwd_packed", "idx=(7,)")
+        for form, fn in (("pair", "mfb_fuse_fwd"), ("packed", "mfb_fuse_fwd_packed"), ("packed-coatt", "mfb_fuse_fwd_packed_rows")):
+            bf, co = ("mfb/fp32/N128/H256/%s/regions-bf16%s" % (form, t) for t in ("", "-coatt"))
+            differ(co, bf)
+            assert has(bf, fn, ", 5000):bfloat16:") and has(co, fn, ", 5000):bfloat16:") and not has("mfb/fp32/" + form, fn, ":bfloat16:")
+            assert has(co, fn, "r_bf16=[]") and not has(bf, fn, "r_bf16=[]")
     if "mfb/bf16/N8" in logs:
         b = "mfb/bf16/N8"
         for other in ("N8/masks", "N8/multilayer", "N8/nofuse-dp", "N8/side-bf16", "N8/nofold", "N8/p-fp32", "N128/H256", "N8/bf16-features"):

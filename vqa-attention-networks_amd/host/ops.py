@@ -1228,69 +1228,189 @@ def _chk_roff(name, roff, U):
         raise _l.VqfError("%s: roff must be a contiguous (%d,) int32 GPU tensor of row offsets" % (name, U + 1))
 
 
-def _rb_alloc(rows, O, dev):
-    """the bf16 copy of R of the region forms' _rb kernels: (pad_rows(rows), O rounded up to 32), written whole by the call"""
-    return torch.empty((pad_rows(rows), (O + 31) // 32 * 32), dtype=torch.bfloat16, device=dev)
+# The MFB fusion's launch entry points (include/vqa_fusion.h), every one of them, keyed by what selects it:
+#   (direction, grouped, form, storage, rb)
+#   direction  "fwd" | "bwd"
+#   grouped    N questions over U shared images (idx; the backward also order / grp_off)
+#   form       "plain": (N*L, 5*O) rows | "len": region counts (lens) | "packed": P holds the real rows (roff), Y (N*L, O) |
+#              "rows": packed, and Y / dY on the real rows too (packed_coatt)
+#   storage    "f32" | "pbf16": a bf16 P (and, in the backward, a bf16 dP) | "bf16dp": an fp32 P with a bf16 dP
+#              ("pbf16_f32dp", a bf16 P with an fp32 dP, is the storage no entry has)
+#   rb         the forward leaves the bf16 copy of R as well
+# A key that is not here is a combination the library does not have: _fuse_entry says which rule it breaks.
+_FUSE_ENTRIES = {
+    ("fwd", False, "plain", "f32", False): "vqf_mfb_fuse_fwd",
+    ("fwd", False, "plain", "pbf16", False): "vqf_mfb_fuse_fwd_pbf16",
+    ("fwd", False, "plain", "pbf16", True): "vqf_mfb_fuse_fwd_pbf16_rb",
+    ("fwd", False, "len", "f32", False): "vqf_mfb_fuse_fwd_len",
+    ("fwd", False, "len", "pbf16", False): "vqf_mfb_fuse_fwd_len_pbf16",
+    ("fwd", False, "len", "pbf16", True): "vqf_mfb_fuse_fwd_len_pbf16_rb",
+    ("fwd", False, "packed", "f32", False): "vqf_mfb_fuse_fwd_packed",
+    ("fwd", False, "packed", "pbf16", False): "vqf_mfb_fuse_fwd_packed_pbf16",
+    ("fwd", False, "packed", "pbf16", True): "vqf_mfb_fuse_fwd_packed_pbf16_rb",
+    ("fwd", False, "rows", "f32", False): "vqf_mfb_fuse_fwd_packed_rows",
+    ("fwd", False, "rows", "pbf16", False): "vqf_mfb_fuse_fwd_packed_rows_pbf16",
+    ("fwd", False, "rows", "pbf16", True): "vqf_mfb_fuse_fwd_packed_rows_pbf16_rb",
+    ("fwd", True, "plain", "f32", False): "vqf_mfb_fuse_fwd_grouped",
+    ("fwd", True, "len", "f32", False): "vqf_mfb_fuse_fwd_grouped_len",
+    ("fwd", True, "packed", "f32", False): "vqf_mfb_fuse_fwd_grouped_packed",
+    ("bwd", False, "plain", "f32", False): "vqf_mfb_fuse_bwd",
+    ("bwd", False, "plain", "pbf16", False): "vqf_mfb_fuse_bwd_pbf16",
+    ("bwd", False, "plain", "bf16dp", False): "vqf_mfb_fuse_bwd_bf16dp",
+    ("bwd", False, "len", "f32", False): "vqf_mfb_fuse_bwd_len",
+    ("bwd", False, "len", "pbf16", False): "vqf_mfb_fuse_bwd_len_pbf16",
+    ("bwd", False, "len", "bf16dp", False): "vqf_mfb_fuse_bwd_len_bf16dp",
+    ("bwd", False, "packed", "f32", False): "vqf_mfb_fuse_bwd_packed",
+    ("bwd", False, "packed", "pbf16", False): "vqf_mfb_fuse_bwd_packed_pbf16",
+    ("bwd", False, "packed", "bf16dp", False): "vqf_mfb_fuse_bwd_packed_bf16dp",
+    ("bwd", False, "rows", "f32", False): "vqf_mfb_fuse_bwd_packed_rows",
+    ("bwd", False, "rows", "pbf16", False): "vqf_mfb_fuse_bwd_packed_rows_pbf16",
+    ("bwd", False, "rows", "bf16dp", False): "vqf_mfb_fuse_bwd_packed_rows_bf16dp",
+    ("bwd", True, "plain", "f32", False): "vqf_mfb_fuse_bwd_grouped",
+    ("bwd", True, "len", "f32", False): "vqf_mfb_fuse_bwd_grouped_len",
+    ("bwd", True, "packed", "f32", False): "vqf_mfb_fuse_bwd_grouped_packed",
+}
+_FUSE_FULL = (False, "plain", "f32", False)        # the one pair of entries with cascade / zdrop / dzdrop / dcascade
 
 
-def _rb_packed_ok(name, P, r_bf16, normalise, grouped=False):
-    if r_bf16 is not None and (P.dtype != torch.bfloat16 or normalise or grouped):
-        raise _l.VqfError(name + ": r_bf16 needs a bf16 P, normalise=False and no idx")
+def _fuse_entry(key, name="mfb_fuse"):
+    """key -> the entry's name; a key outside _FUSE_ENTRIES is refused with the rule it breaks.  The rules the table states:
+    a bf16 P comes with a bf16 dP; bf16 (P, dP, the copy of R) is un-grouped only; the copy of R is the forward's, beside a bf16 P;
+    the packed rows are un-grouped."""
+    entry = _FUSE_ENTRIES.get(key)
+    if entry is not None:
+        return entry
+    direction, grouped, form, storage, rb = key
+    if storage == "pbf16_f32dp":
+        why = "a bf16 P comes with a bf16 dP"
+    elif grouped and (storage != "f32" or rb):
+        why = "a bf16 P / dP / r_bf16 is un-grouped only (the grouped fusion kernels are fp32; no idx / grp)"
+    elif rb:
+        why = "r_bf16 needs a bf16 P, normalise=False and no idx, in the forward"
+    elif grouped and form == "rows":
+        why = "Y on the packed rows is un-grouped only (no idx / grp)"
+    else:
+        why = "the library has no such entry"
+    raise _l.VqfError("%s: %r: %s" % (name, key, why))
+
+
+_FUSE_FORM_ARG = {"len": "lens", "packed": "roff", "rows": "roff (packed rows)"}
+
+
+def _fuse_key(name, direction, grouped, form, P, dp_bf16=False, regions_bf16=False, rb=False, normalise=False, extras=False):
+    """The key of a wrapper call into _FUSE_ENTRIES, refused here (before anything is allocated) where the call breaks a rule.
+    Beside those of _fuse_entry, the rules the key does not hold:
+    cascade / zdrop / dzdrop (extras) exist on the plain fp32 entry alone; on a layout form (lens / roff) bf16 needs regions_bf16
+    (the models' attribute), and r_bf16 needs normalise=False."""
+    if direction == "fwd":
+        storage = "pbf16" if P.dtype == torch.bfloat16 else "f32"
+    elif P.dtype == torch.bfloat16:
+        storage = "pbf16" if dp_bf16 else "pbf16_f32dp"
+    else:
+        storage = "bf16dp" if dp_bf16 else "f32"
+    if form != "plain":
+        arg = _FUSE_FORM_ARG[form]
+        if extras:
+            raise _l.VqfError("%s: %s comes without cascade / zdrop / dzdrop" % (name, arg))
+        if storage != "f32" and not regions_bf16:
+            raise _l.VqfError("%s: %s takes an fp32 P / dP; bf16 ones with regions_bf16" % (name, arg))
+        if rb and normalise:
+            raise _l.VqfError("%s: %s: r_bf16 needs a bf16 P, normalise=False and no idx" % (name, arg))
+    elif extras and storage != "f32":
+        raise _l.VqfError("%s: a bf16 P / dP is only available without cascade / zdrop / dzdrop" % name)
+    key = (direction, bool(grouped), form, storage, bool(rb))
+    _fuse_entry(key, name)
+    return key
+
+
+def _fuse_fwd_args(key, P, pbias, q, keep, seed, p_drop, N, L, O, Rout, rowssq, stream, cascade=None, zdrop=None, idx=None, lens=(),
+                   roff=None, U=None, R=None, R_bf16=None, ldrb=None, rb_rows=None):
+    """key + operands (pointers or None, ints, floats; lens: the form's count pointers, (lens,) or (lens_q, lens_u))
+    -> (entry name, its positional arguments in the header's order).  Pure."""
+    entry = _fuse_entry(key)
+    _, grouped, form, _, rb = key
+    full, packed = key[1:] == _FUSE_FULL, form in ("packed", "rows")
+    args = [P, pbias, q] + [cascade] * full + [idx] * grouped + list(lens) + [roff] * packed + [keep, seed, p_drop]
+    args += [N] + [U] * grouped + [R] * packed + [L, O, Rout]
+    if rb:
+        args += [R_bf16, ldrb] + [rb_rows] * (form != "plain")
+    return entry, tuple(args + [rowssq] + [zdrop] * full + [stream])
+
+
+def _fuse_bwd_args(key, dY, Y, inv, coefA, coefB, P, pbias, q, keep, seed, p_drop, N, L, O, dP, dq, dbiasP, ws, ws_bytes, stream,
+                   dzdrop=None, cascade=None, dcascade=None, idx=None, order=None, grp_off=None, lens=(), roff=None, U=None, R=None,
+                   dP_rows=None):
+    """_fuse_fwd_args for the backward entries"""
+    entry = _fuse_entry(key)
+    _, grouped, form, storage, _ = key
+    full, packed = key[1:] == _FUSE_FULL, form in ("packed", "rows")
+    args = [dY] + [dzdrop] * full + [Y, inv, coefA, coefB, P, pbias, q] + [cascade] * full + [idx, order, grp_off] * grouped
+    args += list(lens) + [roff] * packed + [keep, seed, p_drop, N] + [U] * grouped + [R] * packed + [L, O, dP]
+    args += [dP_rows] * (storage != "f32" and form != "plain") + [dq] + [dcascade] * full
+    return entry, tuple(args + [dbiasP, ws, ws_bytes, stream])
+
+
+def _fuse_fwd_run(key, P, pbias, q, keep, seed, p_drop, N, L, O, rows, r_bf16=None, rb_rows=0, cascade=None, zdrop=None, idx=None,
+                  lens=(), roff=None, U=None, R=None):
+    """The launch of every mfb_fuse_fwd* on the caller's stream, through _fuse_fwd_args (lens: a tuple of tensors)
+    -> (the (rows, O) output, its four partial sums of squares per row, one per wave).  A key with rb: r_bf16 receives the
+    (rb_rows, O rounded up to 32) bf16 copy, written whole by the call."""
+    Rout = torch.empty((rows, O), dtype=torch.float32, device=P.device)
+    rowssq = torch.empty(rows * 4, dtype=torch.float32, device=P.device)
+    Rb = torch.empty((rb_rows, (O + 31) // 32 * 32), dtype=torch.bfloat16, device=P.device) if key[4] else None
+    entry, args = _fuse_fwd_args(key, _ptr(P), _ptr(pbias), _ptr(q), _keep_ptr(keep), int(seed), float(p_drop), N, L, O, _ptr(Rout),
+                                 _ptr(rowssq), _stream(), cascade=_ptr(cascade), zdrop=_ptr(zdrop), idx=_ptr(idx),
+                                 lens=tuple(_ptr(x) for x in lens), roff=_ptr(roff), U=U, R=R, R_bf16=_ptr(Rb),
+                                 ldrb=(O + 31) // 32 * 32, rb_rows=rb_rows)
+    _l.check(getattr(_lib(), entry)(*args), entry)
+    if Rb is not None:
+        r_bf16.append(Rb)
+    return Rout, rowssq
+
+
+def _fuse_bwd_run(key, dY, Y, inv, cA, cB, P, pbias, q, keep, seed, p_drop, N, L, O, want_dbias, dp_rows, ws_bytes, dzdrop=None,
+                  cascade=None, grp=None, lens=(), roff=None, U=None, R=None):
+    """The launch of every mfb_fuse_bwd*, as _fuse_fwd_run; grp = (idx, order, grp_off) -> (dP, dq, dcascade or None, dbiasP or None).
+    dP is like P, or -- a key with a bf16 dP -- bf16 with dp_rows rows: exact zeros behind the real ones on the region forms (the K
+    padding of the weight gradient)."""
+    dev = P.device
+    idx, order, grp_off = (None, None, None) if grp is None else grp
+    dq = torch.empty((N, POOL_K * O), dtype=torch.float32, device=dev)
+    db = torch.empty(POOL_K * O, dtype=torch.float32, device=dev) if want_dbias else None
+    dc = torch.empty_like(P) if cascade is not None else None
+    dP = torch.empty_like(P) if key[3] == "f32" else torch.empty((dp_rows,) + tuple(P.shape[1:]), dtype=torch.bfloat16, device=dev)
+    ws = workspace(dev, ws_bytes)
+    entry, args = _fuse_bwd_args(key, _ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q), _keep_ptr(keep),
+                                 int(seed), float(p_drop), N, L, O, _ptr(dP), _ptr(dq), _ptr(db), _ptr(ws), ws.numel(), _stream(),
+                                 dzdrop=_ptr(dzdrop), cascade=_ptr(cascade), dcascade=_ptr(dc), idx=_ptr(idx), order=_ptr(order),
+                                 grp_off=_ptr(grp_off), lens=tuple(_ptr(x) for x in lens), roff=_ptr(roff), U=U, R=R, dP_rows=dp_rows)
+    _l.check(getattr(_lib(), entry)(*args), entry)
+    return dP, dq, dc, db
 
 
 def mfb_fuse_fwd(P, q, N, L, O, keep=None, seed=0, p_drop=0.0, cascade=None, want_zdrop=False, pbias=None,
                  normalise=True, r_bf16=None, lens=None, regions_bf16=False):
     """-> (Y normalised (N*L,O), norm (N), inv (N), zdrop or None).  pbias: projection bias added on load.
-    P may be bf16 (written by gemm_bf16(out_bf16=True)).  normalise=False: the first output is R, the signed square roots
-    WITHOUT the per-sample 1/norm (no vqf_scale_rows pass: the consumer applies inv in its GEMM epilogue).
-    r_bf16 (bf16 P, normalise=False only): a list; it receives a (N*L, O rounded up to 32) bf16 copy of R with zero pad columns,
-    written by the same launch (the operand of the consumer's bf16 GEMM).
-    lens (N) int32 (no cascade / zdrop; r_bf16 only beside a bf16 P): region counts -- sample n has lens[n] real rows (clamped to [1, L] in the kernel);
-    the padded rows of P are not read, their rows of Y are exact zeros and norm runs over the real rows.  P fp32 -- or, with
-    regions_bf16 (the models' attribute), bf16 (vqf_mfb_fuse_fwd_len_pbf16; P may have more than N*L rows: the K padding of the
-    weight gradient).  With r_bf16 too (regions_bf16_coatt; normalise=False) the copy has pad_rows(N*L) rows: zero rows behind each
-    count and behind N*L (vqf_mfb_fuse_fwd_len_pbf16_rb)."""
+    P may be bf16 (written by gemm_bf16(out_bf16=True)), and then have more than N*L rows (the K padding of the weight gradient).
+    normalise=False: the first output is R, the signed square roots WITHOUT the per-sample 1/norm (no vqf_scale_rows pass: the
+    consumer applies inv in its GEMM epilogue).
+    r_bf16: a list; it receives the bf16 copy of R with zero pad columns, written by the same launch (the operand of the consumer's
+    bf16 GEMM): (N*L, O rounded up to 32), and QUIETLY nothing unless P is bf16, normalise=False and the padded O <= 1024.
+    lens (N) int32: region counts -- sample n has lens[n] real rows (clamped to [1, L] in the kernel); the padded rows of P are not
+    read, their rows of Y are exact zeros and norm runs over the real rows.  There r_bf16 has pad_rows(N*L) rows, zero behind each
+    count and behind N*L.  What lens, bf16 and r_bf16 go with: _fuse_key."""
     (_chk_bf16 if P.dtype == torch.bfloat16 else _chk)(P)
     _chk(q, cascade, pbias)
-    dev = P.device
+    rb = r_bf16 is not None
     if lens is not None:
         _chk_lens(lens, N, "mfb_fuse_fwd")
-        if (P.dtype != torch.float32 and not regions_bf16) or cascade is not None or want_zdrop or \
-                (r_bf16 is not None and (P.dtype != torch.bfloat16 or normalise)):
-            raise _l.VqfError("mfb_fuse_fwd: lens takes an fp32 P (a bf16 one with regions_bf16) without cascade / zdrop, and r_bf16 "
-                              "only beside a bf16 P with normalise=False")
-    R = torch.empty((N * L, O), dtype=torch.float32, device=dev)
-    rowssq = torch.empty(N * L * 4, dtype=torch.float32, device=dev)       # four partial sums per row (one per wave)
-    zdrop = torch.empty_like(P) if want_zdrop else None
-    if P.dtype == torch.bfloat16:      # the projection itself stored in bf16 (bf16 mode of the image fusion)
-        if cascade is not None or want_zdrop:
-            raise _l.VqfError("mfb_fuse_fwd: a bf16 P is only available without cascade / zdrop")
-        if lens is not None and r_bf16 is not None:
-            Rb = _rb_alloc(N * L, O, dev)
-            _l.check(_lib().vqf_mfb_fuse_fwd_len_pbf16_rb(_ptr(P), _ptr(pbias), _ptr(q), _ptr(lens), _keep_ptr(keep), int(seed),
-                                                          float(p_drop), N, L, O, _ptr(R), _ptr(Rb), Rb.shape[1], Rb.shape[0],
-                                                          _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_len_pbf16_rb")
-            r_bf16.append(Rb)
-        elif lens is not None:
-            _l.check(_lib().vqf_mfb_fuse_fwd_len_pbf16(_ptr(P), _ptr(pbias), _ptr(q), _ptr(lens), _keep_ptr(keep), int(seed),
-                                                       float(p_drop), N, L, O, _ptr(R), _ptr(rowssq), _stream()),
-                     "vqf_mfb_fuse_fwd_len_pbf16")
-        elif r_bf16 is not None and not normalise and (O + 31) // 32 * 32 <= 1024:
-            Rb = torch.empty((N * L, (O + 31) // 32 * 32), dtype=torch.bfloat16, device=dev)
-            _l.check(_lib().vqf_mfb_fuse_fwd_pbf16_rb(_ptr(P), _ptr(pbias), _ptr(q), _keep_ptr(keep), int(seed), float(p_drop),
-                                                      N, L, O, _ptr(R), ctypes.c_void_p(Rb.data_ptr()), Rb.shape[1], _ptr(rowssq),
-                                                      _stream()), "vqf_mfb_fuse_fwd_pbf16_rb")
-            r_bf16.append(Rb)
-        else:
-            _l.check(_lib().vqf_mfb_fuse_fwd_pbf16(_ptr(P), _ptr(pbias), _ptr(q), _keep_ptr(keep), int(seed), float(p_drop),
-                                                   N, L, O, _ptr(R), _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_pbf16")
-    elif lens is not None:
-        _l.check(_lib().vqf_mfb_fuse_fwd_len(_ptr(P), _ptr(pbias), _ptr(q), _ptr(lens), _keep_ptr(keep), int(seed), float(p_drop),
-                                             N, L, O, _ptr(R), _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_len")
     else:
-        _l.check(_lib().vqf_mfb_fuse_fwd(_ptr(P), _ptr(pbias), _ptr(q), _ptr(cascade), _keep_ptr(keep), int(seed),
-                                         float(p_drop), N, L, O, _ptr(R), _ptr(rowssq), _ptr(zdrop), _stream()),
-                 "vqf_mfb_fuse_fwd")
+        rb = rb and P.dtype == torch.bfloat16 and not normalise and (O + 31) // 32 * 32 <= 1024
+    key = _fuse_key("mfb_fuse_fwd", "fwd", False, "plain" if lens is None else "len", P, regions_bf16=regions_bf16, rb=rb,
+                    normalise=normalise, extras=cascade is not None or want_zdrop)
+    zdrop = torch.empty_like(P) if want_zdrop else None
+    R, rowssq = _fuse_fwd_run(key, P, pbias, q, keep, seed, p_drop, N, L, O, N * L, r_bf16, N * L if lens is None else pad_rows(N * L),
+                              cascade=cascade, zdrop=zdrop, lens=() if lens is None else (lens,))
     return (R,) + _l2_norm_tail(R, rowssq, N, L, O, normalise) + (zdrop,)
 
 
@@ -1300,58 +1420,20 @@ def mfb_fuse_bwd(dY, Y, norm, inv, P, q, N, L, O, keep=None, seed=0, p_drop=0.0,
     lin = (dlogits, lin) of the consumer's attention head: the UN-NORMALISED formulation -- Y is R (mfb_fuse_fwd(normalise=
     False)), dY is dYs = dY / norm, and sum(R * dYs) per sample comes from the head's (N*L, G) tensors instead of a
     rowdot pass over the (N*L, O) ones (vqf_l2_norm_bwd_coef_lin).
-    lens (N) int32 (no cascade / dzdrop), with Y from mfb_fuse_fwd(lens=lens): dY / Y / P are not read on padded rows, whose
-    dP rows are exact zeros; dq and dbiasP sum the real rows.  With regions_bf16 (the models' attribute) and dp_bf16, P fp32 or
-    bf16: dP is bf16 with dp_rows >= N*L rows (default: those of P), exact zeros from row N*L on -- the K padding of the weight
-    gradient (vqf_mfb_fuse_bwd_len_pbf16 / _bf16dp)."""
+    dp_bf16: dP is bf16, shaped like P.
+    lens (N) int32, with Y from mfb_fuse_fwd(lens=lens): dY / Y / P are not read on padded rows, whose dP rows are exact zeros; dq
+    and dbiasP sum the real rows.  There a bf16 dP has dp_rows >= N*L rows (default: those of P, N*L at the least), exact zeros
+    from row N*L on.  What lens and bf16 go with: _fuse_key."""
     (_chk_bf16 if P.dtype == torch.bfloat16 else _chk)(P)
     _chk(dY, Y, norm, inv, q, cascade, dzdrop, pbias)
     if lens is not None:
         _chk_lens(lens, N, "mfb_fuse_bwd")
-        if ((P.dtype != torch.float32 or dp_bf16) and not regions_bf16) or cascade is not None or dzdrop is not None:
-            raise _l.VqfError("mfb_fuse_bwd: lens takes an fp32 P / dP (bf16 ones with regions_bf16) without cascade / dzdrop")
-    if P.dtype == torch.bfloat16 and not dp_bf16:
-        raise _l.VqfError("mfb_fuse_bwd: a bf16 P comes with a bf16 dP")
-    dev = P.device
+    key = _fuse_key("mfb_fuse_bwd", "bwd", False, "plain" if lens is None else "len", P, dp_bf16=dp_bf16, regions_bf16=regions_bf16,
+                    extras=cascade is not None or dzdrop is not None)
     cA, cB, inv = _l2_norm_bwd_coefs(dY, Y, norm, inv, N, L, O, lin)
-    dq = torch.empty((N, POOL_K * O), dtype=torch.float32, device=dev)
-    db = torch.empty(POOL_K * O, dtype=torch.float32, device=dev) if want_dbias else None
-    ws = workspace(dev, _lib().vqf_mfb_fuse_bwd_ws_bytes(N, L, O))
-    if dp_bf16:                       # bf16 mode of the image fusion: dP goes straight to the wgrad GEMM
-        if cascade is not None or dzdrop is not None:
-            raise _l.VqfError("mfb_fuse_bwd: bf16 dP is only available without cascade / dzdrop")
-        if lens is not None:
-            rows = max(P.shape[0], N * L) if dp_rows is None else int(dp_rows)
-            dP = torch.empty((rows, P.shape[1]), dtype=torch.bfloat16, device=dev)
-            fn = "vqf_mfb_fuse_bwd_len_pbf16" if P.dtype == torch.bfloat16 else "vqf_mfb_fuse_bwd_len_bf16dp"
-            _l.check(getattr(_lib(), fn)(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q), _ptr(lens),
-                                         _keep_ptr(keep), int(seed), float(p_drop), N, L, O, _ptr(dP), rows, _ptr(dq), _ptr(db),
-                                         _ptr(ws), ws.numel(), _stream()), fn)
-            return dP, dq, None, db
-        dP = torch.empty(P.shape, dtype=torch.bfloat16, device=dev)
-        if P.dtype == torch.bfloat16:
-            _l.check(_lib().vqf_mfb_fuse_bwd_pbf16(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias),
-                                                   _ptr(q), _keep_ptr(keep), int(seed), float(p_drop), N, L, O, _ptr(dP),
-                                                   _ptr(dq), _ptr(db), _ptr(ws), ws.numel(), _stream()),
-                     "vqf_mfb_fuse_bwd_pbf16")
-            return dP, dq, None, db
-        _l.check(_lib().vqf_mfb_fuse_bwd_bf16dp(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias),
-                                                _ptr(q), _keep_ptr(keep), int(seed), float(p_drop), N, L, O, _ptr(dP),
-                                                _ptr(dq), _ptr(db), _ptr(ws), ws.numel(), _stream()),
-                 "vqf_mfb_fuse_bwd_bf16dp")
-        return dP, dq, None, db
-    dP = torch.empty_like(P)
-    if lens is not None:
-        _l.check(_lib().vqf_mfb_fuse_bwd_len(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
-                                             _ptr(lens), _keep_ptr(keep), int(seed), float(p_drop), N, L, O, _ptr(dP), _ptr(dq),
-                                             _ptr(db), _ptr(ws), ws.numel(), _stream()), "vqf_mfb_fuse_bwd_len")
-        return dP, dq, None, db
-    dc = torch.empty_like(P) if cascade is not None else None
-    _l.check(_lib().vqf_mfb_fuse_bwd(_ptr(dY), _ptr(dzdrop), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
-                                     _ptr(cascade), _keep_ptr(keep), int(seed), float(p_drop), N, L, O,
-                                     _ptr(dP), _ptr(dq), _ptr(dc), _ptr(db), _ptr(ws), ws.numel(), _stream()),
-             "vqf_mfb_fuse_bwd")
-    return dP, dq, dc, db
+    rows = P.shape[0] if lens is None else max(P.shape[0], N * L) if dp_rows is None else int(dp_rows)
+    return _fuse_bwd_run(key, dY, Y, inv, cA, cB, P, pbias, q, keep, seed, p_drop, N, L, O, want_dbias, rows,
+                         _lib().vqf_mfb_fuse_bwd_ws_bytes(N, L, O), dzdrop=dzdrop, cascade=cascade, lens=() if lens is None else (lens,))
 
 
 def mfb_fuse_grouped_supported(N, U, L, O):
@@ -1370,15 +1452,14 @@ def _fuse_grouped_operands(name, P, q, N, U, L, O, pbias):
 
 
 def _chk_lens_grouped(name, lens, N, U):
-    """lens of the grouped region-count forms: None, or (lens_q (N,), lens_u (U,)), contiguous int32 GPU tensors"""
+    """lens of the grouped region-count forms: None -> (), or (lens_q (N,), lens_u (U,)), contiguous int32 GPU tensors"""
     if lens is None:
-        return None, None
+        return ()
     if not isinstance(lens, (tuple, list)) or len(lens) != 2:
         raise _l.VqfError(name + ": lens must be the pair (lens_q (N,), lens_u (U,))")
-    lens_q, lens_u = lens
-    _chk_lens(lens_q, N, name)
-    _chk_lens(lens_u, U, name)
-    return lens_q, lens_u
+    _chk_lens(lens[0], N, name)
+    _chk_lens(lens[1], U, name)
+    return tuple(lens)
 
 
 def mfb_fuse_fwd_grouped(P, q, idx, N, U, L, O, keep=None, seed=0, p_drop=0.0, pbias=None, normalise=True, lens=None):
@@ -1388,17 +1469,9 @@ def mfb_fuse_fwd_grouped(P, q, idx, N, U, L, O, keep=None, seed=0, p_drop=0.0, p
     lens = (lens_q (N,), lens_u (U,)) int32: region counts per image and, gathered, per question (mfb_fuse_fwd's lens)."""
     _fuse_grouped_operands("mfb_fuse_fwd_grouped", P, q, N, U, L, O, pbias)
     _chk_group("mfb_fuse_fwd_grouped", N, U, idx=idx)
-    lens_q, lens_u = _chk_lens_grouped("mfb_fuse_fwd_grouped", lens, N, U)
-    dev = P.device
-    R = torch.empty((N * L, O), dtype=torch.float32, device=dev)
-    rowssq = torch.empty(N * L * 4, dtype=torch.float32, device=dev)
-    if lens_q is not None:
-        _l.check(_lib().vqf_mfb_fuse_fwd_grouped_len(_ptr(P), _ptr(pbias), _ptr(q), _ptr(idx), _ptr(lens_q), _ptr(lens_u),
-                                                     _keep_ptr(keep), int(seed), float(p_drop), N, U, L, O, _ptr(R), _ptr(rowssq),
-                                                     _stream()), "vqf_mfb_fuse_fwd_grouped_len")
-    else:
-        _l.check(_lib().vqf_mfb_fuse_fwd_grouped(_ptr(P), _ptr(pbias), _ptr(q), _ptr(idx), _keep_ptr(keep), int(seed), float(p_drop),
-                                                 N, U, L, O, _ptr(R), _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_grouped")
+    lens = _chk_lens_grouped("mfb_fuse_fwd_grouped", lens, N, U)
+    key = _fuse_key("mfb_fuse_fwd_grouped", "fwd", True, "len" if lens else "plain", P)
+    R, rowssq = _fuse_fwd_run(key, P, pbias, q, keep, seed, p_drop, N, L, O, N * L, idx=idx, U=U, lens=lens)
     return (R,) + _l2_norm_tail(R, rowssq, N, L, O, normalise)
 
 
@@ -1409,26 +1482,14 @@ def mfb_fuse_bwd_grouped(dY, Y, norm, inv, P, q, idx, order, grp_off, N, U, L, O
     lens = (lens_q, lens_u) as in mfb_fuse_fwd_grouped: the dP rows beyond an image's count are exact zeros."""
     _fuse_grouped_operands("mfb_fuse_bwd_grouped", P, q, N, U, L, O, pbias)
     _chk_group("mfb_fuse_bwd_grouped", N, U, idx=idx, order=order, grp_off=grp_off)
-    lens_q, lens_u = _chk_lens_grouped("mfb_fuse_bwd_grouped", lens, N, U)
+    lens = _chk_lens_grouped("mfb_fuse_bwd_grouped", lens, N, U)
     _chk(dY, Y, norm, inv)
     if tuple(dY.shape) != (N * L, O) or tuple(Y.shape) != (N * L, O):
         raise _l.VqfError("mfb_fuse_bwd_grouped: dY and Y must be (N*L, O)")
-    dev = P.device
+    key = _fuse_key("mfb_fuse_bwd_grouped", "bwd", True, "len" if lens else "plain", P)
     cA, cB, inv = _l2_norm_bwd_coefs(dY, Y, norm, inv, N, L, O, lin)
-    dP = torch.empty_like(P)
-    dq = torch.empty((N, POOL_K * O), dtype=torch.float32, device=dev)
-    db = torch.empty(POOL_K * O, dtype=torch.float32, device=dev) if want_dbias else None
-    ws = workspace(dev, _lib().vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O))
-    if lens_q is not None:
-        _l.check(_lib().vqf_mfb_fuse_bwd_grouped_len(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
-                                                     _ptr(idx), _ptr(order), _ptr(grp_off), _ptr(lens_q), _ptr(lens_u),
-                                                     _keep_ptr(keep), int(seed), float(p_drop), N, U, L, O, _ptr(dP), _ptr(dq),
-                                                     _ptr(db), _ptr(ws), ws.numel(), _stream()), "vqf_mfb_fuse_bwd_grouped_len")
-        return dP, dq, db
-    _l.check(_lib().vqf_mfb_fuse_bwd_grouped(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
-                                             _ptr(idx), _ptr(order), _ptr(grp_off), _keep_ptr(keep), int(seed), float(p_drop),
-                                             N, U, L, O, _ptr(dP), _ptr(dq), _ptr(db), _ptr(ws), ws.numel(), _stream()),
-             "vqf_mfb_fuse_bwd_grouped")
+    dP, dq, _, db = _fuse_bwd_run(key, dY, Y, inv, cA, cB, P, pbias, q, keep, seed, p_drop, N, L, O, want_dbias, None,
+                                  _lib().vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O), grp=(idx, order, grp_off), U=U, lens=lens)
     return dP, dq, db
 
 
@@ -1461,54 +1522,20 @@ def _packed_operands(name, P, q, roff, N, U, L, O, pbias, R=None, regions_bf16=F
     return R
 
 
-def _fuse_bwd_packed_bf16(entry, dY, Y, inv, cA, cB, P, pbias, q, roff, keep, seed, p_drop, N, R, L, O, dp_rows, dq, db):
-    """The bf16-dP call of mfb_fuse_bwd_packed / _packed_rows (entry + "_pbf16" beside a bf16 P, "_bf16dp" beside an fp32 one)
-    -> (dP bf16 (dp_rows, 5*O) with exact zero rows behind the R real ones, dq, db)"""
-    rows = P.shape[0] if dp_rows is None else int(dp_rows)
-    dP = torch.empty((rows, P.shape[1]), dtype=torch.bfloat16, device=P.device)
-    ws = workspace(P.device, _lib().vqf_mfb_fuse_bwd_ws_bytes(N, L, O))
-    fn = entry + ("_pbf16" if P.dtype == torch.bfloat16 else "_bf16dp")
-    _l.check(getattr(_lib(), fn)(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q), _ptr(roff),
-                                 _keep_ptr(keep), int(seed), float(p_drop), N, R, L, O, _ptr(dP), rows, _ptr(dq), _ptr(db), _ptr(ws),
-                                 ws.numel(), _stream()), fn)
-    return dP, dq, db
-
-
-def _no_bf16_grouped(name, P, grouped):
-    if grouped and P.dtype == torch.bfloat16:
-        raise _l.VqfError(name + ": a bf16 P / dP is un-grouped only (the grouped fusion kernels are fp32)")
-
-
 def mfb_fuse_fwd_packed(P, q, roff, N, L, O, idx=None, keep=None, seed=0, p_drop=0.0, pbias=None, normalise=True, R=None,
                         regions_bf16=False, r_bf16=None):
     """The image fusion on packed rows: P (R, 5*O) fp32, q (N, 5*O), roff (N + 1) int32 -- with idx (N) int32: (U + 1), question n
     reads the rows of image idx[n]; keep (N*L, 5*O) / the Philox draw stay in the padded coordinates
     -> (Y (N*L, O), norm (N), inv (N)): the bits of mfb_fuse_fwd(lens=) / mfb_fuse_fwd_grouped(lens=) on the zero-padded copy of P.
-    regions_bf16 (the models' attribute; without idx): P may be bf16 (vqf_mfb_fuse_fwd_packed_pbf16) and hold more than the R real
-    rows given.  r_bf16 (a list; bf16 P, normalise=False, no idx): it receives the (pad_rows(N*L), O rounded up to 32) bf16 copy of
-    Y the same launch wrote, zero rows behind each count and behind N*L (vqf_mfb_fuse_fwd_packed_pbf16_rb)."""
+    A bf16 P may hold more than the R real rows given.  r_bf16 (a list) receives the (pad_rows(N*L), O rounded up to 32) bf16 copy
+    of Y the same launch wrote, zero rows behind each count and behind N*L.  What bf16 and r_bf16 go with: _fuse_key."""
     U = N if idx is None else roff.shape[0] - 1
-    _no_bf16_grouped("mfb_fuse_fwd_packed", P, idx is not None)
-    _rb_packed_ok("mfb_fuse_fwd_packed", P, r_bf16, normalise, idx is not None)
+    key = _fuse_key("mfb_fuse_fwd_packed", "fwd", idx is not None, "packed", P, regions_bf16=regions_bf16, rb=r_bf16 is not None,
+                    normalise=normalise)
     R = _packed_operands("mfb_fuse_fwd_packed", P, q, roff, N, U, L, O, pbias, R, regions_bf16)
-    dev = P.device
-    Y = torch.empty((N * L, O), dtype=torch.float32, device=dev)
-    rowssq = torch.empty(N * L * 4, dtype=torch.float32, device=dev)
-    if r_bf16 is not None:
-        Rb = _rb_alloc(N * L, O, dev)
-        _l.check(_lib().vqf_mfb_fuse_fwd_packed_pbf16_rb(_ptr(P), _ptr(pbias), _ptr(q), _ptr(roff), _keep_ptr(keep), int(seed),
-                                                         float(p_drop), N, R, L, O, _ptr(Y), _ptr(Rb), Rb.shape[1], Rb.shape[0],
-                                                         _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_packed_pbf16_rb")
-        r_bf16.append(Rb)
-    elif idx is None:
-        fn = "vqf_mfb_fuse_fwd_packed_pbf16" if P.dtype == torch.bfloat16 else "vqf_mfb_fuse_fwd_packed"
-        _l.check(getattr(_lib(), fn)(_ptr(P), _ptr(pbias), _ptr(q), _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop),
-                                     N, R, L, O, _ptr(Y), _ptr(rowssq), _stream()), fn)
-    else:
+    if idx is not None:
         _chk_group("mfb_fuse_fwd_packed", N, U, idx=idx)
-        _l.check(_lib().vqf_mfb_fuse_fwd_grouped_packed(_ptr(P), _ptr(pbias), _ptr(q), _ptr(idx), _ptr(roff), _keep_ptr(keep), int(seed),
-                                                        float(p_drop), N, U, R, L, O, _ptr(Y), _ptr(rowssq), _stream()),
-                 "vqf_mfb_fuse_fwd_grouped_packed")
+    Y, rowssq = _fuse_fwd_run(key, P, pbias, q, keep, seed, p_drop, N, L, O, N * L, r_bf16, pad_rows(N * L), idx=idx, roff=roff, U=U, R=R)
     return (Y,) + _l2_norm_tail(Y, rowssq, N, L, O, normalise)
 
 
@@ -1516,37 +1543,20 @@ def mfb_fuse_bwd_packed(dY, Y, norm, inv, P, q, roff, N, L, O, grp=None, keep=No
                         lin=None, dp_bf16=False, R=None, dp_rows=None, regions_bf16=False):
     """-> (dP (R, 5*O), dq (N, 5*O), dbiasP or None).  grp = (idx, order, grp_off): roff is per image and dP sums each image's
     questions in `order` (zero rows for an image without a question).  lin as in mfb_fuse_bwd.
-    regions_bf16 (the models' attribute) with dp_bf16 (without grp; P fp32 or bf16, of which R rows are real): dP is bf16 with dp_rows >= R rows (default: those of P), exact
-    zeros from row R on -- the K padding of the weight gradient (vqf_mfb_fuse_bwd_packed_pbf16 / _bf16dp)."""
+    dp_bf16 (P fp32 or bf16, of which R rows are real): dP is bf16 with dp_rows >= R rows (default: those of P), exact zeros from
+    row R on -- the K padding of the weight gradient.  What bf16 goes with: _fuse_key."""
     U = N if grp is None else roff.shape[0] - 1
-    _no_bf16_grouped("mfb_fuse_bwd_packed", P, grp is not None)
+    key = _fuse_key("mfb_fuse_bwd_packed", "bwd", grp is not None, "packed", P, dp_bf16=dp_bf16, regions_bf16=regions_bf16)
     R = _packed_operands("mfb_fuse_bwd_packed", P, q, roff, N, U, L, O, pbias, R, regions_bf16)
     _chk(dY, Y, norm, inv)
     if tuple(dY.shape) != (N * L, O) or tuple(Y.shape) != (N * L, O):
         raise _l.VqfError("mfb_fuse_bwd_packed: dY and Y must be (N*L, O)")
-    if (dp_bf16 and (grp is not None or not regions_bf16)) or (P.dtype == torch.bfloat16 and not dp_bf16):
-        raise _l.VqfError("mfb_fuse_bwd_packed: a bf16 dP needs regions_bf16 and no grp, and a bf16 P comes with a bf16 dP")
-    dev = P.device
+    if grp is not None:
+        _chk_group("mfb_fuse_bwd_packed", N, U, idx=grp[0], order=grp[1], grp_off=grp[2])
     cA, cB, inv = _l2_norm_bwd_coefs(dY, Y, norm, inv, N, L, O, lin)
-    dq = torch.empty((N, POOL_K * O), dtype=torch.float32, device=dev)
-    db = torch.empty(POOL_K * O, dtype=torch.float32, device=dev) if want_dbias else None
-    if dp_bf16:
-        return _fuse_bwd_packed_bf16("vqf_mfb_fuse_bwd_packed", dY, Y, inv, cA, cB, P, pbias, q, roff, keep, seed, p_drop, N, R, L, O,
-                                     dp_rows, dq, db)
-    dP = torch.empty_like(P)
-    if grp is None:
-        ws = workspace(dev, _lib().vqf_mfb_fuse_bwd_ws_bytes(N, L, O))
-        _l.check(_lib().vqf_mfb_fuse_bwd_packed(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
-                                                _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop), N, R, L, O, _ptr(dP), _ptr(dq),
-                                                _ptr(db), _ptr(ws), ws.numel(), _stream()), "vqf_mfb_fuse_bwd_packed")
-        return dP, dq, db
-    idx, order, grp_off = grp
-    _chk_group("mfb_fuse_bwd_packed", N, U, idx=idx, order=order, grp_off=grp_off)
-    ws = workspace(dev, _lib().vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O))
-    _l.check(_lib().vqf_mfb_fuse_bwd_grouped_packed(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
-                                                    _ptr(idx), _ptr(order), _ptr(grp_off), _ptr(roff), _keep_ptr(keep), int(seed),
-                                                    float(p_drop), N, U, R, L, O, _ptr(dP), _ptr(dq), _ptr(db), _ptr(ws), ws.numel(),
-                                                    _stream()), "vqf_mfb_fuse_bwd_grouped_packed")
+    ws_bytes = _lib().vqf_mfb_fuse_bwd_ws_bytes(N, L, O) if grp is None else _lib().vqf_mfb_fuse_bwd_grouped_ws_bytes(N, U, L, O)
+    dP, dq, _, db = _fuse_bwd_run(key, dY, Y, inv, cA, cB, P, pbias, q, keep, seed, p_drop, N, L, O, want_dbias,
+                                  P.shape[0] if dp_rows is None else int(dp_rows), ws_bytes, grp=grp, roff=roff, U=U, R=R)
     return dP, dq, db
 
 
@@ -1665,24 +1675,11 @@ def mfb_fuse_fwd_packed_rows(P, q, roff, N, L, O, keep=None, seed=0, p_drop=0.0,
     """mfb_fuse_fwd_packed with the output on the packed rows: P (R, 5*O), q (N, 5*O), roff (N + 1) int32; keep (N*L, 5*O) / the Philox
     draw stay in the padded coordinates -> (Y (R, O), norm (N), inv (N), rowinv (R)): the real rows of mfb_fuse_fwd_packed's Y, bit
     for bit; nothing of N*L rows is allocated.  rowinv[r] = inv of row r's sample (the consumers' per-row scale).
-    regions_bf16: P may be bf16 (vqf_mfb_fuse_fwd_packed_rows_pbf16) and hold more than the R real rows given.  r_bf16 (a list; bf16
-    P, normalise=False): it receives the (pad_rows(R), O rounded up to 32) bf16 copy of Y the same launch wrote, zero rows behind R
-    (vqf_mfb_fuse_fwd_packed_rows_pbf16_rb)."""
-    _rb_packed_ok("mfb_fuse_fwd_packed_rows", P, r_bf16, normalise)
+    r_bf16 as there, with pad_rows(R) rows: zero rows behind R."""
+    key = _fuse_key("mfb_fuse_fwd_packed_rows", "fwd", False, "rows", P, regions_bf16=regions_bf16, rb=r_bf16 is not None,
+                    normalise=normalise)
     R = _packed_operands("mfb_fuse_fwd_packed_rows", P, q, roff, N, N, L, O, pbias, R, regions_bf16)
-    dev = P.device
-    Y = torch.empty((R, O), dtype=torch.float32, device=dev)
-    rowssq = torch.empty(R * 4, dtype=torch.float32, device=dev)
-    if r_bf16 is not None:
-        Rb = _rb_alloc(R, O, dev)
-        _l.check(_lib().vqf_mfb_fuse_fwd_packed_rows_pbf16_rb(_ptr(P), _ptr(pbias), _ptr(q), _ptr(roff), _keep_ptr(keep), int(seed),
-                                                              float(p_drop), N, R, L, O, _ptr(Y), _ptr(Rb), Rb.shape[1], Rb.shape[0],
-                                                              _ptr(rowssq), _stream()), "vqf_mfb_fuse_fwd_packed_rows_pbf16_rb")
-        r_bf16.append(Rb)
-    else:
-        fn = "vqf_mfb_fuse_fwd_packed_rows_pbf16" if P.dtype == torch.bfloat16 else "vqf_mfb_fuse_fwd_packed_rows"
-        _l.check(getattr(_lib(), fn)(_ptr(P), _ptr(pbias), _ptr(q), _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop),
-                                     N, R, L, O, _ptr(Y), _ptr(rowssq), _stream()), fn)
+    Y, rowssq = _fuse_fwd_run(key, P, pbias, q, keep, seed, p_drop, N, L, O, R, r_bf16, pad_rows(R), roff=roff, R=R)
     norm, inv, rowinv = l2_group_norm_packed(rowssq, roff, N, R, L)
     if normalise:
         _l.check(_lib().vqf_scale_rows(_ptr(Y), _ptr(rowinv), R, 1, O, _ptr(Y), _stream()), "vqf_scale_rows")
@@ -1692,30 +1689,21 @@ def mfb_fuse_fwd_packed_rows(P, q, roff, N, L, O, keep=None, seed=0, p_drop=0.0,
 def mfb_fuse_bwd_packed_rows(dY, Y, norm, inv, P, q, roff, N, L, O, keep=None, seed=0, p_drop=0.0, want_dbias=False, pbias=None,
                              lin=None, dp_bf16=False, R=None, dp_rows=None, regions_bf16=False):
     """mfb_fuse_bwd_packed with dY / Y (R, O) on the packed rows (and lin = (dlogits, lin) (R, G)) -> (dP (R, 5*O), dq (N, 5*O),
-    dbiasP or None); regions_bf16 / dp_bf16 / R / dp_rows as there (vqf_mfb_fuse_bwd_packed_rows_pbf16 / _bf16dp)."""
+    dbiasP or None); dp_bf16 / R / dp_rows as there."""
+    key = _fuse_key("mfb_fuse_bwd_packed_rows", "bwd", False, "rows", P, dp_bf16=dp_bf16, regions_bf16=regions_bf16)
     R = _packed_operands("mfb_fuse_bwd_packed_rows", P, q, roff, N, N, L, O, pbias, R, regions_bf16)
-    if (dp_bf16 and not regions_bf16) or (P.dtype == torch.bfloat16 and not dp_bf16):
-        raise _l.VqfError("mfb_fuse_bwd_packed_rows: a bf16 dP needs regions_bf16, and a bf16 P comes with a bf16 dP")
     _chk(dY, Y, norm, inv)
     if tuple(dY.shape) != (R, O) or tuple(Y.shape) != (R, O):
         raise _l.VqfError("mfb_fuse_bwd_packed_rows: dY and Y must be (R, O) = (%d, %d)" % (R, O))
-    dev = P.device
     if lin is not None:
         cA, cB, inv = l2_norm_bwd_coef_lin_packed(lin[0], lin[1], roff, norm, inv, N, L)
     else:
-        rowdot = torch.empty(R, dtype=torch.float32, device=dev)
+        rowdot = torch.empty(R, dtype=torch.float32, device=P.device)
         _l.check(_lib().vqf_rowdot(_ptr(Y), _ptr(dY), R, O, _ptr(rowdot), _stream()), "vqf_rowdot")
         cA, cB = l2_norm_bwd_coef_packed(rowdot, roff, norm, inv, N, L)
-    dq = torch.empty((N, POOL_K * O), dtype=torch.float32, device=dev)
-    db = torch.empty(POOL_K * O, dtype=torch.float32, device=dev) if want_dbias else None
-    if dp_bf16:
-        return _fuse_bwd_packed_bf16("vqf_mfb_fuse_bwd_packed_rows", dY, Y, inv, cA, cB, P, pbias, q, roff, keep, seed, p_drop, N, R, L,
-                                     O, dp_rows, dq, db)
-    dP = torch.empty_like(P)
-    ws = workspace(dev, _lib().vqf_mfb_fuse_bwd_ws_bytes(N, L, O))
-    _l.check(_lib().vqf_mfb_fuse_bwd_packed_rows(_ptr(dY), _ptr(Y), _ptr(inv), _ptr(cA), _ptr(cB), _ptr(P), _ptr(pbias), _ptr(q),
-                                                 _ptr(roff), _keep_ptr(keep), int(seed), float(p_drop), N, R, L, O, _ptr(dP), _ptr(dq),
-                                                 _ptr(db), _ptr(ws), ws.numel(), _stream()), "vqf_mfb_fuse_bwd_packed_rows")
+    dP, dq, _, db = _fuse_bwd_run(key, dY, Y, inv, cA, cB, P, pbias, q, keep, seed, p_drop, N, L, O, want_dbias,
+                                  P.shape[0] if dp_rows is None else int(dp_rows), _lib().vqf_mfb_fuse_bwd_ws_bytes(N, L, O), roff=roff,
+                                  R=R)
     return dP, dq, db
 
 
